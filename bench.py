@@ -19,6 +19,11 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   r200k, smoothl1_ce   the same step on a 200 000-point sweep / with BASELINE config 4's loss pair
   cpu_baseline  the dense torch-CPU oracle (port of the reference's dense Keras graph) timed on this
                 host, on a stated shrunken grid, extrapolated by dense row count.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0): loss.npy (total, class, regression), theta.npy
+(the trained variables after the update), velocity.npy (SGD-Nesterov momentum), state.npy (BatchNormalization moving
+statistics), all float32, ~50 MB.  Inputs and initial variables are seeded, so two builds run with the same arguments
+can be compared array for array.
 """
 import argparse
 import json
@@ -76,6 +81,20 @@ def synthetic_targets(seed, Ho, Wo):
     pos = np.unique(idx // 2)
     reg[pos] = rng.normal(0, 1, (len(pos), 14))
     return cls.reshape(Ho, Wo, 2), reg.reshape(Ho, Wo, 14)
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: numpy array} as out_dir/<name>.npy (float32 / float64 only, DUMP_MAX_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def event_time_ms(fn, iters):
@@ -290,7 +309,12 @@ def main():
                          "sigmoid cross-entropy + SmoothL1 pair BASELINE.json's config 3 names (same kernels otherwise)")
     ap.add_argument("--cloud", choices=["u20k", "r200k"], default="u20k",
                     help="u20k: the headline workload (BASELINE configs 2-4); r200k: a Lyft-size sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss and the variables after the last timed step to DIR/<name>.npy (rank 0); "
+                         "inside the tree use bench_outputs/..., which git ignores")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process becomes the launcher (it never touches the GPU)
@@ -372,6 +396,10 @@ def main():
     if dp is not None:
         dt = dp.max_float(dt)
     loss_val = float(loss[0].item())
+    if args.dump_outputs and rank == 0:
+        # taken now: the roofline and side legs below run more steps on the same variables
+        dump_outputs(args.dump_outputs, {"loss": loss.cpu().numpy(), "theta": net.params.theta.cpu().numpy(),
+                                         "velocity": net.velocity.cpu().numpy(), "state": net.params.state.cpu().numpy()})
 
     result = None
     if rank == 0:

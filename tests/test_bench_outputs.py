@@ -1,0 +1,59 @@
+"""bench.py --dump-outputs / --steps: what the timed path computed in its last step, written for comparison between builds."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BENCH = os.path.join(ROOT, "bench.py")
+
+
+def _bench(*argv, env=None):
+    e = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    e.update(env or {})
+    return subprocess.run([sys.executable, BENCH, *argv], env=e, capture_output=True, text=True, timeout=900)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    import bench
+    arrays = {"loss": np.arange(3, dtype=np.float32), "theta": np.linspace(0, 1, 7)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    assert sorted(os.listdir(tmp_path / "d")) == ["loss.npy", "theta.npy"]
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.parametrize("argv", [("--steps", "0"), ("--warmup", "-1")])
+def test_bench_refuses_a_timed_region_without_steps(argv):
+    r = _bench(*argv, env=dict(LISEC_BENCH_DRYRUN="1"))
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step_reproducibly(tmp_path):
+    """--steps K times K steps, ms_per_step is their mean, and the dump holds the loss the result line reports and the
+    variables after that step: bit-identical from run to run with the same arguments (seeded inputs and variables)."""
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-3000:]
+        j = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][0]
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        assert abs(j["value"] - 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+        assert sorted(os.listdir(out)) == ["loss.npy", "state.npy", "theta.npy", "velocity.npy"]
+        d = {n: np.load(out / f"{n}.npy") for n in ("loss", "state", "theta", "velocity")}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+        assert sum(a.nbytes for a in d.values()) <= 64 * 1000 * 1000
+        assert d["loss"].shape == (3,) and float(d["loss"][0]) == j["config"]["final_loss"]
+        assert d["theta"].shape == d["velocity"].shape and np.abs(d["velocity"]).max() > 0
+        dumps.append(d)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
