@@ -613,6 +613,22 @@ int lisec_sgd_nesterov_step_dev(float* theta, const float* grad, float* velocity
 int lisec_sgd_nesterov_step_dev_part(float* theta, const float* grad, float* velocity, long long n, double lr, double decay,
                                      float momentum, const long long* state, lisec_stream_t stream);
 
+/* tf.keras 2.4 optimizers beyond the reference's one (csrc/optim.hip), with the device iteration count of
+ * lisec_sgd_nesterov_step_dev: state = long long[2] {iterations, 0}, lr_t = (float)(lr / (1 + decay*iterations)) in
+ * double.  advance = 1: state[0] is incremented once every workgroup has read it (the call that ends the step);
+ * advance = 0: a PART of the variables ahead of the rest of the step, state[0] is read and left alone.  n % 4 == 0.
+ *   SGD, momentum == 0 (velocity NULL):  w <- w - lr_t*g
+ *   SGD, momentum > 0:                    v <- m*v - lr_t*g, then w <- w + v (nesterov = 0) or w <- w + m*v - lr_t*g (1) */
+int lisec_sgd_step_dev(float* theta, const float* grad, float* velocity /* NULL iff momentum == 0 */, long long n,
+                       double lr, double decay, float momentum, int nesterov, long long* state, int advance,
+                       lisec_stream_t stream);
+/* Adam, t = iterations + 1, b1^t and b2^t in fp32, alpha = lr_t*sqrt(1 - b2^t)/(1 - b1^t):
+ *   m <- m + (g - m)(1 - b1);  v <- v + (g^2 - v)(1 - b2);  w <- w - alpha*m/(sqrt(v) + epsilon)
+ * AMSGrad when vhat is not NULL: vhat <- max(vhat, v), and vhat takes the place of v in the update of w. */
+int lisec_adam_step_dev(float* theta, const float* grad, float* m, float* v, float* vhat /* NULL iff !amsgrad */,
+                        long long n, double lr, double decay, float beta1, float beta2, float epsilon, long long* state,
+                        int advance, lisec_stream_t stream);
+
 /* x *= s  (gradient averaging after the data-parallel all-reduce) */
 int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);
 

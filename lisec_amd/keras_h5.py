@@ -8,6 +8,7 @@ Predict.py:51-52).  A Keras `.h5` holds
     /model_weights      attrs layer_names, backend, keras_version
         /<layer>        attr weight_names = [b'<layer>/kernel:0', ...]; datasets at <layer>/<weight>:0
     /optimizer_weights  attr weight_names = [b'SGD/iter:0', b'SGD/<layer>/<weight>/momentum:0', ...] + datasets
+                        (Adam: b'Adam/iter:0', every .../m:0, every .../v:0, every .../vhat:0 with amsgrad)
 
 This module rebuilds the layer list that createModel (model_training.py:222-257) produces -- with the names Keras
 assigns automatically (dense, dense_1, batch_normalization_7, conv2d_transpose_2 ...) and the order of
@@ -196,17 +197,34 @@ def model_config(nx, ny, nz, maxPoints):
 
 def _training_config(optimizer):
     o = optimizer or {}
+    if o.get("class_name", "SGD") == "Adam":
+        oc = {"class_name": "Adam", "config": {
+            "name": "Adam", "learning_rate": float(o.get("lr", 0.001)), "decay": float(o.get("decay", 0.0)),
+            "beta_1": float(o.get("beta_1", 0.9)), "beta_2": float(o.get("beta_2", 0.999)),
+            "epsilon": float(o.get("epsilon", 1e-7)), "amsgrad": bool(o.get("amsgrad", False))}}
+    else:
+        oc = {"class_name": "SGD", "config": {
+            "name": "SGD", "learning_rate": float(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
+            "momentum": float(o.get("momentum", 0.0)), "nesterov": bool(o.get("nesterov", False))}}
     return {"loss": ["mse", "mse"], "metrics": None, "weighted_metrics": None, "loss_weights": None,
-            "optimizer_config": {"class_name": "SGD", "config": {
-                "name": "SGD", "learning_rate": float(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
-                "momentum": float(o.get("momentum", 0.0)), "nesterov": bool(o.get("nesterov", False))}}}
+            "optimizer_config": oc}
+
+
+def _slot_kinds(optimizer):
+    """(class name, slot kinds in Keras' order): the slots of one kind are written for every variable before the next kind."""
+    if optimizer.get("class_name", "SGD") == "Adam":
+        return "Adam", (("m", "v", "vhat") if optimizer.get("amsgrad") else ("m", "v"))
+    return "SGD", (("momentum",) if float(optimizer.get("momentum", 0.0)) > 0 else ())
 
 
 # ---------------------------------------------------------------------------------------------------
-def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None):
-    """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) or None (a model that
-    was never compiled: no training_config / optimizer_weights, like Keras).  velocity: dict of trainable
-    ParamStore name -> momentum accumulator."""
+def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None, m=None, v=None,
+               vhat=None):
+    """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
+    dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam, or None (a model that was never
+    compiled: no training_config / optimizer_weights, like Keras).  The slots, each a dict of trainable ParamStore
+    name -> array: velocity (SGD momentum accumulators, momentum > 0), m and v (Adam moments), vhat (AMSGrad).
+    optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none)."""
     layers, _ = keras_layers(nx, ny, nz, maxPoints)
     with hdf5_lite.File(path, "w") as f:
         f.attrs["keras_version"] = KERAS_VERSION.encode()
@@ -226,13 +244,19 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
             for n, (w, pname) in zip(names, L["weights"]):
                 lg.create_dataset(n, data=np.asarray(params[pname], dtype=np.float32))
                 if w in ("kernel", "bias", "gamma", "beta"):
-                    slots.append((f"SGD/{L['name']}/{w}/momentum:0", pname))
-        if optimizer is not None and velocity is not None:
-            og = f.create_group("optimizer_weights")
-            og.attrs["weight_names"] = [b"SGD/iter:0"] + [n.encode("utf8") for n, _ in slots]
-            og.create_dataset("SGD/iter:0", data=np.array(int(iterations), dtype=np.int64))
-            for n, pname in slots:
-                og.create_dataset(n, data=np.asarray(velocity[pname], dtype=np.float32))
+                    slots.append((f"{L['name']}/{w}", pname))
+        if optimizer is None:
+            return
+        cls, kinds = _slot_kinds(optimizer)
+        given = dict(momentum=velocity, m=m, v=v, vhat=vhat)
+        if any(given[k] is None for k in kinds):
+            return
+        entries = [(f"{cls}/{var}/{k}:0", given[k][pname]) for k in kinds for var, pname in slots]
+        og = f.create_group("optimizer_weights")
+        og.attrs["weight_names"] = [f"{cls}/iter:0".encode()] + [n.encode("utf8") for n, _ in entries]
+        og.create_dataset(f"{cls}/iter:0", data=np.array(int(iterations), dtype=np.int64))
+        for n, a in entries:
+            og.create_dataset(n, data=np.asarray(a, dtype=np.float32))
 
 
 def _text(v):
@@ -268,7 +292,8 @@ def _suffix_number(name, base):
 
 def load_model(path, grid=None):
     """Reads a Keras `.h5` written by the reference (or by save_model).  Returns dict(params, nx, ny, nz, maxPoints,
-    iterations, velocity (dict or None), optimizer (dict or None)).
+    iterations, optimizer (dict or None, as save_model takes it), and the slots velocity, m, v, vhat (each a dict of
+    trainable ParamStore name -> array, or None)).  Slots are matched by name, not by position.
 
     Layers are matched by class and creation order (the numeric suffix of Keras' automatic names), not by the exact
     suffix: a model built as the second one of a Python session carries shifted suffixes."""
@@ -316,24 +341,29 @@ def load_model(path, grid=None):
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
         out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, velocity=None,
-                   optimizer=None)
+                   m=None, v=None, vhat=None, optimizer=None)
         if "training_config" in f.attrs:
             oc = json.loads(_text(f.attrs["training_config"])).get("optimizer_config", {})
             c = oc.get("config", {})
             if oc.get("class_name") == "SGD":
                 out["optimizer"] = dict(lr=c.get("learning_rate", c.get("lr", 0.01)), decay=c.get("decay", 0.0),
                                         momentum=c.get("momentum", 0.0), nesterov=c.get("nesterov", False))
+            elif oc.get("class_name") == "Adam":
+                out["optimizer"] = dict(class_name="Adam", lr=c.get("learning_rate", c.get("lr", 0.001)),
+                                        decay=c.get("decay", 0.0), beta_1=c.get("beta_1", 0.9),
+                                        beta_2=c.get("beta_2", 0.999), epsilon=c.get("epsilon", 1e-7),
+                                        amsgrad=c.get("amsgrad", False))
         if "optimizer_weights" in f:
             og = f["optimizer_weights"]
-            vel = {}
+            found_slots = {}
             for w in _attr_list(og, "weight_names"):
                 a = og[w][()]
                 if w.endswith("iter:0"):
                     out["iterations"] = int(a)
                     continue
-                m = re.fullmatch(r"[^/]+/(.+)/momentum:0", w)
+                m = re.fullmatch(r"[^/]+/(.+)/(momentum|m|v|vhat):0", w)
                 if m and m.group(1) in keras_to_param:
-                    vel[keras_to_param[m.group(1)]] = np.asarray(a, dtype=np.float32)
-            if vel:
-                out["velocity"] = vel
+                    kind = "velocity" if m.group(2) == "momentum" else m.group(2)
+                    found_slots.setdefault(kind, {})[keras_to_param[m.group(1)]] = np.asarray(a, dtype=np.float32)
+            out.update(found_slots)
         return out

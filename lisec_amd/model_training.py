@@ -1,7 +1,7 @@
 """Drop-in counterpart of the reference's model_training.py (same public names and argument order):
 
     get_voxel, VFE_preprocessing, combine_lidar_data, rotate_points, RepeatLayer, MaxPoolingVFELayer,
-    createModel, load_model, optimizers.SGD, train, train_with_model
+    createModel, load_model, optimizers.SGD, optimizers.Adam, train, train_with_model
 
 The Keras graph is replaced by lisec_amd.network.LisecNet (HIP kernels behind the C ABI); lidar sweeps
 stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacked in host RAM
@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from .network import LisecNet
+from .network import LisecNet, OptimizerSpec
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
 
@@ -220,13 +220,62 @@ class MaxPoolingVFELayer:
 
 
 # ---------------------------------------------------------------------------------------------------
+def _no_clipping(cls, kwargs):
+    """tf.keras optimizers take clipnorm / clipvalue / global_clipnorm: gradient clipping is not implemented here."""
+    clip = sorted(k for k in ("clipnorm", "clipvalue", "global_clipnorm") if kwargs.get(k) is not None)
+    if clip:
+        raise NotImplementedError(f"{cls}: gradient clipping ({', '.join(clip)}) is not implemented")
+    rest = sorted(k for k in kwargs if k not in ("clipnorm", "clipvalue", "global_clipnorm"))
+    if rest:
+        raise TypeError(f"{cls}: unexpected keyword argument(s) {', '.join(rest)}")
+
+
 class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimizers`)
+    """tf.keras 2.4 SGD and Adam (OptimizerV2): lr_t = lr / (1 + decay*iterations) for both; `lr=` is the legacy spelling
+    of `learning_rate=`.  The updates run as HIP kernels on the flat variables (csrc/eltwise.hip, csrc/optim.hip)."""
+
     class SGD:
-        def __init__(self, lr=0.01, decay=0.0, momentum=0.0, nesterov=False, learning_rate=None):
-            self.lr = learning_rate if learning_rate is not None else lr
-            self.decay, self.momentum, self.nesterov = decay, momentum, nesterov
-            if not nesterov:
-                raise NotImplementedError("only the reference's configuration (nesterov=True) is implemented")
+        def __init__(self, lr=0.01, decay=0.0, momentum=0.0, nesterov=False, learning_rate=None, name="SGD", **kwargs):
+            _no_clipping("SGD", kwargs)
+            self.lr = float(learning_rate if learning_rate is not None else lr)
+            self.decay, self.momentum, self.nesterov, self.name = float(decay), float(momentum), bool(nesterov), name
+            if not 0.0 <= self.momentum <= 1.0:
+                raise ValueError("`momentum` must be between [0, 1].")
+
+        def spec(self):
+            return OptimizerSpec("sgd", self.lr, self.decay, self.momentum, self.nesterov)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": self.lr, "decay": self.decay, "momentum": self.momentum,
+                    "nesterov": self.nesterov}
+
+    class Adam:
+        def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, name="Adam",
+                     lr=None, decay=0.0, **kwargs):
+            _no_clipping("Adam", kwargs)
+            self.lr = float(lr if lr is not None else learning_rate)
+            self.decay, self.beta_1, self.beta_2 = float(decay), float(beta_1), float(beta_2)
+            self.epsilon, self.amsgrad, self.name = float(epsilon), bool(amsgrad), name
+            self.spec()                                      # range checks
+
+        def spec(self):
+            return OptimizerSpec("adam", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
+                                 amsgrad=self.amsgrad)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": self.lr, "decay": self.decay, "beta_1": self.beta_1,
+                    "beta_2": self.beta_2, "epsilon": self.epsilon, "amsgrad": self.amsgrad}
+
+    @staticmethod
+    def get(identifier):
+        """compile(optimizer='sgd' | 'adam') -> the optimizer with Keras' defaults; an optimizer object is returned as is."""
+        if isinstance(identifier, (optimizers.SGD, optimizers.Adam)):
+            return identifier
+        if isinstance(identifier, str):
+            kinds = {"sgd": optimizers.SGD, "adam": optimizers.Adam}
+            if identifier.lower() in kinds:
+                return kinds[identifier.lower()]()
+        raise ValueError(f"unsupported optimizer {identifier!r}: optimizers.SGD, optimizers.Adam, 'sgd' or 'adam'")
 
 
 class History:
@@ -251,8 +300,10 @@ class Model:
 
     # -- compile / fit / predict / save ------------------------------------------------------------
     def compile(self, optimizer, loss):
-        """compile(optimizer=sgd, loss=['mse','mse']) (model_training.py:296).  A fresh optimizer discards
-        velocity and iteration count, as re-compiling does in the reference (:339-340)."""
+        """compile(optimizer=sgd, loss=['mse','mse']) (model_training.py:296); optimizer: optimizers.SGD / optimizers.Adam
+        or the string 'sgd' / 'adam'.  A fresh optimizer discards every slot (momentum accumulators, Adam moments) and the
+        iteration count, as re-compiling does in the reference (:339-340)."""
+        optimizer = optimizers.get(optimizer)
         if isinstance(loss, (list, tuple)):
             kinds = [str(x).lower() for x in loss]
             if kinds == ['mse', 'mse']:
@@ -265,7 +316,10 @@ class Model:
             raise ValueError(f"unsupported loss {loss}")
         self.optimizer, self.loss = optimizer, loss
         self.net._prepare_training()
-        self.net.velocity.zero_()
+        for name in optimizer.spec().slots:
+            self.net.slot(name)
+        for t in self.net.slots().values():
+            t.zero_()
         self.net.iterations = 0
 
     def _as_samples(self, x):
@@ -305,7 +359,7 @@ class Model:
             steps = max(1, steps_per_epoch // self.dp.world)
         dev = self.net.device
         hist = History()
-        o = self.optimizer
+        opt = self.optimizer.spec()
         # targets live on the device for the whole fit when they fit comfortably (1.28 MB per sample)
         on_dev = n * ycls[0].size * 4 * 8 < (2 << 30)
         if on_dev:
@@ -345,9 +399,9 @@ class Model:
                                           rpn_grads_ready=lambda lo, hi, avg=avg: avg.start_tail(self.net.grad, lo, hi))
                         avg.finish(self.net.grad)
                     else:
-                        self.net.backward(yc, yr, loss=self.loss, rpn_grads_ready=lambda lo, hi: self.net.early_update(
-                            lo, hi, lr=o.lr, decay=o.decay, momentum=o.momentum))
-                    self.net.apply_gradients(lr=o.lr, decay=o.decay, momentum=o.momentum)
+                        self.net.backward(yc, yr, loss=self.loss,
+                                          rpn_grads_ready=lambda lo, hi: self.net.early_update(lo, hi, opt=opt))
+                    self.net.apply_gradients(opt=opt)
                 tot_dev += self.net.loss_out
                 if verbose and ((st + 1) % every == 0 or st + 1 == steps):
                     print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / (st + 1):.4f}", end="", flush=True)
@@ -376,8 +430,9 @@ class Model:
                 return None
         dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         need = max(int(p.shape[0]) for p in pts)
-        o = self.optimizer
-        key = (key0, dtype, self.loss, o.lr, o.decay, o.momentum, id(self.net), torch.cuda.current_stream().cuda_stream)
+        opt = self.optimizer.spec()
+        # the full optimizer config: a re-compile with another optimizer records a new plan
+        key = (key0, dtype, self.loss, opt.config, id(self.net), torch.cuda.current_stream().cuda_stream)
         cur = getattr(self, "_captured", None)
         if cur is not None and cur[0] == key and cur[1].capacity >= need and cur[1].alloc_gen == _lib.alloc_generation():
             return cur[1]
@@ -388,7 +443,7 @@ class Model:
         from .network import RecordedStep, PipelinedStep
         capacity = max(1024, -(-need // 4096) * 4096)        # a little head-room: later fits reuse the plan
         step = (PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep)(self.net, Voxelizer(*key0[:3], key0[3], *key0[4:], device=self.net.device), capacity,
-                            dtype=dtype, loss=self.loss, lr=o.lr, decay=o.decay, momentum=o.momentum,
+                            dtype=dtype, loss=self.loss, opt=opt,
                             allreduce=self.dp.bucketed() if self.dp is not None else None)
         self._captured = (key, step)
         return step
@@ -405,9 +460,10 @@ class Model:
 
     def save(self, path):
         """model.save(save_path) (model_training.py:302): a Keras-layout HDF5 file (model_config, model_weights/<layer>/
-        <layer>/<weight>:0 with Keras' automatic layer names, training_config and the SGD iteration count + momentum
-        accumulators under optimizer_weights), written by lisec_amd.hdf5_lite -- see lisec_amd/keras_h5.py.  A path
-        ending in .npz gets a plain numpy archive with the names of lisec_amd.params.param_specs() instead."""
+        <layer>/<weight>:0 with Keras' automatic layer names, training_config and the optimizer's iteration count + slots
+        -- SGD momentum accumulators, Adam moments -- under optimizer_weights), written by lisec_amd.hdf5_lite -- see
+        lisec_amd/keras_h5.py.  A path ending in .npz gets a plain numpy archive with the names of
+        lisec_amd.params.param_specs() instead."""
         p = self.net.params
         if self.dp is not None:
             # data parallel: theta is identical on every rank, the BatchNormalization moving statistics are per
@@ -437,14 +493,20 @@ class Model:
                 np.savez(f, __meta__=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8), **d)
             return
         from . import keras_h5
-        opt = vel = None
+        opt, slots = None, {}
         if self.optimizer is not None:
             o = self.optimizer
-            opt = dict(lr=o.lr, decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
+            if isinstance(o, optimizers.Adam):
+                opt = dict(class_name="Adam", lr=o.lr, decay=o.decay, beta_1=o.beta_1, beta_2=o.beta_2, epsilon=o.epsilon,
+                           amsgrad=o.amsgrad)
+            else:
+                opt = dict(lr=o.lr, decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
             p = self.net.params
-            vel = {n: p.view(n, buf=self.net.velocity).detach().cpu().numpy() for n in p.trainable_names()}
+            for name in o.spec().slots:
+                buf = self.net.slot(name)
+                slots[name] = {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
         keras_h5.save_model(path, d, self.nx, self.ny, self.nz, self.maxPoints, optimizer=opt,
-                            iterations=self.net.iterations, velocity=vel)
+                            iterations=self.net.iterations, **slots)
 
     def summary(self):
         n = self.net.params.n_trainable()
@@ -460,7 +522,7 @@ def createModel(nx, ny, nz, maxPoints):
 def load_model(path, custom_objects=None):
     """load_model(model_path, custom_objects={'RepeatLayer':…, 'MaxPoolingVFELayer':…}) (:337-338, Predict.py:51-52).
     Reads Keras HDF5 files (the reference's own checkpoints or Model.save's) and the .npz variant.  Like Keras, a file
-    that carries a training_config comes back compiled, with the saved iteration count and momentum accumulators."""
+    that carries a training_config (SGD or Adam) comes back compiled, with the saved iteration count and optimizer slots."""
     with open(path, "rb") as f:
         magic = f.read(8)
     dev = _lib.require_gpu()
@@ -475,15 +537,23 @@ def load_model(path, custom_objects=None):
     ck = keras_h5.load_model(path)
     m = Model(ck["nx"], ck["ny"], ck["nz"], ck["maxPoints"], params=ParamStore(dev, init=ck["params"]))
     o = ck["optimizer"]
-    if o is not None and o.get("nesterov"):
-        m.compile(optimizer=optimizers.SGD(lr=o["lr"], decay=o["decay"], momentum=o["momentum"], nesterov=True),
-                  loss=['mse', 'mse'])
+    if o is not None:
+        if o.get("class_name", "SGD") == "Adam":
+            opt = optimizers.Adam(learning_rate=o["lr"], decay=o["decay"], beta_1=o["beta_1"], beta_2=o["beta_2"],
+                                  epsilon=o["epsilon"], amsgrad=o["amsgrad"])
+        else:
+            opt = optimizers.SGD(lr=o["lr"], decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
+        m.compile(optimizer=opt, loss=['mse', 'mse'])
         m.net.iterations = ck["iterations"]
-        if ck["velocity"] is not None:
-            p = m.net.params
+        p = m.net.params
+        for name in opt.spec().slots:
+            saved = ck.get(name)
+            if saved is None:
+                continue
+            buf = m.net.slot(name)
             for n in p.trainable_names():
-                if n in ck["velocity"]:
-                    p.view(n, buf=m.net.velocity).copy_(torch.from_numpy(np.ascontiguousarray(ck["velocity"][n])))
+                if n in saved:
+                    p.view(n, buf=buf).copy_(torch.from_numpy(np.ascontiguousarray(saved[n])))
     return m
 
 

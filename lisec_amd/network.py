@@ -23,6 +23,51 @@ from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
 
+class OptimizerSpec:
+    """One optimizer of the step: its kind ("sgd" | "adam"), the tf.keras 2.4 hyper-parameters and the names of the slots
+    it keeps -- per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
+    SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295).
+
+        sgd    momentum == 0: no slot;  momentum > 0: "velocity" (v <- m*v - lr_t*g, then w <- w + v, or Nesterov)
+        adam   "m", "v", and "vhat" with amsgrad"""
+
+    def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
+                 epsilon=1e-7, amsgrad=False):
+        if kind not in ("sgd", "adam"):
+            raise ValueError(f"unknown optimizer kind {kind!r}")
+        self.kind, self.lr, self.decay = kind, float(lr), float(decay)
+        if kind == "sgd":
+            self.momentum, self.nesterov = float(momentum), bool(nesterov)
+            if self.momentum < 0:
+                raise ValueError("momentum must be >= 0")
+        else:
+            self.beta_1, self.beta_2, self.epsilon, self.amsgrad = float(beta_1), float(beta_2), float(epsilon), bool(amsgrad)
+            if not (0 <= self.beta_1 < 1 and 0 <= self.beta_2 < 1 and self.epsilon >= 0):
+                raise ValueError("beta_1 and beta_2 must lie in [0, 1), epsilon must be >= 0")
+
+    @property
+    def config(self):
+        """Every hyper-parameter, hashable: two specs with equal configs issue the same launches."""
+        if self.kind == "sgd":
+            return ("sgd", self.lr, self.decay, self.momentum, self.nesterov)
+        return ("adam", self.lr, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
+
+    @property
+    def slots(self):
+        if self.kind == "sgd":
+            return ("velocity",) if self.momentum > 0 else ()
+        return ("m", "v", "vhat") if self.amsgrad else ("m", "v")
+
+    def __eq__(self, other):
+        return isinstance(other, OptimizerSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(self.config)
+
+    def __repr__(self):
+        return f"OptimizerSpec{self.config}"
+
+
 class ConvLayer:
     """One dense contraction: geometry + packed-weight slot + (optional) BatchNormalization."""
 
@@ -493,7 +538,8 @@ class LisecNet:
         dev, f32 = self.device, torch.float32
         p = self.params
         self.grad = torch.zeros_like(p.theta)
-        self.velocity = torch.zeros_like(p.theta)
+        self.velocity = torch.zeros_like(p.theta)     # the SGD momentum slot; the Adam slots are made by slot() when asked for
+        self._slots = {"velocity": self.velocity}
         self.dact = {}
         for name, t in self.act.items():
             if name.endswith(".u") or name in ("concat", "head", "fold") or ".y" in name:
@@ -1080,32 +1126,64 @@ class LisecNet:
         self._mark("bwd:joined")
         return self.loss_out
 
-    def early_update(self, lo, hi, lr=0.01, decay=1e-6, momentum=0.9):
-        """SGD-Nesterov of theta[lo:hi] AHEAD of the rest of the step (backward's rpn_grads_ready hook, on the second stream):
-        the RPN + head variables -- 94 % of the parameters -- have final gradients while the middle layers and the VFE are
+    def slot(self, name):
+        """The optimizer slot `name` ("velocity", "m", "v", "vhat"; see OptimizerSpec): a buffer shaped like theta, zero when
+        first asked for, at a fixed address from then on (recorded step plans point at it)."""
+        self._prepare_training()
+        t = self._slots.get(name)
+        if t is None:
+            if name not in ("m", "v", "vhat"):
+                raise KeyError(f"unknown optimizer slot {name!r}")
+            t = self._slots[name] = torch.zeros_like(self.params.theta)
+            torch.cuda.synchronize(self.device)   # zero before any stream of the step (the second one included) uses it
+        return t
+
+    def slots(self):
+        """Every slot made so far, by name (the SGD velocity always among them)."""
+        self._prepare_training()
+        return dict(self._slots)
+
+    def _update(self, opt, lo, hi, advance):
+        """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step)."""
+        th, g = self.params.theta[lo:hi], self.grad[lo:hi]
+        sl = [self.slot(name)[lo:hi] for name in opt.slots]
+        if opt.kind == "adam":
+            ops.adam_step_dev(th, g, sl[0], sl[1], sl[2] if opt.amsgrad else None, opt.lr, opt.decay, opt.beta_1,
+                              opt.beta_2, opt.epsilon, self._iter_dev, advance=advance)
+        elif opt.momentum > 0 and opt.nesterov:
+            # the reference's configuration keeps its own kernel (eltwise.hip)
+            ops.sgd_nesterov_step_dev(th, g, sl[0], opt.lr, opt.decay, opt.momentum, self._iter_dev, advance=advance)
+        else:
+            ops.sgd_step_dev(th, g, sl[0] if sl else None, opt.lr, opt.decay, opt.momentum, opt.nesterov, self._iter_dev,
+                             advance=advance)
+
+    def early_update(self, lo, hi, lr=0.01, decay=1e-6, momentum=0.9, opt=None):
+        """SGD-Nesterov (or `opt`, an OptimizerSpec) of theta[lo:hi] AHEAD of the rest of the step (backward's
+        rpn_grads_ready hook, on the second stream): the RPN + head variables -- 94 % of the parameters -- have final gradients while the middle layers and the VFE are
         still being differentiated, and nothing in the rest of the backward pass reads theta itself (the contractions read
         the packed copies), so their 26 MB update runs under the MFMA-bound kernels instead of at the serial end of the
-        step.  Elementwise, hence the same values whichever call updates an element.  apply_gradients() then updates
-        theta[:lo] and advances the iteration count."""
+        step.  Elementwise, hence the same values whichever call updates an element -- for every optimizer of
+        OptimizerSpec, as both calls read the same iteration count: this one on the second stream, which the main stream
+        joins before apply_gradients() updates theta[:lo] and advances the count."""
         if not self.early_sgd or lo % 4 or hi != self.params.n_theta:
             return
-        p = self.params
+        opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
         n = (hi - lo) // 4 * 4
-        ops.sgd_nesterov_step_dev(p.theta[lo:lo + n], self.grad[lo:lo + n], self.velocity[lo:lo + n], lr, decay, momentum,
-                                  self._iter_dev, advance=False)
+        self._update(opt, lo, lo + n, advance=False)
         self._early_from = lo
 
-    def apply_gradients(self, lr=0.01, decay=1e-6, momentum=0.9):
-        """optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295)."""
+    def apply_gradients(self, lr=0.01, decay=1e-6, momentum=0.9, opt=None):
+        """optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295), or `opt` (an
+        OptimizerSpec: the same one early_update() was given in this step)."""
         # lr_t = lr / (1 + decay * iterations), derived on the device from its own iteration counter
+        opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
         lo = getattr(self, "_early_from", None)
         self._early_from = None
         if lo is not None:
             # the tail of the buffer was updated by early_update() during the backward pass
-            ops.sgd_nesterov_step_dev(self.params.theta[:lo], self.grad[:lo], self.velocity[:lo], lr, decay, momentum,
-                                      self._iter_dev)
+            self._update(opt, 0, lo, advance=True)
         else:
-            ops.sgd_nesterov_step_dev(self.params.theta, self.grad, self.velocity, lr, decay, momentum, self._iter_dev)
+            self._update(opt, 0, self.params.theta.numel(), advance=True)
         self._mark("step:updated")
         self._iterations += 1
         self.params_version += 1
@@ -1171,10 +1249,28 @@ def _sync_packed(net):
         net._late_pending = True
 
 
+def _snapshot(net):
+    """The variables, BN state, every optimizer slot and the iteration count, before the warm-up / recording steps."""
+    p = net.params
+    return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
+            net._iterations)
+
+
+def _restore(net, keep):
+    p = net.params
+    p.theta.copy_(keep[0])
+    p.state.copy_(keep[1])
+    for k, t in keep[2].items():
+        net.slot(k).copy_(t)
+    net._iter_dev.copy_(keep[3])
+    net._iterations = keep[4]
+
+
 class RecordedStep:
-    """One whole fit() step -- voxelise, forward, backward (both streams, fork / join events included), SGD-Nesterov, the
-    weight repack for the next step -- recorded ONCE as a step plan of the C ABI (lisec_step_plan_*, csrc/plan.hip) and
-    re-issued by one C call per step: the ~250 launches cost the host one ctypes call instead of ~1.5 ms of Python
+    """One whole fit() step -- voxelise, forward, backward (both streams, fork / join events included), the optimizer
+    update (opt: an OptimizerSpec, SGD-Nesterov by default), the weight repack for the next step -- recorded ONCE as a
+    step plan of the C ABI (lisec_step_plan_*, csrc/plan.hip) and re-issued by one C call per step: the ~250 launches
+    cost the host one ctypes call instead of ~1.5 ms of Python
     (schedule, plan selection, argument marshalling).  It IS the eager schedule -- same kernels, same streams, same
     events, bit-identical variables -- not a HIP graph (a captured graph of this two-stream step replays 2x slower than
     the eager launches on ROCm 7.2).  The schedule is static; what varies from sample to sample lives in device memory:
@@ -1183,7 +1279,8 @@ class RecordedStep:
                the grid, which the voxeliser's range test (model_training.py:118-120) drops -- kept points, their
                order and therefore every voxel and feature row are exactly those of the unpadded sweep
       targets  (Ho,Wo,2) / (Ho,Wo,14) static buffers
-      lr_t     derived by the SGD kernel from the device iteration counter (lisec_sgd_nesterov_step_dev)
+      lr_t     derived by the optimizer kernels from the device iteration counter (lisec_sgd_nesterov_step_dev,
+               lisec_sgd_step_dev, lisec_adam_step_dev)
 
     Record and replay on ONE torch stream (the current stream at construction).  Data parallel (allreduce=): the gradient
     exchange is part of the plan."""
@@ -1191,7 +1288,7 @@ class RecordedStep:
     PAD = 1.0e6          # metres: floor(1e6 / 0.5) is far beyond maxVoxelX, the point is dropped like any other outlier
 
     def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", lr=0.01, decay=1e-6, momentum=0.9,
-                 warmup=2, allreduce=None):
+                 warmup=2, allreduce=None, opt=None):
         import ctypes
         self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
         # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
@@ -1203,13 +1300,16 @@ class RecordedStep:
         self.points = torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev)
         self.ycls = torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev)
         self.yreg = torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev)
-        self.hyper = (lr, decay, momentum)
+        # the optimizer of the recorded step (OptimizerSpec); lr / decay / momentum: the reference's SGD-Nesterov
+        self.opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
         self.sample = None
         self.stream_handle = torch.cuda.current_stream().cuda_stream
         torch.cuda.synchronize(dev)
         net._prepare_training()
         p = net.params
-        keep = (p.theta.clone(), p.state.clone(), net.velocity.clone(), net._iter_dev.clone(), net._iterations)
+        for name in self.opt.slots:
+            net.slot(name)                       # made before the plan records their addresses
+        keep = _snapshot(net)
         # eager warm-up (lazy workspaces, descriptor tables, events; it leaves the next step's repack pending, which is
         # the state every recorded step starts from), then one more step that is recorded while it runs
         for _ in range(max(1, warmup)):
@@ -1225,8 +1325,7 @@ class RecordedStep:
         torch.cuda.synchronize(dev)
         self.launches = self.lib.lisec_step_plan_size(self.plan)
         # those steps trained on the padding: put every variable back and repack the kernels from them
-        p.theta.copy_(keep[0]); p.state.copy_(keep[1]); net.velocity.copy_(keep[2]); net._iter_dev.copy_(keep[3])
-        net._iterations = keep[4]
+        _restore(net, keep)
         net.params_version += 1
         net.state_version += 1
         p.touch()
@@ -1254,8 +1353,8 @@ class RecordedStep:
             ar(net.grad)
         else:
             net.backward(self.ycls, self.yreg, loss=self.loss,
-                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, *self.hyper))
-        net.apply_gradients(*self.hyper)
+                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, opt=self.opt))
+        net.apply_gradients(opt=self.opt)
 
     def _check_stream(self):
         if torch.cuda.current_stream().cuda_stream != self.stream_handle:
@@ -1323,7 +1422,7 @@ class PipelinedStep:
     PAD = RecordedStep.PAD
 
     def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", lr=0.01, decay=1e-6, momentum=0.9,
-                 warmup=2, allreduce=None):
+                 warmup=2, allreduce=None, opt=None):
         import ctypes
         self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
         self.allreduce = allreduce                 # data parallel: see RecordedStep
@@ -1332,12 +1431,15 @@ class PipelinedStep:
         self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(2)]
         self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(2)]
         self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(2)]
-        self.hyper = (lr, decay, momentum)
+        # the optimizer of the recorded step (OptimizerSpec); lr / decay / momentum: the reference's SGD-Nesterov
+        self.opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
         self.stream_handle = torch.cuda.current_stream().cuda_stream
         torch.cuda.synchronize(dev)
         net._prepare_training()
         p = net.params
-        keep = (p.theta.clone(), p.state.clone(), net.velocity.clone(), net._iter_dev.clone(), net._iterations)
+        for name in self.opt.slots:
+            net.slot(name)                       # made before the plan records their addresses
+        keep = _snapshot(net)
         self.samples = [self.vox(self.points[j]) for j in range(2)]
         for k in range(2 * max(1, warmup)):
             self._enqueue(k & 1)
@@ -1354,8 +1456,7 @@ class PipelinedStep:
             self.plans.append(plan)
         torch.cuda.synchronize(dev)
         self.launches = self.lib.lisec_step_plan_size(self.plans[0])
-        p.theta.copy_(keep[0]); p.state.copy_(keep[1]); net.velocity.copy_(keep[2]); net._iter_dev.copy_(keep[3])
-        net._iterations = keep[4]
+        _restore(net, keep)
         net.params_version += 1
         net.state_version += 1
         p.touch()
@@ -1384,8 +1485,8 @@ class PipelinedStep:
             ar(net.grad)
         else:
             net.backward(self.ycls[j], self.yreg[j], loss=self.loss, side_filler=filler,
-                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, *self.hyper))
-        net.apply_gradients(*self.hyper)
+                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, opt=self.opt))
+        net.apply_gradients(opt=self.opt)
 
     def _check_stream(self):
         if torch.cuda.current_stream().cuda_stream != self.stream_handle:

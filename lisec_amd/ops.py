@@ -384,6 +384,20 @@ def sgd_nesterov_step_dev(theta, grad, velocity, lr, decay, momentum, state, adv
                   _lib.ptr(state), _lib.current_stream()))
 
 
+def sgd_step_dev(theta, grad, velocity, lr, decay, momentum, nesterov, state, advance=True):
+    """tf.keras SGD on the device iteration count (lisec_sgd_step_dev): velocity is None exactly when momentum == 0."""
+    _lib.check(_lib.load().lisec_sgd_step_dev(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity), theta.numel(),
+                                              float(lr), float(decay), float(momentum), 1 if nesterov else 0,
+                                              _lib.ptr(state), 1 if advance else 0, _lib.current_stream()))
+
+
+def adam_step_dev(theta, grad, m, v, vhat, lr, decay, beta_1, beta_2, epsilon, state, advance=True):
+    """tf.keras Adam on the device iteration count (lisec_adam_step_dev); vhat not None: AMSGrad."""
+    _lib.check(_lib.load().lisec_adam_step_dev(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v), _lib.ptr(vhat),
+                                               theta.numel(), float(lr), float(decay), float(beta_1), float(beta_2),
+                                               float(epsilon), _lib.ptr(state), 1 if advance else 0, _lib.current_stream()))
+
+
 def fold_depth(x, out, D, HW, C, inverse=False, mask=None):
     """(D,H,W,C) <-> (H,W,C*D) (Permute + Reshape of model_training.py:242-243); inverse: gradient, ReLU-gated by mask."""
     _lib.check(_lib.load().lisec_fold_depth(_lib.ptr(x), _lib.ptr(out), D, HW, C, 1 if inverse else 0, _lib.ptr(mask),
