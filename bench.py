@@ -2,6 +2,7 @@
 """Headline benchmark: Lyft-grid samples/s, forward + backward + SGD step (BASELINE.json metric).
 
     python bench.py --gpus 1 --steps 100 --warmup 5
+    python bench.py --gpus 1 --steps 100 --warmup 5 --full   (adds the side measurements below)
     python bench.py --gpus N --steps K --warmup W         (starts the N ranks itself, one fresh process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,14 +12,17 @@ in HBM: voxelise (U20k cloud) -> sparse-exact VFE -> 3 Conv3D middle 
 MSE+MSE loss (the reference's compile(), model_training.py:296) -> full backward -> (N > 1: RCCL
 all-reduce of the 6.49 M fp32 gradients) -> SGD-Nesterov update.  Weak scaling: one sample per GPU.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints that line; with --full it first measures, after the timed steps and on rank 0 only,
   roofline      dominant kernel = the second middle Conv3D in its Winograd form (k_wino, fp32 MFMA bound; forward launch), timed
                 live with HIP events on the launch stream; clock and HBM traffic of that kernel come from the PMC passes
                 summarised in profiles/r03_pmc_dominant.json (tools/pmc_summary.py writes it; null when absent)
   roofline_vfe  the VFE grid writer (HBM bound)
+  voxelizer     the HIP voxeliser alone on both sweeps, next to its CPU restatement and the reference's own loop
   r200k, smoothl1_ce   the same step on a 200 000-point sweep / with BASELINE config 4's loss pair
   cpu_baseline  the dense torch-CPU oracle (port of the reference's dense Keras graph) timed on this
-                host, on a stated shrunken grid, extrapolated by dense row count.
+                host, on a stated shrunken grid, extrapolated by dense row count (--no-cpu-baseline skips it)
+and adds them to the line; a plain run prints roofline, roofline_vfe, voxelizer, r200k and cpu_baseline as null.
 
 --dump-outputs DIR writes what the last timed step computed (rank 0): loss.npy (total, class, regression), theta.npy
 (the trained variables after the update), velocity.npy (SGD-Nesterov momentum), state.npy (BatchNormalization moving
@@ -298,12 +302,165 @@ def dry_run(rank, world, args):
         dp.close()
 
 
+def side_measurements(args, net, vox, dev, rank, world, cloud, pts, ycls, yreg, use_plan):
+    """--full: what the headline figure does not need, measured after the timed steps on rank 0 (the keys roofline,
+    roofline_vfe, voxelizer, r200k, the other loss pair's name and cpu_baseline of the result line).  Runs more steps on
+    the same variables."""
+    from lisec_amd import _lib, ops
+    # ---- roofline of the dominant kernel, timed live on the launch stream ----------------------
+    # Since the first Conv3D runs over the VFE's compact output (csrc/field_conv.hip, ~1 GFLOP), the largest contraction
+    # of the step is the second middle block's (2 * 160 000 positions * 27 taps * 64 * 64 = 35.4 GFLOP forward, the same
+    # again for each gradient).  Its forward and data gradient run in the Winograd F(2x2, 3x3) form (csrc/wino.hip, 4/9 of
+    # the multiplications); k_wino is the symbol with the most time in the step and the forward its longest launch.
+    mid2 = next(L for L in net.layers if L["name"] == "mid2")
+    c2, dg2 = mid2["conv"], net.dgeom[mid2["conv"].name]
+    dz2, du1 = net.dact["mid2.z"], net.dact["mid1.u"]
+    flops = 2.0 * c2.M * 27 * 64 * 64
+    pmc = pmc_dominant()
+    pmc_src = "PMC passes of this file: " + pmc.get("source", "profiles/r*_pmc_dominant.json absent")
+
+    def run_mid2_dgrad_direct():
+        # TAG_ROOFLINE: one un-sliced launch under its own symbol (k_igemm_halo<1,false,1,2,64,false>), so the row of that
+        # symbol in the rocprofv3 --stats summary of this command is this layer alone
+        ops.conv_forward(dg2, dz2, net.packed_t[c2.name][0], du1, flags=ops.TAG_ROOFLINE)
+    ms_direct = event_time_ms(run_mid2_dgrad_direct, 20)
+    if c2.name in net.packed_wu:
+        def run_mid2_forward_winograd():
+            # TAG_ROOFLINE: the same kernel under the symbol k_wino<false,0,1>
+            ops.conv_forward_winograd(c2.g, net.act["mid1.u"], net.packed_wu[c2.name], net.act["mid2.y"],
+                                      bias=net.params.view(c2.bias), flags=ops.TAG_ROOFLINE)
+        ms = event_time_ms(run_mid2_forward_winograd, 20)
+        tf = flops / (ms * 1e-3) / 1e12
+        # algorithmic FLOPs = the contraction's own (SURVEY 8d: every (position, tap, channel pair) once); the Winograd
+        # form EXECUTES 16 / 36 of them as MFMA work on 650 blocks of 64 tiles (40 000 tiles padded to 41 600)
+        share = (16.0 / 36.0) * (650.0 * 64.0 / (c2.M / 4.0))
+        roofline = dict(bound="mfma", kernel="k_wino<false,0,1> mid2 Conv3D 64->64 k3 s1 forward, Winograd F(2x2,3x3) form",
+                        achieved=tf, peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=tf / PEAK_F32_MFMA_TFLOPS,
+                        frac_executed=tf * share / PEAK_F32_MFMA_TFLOPS, executed_share=share,
+                        note="achieved = algorithmic FLOPs of the contraction / time; the kernel executes executed_share of "
+                             "them on the matrix cores (frac_executed = that work against the same peak)",
+                        clock_ghz=pmc.get("clock_ghz"), clock_note="GRBM_GUI_ACTIVE/8/duration, " + pmc_src,
+                        traffic=pmc.get("traffic_bytes"), traffic_unit="bytes/launch, " + pmc_src,
+                        mfma_busy=pmc.get("mfma_busy"),
+                        us_per_launch=ms * 1e3, flops_per_launch=flops,
+                        in_step_us=pmc.get("in_step_us"),
+                        in_step_frac=(flops / (pmc["in_step_us"] * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS
+                                      if pmc.get("in_step_us") else None))
+    else:                                        # LISEC_TUNING=winograd=0: the direct data gradient is the dominant launch
+        tf = flops / (ms_direct * 1e-3) / 1e12
+        roofline = dict(bound="mfma", kernel="k_igemm_halo<1,false,1,2,64,false> mid2 Conv3D 64->64 k3 s1 data gradient", achieved=tf,
+                        peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=tf / PEAK_F32_MFMA_TFLOPS,
+                        frac_executed=tf / PEAK_F32_MFMA_TFLOPS, executed_share=1.0,
+                        clock_ghz=None, traffic=None, us_per_launch=ms_direct * 1e3, flops_per_launch=flops)
+    # the other large contractions, same clock: mid2 forward, and the dense form of the first Conv3D (the dominant
+    # kernel of rounds 1-2; sweeps beyond LISEC_FIELD_MAX_VOXELS still take it)
+    grid = net.dense_grid()
+    mid1 = next(L for L in net.layers if L["name"] == "mid1")
+    c1 = mid1["conv"]
+    ms_f2 = event_time_ms(lambda: ops.conv_forward(c2.g, net.act["mid1.u"], net.packed[c2.name], net.act["mid2.y"],
+                                                   bias=net.params.view(c2.bias), stats=net.parts), 20)
+    ms_f1 = event_time_ms(lambda: ops.conv_forward(c1.g, grid, net.packed[c1.name], net.act["mid1.y"],
+                                                   bias=net.params.view(c1.bias), stats=net.parts), 10)
+    vout, delta = net.vfe.saved_field("vout"), net.vfe.saved_field("delta")
+    ms_field = event_time_ms(lambda: ops.conv_field_forward(c1.g, vout, delta, net.vfe._sample, net.packed[c1.name],
+                                                            net.act["mid1.y"], net.field_ws,
+                                                            bias=net.params.view(c1.bias)), 20)
+    f1 = 2.0 * c1.M * 27 * 64 * 64
+    roofline["others"] = {
+        "mid2_data_gradient_direct": dict(kernel="k_igemm_halo<1,false,1,2,64,false>", us_per_launch=ms_direct * 1e3,
+                                          achieved=flops / (ms_direct * 1e-3) / 1e12,
+                                          frac=flops / (ms_direct * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=flops,
+                                          note="the direct (implicit-GEMM) form of the same contraction's data gradient: the "
+                                               "dominant launch of rounds 3-4a, executed == algorithmic"),
+        "mid2_forward_direct": dict(us_per_launch=ms_f2 * 1e3, achieved=flops / (ms_f2 * 1e-3) / 1e12,
+                                    frac=flops / (ms_f2 * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=flops),
+        "mid1_dense_form": dict(us_per_launch=ms_f1 * 1e3, achieved=f1 / (ms_f1 * 1e-3) / 1e12,
+                                frac=f1 / (ms_f1 * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=f1),
+        "mid1_field_form": dict(us_per_call=ms_field * 1e3, launches=2,
+                                note="what the step runs: k_field_taps + k_field_combine over the VFE's compact output, "
+                                     "same values as mid1_dense_form"),
+    }
+    sample = vox(pts)
+
+    def run_vfe():
+        net.vfe.forward(sample, True, out=grid)
+    ms_v = event_time_ms(run_vfe, 20)
+    hi = sample.host_info()
+    vfe_bytes = 12.0 * len(cloud) + 24.0 * hi["rows"] + 4.0 * 64 * net.D * net.H * net.W
+    ms_vc = event_time_ms(lambda: net.vfe.forward(sample, True, dense=False), 20)
+    vfe_compact_bytes = 12.0 * len(cloud) + 24.0 * hi["rows"] + 2.0 * 256 * (hi["V"] + 1)
+    ms_g = event_time_ms(lambda: net.vfe.rewrite_grid(grid), 50)
+    grid_bytes = 4.0 * 64 * net.D * net.H * net.W
+    gbs = grid_bytes / (ms_g * 1e-3) / 1e9
+    # traffic from the committed PMC passes (WRITE_SIZE + 2 x FETCH_SIZE of k_vfe_grid's launches WITH the dense grid)
+    vfe_pmc = pmc.get("vfe_grid", {})
+    roofline_vfe = dict(bound="hbm", kernel="k_vfe_grid (dense (8,200,400,64) VFE output writer; lisec_vfe_forward with a grid)", achieved=gbs,
+                        peak=PEAK_HBM_GBS, unit="GB/s", frac=gbs / PEAK_HBM_GBS,
+                        traffic=vfe_pmc.get("traffic_bytes"),
+                        traffic_unit="bytes/launch, " + pmc.get("file", "profiles/r*_pmc_dominant.json absent") + " (vfe_grid)",
+                        us_per_launch=ms_g * 1e3, bytes_per_launch=grid_bytes,
+                        whole_vfe_forward=dict(us_per_call=ms_v * 1e3, bytes_per_call=vfe_bytes,
+                                               achieved=vfe_bytes / (ms_v * 1e-3) / 1e9,
+                                               frac=vfe_bytes / (ms_v * 1e-3) / 1e9 / PEAK_HBM_GBS,
+                                               launches=3),
+                        in_step=dict(us_per_call=ms_vc * 1e3, bytes_per_call=vfe_compact_bytes, launches=3,
+                                     note="what the training step runs: the same three launches without the dense "
+                                          "grid (per-voxel outputs only, read by the field form of the first Conv3D); "
+                                          "latency-bound, not an HBM roofline case"))
+    voxelizer = voxelizer_leg(vox, dev, args.no_cpu_baseline)
+    def side_leg(points_np, loss_name, steps=10):
+        """The same step on another sweep / loss pair, `steps` timed steps after 2 warm-up steps."""
+        p2 = torch.from_numpy(points_np).to(dev)
+        if use_plan and _lib.knob("pipeline_voxels", True):
+            from lisec_amd.network import PipelinedStep
+            rec = PipelinedStep(net, vox, len(points_np), dtype=p2.dtype, loss=loss_name)
+            rec.prime(p2, ycls, yreg)
+            rec.stage_next(p2, ycls, yreg)
+            rec.step()
+            rec.stage_next(p2, ycls, yreg)
+            run = rec.step
+        elif use_plan:
+            from lisec_amd.network import RecordedStep
+            rec = RecordedStep(net, vox, len(points_np), dtype=p2.dtype, loss=loss_name)
+            rec.load(p2, ycls, yreg)
+            run = rec.replay
+        else:
+            rec, run = None, (lambda: net.train_step(vox(p2), ycls, yreg, loss=loss_name))
+        for _ in range(2):
+            run()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(steps):
+            run()
+        torch.cuda.synchronize()
+        d2 = (time.perf_counter() - t1) / steps
+        if rec is not None:
+            rec.close()
+        return dict(value=1.0 / d2, unit="samples/s", ms_per_step=1e3 * d2, points=int(p2.shape[0]),
+                    voxels=vox(p2).host_info()["V"], steps=steps, loss=loss_name)
+    r200k = other_loss = None
+    if args.cloud == "u20k" and world == 1:
+        # real Lyft sweeps are ~200 000 points (model_training.py:116): the same step on the R200k sweep
+        r200k = side_leg(r200k_cloud(rank), args.loss)
+        # the loss pair BASELINE config 4 names, next to the reference's own ['mse','mse'] (model_training.py:296)
+        other = "smoothl1_ce" if args.loss == "mse" else "mse"
+        other_loss = side_leg(cloud, other)
+    out = {"roofline": roofline, "roofline_vfe": roofline_vfe, "voxelizer": voxelizer, "r200k": r200k}
+    if other_loss is not None:
+        out[other_loss["loss"]] = other_loss
+    out["cpu_baseline"] = cpu_baseline() if world == 1 and not args.no_cpu_baseline else None
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)     # 100 steps = 0.56 s of GPU time at 5.6 ms per step
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the rooflines, the voxeliser alone, the R200k and other-loss "
+                         "steps and the CPU baseline (rank 0); a plain run prints those keys as null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--loss", choices=["mse", "smoothl1_ce"], default="mse",
                     help="mse = the reference's compile(loss=['mse','mse']) (model_training.py:296); smoothl1_ce = the "
                          "sigmoid cross-entropy + SmoothL1 pair BASELINE.json's config 3 names (same kernels otherwise)")
@@ -331,7 +488,7 @@ def main():
     from lisec_amd.parallel import select_device
     dev = select_device(local_rank=local_rank, world=world)
 
-    from lisec_amd import Constants, ops
+    from lisec_amd import Constants
     from lisec_amd.network import LisecNet
     from lisec_amd.parallel import DataParallel
     from lisec_amd.voxelizer import Voxelizer
@@ -397,150 +554,13 @@ def main():
         dt = dp.max_float(dt)
     loss_val = float(loss[0].item())
     if args.dump_outputs and rank == 0:
-        # taken now: the roofline and side legs below run more steps on the same variables
+        # taken now: --full (side_measurements) runs more steps on the same variables
         dump_outputs(args.dump_outputs, {"loss": loss.cpu().numpy(), "theta": net.params.theta.cpu().numpy(),
                                          "velocity": net.velocity.cpu().numpy(), "state": net.params.state.cpu().numpy()})
 
     result = None
     if rank == 0:
-        # ---- roofline of the dominant kernel, timed live on the launch stream ----------------------
-        # Since the first Conv3D runs over the VFE's compact output (csrc/field_conv.hip, ~1 GFLOP), the largest contraction
-        # of the step is the second middle block's (2 * 160 000 positions * 27 taps * 64 * 64 = 35.4 GFLOP forward, the same
-        # again for each gradient).  Its forward and data gradient run in the Winograd F(2x2, 3x3) form (csrc/wino.hip, 4/9 of
-        # the multiplications); k_wino is the symbol with the most time in the step and the forward its longest launch.
-        mid2 = next(L for L in net.layers if L["name"] == "mid2")
-        c2, dg2 = mid2["conv"], net.dgeom[mid2["conv"].name]
-        dz2, du1 = net.dact["mid2.z"], net.dact["mid1.u"]
-        flops = 2.0 * c2.M * 27 * 64 * 64
-        pmc = pmc_dominant()
-        pmc_src = "PMC passes of this file: " + pmc.get("source", "profiles/r*_pmc_dominant.json absent")
-
-        def run_mid2_dgrad_direct():
-            # TAG_ROOFLINE: one un-sliced launch under its own symbol (k_igemm_halo<1,false,1,2,64,false>), so the row of that
-            # symbol in the rocprofv3 --stats summary of this command is this layer alone
-            ops.conv_forward(dg2, dz2, net.packed_t[c2.name][0], du1, flags=ops.TAG_ROOFLINE)
-        ms_direct = event_time_ms(run_mid2_dgrad_direct, 20)
-        if c2.name in net.packed_wu:
-            def run_mid2_forward_winograd():
-                # TAG_ROOFLINE: the same kernel under the symbol k_wino<false,0,1>
-                ops.conv_forward_winograd(c2.g, net.act["mid1.u"], net.packed_wu[c2.name], net.act["mid2.y"],
-                                          bias=net.params.view(c2.bias), flags=ops.TAG_ROOFLINE)
-            ms = event_time_ms(run_mid2_forward_winograd, 20)
-            tf = flops / (ms * 1e-3) / 1e12
-            # algorithmic FLOPs = the contraction's own (every (position, tap, channel pair) once); the Winograd
-            # form EXECUTES 16 / 36 of them as MFMA work on 650 blocks of 64 tiles (40 000 tiles padded to 41 600)
-            share = (16.0 / 36.0) * (650.0 * 64.0 / (c2.M / 4.0))
-            roofline = dict(bound="mfma", kernel="k_wino<false,0,1> mid2 Conv3D 64->64 k3 s1 forward, Winograd F(2x2,3x3) form",
-                            achieved=tf, peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=tf / PEAK_F32_MFMA_TFLOPS,
-                            frac_executed=tf * share / PEAK_F32_MFMA_TFLOPS, executed_share=share,
-                            note="achieved = algorithmic FLOPs of the contraction / time; the kernel executes executed_share of "
-                                 "them on the matrix cores (frac_executed = that work against the same peak)",
-                            clock_ghz=pmc.get("clock_ghz"), clock_note="GRBM_GUI_ACTIVE/8/duration, " + pmc_src,
-                            traffic=pmc.get("traffic_bytes"), traffic_unit="bytes/launch, " + pmc_src,
-                            mfma_busy=pmc.get("mfma_busy"),
-                            us_per_launch=ms * 1e3, flops_per_launch=flops,
-                            in_step_us=pmc.get("in_step_us"),
-                            in_step_frac=(flops / (pmc["in_step_us"] * 1e-6) / 1e12 / PEAK_F32_MFMA_TFLOPS
-                                          if pmc.get("in_step_us") else None))
-        else:                                        # LISEC_TUNING=winograd=0: the direct data gradient is the dominant launch
-            tf = flops / (ms_direct * 1e-3) / 1e12
-            roofline = dict(bound="mfma", kernel="k_igemm_halo<1,false,1,2,64,false> mid2 Conv3D 64->64 k3 s1 data gradient", achieved=tf,
-                            peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s", frac=tf / PEAK_F32_MFMA_TFLOPS,
-                            frac_executed=tf / PEAK_F32_MFMA_TFLOPS, executed_share=1.0,
-                            clock_ghz=None, traffic=None, us_per_launch=ms_direct * 1e3, flops_per_launch=flops)
-        # the other large contractions, same clock: mid2 forward, and the dense form of the first Conv3D (the dominant
-        # kernel of rounds 1-2; sweeps beyond LISEC_FIELD_MAX_VOXELS still take it)
-        grid = net.dense_grid()
-        mid1 = next(L for L in net.layers if L["name"] == "mid1")
-        c1 = mid1["conv"]
-        ms_f2 = event_time_ms(lambda: ops.conv_forward(c2.g, net.act["mid1.u"], net.packed[c2.name], net.act["mid2.y"],
-                                                       bias=net.params.view(c2.bias), stats=net.parts), 20)
-        ms_f1 = event_time_ms(lambda: ops.conv_forward(c1.g, grid, net.packed[c1.name], net.act["mid1.y"],
-                                                       bias=net.params.view(c1.bias), stats=net.parts), 10)
-        vout, delta = net.vfe.saved_field("vout"), net.vfe.saved_field("delta")
-        ms_field = event_time_ms(lambda: ops.conv_field_forward(c1.g, vout, delta, net.vfe._sample, net.packed[c1.name],
-                                                                net.act["mid1.y"], net.field_ws,
-                                                                bias=net.params.view(c1.bias)), 20)
-        f1 = 2.0 * c1.M * 27 * 64 * 64
-        roofline["others"] = {
-            "mid2_data_gradient_direct": dict(kernel="k_igemm_halo<1,false,1,2,64,false>", us_per_launch=ms_direct * 1e3,
-                                              achieved=flops / (ms_direct * 1e-3) / 1e12,
-                                              frac=flops / (ms_direct * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=flops,
-                                              note="the direct (implicit-GEMM) form of the same contraction's data gradient: the "
-                                                   "dominant launch of rounds 3-4a, executed == algorithmic"),
-            "mid2_forward_direct": dict(us_per_launch=ms_f2 * 1e3, achieved=flops / (ms_f2 * 1e-3) / 1e12,
-                                        frac=flops / (ms_f2 * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=flops),
-            "mid1_dense_form": dict(us_per_launch=ms_f1 * 1e3, achieved=f1 / (ms_f1 * 1e-3) / 1e12,
-                                    frac=f1 / (ms_f1 * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, flops_per_launch=f1),
-            "mid1_field_form": dict(us_per_call=ms_field * 1e3, launches=2,
-                                    note="what the step runs: k_field_taps + k_field_combine over the VFE's compact output, "
-                                         "same values as mid1_dense_form"),
-        }
-        sample = vox(pts)
-
-        def run_vfe():
-            net.vfe.forward(sample, True, out=grid)
-        ms_v = event_time_ms(run_vfe, 20)
-        hi = sample.host_info()
-        vfe_bytes = 12.0 * len(cloud) + 24.0 * hi["rows"] + 4.0 * 64 * net.D * net.H * net.W
-        ms_vc = event_time_ms(lambda: net.vfe.forward(sample, True, dense=False), 20)
-        vfe_compact_bytes = 12.0 * len(cloud) + 24.0 * hi["rows"] + 2.0 * 256 * (hi["V"] + 1)
-        ms_g = event_time_ms(lambda: net.vfe.rewrite_grid(grid), 50)
-        grid_bytes = 4.0 * 64 * net.D * net.H * net.W
-        gbs = grid_bytes / (ms_g * 1e-3) / 1e9
-        # traffic from the committed PMC passes (WRITE_SIZE + 2 x FETCH_SIZE of k_vfe_grid's launches WITH the dense grid)
-        vfe_pmc = pmc.get("vfe_grid", {})
-        roofline_vfe = dict(bound="hbm", kernel="k_vfe_grid (dense (8,200,400,64) VFE output writer; lisec_vfe_forward with a grid)", achieved=gbs,
-                            peak=PEAK_HBM_GBS, unit="GB/s", frac=gbs / PEAK_HBM_GBS,
-                            traffic=vfe_pmc.get("traffic_bytes"),
-                            traffic_unit="bytes/launch, " + pmc.get("file", "profiles/r*_pmc_dominant.json absent") + " (vfe_grid)",
-                            us_per_launch=ms_g * 1e3, bytes_per_launch=grid_bytes,
-                            whole_vfe_forward=dict(us_per_call=ms_v * 1e3, bytes_per_call=vfe_bytes,
-                                                   achieved=vfe_bytes / (ms_v * 1e-3) / 1e9,
-                                                   frac=vfe_bytes / (ms_v * 1e-3) / 1e9 / PEAK_HBM_GBS,
-                                                   launches=3),
-                            in_step=dict(us_per_call=ms_vc * 1e3, bytes_per_call=vfe_compact_bytes, launches=3,
-                                         note="what the training step runs: the same three launches without the dense "
-                                              "grid (per-voxel outputs only, read by the field form of the first Conv3D); "
-                                              "latency-bound, not an HBM roofline case"))
-        voxelizer = voxelizer_leg(vox, dev, args.no_cpu_baseline)
-        def side_leg(points_np, loss_name, steps=10):
-            """The same step on another sweep / loss pair, `steps` timed steps after 2 warm-up steps."""
-            p2 = torch.from_numpy(points_np).to(dev)
-            if use_plan and _lib.knob("pipeline_voxels", True):
-                from lisec_amd.network import PipelinedStep
-                rec = PipelinedStep(net, vox, len(points_np), dtype=p2.dtype, loss=loss_name)
-                rec.prime(p2, ycls, yreg)
-                rec.stage_next(p2, ycls, yreg)
-                rec.step()
-                rec.stage_next(p2, ycls, yreg)
-                run = rec.step
-            elif use_plan:
-                from lisec_amd.network import RecordedStep
-                rec = RecordedStep(net, vox, len(points_np), dtype=p2.dtype, loss=loss_name)
-                rec.load(p2, ycls, yreg)
-                run = rec.replay
-            else:
-                rec, run = None, (lambda: net.train_step(vox(p2), ycls, yreg, loss=loss_name))
-            for _ in range(2):
-                run()
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(steps):
-                run()
-            torch.cuda.synchronize()
-            d2 = (time.perf_counter() - t1) / steps
-            if rec is not None:
-                rec.close()
-            return dict(value=1.0 / d2, unit="samples/s", ms_per_step=1e3 * d2, points=int(p2.shape[0]),
-                        voxels=vox(p2).host_info()["V"], steps=steps, loss=loss_name)
-        r200k = other_loss = None
-        if args.cloud == "u20k" and world == 1:
-            # real Lyft sweeps are ~200 000 points (model_training.py:116): the same step on the R200k sweep
-            r200k = side_leg(r200k_cloud(rank), args.loss)
-            # the loss pair BASELINE config 4 names, next to the reference's own ['mse','mse'] (model_training.py:296)
-            other = "smoothl1_ce" if args.loss == "mse" else "mse"
-            other_loss = side_leg(cloud, other)
+        voxels = vox(pts).host_info()["V"]
         result = {
             "metric": "lyft_samples_per_sec_fwd_bwd", "value": world * args.steps / dt, "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -556,15 +576,12 @@ def main():
                        "global_batch": world, "parallelism": f"dp{world}", "points_per_sample": int(len(cloud)),
                        "launch": ("step plan (lisec_step_plan_run: %d recorded launches / event edges per step)" % captured.launches)
                                  if use_plan else "Python schedule (one ctypes call per launch)",
-                       "voxels": hi["V"], "final_loss": loss_val},
-            "roofline": roofline, "roofline_vfe": roofline_vfe, "voxelizer": voxelizer, "r200k": r200k,
+                       "voxels": voxels, "final_loss": loss_val},
         }
-        if other_loss is not None:
-            result[other_loss["loss"]] = other_loss
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            result.update(side_measurements(args, net, vox, dev, rank, world, cloud, pts, ycls, yreg, use_plan))
         else:
-            result["cpu_baseline"] = None
+            result.update(roofline=None, roofline_vfe=None, voxelizer=None, r200k=None, cpu_baseline=None)
         print(json.dumps(result), flush=True)
     if dp is not None:
         dp.barrier()

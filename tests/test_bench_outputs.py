@@ -57,3 +57,29 @@ def test_bench_dumps_the_last_timed_step_reproducibly(tmp_path):
         dumps.append(d)
     for n in dumps[0]:
         assert np.array_equal(dumps[0][n], dumps[1][n]), n
+
+
+@pytest.mark.gpu
+def test_bench_full_adds_the_side_measurements():
+    """A plain run prints the headline line with the side measurements null; --full times the same steps and then adds
+    them (rank 0): the rooflines, the voxeliser alone, the R200k and other-loss steps."""
+    lines = {}
+    for mode, extra in (("plain", ()), ("full", ("--full", "--no-cpu-baseline"))):
+        r = _bench("--steps", "3", "--warmup", "1", *extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        got = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1
+        lines[mode] = got[0]
+    p, f = lines["plain"], lines["full"]
+    for j in (p, f):
+        assert j["metric"] == "lyft_samples_per_sec_fwd_bwd" and j["unit"] == "samples/s" and j["dtype"] == "f32"
+        assert j["higher_is_better"] is True and j["steps"] == 3 and j["ms_per_step"] > 0
+    assert all(p[k] is None for k in ("roofline", "roofline_vfe", "voxelizer", "r200k", "cpu_baseline"))
+    assert "smoothl1_ce" not in p
+    assert p["config"]["final_loss"] == f["config"]["final_loss"] and p["config"]["voxels"] == f["config"]["voxels"]
+    assert f["roofline"]["us_per_launch"] > 0 and f["roofline"]["others"]["mid1_dense_form"]["us_per_launch"] > 0
+    assert f["roofline_vfe"]["us_per_launch"] > 0
+    assert f["voxelizer"]["u20k"]["voxels"] == f["config"]["voxels"] and "cpu_restatement" not in f["voxelizer"]
+    assert f["r200k"]["value"] > 0 and f["r200k"]["points"] == 200000
+    assert f["smoothl1_ce"]["loss"] == "smoothl1_ce" and f["smoothl1_ce"]["value"] > 0
+    assert f["cpu_baseline"] is None

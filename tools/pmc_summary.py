@@ -57,7 +57,7 @@ for d in args:
 if dominant_out:
     import json
     out = {"kernel": "k_wino<false,0,1> (mid2 Conv3D forward in the Winograd form, bench.py's roofline launch)",
-           "source": "rocprofv3 --pmc passes of `python bench.py --steps 3 --warmup 2 --no-cpu-baseline`, one counter set per pass "
+           "source": "rocprofv3 --pmc passes of `python bench.py --steps 3 --warmup 2 --full --no-cpu-baseline`, one counter set per pass "
                      "(tools/profile_round.sh), summarised by tools/pmc_summary.py"}
     if "FETCH_SIZE" in dom and "WRITE_SIZE" in dom:
         out["fetch_size_kib"], out["write_size_kib"] = dom["FETCH_SIZE"], dom["WRITE_SIZE"]
