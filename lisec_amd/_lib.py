@@ -295,6 +295,7 @@ def load():
     """Returns the loaded library; raises LisecError when it has not been built."""
     global _lib
     if _lib is None:
+        spec = _tuning_spec()
         if not os.path.exists(LIB_PATH):
             raise LisecError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -302,11 +303,29 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
         _declare(lib)
         _lib = lib
-        spec = os.environ.get("LISEC_TUNING")       # measurement aid: "max_splitk=8,half_n=0" (see set_tuning)
         if spec:
-            set_tuning(**{k.strip(): int(v) for k, v in (kv.split("=") for kv in spec.split(",") if kv.strip())
-                          if k.strip() in dict(Tuning._fields_)})
+            set_tuning(**{k: int(v) for k, v in spec.items() if k not in HOST_KNOBS})
     return _lib
+
+
+# The schedule knobs of the Python host layer (knob()).  Every other key of LISEC_TUNING must be a lisec_tuning field.
+HOST_KNOBS = frozenset(("winograd", "step_plan", "pipeline_voxels", "field_conv", "field_max_voxels", "vfe_bwd_tiled",
+                        "vfe_tiled_min_points", "comm_priority"))
+
+
+def _tuning_spec():
+    """LISEC_TUNING="max_splitk=8,half_n=0,..." (a measurement aid) as a dict.  A key that is neither a host knob nor a
+    lisec_tuning field raises LisecError: a knob that no longer exists would otherwise measure the default silently."""
+    spec = {}
+    for kv in os.environ.get("LISEC_TUNING", "").split(","):
+        if kv.strip():
+            k, _, v = kv.partition("=")
+            spec[k.strip()] = v.strip()
+    unknown = [k for k in spec if k not in HOST_KNOBS and (k not in dict(Tuning._fields_) or k == "struct_bytes")]
+    if unknown:
+        raise LisecError(f"LISEC_TUNING names unknown knob(s) {', '.join(unknown)}: the host layer reads "
+                         f"{', '.join(sorted(HOST_KNOBS))}, the rest are lisec_tuning fields")
+    return spec
 
 
 # Grow-on-demand device buffers (VFE saved state / backward scratch, field workspace, weight-gradient scratch, row-list
@@ -325,15 +344,14 @@ def bump_alloc_generation():
 
 
 def knob(name, default):
-    """Schedule knobs of the Python host layer (measurement aids; the defaults are the measured optimum): read once from
-    the same LISEC_TUNING="key=value,..." string as the library's lisec_tuning record."""
-    spec = os.environ.get("LISEC_TUNING", "")
-    for kv in spec.split(","):
-        if "=" in kv:
-            k, v = kv.split("=", 1)
-            if k.strip() == name:
-                return type(default)(v) if not isinstance(default, bool) else v.strip() not in ("0", "false", "")
-    return default
+    """Schedule knobs of the Python host layer (HOST_KNOBS; the defaults are the measured optimum): read from the same
+    LISEC_TUNING="key=value,..." string as the library's lisec_tuning record."""
+    if name not in HOST_KNOBS:
+        raise KeyError(f"{name!r} is not a host knob (HOST_KNOBS)")
+    v = _tuning_spec().get(name)
+    if v is None:
+        return default
+    return type(default)(v) if not isinstance(default, bool) else v not in ("0", "false", "")
 
 
 def get_tuning():

@@ -392,16 +392,8 @@ class Model:
                     # the whole step (voxelise + forward + backward + update) re-issued from its recorded plan: one C call
                     captured(samples[i]._keepalive, yc, yr)
                 else:
-                    self.net.forward(samples[i], training=True)
-                    if self.dp is not None:
-                        avg = self.dp.bucketed()
-                        self.net.backward(yc, yr, loss=self.loss,
-                                          rpn_grads_ready=lambda lo, hi, avg=avg: avg.start_tail(self.net.grad, lo, hi))
-                        avg.finish(self.net.grad)
-                    else:
-                        self.net.backward(yc, yr, loss=self.loss,
-                                          rpn_grads_ready=lambda lo, hi: self.net.early_update(lo, hi, opt=opt))
-                    self.net.apply_gradients(opt=opt)
+                    self.net.train_step(samples[i], yc, yr, loss=self.loss, opt=opt,
+                                        allreduce=self.dp.bucketed() if self.dp is not None else None)
                 tot_dev += self.net.loss_out
                 if verbose and ((st + 1) % every == 0 or st + 1 == steps):
                     print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / (st + 1):.4f}", end="", flush=True)

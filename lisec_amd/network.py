@@ -230,7 +230,6 @@ class LisecNet:
                                                      if L["kind"] == "deconv" and L["T"] is not None])
         self.parts = torch.empty(max_parts, dtype=torch.float64, device=dev)
         self._sinks, self._bsinks = {}, {}
-        self.early_pack = _lib.knob("pack_early", True)
         # The second HIP stream.  Backward: weight gradients are leaves of the graph and run beside the BN-backward /
         # data-gradient chain (the RPN layers are too small to fill 256 CUs on their own).  Forward and backward: the
         # Conv2DTranspose branches of RPN blocks 1 and 2 (model_training.py:246,249) only meet the rest of the network at the
@@ -241,25 +240,16 @@ class LisecNet:
         # (Round 4: with GPU_MAX_HW_QUEUES=8 -- set when lisec_amd is imported -- a stream of the SAME priority gets a queue
         # of its own, and that is the faster arrangement: the high-priority queue was served first whenever it held a ready
         # packet, which starved the chain during the head phase; one rank through RCCL 5.13 -> 4.25 ms, one GPU +0.8 %.)
-        self.side = torch.cuda.Stream(device=dev, priority=_lib.knob("side_priority", 0))
+        self.side = torch.cuda.Stream(device=dev, priority=0)
 
-        self.branch_overlap = _lib.knob("branch_overlap", True)
         self._tail_ok = {}
-        self._fold_ok = {}
-        # BatchNormalization backward applied on load by the next data gradient: 0 = never (default: measured equal at best),
-        # 1 = on the w-halo kernels of the small maps (see _fold_supported), 2 = everywhere (4 % slower)
-        self.fold_bn_bwd = _lib.knob("fold_bn_bwd", 0)
-        self.early_sgd = _lib.knob("early_sgd", True)           # RPN + head variables updated under the rest of the backward pass
-        self._early_from = None
-        self.dense_wgrad_late = _lib.knob("dense_wgrad_late", True)   # Dense weight gradient behind the block's ring weight gradient
-        self.mid_wgrad_first = _lib.knob("mid_wgrad_first", True)   # ring weight gradient enqueued before the block's data gradient
-        self.pack_mid_first = _lib.knob("pack_mid_first", True)   # the forward waits for the middle blocks' repack only
-        self.dense_dw = _lib.knob("dense_dw", True)
-        self.dense_dw_late = _lib.knob("dense_dw_late", True)   # their slab sums behind the last weight gradient of the second stream      # Dense(64) weight gradients ride on the Dense data gradients
+        self._early = None                               # (lo, OptimizerSpec) of the pending early_update()
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
-        self.fuse_dense_bwd = _lib.knob("fuse_dense_bwd", True)   # Dense(64) data gradients ride on the tile of the block above
-        self.chain_first = _lib.knob("chain_first", True)      # head phase: the chain's contraction is enqueued before the leaves
         self._fwd_events = {}
+        # a repack enqueued on the second stream is pending (_arm_repack, apply_gradients): the forward waits for
+        # _pack_done before its first contraction, for _pack_late before the first reader of the rest
+        self._pack_pending = self._late_pending = False
+        self._pack_done = self._pack_late = None
         self._packed_version = -1
         self.params_version = 0
         self.state_version = 0
@@ -320,12 +310,10 @@ class LisecNet:
         # the first Conv2D of the RPN, ~0.5 ms into the step, waits for all of them (_pack_late)
         self._pack_table.run()
         wino_packs(True)
-        if after_main is not None and self.pack_mid_first:
+        if after_main is not None:
             after_main()
         self._pack_table_rest.run()
         wino_packs(False)
-        if after_main is not None and not self.pack_mid_first:
-            after_main()
         if self.compose_head:
             self._compose_all()
         if self._pack_table_wc is not None:
@@ -435,7 +423,7 @@ class LisecNet:
 
     def _forward(self, sample, training):
         self._mark("step:begin")
-        pending = getattr(self, "_pack_pending", False)
+        pending = self._pack_pending
         if pending and (self._packed_version != (self.params_version, self.params.version)):
             self._wait(self._pack_late, torch.cuda.current_stream())     # variables changed since the early repack
             self._pack_pending = pending = False
@@ -475,7 +463,7 @@ class LisecNet:
                     self._run_conv(L["conv"], a[L["src"]], a[n + ".y"], training)
                 self._run_conv(L["dense"], a[n + ".y"], a[n + ".u"], training)
             elif L["kind"] == "conv":
-                if getattr(self, "_late_pending", False):
+                if self._late_pending:
                     # first reader of a kernel repacked behind the middle blocks' (see _pack_all)
                     self._wait(self._pack_late, torch.cuda.current_stream())
                     self._late_pending = False
@@ -497,12 +485,7 @@ class LisecNet:
                 else:
                     def run(ws_tag, L=L, b=b):
                         self._run_conv(L["conv"], a[L["src"]], a["concat"][:, :, 256 * b:], training, ws_tag=ws_tag)
-                if getattr(self, "_late_pending", False) and not (self.branch_overlap and b < len(DECONVS) - 1):
-                    # first reader on THIS stream of a kernel repacked late on the second one (composite kernels, and the
-                    # transposed set the backward reads)
-                    self._wait(self._pack_late, torch.cuda.current_stream())
-                    self._late_pending = False
-                if self.branch_overlap and b < len(DECONVS) - 1:
+                if b < len(DECONVS) - 1:
                     # an upsampling branch that is not the last: beside the next block, on the second stream
                     main = torch.cuda.current_stream()
                     fork = self._event("fwd_fork%d" % b)
@@ -515,8 +498,13 @@ class LisecNet:
                         _lib.pin_stream(pin)
                     side_used = True
                 else:
+                    if self._late_pending:
+                        # first reader on THIS stream of a kernel repacked late on the second one (composite kernels, and
+                        # the transposed set the backward reads)
+                        self._wait(self._pack_late, torch.cuda.current_stream())
+                        self._late_pending = False
                     run("main")
-        if getattr(self, "_late_pending", False):
+        if self._late_pending:
             self._wait(self._pack_late, torch.cuda.current_stream())
             self._late_pending = False
         if side_used:
@@ -626,26 +614,16 @@ class LisecNet:
         # the stride-1 convolutions of an RPN block (model_training.py:210-214) share ONE weight-gradient launch: maps of
         # 1 250 - 20 000 positions fill a fraction of the chip each, and as leaves of the backward pass they can wait for each
         # other (lisec_conv_wgrad_batched)
-        # BatchNormalization backward folded into the NEXT data gradient's load (fold_bn_bwd): the chain reads the raw
-        # gradient d[dst] and applies the backward on load; the weight gradient (second stream) reads the applied gradient
-        # from a buffer of its own, written by an apply launch on THAT stream -- off the chain
-        self.dyb = {}
-        if self.fold_bn_bwd:
-            for L in self.layers:
-                if L["kind"] == "conv":
-                    self.dyb[L["dst"]] = torch.empty_like(self.dact[L["dst"]])
         self.wgrad_batches = {}
-        if _lib.knob("wgrad_batch", True):
-            for b in range(len(RPN_BLOCKS)):
-                convs = [L for L in self.layers if L["kind"] == "conv" and L["name"].startswith(f"rpn{b+1}.conv")
-                         and L["name"] != f"rpn{b+1}.conv0"]
-                items = [(L["conv"].g, self.act[L["src"]], self.dyb.get(L["dst"], self.dact[L["dst"]]),
-                          p.grad_view(self.grad, L["conv"].wname), self.bnstate[L["conv"].in_bn], ops.IN_RELU, False)
-                         for L in convs]
-                if 2 <= len(items) <= 6:
-                    batch = ops.WgradBatch(items)
-                    ws_bytes = max(ws_bytes, batch.workspace_bytes())
-                    self.wgrad_batches[convs[0]["name"]] = (batch, {L["name"] for L in convs})
+        for b in range(len(RPN_BLOCKS)):
+            convs = [L for L in self.layers if L["kind"] == "conv" and L["name"].startswith(f"rpn{b+1}.conv")
+                     and L["name"] != f"rpn{b+1}.conv0"]
+            items = [(L["conv"].g, self.act[L["src"]], self.dact[L["dst"]], p.grad_view(self.grad, L["conv"].wname),
+                      self.bnstate[L["conv"].in_bn], ops.IN_RELU, False) for L in convs]
+            if 2 <= len(items) <= 6:
+                batch = ops.WgradBatch(items)
+                ws_bytes = max(ws_bytes, batch.workspace_bytes())
+                self.wgrad_batches[convs[0]["name"]] = (batch, {L["name"] for L in convs})
         # zero-filled: the head of the workspace holds the arrival counters of the slab-combining kernels
         self.wgrad_ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
         # weight gradients of the Conv3D blocks behind the first in the Winograd form (winograd bit 3): one slab workspace for
@@ -657,14 +635,14 @@ class LisecNet:
             if mids:
                 shared = torch.empty(max(ops.wgrad_winograd_workspace_bytes(c.g) for c in mids), dtype=torch.uint8, device=dev)
                 self.wino_wgrad_ws = {c.name: shared for c in mids}
-        # Dense(64) weight gradients carried by the Dense data gradients (dense_dw): one slab buffer per middle block -- the sum
-        # runs on the second stream, possibly after the next block's data gradient has started writing its own
+        # Dense(64) weight gradients carried by the Dense data gradients (lisec_conv_extras.dense_dw): one slab buffer per
+        # middle block -- the sum runs on the second stream, possibly after the next block's data gradient has started
+        # writing its own
         self.dense_dw_slabs = {}
-        if self.dense_dw:
-            nslabs = ops.dense_dw_slabs()
-            for L in self.layers:
-                if L["kind"] == "mid" and (L["conv"].M + 127) // 128 >= nslabs:
-                    self.dense_dw_slabs[L["name"]] = torch.empty(nslabs * 4096, dtype=torch.float32, device=dev)
+        nslabs = ops.dense_dw_slabs()
+        for L in self.layers:
+            if L["kind"] == "mid" and (L["conv"].M + 127) // 128 >= nslabs:
+                self.dense_dw_slabs[L["name"]] = torch.empty(nslabs * 4096, dtype=torch.float32, device=dev)
         self._packed_t_version = -1
         self._train_ready = True
 
@@ -718,42 +696,12 @@ class LisecNet:
         finally:
             _lib.pin_stream(prev_pin)
 
-    def _fold_supported(self, c, dst):
-        """Does the data gradient of conv `c` take the BatchNormalization backward of its input gradient on load?  (asked of
-        the library once per layer)"""
-        ok = self._fold_ok.get(c.name)
-        if ok is None:
-            try:
-                sink = self._bwd_sink(c.bn, c.g.Cout, c.M)
-                plan = ops.conv_plan(self.dgeom[c.name], fold=(self.act[dst], self.bnstate[c.bn], sink.coef, True))
-                # measured per layer (tools/phase_times.py, round 4): the fold pays where the A tile is staged once per three
-                # K steps (w-halo kernels of the small maps: -3.5 us per layer); on the generic gather (a second operand
-                # load in EVERY step of a lone wave) and on the 3-per-CU kernels it costs 4 - 44 us per layer
-                ok = self.fold_bn_bwd == 2 or (plan["kernel"] == "halo3" and plan["double_buffered"] == 1)
-            except _lib.LisecError:
-                ok = False
-            self._fold_ok[c.name] = ok
-        return ok
-
-    def _tail_supported(self, c, dst_name, winograd=False):
-        """Can the Dense data gradient of block dst_name[:-2] ride on the data gradient of conv `c`?  (asked of the library
-        once per layer: lisec_conv_plan_query refuses geometries the two-line w-halo kernel does not serve;
-        lisec_conv_winograd_supported answers for the Winograd form)"""
-        ok = self._tail_ok.get((c.name, winograd))
-        if ok is None and winograd:
-            # (LISEC_TUNING winograd_tail: the tail on the Winograd epilogue is built and parity-tested
-            # (tests/test_gpu_winograd.py) and measured 0.5 % SLOWER in the step than the separate HBM-bound Dense launch,
-            # which hides beside the MFMA-bound weight gradients of the second stream: off)
-            n = dst_name[:-2]
-            Ln = {L["name"]: L for L in self.layers}.get(n)
-            ok = False
-            if Ln is not None and "dense" in Ln and self.dgeom[c.name].Cout == 64 and _lib.knob("winograd_tail", False):
-                cn, dn = Ln["conv"], Ln["dense"]
-                ok = ops.winograd_supported(self.dgeom[c.name], out_mask=self.act[dst_name],
-                                            bwd=(self.act[n + ".y"], self.bnstate[cn.bn], False),
-                                            sink=self._bwd_sink(cn.bn, 64, cn.M),
-                                            tail=(self.packed_t[dn.name][0], self.dact[n + ".z"]))
-            self._tail_ok[(c.name, winograd)] = ok
+    def _tail_supported(self, c, dst_name):
+        """Can the Dense data gradient of block dst_name[:-2] ride on the direct data gradient of conv `c`?  (asked of the
+        library once per layer: lisec_conv_plan_query refuses geometries the two-line w-halo kernel does not serve.  The
+        Winograd form can carry it too (ops.conv_forward_winograd(tail=)), measured 0.5 % slower in the step than the
+        separate HBM-bound Dense launch, which hides beside the MFMA-bound weight gradients of the second stream)"""
+        ok = self._tail_ok.get(c.name)
         if ok is None:
             n = dst_name[:-2]
             Ln = {L["name"]: L for L in self.layers}.get(n)
@@ -767,7 +715,7 @@ class LisecNet:
                     ok = True
                 except _lib.LisecError:
                     ok = False
-            self._tail_ok[(c.name, winograd)] = ok
+            self._tail_ok[c.name] = ok
         return ok
 
     def _backward(self, y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler=None):
@@ -825,15 +773,10 @@ class LisecNet:
                 _lib.pin_stream(pin)
                 del pending[:]
 
-        skip_leaves = _lib.knob("skip_leaves", False)      # measurement aid (WRONG gradients): the chain alone
-
         def on_side(fn, torch_ops=False):
             """Runs fn's launches on the second stream after everything issued so far on the main one.  C-ABI launches
             take the pinned handle; only a fn that also issues torch / torch.distributed work needs torch's (slow)
             stream context."""
-            if skip_leaves and not torch_ops:
-                flush_side()
-                return
             pending.append((fn, torch_ops))
             flush_side()
 
@@ -869,8 +812,7 @@ class LisecNet:
             self._dshuffle.run(d["head"], backward=True)
             # (queued, not flushed: the leaves and branches that hang off the head gradient cross to the second stream
             # behind ONE event, with the first of them that is issued through on_side below)
-            if not skip_leaves:
-                pending.append((lambda: ops.colsum(d["head"], 16, M, 16, self.head_db, ws_tag="side"), False))
+            pending.append((lambda: ops.colsum(d["head"], 16, M, 16, self.head_db, ws_tag="side"), False))
         else:
             on_side(head_leaves)
             ops.conv_forward(self.head_dgeom, d["head"], self.packed_t["head"][0], d["concat"])
@@ -886,9 +828,9 @@ class LisecNet:
 
         early_dst = {}                         # gradient buffer -> event behind a contribution made on the second stream
         fused_dense = {}                       # middle block -> backward sink of a Dense data gradient that rode on a tile
-        late_reduces = []                      # slab sums of the carried Dense weight gradients (dense_dw_late)
+        late_reduces = []                      # slab sums of the carried Dense weight gradients
 
-        def dgrad_into(c, dy, dst_name, ws_tag="main", fold=None):
+        def dgrad_into(c, dy, dst_name, ws_tag="main"):
             ev = early_dst.pop(dst_name, None) if ws_tag == "main" else None
             if ev is not None:
                 self._wait(ev, main)           # the branch's contribution is stored before this one accumulates onto it
@@ -904,8 +846,8 @@ class LisecNet:
                 bn_name, C = self.bn_of[dst_name]
                 bwd, sink = (a[dst_name], self.bnstate[bn_name], True), self._bwd_sink(bn_name, C, a[dst_name].numel() // C)
                 bwd_ready[dst_name] = sink
-            use_w = c.name in self.packed_wu_t and fold is None
-            if mask is not None and self.fuse_dense_bwd and self._tail_supported(c, dst_name, use_w):
+            use_w = c.name in self.packed_wu_t
+            if mask is not None and not use_w and self._tail_supported(c, dst_name):
                 # the Dense(64, relu) of the block BELOW (model_training.py:195) rides on this tile: its data gradient
                 # dz = (gated gradient) @ Wd^T and the statistics of the BatchNormalization under it come out of the same
                 # launch (lisec_conv_extras.tail_w); the separate Dense data-gradient launch is skipped further down
@@ -921,7 +863,7 @@ class LisecNet:
                                           out_mask=mask, bwd=bwd, sink=sink, tail=tail)
             else:
                 ops.conv_forward(self.dgeom[c.name], dy, self.packed_t[c.name][0], d[dst_name], flags=flags, out_mask=mask,
-                                 bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail, fold=fold)
+                                 bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail)
             first_write.add(dst_name)
 
         def branch_dy(L):
@@ -957,20 +899,19 @@ class LisecNet:
         # their gradients go to the second stream at once, beside the small layers of blocks 3 and 2, instead of waiting
         # on the chain for their turn; the chain picks their contribution up where it reaches the block's last conv
         early_layers = set()
-        if self.branch_overlap:
-            for L in layers:
-                if L["kind"] == "deconv" and L["slot"] < len(DECONVS) - 1:
-                    ev = self._event("bwd_branch%d" % L["slot"])
+        for L in layers:
+            if L["kind"] == "deconv" and L["slot"] < len(DECONVS) - 1:
+                ev = self._event("bwd_branch%d" % L["slot"])
 
-                    def branch(L=L, ev=ev):
-                        deconv_wgrad(L)
-                        dgrad_into(L["conv"], branch_dy(L), L["src"], ws_tag="side")
-                        self._record(ev, self.side)
-                    pending.append((branch, False))
-                    if not self.compose_head:
-                        flush_side()
-                    early_dst[L["src"]] = ev
-                    early_layers.add(L["name"])
+                def branch(L=L, ev=ev):
+                    deconv_wgrad(L)
+                    dgrad_into(L["conv"], branch_dy(L), L["src"], ws_tag="side")
+                    self._record(ev, self.side)
+                pending.append((branch, False))
+                if not self.compose_head:
+                    flush_side()
+                early_dst[L["src"]] = ev
+                early_layers.add(L["name"])
 
         for L in reversed(layers):
             c = L["conv"]
@@ -978,46 +919,27 @@ class LisecNet:
             if L["kind"] == "deconv":
                 if L["name"] in early_layers:
                     continue
-                if self.chain_first:
-                    # the chain's contraction goes into its queue BEFORE the leaves that hang off the same gradient: the
-                    # second stream's queue is served first (priority) and its kernels fill every CU's LDS, so a chain
-                    # kernel enqueued behind them waited for the whole leaf sequence (r03 timeline: 214 us)
-                    mark_fork()
-                    dgrad_into(c, branch_dy(L), L["src"])
-                    on_side(lambda L=L: deconv_wgrad(L))
-                else:
-                    on_side(lambda L=L: deconv_wgrad(L))
+                # the chain's contraction goes into its queue BEFORE the leaves that hang off the same gradient: the
+                # second stream's queue is served first (priority) and its kernels fill every CU's LDS, so a chain
+                # kernel enqueued behind them waited for the whole leaf sequence (r03 timeline: 214 us)
+                mark_fork()
+                dgrad_into(c, branch_dy(L), L["src"])
+                on_side(lambda L=L: deconv_wgrad(L))
                 if side_filler is not None:
                     pending.append((side_filler, False))
                     flush_side()
                     side_filler = None
-                if not self.chain_first:
-                    dgrad_into(c, branch_dy(L), L["src"])
             elif L["kind"] == "conv":
                 dst = L["dst"]
                 C = c.g.Cout
                 is_first_rpn = L["name"] == "rpn1.conv0"
-                fold = None
-                grad_w = d[dst]                        # what the weight gradient of this layer contracts against
-                if dst in bwd_ready and self.fold_bn_bwd and dst in self.dyb and self._fold_supported(c, dst):
-                    # dgamma / dbeta / coefficients were finalised inside the data-gradient call that stored d[dst]; the apply
-                    # pass rides on the load of this layer's data gradient (no launch on the chain), and runs as a launch of
-                    # the second stream into a buffer of its own for the weight gradient
-                    coef = bwd_ready.pop(dst).coef
-                    fold = (a[dst], self.bnstate[c.bn], coef, True)
-                    grad_w = self.dyb[dst]
-                    if not skip_leaves:
-                        pending.append((lambda dst=dst, C=C, c=c, coef=coef, grad_w=grad_w: ops.bn_backward_apply_coef(
-                            d[dst], C, a[dst], self.bnstate[c.bn], c.M, C, True, coef, grad_w), False))
-                elif dst in bwd_ready:
+                if dst in bwd_ready:
+                    # dgamma / dbeta / coefficients were finalised inside the data-gradient call that stored d[dst]
                     ops.bn_backward_apply_coef(d[dst], C, a[dst], self.bnstate[c.bn], c.M, C, True,
                                                bwd_ready.pop(dst).coef, d[dst])
                 else:
                     ops.bn_backward(d[dst], C, a[dst], self.bnstate[c.bn], c.M, C, True,
                                     p.grad_view(G, c.bn + ".gamma"), p.grad_view(G, c.bn + ".beta"), d[dst])
-                if fold is None and dst in self.dyb and L["name"] in batched_convs:
-                    # (the batched weight gradients were built over the dyb buffers: hand them the gradient applied in place)
-                    pending.append((lambda dst=dst: self.dyb[dst].copy_(d[dst]), True))
                 # the bias of a conv feeding a training-mode BN has gradient sum(dy) == 0 identically (BN removes
                 # the mean); Keras' autograd returns rounding noise there -- the exact 0 stays in self.grad
                 if L["name"] in batched_convs:
@@ -1026,13 +948,13 @@ class LisecNet:
                     if L["name"] in self.wgrad_batches:
                         on_side(lambda batch=self.wgrad_batches[L["name"]][0]: batch.run(self.wgrad_ws))
                 else:
-                    on_side(lambda L=L, c=c, grad_w=grad_w: ops.conv_wgrad(
-                        c.g, a[L["src"]], grad_w, p.grad_view(G, c.wname), self.wgrad_ws,
+                    on_side(lambda L=L, c=c, dst=dst: ops.conv_wgrad(
+                        c.g, a[L["src"]], d[dst], p.grad_view(G, c.wname), self.wgrad_ws,
                         in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=ops.IN_RELU if c.in_relu else 0))
                 if is_first_rpn and rpn_grads_ready is not None:
                     lo = p.offsets["rpn1.conv0.kernel"][1]
                     on_side(lambda lo=lo: rpn_grads_ready(lo, p.n_theta), torch_ops=True)
-                dgrad_into(c, d[dst], L["src"], fold=fold)
+                dgrad_into(c, d[dst], L["src"])
                 if L["src"] == "fold":
                     # back through Permute + Reshape, gated by the ReLU of the last middle block's Dense (:195)
                     ops.fold_depth(d["fold"], d[self.fold_src], self.dprime, self.H * self.W, 64, inverse=True,
@@ -1043,9 +965,10 @@ class LisecNet:
                                                              self.wgrad_ws, in_bn=self.bnstate[dn.in_bn])
                 # the Dense weight gradient (HBM-bound, 52 granules of LDS) finds no room beside three data-gradient
                 # workgroups per CU and waited 474 us in the queue IN FRONT of the block's ring weight gradient: behind it
-                # (dense_wgrad_late) the ring kernel starts as soon as its gradient exists
-                late_dense = self.dense_wgrad_late and self.mid_wgrad_first and L["src"] != "grid"
-                # the Dense data gradient below reads both operands of the Dense weight gradient: it carries it (dense_dw)
+                # the ring kernel starts as soon as its gradient exists
+                late_dense = L["src"] != "grid"
+                # the Dense data gradient below reads both operands of the Dense weight gradient: it carries it
+                # (lisec_conv_extras.dense_dw)
                 carried = n not in fused_dense and n in self.dense_dw_slabs
                 if carried:
                     late_dense = False
@@ -1060,14 +983,11 @@ class LisecNet:
                                      bwd=(a[n + ".y"], self.bnstate[c.bn], False), sink=msink,
                                      dense_dw=self.dense_dw_slabs[n] if carried else None)
                     if carried:
-                        reduce = lambda n=n, dn=dn: ops.dense_dw_reduce(self.dense_dw_slabs[n], p.grad_view(G, dn.wname))
                         # the 8 MB slab sum finds no registers beside the Winograd workgroups (46 - 60 us in the step for 6 us of
                         # work) and the second stream is in order: enqueued right here it held the block's weight gradient back;
                         # nothing reads the result before the optimizer, so the three sums go behind the last weight gradient
-                        if self.dense_dw_late:
-                            late_reduces.append(reduce)
-                        else:
-                            on_side(reduce)
+                        late_reduces.append(lambda n=n, dn=dn: ops.dense_dw_reduce(self.dense_dw_slabs[n],
+                                                                                   p.grad_view(G, dn.wname)))
                 if L["src"] != "grid":
                     ops.bn_backward_apply_coef(d[n + ".z"], 64, a[n + ".y"], self.bnstate[c.bn], c.M, 64, False, msink.coef,
                                                d[n + ".z"])
@@ -1092,10 +1012,8 @@ class LisecNet:
                     ops.conv_forward(dg, d[n + ".z"], self.packed_t[c.name][0], self.dout_rows, rows=rows,
                                      queue=self.rows_queue)
                 else:
-                    # the data gradient FIRST, the weight gradient behind it on the second stream: both fill the chip
-                    # on their own and run slower side by side than one after the other (mid2: 800 us together,
-                    # 333 + 358 alone); behind the data gradient the weight gradient shares the chip with the
-                    # short kernels of the rest of the chain instead
+                    # the weight gradient (second stream) is enqueued BEFORE the block's data gradient: measured 1 % faster
+                    # than the other order
                     if c.name in self.wino_wgrad_ws:
                         # Winograd-domain weight gradient (csrc/wino_wgrad.hip): 4 / 9 of the ring kernel's MFMAs
                         wg = lambda L=L, c=c, n=n: ops.conv_wgrad_winograd(c.g, a[L["src"]], d[n + ".z"],
@@ -1103,15 +1021,11 @@ class LisecNet:
                     else:
                         wg = lambda L=L, c=c, n=n: ops.conv_wgrad(c.g, a[L["src"]], d[n + ".z"], p.grad_view(G, c.wname),
                                                                   self.wgrad_ws)
-                    if self.mid_wgrad_first:
-                        on_side(wg)
-                        if late_dense:
-                            pending.append((dense_wg, False))
-                            flush_side()
-                        dgrad_into(c, d[n + ".z"], L["src"])
-                    else:
-                        dgrad_into(c, d[n + ".z"], L["src"])
-                        on_side(wg)
+                    on_side(wg)
+                    if late_dense:
+                        pending.append((dense_wg, False))
+                        flush_side()
+                    dgrad_into(c, d[n + ".z"], L["src"])
         # ---- VFE -----------------------------------------------------------------------------------
         self._mark("bwd:before vfe")
         for fn in late_reduces:
@@ -1157,40 +1071,46 @@ class LisecNet:
             ops.sgd_step_dev(th, g, sl[0] if sl else None, opt.lr, opt.decay, opt.momentum, opt.nesterov, self._iter_dev,
                              advance=advance)
 
-    def early_update(self, lo, hi, lr=0.01, decay=1e-6, momentum=0.9, opt=None):
-        """SGD-Nesterov (or `opt`, an OptimizerSpec) of theta[lo:hi] AHEAD of the rest of the step (backward's
-        rpn_grads_ready hook, on the second stream): the RPN + head variables -- 94 % of the parameters -- have final gradients while the middle layers and the VFE are
-        still being differentiated, and nothing in the rest of the backward pass reads theta itself (the contractions read
-        the packed copies), so their 26 MB update runs under the MFMA-bound kernels instead of at the serial end of the
-        step.  Elementwise, hence the same values whichever call updates an element -- for every optimizer of
-        OptimizerSpec, as both calls read the same iteration count: this one on the second stream, which the main stream
-        joins before apply_gradients() updates theta[:lo] and advances the count."""
-        if not self.early_sgd or lo % 4 or hi != self.params.n_theta:
+    def early_update(self, lo, hi, opt=None):
+        """`opt` (an OptimizerSpec; None: the reference's SGD-Nesterov) of theta[lo:hi] AHEAD of the rest of the step
+        (backward's rpn_grads_ready hook, on the second stream): the RPN + head variables -- 94 % of the parameters -- have
+        final gradients while the middle layers and the VFE are still being differentiated, and nothing in the rest of the
+        backward pass reads theta itself (the contractions read the packed copies), so their 26 MB update runs under the
+        MFMA-bound kernels instead of at the serial end of the step.  Elementwise, hence the same values whichever call
+        updates an element -- for every optimizer of OptimizerSpec, as both calls read the same iteration count: this one
+        on the second stream, which the main stream joins before apply_gradients() updates theta[:lo] and advances the
+        count.  The update stays pending until that apply_gradients(), which must be given the same spec; a second early
+        update before it raises RuntimeError."""
+        if self._early is not None:
+            raise RuntimeError("early_update() while an early update is pending: apply_gradients() ends the step first")
+        if lo % 4 or hi != self.params.n_theta:
             return
-        opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
-        n = (hi - lo) // 4 * 4
-        self._update(opt, lo, lo + n, advance=False)
-        self._early_from = lo
+        opt = OptimizerSpec() if opt is None else opt
+        self._update(opt, lo, lo + (hi - lo) // 4 * 4, advance=False)
+        self._early = (lo, opt)
 
-    def apply_gradients(self, lr=0.01, decay=1e-6, momentum=0.9, opt=None):
-        """optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295), or `opt` (an
-        OptimizerSpec: the same one early_update() was given in this step)."""
+    def apply_gradients(self, opt=None):
+        """`opt` (an OptimizerSpec; None: optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True),
+        model_training.py:295) of every variable that early_update() did not update in this step.  Raises RuntimeError,
+        before any launch, when the pending early update was made with another spec."""
+        opt = OptimizerSpec() if opt is None else opt
+        hi = self.params.theta.numel()
+        if self._early is not None:
+            lo, early_opt = self._early
+            if early_opt != opt:
+                raise RuntimeError(f"apply_gradients(opt={opt}) after an early update with {early_opt}: the variables "
+                                   f"would be updated by two different optimizers")
+            hi = lo                              # the tail of the buffer was updated during the backward pass
+            self._early = None
         # lr_t = lr / (1 + decay * iterations), derived on the device from its own iteration counter
-        opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
-        lo = getattr(self, "_early_from", None)
-        self._early_from = None
-        if lo is not None:
-            # the tail of the buffer was updated by early_update() during the backward pass
-            self._update(opt, 0, lo, advance=True)
-        else:
-            self._update(opt, 0, self.params.theta.numel(), advance=True)
+        self._update(opt, 0, hi, advance=True)
         self._mark("step:updated")
         self._iterations += 1
         self.params_version += 1
-        if self._train_ready and self.early_pack:
+        if self._train_ready:
             # both repacks (forward and transposed layouts, ~75 us) for the NEXT step go to the second stream now: they
             # only depend on this update, and the next sweep's voxeliser + VFE (~105 us) do not read them
-            if getattr(self, "_pack_done", None) is None:
+            if self._pack_done is None:
                 self._pack_fork, self._pack_done, self._pack_late = self._new_event(), self._new_event(), self._new_event()
             self._record(self._pack_fork, torch.cuda.current_stream())
             self._wait(self._pack_fork, self.side)
@@ -1204,20 +1124,44 @@ class LisecNet:
             self._pack_pending = True
             self._late_pending = True
 
-    def train_step(self, sample, y_cls, y_reg, loss="mse", allreduce=None):
-        """One fit() step at batch_size=1: forward (batch statistics) + backward + SGD-Nesterov.
-        allreduce: optional callable(grad) that averages the flat gradient across data-parallel ranks."""
+    def _arm_repack(self):
+        """Repacks the variables now, on the current stream, and arms the two events the forward of a recorded step waits
+        for (a step plan holds no repack of its own: the update of the step before left one pending)."""
+        self._pack_pending = self._late_pending = False
+        self._pack_all()
+        self._pack_all_t()
+        self._record(self._pack_done, torch.cuda.current_stream())
+        self._record(self._pack_late, torch.cuda.current_stream())
+        self._pack_pending = self._late_pending = True
+
+    def _replayed(self):
+        """Host bookkeeping of one replayed step plan: the update advanced the iteration count and moved theta, and the plan
+        also repacked theta for the next step."""
+        self._iterations += 1
+        self.params_version += 1
+        self.state_version += 1
+        self._packed_version = self._packed_t_version = (self.params_version, self.params.version)
+        self._pack_pending = self._late_pending = True
+
+    def train_step(self, sample, y_cls, y_reg, loss="mse", allreduce=None, opt=None, side_filler=None):
+        """One fit() step at batch_size=1: forward (batch statistics) + backward + the update by `opt` (an OptimizerSpec;
+        None: the reference's SGD-Nesterov).  side_filler: see backward().
+        allreduce: optional data-parallel gradient average -- with start_tail (parallel._BucketedAverage) in two buckets,
+        otherwise a callable(grad) run after the backward pass."""
         self.forward(sample, training=True)
         if allreduce is not None and hasattr(allreduce, "start_tail"):
             # two buckets: the RPN + head gradients (the tail of theta) are reduced under the rest of the backward
-            self.backward(y_cls, y_reg, loss=loss, rpn_grads_ready=lambda lo, hi: allreduce.start_tail(self.grad, lo, hi))
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler,
+                          rpn_grads_ready=lambda lo, hi: allreduce.start_tail(self.grad, lo, hi))
             allreduce.finish(self.grad)
         elif allreduce is not None:
-            self.backward(y_cls, y_reg, loss=loss)
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler)
             allreduce(self.grad)
         else:
-            self.backward(y_cls, y_reg, loss=loss, rpn_grads_ready=lambda lo, hi: self.early_update(lo, hi))
-        self.apply_gradients()
+            # one rank: the RPN + head variables are updated under the rest of the backward
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler,
+                          rpn_grads_ready=lambda lo, hi: self.early_update(lo, hi, opt=opt))
+        self.apply_gradients(opt=opt)
         return self.loss_out
 
 
@@ -1225,48 +1169,136 @@ class StalePlanError(RuntimeError):
     """A recorded step plan holds raw addresses of buffers that an eager call has since reallocated."""
 
 
-def _check_plan_fresh(step):
-    if step.alloc_gen != _lib.alloc_generation():
-        raise StalePlanError(
-            "this step plan was recorded before a workspace of the network / VFE / voxeliser was reallocated (an eager "
-            "call on a larger sweep or grid): replaying it would write through freed addresses.  Record a new one "
-            "(Model.fit does so by itself).")
+class _StepPlans:
+    """What RecordedStep and PipelinedStep share: `nbuf` sets of (points, targets, voxel sample) buffers and one step plan
+    recorded per set, the eager warm-up and recording steps (LisecNet.train_step), the replay and its bookkeeping.  The
+    two differ in the number of sets and in where a step voxelises its sweep (_voxelise)."""
+
+    PAD = 1.0e6          # metres: floor(1e6 / 0.5) is far beyond maxVoxelX, the point is dropped like any other outlier
+
+    def __init__(self, net, voxelizer, capacity, nbuf, dtype, loss, warmup, allreduce, opt):
+        import ctypes
+        self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
+        # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
+        # lisec_allreduce_grads and its event edges record themselves, a torch.distributed exchange rides as host calls.
+        # Every rank records and replays the same sequence (the warm-up and recording steps exchange gradients for real).
+        self.allreduce = allreduce
+        dev = net.device
+        self.lib = _lib.load()
+        self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(nbuf)]
+        self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        self.opt = OptimizerSpec() if opt is None else opt      # the optimizer of the recorded step
+        self.stream_handle = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize(dev)
+        net._prepare_training()
+        for name in self.opt.slots:
+            net.slot(name)                       # made before the plan records their addresses
+        keep = self._snapshot()
+        self.samples = [self.vox(pts) for pts in self.points]
+        # eager warm-up (lazy workspaces, descriptor tables, events; it leaves the next step's repack pending, which is
+        # the state every recorded step starts from), then one more step per buffer set that is recorded while it runs
+        for k in range(nbuf * max(1, warmup)):
+            self._enqueue(k % nbuf)
+        torch.cuda.synchronize(dev)
+        self.plans = []
+        for j in range(nbuf):
+            plan = ctypes.c_void_p()
+            _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(plan)))
+            self.plans.append(plan)
+            _lib.check(self.lib.lisec_step_plan_begin(plan))
+            try:
+                self._enqueue(j)
+            finally:
+                _lib.check(self.lib.lisec_step_plan_end(plan))
+        torch.cuda.synchronize(dev)
+        self.launches = self.lib.lisec_step_plan_size(self.plans[0])
+        # those steps trained on the padding: put every variable back and repack the kernels from them
+        self._restore(keep)
+        net.params_version += 1
+        net.state_version += 1
+        net.params.touch()
+        net._arm_repack()
+        self.cur = 0
+        torch.cuda.synchronize(dev)
+        self.alloc_gen = _lib.alloc_generation()
+
+    def _snapshot(self):
+        """The variables, BN state, every optimizer slot and the iteration count, before the warm-up / recording steps."""
+        net, p = self.net, self.net.params
+        return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
+                net._iterations)
+
+    def _restore(self, keep):
+        net, p = self.net, self.net.params
+        p.theta.copy_(keep[0])
+        p.state.copy_(keep[1])
+        for k, t in keep[2].items():
+            net.slot(k).copy_(t)
+        net._iter_dev.copy_(keep[3])
+        net._iterations = keep[4]
+
+    def _voxelise(self, j):
+        """The voxelisation of buffer set j's step: issued here, or returned as the side_filler of its backward pass."""
+        raise NotImplementedError
+
+    def _enqueue(self, j):
+        """One eager step on buffer set j (warm-up, or recorded while it runs)."""
+        self.net.train_step(self.samples[j], self.ycls[j], self.yreg[j], loss=self.loss, allreduce=self.allreduce,
+                            opt=self.opt, side_filler=self._voxelise(j))
+
+    def _check_stream(self):
+        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
+            raise RuntimeError(f"a {type(self).__name__} replays on the stream it was recorded on: make that stream current")
+
+    def _load(self, j, points, ycls, yreg):
+        """Stages one sweep into buffer set j: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets
+        (Ho,Wo,2|14)."""
+        pts = torch.as_tensor(points)
+        n = int(pts.shape[0])
+        if n > self.capacity:
+            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
+        self.points[j][:n].copy_(pts[:, :3], non_blocking=True)
+        if n < self.capacity:
+            self.points[j][n:].fill_(self.PAD)
+        self.ycls[j].copy_(torch.as_tensor(ycls).reshape(self.ycls[j].shape), non_blocking=True)
+        self.yreg[j].copy_(torch.as_tensor(yreg).reshape(self.yreg[j].shape), non_blocking=True)
+
+    def _run(self):
+        """Replays the plan of the current buffer set; returns net.loss_out (device, [total, class, regression])."""
+        if self.alloc_gen != _lib.alloc_generation():
+            raise StalePlanError(
+                "this step plan was recorded before a workspace of the network / VFE / voxeliser was reallocated (an eager "
+                "call on a larger sweep or grid): replaying it would write through freed addresses.  Record a new one "
+                "(Model.fit does so by itself).")
+        net = self.net
+        cur = (net.params_version, net.params.version)
+        if net._packed_version != cur or net._packed_t_version != cur or not net._pack_pending:
+            # the variables were changed since the last step (params.load_dict / touch, an eager step): the recorded
+            # forward contains no repack, so it is made now on the replay stream
+            net._arm_repack()
+        _lib.check(self.lib.lisec_step_plan_run(self.plans[self.cur]))
+        net._replayed()
+        for s_ in self.samples:
+            s_._host_info = None
+        self.cur = (self.cur + 1) % len(self.plans)
+        return net.loss_out
+
+    def close(self):
+        if getattr(self, "plans", None):
+            torch.cuda.synchronize(self.net.device)
+            for plan in self.plans:
+                self.lib.lisec_step_plan_destroy(plan)
+            self.plans = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
-def _sync_packed(net):
-    """The recorded forward contains no repack (the previous step's update left one pending).  If the variables were
-    changed since (params.load_dict / touch, an eager step), repack them now on the replay stream and re-arm the two events
-    the recorded forward waits for."""
-    cur = (net.params_version, net.params.version)
-    if net._packed_version != cur or net._packed_t_version != cur or not getattr(net, "_pack_pending", False):
-        net._pack_pending = False
-        net._late_pending = False
-        net._pack_all()
-        net._pack_all_t()
-        net._record(net._pack_done, torch.cuda.current_stream())
-        net._record(net._pack_late, torch.cuda.current_stream())
-        net._pack_pending = True
-        net._late_pending = True
-
-
-def _snapshot(net):
-    """The variables, BN state, every optimizer slot and the iteration count, before the warm-up / recording steps."""
-    p = net.params
-    return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
-            net._iterations)
-
-
-def _restore(net, keep):
-    p = net.params
-    p.theta.copy_(keep[0])
-    p.state.copy_(keep[1])
-    for k, t in keep[2].items():
-        net.slot(k).copy_(t)
-    net._iter_dev.copy_(keep[3])
-    net._iterations = keep[4]
-
-
-class RecordedStep:
+class RecordedStep(_StepPlans):
     """One whole fit() step -- voxelise, forward, backward (both streams, fork / join events included), the optimizer
     update (opt: an OptimizerSpec, SGD-Nesterov by default), the weight repack for the next step -- recorded ONCE as a
     step plan of the C ABI (lisec_step_plan_*, csrc/plan.hip) and re-issued by one C call per step: the ~250 launches
@@ -1285,128 +1317,29 @@ class RecordedStep:
     Record and replay on ONE torch stream (the current stream at construction).  Data parallel (allreduce=): the gradient
     exchange is part of the plan."""
 
-    PAD = 1.0e6          # metres: floor(1e6 / 0.5) is far beyond maxVoxelX, the point is dropped like any other outlier
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
+        super().__init__(net, voxelizer, capacity, 1, dtype, loss, warmup, allreduce, opt)
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", lr=0.01, decay=1e-6, momentum=0.9,
-                 warmup=2, allreduce=None, opt=None):
-        import ctypes
-        self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
-        # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
-        # lisec_allreduce_grads and its event edges record themselves, a torch.distributed exchange rides as host calls.
-        # Every rank records and replays the same sequence (the warm-up and recording steps exchange gradients for real).
-        self.allreduce = allreduce
-        dev = net.device
-        self.lib = _lib.load()
-        self.points = torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev)
-        self.ycls = torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev)
-        self.yreg = torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev)
-        # the optimizer of the recorded step (OptimizerSpec); lr / decay / momentum: the reference's SGD-Nesterov
-        self.opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
-        self.sample = None
-        self.stream_handle = torch.cuda.current_stream().cuda_stream
-        torch.cuda.synchronize(dev)
-        net._prepare_training()
-        p = net.params
-        for name in self.opt.slots:
-            net.slot(name)                       # made before the plan records their addresses
-        keep = _snapshot(net)
-        # eager warm-up (lazy workspaces, descriptor tables, events; it leaves the next step's repack pending, which is
-        # the state every recorded step starts from), then one more step that is recorded while it runs
-        for _ in range(max(1, warmup)):
-            self._enqueue()
-        torch.cuda.synchronize(dev)
-        self.plan = ctypes.c_void_p()
-        _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(self.plan)))
-        _lib.check(self.lib.lisec_step_plan_begin(self.plan))
-        try:
-            self._enqueue()
-        finally:
-            _lib.check(self.lib.lisec_step_plan_end(self.plan))
-        torch.cuda.synchronize(dev)
-        self.launches = self.lib.lisec_step_plan_size(self.plan)
-        # those steps trained on the padding: put every variable back and repack the kernels from them
-        _restore(net, keep)
-        net.params_version += 1
-        net.state_version += 1
-        p.touch()
-        net._pack_pending = False
-        net._pack_all()
-        net._pack_all_t()
-        net._record(net._pack_done, torch.cuda.current_stream())   # what the recorded forward waits for
-        net._record(net._pack_late, torch.cuda.current_stream())
-        net._pack_pending = True
-        net._late_pending = True
-        torch.cuda.synchronize(dev)
-        self.alloc_gen = _lib.alloc_generation()
-
-    def _enqueue(self):
-        net = self.net
-        self.sample = self.vox(self.points, out=self.sample)
-        net.forward(self.sample, training=True)
-        ar = self.allreduce
-        if ar is not None and hasattr(ar, "start_tail"):
-            net.backward(self.ycls, self.yreg, loss=self.loss,
-                         rpn_grads_ready=lambda lo, hi: ar.start_tail(net.grad, lo, hi))
-            ar.finish(net.grad)
-        elif ar is not None:
-            net.backward(self.ycls, self.yreg, loss=self.loss)
-            ar(net.grad)
-        else:
-            net.backward(self.ycls, self.yreg, loss=self.loss,
-                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, opt=self.opt))
-        net.apply_gradients(opt=self.opt)
-
-    def _check_stream(self):
-        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
-            raise RuntimeError("a RecordedStep replays on the stream it was recorded on: make that stream current")
+    def _voxelise(self, j):
+        self.vox(self.points[0], out=self.samples[0])       # at the head of the step
+        return None
 
     def load(self, points, ycls, yreg):
         """Stage one sweep: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets (Ho,Wo,2|14)."""
         self._check_stream()
-        pts = torch.as_tensor(points)
-        n = int(pts.shape[0])
-        if n > self.capacity:
-            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
-        self.points[:n].copy_(pts[:, :3], non_blocking=True)
-        if n < self.capacity:
-            self.points[n:].fill_(self.PAD)
-        self.ycls.copy_(torch.as_tensor(ycls).reshape(self.ycls.shape), non_blocking=True)
-        self.yreg.copy_(torch.as_tensor(yreg).reshape(self.yreg.shape), non_blocking=True)
+        self._load(0, points, ycls, yreg)
 
     def replay(self):
         """Runs the recorded step on what load() staged; returns net.loss_out (device, [total, class, regression])."""
         self._check_stream()
-        _check_plan_fresh(self)
-        net = self.net
-        _sync_packed(net)
-        _lib.check(self.lib.lisec_step_plan_run(self.plan))
-        net._iterations += 1
-        net.params_version += 1          # theta moved; the recorded step also repacked it for the next one
-        net.state_version += 1
-        net._packed_version = net._packed_t_version = (net.params_version, net.params.version)
-        net._pack_pending = True
-        net._late_pending = True
-        self.sample._host_info = None
-        return net.loss_out
+        return self._run()
 
     def __call__(self, points, ycls, yreg):
         self.load(points, ycls, yreg)
         return self.replay()
 
-    def close(self):
-        if getattr(self, "plan", None):
-            torch.cuda.synchronize(self.net.device)
-            self.lib.lisec_step_plan_destroy(self.plan)
-            self.plan = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PipelinedStep:
+class PipelinedStep(_StepPlans):
     """RecordedStep with the input pipeline folded in: step k voxelises the sweep of step k + 1 on the second stream, in the
     ~200 us that stream idles at the start of the backward pass, instead of step k + 1 starting with 90 us of seven small
     dependent launches in front of its first contraction.  Two sets of (points, targets, voxel sample) buffers alternate,
@@ -1419,89 +1352,13 @@ class PipelinedStep:
             loss = step.step(points[k + 1], ycls[k + 1], yreg[k + 1])     # trains on sweep k, prepares sweep k + 1
                                                                           # (no arguments: the staged buffers are reused)
     """
-    PAD = RecordedStep.PAD
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", lr=0.01, decay=1e-6, momentum=0.9,
-                 warmup=2, allreduce=None, opt=None):
-        import ctypes
-        self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
-        self.allreduce = allreduce                 # data parallel: see RecordedStep
-        dev = net.device
-        self.lib = _lib.load()
-        self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(2)]
-        self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(2)]
-        self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(2)]
-        # the optimizer of the recorded step (OptimizerSpec); lr / decay / momentum: the reference's SGD-Nesterov
-        self.opt = opt if opt is not None else OptimizerSpec("sgd", lr, decay, momentum, nesterov=True)
-        self.stream_handle = torch.cuda.current_stream().cuda_stream
-        torch.cuda.synchronize(dev)
-        net._prepare_training()
-        p = net.params
-        for name in self.opt.slots:
-            net.slot(name)                       # made before the plan records their addresses
-        keep = _snapshot(net)
-        self.samples = [self.vox(self.points[j]) for j in range(2)]
-        for k in range(2 * max(1, warmup)):
-            self._enqueue(k & 1)
-        torch.cuda.synchronize(dev)
-        self.plans = []
-        for j in range(2):
-            plan = ctypes.c_void_p()
-            _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(plan)))
-            _lib.check(self.lib.lisec_step_plan_begin(plan))
-            try:
-                self._enqueue(j)
-            finally:
-                _lib.check(self.lib.lisec_step_plan_end(plan))
-            self.plans.append(plan)
-        torch.cuda.synchronize(dev)
-        self.launches = self.lib.lisec_step_plan_size(self.plans[0])
-        _restore(net, keep)
-        net.params_version += 1
-        net.state_version += 1
-        p.touch()
-        net._pack_pending = False
-        net._pack_all()
-        net._pack_all_t()
-        net._record(net._pack_done, torch.cuda.current_stream())   # what the recorded forward waits for
-        net._record(net._pack_late, torch.cuda.current_stream())
-        net._pack_pending = True
-        net._late_pending = True
-        self.cur = 0
-        torch.cuda.synchronize(dev)
-        self.alloc_gen = _lib.alloc_generation()
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
+        super().__init__(net, voxelizer, capacity, 2, dtype, loss, warmup, allreduce, opt)
 
-    def _enqueue(self, j):
-        net = self.net
-        net.forward(self.samples[j], training=True)
-        filler = lambda: self.vox(self.points[1 - j], out=self.samples[1 - j])
-        ar = self.allreduce
-        if ar is not None and hasattr(ar, "start_tail"):
-            net.backward(self.ycls[j], self.yreg[j], loss=self.loss, side_filler=filler,
-                         rpn_grads_ready=lambda lo, hi: ar.start_tail(net.grad, lo, hi))
-            ar.finish(net.grad)
-        elif ar is not None:
-            net.backward(self.ycls[j], self.yreg[j], loss=self.loss, side_filler=filler)
-            ar(net.grad)
-        else:
-            net.backward(self.ycls[j], self.yreg[j], loss=self.loss, side_filler=filler,
-                         rpn_grads_ready=lambda lo, hi: net.early_update(lo, hi, opt=self.opt))
-        net.apply_gradients(opt=self.opt)
-
-    def _check_stream(self):
-        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
-            raise RuntimeError("a PipelinedStep replays on the stream it was recorded on: make that stream current")
-
-    def _load(self, j, points, ycls, yreg):
-        pts = torch.as_tensor(points)
-        n = int(pts.shape[0])
-        if n > self.capacity:
-            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
-        self.points[j][:n].copy_(pts[:, :3], non_blocking=True)
-        if n < self.capacity:
-            self.points[j][n:].fill_(self.PAD)
-        self.ycls[j].copy_(torch.as_tensor(ycls).reshape(self.ycls[j].shape), non_blocking=True)
-        self.yreg[j].copy_(torch.as_tensor(yreg).reshape(self.yreg[j].shape), non_blocking=True)
+    def _voxelise(self, j):
+        # the sweep of this step was voxelised by the step before; this one voxelises the next under its backward pass
+        return lambda: self.vox(self.points[1 - j], out=self.samples[1 - j])
 
     def prime(self, points, ycls, yreg):
         """Stages the FIRST sweep and voxelises it (outside the plans); the next step() trains on it."""
@@ -1519,30 +1376,4 @@ class PipelinedStep:
         self._check_stream()
         if next_points is not None:
             self._load(1 - self.cur, next_points, next_ycls, next_yreg)
-        _check_plan_fresh(self)
-        net = self.net
-        _sync_packed(net)
-        _lib.check(self.lib.lisec_step_plan_run(self.plans[self.cur]))
-        net._iterations += 1
-        net.params_version += 1
-        net.state_version += 1
-        net._packed_version = net._packed_t_version = (net.params_version, net.params.version)
-        net._pack_pending = True
-        net._late_pending = True
-        for s_ in self.samples:
-            s_._host_info = None
-        self.cur ^= 1
-        return net.loss_out
-
-    def close(self):
-        if getattr(self, "plans", None):
-            torch.cuda.synchronize(self.net.device)
-            for plan in self.plans:
-                self.lib.lisec_step_plan_destroy(plan)
-            self.plans = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._run()

@@ -86,3 +86,22 @@ def test_product_does_not_import_oracle():
             if f.endswith(".py"):
                 text = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", text, flags=re.M), f
+
+
+def test_tuning_spec_accepts_host_knobs_and_record_fields(monkeypatch):
+    from lisec_amd import _lib
+    monkeypatch.setenv("LISEC_TUNING", "winograd=7, max_splitk=8,step_plan=0")
+    assert _lib._tuning_spec() == {"winograd": "7", "max_splitk": "8", "step_plan": "0"}
+    assert _lib.knob("winograd", 15) == 7 and _lib.knob("step_plan", True) is False and _lib.knob("field_conv", True)
+
+
+def test_load_rejects_an_unknown_tuning_knob():
+    """A LISEC_TUNING key that is neither a host knob nor a lisec_tuning field -- here a schedule knob that was retired --
+    is an error at load(), not a run that silently measures the default."""
+    import subprocess
+    import sys
+    env = dict(os.environ, LISEC_TUNING="max_splitk=8,chain_first=0")
+    r = subprocess.run([sys.executable, "-c", "from lisec_amd import _lib; _lib.load()"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0
+    assert "LisecError" in r.stderr and "unknown knob(s) chain_first:" in r.stderr, r.stderr[-2000:]

@@ -175,6 +175,43 @@ def test_train_steps_small_grid_vs_oracle_autograd(loss):
         p64, vel = p64_new, vel_new
 
 
+def test_early_update_is_pending_until_apply_gradients_with_the_same_optimizer():
+    """early_update() (the RPN + head variables, under the rest of the backward pass) stays pending until
+    apply_gradients() ends the step.  A second early update before that raises, and so does an apply_gradients() with
+    another optimizer than the early update's -- before any launch: theta is left as the early update left it, and the
+    step still ends with the right optimizer."""
+    from lisec_amd.network import LisecNet, OptimizerSpec
+    from lisec_amd.params import ParamStore
+    from lisec_amd.voxelizer import Voxelizer
+    from oracle import model_ref as M
+
+    dev = torch.device("cuda")
+    net = LisecNet(16, 32, 8, 35, params=ParamStore(dev, init=M.glorot_params(seed=21, randomize_bn=True)))
+    sample = Voxelizer(**SMALL)(small_cloud(5))
+    y_cls = torch.ones(8, 16, 2, device=dev)
+    y_reg = torch.zeros(8, 16, 14, device=dev)
+    theta0 = net.params.theta.clone()
+    hook = []
+    net.forward(sample, training=True)
+    net.backward(y_cls, y_reg, rpn_grads_ready=lambda lo, hi: (hook.append((lo, hi)), net.early_update(lo, hi)))
+    assert len(hook) == 1
+    lo, hi = hook[0]
+    with pytest.raises(RuntimeError):
+        net.early_update(lo, hi)
+    with pytest.raises(RuntimeError):
+        net.apply_gradients(opt=OptimizerSpec("adam"))
+    torch.cuda.synchronize()
+    th = net.params.theta
+    assert torch.equal(th[:lo], theta0[:lo]) and not torch.equal(th[lo:], theta0[lo:])
+    assert net.iterations == 0 and net._iter_dev.cpu().tolist() == [0, 0]
+    net.apply_gradients(opt=OptimizerSpec())
+    torch.cuda.synchronize()
+    assert net.iterations == 1 and not torch.equal(net.params.theta[:lo], theta0[:lo])
+    lo_ = net.train_step(sample, y_cls, y_reg)              # the guard was cleared: the next step runs as ever
+    torch.cuda.synchronize()
+    assert net.iterations == 2 and torch.isfinite(lo_).all()
+
+
 def test_train_step_fully_occupied_grid_vs_oracle():
     """Every cell of the grid occupied (a dense (D,H,W,T,6) array handed to the model, as Model.fit accepts): there is
     no "empty cell" class, the constant row V of the per-voxel outputs is defined as 0 and must not be read from
