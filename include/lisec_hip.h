@@ -629,6 +629,70 @@ int lisec_adam_step_dev(float* theta, const float* grad, float* m, float* v, flo
                         long long n, double lr, double decay, float beta1, float beta2, float epsilon, long long* state,
                         int advance, lisec_stream_t stream);
 
+/* Learning-rate schedules (tf.keras 2.4 optimizers.schedules, OptimizerV2._decayed_lr) read by the update kernels from
+ * DEVICE memory, like the iteration count: a recorded step keeps replaying correctly, and the host may rewrite the
+ * descriptor between steps (lisec_lr_schedule_set, stream-ordered) without recording the step again.  With s = state[0],
+ * the iteration count before the update, every workgroup computes once, in double, rounded to float once:
+ *     lr_t = (float)(schedule(s) / (1 + decay*s))
+ *   CONSTANT           initial                                                         (decay as before: the by-value entries)
+ *   EXPONENTIAL        p = s/decay_steps (floored if flag);  initial * decay_rate^p
+ *   PIECEWISE          values[i] for the first i with s <= boundaries[i], else values[n_boundaries]
+ *   POLYNOMIAL         flag (cycle): decay_steps *= (s == 0 ? 1 : ceil(s/decay_steps)), else s = min(s, decay_steps);
+ *                      (initial - end_learning_rate)*(1 - s/decay_steps)^power + end_learning_rate
+ *   INVERSE_TIME       p = s/decay_steps (floored if flag);  initial / (1 + decay_rate*p)
+ *   COSINE             s = min(s, decay_steps);  initial * ((1 - alpha)*0.5*(1 + cos(pi*s/decay_steps)) + alpha)
+ *   COSINE_RESTARTS    f = s/decay_steps (first_decay_steps);  t_mul == 1: i = floor(f), f -= i;  otherwise
+ *                      i = floor(log(1 - f*(1 - t_mul))/log(t_mul)), f = (f - (1 - t_mul^i)/(1 - t_mul))/t_mul^i;
+ *                      initial * ((1 - alpha)*0.5*m_mul^i*(1 + cos(pi*f)) + alpha)
+ * Parameters a kind does not use are ignored. */
+#define LISEC_LR_MAX_BOUNDARIES 64
+enum {
+    LISEC_LR_CONSTANT = 0,
+    LISEC_LR_EXPONENTIAL = 1,
+    LISEC_LR_PIECEWISE = 2,
+    LISEC_LR_POLYNOMIAL = 3,
+    LISEC_LR_INVERSE_TIME = 4,
+    LISEC_LR_COSINE = 5,
+    LISEC_LR_COSINE_RESTARTS = 6
+};
+typedef struct lisec_lr_schedule {
+    int kind;                 /* LISEC_LR_* */
+    int flag;                 /* staircase (EXPONENTIAL, INVERSE_TIME) or cycle (POLYNOMIAL) */
+    int n_boundaries;         /* PIECEWISE: 1 .. LISEC_LR_MAX_BOUNDARIES */
+    int reserved;             /* 0 */
+    double initial;           /* initial_learning_rate (CONSTANT: the learning rate) */
+    double decay_steps;       /* decay_steps (COSINE_RESTARTS: first_decay_steps); > 0 */
+    double decay_rate;
+    double end_learning_rate;
+    double power;
+    double alpha;
+    double t_mul;
+    double m_mul;
+    double decay;             /* the optimizer's legacy `decay`, applied on top */
+    double boundaries[LISEC_LR_MAX_BOUNDARIES];
+    double values[LISEC_LR_MAX_BOUNDARIES + 1];
+} lisec_lr_schedule;
+
+/* Validates *host_desc (a host pointer) and enqueues its copy into dev_desc (device memory, the address the update
+ * kernels are given) on `stream`, ordered after every update already enqueued there.  LISEC_EINVAL, nothing enqueued:
+ * NULL pointer, unknown kind, decay_steps <= 0 where the kind divides by it, n_boundaries outside
+ * 1..LISEC_LR_MAX_BOUNDARIES for PIECEWISE, or a step plan being recorded on this thread (a plan re-issues launches
+ * only: the copy would not be part of it). */
+int lisec_lr_schedule_set(lisec_lr_schedule* dev_desc, const lisec_lr_schedule* host_desc, lisec_stream_t stream);
+/* lr_out[k] = lr_t at s = state[0] + k, k < n (dev pointers; state is read, never advanced): the device function of the
+ * update kernels, for tests. */
+int lisec_lr_schedule_eval(const lisec_lr_schedule* sched, const long long* state, long long n, float* lr_out,
+                           lisec_stream_t stream);
+/* lisec_sgd_step_dev / lisec_adam_step_dev with lr_t from the descriptor `sched` (dev) instead of (lr, decay), and the
+ * same state / advance semantics.  Given a CONSTANT descriptor they compute the bits of the by-value entries (nesterov
+ * = 1: the bits of lisec_sgd_nesterov_step_dev). */
+int lisec_sgd_step_sched(float* theta, const float* grad, float* velocity /* NULL iff momentum == 0 */, long long n,
+                         const lisec_lr_schedule* sched, float momentum, int nesterov, long long* state, int advance,
+                         lisec_stream_t stream);
+int lisec_adam_step_sched(float* theta, const float* grad, float* m, float* v, float* vhat /* NULL iff !amsgrad */,
+                          long long n, const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon,
+                          long long* state, int advance, lisec_stream_t stream);
+
 /* x *= s  (gradient averaging after the data-parallel all-reduce) */
 int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);
 

@@ -77,6 +77,16 @@ class PackDesc(Structure):
                 ("ntaps", c_int), ("K", c_int), ("N", c_int), ("Kp", c_int), ("Np", c_int), ("pad_", c_int)]
 
 
+LR_MAX_BOUNDARIES = 64                         # LISEC_LR_MAX_BOUNDARIES
+
+
+class LrSchedule(Structure):                   # lisec_lr_schedule
+    _fields_ = ([("kind", c_int), ("flag", c_int), ("n_boundaries", c_int), ("reserved", c_int)]
+                + [(n, c_double) for n in ("initial", "decay_steps", "decay_rate", "end_learning_rate", "power", "alpha",
+                                           "t_mul", "m_mul", "decay")]
+                + [("boundaries", c_double * LR_MAX_BOUNDARIES), ("values", c_double * (LR_MAX_BOUNDARIES + 1))])
+
+
 class ConvGeom(Structure):
     _fields_ = [(n, c_int) for n in ("mode", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "KD", "KH", "KW",
                                      "sd", "sh", "sw", "pd", "ph", "pw", "Cin", "in_stride", "Cout",
@@ -221,6 +231,14 @@ def _declare(lib):
     lib.lisec_sgd_step_dev.argtypes = [P, P, P, LL, c_double, c_double, c_float, c_int, P, c_int, P]
     lib.lisec_adam_step_dev.restype = c_int
     lib.lisec_adam_step_dev.argtypes = [P, P, P, P, P, LL, c_double, c_double, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_lr_schedule_set.restype = c_int
+    lib.lisec_lr_schedule_set.argtypes = [P, POINTER(LrSchedule), P]
+    lib.lisec_lr_schedule_eval.restype = c_int
+    lib.lisec_lr_schedule_eval.argtypes = [P, P, LL, P, P]
+    lib.lisec_sgd_step_sched.restype = c_int
+    lib.lisec_sgd_step_sched.argtypes = [P, P, P, LL, P, c_float, c_int, P, c_int, P]
+    lib.lisec_adam_step_sched.restype = c_int
+    lib.lisec_adam_step_sched.argtypes = [P, P, P, P, P, LL, P, c_float, c_float, c_float, P, c_int, P]
     lib.lisec_fold_depth.restype = c_int
     lib.lisec_fold_depth.argtypes = [P, P, c_int, LL, c_int, c_int, P, P]
     lib.lisec_scale.restype = c_int

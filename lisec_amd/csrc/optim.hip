@@ -3,6 +3,9 @@
 // ResourceApplyGradientDescent / ResourceApplyKerasMomentum / ResourceApplyAdam).
 // Single-pass streaming kernels: float4 loads and stores, grid-stride, no LDS.  The iteration count lives on the device
 // (state[0]), exactly as for lisec_sgd_nesterov_step_dev, so that a recorded step re-issues them unchanged.
+// The *_sched kernels take lr_t from a learning-rate schedule descriptor in device memory (lisec_lr_schedule, the
+// tf.keras 2.4 optimizers.schedules), evaluated at that iteration count once per workgroup and handed to its other
+// waves through 4 bytes of LDS (their only LDS).
 #include "common.h"
 
 namespace lisec {
@@ -41,34 +44,118 @@ __device__ __forceinline__ float decayed_lr(double lr, double decay, long long i
     return (float)(lr / (1.0 + decay * (double)it));
 }
 
+// schedule(it) of the descriptor (include/lisec_hip.h), in double: the arithmetic of tf.keras 2.4
+// optimizers.schedules, with TF's order of operations.
+__device__ double schedule_value(const lisec_lr_schedule* __restrict__ s, double step) {
+    constexpr double kPi = 3.14159265358979323846;
+    const double init = s->initial, ds = s->decay_steps;
+    switch (s->kind) {
+    case LISEC_LR_EXPONENTIAL: {
+        double p = step / ds;
+        if (s->flag) p = floor(p);
+        return init * pow(s->decay_rate, p);
+    }
+    case LISEC_LR_PIECEWISE: {
+        int nb = s->n_boundaries;
+        nb = nb < 0 ? 0 : (nb > LISEC_LR_MAX_BOUNDARIES ? LISEC_LR_MAX_BOUNDARIES : nb);   // never read past the tables
+        for (int i = 0; i < nb; ++i)
+            if (step <= s->boundaries[i]) return s->values[i];
+        return s->values[nb];
+    }
+    case LISEC_LR_POLYNOMIAL: {
+        double d = ds, x = step;
+        if (s->flag) d *= (x == 0.0 ? 1.0 : ceil(x / ds));
+        else x = fmin(x, ds);
+        return (init - s->end_learning_rate) * pow(1.0 - x / d, s->power) + s->end_learning_rate;
+    }
+    case LISEC_LR_INVERSE_TIME: {
+        double p = step / ds;
+        if (s->flag) p = floor(p);
+        return init / (1.0 + s->decay_rate * p);
+    }
+    case LISEC_LR_COSINE: {
+        const double f = fmin(step, ds) / ds;
+        const double c = 0.5 * (1.0 + cos(kPi * f));
+        return init * ((1.0 - s->alpha) * c + s->alpha);
+    }
+    case LISEC_LR_COSINE_RESTARTS: {
+        double f = step / ds, i;
+        const double tm = s->t_mul;
+        if (tm == 1.0) {
+            i = floor(f);
+            f -= i;
+        } else {
+            i = floor(log(1.0 - f * (1.0 - tm)) / log(tm));
+            const double ti = pow(tm, i);
+            f = (f - (1.0 - ti) / (1.0 - tm)) / ti;
+        }
+        const double c = 0.5 * pow(s->m_mul, i) * (1.0 + cos(kPi * f));
+        return init * ((1.0 - s->alpha) * c + s->alpha);
+    }
+    default:                                                           // LISEC_LR_CONSTANT
+        return init;
+    }
+}
+
+// lr_t = schedule(it) / (1 + decay*it), rounded once; a CONSTANT descriptor gives decayed_lr(lr, decay, it) bit for bit
+__device__ __forceinline__ float scheduled_lr(const lisec_lr_schedule* __restrict__ s, long long it) {
+    return decayed_lr(schedule_value(s, (double)it), s->decay, it);
+}
+
+// lr_t evaluated by one thread of the workgroup and shared through LDS: the double-precision schedule runs once per
+// workgroup, ahead of the streaming loop.
+__device__ __forceinline__ float workgroup_lr(const lisec_lr_schedule* __restrict__ s, long long it) {
+    __shared__ float lr_shared;
+    if (threadIdx.x == 0) lr_shared = scheduled_lr(s, it);
+    __syncthreads();
+    return lr_shared;
+}
+
 enum SgdKind { kSgdPlain = 0, kSgdMomentum = 1, kSgdNesterov = 2 };
 
+// The streaming loops of the update kernels, as macros: the by-value and the descriptor kernels expand the same tokens
+// inside the kernel itself (a shared helper function changes the code generated for the existing kernels).
+//
 // KIND 0 (momentum == 0):  w <- w - lr_t*g                     (no slot: v is not touched)
 // KIND 1:                  v <- m*v - lr_t*g;  w <- w + v
 // KIND 2 (Nesterov):       v <- m*v - lr_t*g;  w <- w + m*v - lr_t*g   (the arithmetic of k_sgd_nesterov_dev)
+#define LISEC_SGD_UPD(f) { float nv = mom * V.f - lr_t * G.f; V.f = nv;                                       \
+                           W.f = KIND == kSgdNesterov ? W.f + mom * nv - lr_t * G.f : W.f + nv; }
+#define LISEC_SGD_LOOP                                                                                                  \
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) { \
+        float4 W = reinterpret_cast<float4*>(w)[i];                                                                     \
+        const float4 G = reinterpret_cast<const float4*>(g)[i];                                                         \
+        if constexpr (KIND == kSgdPlain) {                                                                              \
+            W.x -= lr_t * G.x; W.y -= lr_t * G.y; W.z -= lr_t * G.z; W.w -= lr_t * G.w;                                 \
+        } else {                                                                                                        \
+            float4 V = reinterpret_cast<float4*>(v)[i];                                                                 \
+            LISEC_SGD_UPD(x) LISEC_SGD_UPD(y) LISEC_SGD_UPD(z) LISEC_SGD_UPD(w)                                         \
+            reinterpret_cast<float4*>(v)[i] = V;                                                                        \
+        }                                                                                                               \
+        reinterpret_cast<float4*>(w)[i] = W;                                                                            \
+    }
+
 template <int KIND>
 __global__ void __launch_bounds__(kOptThreads)
 k_sgd_dev(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v, long long n4, double lr,
           double decay, float mom, long long* __restrict__ state, int advance) {
     const long long it = read_iterations(state);
     const float lr_t = decayed_lr(lr, decay, it);
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 W = reinterpret_cast<float4*>(w)[i];
-        const float4 G = reinterpret_cast<const float4*>(g)[i];
-        if constexpr (KIND == kSgdPlain) {
-            W.x -= lr_t * G.x; W.y -= lr_t * G.y; W.z -= lr_t * G.z; W.w -= lr_t * G.w;
-        } else {
-            float4 V = reinterpret_cast<float4*>(v)[i];
-#define LISEC_UPD(f) { float nv = mom * V.f - lr_t * G.f; V.f = nv;                                       \
-                       W.f = KIND == kSgdNesterov ? W.f + mom * nv - lr_t * G.f : W.f + nv; }
-            LISEC_UPD(x) LISEC_UPD(y) LISEC_UPD(z) LISEC_UPD(w)
-#undef LISEC_UPD
-            reinterpret_cast<float4*>(v)[i] = V;
-        }
-        reinterpret_cast<float4*>(w)[i] = W;
-    }
+    LISEC_SGD_LOOP
     if (advance) advance_iterations(state, it);
 }
+
+template <int KIND>
+__global__ void __launch_bounds__(kOptThreads)
+k_sgd_sched(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v, long long n4,
+            const lisec_lr_schedule* __restrict__ sched, float mom, long long* __restrict__ state, int advance) {
+    const long long it = read_iterations(state);
+    const float lr_t = workgroup_lr(sched, it);
+    LISEC_SGD_LOOP
+    if (advance) advance_iterations(state, it);
+}
+#undef LISEC_SGD_LOOP
+#undef LISEC_SGD_UPD
 
 // Adam (AMSGRAD: the amsgrad path), t = it + 1:
 //   alpha = lr_t * sqrt(1 - b2^t) / (1 - b1^t)          (b1^t, b2^t in fp32)
@@ -76,6 +163,29 @@ k_sgd_dev(float* __restrict__ w, const float* __restrict__ g, float* __restrict_
 //   AMSGRAD: vhat <- max(vhat, v), and vhat replaces v below
 //   w <- w - alpha * m / (sqrt(v) + eps)                 (eps outside the square root, as in TF)
 // sqrtf and the divisions are correctly rounded (hipcc's default; no fast-math flag is used anywhere in the library).
+#define LISEC_ADAM_UPD(f) {                                                               \
+            M.f += (G.f - M.f) * c1;                                                      \
+            V.f += (G.f * G.f - V.f) * c2;                                                \
+            float den = V.f;                                                              \
+            if constexpr (AMSGRAD) { H.f = fmaxf(H.f, V.f); den = H.f; }                  \
+            W.f -= alpha * M.f / (sqrtf(den) + eps); }
+#define LISEC_ADAM_LOOP                                                                                                 \
+    const float t = (float)(it + 1);                                                                                    \
+    const float b1p = powf(b1, t), b2p = powf(b2, t);                                                                   \
+    const float alpha = lr_t * sqrtf(1.f - b2p) / (1.f - b1p);                                                          \
+    const float c1 = 1.f - b1, c2 = 1.f - b2;                                                                           \
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) { \
+        float4 W = reinterpret_cast<float4*>(w)[i], M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i]; \
+        const float4 G = reinterpret_cast<const float4*>(g)[i];                                                         \
+        float4 H;                                                                                                       \
+        if constexpr (AMSGRAD) H = reinterpret_cast<float4*>(vhat)[i];                                                  \
+        LISEC_ADAM_UPD(x) LISEC_ADAM_UPD(y) LISEC_ADAM_UPD(z) LISEC_ADAM_UPD(w)                                         \
+        reinterpret_cast<float4*>(w)[i] = W;                                                                            \
+        reinterpret_cast<float4*>(m)[i] = M;                                                                            \
+        reinterpret_cast<float4*>(v)[i] = V;                                                                            \
+        if constexpr (AMSGRAD) reinterpret_cast<float4*>(vhat)[i] = H;                                                  \
+    }
+
 template <bool AMSGRAD>
 __global__ void __launch_bounds__(kOptThreads)
 k_adam_dev(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -83,29 +193,30 @@ k_adam_dev(float* __restrict__ w, const float* __restrict__ g, float* __restrict
            long long* __restrict__ state, int advance) {
     const long long it = read_iterations(state);
     const float lr_t = decayed_lr(lr, decay, it);
-    const float t = (float)(it + 1);
-    const float b1p = powf(b1, t), b2p = powf(b2, t);
-    const float alpha = lr_t * sqrtf(1.f - b2p) / (1.f - b1p);
-    const float c1 = 1.f - b1, c2 = 1.f - b2;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
-        float4 W = reinterpret_cast<float4*>(w)[i], M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
-        const float4 G = reinterpret_cast<const float4*>(g)[i];
-        float4 H;
-        if constexpr (AMSGRAD) H = reinterpret_cast<float4*>(vhat)[i];
-#define LISEC_UPD(f) {                                                                    \
-            M.f += (G.f - M.f) * c1;                                                      \
-            V.f += (G.f * G.f - V.f) * c2;                                                \
-            float den = V.f;                                                              \
-            if constexpr (AMSGRAD) { H.f = fmaxf(H.f, V.f); den = H.f; }                  \
-            W.f -= alpha * M.f / (sqrtf(den) + eps); }
-        LISEC_UPD(x) LISEC_UPD(y) LISEC_UPD(z) LISEC_UPD(w)
-#undef LISEC_UPD
-        reinterpret_cast<float4*>(w)[i] = W;
-        reinterpret_cast<float4*>(m)[i] = M;
-        reinterpret_cast<float4*>(v)[i] = V;
-        if constexpr (AMSGRAD) reinterpret_cast<float4*>(vhat)[i] = H;
-    }
+    LISEC_ADAM_LOOP
     if (advance) advance_iterations(state, it);
+}
+
+template <bool AMSGRAD>
+__global__ void __launch_bounds__(kOptThreads)
+k_adam_sched(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+             float* __restrict__ vhat, long long n4, const lisec_lr_schedule* __restrict__ sched, float b1, float b2,
+             float eps, long long* __restrict__ state, int advance) {
+    const long long it = read_iterations(state);
+    const float lr_t = workgroup_lr(sched, it);
+    LISEC_ADAM_LOOP
+    if (advance) advance_iterations(state, it);
+}
+#undef LISEC_ADAM_LOOP
+#undef LISEC_ADAM_UPD
+
+// lr_out[k] = lr_t at it = state[0] + k (lisec_lr_schedule_eval): one schedule evaluation per element, for tests.
+__global__ void __launch_bounds__(kOptThreads)
+k_lr_schedule_eval(const lisec_lr_schedule* __restrict__ sched, const long long* __restrict__ state, long long n,
+                   float* __restrict__ lr_out) {
+    const long long it0 = read_iterations(state);
+    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x)
+        lr_out[k] = scheduled_lr(sched, it0 + k);
 }
 
 }  // namespace
@@ -146,6 +257,78 @@ extern "C" int lisec_adam_step_dev(float* theta, const float* grad, float* m, fl
                      state, advance);
     else
         LISEC_LAUNCH(k_adam_dev<false>, grid, block, 0, st, theta, grad, m, v, vhat, n / 4, lr, decay, beta1, beta2, epsilon,
+                     state, advance);
+    LISEC_LAUNCH_CHECK();
+    return LISEC_OK;
+}
+
+extern "C" int lisec_lr_schedule_set(lisec_lr_schedule* dev_desc, const lisec_lr_schedule* host_desc,
+                                     lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(dev_desc && host_desc, "lr_schedule_set: NULL descriptor");
+    const lisec_lr_schedule& d = *host_desc;
+    LISEC_CHECK_ARG(d.kind >= LISEC_LR_CONSTANT && d.kind <= LISEC_LR_COSINE_RESTARTS, "lr_schedule_set: unknown kind %d",
+                    d.kind);
+    LISEC_CHECK_ARG(d.kind == LISEC_LR_CONSTANT || d.kind == LISEC_LR_PIECEWISE || d.decay_steps > 0.0,
+                    "lr_schedule_set: decay_steps must be > 0");
+    LISEC_CHECK_ARG(d.kind != LISEC_LR_PIECEWISE || (d.n_boundaries >= 1 && d.n_boundaries <= LISEC_LR_MAX_BOUNDARIES),
+                    "lr_schedule_set: a piecewise schedule takes 1 to %d boundaries", LISEC_LR_MAX_BOUNDARIES);
+    LISEC_CHECK_ARG(!plan_recording(), "lr_schedule_set: a step plan is being recorded (it would not re-issue the copy)");
+    if (hipMemcpyAsync(dev_desc, host_desc, sizeof(lisec_lr_schedule), hipMemcpyHostToDevice,
+                       static_cast<hipStream_t>(stream_)) != hipSuccess) {
+        set_error("lr_schedule_set: hipMemcpyAsync failed: %s", hipGetErrorString(hipGetLastError()));
+        return LISEC_EHIP;
+    }
+    return LISEC_OK;
+}
+
+extern "C" int lisec_lr_schedule_eval(const lisec_lr_schedule* sched, const long long* state, long long n, float* lr_out,
+                                      lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(sched && state && lr_out && n >= 0, "lr_schedule_eval: NULL pointer or n < 0");
+    if (n == 0) return LISEC_OK;
+    LISEC_LAUNCH(k_lr_schedule_eval, dim3(opt_blocks(n)), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream_), sched,
+                 state, n, lr_out);
+    LISEC_LAUNCH_CHECK();
+    return LISEC_OK;
+}
+
+extern "C" int lisec_sgd_step_sched(float* theta, const float* grad, float* velocity, long long n,
+                                    const lisec_lr_schedule* sched, float momentum, int nesterov, long long* state,
+                                    int advance, lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(theta && grad && sched && state && n >= 0 && n % 4 == 0,
+                    "sgd_sched: NULL pointer or n not a multiple of 4");
+    LISEC_CHECK_ARG(momentum >= 0.f && (advance == 0 || advance == 1), "sgd_sched: momentum must be >= 0, advance 0 or 1");
+    LISEC_CHECK_ARG((velocity == nullptr) == (momentum == 0.f), "sgd_sched: velocity must be NULL exactly when momentum == 0");
+    if (n == 0) return LISEC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    if (momentum == 0.f)
+        LISEC_LAUNCH(k_sgd_sched<kSgdPlain>, grid, block, 0, st, theta, grad, velocity, n / 4, sched, momentum, state, advance);
+    else if (nesterov)
+        LISEC_LAUNCH(k_sgd_sched<kSgdNesterov>, grid, block, 0, st, theta, grad, velocity, n / 4, sched, momentum, state,
+                     advance);
+    else
+        LISEC_LAUNCH(k_sgd_sched<kSgdMomentum>, grid, block, 0, st, theta, grad, velocity, n / 4, sched, momentum, state,
+                     advance);
+    LISEC_LAUNCH_CHECK();
+    return LISEC_OK;
+}
+
+extern "C" int lisec_adam_step_sched(float* theta, const float* grad, float* m, float* v, float* vhat, long long n,
+                                     const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon,
+                                     long long* state, int advance, lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(theta && grad && m && v && sched && state && n >= 0 && n % 4 == 0,
+                    "adam_sched: NULL pointer or n not a multiple of 4");
+    LISEC_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && epsilon >= 0.f,
+                    "adam_sched: beta_1 and beta_2 must lie in [0, 1), epsilon must be >= 0");
+    LISEC_CHECK_ARG(advance == 0 || advance == 1, "adam_sched: advance must be 0 or 1");
+    if (n == 0) return LISEC_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    if (vhat)                                                          // AMSGrad
+        LISEC_LAUNCH(k_adam_sched<true>, grid, block, 0, st, theta, grad, m, v, vhat, n / 4, sched, beta1, beta2, epsilon,
+                     state, advance);
+    else
+        LISEC_LAUNCH(k_adam_sched<false>, grid, block, 0, st, theta, grad, m, v, vhat, n / 4, sched, beta1, beta2, epsilon,
                      state, advance);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;

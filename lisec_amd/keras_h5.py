@@ -195,16 +195,21 @@ def model_config(nx, ny, nz, maxPoints):
             "keras_version": KERAS_VERSION, "backend": "tensorflow"}
 
 
+def _rate(lr):
+    """A learning rate of training_config: a number, or a serialized schedule ({"class_name", "config"}) as is."""
+    return lr if isinstance(lr, dict) else float(lr)
+
+
 def _training_config(optimizer):
     o = optimizer or {}
     if o.get("class_name", "SGD") == "Adam":
         oc = {"class_name": "Adam", "config": {
-            "name": "Adam", "learning_rate": float(o.get("lr", 0.001)), "decay": float(o.get("decay", 0.0)),
+            "name": "Adam", "learning_rate": _rate(o.get("lr", 0.001)), "decay": float(o.get("decay", 0.0)),
             "beta_1": float(o.get("beta_1", 0.9)), "beta_2": float(o.get("beta_2", 0.999)),
             "epsilon": float(o.get("epsilon", 1e-7)), "amsgrad": bool(o.get("amsgrad", False))}}
     else:
         oc = {"class_name": "SGD", "config": {
-            "name": "SGD", "learning_rate": float(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
+            "name": "SGD", "learning_rate": _rate(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
             "momentum": float(o.get("momentum", 0.0)), "nesterov": bool(o.get("nesterov", False))}}
     return {"loss": ["mse", "mse"], "metrics": None, "weighted_metrics": None, "loss_weights": None,
             "optimizer_config": oc}
@@ -221,7 +226,8 @@ def _slot_kinds(optimizer):
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None, m=None, v=None,
                vhat=None):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
-    dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam, or None (a model that was never
+    dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
+    schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
     compiled: no training_config / optimizer_weights, like Keras).  The slots, each a dict of trainable ParamStore
     name -> array: velocity (SGD momentum accumulators, momentum > 0), m and v (Adam moments), vhat (AMSGrad).
     optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none)."""

@@ -3,6 +3,9 @@
     get_voxel, VFE_preprocessing, combine_lidar_data, rotate_points, RepeatLayer, MaxPoolingVFELayer,
     createModel, load_model, optimizers.SGD, optimizers.Adam, train, train_with_model
 
+and, for Model.fit, the tf.keras 2.4 learning-rate schedules (optimizers.schedules) and callbacks
+(callbacks.Callback, callbacks.LearningRateScheduler).
+
 The Keras graph is replaced by lisec_amd.network.LisecNet (HIP kernels behind the C ABI); lidar sweeps
 stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacked in host RAM
 (reference model_training.py:279,285).  There is no CPU fallback.
@@ -15,6 +18,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
+from . import callbacks, lr_schedules
 from .network import LisecNet, OptimizerSpec
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
@@ -230,40 +234,57 @@ def _no_clipping(cls, kwargs):
         raise TypeError(f"{cls}: unexpected keyword argument(s) {', '.join(rest)}")
 
 
+def _rate(lr):
+    """A learning rate as the optimizers keep it: a LearningRateSchedule as is, anything else as a float."""
+    return lr if isinstance(lr, lr_schedules.LearningRateSchedule) else float(lr)
+
+
+def _serialize_rate(lr):
+    """Keras' _serialize_hyperparameter: a schedule as its {"class_name", "config"} dict."""
+    return lr_schedules.serialize(lr) if isinstance(lr, lr_schedules.LearningRateSchedule) else lr
+
+
 class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimizers`)
-    """tf.keras 2.4 SGD and Adam (OptimizerV2): lr_t = lr / (1 + decay*iterations) for both; `lr=` is the legacy spelling
-    of `learning_rate=`.  The updates run as HIP kernels on the flat variables (csrc/eltwise.hip, csrc/optim.hip)."""
+    """tf.keras 2.4 SGD and Adam (OptimizerV2): lr_t = lr / (1 + decay*iterations) for both, lr either a number or one
+    of the built-in schedules of optimizers.schedules (then lr_t = schedule(iterations) / (1 + decay*iterations)); `lr=`
+    is the legacy spelling of `learning_rate=`.  The updates run as HIP kernels on the flat variables
+    (csrc/eltwise.hip, csrc/optim.hip)."""
+
+    schedules = lr_schedules
 
     class SGD:
         def __init__(self, lr=0.01, decay=0.0, momentum=0.0, nesterov=False, learning_rate=None, name="SGD", **kwargs):
             _no_clipping("SGD", kwargs)
-            self.lr = float(learning_rate if learning_rate is not None else lr)
+            self.lr = _rate(learning_rate if learning_rate is not None else lr)
             self.decay, self.momentum, self.nesterov, self.name = float(decay), float(momentum), bool(nesterov), name
             if not 0.0 <= self.momentum <= 1.0:
                 raise ValueError("`momentum` must be between [0, 1].")
+            self.spec()                                      # a schedule the kernels cannot evaluate is refused here
 
-        def spec(self):
-            return OptimizerSpec("sgd", self.lr, self.decay, self.momentum, self.nesterov)
+        def spec(self, device_lr=False):
+            """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
+            callbacks, which may change it between epochs)."""
+            return OptimizerSpec("sgd", self.lr, self.decay, self.momentum, self.nesterov, device_lr=device_lr)
 
         def get_config(self):
-            return {"name": self.name, "learning_rate": self.lr, "decay": self.decay, "momentum": self.momentum,
-                    "nesterov": self.nesterov}
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
+                    "momentum": self.momentum, "nesterov": self.nesterov}
 
     class Adam:
         def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, name="Adam",
                      lr=None, decay=0.0, **kwargs):
             _no_clipping("Adam", kwargs)
-            self.lr = float(lr if lr is not None else learning_rate)
+            self.lr = _rate(lr if lr is not None else learning_rate)
             self.decay, self.beta_1, self.beta_2 = float(decay), float(beta_1), float(beta_2)
             self.epsilon, self.amsgrad, self.name = float(epsilon), bool(amsgrad), name
             self.spec()                                      # range checks
 
-        def spec(self):
+        def spec(self, device_lr=False):
             return OptimizerSpec("adam", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
-                                 amsgrad=self.amsgrad)
+                                 amsgrad=self.amsgrad, device_lr=device_lr)
 
         def get_config(self):
-            return {"name": self.name, "learning_rate": self.lr, "decay": self.decay, "beta_1": self.beta_1,
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "beta_1": self.beta_1,
                     "beta_2": self.beta_2, "epsilon": self.epsilon, "amsgrad": self.amsgrad}
 
     @staticmethod
@@ -336,11 +357,14 @@ class Model:
             raise ValueError("expected SparseVoxels / list of them / dense (n,D,H,W,T,6) array")
         return [dense_to_sample(a, self.net.device) for a in arr]
 
-    def fit(self, x, y, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True):
+    def fit(self, x, y, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None):
         """fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, epochs=1, steps_per_epoch=180)
         (model_training.py:299).  batch_size must be 1 (the reference's setting: BatchNormalization
         statistics are per sample).  With WORLD_SIZE > 1 whole samples are sharded over the ranks and the
-        gradients averaged with one RCCL all-reduce per step."""
+        gradients averaged with one RCCL all-reduce per step.
+        callbacks: a list of callbacks.Callback (LearningRateScheduler, or one's own), called as Keras does.  With
+        callbacks the update kernels read the learning rate from the device descriptor, so that a rate set between
+        epochs reaches the recorded step without recording it again."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if batch_size != 1:
@@ -359,7 +383,10 @@ class Model:
             steps = max(1, steps_per_epoch // self.dp.world)
         dev = self.net.device
         hist = History()
-        opt = self.optimizer.spec()
+        callbacks = list(callbacks or [])
+        for cb in callbacks:
+            cb.set_model(self)
+            cb.set_params(dict(verbose=verbose, epochs=epochs, steps=steps))
         # targets live on the device for the whole fit when they fit comfortably (1.28 MB per sample)
         on_dev = n * ycls[0].size * 4 * 8 < (2 << 30)
         if on_dev:
@@ -368,8 +395,16 @@ class Model:
         target = (lambda i: (ycls_d[i], yreg_d[i])) if on_dev else (
             lambda i: (torch.from_numpy(np.ascontiguousarray(ycls[i])).to(dev),
                        torch.from_numpy(np.ascontiguousarray(yreg[i])).to(dev)))
-        captured = self._captured_step(samples)
-        for _ in range(epochs):
+        for cb in callbacks:
+            cb.on_train_begin()
+        for epoch in range(epochs):
+            for cb in callbacks:
+                cb.on_epoch_begin(epoch, {})
+            opt = self.optimizer.spec(device_lr=bool(callbacks))
+            # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
+            # the descriptor on this stream, behind the previous epoch's last update
+            captured = self._captured_step(samples, opt)
+            self.net._sync_lr(opt)
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
@@ -400,11 +435,17 @@ class Model:
             tot = tot_dev.cpu().numpy()
             if verbose:
                 print(f" - {time.time() - t0:.1f}s")
-            for key, v in zip(("loss", "ClassificationLayer_loss", "RegressionLayer_loss"), tot / max(steps, 1)):
-                hist.history.setdefault(key, []).append(float(v))
+            logs = {key: float(v) for key, v in zip(("loss", "ClassificationLayer_loss", "RegressionLayer_loss"),
+                                                    tot / max(steps, 1))}
+            for cb in callbacks:
+                cb.on_epoch_end(epoch, logs)
+            for key, v in logs.items():
+                hist.history.setdefault(key, []).append(v)
+        for cb in callbacks:
+            cb.on_train_end()
         return hist
 
-    def _captured_step(self, samples):
+    def _captured_step(self, samples, opt):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
@@ -422,7 +463,6 @@ class Model:
                 return None
         dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         need = max(int(p.shape[0]) for p in pts)
-        opt = self.optimizer.spec()
         # the full optimizer config: a re-compile with another optimizer records a new plan
         key = (key0, dtype, self.loss, opt.config, id(self.net), torch.cuda.current_stream().cuda_stream)
         cur = getattr(self, "_captured", None)
@@ -489,10 +529,10 @@ class Model:
         if self.optimizer is not None:
             o = self.optimizer
             if isinstance(o, optimizers.Adam):
-                opt = dict(class_name="Adam", lr=o.lr, decay=o.decay, beta_1=o.beta_1, beta_2=o.beta_2, epsilon=o.epsilon,
+                opt = dict(class_name="Adam", lr=_serialize_rate(o.lr), decay=o.decay, beta_1=o.beta_1, beta_2=o.beta_2, epsilon=o.epsilon,
                            amsgrad=o.amsgrad)
             else:
-                opt = dict(lr=o.lr, decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
+                opt = dict(lr=_serialize_rate(o.lr), decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
             p = self.net.params
             for name in o.spec().slots:
                 buf = self.net.slot(name)
@@ -514,7 +554,8 @@ def createModel(nx, ny, nz, maxPoints):
 def load_model(path, custom_objects=None):
     """load_model(model_path, custom_objects={'RepeatLayer':…, 'MaxPoolingVFELayer':…}) (:337-338, Predict.py:51-52).
     Reads Keras HDF5 files (the reference's own checkpoints or Model.save's) and the .npz variant.  Like Keras, a file
-    that carries a training_config (SGD or Adam) comes back compiled, with the saved iteration count and optimizer slots."""
+    that carries a training_config (SGD or Adam) comes back compiled, with the saved iteration count and optimizer slots;
+    a learning-rate schedule in it is rebuilt, and continues from that iteration count."""
     with open(path, "rb") as f:
         magic = f.read(8)
     dev = _lib.require_gpu()
@@ -530,11 +571,14 @@ def load_model(path, custom_objects=None):
     m = Model(ck["nx"], ck["ny"], ck["nz"], ck["maxPoints"], params=ParamStore(dev, init=ck["params"]))
     o = ck["optimizer"]
     if o is not None:
+        lr = o["lr"]
+        if isinstance(lr, dict):
+            lr = lr_schedules.deserialize(lr)
         if o.get("class_name", "SGD") == "Adam":
-            opt = optimizers.Adam(learning_rate=o["lr"], decay=o["decay"], beta_1=o["beta_1"], beta_2=o["beta_2"],
+            opt = optimizers.Adam(learning_rate=lr, decay=o["decay"], beta_1=o["beta_1"], beta_2=o["beta_2"],
                                   epsilon=o["epsilon"], amsgrad=o["amsgrad"])
         else:
-            opt = optimizers.SGD(lr=o["lr"], decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
+            opt = optimizers.SGD(lr=lr, decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
         m.compile(optimizer=opt, loss=['mse', 'mse'])
         m.net.iterations = ck["iterations"]
         p = m.net.params

@@ -13,12 +13,14 @@ model_training.py:299):
     up_b  : concat[..., 256b:256(b+1)] = deconv(relu(bn(y_{b,q})))
     head  : (M,16) = concat @ [W_cls | W_reg] + bias     (cls = [:, :2], reg = [:, 2:])
 """
+import ctypes
+import json
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, lr_schedules, ops
 from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
@@ -29,13 +31,22 @@ class OptimizerSpec:
     SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295).
 
         sgd    momentum == 0: no slot;  momentum > 0: "velocity" (v <- m*v - lr_t*g, then w <- w + v, or Nesterov)
-        adam   "m", "v", and "vhat" with amsgrad"""
+        adam   "m", "v", and "vhat" with amsgrad
+
+    lr is a number or a LearningRateSchedule (lisec_amd.lr_schedules).  With a schedule, or with device_lr=True (a
+    number that may change between steps, e.g. from a LearningRateScheduler callback), the update kernels read lr_t from
+    LisecNet's device descriptor (lisec_lr_schedule), which holds `lr_descriptor`; otherwise (lr, decay) are kernel
+    arguments, as they always were."""
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, amsgrad=False):
+                 epsilon=1e-7, amsgrad=False, device_lr=False):
         if kind not in ("sgd", "adam"):
             raise ValueError(f"unknown optimizer kind {kind!r}")
-        self.kind, self.lr, self.decay = kind, float(lr), float(decay)
+        self.schedule = lr if isinstance(lr, lr_schedules.LearningRateSchedule) else None
+        self.kind, self.lr, self.decay = kind, (lr if self.schedule is not None else float(lr)), float(decay)
+        self.device_lr = bool(device_lr) or self.schedule is not None
+        # validates a schedule: NotImplementedError for one of the user's own, ValueError past the device's limits
+        self.lr_descriptor = lr_schedules.descriptor(self.lr, self.decay) if self.device_lr else None
         if kind == "sgd":
             self.momentum, self.nesterov = float(momentum), bool(nesterov)
             if self.momentum < 0:
@@ -47,10 +58,18 @@ class OptimizerSpec:
 
     @property
     def config(self):
-        """Every hyper-parameter, hashable: two specs with equal configs issue the same launches."""
+        """Every hyper-parameter, hashable: two specs with equal configs issue the same launches.  A schedule enters with
+        its whole Keras config; a number read from the device descriptor (device_lr) does not enter at all -- like the
+        iteration count, it is data of the step, not of its launches."""
+        if self.schedule is not None:
+            rate = ("schedule", json.dumps(lr_schedules.serialize(self.schedule), sort_keys=True))
+        elif self.device_lr:
+            rate = ("device",)
+        else:
+            rate = self.lr
         if self.kind == "sgd":
-            return ("sgd", self.lr, self.decay, self.momentum, self.nesterov)
-        return ("adam", self.lr, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
+            return ("sgd", rate, self.decay, self.momentum, self.nesterov)
+        return ("adam", rate, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
 
     @property
     def slots(self):
@@ -259,6 +278,10 @@ class LisecNet:
         # that a captured step can be replayed; the host mirror is what save()/load_model() and the tests read
         self._iter_dev = torch.zeros(2, dtype=torch.int64, device=dev)
         self._iterations = 0
+        # learning-rate descriptor (lisec_lr_schedule) of the OptimizerSpecs with device_lr, at a fixed address like the
+        # iteration count; _sync_lr rewrites it, stream-ordered, when a step needs other contents
+        self._lr_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
+        self._lr_host = None
         self.loss_out = torch.zeros(3, dtype=f32, device=dev)
 
     @property
@@ -1057,11 +1080,31 @@ class LisecNet:
         self._prepare_training()
         return dict(self._slots)
 
+    def _sync_lr(self, opt):
+        """Makes the device learning-rate descriptor hold opt.lr_descriptor (nothing for a spec without device_lr): a
+        copy on the current stream, behind every update already enqueued, when the contents differ from the last ones
+        written.  A recorded step plan does not re-issue the copy; Model.fit calls this before the steps of an epoch."""
+        if not opt.device_lr:
+            return
+        raw = bytes(opt.lr_descriptor)
+        if self._lr_host is None or bytes(self._lr_host) != raw:
+            ops.lr_schedule_set(self._lr_dev, opt.lr_descriptor)
+            self._lr_host = opt.lr_descriptor                 # kept alive: the source of the copy
+
     def _update(self, opt, lo, hi, advance):
         """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step)."""
         th, g = self.params.theta[lo:hi], self.grad[lo:hi]
         sl = [self.slot(name)[lo:hi] for name in opt.slots]
-        if opt.kind == "adam":
+        if opt.device_lr:
+            # lr_t from the descriptor (a schedule, or a rate a callback may change): the *_sched entries
+            self._sync_lr(opt)
+            if opt.kind == "adam":
+                ops.adam_step_sched(th, g, sl[0], sl[1], sl[2] if opt.amsgrad else None, self._lr_dev, opt.beta_1,
+                                    opt.beta_2, opt.epsilon, self._iter_dev, advance=advance)
+            else:
+                ops.sgd_step_sched(th, g, sl[0] if sl else None, self._lr_dev, opt.momentum, opt.nesterov, self._iter_dev,
+                                   advance=advance)
+        elif opt.kind == "adam":
             ops.adam_step_dev(th, g, sl[0], sl[1], sl[2] if opt.amsgrad else None, opt.lr, opt.decay, opt.beta_1,
                               opt.beta_2, opt.epsilon, self._iter_dev, advance=advance)
         elif opt.momentum > 0 and opt.nesterov:
@@ -1097,7 +1140,7 @@ class LisecNet:
         hi = self.params.theta.numel()
         if self._early is not None:
             lo, early_opt = self._early
-            if early_opt != opt:
+            if early_opt != opt or (opt.device_lr and bytes(early_opt.lr_descriptor) != bytes(opt.lr_descriptor)):
                 raise RuntimeError(f"apply_gradients(opt={opt}) after an early update with {early_opt}: the variables "
                                    f"would be updated by two different optimizers")
             hi = lo                              # the tail of the buffer was updated during the backward pass
@@ -1312,7 +1355,9 @@ class RecordedStep(_StepPlans):
                order and therefore every voxel and feature row are exactly those of the unpadded sweep
       targets  (Ho,Wo,2) / (Ho,Wo,14) static buffers
       lr_t     derived by the optimizer kernels from the device iteration counter (lisec_sgd_nesterov_step_dev,
-               lisec_sgd_step_dev, lisec_adam_step_dev)
+               lisec_sgd_step_dev, lisec_adam_step_dev) -- and with a learning-rate schedule or a rate that changes
+               between epochs, from the descriptor LisecNet._lr_dev (lisec_*_step_sched), which LisecNet._sync_lr
+               rewrites between replays
 
     Record and replay on ONE torch stream (the current stream at construction).  Data parallel (allreduce=): the gradient
     exchange is part of the plan."""

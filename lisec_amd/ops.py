@@ -398,6 +398,33 @@ def adam_step_dev(theta, grad, m, v, vhat, lr, decay, beta_1, beta_2, epsilon, s
                                                float(epsilon), _lib.ptr(state), 1 if advance else 0, _lib.current_stream()))
 
 
+def lr_schedule_set(dev_desc, desc):
+    """Stream-ordered write of the learning-rate descriptor `desc` (an _lib.LrSchedule, validated by the library) into
+    dev_desc, a device buffer of ctypes.sizeof(_lib.LrSchedule) bytes (lisec_lr_schedule_set)."""
+    _lib.check(_lib.load().lisec_lr_schedule_set(_lib.ptr(dev_desc), ctypes.byref(desc), _lib.current_stream()))
+
+
+def lr_schedule_eval(dev_desc, state, n, out):
+    """out[k] = lr_t at iteration state[0] + k, k < n (lisec_lr_schedule_eval; state is not advanced)."""
+    _lib.check(_lib.load().lisec_lr_schedule_eval(_lib.ptr(dev_desc), _lib.ptr(state), int(n), _lib.ptr(out),
+                                                  _lib.current_stream()))
+
+
+def sgd_step_sched(theta, grad, velocity, dev_desc, momentum, nesterov, state, advance=True):
+    """sgd_step_dev with lr_t from the device descriptor dev_desc (lisec_sgd_step_sched)."""
+    _lib.check(_lib.load().lisec_sgd_step_sched(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity), theta.numel(),
+                                                _lib.ptr(dev_desc), float(momentum), 1 if nesterov else 0,
+                                                _lib.ptr(state), 1 if advance else 0, _lib.current_stream()))
+
+
+def adam_step_sched(theta, grad, m, v, vhat, dev_desc, beta_1, beta_2, epsilon, state, advance=True):
+    """adam_step_dev with lr_t from the device descriptor dev_desc (lisec_adam_step_sched); vhat not None: AMSGrad."""
+    _lib.check(_lib.load().lisec_adam_step_sched(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(m), _lib.ptr(v),
+                                                 _lib.ptr(vhat), theta.numel(), _lib.ptr(dev_desc), float(beta_1),
+                                                 float(beta_2), float(epsilon), _lib.ptr(state), 1 if advance else 0,
+                                                 _lib.current_stream()))
+
+
 def fold_depth(x, out, D, HW, C, inverse=False, mask=None):
     """(D,H,W,C) <-> (H,W,C*D) (Permute + Reshape of model_training.py:242-243); inverse: gradient, ReLU-gated by mask."""
     _lib.check(_lib.load().lisec_fold_depth(_lib.ptr(x), _lib.ptr(out), D, HW, C, 1 if inverse else 0, _lib.ptr(mask),
