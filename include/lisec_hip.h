@@ -594,6 +594,12 @@ int lisec_rpn_loss(const float* head, const float* y_cls, const float* y_reg, lo
                    float grad_scale, float* dhead, float* loss_out, void* workspace, size_t workspace_bytes,
                    lisec_stream_t stream);
 
+/* The evaluation loss (Model.evaluate, validation in fit): the [total, class, regression] lisec_rpn_loss writes to
+ * loss_out for the same inputs, bit for bit, without a gradient.  They are ADDED, as doubles, to acc[0..2], and acc[3] is
+ * incremented (the number of sweeps); acc (double[4], device) is zeroed by the caller.  No atomics: deterministic. */
+int lisec_rpn_loss_eval(const float* head, const float* y_cls, const float* y_reg, long long M, int kind, double* acc,
+                        void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+
 /* optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (:295) on the flat parameter buffer:
  * v <- m*v - lr_t*g;  w <- w + m*v - lr_t*g;  lr_t = lr/(1 + decay*iterations) is computed by the caller. */
 int lisec_sgd_nesterov_step(float* theta, const float* grad, float* velocity, long long n, float lr_t,

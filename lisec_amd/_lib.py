@@ -221,6 +221,8 @@ def _declare(lib):
     lib.lisec_colsum.argtypes = [P, c_int, LL, c_int, P, P, c_size_t, P]
     lib.lisec_rpn_loss.restype = c_int
     lib.lisec_rpn_loss.argtypes = [P, P, P, LL, c_int, c_float, P, P, P, c_size_t, P]
+    lib.lisec_rpn_loss_eval.restype = c_int
+    lib.lisec_rpn_loss_eval.argtypes = [P, P, P, LL, c_int, P, P, c_size_t, P]
     lib.lisec_sgd_nesterov_step.restype = c_int
     lib.lisec_sgd_nesterov_step.argtypes = [P, P, P, LL, c_float, c_float, P]
     lib.lisec_sgd_nesterov_step_dev.restype = c_int
@@ -328,7 +330,7 @@ def load():
 
 # The schedule knobs of the Python host layer (knob()).  Every other key of LISEC_TUNING must be a lisec_tuning field.
 HOST_KNOBS = frozenset(("winograd", "step_plan", "pipeline_voxels", "field_conv", "field_max_voxels", "vfe_bwd_tiled",
-                        "vfe_tiled_min_points", "comm_priority"))
+                        "vfe_tiled_min_points", "comm_priority", "eval_plan"))
 
 
 def _tuning_spec():

@@ -1,7 +1,11 @@
-"""tf.keras 2.4 callbacks for Model.fit(callbacks=...), exposed as lisec_amd.model_training.callbacks: the Callback base
-class (set_model, set_params, on_train_begin / on_train_end, on_epoch_begin / on_epoch_end) and LearningRateScheduler.
-A learning rate set between epochs reaches the update kernels through the device descriptor of LisecNet, written on
-the stream of the step: the recorded step plan is not recorded again."""
+"""tf.keras 2.4 callbacks for Model.fit(callbacks=...) and Model.evaluate(callbacks=...), exposed as
+lisec_amd.model_training.callbacks: the Callback base class (set_model, set_params, on_train_begin / on_train_end,
+on_epoch_begin / on_epoch_end, on_test_begin / on_test_end), LearningRateScheduler, EarlyStopping, ModelCheckpoint and
+ReduceLROnPlateau.  A learning rate set between epochs reaches the update kernels through the device descriptor of
+LisecNet, written on the stream of the step: the recorded step plan is not recorded again.  There are no per-batch hooks:
+the fit loop reads nothing back from the device inside an epoch."""
+import warnings
+
 import numpy as np
 
 from .lr_schedules import LearningRateSchedule
@@ -31,6 +35,221 @@ class Callback:
 
     def on_epoch_end(self, epoch, logs=None):
         pass
+
+    def on_test_begin(self, logs=None):
+        """Called by Model.evaluate, and by the validation inside Model.fit, before the first evaluated sweep."""
+        pass
+
+    def on_test_end(self, logs=None):
+        """Called with the evaluation's logs (loss, ClassificationLayer_loss, RegressionLayer_loss) after it."""
+        pass
+
+
+def _monitor_op(mode, monitor, name):
+    """Keras' choice of comparison: 'min' -> np.less, 'max' -> np.greater, 'auto' -> np.greater if 'acc' is in the
+    monitored name, np.less otherwise.  An unknown mode warns and falls back to 'auto'."""
+    if mode not in ("auto", "min", "max"):
+        warnings.warn(f"{name} mode {mode} is unknown, fallback to auto mode.")
+        mode = "auto"
+    if mode == "min" or (mode == "auto" and "acc" not in monitor):
+        return np.less
+    return np.greater
+
+
+def _lr_number(optimizer, name):
+    """optimizer.lr as a float; a LearningRateSchedule is refused (the callback would overwrite it)."""
+    if not hasattr(optimizer, "lr"):
+        raise ValueError('Optimizer must have a "lr" attribute.')
+    if isinstance(optimizer.lr, LearningRateSchedule):
+        raise ValueError(f"{name} sets optimizer.lr, which is a {type(optimizer.lr).__name__} schedule here: give the "
+                         f"optimizer a number, or keep the schedule without this callback")
+    return float(optimizer.lr)
+
+
+class EarlyStopping(Callback):
+    """Stops training when the monitored value has stopped improving (tf.keras 2.4 rules):
+
+    - mode 'min' / 'max' / 'auto' ('auto': max if 'acc' is in `monitor`, else min); min_delta is taken as |min_delta|,
+      negated in min mode: an epoch improves when monitor_op(current - min_delta, best).
+    - on_train_begin resets wait = 0, stopped_epoch = 0 and best = baseline when given (the value to beat), else +inf
+      (min) / -inf (max).
+    - on_epoch_end: an improvement sets best = current, wait = 0 and, with restore_best_weights, snapshots the
+      variables; otherwise wait += 1 and at wait >= patience: stopped_epoch = epoch, model.stop_training = True and, with
+      restore_best_weights, the snapshot is put back -- theta and the BatchNormalization moving statistics (Keras'
+      get_weights / set_weights), not the optimizer slots.  No snapshot (no epoch beat the baseline): nothing is restored.
+    - a monitored key missing from the logs warns and skips the epoch.
+    The model's variables are snapshotted by model._snapshot_weights() and put back by model._restore_weights(w)."""
+
+    def __init__(self, monitor="val_loss", min_delta=0, patience=0, verbose=0, mode="auto", baseline=None,
+                 restore_best_weights=False):
+        super().__init__()
+        self.monitor, self.patience, self.verbose, self.baseline = monitor, patience, verbose, baseline
+        self.min_delta = abs(min_delta)
+        self.wait, self.stopped_epoch = 0, 0
+        self.restore_best_weights, self.best_weights = restore_best_weights, None
+        self.monitor_op = _monitor_op(mode, monitor, "EarlyStopping")
+        self.min_delta *= 1 if self.monitor_op == np.greater else -1
+
+    def on_train_begin(self, logs=None):
+        self.wait, self.stopped_epoch = 0, 0
+        if self.baseline is not None:
+            self.best = self.baseline
+        else:
+            self.best = np.inf if self.monitor_op == np.less else -np.inf
+        self.best_weights = None
+
+    def on_epoch_end(self, epoch, logs=None):
+        current = self.get_monitor_value(logs)
+        if current is None:
+            return
+        if self.monitor_op(current - self.min_delta, self.best):
+            self.best = current
+            self.wait = 0
+            if self.restore_best_weights:
+                self.best_weights = self.model._snapshot_weights()
+        else:
+            self.wait += 1
+            if self.wait >= self.patience:
+                self.stopped_epoch = epoch
+                self.model.stop_training = True
+                if self.restore_best_weights and self.best_weights is not None:
+                    if self.verbose > 0:
+                        print("Restoring model weights from the end of the best epoch.")
+                    self.model._restore_weights(self.best_weights)
+
+    def on_train_end(self, logs=None):
+        if self.stopped_epoch > 0 and self.verbose > 0:
+            print(f"Epoch {self.stopped_epoch + 1:05d}: early stopping")
+
+    def get_monitor_value(self, logs):
+        logs = logs or {}
+        value = logs.get(self.monitor)
+        if value is None:
+            warnings.warn(f"Early stopping conditioned on metric `{self.monitor}` which is not available. "
+                          f"Available metrics are: {','.join(logs.keys())}")
+        return value
+
+
+class ModelCheckpoint(Callback):
+    """Saves the model (model.save) at the end of every epoch (tf.keras 2.4 rules):
+
+    - the path is filepath.format(epoch=epoch + 1, **logs), e.g. 'ck-{epoch:02d}-{val_loss:.4f}.h5'.
+    - save_best_only: saves only when monitor_op(current, best) -- no min_delta -- with best starting at +inf (min) /
+      -inf (max) when the callback is made; mode as EarlyStopping ('auto': max if 'acc' is in `monitor`, else min).  A
+      monitored key missing from the logs warns and skips the save.
+    - data parallel: every rank calls model.save (identical logs on every rank), which writes from rank 0 behind a
+      barrier.
+    save_weights_only=True and a save_freq other than 'epoch' raise NotImplementedError."""
+
+    def __init__(self, filepath, monitor="val_loss", verbose=0, save_best_only=False, save_weights_only=False,
+                 mode="auto", save_freq="epoch", options=None, **kwargs):
+        super().__init__()
+        if save_weights_only:
+            raise NotImplementedError("ModelCheckpoint(save_weights_only=True): save_weights is not implemented; "
+                                      "model.save writes the whole model")
+        if save_freq != "epoch":
+            raise NotImplementedError(f"ModelCheckpoint(save_freq={save_freq!r}): only save_freq='epoch' is implemented "
+                                      f"(there are no per-batch hooks)")
+        if kwargs:
+            raise TypeError(f"ModelCheckpoint: unexpected keyword argument(s) {', '.join(sorted(kwargs))}")
+        self.filepath, self.monitor, self.verbose, self.save_best_only = str(filepath), monitor, verbose, save_best_only
+        self.monitor_op = _monitor_op(mode, monitor, "ModelCheckpoint")
+        self.best = np.inf if self.monitor_op == np.less else -np.inf
+
+    def on_epoch_end(self, epoch, logs=None):
+        logs = logs or {}
+        filepath = self.filepath.format(epoch=epoch + 1, **logs)
+        if self.save_best_only:
+            current = logs.get(self.monitor)
+            if current is None:
+                warnings.warn(f"Can save best model only with {self.monitor} available, skipping.")
+                return
+            if not self.monitor_op(current, self.best):
+                if self.verbose > 0:
+                    print(f"\nEpoch {epoch + 1:05d}: {self.monitor} did not improve from {self.best:0.5f}")
+                return
+            if self.verbose > 0:
+                print(f"\nEpoch {epoch + 1:05d}: {self.monitor} improved from {self.best:0.5f} to {current:0.5f}, "
+                      f"saving model to {filepath}")
+            self.best = current
+        elif self.verbose > 0:
+            print(f"\nEpoch {epoch + 1:05d}: saving model to {filepath}")
+        self.model.save(filepath)
+
+
+class ReduceLROnPlateau(Callback):
+    """Multiplies the learning rate by `factor` when the monitored value has stopped improving (tf.keras 2.4 rules):
+
+    - factor >= 1 raises ValueError.  mode 'min' (or 'auto' without 'acc' in `monitor`): improvement is
+      current < best - min_delta, best starting at +inf; 'max': current > best + min_delta, from -inf.  on_train_begin
+      resets best, wait and the cooldown counter.
+    - on_epoch_end writes logs['lr'] (the rate of the epoch that ended).  Missing monitor key: warn and skip.  In cooldown
+      the counter counts down and wait stays 0; an improvement sets best and wait = 0; otherwise, out of cooldown,
+      wait += 1 and at wait >= patience, if lr > min_lr: lr = max(lr * factor, min_lr), the cooldown starts
+      (cooldown_counter = cooldown) and wait = 0.
+    - the optimizer's rate must be a number: a LearningRateSchedule is refused (ValueError), as LearningRateScheduler
+      does.  The new rate reaches the recorded step through the device descriptor (Model.fit), without recording it again."""
+
+    def __init__(self, monitor="val_loss", factor=0.1, patience=10, verbose=0, mode="auto", min_delta=1e-4, cooldown=0,
+                 min_lr=0, **kwargs):
+        super().__init__()
+        if factor >= 1.0:
+            raise ValueError("ReduceLROnPlateau does not support a factor >= 1.0.")
+        if "epsilon" in kwargs:
+            min_delta = kwargs.pop("epsilon")
+            warnings.warn("`epsilon` argument is deprecated and will be removed, use `min_delta` instead.")
+        if kwargs:
+            raise TypeError(f"ReduceLROnPlateau: unexpected keyword argument(s) {', '.join(sorted(kwargs))}")
+        self.monitor, self.factor, self.min_lr, self.min_delta = monitor, float(factor), float(min_lr), float(min_delta)
+        self.patience, self.verbose, self.cooldown, self.mode = patience, verbose, cooldown, mode
+        self._reset()
+
+    def _reset(self):
+        if self.mode not in ("auto", "min", "max"):
+            warnings.warn(f"Learning rate reduction mode {self.mode} is unknown, fallback to auto mode.")
+            self.mode = "auto"
+        if self.mode == "min" or (self.mode == "auto" and "acc" not in self.monitor):
+            self.monitor_op = lambda a, b: np.less(a, b - self.min_delta)
+            self.best = np.inf
+        else:
+            self.monitor_op = lambda a, b: np.greater(a, b + self.min_delta)
+            self.best = -np.inf
+        self.cooldown_counter = 0
+        self.wait = 0
+
+    def on_train_begin(self, logs=None):
+        _lr_number(self.model.optimizer, "ReduceLROnPlateau")       # a schedule is refused before the first epoch
+        self._reset()
+
+    def in_cooldown(self):
+        return self.cooldown_counter > 0
+
+    def on_epoch_end(self, epoch, logs=None):
+        logs = logs if logs is not None else {}
+        optimizer = self.model.optimizer
+        logs["lr"] = _lr_number(optimizer, "ReduceLROnPlateau")
+        current = logs.get(self.monitor)
+        if current is None:
+            warnings.warn(f"Learning rate reduction is conditioned on metric `{self.monitor}` which is not available. "
+                          f"Available metrics are: {','.join(logs.keys())}")
+            return
+        if self.in_cooldown():
+            self.cooldown_counter -= 1
+            self.wait = 0
+        if self.monitor_op(current, self.best):
+            self.best = current
+            self.wait = 0
+        elif not self.in_cooldown():
+            self.wait += 1
+            if self.wait >= self.patience:
+                old_lr = float(optimizer.lr)
+                if old_lr > self.min_lr:
+                    new_lr = max(old_lr * self.factor, self.min_lr)
+                    optimizer.lr = new_lr
+                    if self.verbose > 0:
+                        print(f"\nEpoch {epoch + 1:05d}: ReduceLROnPlateau reducing learning rate to {new_lr}.")
+                    self.cooldown_counter = self.cooldown
+                    self.wait = 0
 
 
 class LearningRateScheduler(Callback):

@@ -191,6 +191,67 @@ k_loss_finalize(const double* __restrict__ parts, int nparts, double M, float* _
     }
 }
 
+// Evaluation loss (Model.evaluate, fit's validation): k_loss's per-element losses, block partition and partials without
+// the gradient store, then k_loss_finalize's reduction order, so the fp32 [total, class, regression] of a sweep are the
+// bits lisec_rpn_loss writes to loss_out.  They are added, as doubles, to acc[0..2] and the sweep is counted in acc[3]
+// by the single finalizing thread: stream-ordered, no atomics, the same bits on every run.
+__global__ void __launch_bounds__(kEwThreads)
+k_loss_eval(const float* __restrict__ head, const float* __restrict__ ycls, const float* __restrict__ yreg,
+            long long M, int kind, double* __restrict__ parts) {
+    __shared__ double red[2][kEwThreads / 64];
+    double lc = 0.0, lr = 0.0;
+    for (long long i = blockIdx.x * (long long)kEwThreads + threadIdx.x; i < M * 16; i += (long long)gridDim.x * kEwThreads) {
+        const long long m = i >> 4;
+        const int c = (int)(i & 15);
+        const float p = head[i];
+        if (c < 2) {
+            const float t = ycls[m * 2 + c];
+            if (kind == 0) {
+                const float d = p - t;
+                lc += (double)d * d;
+            } else {
+                const float tt = fminf(fmaxf(t, 0.f), 1.f);
+                lc += (double)(fmaxf(p, 0.f) - p * tt + log1pf(expf(-fabsf(p))));
+            }
+        } else {
+            const float t = yreg[m * 14 + (c - 2)];
+            const float d = p - t;
+            if (kind == 0) {
+                lr += (double)d * d;
+            } else {
+                const float ad = fabsf(d);
+                lr += (double)(ad < 1.f ? 0.5f * d * d : ad - 0.5f);
+            }
+        }
+    }
+    lc = wave_sum(lc); lr = wave_sum(lr);
+    if (lane_id() == 0) { red[0][threadIdx.x >> 6] = lc; red[1][threadIdx.x >> 6] = lr; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double a = 0.0;
+        for (int k = 0; k < kEwThreads / 64; ++k) a += red[threadIdx.x][k];
+        parts[(size_t)blockIdx.x * 2 + threadIdx.x] = a;
+    }
+}
+
+__global__ void __launch_bounds__(256)
+k_loss_eval_finalize(const double* __restrict__ parts, int nparts, double M, double* __restrict__ acc) {
+    __shared__ double red[2][256];
+    double a = 0.0, b = 0.0;
+    for (int k = threadIdx.x; k < nparts; k += 256) { a += parts[2 * k]; b += parts[2 * k + 1]; }
+    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        a = red[0][0] / (M * 2.0); b = red[1][0] / (M * 14.0);
+        const float tot = (float)(a + b), cls = (float)a, reg = (float)b;
+        acc[0] += (double)tot; acc[1] += (double)cls; acc[2] += (double)reg; acc[3] += 1.0;
+    }
+}
+
 // optimizers.SGD(lr, decay, momentum, nesterov=True) (model_training.py:295):
 //   v <- m*v - lr_t*g ;  w <- w + m*v - lr_t*g       (lr_t = lr/(1+decay*iter), computed by the host)
 __global__ void k_sgd_nesterov(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ v,
@@ -417,6 +478,23 @@ extern "C" int lisec_rpn_loss(const float* head, const float* y_cls, const float
     int nb = ew_blocks(M * 16);
     LISEC_LAUNCH(k_loss, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, grad_scale, dhead, parts);
     LISEC_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, loss_out);
+    LISEC_LAUNCH_CHECK();
+    return LISEC_OK;
+}
+
+extern "C" int lisec_rpn_loss_eval(const float* head, const float* y_cls, const float* y_reg, long long M, int kind,
+                                   double* acc, void* workspace, size_t workspace_bytes, lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(head && y_cls && y_reg && acc && workspace && M > 0, "NULL pointer");
+    LISEC_CHECK_ARG(kind == 0 || kind == 1, "loss kind must be 0 (mse+mse) or 1 (sigmoid-CE + SmoothL1)");
+    if (workspace_bytes < lisec_eltwise_workspace_bytes()) {
+        set_error("eltwise workspace too small");
+        return LISEC_ENOSPC;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    double* parts = static_cast<double*>(workspace);
+    int nb = ew_blocks(M * 16);                       // lisec_rpn_loss's partition: the same partials
+    LISEC_LAUNCH(k_loss_eval, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, parts);
+    LISEC_LAUNCH(k_loss_eval_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, acc);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }

@@ -3,14 +3,17 @@
     get_voxel, VFE_preprocessing, combine_lidar_data, rotate_points, RepeatLayer, MaxPoolingVFELayer,
     createModel, load_model, optimizers.SGD, optimizers.Adam, train, train_with_model
 
-and, for Model.fit, the tf.keras 2.4 learning-rate schedules (optimizers.schedules) and callbacks
-(callbacks.Callback, callbacks.LearningRateScheduler).
+and, for Model.fit / Model.evaluate, the tf.keras 2.4 learning-rate schedules (optimizers.schedules) and callbacks
+(callbacks.Callback, LearningRateScheduler, EarlyStopping, ModelCheckpoint, ReduceLROnPlateau).
 
 The Keras graph is replaced by lisec_amd.network.LisecNet (HIP kernels behind the C ABI); lidar sweeps
 stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacked in host RAM
 (reference model_training.py:279,285).  There is no CPU fallback.
 """
+import collections.abc
 import json
+import math
+import numbers
 import os
 import time
 
@@ -18,7 +21,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, lr_schedules
+from . import callbacks, lr_schedules, ops
 from .network import LisecNet, OptimizerSpec
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
@@ -304,6 +307,48 @@ class History:
         self.history = {}
 
 
+_LOSS_NAMES = ("loss", "ClassificationLayer_loss", "RegressionLayer_loss")
+
+
+def _validation_split_at(n, validation_split):
+    """Keras 2.4 fit(validation_split=f): the first floor(n * (1 - f)) sweeps train, the tail validates (taken before
+    any shuffling).  ValueError for f outside (0, 1) or a split that leaves either part empty."""
+    f = float(validation_split)
+    if not 0.0 < f < 1.0:
+        raise ValueError(f"validation_split must lie in (0, 1), got {validation_split}")
+    split_at = int(math.floor(n * (1.0 - f)))
+    if split_at == 0 or split_at == n:
+        raise ValueError(f"Training data contains {n} samples, which is not sufficient to split it into a validation and "
+                         f"training set as specified by `validation_split={validation_split}`. Either provide more data, "
+                         f"or a different value for the `validation_split` argument.")
+    return split_at
+
+
+def _should_validate(epoch, validation_freq):
+    """Keras 2.4: an int validates when (epoch + 1) % validation_freq == 0, a container (list, set, range, ...) on the
+    1-based epochs it holds."""
+    if isinstance(validation_freq, bool):
+        raise ValueError(f"Expected `validation_freq` to be a list or int. Received: validation_freq={validation_freq!r}")
+    if isinstance(validation_freq, numbers.Integral):
+        if validation_freq < 1:
+            raise ValueError("`validation_freq` can not be less than 1.")
+        return (epoch + 1) % int(validation_freq) == 0
+    if isinstance(validation_freq, collections.abc.Container) and not isinstance(validation_freq, (str, bytes)):
+        return epoch + 1 in validation_freq
+    raise ValueError(f"Expected `validation_freq` to be a list or int. Received: validation_freq={validation_freq!r}")
+
+
+def _grid_key(samples):
+    """The voxel grid every sample shares, when each is a voxelised sweep that still holds its device points; else None
+    (e.g. dense arrays turned into samples: no point cloud to voxelise again)."""
+    pts = [getattr(s, "_keepalive", None) for s in samples]
+    if not samples or any(p is None or not p.is_cuda for p in pts):
+        return None
+    keys = {(c.xSize, c.ySize, c.zSize, c.sampleSize, c.maxVoxelX, c.maxVoxelY, c.maxVoxelZ)
+            for c in (s.cfg for s in samples)}
+    return keys.pop() if len(keys) == 1 else None
+
+
 class Model:
     """What createModel returns: the subset of the keras.Model interface the reference uses."""
 
@@ -312,6 +357,7 @@ class Model:
         self.net = LisecNet(nx, ny, nz, maxPoints, params=params)
         self.optimizer, self.loss = None, None
         self.dp = None
+        self.stop_training = False          # set by a callback (EarlyStopping): fit ends after the epoch
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             from .parallel import DataParallel
             self.dp = DataParallel(self.net.device)
@@ -357,14 +403,21 @@ class Model:
             raise ValueError("expected SparseVoxels / list of them / dense (n,D,H,W,T,6) array")
         return [dense_to_sample(a, self.net.device) for a in arr]
 
-    def fit(self, x, y, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None):
+    def fit(self, x, y, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None,
+            validation_split=0.0, validation_data=None, validation_steps=None, validation_freq=1):
         """fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, epochs=1, steps_per_epoch=180)
         (model_training.py:299).  batch_size must be 1 (the reference's setting: BatchNormalization
         statistics are per sample).  With WORLD_SIZE > 1 whole samples are sharded over the ranks and the
         gradients averaged with one RCCL all-reduce per step.
         callbacks: a list of callbacks.Callback (LearningRateScheduler, or one's own), called as Keras does.  With
         callbacks the update kernels read the learning rate from the device descriptor, so that a rate set between
-        epochs reaches the recorded step without recording it again."""
+        epochs reaches the recorded step without recording it again.
+        validation_data=(x_val, [y_cls, y_reg]), or validation_split=f (the last floor-split fraction of x / y, taken
+        before shuffling; validation_data takes precedence): after the steps of an epoch that validation_freq selects (an
+        int: every validation_freq-th epoch; a container: those 1-based epochs), evaluate() runs on the validation sweeps
+        (validation_steps of them at most) with on_test_begin / on_test_end, and val_loss, val_ClassificationLayer_loss and
+        val_RegressionLayer_loss join the logs of on_epoch_end and History.  fit ends after any epoch whose callbacks set
+        model.stop_training."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if batch_size != 1:
@@ -375,6 +428,21 @@ class Model:
         n = len(samples)
         if len(ycls) < n or len(yreg) < n:
             raise ValueError("fewer label maps than samples")
+        val = None
+        if validation_data is not None:
+            if len(validation_data) > 2 and validation_data[2] is not None:
+                raise NotImplementedError("validation sample weights are not implemented")
+            val_samples = self._as_samples(validation_data[0])
+            val_y = validation_data[1]
+        elif validation_split:
+            at = _validation_split_at(n, validation_split)
+            val_samples, val_y = samples[at:], (ycls[at:n], yreg[at:n])
+            samples, n = samples[:at], at
+        if validation_data is not None or validation_split:
+            vn = len(val_samples) if validation_steps is None else min(len(val_samples), int(validation_steps) * batch_size)
+            val = (val_samples[:vn],) + self._labels(val_y, vn)
+            _should_validate(0, validation_freq)           # a malformed validation_freq is refused before any step
+        self.stop_training = False
         idx = list(range(n))
         if self.dp is not None:
             idx = self.dp.shard(idx)
@@ -437,10 +505,17 @@ class Model:
                 print(f" - {time.time() - t0:.1f}s")
             logs = {key: float(v) for key, v in zip(("loss", "ClassificationLayer_loss", "RegressionLayer_loss"),
                                                     tot / max(steps, 1))}
+            if val is not None and _should_validate(epoch, validation_freq):
+                vlogs = self._evaluate(*val, callbacks=callbacks, verbose=0)
+                logs.update({"val_" + key: v for key, v in vlogs.items()})
+                if verbose:
+                    print(" - ".join(f"val_{key}: {v:.4f}" for key, v in vlogs.items()))
             for cb in callbacks:
                 cb.on_epoch_end(epoch, logs)
             for key, v in logs.items():
                 hist.history.setdefault(key, []).append(v)
+            if self.stop_training:
+                break
         for cb in callbacks:
             cb.on_train_end()
         return hist
@@ -450,17 +525,12 @@ class Model:
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
         Otherwise (None) the Python schedule issues every step."""
-        if not _lib.knob("step_plan", True) or not samples:
+        if not _lib.knob("step_plan", True):
             return None
-        pts = [getattr(s, "_keepalive", None) for s in samples]
-        if any(p is None or not p.is_cuda for p in pts):
-            return None                       # e.g. dense arrays turned into samples: no point cloud to re-voxelise
-        c0 = samples[0].cfg
-        key0 = (c0.xSize, c0.ySize, c0.zSize, c0.sampleSize, c0.maxVoxelX, c0.maxVoxelY, c0.maxVoxelZ)
-        for s_ in samples:
-            c = s_.cfg
-            if (c.xSize, c.ySize, c.zSize, c.sampleSize, c.maxVoxelX, c.maxVoxelY, c.maxVoxelZ) != key0:
-                return None
+        key0 = _grid_key(samples)
+        if key0 is None:
+            return None
+        pts = [s._keepalive for s in samples]
         dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         need = max(int(p.shape[0]) for p in pts)
         # the full optimizer config: a re-compile with another optimizer records a new plan
@@ -479,6 +549,148 @@ class Model:
                             allreduce=self.dp.bucketed() if self.dp is not None else None)
         self._captured = (key, step)
         return step
+
+    def _eval_step(self, samples):
+        """The recorded evaluation sweep (lisec_amd.network.EvalStep: voxelise + forward(training=False) + eval loss, one
+        C call per sweep) when it applies -- as for _captured_step: every sample a voxelised sweep that still holds its
+        device points, one grid -- and LISEC_TUNING=eval_plan=1 asks for it.  Otherwise (None) the eager forward evaluates
+        each sweep: the default, as the inference forward is GPU-bound (~1.3 ms per Lyft-grid sweep) and the plan, which
+        voxelises every sweep again from its points, measured 3-4 % slower (tools/bench_eval.py)."""
+        if not _lib.knob("eval_plan", False):
+            return None
+        key0 = _grid_key(samples)
+        if key0 is None:
+            return None
+        pts = [s._keepalive for s in samples]
+        dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
+        need = max(int(p.shape[0]) for p in pts)
+        key = (key0, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream)
+        cur = getattr(self, "_eval_captured", None)
+        if cur is not None and cur[0] == key and cur[1].capacity >= need and cur[1].alloc_gen == _lib.alloc_generation():
+            return cur[1]
+        if cur is not None:
+            cur[1].close()
+        from .network import EvalStep
+        # the training step's voxeliser, whose workspace already holds a training sweep: a validation sweep no larger than
+        # the training ones then allocates nothing, and the recorded training step stays valid
+        train = getattr(self, "_captured", None)
+        if train is not None and train[0][0] == key0 and getattr(train[1], "plans", None):
+            vox = train[1].vox
+        else:
+            vox = Voxelizer(*key0[:3], key0[3], *key0[4:], device=self.net.device)
+        capacity = max(1024, -(-need // 4096) * 4096)
+        step = EvalStep(self.net, vox, capacity, dtype=dtype, loss=self.loss)
+        self._eval_captured = (key, step)
+        return step
+
+    def _labels(self, y, n):
+        """[y_cls, y_reg] -> float32 arrays holding at least n label maps of the model's output grid each."""
+        ycls = np.asarray(y[0], dtype=np.float32)
+        yreg = np.asarray(y[1], dtype=np.float32)
+        if len(ycls) < n or len(yreg) < n:
+            raise ValueError("fewer label maps than samples")
+        hw = self.net.Ho * self.net.Wo
+        if n and (ycls[0].size != hw * 2 or yreg[0].size != hw * 14):
+            raise ValueError(f"label maps must be ({self.net.Ho},{self.net.Wo},2) and ({self.net.Ho},{self.net.Wo},14)")
+        return ycls, yreg
+
+    def evaluate(self, x, y, batch_size=None, verbose=1, sample_weight=None, steps=None, callbacks=None,
+                 return_dict=False):
+        """model.evaluate(x, [y_cls, y_reg]) -> [loss, ClassificationLayer_loss, RegressionLayer_loss] (a dict with those
+        keys with return_dict=True): the compiled loss with inference BatchNormalization (the moving statistics), as a mean
+        over the evaluated sweeps.  The sweeps are independent, so every batch_size gives that value -- Keras' mean
+        weighted by batch size; batch_size (Keras' default 32) only sets what `steps` counts: steps * batch_size sweeps.
+        callbacks get on_test_begin / on_test_end.  Each sweep runs the eager forward(training=False), or, with
+        LISEC_TUNING=eval_plan=1 and voxelised sweeps, the recorded evaluation step (EvalStep), which pads every sweep to
+        its point capacity: the values of the eager path bit for bit on sweeps already padded to that capacity, and
+        equal within rounding on others (kernels that plan per capacity may sum in another order).  Data parallel: every
+        rank evaluates its share samples[rank::world] with the rank-mean moving statistics (what save() writes) and all
+        ranks return the same values.  Changes no variable, slot or iteration count."""
+        if self.optimizer is None:
+            raise RuntimeError("compile() the model first")
+        if sample_weight is not None:
+            raise NotImplementedError("evaluate(sample_weight=...) is not implemented")
+        samples = self._as_samples(x)
+        n = len(samples)
+        if steps is not None:
+            n = min(n, int(steps) * (32 if batch_size is None else int(batch_size)))
+        ycls, yreg = self._labels(y, n)
+        callbacks = list(callbacks or [])
+        for cb in callbacks:
+            cb.set_model(self)
+            cb.set_params(dict(verbose=verbose, epochs=1, steps=steps))
+        logs = self._evaluate(samples[:n], ycls, yreg, callbacks=callbacks, verbose=verbose)
+        return dict(logs) if return_dict else [logs[k] for k in _LOSS_NAMES]
+
+    def _evaluate(self, samples, ycls, yreg, callbacks=(), verbose=0):
+        for cb in callbacks:
+            cb.on_test_begin()
+        t0 = time.time()
+        sums = self._eval_sums(samples, ycls, yreg)
+        count = sums[3]
+        logs = {k: (float(v / count) if count else float("nan")) for k, v in zip(_LOSS_NAMES, sums[:3])}
+        if verbose:
+            print(f"{int(count)}/{int(count)} - {time.time() - t0:.1f}s - " +
+                  " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
+        for cb in callbacks:
+            cb.on_test_end(logs)
+        return logs
+
+    def _eval_sums(self, samples, ycls, yreg):
+        """float64 [total, class, regression, sweeps] summed over the sweeps, read back once.  Data parallel: rank r takes
+        samples[r::world] (every sweep is evaluated once; DataParallel.shard would drop the tail), evaluates with the
+        rank-mean BatchNormalization moving statistics (copy, average, evaluate, restore) and the sums are all-reduced."""
+        net, dev = self.net, self.net.device
+        idx = list(range(len(samples)))
+        own = None
+        if self.dp is not None:
+            idx = idx[self.dp.rank::self.dp.world]
+            own = net.params.state.clone()
+            self.dp.average_(net.params.state)
+            net.state_version += 1                  # the folds of the replica's own statistics are stale
+        try:
+            step = self._eval_step([samples[i] for i in idx]) if idx else None
+            if step is not None:
+                step.reset()
+                acc = step.acc
+            else:
+                acc = torch.zeros(4, dtype=torch.float64, device=dev)
+            if idx:
+                on_dev = len(idx) * ycls[0].size * 4 * 8 < (2 << 30)
+                if on_dev:
+                    yc_d = torch.from_numpy(np.ascontiguousarray(ycls[idx])).to(dev)
+                    yr_d = torch.from_numpy(np.ascontiguousarray(yreg[idx])).to(dev)
+                kind = {"mse": 0, "smoothl1_ce": 1}[self.loss]
+                for k, i in enumerate(idx):
+                    if on_dev:
+                        yc, yr = yc_d[k], yr_d[k]
+                    else:
+                        yc = torch.from_numpy(np.ascontiguousarray(ycls[i])).to(dev)
+                        yr = torch.from_numpy(np.ascontiguousarray(yreg[i])).to(dev)
+                    if step is not None:
+                        step(samples[i]._keepalive, yc, yr)
+                    else:
+                        net.forward(samples[i], training=False)
+                        ops.rpn_loss_eval(net.act["head"], yc, yr, net.Ho * net.Wo, kind, acc)
+            if self.dp is not None:
+                self.dp.sum_(acc)
+            return acc.cpu().numpy().copy()
+        finally:
+            if own is not None:
+                net.params.state.copy_(own)
+                net.state_version += 1
+
+    def _snapshot_weights(self):
+        """theta and the BatchNormalization moving statistics (what Keras' get_weights holds; no optimizer slots), as
+        device copies (EarlyStopping(restore_best_weights=True))."""
+        p = self.net.params
+        return p.theta.clone(), p.state.clone()
+
+    def _restore_weights(self, w):
+        p = self.net.params
+        p.theta.copy_(w[0])
+        p.state.copy_(w[1])
+        p.touch()                                   # every packed copy and fold is stale
 
     def predict(self, x):
         """predict(testVFEPointsDense) -> [prob (n,Ho,Wo,2), regress (n,Ho,Wo,14)] (Predict.py:38);

@@ -380,6 +380,15 @@ class LisecNet:
                         p.view(c.bn + ".moving_variance"), C, self.bnstate[c.bn])
             self._folded[c.bn] = (self.params_version, self.state_version, p.version)
 
+    def _fold_inference(self):
+        """Issues, on the current stream, every BatchNormalization fold (_bn_after) that is stale for the current weights
+        and moving statistics: a forward(training=False) then launches none of its own (EvalStep)."""
+        for L in self.layers:
+            for key in ("conv", "dense"):
+                c = L.get(key)
+                if c is not None and c.bn:
+                    self._bn_after(c, False)
+
     def _run_conv(self, c, x, out, training, ws_tag="main"):
         p = self.params
         flags = (ops.IN_RELU if c.in_relu else 0) | (ops.OUT_RELU if c.out_relu else 0)
@@ -1422,3 +1431,126 @@ class PipelinedStep(_StepPlans):
         if next_points is not None:
             self._load(1 - self.cur, next_points, next_ycls, next_yreg)
         return self._run()
+
+
+class EvalStep:
+    """One evaluation sweep -- voxelise a fixed-capacity padded sweep (as RecordedStep), forward(training=False), add the
+    sweep's loss to a device accumulator (lisec_rpn_loss_eval) -- recorded ONCE as a step plan and re-issued by one C call
+    per sweep (Model.evaluate and the validation of Model.fit with LISEC_TUNING=eval_plan=1; by default they run the eager
+    forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps]
+    (float64, device) is read by the host once per evaluation.  Invariants:
+
+      BN fold   inference scale/shift come from ops.bn_fold (LisecNet._bn_after), cached per (params_version,
+                state_version, params.version); a training step overwrites bnstate with batch statistics and moves the
+                moving statistics.  The plan holds NO fold: prepare() re-folds eagerly, on the replay stream, whatever is
+                stale before the first replay of a new version, and the plan is recorded with every fold current.
+      repack    the plan holds no repack and no wait for one.  prepare() makes the packed kernels current: a repack left
+                pending on the second stream by a training step (_pack_pending / _late_pending) is waited for through
+                _pack_late (the flags stay set: the training plan's own waits for the same events are then already
+                satisfied); otherwise a stale pack is redone eagerly by _pack_all(), which leaves _packed_t_version behind,
+                so the training plan's _run() guard re-arms its repack.
+      training  nothing of training is written: theta, state, the optimizer slots, the iteration counts and
+                params_version are untouched (only bnstate, which every training forward rewrites before it reads it,
+                and the activations); the sweep is staged into buffers of its own (points, targets, voxel sample).
+      workspaces  the shared grow-on-demand buffers (VFE saved state, field and split-K workspaces, the voxeliser's when
+                it shares the training step's) only grow for a sweep larger than any before: an evaluation no larger than
+                the training sweeps leaves _lib.alloc_generation() -- and so the training plan -- as it is.
+
+    Record and replay on ONE torch stream (the current stream at construction)."""
+
+    PAD = _StepPlans.PAD
+
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse"):
+        import ctypes
+        self.net, self.vox, self.capacity = net, voxelizer, int(capacity)
+        self.kind = {"mse": 0, "smoothl1_ce": 1}[loss]
+        dev = net.device
+        self.lib = _lib.load()
+        self.points = torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev)
+        self.ycls = torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev)
+        self.yreg = torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev)
+        self.acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.stream_handle = torch.cuda.current_stream().cuda_stream
+        self.sample = self.vox(self.points)
+        self.prepare()
+        scratch = torch.zeros(4, dtype=torch.float64, device=dev)
+        self._enqueue(scratch)                    # eager warm-up: lazy workspaces, descriptor tables, events
+        torch.cuda.synchronize(dev)
+        self.plan = ctypes.c_void_p()
+        _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(self.plan)))
+        _lib.check(self.lib.lisec_step_plan_begin(self.plan))
+        try:
+            self._enqueue(self.acc)
+        finally:
+            _lib.check(self.lib.lisec_step_plan_end(self.plan))
+        self.launches = self.lib.lisec_step_plan_size(self.plan)
+        self.acc.zero_()                          # the recording ran on the padding
+        torch.cuda.synchronize(dev)
+        self.alloc_gen = _lib.alloc_generation()
+
+    def _enqueue(self, acc):
+        net = self.net
+        pending = net._pack_pending, net._late_pending
+        net._pack_pending = net._late_pending = False      # prepare() made every packed kernel current: no waits
+        try:
+            self.vox(self.points, out=self.sample)
+            net.forward(self.sample, training=False)
+        finally:
+            net._pack_pending, net._late_pending = pending
+        ops.rpn_loss_eval(net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, self.kind, acc)
+
+    def prepare(self):
+        """Packed kernels and BatchNormalization folds current for the weights and statistics of now (see the class)."""
+        net = self.net
+        key = (net.params_version, net.state_version, net.params.version)
+        if getattr(self, "_ready", None) == key:
+            return                                # nothing moved since the last sweep: the plan's inputs are current
+        main = torch.cuda.current_stream()
+        if net._pack_pending or net._late_pending:
+            net._wait(net._pack_late, main)
+            if net._packed_version != (net.params_version, net.params.version):
+                net._pack_pending = net._late_pending = False       # variables changed since that repack
+        prev_pin = _lib.pin_stream(main.cuda_stream)
+        try:
+            net._pack_all()
+            net._fold_inference()
+        finally:
+            _lib.pin_stream(prev_pin)
+        self._ready = key
+
+    def reset(self):
+        """Zeroes the accumulator (stream-ordered)."""
+        self.acc.zero_()
+
+    def __call__(self, points, ycls, yreg):
+        """Stages one sweep (points: n <= capacity rows, >= 3 columns; targets (Ho,Wo,2|14)) and replays the plan: its
+        loss is added to self.acc."""
+        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
+            raise RuntimeError("an EvalStep replays on the stream it was recorded on: make that stream current")
+        if self.alloc_gen != _lib.alloc_generation():
+            raise StalePlanError("this evaluation plan was recorded before a workspace was reallocated: record a new one")
+        pts = torch.as_tensor(points)
+        n = int(pts.shape[0])
+        if n > self.capacity:
+            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
+        self.points[:n].copy_(pts[:, :3], non_blocking=True)
+        if n < self.capacity:
+            self.points[n:].fill_(self.PAD)
+        self.ycls.copy_(torch.as_tensor(ycls).reshape(self.ycls.shape), non_blocking=True)
+        self.yreg.copy_(torch.as_tensor(yreg).reshape(self.yreg.shape), non_blocking=True)
+        self.prepare()
+        _lib.check(self.lib.lisec_step_plan_run(self.plan))
+        self.sample._host_info = None
+        return self.acc
+
+    def close(self):
+        if getattr(self, "plan", None) is not None:
+            torch.cuda.synchronize(self.net.device)
+            self.lib.lisec_step_plan_destroy(self.plan)
+            self.plan = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -371,6 +371,14 @@ def rpn_loss(head, y_cls, y_reg, M, kind, dhead, loss_out, grad_scale=1.0):
                                           _lib.current_stream()))
 
 
+def rpn_loss_eval(head, y_cls, y_reg, M, kind, acc):
+    """Adds the [total, class, regression] that rpn_loss would write to loss_out (the same fp32 bits) to acc[0:3] and
+    counts the sweep in acc[3] (acc: float64[4] device tensor); no gradient."""
+    ws = _ew_workspace(head.device)
+    _lib.check(_lib.load().lisec_rpn_loss_eval(_lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M, kind, _lib.ptr(acc),
+                                               _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
 def sgd_nesterov_step(theta, grad, velocity, lr_t, momentum):
     _lib.check(_lib.load().lisec_sgd_nesterov_step(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity),
                                                    theta.numel(), lr_t, momentum, _lib.current_stream()))

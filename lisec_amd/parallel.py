@@ -201,6 +201,12 @@ class DataParallel:
             tensor.mul_(1.0 / self.world)
         return tensor
 
+    def sum_(self, tensor):
+        """In-place sum over ranks (torch.distributed all-reduce), e.g. the float64 loss sums of an evaluation."""
+        if self.world > 1:
+            dist.all_reduce(tensor, op=dist.ReduceOp.SUM)
+        return tensor
+
     def bucketed(self):
         """Gradient averaging in two buckets for LisecNet.train_step: start_tail() launches the all-reduce of the
         RPN/head gradients asynchronously (from the stream that produced them), finish() reduces the small head of

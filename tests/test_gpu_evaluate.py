@@ -1,0 +1,340 @@
+"""Model.evaluate, validation in fit and the Keras callbacks that act on it, on the GPU: the evaluation loss kernel
+(lisec_rpn_loss_eval), the recorded evaluation step (network.EvalStep) against the eager forward and the fp64 oracle,
+and the two-rank data-parallel validation.  Seeded synthetic clouds on the 16x32x8x35 grid."""
+import os
+import socket
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from lisec_amd import callbacks
+
+pytestmark = pytest.mark.gpu
+SMALL = dict(xSize=0.5, ySize=0.25, zSize=0.25, sampleSize=35, maxVoxelX=8, maxVoxelY=16, maxVoxelZ=8)
+
+
+def _cloud(seed, n=2500, pad_to=None):
+    rng = np.random.default_rng(seed)
+    pts = np.stack([rng.uniform(-4.2, 4.2, n), rng.uniform(-4.2, 4.2, n), rng.uniform(0.0, 2.1, n)], 1)
+    pts = pts.astype(np.float32)
+    if pad_to:
+        # the recorded steps pad every sweep into a 4096-point buffer with points the voxeliser drops; the eager forward
+        # gets the same padded sweep (the row-list kernels plan per capacity: same summation order, same bits)
+        out = np.full((pad_to, 3), 1.0e6, np.float32)
+        out[:n] = pts
+        pts = out
+    return pts
+
+
+def _targets(seed):
+    rng = np.random.default_rng(100 + seed)
+    return rng.integers(0, 3, (8, 16, 2)).astype(np.float32), rng.normal(0, 1, (8, 16, 14)).astype(np.float32)
+
+
+def _data(seeds, pad_to=None):
+    from lisec_amd import model_training as mt
+    x = [mt.VFE_preprocessing(_cloud(s, pad_to=pad_to), **SMALL) for s in seeds]
+    ys = [_targets(s) for s in seeds]
+    return x, [np.stack([y[0] for y in ys]), np.stack([y[1] for y in ys])]
+
+
+def _model(seed=7, opt=None):
+    from lisec_amd import model_training as mt
+    from lisec_amd.params import ParamStore
+    from oracle import model_ref as M
+    m = mt.Model(16, 32, 8, 35, params=ParamStore(torch.device("cuda"), init=M.glorot_params(seed=seed, randomize_bn=True)))
+    m.compile(optimizer=opt or mt.optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True), loss=['mse', 'mse'])
+    return m
+
+
+def _variables(model):
+    net = model.net
+    torch.cuda.synchronize()
+    return dict(theta=net.params.theta.cpu().numpy().copy(), state=net.params.state.cpu().numpy().copy(),
+                it=net._iter_dev.cpu().numpy().copy(), iterations=net.iterations, pv=net.params_version,
+                **{"slot_" + k: t.cpu().numpy().copy() for k, t in net.slots().items()})
+
+
+def _same(a, b):
+    assert a.keys() == b.keys()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+# ---- kernel level ------------------------------------------------------------------------------------------------
+def _ref_loss(head, yc, yr, kind):
+    h, yc, yr = head.astype(np.float64), yc.astype(np.float64), yr.astype(np.float64)
+    if kind == 0:
+        lc, lr = ((h[:, :2] - yc) ** 2).mean(), ((h[:, 2:] - yr) ** 2).mean()
+    else:
+        p, t = h[:, :2], np.clip(yc, 0, 1)
+        lc = (np.maximum(p, 0) - p * t + np.log1p(np.exp(-np.abs(p)))).mean()
+        d = np.abs(h[:, 2:] - yr)
+        lr = np.where(d < 1, 0.5 * d * d, d - 0.5).mean()
+    return np.array([lc + lr, lc, lr])
+
+
+@pytest.mark.parametrize("M", [3001, 20000])
+@pytest.mark.parametrize("kind", [0, 1])
+def test_eval_loss_kernel(kind, M):
+    from lisec_amd import ops
+    rng = np.random.default_rng(M + kind)
+    heads = [rng.normal(0, 2, (M, 16)).astype(np.float32) for _ in range(4)]
+    yc = rng.uniform(-0.3, 1.3, (M, 2)).astype(np.float32)
+    yr = rng.normal(0, 1, (M, 14)).astype(np.float32)
+    d = lambda a: torch.from_numpy(a).cuda()         # noqa: E731
+    yc_d, yr_d = d(yc), d(yr)
+    dh = torch.empty(M, 16, device="cuda")
+    lo = torch.empty(3, device="cuda")
+    acc = torch.zeros(4, dtype=torch.float64, device="cuda")
+    per_sweep = []
+    for h in heads:
+        ops.rpn_loss(d(h), yc_d, yr_d, M, kind, dh, lo)
+        one = torch.zeros(4, dtype=torch.float64, device="cuda")
+        ops.rpn_loss_eval(d(h), yc_d, yr_d, M, kind, one)
+        ops.rpn_loss_eval(d(h), yc_d, yr_d, M, kind, acc)
+        torch.cuda.synchronize()
+        lo_h, one_h = lo.cpu().numpy(), one.cpu().numpy()
+        assert np.array_equal(one_h[:3], lo_h.astype(np.float64)) and one_h[3] == 1.0     # loss_out's bits
+        np.testing.assert_allclose(one_h[:3], _ref_loss(h, yc, yr, kind), rtol=1e-5)
+        per_sweep.append(lo_h.astype(np.float64))
+    want = np.zeros(3)
+    for v in per_sweep:                               # the accumulator adds the fp32 values in order, in fp64
+        want = want + v
+    got = acc.cpu().numpy()
+    assert np.array_equal(got[:3], want) and got[3] == 4.0
+    again = torch.zeros(4, dtype=torch.float64, device="cuda")
+    for h in heads:
+        ops.rpn_loss_eval(d(h), yc_d, yr_d, M, kind, again)
+    assert again.cpu().numpy().tobytes() == got.tobytes()
+
+
+# ---- model level ---------------------------------------------------------------------------------------------------
+def test_evaluate_vs_oracle_and_predict():
+    from oracle import model_ref as M
+    from oracle import voxel_ref
+    model = _model()
+    x, y = _data(range(5))
+    res = model.evaluate(x, y, verbose=0)
+    d = model.evaluate(x, y, verbose=0, return_dict=True)
+    assert list(d) == ["loss", "ClassificationLayer_loss", "RegressionLayer_loss"] and list(d.values()) == res
+    p64 = {k: v.double() for k, v in M.glorot_params(seed=7, randomize_bn=True).items()}
+    ref, mine = [], []
+    probs, regs = model.predict(x)
+    for k, s in enumerate(range(5)):
+        vox = voxel_ref.voxelize_ref(_cloud(s).astype(np.float64), **SMALL)
+        dense = torch.from_numpy(voxel_ref.to_dense(vox, (8, 16, 32, 35, 6)))[None].double()
+        with torch.no_grad():
+            cls, reg = M.forward(p64, dense, training=False)
+        yc, yr = torch.from_numpy(y[0][k])[None].double(), torch.from_numpy(y[1][k])[None].double()
+        lc, lr = float(((cls - yc) ** 2).mean()), float(((reg - yr) ** 2).mean())
+        assert lc + lr == pytest.approx(float(M.mse_loss(cls, reg, yc, yr)), rel=1e-12)
+        ref.append([lc + lr, lc, lr])
+        dc = (probs[k] - y[0][k]).astype(np.float64)
+        dr = (regs[k] - y[1][k]).astype(np.float64)
+        mine.append([(dc ** 2).mean() + (dr ** 2).mean(), (dc ** 2).mean(), (dr ** 2).mean()])
+    np.testing.assert_allclose(res, np.mean(ref, 0), rtol=1e-3)          # the inference-parity tolerance
+    np.testing.assert_allclose(res, np.mean(mine, 0), rtol=1e-5)         # the mean of predict()'s losses
+    # batch_size only sets what steps counts
+    assert model.evaluate(x, y, verbose=0, batch_size=2, steps=2) == model.evaluate(x[:4], y, verbose=0)
+    assert model.evaluate(x, y, verbose=0, batch_size=3, steps=1) == model.evaluate(x[:3], y, verbose=0)
+
+
+@pytest.mark.parametrize("plan", [False, True])
+def test_evaluate_leaves_training_state_alone_and_fit_eval_fit_equals_fit_fit(plan, monkeypatch):
+    monkeypatch.setenv("LISEC_TUNING", "eval_plan=%d" % plan)
+    from lisec_amd import _lib
+    from lisec_amd import model_training as mt
+    x, y = _data(range(4))
+    xv, yv = _data(range(10, 13))
+    runs = {}
+    for with_eval in (False, True):
+        model = _model(opt=mt.optimizers.Adam(1e-3))
+        np.random.seed(3)
+        model.fit(x, y, verbose=0, epochs=1, steps_per_epoch=4)
+        if with_eval:
+            before, rng, gen = _variables(model), np.random.get_state(), _lib.alloc_generation()
+            step = model._captured[1]
+            model.evaluate(xv, yv, verbose=0)
+            model.evaluate(x, y, verbose=0)
+            assert (getattr(model, "_eval_captured", None) is not None) == plan
+            _same(before, _variables(model))
+            now = np.random.get_state()
+            assert np.array_equal(rng[1], now[1]) and rng[2] == now[2]
+            assert _lib.alloc_generation() == gen            # no larger than the training sweeps: nothing reallocated
+        model.fit(x, y, verbose=0, epochs=1, steps_per_epoch=4)
+        if with_eval:
+            assert model._captured[1] is step                # the training plan was not recorded again
+        runs[with_eval] = _variables(model)
+    _same(runs[False], runs[True])
+
+
+def test_eval_plan_replay_equals_eager_across_training(monkeypatch):
+    from oracle import voxel_ref
+    x, y = _data(range(4), pad_to=4096)
+    xv, yv = _data(range(20, 23), pad_to=4096)
+    model = _model()
+    seen = []
+    for epoch in range(3):
+        monkeypatch.setenv("LISEC_TUNING", "eval_plan=1")
+        replay = model.evaluate(xv, yv, verbose=0)
+        assert model._eval_captured is not None
+        monkeypatch.setenv("LISEC_TUNING", "eval_plan=0")
+        eager = model.evaluate(xv, yv, verbose=0)
+        assert replay == eager                   # a stale fold or pack in the replay would show here
+        seen.append(replay)
+        monkeypatch.delenv("LISEC_TUNING", raising=False)
+        model.fit(x, y, verbose=0, epochs=1, steps_per_epoch=4, shuffle=False)
+    assert seen[0] != seen[1] != seen[2]          # the epochs in between did change the model
+    # unpadded sweeps: the plan pads them to its capacity, the eager path does not -- equal within rounding
+    xu, yu = _data(range(20, 23))
+    monkeypatch.setenv("LISEC_TUNING", "eval_plan=1")
+    replay = model.evaluate(xu, yu, verbose=0)
+    monkeypatch.setenv("LISEC_TUNING", "eval_plan=0")
+    np.testing.assert_allclose(replay, model.evaluate(xu, yu, verbose=0), rtol=1e-6)
+    # dense arrays: no point cloud to voxelise again -> the eager path
+    monkeypatch.setenv("LISEC_TUNING", "eval_plan=1")
+    dense = np.stack([voxel_ref.to_dense(voxel_ref.voxelize_ref(_cloud(s).astype(np.float64), **SMALL), (8, 16, 32, 35, 6))
+                      for s in range(20, 23)])
+    np.testing.assert_allclose(model.evaluate(dense, yv, verbose=0), model.evaluate(xv, yv, verbose=0), rtol=1e-5)
+
+
+class _Recorder(callbacks.Callback):
+    """What fit hands over, and the model's own evaluate() at each epoch's end."""
+
+    def __init__(self, val=None):
+        super().__init__()
+        self.val, self.events, self.evals, self.steps = val, [], {}, []
+
+    def on_test_begin(self, logs=None):
+        self.events.append("test_begin")
+
+    def on_test_end(self, logs=None):
+        self.events.append(("test_end", dict(logs)))
+
+    def on_epoch_end(self, epoch, logs=None):
+        self.events.append(("epoch_end", epoch))
+        self.steps.append(self.model._captured[1])
+        if self.val is not None:
+            self.evals[epoch] = self.model.evaluate(*self.val, verbose=0, return_dict=True)
+
+
+@pytest.mark.parametrize("plan", [False, True])
+def test_fit_validation_logs_equal_evaluate_and_freq(plan, monkeypatch):
+    monkeypatch.setenv("LISEC_TUNING", "eval_plan=%d" % plan)
+    x, y = _data(range(4))
+    xv, yv = _data(range(30, 33))
+    model = _model()
+    rec = _Recorder(val=(xv, yv))
+    hist = model.fit(x, y, verbose=0, epochs=3, steps_per_epoch=4, validation_data=(xv, yv), validation_freq=[1, 3],
+                     callbacks=[rec])
+    h = hist.history
+    assert len(h["loss"]) == 3 and len(h["val_loss"]) == 2
+    for key in ("loss", "ClassificationLayer_loss", "RegressionLayer_loss"):
+        assert h["val_" + key] == [rec.evals[0][key], rec.evals[2][key]]
+    assert sum(e == "test_begin" for e in rec.events) == 2
+    assert rec.steps[0] is rec.steps[1] is rec.steps[2]        # validation does not make fit record its step again
+    assert rec.events[rec.events.index("test_begin") + 1][0] == "test_end"
+    assert rec.events.index("test_begin") < rec.events.index(("epoch_end", 0))    # validation before on_epoch_end
+    h2 = _model().fit(x, y, verbose=0, epochs=3, steps_per_epoch=4, validation_data=(xv, yv), validation_freq=2).history
+    assert len(h2["val_loss"]) == 1 and len(h2["loss"]) == 3
+
+
+def test_validation_split_equals_validation_data():
+    x, y = _data(range(5))
+    a, b = _model(), _model()
+    ha = a.fit(x, y, verbose=0, epochs=2, shuffle=False, validation_split=0.4).history
+    hb = b.fit(x[:3], [y[0][:3], y[1][:3]], verbose=0, epochs=2, shuffle=False,
+               validation_data=(x[3:], [y[0][3:], y[1][3:]])).history
+    assert ha == hb
+    assert np.array_equal(a.net.params.theta.cpu().numpy(), b.net.params.theta.cpu().numpy())
+
+
+def test_early_stopping_restores_best_epoch():
+    x, y = _data(range(4))
+    xv, yv = _data(range(40, 42))
+    model = _model()
+    snaps = {}
+
+    class Script(callbacks.Callback):
+        def on_epoch_end(self, epoch, logs=None):
+            assert "val_loss" in logs
+            logs["val_loss"] = [3.0, 1.0, 2.0, 2.0, 2.0, 2.0][epoch]
+            snaps[epoch] = _variables(self.model)
+
+    es = callbacks.EarlyStopping(patience=2, restore_best_weights=True)
+    hist = model.fit(x, y, verbose=0, epochs=6, steps_per_epoch=4, validation_data=(xv, yv), callbacks=[Script(), es])
+    assert len(hist.history["loss"]) == 4 and es.stopped_epoch == 3 and model.stop_training
+    got = _variables(model)
+    assert np.array_equal(got["theta"], snaps[1]["theta"]) and np.array_equal(got["state"], snaps[1]["state"])
+    assert not np.array_equal(got["theta"], snaps[3]["theta"])
+
+
+def test_model_checkpoint_best_only_reloads(tmp_path):
+    from lisec_amd import model_training as mt
+    x, y = _data(range(4))
+    xv, yv = _data(range(50, 53))
+    model = _model()
+    path = str(tmp_path / "best.h5")
+    hist = model.fit(x, y, verbose=0, epochs=3, steps_per_epoch=4, validation_data=(xv, yv),
+                     callbacks=[callbacks.ModelCheckpoint(path, save_best_only=True)])
+    best = min(hist.history["val_loss"])
+    back = mt.load_model(path)
+    assert back.evaluate(xv, yv, verbose=0)[0] == pytest.approx(best, rel=1e-6)
+
+
+def test_reduce_lr_on_plateau_same_plan_and_bits_as_set_by_hand():
+    x, y = _data(range(4))
+    xv, yv = _data(range(60, 62))
+
+    class Flat(callbacks.Callback):
+        def on_epoch_begin(self, epoch, logs=None):
+            self.step = getattr(self.model, "_captured", (None, None))[1]
+
+        def on_epoch_end(self, epoch, logs=None):
+            logs["val_loss"] = 1.0                  # a plateau from the second epoch on
+            if epoch:
+                assert self.model._captured[1] is self.step
+
+    a = _model()
+    ha = a.fit(x, y, verbose=0, epochs=4, steps_per_epoch=4, shuffle=False, validation_data=(xv, yv),
+               callbacks=[Flat(), callbacks.ReduceLROnPlateau(factor=0.5, patience=1)]).history
+    assert ha["lr"] == [0.01, 0.01, 0.005, 0.0025]
+    rates = ha["lr"]
+    b = _model()
+    b.fit(x, y, verbose=0, epochs=4, steps_per_epoch=4, shuffle=False,
+          callbacks=[callbacks.LearningRateScheduler(lambda epoch, lr: rates[epoch])])
+    _same(_variables(a), _variables(b))
+
+
+# ---- data parallel ---------------------------------------------------------------------------------------------------
+def _dp_worker(rank, world, port, out_dir):
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                      MASTER_PORT=str(port), LISEC_DIST_BACKEND="gloo", LISEC_BENCH_DEVICE="0")
+    model = _model()                                 # WORLD_SIZE=2 -> DataParallel inside, params broadcast
+    assert model.dp is not None and model.dp.world == 2
+    x, y = _data(range(4))
+    xv, yv = _data(range(70, 75))                    # an odd number of validation sweeps: 3 on rank 0, 2 on rank 1
+    np.random.seed(0)
+    hist = model.fit(x, y, verbose=0, epochs=1, steps_per_epoch=4, validation_data=(xv, yv),
+                     callbacks=[callbacks.ModelCheckpoint(os.path.join(out_dir, "ck.h5"))])
+    np.save(os.path.join(out_dir, f"val{rank}.npy"), np.array([hist.history["val_" + k][0] for k in
+                                                               ("loss", "ClassificationLayer_loss", "RegressionLayer_loss")]))
+    model.dp.barrier()
+    model.dp.close()
+
+
+def test_two_ranks_log_identical_val_loss_equal_to_checkpoint_evaluate(tmp_path):
+    from lisec_amd import model_training as mt
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    mp.spawn(_dp_worker, args=(2, port, str(tmp_path)), nprocs=2, join=True)
+    v0, v1 = np.load(tmp_path / "val0.npy"), np.load(tmp_path / "val1.npy")
+    assert np.array_equal(v0, v1)
+    xv, yv = _data(range(70, 75))
+    back = mt.load_model(str(tmp_path / "ck.h5"))
+    np.testing.assert_allclose(back.evaluate(xv, yv, verbose=0), v0, rtol=1e-9)
