@@ -600,6 +600,59 @@ int lisec_rpn_loss(const float* head, const float* y_cls, const float* y_reg, lo
 int lisec_rpn_loss_eval(const float* head, const float* y_cls, const float* y_reg, long long M, int kind, double* acc,
                         void* workspace, size_t workspace_bytes, lisec_stream_t stream);
 
+/* tf.keras 2.4 losses and metrics of Model.compile(loss=, loss_weights=, metrics=) on the two head outputs (csrc/losses.hip).
+ * With e = p - t, eps = 1e-7, every term is a mean over all M*C elements of the output (C = 2 class, 14 regression):
+ *   MSE e^2 | MAE |e| | MAPE 100|t-p|/max(|t|,eps) | MSLE (log(max(p,eps)+1) - log(max(t,eps)+1))^2
+ *   HUBER |e| <= delta ? e^2/2 : delta^2/2 + delta(|e| - delta) | LOGCOSH e + softplus(-2e) - log 2
+ *   BCE t <- t(1-ls) + ls/2; from_logits: max(p,0) - p t + log1p(exp(-|p|)), else o = clip(p, eps, 1-eps),
+ *       -(t log(o+eps) + (1-t) log(1-o+eps)) | POISSON p - t log(p+eps)
+ *   SIGMOID_CE_CLAMPED, SMOOTH_L1: the two halves of lisec_rpn_loss kind 1, with its fp32 arithmetic
+ *   BINARY_ACCURACY (metric) t == (p > threshold) | CATEGORICAL_ACCURACY (metric, a mean over the M cells)
+ *       argmax(t) == argmax(p) over the C channels of a cell, the first index winning ties
+ * Labels are not clamped (except by SIGMOID_CE_CLAMPED).  Gradients are TF's of the same formulas. */
+#define LISEC_LOSS_MAX_METRICS 4
+enum {
+    LISEC_LOSS_MSE = 0,
+    LISEC_LOSS_MAE = 1,
+    LISEC_LOSS_MAPE = 2,
+    LISEC_LOSS_MSLE = 3,
+    LISEC_LOSS_HUBER = 4,
+    LISEC_LOSS_LOGCOSH = 5,
+    LISEC_LOSS_BCE = 6,
+    LISEC_LOSS_POISSON = 7,
+    LISEC_LOSS_SIGMOID_CE_CLAMPED = 8,
+    LISEC_LOSS_SMOOTH_L1 = 9,
+    LISEC_METRIC_BINARY_ACCURACY = 10,   /* metrics only */
+    LISEC_METRIC_CATEGORICAL_ACCURACY = 11
+};
+typedef struct lisec_loss_term {
+    int kind;                 /* LISEC_LOSS_* / LISEC_METRIC_* */
+    int from_logits;          /* BCE */
+    float param;              /* HUBER: delta (> 0); BINARY_ACCURACY: threshold */
+    float label_smoothing;    /* BCE, in [0, 1] */
+} lisec_loss_term;
+typedef struct lisec_loss_cfg {
+    lisec_loss_term loss[2];                              /* [0] class output, [1] regression output */
+    float weight[2];                                      /* loss_weights */
+    int n_metrics[2];                                     /* 0 .. LISEC_LOSS_MAX_METRICS */
+    lisec_loss_term metric[2][LISEC_LOSS_MAX_METRICS];
+} lisec_loss_cfg;
+
+/* One pass over head (M,16), y_cls (M,2), y_reg (M,14): dhead = grad_scale * d(weight[0]*L_cls + weight[1]*L_reg)/dhead,
+ * loss_out[3] = {weight[0]*L_cls + weight[1]*L_reg, L_cls, L_reg} and metric_out[n_metrics[0] + n_metrics[1]] (the class
+ * output's metrics, then the regression output's), fp32.  Per-workgroup fp64 partials in a fixed partition and one
+ * finalize: no atomics, the same bits on every run.  metric_out may be NULL when there are no metrics.  With both losses
+ * MSE at unit weights, dhead is bit-identical to lisec_rpn_loss kind 0 (and with SIGMOID_CE_CLAMPED + SMOOTH_L1, to kind 1). */
+int lisec_head_loss(const lisec_loss_cfg* cfg, const float* head, const float* y_cls, const float* y_reg, long long M,
+                    float grad_scale, float* dhead, float* loss_out, float* metric_out, void* workspace,
+                    size_t workspace_bytes, lisec_stream_t stream);
+/* The evaluation form: the same partition and finalize without the gradient, so that the values of a sweep are the bits
+ * lisec_head_loss writes.  They are ADDED, as doubles, to acc = {total, class, regression, metrics..., sweeps} (device,
+ * 4 + n_metrics[0] + n_metrics[1] doubles, zeroed by the caller); the last word counts the sweep. */
+int lisec_head_loss_eval(const lisec_loss_cfg* cfg, const float* head, const float* y_cls, const float* y_reg, long long M,
+                         double* acc, void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+size_t lisec_head_loss_workspace_bytes(void);
+
 /* optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (:295) on the flat parameter buffer:
  * v <- m*v - lr_t*g;  w <- w + m*v - lr_t*g;  lr_t = lr/(1 + decay*iterations) is computed by the caller. */
 int lisec_sgd_nesterov_step(float* theta, const float* grad, float* velocity, long long n, float lr_t,

@@ -87,6 +87,18 @@ class LrSchedule(Structure):                   # lisec_lr_schedule
                 + [("boundaries", c_double * LR_MAX_BOUNDARIES), ("values", c_double * (LR_MAX_BOUNDARIES + 1))])
 
 
+LOSS_MAX_METRICS = 4                           # LISEC_LOSS_MAX_METRICS
+
+
+class LossTerm(Structure):                     # lisec_loss_term
+    _fields_ = [("kind", c_int), ("from_logits", c_int), ("param", c_float), ("label_smoothing", c_float)]
+
+
+class LossCfg(Structure):                      # lisec_loss_cfg
+    _fields_ = [("loss", LossTerm * 2), ("weight", c_float * 2), ("n_metrics", c_int * 2),
+                ("metric", (LossTerm * LOSS_MAX_METRICS) * 2)]
+
+
 class ConvGeom(Structure):
     _fields_ = [(n, c_int) for n in ("mode", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "KD", "KH", "KW",
                                      "sd", "sh", "sw", "pd", "ph", "pw", "Cin", "in_stride", "Cout",
@@ -223,6 +235,12 @@ def _declare(lib):
     lib.lisec_rpn_loss.argtypes = [P, P, P, LL, c_int, c_float, P, P, P, c_size_t, P]
     lib.lisec_rpn_loss_eval.restype = c_int
     lib.lisec_rpn_loss_eval.argtypes = [P, P, P, LL, c_int, P, P, c_size_t, P]
+    lib.lisec_head_loss.restype = c_int
+    lib.lisec_head_loss.argtypes = [POINTER(LossCfg), P, P, P, LL, c_float, P, P, P, P, c_size_t, P]
+    lib.lisec_head_loss_eval.restype = c_int
+    lib.lisec_head_loss_eval.argtypes = [POINTER(LossCfg), P, P, P, LL, P, P, c_size_t, P]
+    lib.lisec_head_loss_workspace_bytes.restype = c_size_t
+    lib.lisec_head_loss_workspace_bytes.argtypes = []
     lib.lisec_sgd_nesterov_step.restype = c_int
     lib.lisec_sgd_nesterov_step.argtypes = [P, P, P, LL, c_float, c_float, P]
     lib.lisec_sgd_nesterov_step_dev.restype = c_int

@@ -48,7 +48,7 @@ extern "C" int lisec_workspace_init(void* workspace, size_t bytes, lisec_stream_
 
 extern "C" const char* lisec_last_error(void) { return lisec::g_err; }
 
-extern "C" int lisec_abi_version(void) { return 13; }
+extern "C" int lisec_abi_version(void) { return 14; }
 
 extern "C" int lisec_device_info(char* name, int cap) {
     int dev = 0;

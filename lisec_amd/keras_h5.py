@@ -200,7 +200,21 @@ def _rate(lr):
     return lr if isinstance(lr, dict) else float(lr)
 
 
-def _training_config(optimizer):
+def _serialize_nested(x):
+    """Keras' _serialize_nested_config: a loss or metric object becomes {"class_name", "config"}, names stay as given,
+    lists and dicts keep their structure."""
+    if hasattr(x, "get_config"):
+        return {"class_name": type(x).__name__, "config": x.get_config()}
+    if isinstance(x, dict):
+        return {k: _serialize_nested(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_serialize_nested(v) for v in x]
+    return x
+
+
+def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
+    """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
+    loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote)."""
     o = optimizer or {}
     if o.get("class_name", "SGD") == "Adam":
         oc = {"class_name": "Adam", "config": {
@@ -211,8 +225,8 @@ def _training_config(optimizer):
         oc = {"class_name": "SGD", "config": {
             "name": "SGD", "learning_rate": _rate(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
             "momentum": float(o.get("momentum", 0.0)), "nesterov": bool(o.get("nesterov", False))}}
-    return {"loss": ["mse", "mse"], "metrics": None, "weighted_metrics": None, "loss_weights": None,
-            "optimizer_config": oc}
+    return {"loss": ["mse", "mse"] if loss is None else _serialize_nested(loss), "metrics": _serialize_nested(metrics),
+            "weighted_metrics": None, "loss_weights": _serialize_nested(loss_weights), "optimizer_config": oc}
 
 
 def _slot_kinds(optimizer):
@@ -224,20 +238,23 @@ def _slot_kinds(optimizer):
 
 # ---------------------------------------------------------------------------------------------------
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None, m=None, v=None,
-               vhat=None):
+               vhat=None, loss=None, loss_weights=None, metrics=None):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
     compiled: no training_config / optimizer_weights, like Keras).  The slots, each a dict of trainable ParamStore
     name -> array: velocity (SGD momentum accumulators, momentum > 0), m and v (Adam moments), vhat (AMSGrad).
-    optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none)."""
+    optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
+    loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
+    as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics."""
     layers, _ = keras_layers(nx, ny, nz, maxPoints)
     with hdf5_lite.File(path, "w") as f:
         f.attrs["keras_version"] = KERAS_VERSION.encode()
         f.attrs["backend"] = b"tensorflow"
         f.attrs["model_config"] = json.dumps(model_config(nx, ny, nz, maxPoints)).encode("utf8")
         if optimizer is not None:
-            f.attrs["training_config"] = json.dumps(_training_config(optimizer)).encode("utf8")
+            f.attrs["training_config"] = json.dumps(_training_config(optimizer, loss, loss_weights,
+                                                                     metrics)).encode("utf8")
         g = f.create_group("model_weights")
         g.attrs["layer_names"] = [L["name"].encode("utf8") for L in layers]
         g.attrs["backend"] = b"tensorflow"
@@ -298,8 +315,9 @@ def _suffix_number(name, base):
 
 def load_model(path, grid=None):
     """Reads a Keras `.h5` written by the reference (or by save_model).  Returns dict(params, nx, ny, nz, maxPoints,
-    iterations, optimizer (dict or None, as save_model takes it), and the slots velocity, m, v, vhat (each a dict of
-    trainable ParamStore name -> array, or None)).  Slots are matched by name, not by position.
+    iterations, optimizer (dict or None, as save_model takes it), loss, loss_weights, metrics (training_config's, as
+    serialized there; None without one), and the slots velocity, m, v, vhat (each a dict of trainable ParamStore name ->
+    array, or None)).  Slots are matched by name, not by position.
 
     Layers are matched by class and creation order (the numeric suffix of Keras' automatic names), not by the exact
     suffix: a model built as the second one of a Python session carries shifted suffixes."""
@@ -347,9 +365,11 @@ def load_model(path, grid=None):
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
         out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, velocity=None,
-                   m=None, v=None, vhat=None, optimizer=None)
+                   m=None, v=None, vhat=None, optimizer=None, loss=None, loss_weights=None, metrics=None)
         if "training_config" in f.attrs:
-            oc = json.loads(_text(f.attrs["training_config"])).get("optimizer_config", {})
+            tc = json.loads(_text(f.attrs["training_config"]))
+            out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))
+            oc = tc.get("optimizer_config", {})
             c = oc.get("config", {})
             if oc.get("class_name") == "SGD":
                 out["optimizer"] = dict(lr=c.get("learning_rate", c.get("lr", 0.01)), decay=c.get("decay", 0.0),

@@ -1,0 +1,345 @@
+"""tf.keras 2.4 losses (tf.keras.losses), exposed as lisec_amd.model_training.losses, and what Model.compile makes of its
+loss / loss_weights / metrics arguments: a LossSpec, the descriptor (lisec_loss_cfg, include/lisec_hip.h) of the kernels
+that evaluate it (csrc/losses.hip).
+
+Same names, constructor arguments, defaults, get_config / from_config and serialize / deserialize as Keras.  Every loss is
+Keras' mean over the last axis and then over the cells (SUM_OVER_BATCH_SIZE): the mean over all M*C elements of an output.
+A loss of one's own -- a Python callable, or a subclass with its own call() -- cannot run in the kernels and is refused
+(NotImplementedError), as are the Keras losses the kernels do not implement (hinge family, categorical and sparse
+cross-entropy, KL divergence, cosine similarity).  Importable and fully validated without the HIP library."""
+from . import _lib
+
+EPSILON = 1e-7                                   # K.epsilon()
+OUTPUTS = ("ClassificationLayer", "RegressionLayer")
+
+# lisec_loss_term kinds (LISEC_LOSS_* / LISEC_METRIC_* of include/lisec_hip.h)
+MSE, MAE, MAPE, MSLE, HUBER, LOGCOSH, BCE, POISSON, SIGMOID_CE_CLAMPED, SMOOTH_L1 = range(10)
+BINARY_ACCURACY, CATEGORICAL_ACCURACY = 10, 11
+MAX_METRICS = _lib.LOSS_MAX_METRICS
+
+
+class Loss:
+    """The base class of the losses (tf.keras.losses.Loss).  term() is what the kernels evaluate:
+    (kind, from_logits, param, label_smoothing)."""
+
+    _kind = None
+
+    def __init__(self, reduction="auto", name=None):
+        if reduction != "auto":
+            raise NotImplementedError(f"{type(self).__name__}: only reduction='auto' (SUM_OVER_BATCH_SIZE) is implemented")
+        self.reduction, self.name = reduction, name
+
+    def __call__(self, y_true, y_pred, sample_weight=None):
+        raise NotImplementedError("the losses are evaluated by the kernels of Model.fit / Model.evaluate")
+
+    def term(self):
+        if type(self) not in _BUILTIN.values() or self._kind is None:
+            raise NotImplementedError(f"loss {type(self).__name__}: only the built-in Keras losses ({', '.join(_BUILTIN)}) "
+                                      "run in the kernels")
+        return (self._kind, 0, 0.0, 0.0)
+
+    def get_config(self):
+        return {"reduction": self.reduction, "name": self.name}
+
+    @classmethod
+    def from_config(cls, config):
+        return cls(**config)
+
+
+class MeanSquaredError(Loss):
+    _kind = MSE
+
+    def __init__(self, reduction="auto", name="mean_squared_error"):
+        super().__init__(reduction, name)
+
+
+class MeanAbsoluteError(Loss):
+    _kind = MAE
+
+    def __init__(self, reduction="auto", name="mean_absolute_error"):
+        super().__init__(reduction, name)
+
+
+class MeanAbsolutePercentageError(Loss):
+    _kind = MAPE
+
+    def __init__(self, reduction="auto", name="mean_absolute_percentage_error"):
+        super().__init__(reduction, name)
+
+
+class MeanSquaredLogarithmicError(Loss):
+    _kind = MSLE
+
+    def __init__(self, reduction="auto", name="mean_squared_logarithmic_error"):
+        super().__init__(reduction, name)
+
+
+class Huber(Loss):
+    _kind = HUBER
+
+    def __init__(self, delta=1.0, reduction="auto", name="huber_loss"):
+        super().__init__(reduction, name)
+        self.delta = delta
+        if not float(delta) > 0:
+            raise ValueError(f"Huber: delta must be > 0, got {delta}")
+
+    def term(self):
+        return (super().term()[0], 0, float(self.delta), 0.0)
+
+    def get_config(self):
+        return dict(super().get_config(), delta=self.delta)
+
+
+class LogCosh(Loss):
+    _kind = LOGCOSH
+
+    def __init__(self, reduction="auto", name="log_cosh"):
+        super().__init__(reduction, name)
+
+
+class BinaryCrossentropy(Loss):
+    _kind = BCE
+
+    def __init__(self, from_logits=False, label_smoothing=0, reduction="auto", name="binary_crossentropy"):
+        super().__init__(reduction, name)
+        self.from_logits, self.label_smoothing = from_logits, label_smoothing
+        if not 0.0 <= float(label_smoothing) <= 1.0:
+            raise ValueError(f"BinaryCrossentropy: label_smoothing must lie in [0, 1], got {label_smoothing}")
+
+    def term(self):
+        return (super().term()[0], int(bool(self.from_logits)), 0.0, float(self.label_smoothing))
+
+    def get_config(self):
+        return dict(super().get_config(), from_logits=self.from_logits, label_smoothing=self.label_smoothing)
+
+
+class Poisson(Loss):
+    _kind = POISSON
+
+    def __init__(self, reduction="auto", name="poisson"):
+        super().__init__(reduction, name)
+
+
+class _NotImplementedLoss(Loss):
+    """A Keras loss the kernels do not implement: it can be built and serialized, compile() refuses it."""
+
+    def __init__(self, *args, reduction="auto", name=None, **kwargs):
+        super().__init__(reduction, name)
+        self._config = kwargs
+
+    def term(self):
+        raise NotImplementedError(f"loss {type(self).__name__} is not implemented: the kernels evaluate "
+                                  f"{', '.join(_BUILTIN)}")
+
+    def get_config(self):
+        return dict(super().get_config(), **self._config)
+
+
+class Hinge(_NotImplementedLoss):
+    pass
+
+
+class SquaredHinge(_NotImplementedLoss):
+    pass
+
+
+class CategoricalHinge(_NotImplementedLoss):
+    pass
+
+
+class CategoricalCrossentropy(_NotImplementedLoss):
+    pass
+
+
+class SparseCategoricalCrossentropy(_NotImplementedLoss):
+    pass
+
+
+class KLDivergence(_NotImplementedLoss):
+    pass
+
+
+class CosineSimilarity(_NotImplementedLoss):
+    pass
+
+
+_BUILTIN = {c.__name__: c for c in (MeanSquaredError, MeanAbsoluteError, MeanAbsolutePercentageError,
+                                    MeanSquaredLogarithmicError, Huber, LogCosh, BinaryCrossentropy, Poisson)}
+_NOT_IMPLEMENTED = {c.__name__: c for c in (Hinge, SquaredHinge, CategoricalHinge, CategoricalCrossentropy,
+                                            SparseCategoricalCrossentropy, KLDivergence, CosineSimilarity)}
+
+# the function names of tf.keras.losses (case-insensitive here, as compile() always was): name -> term
+FUNCTIONS = {
+    "mse": (MSE, 0, 0.0, 0.0), "mean_squared_error": (MSE, 0, 0.0, 0.0),
+    "mae": (MAE, 0, 0.0, 0.0), "mean_absolute_error": (MAE, 0, 0.0, 0.0),
+    "mape": (MAPE, 0, 0.0, 0.0), "mean_absolute_percentage_error": (MAPE, 0, 0.0, 0.0),
+    "msle": (MSLE, 0, 0.0, 0.0), "mean_squared_logarithmic_error": (MSLE, 0, 0.0, 0.0),
+    "huber": (HUBER, 0, 1.0, 0.0),
+    "logcosh": (LOGCOSH, 0, 0.0, 0.0), "log_cosh": (LOGCOSH, 0, 0.0, 0.0),
+    "binary_crossentropy": (BCE, 0, 0.0, 0.0),
+    "poisson": (POISSON, 0, 0.0, 0.0),
+}
+NOT_IMPLEMENTED_FUNCTIONS = frozenset((
+    "hinge", "squared_hinge", "categorical_hinge", "categorical_crossentropy", "sparse_categorical_crossentropy",
+    "kld", "kl_divergence", "kullback_leibler_divergence", "cosine_similarity"))
+
+
+def get(identifier):
+    """A loss function name or a Loss object as is; a {"class_name", "config"} dict deserialized."""
+    if identifier is None or isinstance(identifier, (str, Loss)):
+        return identifier
+    if isinstance(identifier, dict):
+        return deserialize(identifier)
+    if callable(identifier):
+        return identifier
+    raise ValueError(f"Could not interpret loss function identifier: {identifier!r}")
+
+
+def serialize(loss):
+    """A name stays a name; an object becomes {"class_name", "config"} (what Keras writes in training_config)."""
+    if isinstance(loss, Loss):
+        return {"class_name": type(loss).__name__, "config": loss.get_config()}
+    return loss
+
+
+def deserialize(config, custom_objects=None):
+    if isinstance(config, str):
+        return config
+    classes = dict(_BUILTIN, **_NOT_IMPLEMENTED, **(custom_objects or {}))
+    name = config.get("class_name") if isinstance(config, dict) else None
+    if name not in classes:
+        raise ValueError(f"Unknown loss function: {name}")
+    return classes[name].from_config(config.get("config", {}))
+
+
+def loss_term(identifier):
+    """The kernels' term of one output's loss.  ValueError: an unknown name; NotImplementedError: a Keras loss the
+    kernels do not implement, None (no loss for the output) or a callable of one's own."""
+    if identifier is None:
+        raise NotImplementedError("loss=None for an output is not implemented: both outputs need a loss")
+    if isinstance(identifier, str):
+        key = identifier.lower()
+        if key in FUNCTIONS:
+            return FUNCTIONS[key]
+        if key in NOT_IMPLEMENTED_FUNCTIONS or identifier in _NOT_IMPLEMENTED:
+            raise NotImplementedError(f"loss {identifier!r} is not implemented: the kernels evaluate "
+                                      f"{', '.join(sorted(set(FUNCTIONS)))}")
+        raise ValueError(f"Unknown loss function: {identifier}")
+    if isinstance(identifier, Loss):
+        return identifier.term()
+    if callable(identifier):
+        raise NotImplementedError(f"loss {getattr(identifier, '__name__', identifier)!r}: a loss of one's own cannot run "
+                                  "in the kernels; use a built-in Keras loss")
+    raise ValueError(f"Could not interpret loss function identifier: {identifier!r}")
+
+
+# ---- compile() ---------------------------------------------------------------------------------------------------------
+class LossSpec:
+    """The loss of a training step as the kernels see it: per output (class, regression) the loss term, its weight and
+    up to MAX_METRICS metric terms; hashable, so that it keys recorded step plans.  A term is (kind, from_logits, param,
+    label_smoothing).  metric_names (Keras' "<output>_<name>", class output first) are not part of the key."""
+
+    def __init__(self, losses, weights=(1.0, 1.0), metrics=((), ()), metric_names=()):
+        self.losses = tuple(tuple(t) for t in losses)
+        self.weights = tuple(float(w) for w in weights)
+        self.metrics = tuple(tuple(tuple(t) for t in m) for m in metrics)
+        self.metric_names = tuple(metric_names)
+        if len(self.losses) != 2 or len(self.weights) != 2 or len(self.metrics) != 2:
+            raise ValueError("a LossSpec has two outputs")
+        if any(len(m) > MAX_METRICS for m in self.metrics):
+            raise ValueError(f"at most {MAX_METRICS} metrics per output are implemented")
+
+    @property
+    def config(self):
+        return (self.losses, self.weights, self.metrics)
+
+    @property
+    def n_metrics(self):
+        return len(self.metrics[0]) + len(self.metrics[1])
+
+    def descriptor(self):
+        """The lisec_loss_cfg (an _lib.LossCfg)."""
+        d = _lib.LossCfg()
+
+        def fill(dst, t):
+            dst.kind, dst.from_logits, dst.param, dst.label_smoothing = int(t[0]), int(t[1]), float(t[2]), float(t[3])
+
+        for o in range(2):
+            fill(d.loss[o], self.losses[o])
+            d.weight[o] = self.weights[o]
+            d.n_metrics[o] = len(self.metrics[o])
+            for j, t in enumerate(self.metrics[o]):
+                fill(d.metric[o][j], t)
+        return d
+
+    def __eq__(self, other):
+        return isinstance(other, LossSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(self.config)
+
+    def __repr__(self):
+        return f"LossSpec{self.config}"
+
+
+LEGACY = {"mse": ((MSE, 0, 0.0, 0.0), (MSE, 0, 0.0, 0.0)),
+          "smoothl1_ce": ((SIGMOID_CE_CLAMPED, 0, 0.0, 0.0), (SMOOTH_L1, 0, 0.0, 0.0))}
+
+
+def _per_output(arg, what):
+    """One value for both outputs, a list of two in output order, or a dict keyed by output name -> [cls, reg]."""
+    if isinstance(arg, dict):
+        bad = [k for k in arg if k not in OUTPUTS]
+        if bad:
+            raise ValueError(f"Unknown entries in {what} dictionary: {bad}. Only expected following keys: {list(OUTPUTS)}")
+        return [arg.get(o) for o in OUTPUTS]
+    if isinstance(arg, (list, tuple)):
+        if len(arg) != 2:
+            raise ValueError(f"When passing a list as {what}, it should have one entry per model output. The model has 2 "
+                             f"outputs, but you passed {what}={list(arg)!r}")
+        return list(arg)
+    return [arg, arg]
+
+
+def _weights(loss_weights):
+    if loss_weights is None:
+        return (1.0, 1.0)
+    if not isinstance(loss_weights, (list, tuple, dict)):
+        raise ValueError(f"loss_weights must be a list or a dict, got {loss_weights!r}")
+    w = _per_output(loss_weights, "loss_weights")
+    return tuple(1.0 if x is None else float(x) for x in w)
+
+
+def _legacy_key(loss):
+    """'mse' / 'smoothl1_ce' for the spellings compile() accepted before the Keras losses, else None."""
+    if isinstance(loss, str) and loss.lower() in ("smoothl1_ce",):
+        return "smoothl1_ce"
+    if isinstance(loss, (list, tuple)) and all(isinstance(x, str) for x in loss):
+        kinds = [x.lower() for x in loss]
+        if kinds == ["cross_entropy", "smooth_l1"] or kinds == ["smoothl1_ce"]:
+            return "smoothl1_ce"
+    return None
+
+
+def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
+    """Model.compile's loss arguments -> (step loss, metric names).  The step loss is the plain string 'mse' or
+    'smoothl1_ce' -- lisec_rpn_loss, the reference's step unchanged -- when the loss is MSE on both outputs, or the legacy
+    'smoothl1_ce' spelling, with neither loss_weights nor metrics; otherwise a LossSpec (lisec_head_loss).  Every refusal
+    is raised here: ValueError (unknown name, unknown output key, a list of the wrong length), NotImplementedError (a Keras
+    loss or metric the kernels do not implement, one's own callable, loss=None for an output, weighted_metrics)."""
+    from . import metrics as metrics_mod
+    if weighted_metrics is not None:
+        raise NotImplementedError("weighted_metrics is not implemented (there are no sample weights)")
+    legacy = _legacy_key(loss)
+    if legacy is not None:
+        terms = LEGACY[legacy]
+    else:
+        terms = tuple(loss_term(get(x)) for x in _per_output(loss, "loss"))
+    weights = _weights(loss_weights)
+    mterms, names = metrics_mod.compile_metrics(metrics)
+    if loss_weights is None and not any(mterms):
+        if legacy is not None:
+            return legacy, []
+        if terms == LEGACY["mse"]:
+            return "mse", []
+    return LossSpec(terms, weights, mterms, names), list(names)

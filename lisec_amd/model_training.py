@@ -3,8 +3,9 @@
     get_voxel, VFE_preprocessing, combine_lidar_data, rotate_points, RepeatLayer, MaxPoolingVFELayer,
     createModel, load_model, optimizers.SGD, optimizers.Adam, train, train_with_model
 
-and, for Model.fit / Model.evaluate, the tf.keras 2.4 learning-rate schedules (optimizers.schedules) and callbacks
-(callbacks.Callback, LearningRateScheduler, EarlyStopping, ModelCheckpoint, ReduceLROnPlateau).
+and, for Model.fit / Model.evaluate, the tf.keras 2.4 learning-rate schedules (optimizers.schedules), callbacks
+(callbacks.Callback, LearningRateScheduler, EarlyStopping, ModelCheckpoint, ReduceLROnPlateau), losses and metrics
+(losses.MeanSquaredError, ..., BinaryCrossentropy, Huber; metrics.BinaryAccuracy, ...) of compile().
 
 The Keras graph is replaced by lisec_amd.network.LisecNet (HIP kernels behind the C ABI); lidar sweeps
 stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacked in host RAM
@@ -16,13 +17,14 @@ import math
 import numbers
 import os
 import time
+import warnings
 
 import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, lr_schedules, ops
-from .network import LisecNet, OptimizerSpec
+from . import callbacks, losses, lr_schedules, metrics, ops
+from .network import LisecNet, LossSpec, OptimizerSpec
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
 
@@ -366,28 +368,39 @@ class Model:
             self.net.params.touch()
 
     # -- compile / fit / predict / save ------------------------------------------------------------
-    def compile(self, optimizer, loss):
+    def compile(self, optimizer, loss, metrics=None, loss_weights=None, weighted_metrics=None):
         """compile(optimizer=sgd, loss=['mse','mse']) (model_training.py:296); optimizer: optimizers.SGD / optimizers.Adam
         or the string 'sgd' / 'adam'.  A fresh optimizer discards every slot (momentum accumulators, Adam moments) and the
-        iteration count, as re-compiling does in the reference (:339-340)."""
+        iteration count, as re-compiling does in the reference (:339-340).
+        loss: a tf.keras 2.4 loss (a name or a losses.* object; see lisec_amd/losses.py) for both outputs, a list of two in
+        output order or a dict keyed by 'ClassificationLayer' / 'RegressionLayer'; also the project's 'smoothl1_ce' (=
+        ['cross_entropy', 'smooth_l1']: sigmoid cross-entropy on labels clamped to [0, 1] + SmoothL1).  loss_weights: a list
+        or dict of floats (default 1): the step minimises w_c*L_c + w_r*L_r, History's `loss`; the per-output losses are
+        logged unweighted.  metrics: a list (for each output), a list of two lists or a dict per output name; logged as
+        "<output>_<name>" (see metrics_names).  weighted_metrics: not implemented (there are no sample weights).
+        Every refusal (ValueError, NotImplementedError) is raised here, before any launch."""
         optimizer = optimizers.get(optimizer)
-        if isinstance(loss, (list, tuple)):
-            kinds = [str(x).lower() for x in loss]
-            if kinds == ['mse', 'mse']:
-                loss = 'mse'
-            elif kinds == ['cross_entropy', 'smooth_l1'] or kinds == ['smoothl1_ce']:
-                loss = 'smoothl1_ce'
-            else:
-                raise ValueError(f"unsupported loss list {loss}")
-        if loss not in ('mse', 'smoothl1_ce'):
-            raise ValueError(f"unsupported loss {loss}")
-        self.optimizer, self.loss = optimizer, loss
+        step_loss, names = losses.compile_loss(loss, loss_weights, metrics, weighted_metrics)
+        self.optimizer, self.loss = optimizer, step_loss
+        self._metric_names = names
+        # the arguments as given, for the training_config of save() (a legacy step records today's ['mse','mse'])
+        self._compile_args = None if isinstance(step_loss, str) else dict(loss=loss, loss_weights=loss_weights,
+                                                                         metrics=metrics)
         self.net._prepare_training()
         for name in optimizer.spec().slots:
             self.net.slot(name)
         for t in self.net.slots().values():
             t.zero_()
         self.net.iterations = 0
+
+    @property
+    def metrics_names(self):
+        """['loss', 'ClassificationLayer_loss', 'RegressionLayer_loss', <"<output>_<metric>" in compile order>]: the keys of
+        History and of evaluate(return_dict=True), the order of evaluate()'s list.  Unlike Keras, which fills it after the
+        first batch, it is set by compile() ([] before)."""
+        if getattr(self, "optimizer", None) is None:
+            return []
+        return list(_LOSS_NAMES) + list(getattr(self, "_metric_names", []))
 
     def _as_samples(self, x):
         if isinstance(x, SparseVoxels):
@@ -416,7 +429,8 @@ class Model:
         before shuffling; validation_data takes precedence): after the steps of an epoch that validation_freq selects (an
         int: every validation_freq-th epoch; a container: those 1-based epochs), evaluate() runs on the validation sweeps
         (validation_steps of them at most) with on_test_begin / on_test_end, and val_loss, val_ClassificationLayer_loss and
-        val_RegressionLayer_loss join the logs of on_epoch_end and History.  fit ends after any epoch whose callbacks set
+        val_RegressionLayer_loss join the logs of on_epoch_end and History.  The metrics of compile() are logged as epoch
+        means under metrics_names, and with validation as val_<name>.  fit ends after any epoch whose callbacks set
         model.stop_training."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
@@ -477,6 +491,8 @@ class Model:
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
             tot_dev = torch.zeros(3, dtype=torch.float64, device=dev)
+            nm = len(getattr(self, "_metric_names", ()))
+            met_dev = torch.zeros(nm, dtype=torch.float64, device=dev) if nm else None
             every = max(1, steps // 20)
             t0 = time.time()
             for st in range(steps):
@@ -498,13 +514,16 @@ class Model:
                     self.net.train_step(samples[i], yc, yr, loss=self.loss, opt=opt,
                                         allreduce=self.dp.bucketed() if self.dp is not None else None)
                 tot_dev += self.net.loss_out
+                if nm:
+                    met_dev += self.net.metric_out[:nm]
                 if verbose and ((st + 1) % every == 0 or st + 1 == steps):
                     print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / (st + 1):.4f}", end="", flush=True)
             tot = tot_dev.cpu().numpy()
             if verbose:
                 print(f" - {time.time() - t0:.1f}s")
-            logs = {key: float(v) for key, v in zip(("loss", "ClassificationLayer_loss", "RegressionLayer_loss"),
-                                                    tot / max(steps, 1))}
+            if nm:
+                tot = np.concatenate([tot, met_dev.cpu().numpy()])
+            logs = {key: float(v) for key, v in zip(self.metrics_names, tot / max(steps, 1))}
             if val is not None and _should_validate(epoch, validation_freq):
                 vlogs = self._evaluate(*val, callbacks=callbacks, verbose=0)
                 logs.update({"val_" + key: v for key, v in vlogs.items()})
@@ -596,8 +615,8 @@ class Model:
 
     def evaluate(self, x, y, batch_size=None, verbose=1, sample_weight=None, steps=None, callbacks=None,
                  return_dict=False):
-        """model.evaluate(x, [y_cls, y_reg]) -> [loss, ClassificationLayer_loss, RegressionLayer_loss] (a dict with those
-        keys with return_dict=True): the compiled loss with inference BatchNormalization (the moving statistics), as a mean
+        """model.evaluate(x, [y_cls, y_reg]) -> [loss, ClassificationLayer_loss, RegressionLayer_loss, metrics...] in the
+        order of metrics_names (a dict with those keys with return_dict=True): the compiled loss and metrics with inference BatchNormalization (the moving statistics), as a mean
         over the evaluated sweeps.  The sweeps are independent, so every batch_size gives that value -- Keras' mean
         weighted by batch size; batch_size (Keras' default 32) only sets what `steps` counts: steps * batch_size sweeps.
         callbacks get on_test_begin / on_test_end.  Each sweep runs the eager forward(training=False), or, with
@@ -620,15 +639,15 @@ class Model:
             cb.set_model(self)
             cb.set_params(dict(verbose=verbose, epochs=1, steps=steps))
         logs = self._evaluate(samples[:n], ycls, yreg, callbacks=callbacks, verbose=verbose)
-        return dict(logs) if return_dict else [logs[k] for k in _LOSS_NAMES]
+        return dict(logs) if return_dict else [logs[k] for k in self.metrics_names]
 
     def _evaluate(self, samples, ycls, yreg, callbacks=(), verbose=0):
         for cb in callbacks:
             cb.on_test_begin()
         t0 = time.time()
         sums = self._eval_sums(samples, ycls, yreg)
-        count = sums[3]
-        logs = {k: (float(v / count) if count else float("nan")) for k, v in zip(_LOSS_NAMES, sums[:3])}
+        count = sums[-1]
+        logs = {k: (float(v / count) if count else float("nan")) for k, v in zip(self.metrics_names, sums[:-1])}
         if verbose:
             print(f"{int(count)}/{int(count)} - {time.time() - t0:.1f}s - " +
                   " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
@@ -637,7 +656,7 @@ class Model:
         return logs
 
     def _eval_sums(self, samples, ycls, yreg):
-        """float64 [total, class, regression, sweeps] summed over the sweeps, read back once.  Data parallel: rank r takes
+        """float64 [total, class, regression, metrics..., sweeps] summed over the sweeps, read back once.  Data parallel: rank r takes
         samples[r::world] (every sweep is evaluated once; DataParallel.shard would drop the tail), evaluates with the
         rank-mean BatchNormalization moving statistics (copy, average, evaluate, restore) and the sums are all-reduced."""
         net, dev = self.net, self.net.device
@@ -654,13 +673,14 @@ class Model:
                 step.reset()
                 acc = step.acc
             else:
-                acc = torch.zeros(4, dtype=torch.float64, device=dev)
+                acc = torch.zeros(4 + len(getattr(self, "_metric_names", ())), dtype=torch.float64, device=dev)
             if idx:
                 on_dev = len(idx) * ycls[0].size * 4 * 8 < (2 << 30)
                 if on_dev:
                     yc_d = torch.from_numpy(np.ascontiguousarray(ycls[idx])).to(dev)
                     yr_d = torch.from_numpy(np.ascontiguousarray(yreg[idx])).to(dev)
-                kind = {"mse": 0, "smoothl1_ce": 1}[self.loss]
+                spec = self.loss if isinstance(self.loss, LossSpec) else None
+                kind = None if spec is not None else {"mse": 0, "smoothl1_ce": 1}[self.loss]
                 for k, i in enumerate(idx):
                     if on_dev:
                         yc, yr = yc_d[k], yr_d[k]
@@ -671,7 +691,10 @@ class Model:
                         step(samples[i]._keepalive, yc, yr)
                     else:
                         net.forward(samples[i], training=False)
-                        ops.rpn_loss_eval(net.act["head"], yc, yr, net.Ho * net.Wo, kind, acc)
+                        if spec is not None:
+                            ops.head_loss_eval(net._loss_descriptor(spec), net.act["head"], yc, yr, net.Ho * net.Wo, acc)
+                        else:
+                            ops.rpn_loss_eval(net.act["head"], yc, yr, net.Ho * net.Wo, kind, acc)
             if self.dp is not None:
                 self.dp.sum_(acc)
             return acc.cpu().numpy().copy()
@@ -749,13 +772,40 @@ class Model:
             for name in o.spec().slots:
                 buf = self.net.slot(name)
                 slots[name] = {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
+        compiled = getattr(self, "_compile_args", None) or {}
         keras_h5.save_model(path, d, self.nx, self.ny, self.nz, self.maxPoints, optimizer=opt,
-                            iterations=self.net.iterations, **slots)
+                            iterations=self.net.iterations, **compiled, **slots)
 
     def summary(self):
         n = self.net.params.n_trainable()
         print(f"LisecNet grid ({self.nz},{self.nx},{self.ny},{self.maxPoints},6) -> "
               f"({self.nx // 2},{self.ny // 2},2) / ({self.nx // 2},{self.ny // 2},14); trainable params: {n:,}")
+
+
+def _deserialize_nested(x, deserialize):
+    """training_config's loss / metrics -> compile() arguments: {"class_name", "config"} dicts become objects, the rest
+    keeps its structure (Keras' _deserialize_nested_config)."""
+    if isinstance(x, dict) and "class_name" in x:
+        return deserialize(x)
+    if isinstance(x, dict):
+        return {k: _deserialize_nested(v, deserialize) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_deserialize_nested(v, deserialize) for v in x]
+    return x
+
+
+def _compile_saved(m, opt, ck):
+    """Compiles a loaded model with the optimizer and the loss, loss_weights and metrics of its training_config."""
+    saved = {k: ck.get(k) for k in ("loss", "loss_weights", "metrics")}
+    try:
+        loss = _deserialize_nested(saved["loss"], losses.deserialize) if saved["loss"] is not None else ['mse', 'mse']
+        m.compile(optimizer=opt, loss=loss, loss_weights=saved["loss_weights"],
+                  metrics=_deserialize_nested(saved["metrics"], metrics.deserialize))
+    except (ValueError, NotImplementedError, TypeError) as e:
+        warnings.warn(f"load_model: could not restore the compiled loss={saved['loss']!r}, "
+                      f"loss_weights={saved['loss_weights']!r}, metrics={saved['metrics']!r} ({e}); "
+                      "compiled with loss=['mse', 'mse']", stacklevel=3)
+        m.compile(optimizer=opt, loss=['mse', 'mse'])
 
 
 def createModel(nx, ny, nz, maxPoints):
@@ -767,7 +817,9 @@ def load_model(path, custom_objects=None):
     """load_model(model_path, custom_objects={'RepeatLayer':…, 'MaxPoolingVFELayer':…}) (:337-338, Predict.py:51-52).
     Reads Keras HDF5 files (the reference's own checkpoints or Model.save's) and the .npz variant.  Like Keras, a file
     that carries a training_config (SGD or Adam) comes back compiled, with the saved iteration count and optimizer slots;
-    a learning-rate schedule in it is rebuilt, and continues from that iteration count."""
+    a learning-rate schedule in it is rebuilt, and continues from that iteration count.  The loss, loss_weights and metrics
+    of the training_config are compiled again when compile() accepts them; otherwise the model is compiled with
+    loss=['mse','mse'] and a warning names what could not be restored."""
     with open(path, "rb") as f:
         magic = f.read(8)
     dev = _lib.require_gpu()
@@ -791,7 +843,7 @@ def load_model(path, custom_objects=None):
                                   epsilon=o["epsilon"], amsgrad=o["amsgrad"])
         else:
             opt = optimizers.SGD(lr=lr, decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
-        m.compile(optimizer=opt, loss=['mse', 'mse'])
+        _compile_saved(m, opt, ck)
         m.net.iterations = ck["iterations"]
         p = m.net.params
         for name in opt.spec().slots:

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, lr_schedules, ops
+from .losses import LossSpec
 from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
@@ -283,6 +284,8 @@ class LisecNet:
         self._lr_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
         self._lr_host = None
         self.loss_out = torch.zeros(3, dtype=f32, device=dev)
+        # the metrics of a LossSpec loss (lisec_head_loss), class output's first; fixed address, like loss_out
+        self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
 
     @property
     def iterations(self):
@@ -716,6 +719,8 @@ class LisecNet:
     def backward(self, y_cls, y_reg, loss="mse", grad_scale=1.0, rpn_grads_ready=None, side_filler=None):
         """y_cls (Ho,Wo,2), y_reg (Ho,Wo,14): float32 device tensors.  Fills self.grad (layout of theta)
         and self.loss_out = [total, class, regression].  Must follow forward(training=True).
+        loss: 'mse' (loss=['mse','mse'], the reference's) or 'smoothl1_ce' -- lisec_rpn_loss -- or a LossSpec (Keras losses,
+        loss_weights and metrics: lisec_head_loss, which also fills self.metric_out[:loss.n_metrics]).
         side_filler: optional callable issued on the second stream behind the head-phase leaves, where that stream has
         nothing to do for ~200 us (the weight gradients of the last RPN block wait for its chain): independent work such as
         the NEXT sweep's voxelisation (PipelinedStep).
@@ -727,6 +732,13 @@ class LisecNet:
             return self._backward(y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler)
         finally:
             _lib.pin_stream(prev_pin)
+
+    def _loss_descriptor(self, spec):
+        """The lisec_loss_cfg of a LossSpec, built once per spec."""
+        cache = self.__dict__.setdefault("_loss_descs", {})
+        if spec not in cache:
+            cache[spec] = spec.descriptor()
+        return cache[spec]
 
     def _tail_supported(self, c, dst_name):
         """Can the Dense data gradient of block dst_name[:-2] ride on the direct data gradient of conv `c`?  (asked of the
@@ -813,8 +825,12 @@ class LisecNet:
             flush_side()
 
         self._mark("bwd:start")
-        kind = {"mse": 0, "smoothl1_ce": 1}[loss]
-        ops.rpn_loss(a["head"], y_cls, y_reg, M, kind, d["head"], self.loss_out, grad_scale=grad_scale)
+        if isinstance(loss, LossSpec):
+            ops.head_loss(self._loss_descriptor(loss), a["head"], y_cls, y_reg, M, d["head"], self.loss_out,
+                          self.metric_out, grad_scale=grad_scale)
+        else:
+            kind = {"mse": 0, "smoothl1_ce": 1}[loss]
+            ops.rpn_loss(a["head"], y_cls, y_reg, M, kind, d["head"], self.loss_out, grad_scale=grad_scale)
         # ---- heads (model_training.py:254-255) ---------------------------------------------------
         # only the data gradient is on the way to the rest of the backward pass: the heads' weight and bias gradients and
         # the deconv bias gradients (column sums of the concat gradient) are leaves and go to the second stream
@@ -1435,10 +1451,10 @@ class PipelinedStep(_StepPlans):
 
 class EvalStep:
     """One evaluation sweep -- voxelise a fixed-capacity padded sweep (as RecordedStep), forward(training=False), add the
-    sweep's loss to a device accumulator (lisec_rpn_loss_eval) -- recorded ONCE as a step plan and re-issued by one C call
-    per sweep (Model.evaluate and the validation of Model.fit with LISEC_TUNING=eval_plan=1; by default they run the eager
-    forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps]
-    (float64, device) is read by the host once per evaluation.  Invariants:
+    sweep's loss to a device accumulator (lisec_rpn_loss_eval; lisec_head_loss_eval for a LossSpec) -- recorded ONCE as a
+    step plan and re-issued by one C call per sweep (Model.evaluate and the validation of Model.fit with
+    LISEC_TUNING=eval_plan=1; by default they run the eager forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps] -- with a LossSpec
+    [total, class, regression, metrics..., sweeps] -- (float64, device) is read by the host once per evaluation.  Invariants:
 
       BN fold   inference scale/shift come from ops.bn_fold (LisecNet._bn_after), cached per (params_version,
                 state_version, params.version); a training step overwrites bnstate with batch statistics and moves the
@@ -1463,17 +1479,20 @@ class EvalStep:
     def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse"):
         import ctypes
         self.net, self.vox, self.capacity = net, voxelizer, int(capacity)
-        self.kind = {"mse": 0, "smoothl1_ce": 1}[loss]
+        self.loss = loss
+        # a LossSpec: lisec_head_loss_eval, acc = [total, class, regression, metrics..., sweeps]
+        self.nacc = 4 + (loss.n_metrics if isinstance(loss, LossSpec) else 0)
+        self.kind = None if isinstance(loss, LossSpec) else {"mse": 0, "smoothl1_ce": 1}[loss]
         dev = net.device
         self.lib = _lib.load()
         self.points = torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev)
         self.ycls = torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev)
         self.yreg = torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev)
-        self.acc = torch.zeros(4, dtype=torch.float64, device=dev)
+        self.acc = torch.zeros(self.nacc, dtype=torch.float64, device=dev)
         self.stream_handle = torch.cuda.current_stream().cuda_stream
         self.sample = self.vox(self.points)
         self.prepare()
-        scratch = torch.zeros(4, dtype=torch.float64, device=dev)
+        scratch = torch.zeros(self.nacc, dtype=torch.float64, device=dev)
         self._enqueue(scratch)                    # eager warm-up: lazy workspaces, descriptor tables, events
         torch.cuda.synchronize(dev)
         self.plan = ctypes.c_void_p()
@@ -1497,7 +1516,10 @@ class EvalStep:
             net.forward(self.sample, training=False)
         finally:
             net._pack_pending, net._late_pending = pending
-        ops.rpn_loss_eval(net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, self.kind, acc)
+        if self.kind is None:
+            ops.head_loss_eval(net._loss_descriptor(self.loss), net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, acc)
+        else:
+            ops.rpn_loss_eval(net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, self.kind, acc)
 
     def prepare(self):
         """Packed kernels and BatchNormalization folds current for the weights and statistics of now (see the class)."""

@@ -379,6 +379,29 @@ def rpn_loss_eval(head, y_cls, y_reg, M, kind, acc):
                                                _lib.ptr(ws), ws.numel(), _lib.current_stream()))
 
 
+def _loss_workspace(device):
+    ws = _ew_workspace(device)
+    assert ws.numel() >= _lib.load().lisec_head_loss_workspace_bytes()
+    return ws
+
+
+def head_loss(cfg, head, y_cls, y_reg, M, dhead, loss_out, metric_out=None, grad_scale=1.0):
+    """The Keras losses / metrics of cfg (an _lib.LossCfg, lisec_loss_cfg): dhead, loss_out = [total, class, regression]
+    and metric_out (float32 device tensor, one value per metric: the class output's, then the regression output's)."""
+    ws = _loss_workspace(head.device)
+    _lib.check(_lib.load().lisec_head_loss(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                                           grad_scale, _lib.ptr(dhead), _lib.ptr(loss_out), _lib.ptr(metric_out),
+                                           _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
+def head_loss_eval(cfg, head, y_cls, y_reg, M, acc):
+    """Adds the values head_loss would write -- [total, class, regression, metrics...], the same fp32 bits -- to acc
+    (float64 device tensor of 4 + number of metrics) and counts the sweep in its last word; no gradient."""
+    ws = _loss_workspace(head.device)
+    _lib.check(_lib.load().lisec_head_loss_eval(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                                                _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
 def sgd_nesterov_step(theta, grad, velocity, lr_t, momentum):
     _lib.check(_lib.load().lisec_sgd_nesterov_step(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity),
                                                    theta.numel(), lr_t, momentum, _lib.current_stream()))
