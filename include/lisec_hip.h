@@ -688,6 +688,42 @@ int lisec_adam_step_dev(float* theta, const float* grad, float* m, float* v, flo
                         long long n, double lr, double decay, float beta1, float beta2, float epsilon, long long* state,
                         int advance, lisec_stream_t stream);
 
+/* The other tf.keras 2.4 optimizers (csrc/optim_keras.hip), with the arithmetic of TF's dense kernels, the same state /
+ * advance semantics and lr_t = (float)(lr / (1 + decay*iterations)) (Nadam: (float)lr).  Per-step scalars in fp32.
+ * LISEC_EINVAL, nothing enqueued: a NULL pointer, a missing or extra slot, n % 4 != 0, rho or a beta outside [0, 1), a
+ * negative momentum, epsilon or schedule_decay, or advance not 0/1.
+ * RMSprop, c = 1 - rho; mom is NULL iff momentum == 0, mg is NULL iff !centered:
+ *   momentum == 0 (eps outside the root):  rms <- rho*rms + c*g^2;  centered: mg <- rho*mg + c*g, den = rms - mg^2
+ *                                          (else den = rms);  w <- w - lr_t*g/(sqrt(den) + eps)
+ *   momentum > 0 (eps inside the root):    rms <- rms + (g^2 - rms)*c;  centered: mg <- mg + (g - mg)*c,
+ *                                          den = rms - mg^2 + eps (else rms + eps);
+ *                                          mom <- momentum*mom + lr_t*g/sqrt(den);  w <- w - mom */
+int lisec_rmsprop_step_dev(float* theta, const float* grad, float* rms, float* mom /* NULL iff momentum == 0 */,
+                           float* mg /* NULL iff !centered */, long long n, double lr, double decay, float rho,
+                           float momentum, float epsilon, int centered, long long* state, int advance,
+                           lisec_stream_t stream);
+/* Adagrad (accumulator starts at initial_accumulator_value):  acc <- acc + g^2;  w <- w - lr_t*g/(sqrt(acc) + eps) */
+int lisec_adagrad_step_dev(float* theta, const float* grad, float* accumulator, long long n, double lr, double decay,
+                           float epsilon, long long* state, int advance, lisec_stream_t stream);
+/* Adadelta, c = 1 - rho:  ag <- ag*rho + g^2*c;  u = sqrt(av + eps)*rsqrt(ag + eps)*g;  w <- w - u*lr_t;
+ *                         av <- av*rho + u^2*c   (ag: accum_grad, av: accum_var) */
+int lisec_adadelta_step_dev(float* theta, const float* grad, float* accum_grad, float* accum_var, long long n, double lr,
+                            double decay, float rho, float epsilon, long long* state, int advance, lisec_stream_t stream);
+/* Adamax, t = iterations + 1, b1^t in fp32:  m <- m + (g - m)(1 - b1);  v <- max(b2*v, |g|);
+ *                                            w <- w - lr_t/(1 - b1^t) * (m/(v + eps)) */
+int lisec_adamax_step_dev(float* theta, const float* grad, float* m, float* v, long long n, double lr, double decay,
+                          float beta1, float beta2, float epsilon, long long* state, int advance, lisec_stream_t stream);
+/* Nadam, t = iterations + 1, d = schedule_decay; its lr is NOT divided by 1 + decay*iterations:
+ *   mu_t = b1*(1 - 0.5*0.96^(d*t)), mu_t1 = b1*(1 - 0.5*0.96^(d*(t + 1))), P = momentum_cache*mu_t, P1 = P*mu_t1
+ *   m <- b1*m + (1 - b1)*g;  v <- b2*v + (1 - b2)*g^2
+ *   w <- w - lr*((1 - mu_t)*g/(1 - P) + mu_t1*m/(1 - P1)) / (sqrt(v/(1 - b2^t)) + eps)
+ * momentum_cache: one float in device memory (1 before the first step).  Every workgroup reads it; the call that ends
+ * the step (advance = 1) stores P into it where it advances state[0], so that both calls of a split step compute the
+ * same P and the cache moves once per step. */
+int lisec_nadam_step_dev(float* theta, const float* grad, float* m, float* v, float* momentum_cache, long long n,
+                         double lr, float beta1, float beta2, float epsilon, float schedule_decay, long long* state,
+                         int advance, lisec_stream_t stream);
+
 /* Learning-rate schedules (tf.keras 2.4 optimizers.schedules, OptimizerV2._decayed_lr) read by the update kernels from
  * DEVICE memory, like the iteration count: a recorded step keeps replaying correctly, and the host may rewrite the
  * descriptor between steps (lisec_lr_schedule_set, stream-ordered) without recording the step again.  With s = state[0],
@@ -751,6 +787,24 @@ int lisec_sgd_step_sched(float* theta, const float* grad, float* velocity /* NUL
 int lisec_adam_step_sched(float* theta, const float* grad, float* m, float* v, float* vhat /* NULL iff !amsgrad */,
                           long long n, const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon,
                           long long* state, int advance, lisec_stream_t stream);
+/* The same for the optimizers of csrc/optim_keras.hip (a CONSTANT descriptor gives the bits of their by-value entries;
+ * Nadam's descriptor is built with decay = 0). */
+int lisec_rmsprop_step_sched(float* theta, const float* grad, float* rms, float* mom /* NULL iff momentum == 0 */,
+                             float* mg /* NULL iff !centered */, long long n, const lisec_lr_schedule* sched, float rho,
+                             float momentum, float epsilon, int centered, long long* state, int advance,
+                             lisec_stream_t stream);
+int lisec_adagrad_step_sched(float* theta, const float* grad, float* accumulator, long long n,
+                             const lisec_lr_schedule* sched, float epsilon, long long* state, int advance,
+                             lisec_stream_t stream);
+int lisec_adadelta_step_sched(float* theta, const float* grad, float* accum_grad, float* accum_var, long long n,
+                              const lisec_lr_schedule* sched, float rho, float epsilon, long long* state, int advance,
+                              lisec_stream_t stream);
+int lisec_adamax_step_sched(float* theta, const float* grad, float* m, float* v, long long n,
+                            const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon, long long* state,
+                            int advance, lisec_stream_t stream);
+int lisec_nadam_step_sched(float* theta, const float* grad, float* m, float* v, float* momentum_cache, long long n,
+                           const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon, float schedule_decay,
+                           long long* state, int advance, lisec_stream_t stream);
 
 /* x *= s  (gradient averaging after the data-parallel all-reduce) */
 int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);

@@ -259,6 +259,27 @@ def _declare(lib):
     lib.lisec_sgd_step_sched.argtypes = [P, P, P, LL, P, c_float, c_int, P, c_int, P]
     lib.lisec_adam_step_sched.restype = c_int
     lib.lisec_adam_step_sched.argtypes = [P, P, P, P, P, LL, P, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_rmsprop_step_dev.restype = c_int
+    lib.lisec_rmsprop_step_dev.argtypes = [P, P, P, P, P, LL, c_double, c_double, c_float, c_float, c_float, c_int, P,
+                                           c_int, P]
+    lib.lisec_rmsprop_step_sched.restype = c_int
+    lib.lisec_rmsprop_step_sched.argtypes = [P, P, P, P, P, LL, P, c_float, c_float, c_float, c_int, P, c_int, P]
+    lib.lisec_adagrad_step_dev.restype = c_int
+    lib.lisec_adagrad_step_dev.argtypes = [P, P, P, LL, c_double, c_double, c_float, P, c_int, P]
+    lib.lisec_adagrad_step_sched.restype = c_int
+    lib.lisec_adagrad_step_sched.argtypes = [P, P, P, LL, P, c_float, P, c_int, P]
+    lib.lisec_adadelta_step_dev.restype = c_int
+    lib.lisec_adadelta_step_dev.argtypes = [P, P, P, P, LL, c_double, c_double, c_float, c_float, P, c_int, P]
+    lib.lisec_adadelta_step_sched.restype = c_int
+    lib.lisec_adadelta_step_sched.argtypes = [P, P, P, P, LL, P, c_float, c_float, P, c_int, P]
+    lib.lisec_adamax_step_dev.restype = c_int
+    lib.lisec_adamax_step_dev.argtypes = [P, P, P, P, LL, c_double, c_double, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_adamax_step_sched.restype = c_int
+    lib.lisec_adamax_step_sched.argtypes = [P, P, P, P, LL, P, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_nadam_step_dev.restype = c_int
+    lib.lisec_nadam_step_dev.argtypes = [P, P, P, P, P, LL, c_double, c_float, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_nadam_step_sched.restype = c_int
+    lib.lisec_nadam_step_sched.argtypes = [P, P, P, P, P, LL, P, c_float, c_float, c_float, c_float, P, c_int, P]
     lib.lisec_fold_depth.restype = c_int
     lib.lisec_fold_depth.argtypes = [P, P, c_int, LL, c_int, c_int, P, P]
     lib.lisec_scale.restype = c_int

@@ -8,7 +8,9 @@ Predict.py:51-52).  A Keras `.h5` holds
     /model_weights      attrs layer_names, backend, keras_version
         /<layer>        attr weight_names = [b'<layer>/kernel:0', ...]; datasets at <layer>/<weight>:0
     /optimizer_weights  attr weight_names = [b'SGD/iter:0', b'SGD/<layer>/<weight>/momentum:0', ...] + datasets
-                        (Adam: b'Adam/iter:0', every .../m:0, every .../v:0, every .../vhat:0 with amsgrad)
+                        (Adam: b'Adam/iter:0', every .../m:0, every .../v:0, every .../vhat:0 with amsgrad;
+                        RMSprop, Adagrad, Adadelta, Adamax, Nadam: b'<Class>/iter:0', Nadam's
+                        b'Nadam/momentum_cache:0', then their slots kind by kind, as _slot_kinds lists them)
 
 This module rebuilds the layer list that createModel (model_training.py:222-257) produces -- with the names Keras
 assigns automatically (dense, dense_1, batch_normalization_7, conv2d_transpose_2 ...) and the order of
@@ -212,11 +214,31 @@ def _serialize_nested(x):
     return x
 
 
+# Keras' config keys (after name, learning_rate and decay) and defaults of the optimizers beyond SGD and Adam, in
+# Keras' order; Nadam's `decay` is its schedule_decay
+KERAS_EXTRA = {
+    "RMSprop": (("rho", 0.9), ("momentum", 0.0), ("epsilon", 1e-7), ("centered", False)),
+    "Adagrad": (("initial_accumulator_value", 0.1), ("epsilon", 1e-7)),
+    "Adadelta": (("rho", 0.95), ("epsilon", 1e-7)),
+    "Adamax": (("beta_1", 0.9), ("beta_2", 0.999), ("epsilon", 1e-7)),
+    "Nadam": (("beta_1", 0.9), ("beta_2", 0.999), ("epsilon", 1e-7)),
+}
+
+
+def _default_decay(cls):
+    return 0.004 if cls == "Nadam" else 0.0
+
+
 def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
     """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
     loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote)."""
     o = optimizer or {}
-    if o.get("class_name", "SGD") == "Adam":
+    cls = o.get("class_name", "SGD")
+    if cls in KERAS_EXTRA:
+        oc = {"class_name": cls, "config": {
+            "name": cls, "learning_rate": _rate(o.get("lr", 0.001)), "decay": float(o.get("decay", _default_decay(cls))),
+            **{k: type(d)(o.get(k, d)) for k, d in KERAS_EXTRA[cls]}}}
+    elif cls == "Adam":
         oc = {"class_name": "Adam", "config": {
             "name": "Adam", "learning_rate": _rate(o.get("lr", 0.001)), "decay": float(o.get("decay", 0.0)),
             "beta_1": float(o.get("beta_1", 0.9)), "beta_2": float(o.get("beta_2", 0.999)),
@@ -231,20 +253,42 @@ def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
 
 def _slot_kinds(optimizer):
     """(class name, slot kinds in Keras' order): the slots of one kind are written for every variable before the next kind."""
-    if optimizer.get("class_name", "SGD") == "Adam":
+    cls = optimizer.get("class_name", "SGD")
+    if cls == "Adam":
         return "Adam", (("m", "v", "vhat") if optimizer.get("amsgrad") else ("m", "v"))
+    if cls == "RMSprop":
+        return cls, (("rms",) + (("momentum",) if float(optimizer.get("momentum", 0.0)) > 0 else ()) +
+                     (("mg",) if optimizer.get("centered") else ()))
+    if cls == "Adagrad":
+        return cls, ("accumulator",)
+    if cls == "Adadelta":
+        return cls, ("accum_grad", "accum_var")
+    if cls in ("Adamax", "Nadam"):
+        return cls, ("m", "v")
     return "SGD", (("momentum",) if float(optimizer.get("momentum", 0.0)) > 0 else ())
+
+
+def _slot_key(cls, kind):
+    """The save_model / load_model key of the Keras slot `kind` of class `cls`: SGD's "momentum" is its velocity,
+    RMSprop's a buffer of its own."""
+    return "velocity" if cls == "SGD" and kind == "momentum" else kind
+
+
+SLOT_KEYS = ("velocity", "m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad", "accum_var")
 
 
 # ---------------------------------------------------------------------------------------------------
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None, m=None, v=None,
-               vhat=None, loss=None, loss_weights=None, metrics=None):
+               vhat=None, loss=None, loss_weights=None, metrics=None, rms=None, momentum=None, mg=None, accumulator=None,
+               accum_grad=None, accum_var=None, momentum_cache=1.0):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
     compiled: no training_config / optimizer_weights, like Keras).  The slots, each a dict of trainable ParamStore
-    name -> array: velocity (SGD momentum accumulators, momentum > 0), m and v (Adam moments), vhat (AMSGrad).
-    optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
+    name -> array: velocity (SGD momentum accumulators, momentum > 0), m and v (Adam moments), vhat (AMSGrad); rms,
+    momentum (momentum > 0) and mg (centered) of RMSprop; accumulator of Adagrad; accum_grad and accum_var of Adadelta;
+    m and v of Adamax and Nadam.  Other optimizers: dict(class_name=<Keras class>, lr, decay, <their config keys>)
+    (Nadam's decay: schedule_decay); momentum_cache: Nadam's scalar.  optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
     loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
     as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics."""
     layers, _ = keras_layers(nx, ny, nz, maxPoints)
@@ -271,13 +315,17 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
         if optimizer is None:
             return
         cls, kinds = _slot_kinds(optimizer)
-        given = dict(momentum=velocity, m=m, v=v, vhat=vhat)
-        if any(given[k] is None for k in kinds):
+        given = dict(velocity=velocity, m=m, v=v, vhat=vhat, rms=rms, momentum=momentum, mg=mg, accumulator=accumulator,
+                     accum_grad=accum_grad, accum_var=accum_var)
+        if any(given[_slot_key(cls, k)] is None for k in kinds):
             return
-        entries = [(f"{cls}/{var}/{k}:0", given[k][pname]) for k in kinds for var, pname in slots]
+        entries = [(f"{cls}/{var}/{k}:0", given[_slot_key(cls, k)][pname]) for k in kinds for var, pname in slots]
+        head = [f"{cls}/iter:0"] + (["Nadam/momentum_cache:0"] if cls == "Nadam" else [])
         og = f.create_group("optimizer_weights")
-        og.attrs["weight_names"] = [f"{cls}/iter:0".encode()] + [n.encode("utf8") for n, _ in entries]
+        og.attrs["weight_names"] = [n.encode() for n in head] + [n.encode("utf8") for n, _ in entries]
         og.create_dataset(f"{cls}/iter:0", data=np.array(int(iterations), dtype=np.int64))
+        if cls == "Nadam":
+            og.create_dataset("Nadam/momentum_cache:0", data=np.array(momentum_cache, dtype=np.float32))
         for n, a in entries:
             og.create_dataset(n, data=np.asarray(a, dtype=np.float32))
 
@@ -316,8 +364,9 @@ def _suffix_number(name, base):
 def load_model(path, grid=None):
     """Reads a Keras `.h5` written by the reference (or by save_model).  Returns dict(params, nx, ny, nz, maxPoints,
     iterations, optimizer (dict or None, as save_model takes it), loss, loss_weights, metrics (training_config's, as
-    serialized there; None without one), and the slots velocity, m, v, vhat (each a dict of trainable ParamStore name ->
-    array, or None)).  Slots are matched by name, not by position.
+    serialized there; None without one), the slots of SLOT_KEYS (each a dict of trainable ParamStore name -> array, or
+    None; mapped per optimizer class, so "momentum" is SGD's velocity in an SGD file) and momentum_cache (Nadam's, or
+    None)).  Slots are matched by name, not by position.
 
     Layers are matched by class and creation order (the numeric suffix of Keras' automatic names), not by the exact
     suffix: a model built as the second one of a Python session carries shifted suffixes."""
@@ -364,8 +413,8 @@ def load_model(path, grid=None):
                         raise hdf5_lite.H5Error(f"{path}: layer {lname} lacks {w}")
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
-        out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, velocity=None,
-                   m=None, v=None, vhat=None, optimizer=None, loss=None, loss_weights=None, metrics=None)
+        out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, optimizer=None,
+                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, **{k: None for k in SLOT_KEYS})
         if "training_config" in f.attrs:
             tc = json.loads(_text(f.attrs["training_config"]))
             out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))
@@ -374,6 +423,11 @@ def load_model(path, grid=None):
             if oc.get("class_name") == "SGD":
                 out["optimizer"] = dict(lr=c.get("learning_rate", c.get("lr", 0.01)), decay=c.get("decay", 0.0),
                                         momentum=c.get("momentum", 0.0), nesterov=c.get("nesterov", False))
+            elif oc.get("class_name") in KERAS_EXTRA:
+                cls = oc["class_name"]
+                out["optimizer"] = dict(class_name=cls, lr=c.get("learning_rate", c.get("lr", 0.001)),
+                                        decay=c.get("decay", _default_decay(cls)),
+                                        **{k: c.get(k, d) for k, d in KERAS_EXTRA[cls]})
             elif oc.get("class_name") == "Adam":
                 out["optimizer"] = dict(class_name="Adam", lr=c.get("learning_rate", c.get("lr", 0.001)),
                                         decay=c.get("decay", 0.0), beta_1=c.get("beta_1", 0.9),
@@ -387,9 +441,12 @@ def load_model(path, grid=None):
                 if w.endswith("iter:0"):
                     out["iterations"] = int(a)
                     continue
-                m = re.fullmatch(r"[^/]+/(.+)/(momentum|m|v|vhat):0", w)
-                if m and m.group(1) in keras_to_param:
-                    kind = "velocity" if m.group(2) == "momentum" else m.group(2)
-                    found_slots.setdefault(kind, {})[keras_to_param[m.group(1)]] = np.asarray(a, dtype=np.float32)
+                if w.endswith("/momentum_cache:0"):
+                    out["momentum_cache"] = float(np.float32(a))
+                    continue
+                m = re.fullmatch(r"([^/]+)/(.+)/(momentum|m|v|vhat|rms|mg|accumulator|accum_grad|accum_var):0", w)
+                if m and m.group(2) in keras_to_param:
+                    kind = _slot_key(m.group(1), m.group(3))
+                    found_slots.setdefault(kind, {})[keras_to_param[m.group(2)]] = np.asarray(a, dtype=np.float32)
             out.update(found_slots)
         return out

@@ -250,10 +250,11 @@ def _serialize_rate(lr):
 
 
 class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimizers`)
-    """tf.keras 2.4 SGD and Adam (OptimizerV2): lr_t = lr / (1 + decay*iterations) for both, lr either a number or one
-    of the built-in schedules of optimizers.schedules (then lr_t = schedule(iterations) / (1 + decay*iterations)); `lr=`
-    is the legacy spelling of `learning_rate=`.  The updates run as HIP kernels on the flat variables
-    (csrc/eltwise.hip, csrc/optim.hip)."""
+    """tf.keras 2.4 SGD, Adam, RMSprop, Adagrad, Adadelta, Adamax and Nadam (OptimizerV2): lr_t = lr / (1 +
+    decay*iterations) (Nadam: lr), lr either a number or one of the built-in schedules of optimizers.schedules (then
+    lr_t = schedule(iterations) / (1 + decay*iterations); not for Nadam); `lr=` is the legacy spelling of
+    `learning_rate=`.  The updates run as HIP kernels on the flat variables (csrc/eltwise.hip, csrc/optim.hip,
+    csrc/optim_keras.hip)."""
 
     schedules = lr_schedules
 
@@ -292,16 +293,120 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
             return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "beta_1": self.beta_1,
                     "beta_2": self.beta_2, "epsilon": self.epsilon, "amsgrad": self.amsgrad}
 
+    class RMSprop:
+        """Keras' RMSprop: momentum == 0 takes TF's Python path (epsilon outside the square root), momentum > 0
+        ResourceApplyRMSProp / ResourceApplyCenteredRMSProp (epsilon inside it) -- see include/lisec_hip.h."""
+
+        def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, name="RMSprop",
+                     lr=None, decay=0.0, **kwargs):
+            _no_clipping("RMSprop", kwargs)
+            self.lr = _rate(lr if lr is not None else learning_rate)
+            self.decay, self.rho, self.momentum = float(decay), float(rho), float(momentum)
+            self.epsilon, self.centered, self.name = float(epsilon), bool(centered), name
+            if not 0.0 <= self.momentum <= 1.0:
+                raise ValueError("`momentum` must be between [0, 1].")
+            self.spec()                                      # range checks; a schedule the kernels cannot evaluate
+
+        def spec(self, device_lr=False):
+            return OptimizerSpec("rmsprop", self.lr, self.decay, momentum=self.momentum, rho=self.rho,
+                                 epsilon=self.epsilon, centered=self.centered, device_lr=device_lr)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "rho": self.rho,
+                    "momentum": self.momentum, "epsilon": self.epsilon, "centered": self.centered}
+
+    class Adagrad:
+        def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, name="Adagrad", lr=None,
+                     decay=0.0, **kwargs):
+            _no_clipping("Adagrad", kwargs)
+            if initial_accumulator_value < 0.0:
+                raise ValueError(f"initial_accumulator_value must be non-negative: {initial_accumulator_value}")
+            self.lr = _rate(lr if lr is not None else learning_rate)
+            self.decay, self.initial_accumulator_value = float(decay), float(initial_accumulator_value)
+            self.epsilon, self.name = float(epsilon), name
+            self.spec()
+
+        def spec(self, device_lr=False):
+            return OptimizerSpec("adagrad", self.lr, self.decay, epsilon=self.epsilon,
+                                 initial_accumulator_value=self.initial_accumulator_value, device_lr=device_lr)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
+                    "initial_accumulator_value": self.initial_accumulator_value, "epsilon": self.epsilon}
+
+    class Adadelta:
+        def __init__(self, learning_rate=0.001, rho=0.95, epsilon=1e-7, name="Adadelta", lr=None, decay=0.0, **kwargs):
+            _no_clipping("Adadelta", kwargs)
+            self.lr = _rate(lr if lr is not None else learning_rate)
+            self.decay, self.rho, self.epsilon, self.name = float(decay), float(rho), float(epsilon), name
+            self.spec()
+
+        def spec(self, device_lr=False):
+            return OptimizerSpec("adadelta", self.lr, self.decay, rho=self.rho, epsilon=self.epsilon, device_lr=device_lr)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "rho": self.rho,
+                    "epsilon": self.epsilon}
+
+    class Adamax:
+        def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="Adamax", lr=None,
+                     decay=0.0, **kwargs):
+            _no_clipping("Adamax", kwargs)
+            self.lr = _rate(lr if lr is not None else learning_rate)
+            self.decay, self.beta_1, self.beta_2 = float(decay), float(beta_1), float(beta_2)
+            self.epsilon, self.name = float(epsilon), name
+            self.spec()
+
+        def spec(self, device_lr=False):
+            return OptimizerSpec("adamax", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2,
+                                 epsilon=self.epsilon, device_lr=device_lr)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
+                    "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
+
+    class Nadam:
+        """Keras' Nadam: `decay` is the momentum-schedule decay (schedule_decay, default 0.004; `decay=` is taken as
+        its alias, the key its config is saved under), and the learning rate is never divided by 1 + decay*iterations.
+        A LearningRateSchedule is refused (ValueError), as in tf.keras 2.4; a rate set by a callback still reaches the
+        kernels through the device descriptor."""
+
+        def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="Nadam", lr=None,
+                     schedule_decay=0.004, decay=None, **kwargs):
+            _no_clipping("Nadam", kwargs)
+            self.lr = _rate(lr if lr is not None else learning_rate)
+            if isinstance(self.lr, lr_schedules.LearningRateSchedule):
+                raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the "
+                                 "learning rate.")
+            self.decay = float(schedule_decay if decay is None else decay)
+            self.beta_1, self.beta_2, self.epsilon, self.name = float(beta_1), float(beta_2), float(epsilon), name
+            self.spec()
+
+        def spec(self, device_lr=False):
+            return OptimizerSpec("nadam", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2,
+                                 epsilon=self.epsilon, device_lr=device_lr)
+
+        def get_config(self):
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
+                    "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
+
     @staticmethod
     def get(identifier):
         """compile(optimizer='sgd' | 'adam') -> the optimizer with Keras' defaults; an optimizer object is returned as is."""
-        if isinstance(identifier, (optimizers.SGD, optimizers.Adam)):
+        if isinstance(identifier, (optimizers.SGD, optimizers.Adam) + optimizers.KERAS_EXTRA):
             return identifier
         if isinstance(identifier, str):
             kinds = {"sgd": optimizers.SGD, "adam": optimizers.Adam}
             if identifier.lower() in kinds:
                 return kinds[identifier.lower()]()
-        raise ValueError(f"unsupported optimizer {identifier!r}: optimizers.SGD, optimizers.Adam, 'sgd' or 'adam'")
+        raise ValueError(f"unsupported optimizer {identifier!r}: an optimizer object (optimizers.SGD, Adam, RMSprop, "
+                         f"Adagrad, Adadelta, Adamax, Nadam) or the string 'sgd' or 'adam' -- pass the others as "
+                         f"objects, e.g. optimizers.RMSprop()")
+
+
+# the optimizers beyond SGD and Adam (csrc/optim_keras.hip), saved and loaded by their Keras class name
+optimizers.KERAS_EXTRA = (optimizers.RMSprop, optimizers.Adagrad, optimizers.Adadelta, optimizers.Adamax,
+                          optimizers.Nadam)
 
 
 class History:
@@ -391,6 +496,9 @@ class Model:
             self.net.slot(name)
         for t in self.net.slots().values():
             t.zero_()
+        if isinstance(optimizer, optimizers.Adagrad):
+            self.net.slot("accumulator").fill_(optimizer.initial_accumulator_value)
+        self.net.momentum_cache.fill_(1.0)
         self.net.iterations = 0
 
     @property
@@ -728,7 +836,7 @@ class Model:
     def save(self, path):
         """model.save(save_path) (model_training.py:302): a Keras-layout HDF5 file (model_config, model_weights/<layer>/
         <layer>/<weight>:0 with Keras' automatic layer names, training_config and the optimizer's iteration count + slots
-        -- SGD momentum accumulators, Adam moments -- under optimizer_weights), written by lisec_amd.hdf5_lite -- see
+        -- SGD momentum accumulators, Adam moments, ..., Nadam's momentum_cache -- under optimizer_weights), written by lisec_amd.hdf5_lite -- see
         lisec_amd/keras_h5.py.  A path ending in .npz gets a plain numpy archive with the names of
         lisec_amd.params.param_specs() instead."""
         p = self.net.params
@@ -766,6 +874,11 @@ class Model:
             if isinstance(o, optimizers.Adam):
                 opt = dict(class_name="Adam", lr=_serialize_rate(o.lr), decay=o.decay, beta_1=o.beta_1, beta_2=o.beta_2, epsilon=o.epsilon,
                            amsgrad=o.amsgrad)
+            elif isinstance(o, optimizers.KERAS_EXTRA):
+                opt = dict(class_name=type(o).__name__, lr=_serialize_rate(o.lr),
+                           **{k: v for k, v in o.get_config().items() if k not in ("name", "learning_rate")})
+                if isinstance(o, optimizers.Nadam):
+                    slots["momentum_cache"] = float(self.net.momentum_cache.item())
             else:
                 opt = dict(lr=_serialize_rate(o.lr), decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
             p = self.net.params
@@ -816,7 +929,7 @@ def createModel(nx, ny, nz, maxPoints):
 def load_model(path, custom_objects=None):
     """load_model(model_path, custom_objects={'RepeatLayer':…, 'MaxPoolingVFELayer':…}) (:337-338, Predict.py:51-52).
     Reads Keras HDF5 files (the reference's own checkpoints or Model.save's) and the .npz variant.  Like Keras, a file
-    that carries a training_config (SGD or Adam) comes back compiled, with the saved iteration count and optimizer slots;
+    that carries a training_config (SGD, Adam, RMSprop, Adagrad, Adadelta, Adamax or Nadam) comes back compiled, with the saved iteration count and optimizer slots;
     a learning-rate schedule in it is rebuilt, and continues from that iteration count.  The loss, loss_weights and metrics
     of the training_config are compiled again when compile() accepts them; otherwise the model is compiled with
     loss=['mse','mse'] and a warning names what could not be restored."""
@@ -838,9 +951,13 @@ def load_model(path, custom_objects=None):
         lr = o["lr"]
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
-        if o.get("class_name", "SGD") == "Adam":
+        cls = o.get("class_name", "SGD")
+        extra = {c.__name__: c for c in optimizers.KERAS_EXTRA}
+        if cls == "Adam":
             opt = optimizers.Adam(learning_rate=lr, decay=o["decay"], beta_1=o["beta_1"], beta_2=o["beta_2"],
                                   epsilon=o["epsilon"], amsgrad=o["amsgrad"])
+        elif cls in extra:
+            opt = extra[cls](learning_rate=lr, **{k: v for k, v in o.items() if k not in ("class_name", "lr")})
         else:
             opt = optimizers.SGD(lr=lr, decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
         _compile_saved(m, opt, ck)
@@ -854,6 +971,8 @@ def load_model(path, custom_objects=None):
             for n in p.trainable_names():
                 if n in saved:
                     p.view(n, buf=buf).copy_(torch.from_numpy(np.ascontiguousarray(saved[n])))
+        if cls == "Nadam" and ck.get("momentum_cache") is not None:
+            m.net.momentum_cache.fill_(float(ck["momentum_cache"]))
     return m
 
 

@@ -27,35 +27,69 @@ from .vfe import VFEStack
 
 
 class OptimizerSpec:
-    """One optimizer of the step: its kind ("sgd" | "adam"), the tf.keras 2.4 hyper-parameters and the names of the slots
-    it keeps -- per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
+    """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
+    per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
     SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295).
 
-        sgd    momentum == 0: no slot;  momentum > 0: "velocity" (v <- m*v - lr_t*g, then w <- w + v, or Nesterov)
-        adam   "m", "v", and "vhat" with amsgrad
+        sgd       momentum == 0: no slot;  momentum > 0: "velocity" (v <- m*v - lr_t*g, then w <- w + v, or Nesterov)
+        adam      "m", "v", and "vhat" with amsgrad
+        rmsprop   "rms"; "momentum" with momentum > 0 (a buffer of its own: not SGD's velocity); "mg" when centered
+        adagrad   "accumulator" (Model.compile starts it at initial_accumulator_value)
+        adadelta  "accum_grad", "accum_var"
+        adamax    "m", "v"
+        nadam     "m", "v", and LisecNet.momentum_cache (a device scalar next to the iteration count)
 
     lr is a number or a LearningRateSchedule (lisec_amd.lr_schedules).  With a schedule, or with device_lr=True (a
     number that may change between steps, e.g. from a LearningRateScheduler callback), the update kernels read lr_t from
     LisecNet's device descriptor (lisec_lr_schedule), which holds `lr_descriptor`; otherwise (lr, decay) are kernel
-    arguments, as they always were."""
+    arguments, as they always were.  Nadam's `decay` is its momentum-schedule decay (schedule_decay): its rate is not
+    divided by 1 + decay*it, its descriptor is built with decay = 0, and a schedule is refused as in tf.keras 2.4."""
+
+    KINDS = ("sgd", "adam", "rmsprop", "adagrad", "adadelta", "adamax", "nadam")
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, amsgrad=False, device_lr=False):
-        if kind not in ("sgd", "adam"):
+                 epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1):
+        if kind not in self.KINDS:
             raise ValueError(f"unknown optimizer kind {kind!r}")
         self.schedule = lr if isinstance(lr, lr_schedules.LearningRateSchedule) else None
+        if kind == "nadam" and self.schedule is not None:
+            raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the "
+                             "learning rate.")
         self.kind, self.lr, self.decay = kind, (lr if self.schedule is not None else float(lr)), float(decay)
         self.device_lr = bool(device_lr) or self.schedule is not None
         # validates a schedule: NotImplementedError for one of the user's own, ValueError past the device's limits
-        self.lr_descriptor = lr_schedules.descriptor(self.lr, self.decay) if self.device_lr else None
+        self.lr_descriptor = (lr_schedules.descriptor(self.lr, 0.0 if kind == "nadam" else self.decay)
+                              if self.device_lr else None)
         if kind == "sgd":
             self.momentum, self.nesterov = float(momentum), bool(nesterov)
             if self.momentum < 0:
                 raise ValueError("momentum must be >= 0")
-        else:
+        elif kind == "adam":
             self.beta_1, self.beta_2, self.epsilon, self.amsgrad = float(beta_1), float(beta_2), float(epsilon), bool(amsgrad)
             if not (0 <= self.beta_1 < 1 and 0 <= self.beta_2 < 1 and self.epsilon >= 0):
                 raise ValueError("beta_1 and beta_2 must lie in [0, 1), epsilon must be >= 0")
+        else:
+            self.epsilon = float(epsilon)
+            if self.epsilon < 0:
+                raise ValueError("epsilon must be >= 0")
+            if kind in ("rmsprop", "adadelta"):
+                self.rho = float(rho)
+                if not 0 <= self.rho < 1:
+                    raise ValueError("rho must lie in [0, 1)")
+            if kind == "rmsprop":
+                self.momentum, self.centered = float(momentum), bool(centered)
+                if self.momentum < 0:
+                    raise ValueError("momentum must be >= 0")
+            elif kind == "adagrad":
+                self.initial_accumulator_value = float(initial_accumulator_value)
+                if self.initial_accumulator_value < 0:
+                    raise ValueError("initial_accumulator_value must be >= 0")
+            elif kind in ("adamax", "nadam"):
+                self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
+                if not (0 <= self.beta_1 < 1 and 0 <= self.beta_2 < 1):
+                    raise ValueError("beta_1 and beta_2 must lie in [0, 1)")
+                if kind == "nadam" and self.decay < 0:
+                    raise ValueError("schedule_decay must be >= 0")
 
     @property
     def config(self):
@@ -70,13 +104,29 @@ class OptimizerSpec:
             rate = self.lr
         if self.kind == "sgd":
             return ("sgd", rate, self.decay, self.momentum, self.nesterov)
-        return ("adam", rate, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
+        if self.kind == "adam":
+            return ("adam", rate, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
+        if self.kind == "rmsprop":
+            return ("rmsprop", rate, self.decay, self.rho, self.momentum, self.epsilon, self.centered)
+        if self.kind == "adagrad":
+            return ("adagrad", rate, self.decay, self.initial_accumulator_value, self.epsilon)
+        if self.kind == "adadelta":
+            return ("adadelta", rate, self.decay, self.rho, self.epsilon)
+        return (self.kind, rate, self.decay, self.beta_1, self.beta_2, self.epsilon)        # adamax, nadam
 
     @property
     def slots(self):
         if self.kind == "sgd":
             return ("velocity",) if self.momentum > 0 else ()
-        return ("m", "v", "vhat") if self.amsgrad else ("m", "v")
+        if self.kind == "adam":
+            return ("m", "v", "vhat") if self.amsgrad else ("m", "v")
+        if self.kind == "rmsprop":
+            return ("rms",) + (("momentum",) if self.momentum > 0 else ()) + (("mg",) if self.centered else ())
+        if self.kind == "adagrad":
+            return ("accumulator",)
+        if self.kind == "adadelta":
+            return ("accum_grad", "accum_var")
+        return ("m", "v")                                                                   # adamax, nadam
 
     def __eq__(self, other):
         return isinstance(other, OptimizerSpec) and self.config == other.config
@@ -279,6 +329,9 @@ class LisecNet:
         # that a captured step can be replayed; the host mirror is what save()/load_model() and the tests read
         self._iter_dev = torch.zeros(2, dtype=torch.int64, device=dev)
         self._iterations = 0
+        # Nadam's momentum_cache (the product of its momentum schedule so far; 1 before the first step), next to the
+        # iteration count: the Nadam kernels read it and the call that ends a step writes the step's product back
+        self.momentum_cache = torch.ones(1, dtype=torch.float32, device=dev)
         # learning-rate descriptor (lisec_lr_schedule) of the OptimizerSpecs with device_lr, at a fixed address like the
         # iteration count; _sync_lr rewrites it, stream-ordered, when a step needs other contents
         self._lr_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
@@ -1089,16 +1142,19 @@ class LisecNet:
         return self.loss_out
 
     def slot(self, name):
-        """The optimizer slot `name` ("velocity", "m", "v", "vhat"; see OptimizerSpec): a buffer shaped like theta, zero when
-        first asked for, at a fixed address from then on (recorded step plans point at it)."""
+        """The optimizer slot `name` ("velocity", "m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad",
+        "accum_var"; see OptimizerSpec): a buffer shaped like theta, zero when first asked for, at a fixed address from
+        then on (recorded step plans point at it)."""
         self._prepare_training()
         t = self._slots.get(name)
         if t is None:
-            if name not in ("m", "v", "vhat"):
+            if name not in self.SLOT_NAMES:
                 raise KeyError(f"unknown optimizer slot {name!r}")
             t = self._slots[name] = torch.zeros_like(self.params.theta)
             torch.cuda.synchronize(self.device)   # zero before any stream of the step (the second one included) uses it
         return t
+
+    SLOT_NAMES = ("m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad", "accum_var")
 
     def slots(self):
         """Every slot made so far, by name (the SGD velocity always among them)."""
@@ -1120,7 +1176,9 @@ class LisecNet:
         """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step)."""
         th, g = self.params.theta[lo:hi], self.grad[lo:hi]
         sl = [self.slot(name)[lo:hi] for name in opt.slots]
-        if opt.device_lr:
+        if opt.kind not in ("sgd", "adam"):
+            self._update_keras(opt, th, g, sl, advance)
+        elif opt.device_lr:
             # lr_t from the descriptor (a schedule, or a rate a callback may change): the *_sched entries
             self._sync_lr(opt)
             if opt.kind == "adam":
@@ -1138,6 +1196,43 @@ class LisecNet:
         else:
             ops.sgd_step_dev(th, g, sl[0] if sl else None, opt.lr, opt.decay, opt.momentum, opt.nesterov, self._iter_dev,
                              advance=advance)
+
+    def _update_keras(self, opt, th, g, sl, advance):
+        """_update for the optimizers of csrc/optim_keras.hip: lr_t by value, or with device_lr from the descriptor."""
+        desc = self._lr_dev if opt.device_lr else None
+        if desc is not None:
+            self._sync_lr(opt)
+        st, k = self._iter_dev, opt.kind
+        if k == "rmsprop":
+            mom = sl[1] if opt.momentum > 0 else None
+            mg = sl[-1] if opt.centered else None
+            if desc is None:
+                ops.rmsprop_step_dev(th, g, sl[0], mom, mg, opt.lr, opt.decay, opt.rho, opt.momentum, opt.epsilon, st,
+                                     advance=advance)
+            else:
+                ops.rmsprop_step_sched(th, g, sl[0], mom, mg, desc, opt.rho, opt.momentum, opt.epsilon, st, advance=advance)
+        elif k == "adagrad":
+            if desc is None:
+                ops.adagrad_step_dev(th, g, sl[0], opt.lr, opt.decay, opt.epsilon, st, advance=advance)
+            else:
+                ops.adagrad_step_sched(th, g, sl[0], desc, opt.epsilon, st, advance=advance)
+        elif k == "adadelta":
+            if desc is None:
+                ops.adadelta_step_dev(th, g, sl[0], sl[1], opt.lr, opt.decay, opt.rho, opt.epsilon, st, advance=advance)
+            else:
+                ops.adadelta_step_sched(th, g, sl[0], sl[1], desc, opt.rho, opt.epsilon, st, advance=advance)
+        elif k == "adamax":
+            if desc is None:
+                ops.adamax_step_dev(th, g, sl[0], sl[1], opt.lr, opt.decay, opt.beta_1, opt.beta_2, opt.epsilon, st,
+                                    advance=advance)
+            else:
+                ops.adamax_step_sched(th, g, sl[0], sl[1], desc, opt.beta_1, opt.beta_2, opt.epsilon, st, advance=advance)
+        elif desc is None:                                                 # nadam: opt.decay is its schedule_decay
+            ops.nadam_step_dev(th, g, sl[0], sl[1], self.momentum_cache, opt.lr, opt.beta_1, opt.beta_2, opt.epsilon,
+                               opt.decay, st, advance=advance)
+        else:
+            ops.nadam_step_sched(th, g, sl[0], sl[1], self.momentum_cache, desc, opt.beta_1, opt.beta_2, opt.epsilon,
+                                 opt.decay, st, advance=advance)
 
     def early_update(self, lo, hi, opt=None):
         """`opt` (an OptimizerSpec; None: the reference's SGD-Nesterov) of theta[lo:hi] AHEAD of the rest of the step
@@ -1292,10 +1387,11 @@ class _StepPlans:
         self.alloc_gen = _lib.alloc_generation()
 
     def _snapshot(self):
-        """The variables, BN state, every optimizer slot and the iteration count, before the warm-up / recording steps."""
+        """The variables, BN state, every optimizer slot, the iteration count and Nadam's momentum_cache, before the
+        warm-up / recording steps."""
         net, p = self.net, self.net.params
         return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
-                net._iterations)
+                net._iterations, net.momentum_cache.clone())
 
     def _restore(self, keep):
         net, p = self.net, self.net.params
@@ -1305,6 +1401,7 @@ class _StepPlans:
             net.slot(k).copy_(t)
         net._iter_dev.copy_(keep[3])
         net._iterations = keep[4]
+        net.momentum_cache.copy_(keep[5])
 
     def _voxelise(self, j):
         """The voxelisation of buffer set j's step: issued here, or returned as the side_filler of its backward pass."""

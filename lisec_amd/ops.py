@@ -456,6 +456,83 @@ def adam_step_sched(theta, grad, m, v, vhat, dev_desc, beta_1, beta_2, epsilon, 
                                                  _lib.current_stream()))
 
 
+# ---- the other tf.keras optimizers (csrc/optim_keras.hip): *_dev take (lr, decay), *_sched the device descriptor -------
+def rmsprop_step_dev(theta, grad, rms, mom, mg, lr, decay, rho, momentum, epsilon, state, advance=True):
+    """tf.keras RMSprop (lisec_rmsprop_step_dev): mom is None exactly when momentum == 0, mg exactly when not centered."""
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_rmsprop_step_dev(P(theta), P(grad), P(rms), P(mom), P(mg), theta.numel(), float(lr),
+                                                  float(decay), float(rho), float(momentum), float(epsilon),
+                                                  0 if mg is None else 1, P(state), 1 if advance else 0,
+                                                  _lib.current_stream()))
+
+
+def rmsprop_step_sched(theta, grad, rms, mom, mg, dev_desc, rho, momentum, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_rmsprop_step_sched(P(theta), P(grad), P(rms), P(mom), P(mg), theta.numel(), P(dev_desc),
+                                                    float(rho), float(momentum), float(epsilon), 0 if mg is None else 1,
+                                                    P(state), 1 if advance else 0, _lib.current_stream()))
+
+
+def adagrad_step_dev(theta, grad, accumulator, lr, decay, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adagrad_step_dev(P(theta), P(grad), P(accumulator), theta.numel(), float(lr),
+                                                  float(decay), float(epsilon), P(state), 1 if advance else 0,
+                                                  _lib.current_stream()))
+
+
+def adagrad_step_sched(theta, grad, accumulator, dev_desc, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adagrad_step_sched(P(theta), P(grad), P(accumulator), theta.numel(), P(dev_desc),
+                                                    float(epsilon), P(state), 1 if advance else 0, _lib.current_stream()))
+
+
+def adadelta_step_dev(theta, grad, accum_grad, accum_var, lr, decay, rho, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adadelta_step_dev(P(theta), P(grad), P(accum_grad), P(accum_var), theta.numel(),
+                                                   float(lr), float(decay), float(rho), float(epsilon), P(state),
+                                                   1 if advance else 0, _lib.current_stream()))
+
+
+def adadelta_step_sched(theta, grad, accum_grad, accum_var, dev_desc, rho, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adadelta_step_sched(P(theta), P(grad), P(accum_grad), P(accum_var), theta.numel(),
+                                                     P(dev_desc), float(rho), float(epsilon), P(state),
+                                                     1 if advance else 0, _lib.current_stream()))
+
+
+def adamax_step_dev(theta, grad, m, v, lr, decay, beta_1, beta_2, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adamax_step_dev(P(theta), P(grad), P(m), P(v), theta.numel(), float(lr), float(decay),
+                                                 float(beta_1), float(beta_2), float(epsilon), P(state),
+                                                 1 if advance else 0, _lib.current_stream()))
+
+
+def adamax_step_sched(theta, grad, m, v, dev_desc, beta_1, beta_2, epsilon, state, advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_adamax_step_sched(P(theta), P(grad), P(m), P(v), theta.numel(), P(dev_desc),
+                                                   float(beta_1), float(beta_2), float(epsilon), P(state),
+                                                   1 if advance else 0, _lib.current_stream()))
+
+
+def nadam_step_dev(theta, grad, m, v, momentum_cache, lr, beta_1, beta_2, epsilon, schedule_decay, state, advance=True):
+    """tf.keras Nadam (lisec_nadam_step_dev): momentum_cache is a float32 device scalar, advanced with the iteration
+    count; lr is not decayed."""
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_nadam_step_dev(P(theta), P(grad), P(m), P(v), P(momentum_cache), theta.numel(),
+                                                float(lr), float(beta_1), float(beta_2), float(epsilon),
+                                                float(schedule_decay), P(state), 1 if advance else 0,
+                                                _lib.current_stream()))
+
+
+def nadam_step_sched(theta, grad, m, v, momentum_cache, dev_desc, beta_1, beta_2, epsilon, schedule_decay, state,
+                     advance=True):
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_nadam_step_sched(P(theta), P(grad), P(m), P(v), P(momentum_cache), theta.numel(),
+                                                  P(dev_desc), float(beta_1), float(beta_2), float(epsilon),
+                                                  float(schedule_decay), P(state), 1 if advance else 0,
+                                                  _lib.current_stream()))
+
+
 def fold_depth(x, out, D, HW, C, inverse=False, mask=None):
     """(D,H,W,C) <-> (H,W,C*D) (Permute + Reshape of model_training.py:242-243); inverse: gradient, ReLU-gated by mask."""
     _lib.check(_lib.load().lisec_fold_depth(_lib.ptr(x), _lib.ptr(out), D, HW, C, 1 if inverse else 0, _lib.ptr(mask),

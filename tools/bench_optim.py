@@ -1,5 +1,6 @@
 """Cost of the optimizers (GPU box only): Model.fit(batch_size=1) ms/step on the U20k sweeps of bench.py for
-SGD-Nesterov (the reference's), SGD with plain momentum, Adam and AMSGrad, alternated over rounds so that drift shows
+SGD-Nesterov (the reference's), SGD with plain momentum, Adam, AMSGrad, RMSprop (plain and centered with momentum),
+Adagrad, Adadelta, Adamax and Nadam, alternated over rounds so that drift shows
 as spread; then the update kernels alone over the model's 6.49 M variables (device-event timing, us and GB/s of the
 bytes each update must move)."""
 import os
@@ -18,9 +19,16 @@ CONFIGS = {
     "sgd_momentum": lambda: mt.optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=False),
     "adam": lambda: mt.optimizers.Adam(learning_rate=1e-3, decay=1e-6),
     "amsgrad": lambda: mt.optimizers.Adam(learning_rate=1e-3, decay=1e-6, amsgrad=True),
+    "rmsprop": lambda: mt.optimizers.RMSprop(learning_rate=1e-3, decay=1e-6),
+    "rmsprop_cm": lambda: mt.optimizers.RMSprop(learning_rate=1e-3, decay=1e-6, momentum=0.9, centered=True),
+    "adagrad": lambda: mt.optimizers.Adagrad(learning_rate=1e-2, decay=1e-6),
+    "adadelta": lambda: mt.optimizers.Adadelta(learning_rate=1.0, decay=1e-6),
+    "adamax": lambda: mt.optimizers.Adamax(learning_rate=2e-3, decay=1e-6),
+    "nadam": lambda: mt.optimizers.Nadam(learning_rate=2e-3),
 }
 # fp32 arrays each update reads + writes: theta r/w, grad r, and every slot r/w
-STREAMS = {"sgd_nesterov": 5, "sgd_momentum": 5, "sgd": 3, "adam": 7, "amsgrad": 9}
+STREAMS = {"sgd_nesterov": 5, "sgd_momentum": 5, "sgd": 3, "adam": 7, "amsgrad": 9, "rmsprop": 5, "rmsprop_c": 7,
+           "rmsprop_m": 7, "rmsprop_cm": 9, "adagrad": 5, "adadelta": 7, "adamax": 7, "nadam": 7}
 
 
 def fit_times(rounds=3, steps=200):
@@ -52,12 +60,22 @@ def kernel_times(n, reps=200):
     theta = torch.randn(n, device=dev)
     slots = [torch.zeros(n, device=dev) for _ in range(3)]
     state = torch.zeros(2, dtype=torch.int64, device=dev)
+    cache = torch.ones(1, device=dev)
+    s0, s1, s2 = slots
     runs = {
         "sgd_nesterov": lambda: ops.sgd_nesterov_step_dev(theta, g, slots[0], 0.01, 1e-6, 0.9, state),
         "sgd_momentum": lambda: ops.sgd_step_dev(theta, g, slots[0], 0.01, 1e-6, 0.9, False, state),
         "sgd": lambda: ops.sgd_step_dev(theta, g, None, 0.01, 1e-6, 0.0, False, state),
         "adam": lambda: ops.adam_step_dev(theta, g, slots[0], slots[1], None, 1e-3, 1e-6, 0.9, 0.999, 1e-7, state),
         "amsgrad": lambda: ops.adam_step_dev(theta, g, slots[0], slots[1], slots[2], 1e-3, 1e-6, 0.9, 0.999, 1e-7, state),
+        "rmsprop": lambda: ops.rmsprop_step_dev(theta, g, s0, None, None, 1e-3, 1e-6, 0.9, 0.0, 1e-7, state),
+        "rmsprop_c": lambda: ops.rmsprop_step_dev(theta, g, s0, None, s2, 1e-3, 1e-6, 0.9, 0.0, 1e-7, state),
+        "rmsprop_m": lambda: ops.rmsprop_step_dev(theta, g, s0, s1, None, 1e-3, 1e-6, 0.9, 0.9, 1e-7, state),
+        "rmsprop_cm": lambda: ops.rmsprop_step_dev(theta, g, s0, s1, s2, 1e-3, 1e-6, 0.9, 0.9, 1e-7, state),
+        "adagrad": lambda: ops.adagrad_step_dev(theta, g, s0, 1e-2, 1e-6, 1e-7, state),
+        "adadelta": lambda: ops.adadelta_step_dev(theta, g, s0, s1, 1.0, 1e-6, 0.95, 1e-7, state),
+        "adamax": lambda: ops.adamax_step_dev(theta, g, s0, s1, 2e-3, 1e-6, 0.9, 0.999, 1e-7, state),
+        "nadam": lambda: ops.nadam_step_dev(theta, g, s0, s1, cache, 2e-3, 0.9, 0.999, 1e-7, 0.004, state),
     }
     out = {}
     for name, fn in runs.items():
