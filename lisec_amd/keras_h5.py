@@ -10,7 +10,7 @@ Predict.py:51-52).  A Keras `.h5` holds
     /optimizer_weights  attr weight_names = [b'SGD/iter:0', b'SGD/<layer>/<weight>/momentum:0', ...] + datasets
                         (Adam: b'Adam/iter:0', every .../m:0, every .../v:0, every .../vhat:0 with amsgrad;
                         RMSprop, Adagrad, Adadelta, Adamax, Nadam: b'<Class>/iter:0', Nadam's
-                        b'Nadam/momentum_cache:0', then their slots kind by kind, as _slot_kinds lists them)
+                        b'Nadam/momentum_cache:0', then their slots kind by kind, in the order of optimizer_table)
 
 This module rebuilds the layer list that createModel (model_training.py:222-257) produces -- with the names Keras
 assigns automatically (dense, dense_1, batch_normalization_7, conv2d_transpose_2 ...) and the order of
@@ -25,7 +25,7 @@ import re
 
 import numpy as np
 
-from . import hdf5_lite
+from . import hdf5_lite, optimizer_table
 from .params import DECONVS, MID, RPN_BLOCKS
 
 KERAS_VERSION = "2.4.0"
@@ -214,73 +214,27 @@ def _serialize_nested(x):
     return x
 
 
-# Keras' config keys (after name, learning_rate and decay) and defaults of the optimizers beyond SGD and Adam, in
-# Keras' order; Nadam's `decay` is its schedule_decay
-KERAS_EXTRA = {
-    "RMSprop": (("rho", 0.9), ("momentum", 0.0), ("epsilon", 1e-7), ("centered", False)),
-    "Adagrad": (("initial_accumulator_value", 0.1), ("epsilon", 1e-7)),
-    "Adadelta": (("rho", 0.95), ("epsilon", 1e-7)),
-    "Adamax": (("beta_1", 0.9), ("beta_2", 0.999), ("epsilon", 1e-7)),
-    "Nadam": (("beta_1", 0.9), ("beta_2", 0.999), ("epsilon", 1e-7)),
-}
-
-
-def _default_decay(cls):
-    return 0.004 if cls == "Nadam" else 0.0
-
-
 def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
     """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
-    loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote)."""
+    loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote).  optimizer_config holds Keras'
+    keys in Keras' order, a key the dict lacks at Keras' default (optimizer_table)."""
     o = optimizer or {}
-    cls = o.get("class_name", "SGD")
-    if cls in KERAS_EXTRA:
-        oc = {"class_name": cls, "config": {
-            "name": cls, "learning_rate": _rate(o.get("lr", 0.001)), "decay": float(o.get("decay", _default_decay(cls))),
-            **{k: type(d)(o.get(k, d)) for k, d in KERAS_EXTRA[cls]}}}
-    elif cls == "Adam":
-        oc = {"class_name": "Adam", "config": {
-            "name": "Adam", "learning_rate": _rate(o.get("lr", 0.001)), "decay": float(o.get("decay", 0.0)),
-            "beta_1": float(o.get("beta_1", 0.9)), "beta_2": float(o.get("beta_2", 0.999)),
-            "epsilon": float(o.get("epsilon", 1e-7)), "amsgrad": bool(o.get("amsgrad", False))}}
-    else:
-        oc = {"class_name": "SGD", "config": {
-            "name": "SGD", "learning_rate": _rate(o.get("lr", 0.01)), "decay": float(o.get("decay", 0.0)),
-            "momentum": float(o.get("momentum", 0.0)), "nesterov": bool(o.get("nesterov", False))}}
+    rec = optimizer_table.record_of(o)
+    oc = {"class_name": rec.class_name, "config": {
+        "name": rec.class_name, "learning_rate": _rate(o.get("lr", rec.lr)), "decay": float(o.get("decay", rec.decay)),
+        **rec.values(o)}}
     return {"loss": ["mse", "mse"] if loss is None else _serialize_nested(loss), "metrics": _serialize_nested(metrics),
             "weighted_metrics": None, "loss_weights": _serialize_nested(loss_weights), "optimizer_config": oc}
 
 
-def _slot_kinds(optimizer):
-    """(class name, slot kinds in Keras' order): the slots of one kind are written for every variable before the next kind."""
-    cls = optimizer.get("class_name", "SGD")
-    if cls == "Adam":
-        return "Adam", (("m", "v", "vhat") if optimizer.get("amsgrad") else ("m", "v"))
-    if cls == "RMSprop":
-        return cls, (("rms",) + (("momentum",) if float(optimizer.get("momentum", 0.0)) > 0 else ()) +
-                     (("mg",) if optimizer.get("centered") else ()))
-    if cls == "Adagrad":
-        return cls, ("accumulator",)
-    if cls == "Adadelta":
-        return cls, ("accum_grad", "accum_var")
-    if cls in ("Adamax", "Nadam"):
-        return cls, ("m", "v")
-    return "SGD", (("momentum",) if float(optimizer.get("momentum", 0.0)) > 0 else ())
-
-
-def _slot_key(cls, kind):
-    """The save_model / load_model key of the Keras slot `kind` of class `cls`: SGD's "momentum" is its velocity,
-    RMSprop's a buffer of its own."""
-    return "velocity" if cls == "SGD" and kind == "momentum" else kind
-
-
-SLOT_KEYS = ("velocity", "m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad", "accum_var")
+# the slot arguments of save_model and slot keys of load_model: LisecNet's slot names, so Keras' "momentum" is "velocity"
+# in an SGD file and "momentum", a buffer of its own, in an RMSprop file
+SLOT_KEYS = optimizer_table.SLOT_NAMES
 
 
 # ---------------------------------------------------------------------------------------------------
-def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, velocity=None, m=None, v=None,
-               vhat=None, loss=None, loss_weights=None, metrics=None, rms=None, momentum=None, mg=None, accumulator=None,
-               accum_grad=None, accum_var=None, momentum_cache=1.0):
+def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, loss=None, loss_weights=None,
+               metrics=None, momentum_cache=1.0, **given):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
@@ -290,7 +244,11 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
     m and v of Adamax and Nadam.  Other optimizers: dict(class_name=<Keras class>, lr, decay, <their config keys>)
     (Nadam's decay: schedule_decay); momentum_cache: Nadam's scalar.  optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
     loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
-    as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics."""
+    as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics.
+    **given: the slots, by the names of SLOT_KEYS (any other keyword: TypeError)."""
+    for k in given:
+        if k not in SLOT_KEYS:
+            raise TypeError(f"save_model() got an unexpected keyword argument {k!r}")
     layers, _ = keras_layers(nx, ny, nz, maxPoints)
     with hdf5_lite.File(path, "w") as f:
         f.attrs["keras_version"] = KERAS_VERSION.encode()
@@ -314,18 +272,18 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
                     slots.append((f"{L['name']}/{w}", pname))
         if optimizer is None:
             return
-        cls, kinds = _slot_kinds(optimizer)
-        given = dict(velocity=velocity, m=m, v=v, vhat=vhat, rms=rms, momentum=momentum, mg=mg, accumulator=accumulator,
-                     accum_grad=accum_grad, accum_var=accum_var)
-        if any(given[_slot_key(cls, k)] is None for k in kinds):
+        rec = optimizer_table.record_of(optimizer)
+        cls, kept = rec.class_name, rec.active_slots(rec.values(optimizer))
+        if any(given.get(s.name) is None for s in kept):
             return
-        entries = [(f"{cls}/{var}/{k}:0", given[_slot_key(cls, k)][pname]) for k in kinds for var, pname in slots]
-        head = [f"{cls}/iter:0"] + (["Nadam/momentum_cache:0"] if cls == "Nadam" else [])
+        # Keras' order: iter, the optimizer's own scalar, then one slot kind for every variable before the next kind
+        entries = [(f"{cls}/{var}/{s.kind}:0", given[s.name][pname]) for s in kept for var, pname in slots]
+        head = [f"{cls}/iter:0"] + ([f"{cls}/{rec.scalar}:0"] if rec.scalar else [])
         og = f.create_group("optimizer_weights")
         og.attrs["weight_names"] = [n.encode() for n in head] + [n.encode("utf8") for n, _ in entries]
         og.create_dataset(f"{cls}/iter:0", data=np.array(int(iterations), dtype=np.int64))
-        if cls == "Nadam":
-            og.create_dataset("Nadam/momentum_cache:0", data=np.array(momentum_cache, dtype=np.float32))
+        if rec.scalar:
+            og.create_dataset(f"{cls}/{rec.scalar}:0", data=np.array(momentum_cache, dtype=np.float32))
         for n, a in entries:
             og.create_dataset(n, data=np.asarray(a, dtype=np.float32))
 
@@ -420,21 +378,13 @@ def load_model(path, grid=None):
             out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))
             oc = tc.get("optimizer_config", {})
             c = oc.get("config", {})
-            if oc.get("class_name") == "SGD":
-                out["optimizer"] = dict(lr=c.get("learning_rate", c.get("lr", 0.01)), decay=c.get("decay", 0.0),
-                                        momentum=c.get("momentum", 0.0), nesterov=c.get("nesterov", False))
-            elif oc.get("class_name") in KERAS_EXTRA:
-                cls = oc["class_name"]
-                out["optimizer"] = dict(class_name=cls, lr=c.get("learning_rate", c.get("lr", 0.001)),
-                                        decay=c.get("decay", _default_decay(cls)),
-                                        **{k: c.get(k, d) for k, d in KERAS_EXTRA[cls]})
-            elif oc.get("class_name") == "Adam":
-                out["optimizer"] = dict(class_name="Adam", lr=c.get("learning_rate", c.get("lr", 0.001)),
-                                        decay=c.get("decay", 0.0), beta_1=c.get("beta_1", 0.9),
-                                        beta_2=c.get("beta_2", 0.999), epsilon=c.get("epsilon", 1e-7),
-                                        amsgrad=c.get("amsgrad", False))
+            rec = optimizer_table.BY_CLASS.get(oc.get("class_name"))
+            if rec is not None:               # another optimizer class: no optimizer, the model comes back uncompiled
+                out["optimizer"] = rec.as_dict(c.get("learning_rate", c.get("lr", rec.lr)), c.get("decay", rec.decay),
+                                               {h.name: c.get(h.name, h.default) for h in rec.hyper})
         if "optimizer_weights" in f:
             og = f["optimizer_weights"]
+            slot_dataset = re.compile(r"([^/]+)/(.+)/(%s):0" % "|".join(optimizer_table.SLOT_KINDS))
             found_slots = {}
             for w in _attr_list(og, "weight_names"):
                 a = og[w][()]
@@ -444,9 +394,9 @@ def load_model(path, grid=None):
                 if w.endswith("/momentum_cache:0"):
                     out["momentum_cache"] = float(np.float32(a))
                     continue
-                m = re.fullmatch(r"([^/]+)/(.+)/(momentum|m|v|vhat|rms|mg|accumulator|accum_grad|accum_var):0", w)
+                m = slot_dataset.fullmatch(w)
                 if m and m.group(2) in keras_to_param:
-                    kind = _slot_key(m.group(1), m.group(3))
+                    kind = optimizer_table.slot_name(m.group(1), m.group(3))
                     found_slots.setdefault(kind, {})[keras_to_param[m.group(2)]] = np.asarray(a, dtype=np.float32)
             out.update(found_slots)
         return out

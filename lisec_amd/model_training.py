@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, losses, lr_schedules, metrics, ops
+from . import callbacks, losses, lr_schedules, metrics, ops, optimizer_table
 from .network import LisecNet, LossSpec, OptimizerSpec
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
@@ -249,123 +249,94 @@ def _serialize_rate(lr):
     return lr_schedules.serialize(lr) if isinstance(lr, lr_schedules.LearningRateSchedule) else lr
 
 
+class _Optimizer:
+    """What the optimizers share: the attributes (lr, decay, name and the hyper-parameters of the class's record in
+    lisec_amd/optimizer_table.py), spec() and get_config().  lr stays a plain attribute -- callbacks assign it between
+    epochs -- that spec() reads when it is called."""
+
+    @property
+    def record(self):
+        return optimizer_table.BY_CLASS[type(self).__name__]
+
+    def _set(self, name, lr, decay, kwargs, **hyper):
+        _no_clipping(type(self).__name__, kwargs)
+        self.lr = _rate(lr)
+        self.decay, self.name = float(decay), name
+        for h in self.record.hyper:
+            setattr(self, h.name, h.coerce(hyper[h.name]))
+        self.spec()                 # range checks; a schedule the kernels cannot evaluate (or Nadam any) is refused here
+
+    @property
+    def hyper(self):
+        """{name: value} of the hyper-parameters after the rate and decay, in the order of Keras' get_config()."""
+        return {h.name: getattr(self, h.name) for h in self.record.hyper}
+
+    def spec(self, device_lr=False):
+        """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
+        callbacks, which may change it between epochs)."""
+        return OptimizerSpec(self.record.kind, self.lr, self.decay, device_lr=device_lr, **self.hyper)
+
+    def get_config(self):
+        return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper}
+
+
+def _momentum_in_unit_interval(momentum):
+    """Keras' own check of SGD and RMSprop (OptimizerSpec only asks for momentum >= 0)."""
+    if not 0.0 <= float(momentum) <= 1.0:
+        raise ValueError("`momentum` must be between [0, 1].")
+
+
 class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimizers`)
     """tf.keras 2.4 SGD, Adam, RMSprop, Adagrad, Adadelta, Adamax and Nadam (OptimizerV2): lr_t = lr / (1 +
     decay*iterations) (Nadam: lr), lr either a number or one of the built-in schedules of optimizers.schedules (then
     lr_t = schedule(iterations) / (1 + decay*iterations); not for Nadam); `lr=` is the legacy spelling of
     `learning_rate=`.  The updates run as HIP kernels on the flat variables (csrc/eltwise.hip, csrc/optim.hip,
-    csrc/optim_keras.hip)."""
+    csrc/optim_keras.hip).  The signatures mirror Keras'; everything else about an optimizer is its record in
+    lisec_amd/optimizer_table.py."""
 
     schedules = lr_schedules
 
-    class SGD:
+    class SGD(_Optimizer):
         def __init__(self, lr=0.01, decay=0.0, momentum=0.0, nesterov=False, learning_rate=None, name="SGD", **kwargs):
-            _no_clipping("SGD", kwargs)
-            self.lr = _rate(learning_rate if learning_rate is not None else lr)
-            self.decay, self.momentum, self.nesterov, self.name = float(decay), float(momentum), bool(nesterov), name
-            if not 0.0 <= self.momentum <= 1.0:
-                raise ValueError("`momentum` must be between [0, 1].")
-            self.spec()                                      # a schedule the kernels cannot evaluate is refused here
+            _momentum_in_unit_interval(momentum)
+            self._set(name, learning_rate if learning_rate is not None else lr, decay, kwargs, momentum=momentum,
+                      nesterov=nesterov)
 
-        def spec(self, device_lr=False):
-            """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
-            callbacks, which may change it between epochs)."""
-            return OptimizerSpec("sgd", self.lr, self.decay, self.momentum, self.nesterov, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
-                    "momentum": self.momentum, "nesterov": self.nesterov}
-
-    class Adam:
+    class Adam(_Optimizer):
         def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False, name="Adam",
                      lr=None, decay=0.0, **kwargs):
-            _no_clipping("Adam", kwargs)
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            self.decay, self.beta_1, self.beta_2 = float(decay), float(beta_1), float(beta_2)
-            self.epsilon, self.amsgrad, self.name = float(epsilon), bool(amsgrad), name
-            self.spec()                                      # range checks
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs, beta_1=beta_1, beta_2=beta_2,
+                      epsilon=epsilon, amsgrad=amsgrad)
 
-        def spec(self, device_lr=False):
-            return OptimizerSpec("adam", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon,
-                                 amsgrad=self.amsgrad, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "beta_1": self.beta_1,
-                    "beta_2": self.beta_2, "epsilon": self.epsilon, "amsgrad": self.amsgrad}
-
-    class RMSprop:
+    class RMSprop(_Optimizer):
         """Keras' RMSprop: momentum == 0 takes TF's Python path (epsilon outside the square root), momentum > 0
         ResourceApplyRMSProp / ResourceApplyCenteredRMSProp (epsilon inside it) -- see include/lisec_hip.h."""
 
         def __init__(self, learning_rate=0.001, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False, name="RMSprop",
                      lr=None, decay=0.0, **kwargs):
-            _no_clipping("RMSprop", kwargs)
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            self.decay, self.rho, self.momentum = float(decay), float(rho), float(momentum)
-            self.epsilon, self.centered, self.name = float(epsilon), bool(centered), name
-            if not 0.0 <= self.momentum <= 1.0:
-                raise ValueError("`momentum` must be between [0, 1].")
-            self.spec()                                      # range checks; a schedule the kernels cannot evaluate
+            _momentum_in_unit_interval(momentum)
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs, rho=rho, momentum=momentum,
+                      epsilon=epsilon, centered=centered)
 
-        def spec(self, device_lr=False):
-            return OptimizerSpec("rmsprop", self.lr, self.decay, momentum=self.momentum, rho=self.rho,
-                                 epsilon=self.epsilon, centered=self.centered, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "rho": self.rho,
-                    "momentum": self.momentum, "epsilon": self.epsilon, "centered": self.centered}
-
-    class Adagrad:
+    class Adagrad(_Optimizer):
         def __init__(self, learning_rate=0.001, initial_accumulator_value=0.1, epsilon=1e-7, name="Adagrad", lr=None,
                      decay=0.0, **kwargs):
-            _no_clipping("Adagrad", kwargs)
             if initial_accumulator_value < 0.0:
                 raise ValueError(f"initial_accumulator_value must be non-negative: {initial_accumulator_value}")
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            self.decay, self.initial_accumulator_value = float(decay), float(initial_accumulator_value)
-            self.epsilon, self.name = float(epsilon), name
-            self.spec()
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs,
+                      initial_accumulator_value=initial_accumulator_value, epsilon=epsilon)
 
-        def spec(self, device_lr=False):
-            return OptimizerSpec("adagrad", self.lr, self.decay, epsilon=self.epsilon,
-                                 initial_accumulator_value=self.initial_accumulator_value, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
-                    "initial_accumulator_value": self.initial_accumulator_value, "epsilon": self.epsilon}
-
-    class Adadelta:
+    class Adadelta(_Optimizer):
         def __init__(self, learning_rate=0.001, rho=0.95, epsilon=1e-7, name="Adadelta", lr=None, decay=0.0, **kwargs):
-            _no_clipping("Adadelta", kwargs)
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            self.decay, self.rho, self.epsilon, self.name = float(decay), float(rho), float(epsilon), name
-            self.spec()
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs, rho=rho, epsilon=epsilon)
 
-        def spec(self, device_lr=False):
-            return OptimizerSpec("adadelta", self.lr, self.decay, rho=self.rho, epsilon=self.epsilon, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, "rho": self.rho,
-                    "epsilon": self.epsilon}
-
-    class Adamax:
+    class Adamax(_Optimizer):
         def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="Adamax", lr=None,
                      decay=0.0, **kwargs):
-            _no_clipping("Adamax", kwargs)
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            self.decay, self.beta_1, self.beta_2 = float(decay), float(beta_1), float(beta_2)
-            self.epsilon, self.name = float(epsilon), name
-            self.spec()
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs, beta_1=beta_1, beta_2=beta_2,
+                      epsilon=epsilon)
 
-        def spec(self, device_lr=False):
-            return OptimizerSpec("adamax", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2,
-                                 epsilon=self.epsilon, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
-                    "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
-
-    class Nadam:
+    class Nadam(_Optimizer):
         """Keras' Nadam: `decay` is the momentum-schedule decay (schedule_decay, default 0.004; `decay=` is taken as
         its alias, the key its config is saved under), and the learning rate is never divided by 1 + decay*iterations.
         A LearningRateSchedule is refused (ValueError), as in tf.keras 2.4; a rate set by a callback still reaches the
@@ -373,27 +344,13 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
 
         def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, name="Nadam", lr=None,
                      schedule_decay=0.004, decay=None, **kwargs):
-            _no_clipping("Nadam", kwargs)
-            self.lr = _rate(lr if lr is not None else learning_rate)
-            if isinstance(self.lr, lr_schedules.LearningRateSchedule):
-                raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the "
-                                 "learning rate.")
-            self.decay = float(schedule_decay if decay is None else decay)
-            self.beta_1, self.beta_2, self.epsilon, self.name = float(beta_1), float(beta_2), float(epsilon), name
-            self.spec()
-
-        def spec(self, device_lr=False):
-            return OptimizerSpec("nadam", self.lr, self.decay, beta_1=self.beta_1, beta_2=self.beta_2,
-                                 epsilon=self.epsilon, device_lr=device_lr)
-
-        def get_config(self):
-            return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay,
-                    "beta_1": self.beta_1, "beta_2": self.beta_2, "epsilon": self.epsilon}
+            self._set(name, lr if lr is not None else learning_rate, schedule_decay if decay is None else decay, kwargs,
+                      beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
 
     @staticmethod
     def get(identifier):
         """compile(optimizer='sgd' | 'adam') -> the optimizer with Keras' defaults; an optimizer object is returned as is."""
-        if isinstance(identifier, (optimizers.SGD, optimizers.Adam) + optimizers.KERAS_EXTRA):
+        if isinstance(identifier, _Optimizer):
             return identifier
         if isinstance(identifier, str):
             kinds = {"sgd": optimizers.SGD, "adam": optimizers.Adam}
@@ -402,11 +359,6 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
         raise ValueError(f"unsupported optimizer {identifier!r}: an optimizer object (optimizers.SGD, Adam, RMSprop, "
                          f"Adagrad, Adadelta, Adamax, Nadam) or the string 'sgd' or 'adam' -- pass the others as "
                          f"objects, e.g. optimizers.RMSprop()")
-
-
-# the optimizers beyond SGD and Adam (csrc/optim_keras.hip), saved and loaded by their Keras class name
-optimizers.KERAS_EXTRA = (optimizers.RMSprop, optimizers.Adagrad, optimizers.Adadelta, optimizers.Adamax,
-                          optimizers.Nadam)
 
 
 class History:
@@ -492,12 +444,14 @@ class Model:
         self._compile_args = None if isinstance(step_loss, str) else dict(loss=loss, loss_weights=loss_weights,
                                                                          metrics=metrics)
         self.net._prepare_training()
-        for name in optimizer.spec().slots:
+        spec, start = optimizer.spec(), optimizer.record.slot_start
+        for name in spec.slots:
             self.net.slot(name)
         for t in self.net.slots().values():
             t.zero_()
-        if isinstance(optimizer, optimizers.Adagrad):
-            self.net.slot("accumulator").fill_(optimizer.initial_accumulator_value)
+        if start is not None:                    # Adagrad's accumulators start at initial_accumulator_value
+            for name in spec.slots:
+                self.net.slot(name).fill_(getattr(optimizer, start))
         self.net.momentum_cache.fill_(1.0)
         self.net.iterations = 0
 
@@ -870,17 +824,10 @@ class Model:
         from . import keras_h5
         opt, slots = None, {}
         if self.optimizer is not None:
-            o = self.optimizer
-            if isinstance(o, optimizers.Adam):
-                opt = dict(class_name="Adam", lr=_serialize_rate(o.lr), decay=o.decay, beta_1=o.beta_1, beta_2=o.beta_2, epsilon=o.epsilon,
-                           amsgrad=o.amsgrad)
-            elif isinstance(o, optimizers.KERAS_EXTRA):
-                opt = dict(class_name=type(o).__name__, lr=_serialize_rate(o.lr),
-                           **{k: v for k, v in o.get_config().items() if k not in ("name", "learning_rate")})
-                if isinstance(o, optimizers.Nadam):
-                    slots["momentum_cache"] = float(self.net.momentum_cache.item())
-            else:
-                opt = dict(lr=_serialize_rate(o.lr), decay=o.decay, momentum=o.momentum, nesterov=o.nesterov)
+            o, scalar = self.optimizer, self.optimizer.record.scalar
+            opt = o.record.as_dict(_serialize_rate(o.lr), o.decay, o.hyper)
+            if scalar is not None:                                   # Nadam's momentum_cache
+                slots[scalar] = float(getattr(self.net, scalar).item())
             p = self.net.params
             for name in o.spec().slots:
                 buf = self.net.slot(name)
@@ -951,15 +898,9 @@ def load_model(path, custom_objects=None):
         lr = o["lr"]
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
-        cls = o.get("class_name", "SGD")
-        extra = {c.__name__: c for c in optimizers.KERAS_EXTRA}
-        if cls == "Adam":
-            opt = optimizers.Adam(learning_rate=lr, decay=o["decay"], beta_1=o["beta_1"], beta_2=o["beta_2"],
-                                  epsilon=o["epsilon"], amsgrad=o["amsgrad"])
-        elif cls in extra:
-            opt = extra[cls](learning_rate=lr, **{k: v for k, v in o.items() if k not in ("class_name", "lr")})
-        else:
-            opt = optimizers.SGD(lr=lr, decay=o["decay"], momentum=o["momentum"], nesterov=o["nesterov"])
+        rec = optimizer_table.record_of(o)
+        opt = getattr(optimizers, rec.class_name)(learning_rate=lr, decay=o["decay"],
+                                                  **{h.name: o[h.name] for h in rec.hyper})
         _compile_saved(m, opt, ck)
         m.net.iterations = ck["iterations"]
         p = m.net.params
@@ -971,8 +912,8 @@ def load_model(path, custom_objects=None):
             for n in p.trainable_names():
                 if n in saved:
                     p.view(n, buf=buf).copy_(torch.from_numpy(np.ascontiguousarray(saved[n])))
-        if cls == "Nadam" and ck.get("momentum_cache") is not None:
-            m.net.momentum_cache.fill_(float(ck["momentum_cache"]))
+        if rec.scalar is not None and ck.get(rec.scalar) is not None:
+            getattr(m.net, rec.scalar).fill_(float(ck[rec.scalar]))
     return m
 
 

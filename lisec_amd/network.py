@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, lr_schedules, ops
+from . import _lib, lr_schedules, ops, optimizer_table
 from .losses import LossSpec
 from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
@@ -29,7 +29,8 @@ from .vfe import VFEStack
 class OptimizerSpec:
     """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
     per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
-    SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295).
+    SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (model_training.py:295).  What a kind has is read from its
+    record in lisec_amd/optimizer_table.py (`record`); in short:
 
         sgd       momentum == 0: no slot;  momentum > 0: "velocity" (v <- m*v - lr_t*g, then w <- w + v, or Nesterov)
         adam      "m", "v", and "vhat" with amsgrad
@@ -45,51 +46,38 @@ class OptimizerSpec:
     arguments, as they always were.  Nadam's `decay` is its momentum-schedule decay (schedule_decay): its rate is not
     divided by 1 + decay*it, its descriptor is built with decay = 0, and a schedule is refused as in tf.keras 2.4."""
 
-    KINDS = ("sgd", "adam", "rmsprop", "adagrad", "adadelta", "adamax", "nadam")
+    KINDS = tuple(optimizer_table.BY_KIND)
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
                  epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1):
-        if kind not in self.KINDS:
+        rec = self.record = optimizer_table.BY_KIND.get(kind)
+        if rec is None:
             raise ValueError(f"unknown optimizer kind {kind!r}")
         self.schedule = lr if isinstance(lr, lr_schedules.LearningRateSchedule) else None
-        if kind == "nadam" and self.schedule is not None:
-            raise ValueError("The Nadam optimizer does not support tf.keras.optimizers.LearningRateSchedules as the "
-                             "learning rate.")
+        if self.schedule is not None and not rec.takes_schedule:
+            raise ValueError(f"The {rec.class_name} optimizer does not support tf.keras.optimizers.LearningRateSchedules "
+                             f"as the learning rate.")
         self.kind, self.lr, self.decay = kind, (lr if self.schedule is not None else float(lr)), float(decay)
         self.device_lr = bool(device_lr) or self.schedule is not None
         # validates a schedule: NotImplementedError for one of the user's own, ValueError past the device's limits
-        self.lr_descriptor = (lr_schedules.descriptor(self.lr, 0.0 if kind == "nadam" else self.decay)
+        self.lr_descriptor = (lr_schedules.descriptor(self.lr, 0.0 if rec.schedule_decay else self.decay)
                               if self.device_lr else None)
-        if kind == "sgd":
-            self.momentum, self.nesterov = float(momentum), bool(nesterov)
-            if self.momentum < 0:
-                raise ValueError("momentum must be >= 0")
-        elif kind == "adam":
-            self.beta_1, self.beta_2, self.epsilon, self.amsgrad = float(beta_1), float(beta_2), float(epsilon), bool(amsgrad)
-            if not (0 <= self.beta_1 < 1 and 0 <= self.beta_2 < 1 and self.epsilon >= 0):
-                raise ValueError("beta_1 and beta_2 must lie in [0, 1), epsilon must be >= 0")
-        else:
-            self.epsilon = float(epsilon)
-            if self.epsilon < 0:
-                raise ValueError("epsilon must be >= 0")
-            if kind in ("rmsprop", "adadelta"):
-                self.rho = float(rho)
-                if not 0 <= self.rho < 1:
-                    raise ValueError("rho must lie in [0, 1)")
-            if kind == "rmsprop":
-                self.momentum, self.centered = float(momentum), bool(centered)
-                if self.momentum < 0:
-                    raise ValueError("momentum must be >= 0")
-            elif kind == "adagrad":
-                self.initial_accumulator_value = float(initial_accumulator_value)
-                if self.initial_accumulator_value < 0:
-                    raise ValueError("initial_accumulator_value must be >= 0")
-            elif kind in ("adamax", "nadam"):
-                self.beta_1, self.beta_2 = float(beta_1), float(beta_2)
-                if not (0 <= self.beta_1 < 1 and 0 <= self.beta_2 < 1):
-                    raise ValueError("beta_1 and beta_2 must lie in [0, 1)")
-                if kind == "nadam" and self.decay < 0:
-                    raise ValueError("schedule_decay must be >= 0")
+        given = dict(momentum=momentum, nesterov=nesterov, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon, amsgrad=amsgrad,
+                     rho=rho, centered=centered, initial_accumulator_value=initial_accumulator_value)
+        for h in rec.hyper:                     # a spec carries the hyper-parameters of its own kind, and no others
+            value = h.coerce(given[h.name])
+            if not h.valid(value):
+                raise ValueError(h.error)
+            setattr(self, h.name, value)
+        if rec.schedule_decay and self.decay < 0:
+            raise ValueError("schedule_decay must be >= 0")
+        # (ops entry, slot names, argument names) of LisecNet._update, worked out once: it runs twice in every eager step
+        self.launch = rec.launch(self.hyper, self.device_lr)
+
+    @property
+    def hyper(self):
+        """{name: value} of the kind's hyper-parameters after the rate and decay, in Keras' order."""
+        return {h.name: getattr(self, h.name) for h in self.record.hyper}
 
     @property
     def config(self):
@@ -102,31 +90,11 @@ class OptimizerSpec:
             rate = ("device",)
         else:
             rate = self.lr
-        if self.kind == "sgd":
-            return ("sgd", rate, self.decay, self.momentum, self.nesterov)
-        if self.kind == "adam":
-            return ("adam", rate, self.decay, self.beta_1, self.beta_2, self.epsilon, self.amsgrad)
-        if self.kind == "rmsprop":
-            return ("rmsprop", rate, self.decay, self.rho, self.momentum, self.epsilon, self.centered)
-        if self.kind == "adagrad":
-            return ("adagrad", rate, self.decay, self.initial_accumulator_value, self.epsilon)
-        if self.kind == "adadelta":
-            return ("adadelta", rate, self.decay, self.rho, self.epsilon)
-        return (self.kind, rate, self.decay, self.beta_1, self.beta_2, self.epsilon)        # adamax, nadam
+        return (self.kind, rate, self.decay, *self.hyper.values())
 
     @property
     def slots(self):
-        if self.kind == "sgd":
-            return ("velocity",) if self.momentum > 0 else ()
-        if self.kind == "adam":
-            return ("m", "v", "vhat") if self.amsgrad else ("m", "v")
-        if self.kind == "rmsprop":
-            return ("rms",) + (("momentum",) if self.momentum > 0 else ()) + (("mg",) if self.centered else ())
-        if self.kind == "adagrad":
-            return ("accumulator",)
-        if self.kind == "adadelta":
-            return ("accum_grad", "accum_var")
-        return ("m", "v")                                                                   # adamax, nadam
+        return tuple(s.name for s in self.record.active_slots(self.hyper))
 
     def __eq__(self, other):
         return isinstance(other, OptimizerSpec) and self.config == other.config
@@ -1142,9 +1110,8 @@ class LisecNet:
         return self.loss_out
 
     def slot(self, name):
-        """The optimizer slot `name` ("velocity", "m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad",
-        "accum_var"; see OptimizerSpec): a buffer shaped like theta, zero when first asked for, at a fixed address from
-        then on (recorded step plans point at it)."""
+        """The optimizer slot `name` (one of SLOT_NAMES; see OptimizerSpec): a buffer shaped like theta, zero when first
+        asked for, at a fixed address from then on (recorded step plans point at it)."""
         self._prepare_training()
         t = self._slots.get(name)
         if t is None:
@@ -1154,7 +1121,7 @@ class LisecNet:
             torch.cuda.synchronize(self.device)   # zero before any stream of the step (the second one included) uses it
         return t
 
-    SLOT_NAMES = ("m", "v", "vhat", "rms", "momentum", "mg", "accumulator", "accum_grad", "accum_var")
+    SLOT_NAMES = optimizer_table.SLOT_NAMES
 
     def slots(self):
         """Every slot made so far, by name (the SGD velocity always among them)."""
@@ -1173,66 +1140,21 @@ class LisecNet:
             self._lr_host = opt.lr_descriptor                 # kept alive: the source of the copy
 
     def _update(self, opt, lo, hi, advance):
-        """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step)."""
-        th, g = self.params.theta[lo:hi], self.grad[lo:hi]
-        sl = [self.slot(name)[lo:hi] for name in opt.slots]
-        if opt.kind not in ("sgd", "adam"):
-            self._update_keras(opt, th, g, sl, advance)
-        elif opt.device_lr:
-            # lr_t from the descriptor (a schedule, or a rate a callback may change): the *_sched entries
+        """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step), by the
+        entry of ops that the optimizer's record names: lr_t by value -- (lr, decay) are kernel arguments --, or with
+        device_lr from the descriptor (a schedule, or a rate a callback may change)."""
+        rec = opt.record
+        entry, names, args = opt.launch
+        bufs = [None if name is None else self.slot(name)[lo:hi] for name in names]
+        if rec.scalar is not None:
+            bufs.append(getattr(self, rec.scalar))
+        if opt.device_lr:
             self._sync_lr(opt)
-            if opt.kind == "adam":
-                ops.adam_step_sched(th, g, sl[0], sl[1], sl[2] if opt.amsgrad else None, self._lr_dev, opt.beta_1,
-                                    opt.beta_2, opt.epsilon, self._iter_dev, advance=advance)
-            else:
-                ops.sgd_step_sched(th, g, sl[0] if sl else None, self._lr_dev, opt.momentum, opt.nesterov, self._iter_dev,
-                                   advance=advance)
-        elif opt.kind == "adam":
-            ops.adam_step_dev(th, g, sl[0], sl[1], sl[2] if opt.amsgrad else None, opt.lr, opt.decay, opt.beta_1,
-                              opt.beta_2, opt.epsilon, self._iter_dev, advance=advance)
-        elif opt.momentum > 0 and opt.nesterov:
-            # the reference's configuration keeps its own kernel (eltwise.hip)
-            ops.sgd_nesterov_step_dev(th, g, sl[0], opt.lr, opt.decay, opt.momentum, self._iter_dev, advance=advance)
+            rate = (self._lr_dev,)
         else:
-            ops.sgd_step_dev(th, g, sl[0] if sl else None, opt.lr, opt.decay, opt.momentum, opt.nesterov, self._iter_dev,
-                             advance=advance)
-
-    def _update_keras(self, opt, th, g, sl, advance):
-        """_update for the optimizers of csrc/optim_keras.hip: lr_t by value, or with device_lr from the descriptor."""
-        desc = self._lr_dev if opt.device_lr else None
-        if desc is not None:
-            self._sync_lr(opt)
-        st, k = self._iter_dev, opt.kind
-        if k == "rmsprop":
-            mom = sl[1] if opt.momentum > 0 else None
-            mg = sl[-1] if opt.centered else None
-            if desc is None:
-                ops.rmsprop_step_dev(th, g, sl[0], mom, mg, opt.lr, opt.decay, opt.rho, opt.momentum, opt.epsilon, st,
-                                     advance=advance)
-            else:
-                ops.rmsprop_step_sched(th, g, sl[0], mom, mg, desc, opt.rho, opt.momentum, opt.epsilon, st, advance=advance)
-        elif k == "adagrad":
-            if desc is None:
-                ops.adagrad_step_dev(th, g, sl[0], opt.lr, opt.decay, opt.epsilon, st, advance=advance)
-            else:
-                ops.adagrad_step_sched(th, g, sl[0], desc, opt.epsilon, st, advance=advance)
-        elif k == "adadelta":
-            if desc is None:
-                ops.adadelta_step_dev(th, g, sl[0], sl[1], opt.lr, opt.decay, opt.rho, opt.epsilon, st, advance=advance)
-            else:
-                ops.adadelta_step_sched(th, g, sl[0], sl[1], desc, opt.rho, opt.epsilon, st, advance=advance)
-        elif k == "adamax":
-            if desc is None:
-                ops.adamax_step_dev(th, g, sl[0], sl[1], opt.lr, opt.decay, opt.beta_1, opt.beta_2, opt.epsilon, st,
-                                    advance=advance)
-            else:
-                ops.adamax_step_sched(th, g, sl[0], sl[1], desc, opt.beta_1, opt.beta_2, opt.epsilon, st, advance=advance)
-        elif desc is None:                                                 # nadam: opt.decay is its schedule_decay
-            ops.nadam_step_dev(th, g, sl[0], sl[1], self.momentum_cache, opt.lr, opt.beta_1, opt.beta_2, opt.epsilon,
-                               opt.decay, st, advance=advance)
-        else:
-            ops.nadam_step_sched(th, g, sl[0], sl[1], self.momentum_cache, desc, opt.beta_1, opt.beta_2, opt.epsilon,
-                                 opt.decay, st, advance=advance)
+            rate = (opt.lr,) if rec.schedule_decay else (opt.lr, opt.decay)
+        getattr(ops, entry)(self.params.theta[lo:hi], self.grad[lo:hi], *bufs, *rate, *(getattr(opt, a) for a in args),
+                            self._iter_dev, advance=advance)
 
     def early_update(self, lo, hi, opt=None):
         """`opt` (an OptimizerSpec; None: the reference's SGD-Nesterov) of theta[lo:hi] AHEAD of the rest of the step
