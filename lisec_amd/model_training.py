@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, losses, lr_schedules, metrics, ops, optimizer_table
-from .network import LisecNet, LossSpec, OptimizerSpec
+from . import callbacks, losses, lr_schedules, metrics, optimizer_table
+from .network import EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
 
@@ -408,6 +408,29 @@ def _grid_key(samples):
     return keys.pop() if len(keys) == 1 else None
 
 
+def _reusable(cached, key, need):
+    """The step of a cached (key, step) when it serves the request.  Otherwise it is closed: another grid / loss /
+    optimizer / network, a larger sweep, or an eager call since (predict() on a larger sweep, a second model)
+    reallocated a workspace the plan holds the raw address of."""
+    if cached is None:
+        return None
+    if cached[0] == key and cached[1].capacity >= need and cached[1].alloc_gen == _lib.alloc_generation():
+        return cached[1]
+    cached[1].close()
+    return None
+
+
+def _targets(ycls, yreg, rows, dev):
+    """target(i) -> the device (y_cls, y_reg) of label map i, for the i of `rows` (a range).  Those maps live on the
+    device for the whole call when they fit comfortably (1.28 MB per sample); otherwise each is uploaded when asked for."""
+    upload = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    if len(rows) * ycls[0].size * 4 * 8 < (2 << 30):
+        maps = slice(rows.start, rows.stop, rows.step)
+        ycls_d, yreg_d = upload(ycls[maps]), upload(yreg[maps])
+        return lambda i, at=rows.index: (ycls_d[at(i)], yreg_d[at(i)])
+    return lambda i: (upload(ycls[i]), upload(yreg[i]))
+
+
 class Model:
     """What createModel returns: the subset of the keras.Model interface the reference uses."""
 
@@ -415,6 +438,9 @@ class Model:
         self.nx, self.ny, self.nz, self.maxPoints = nx, ny, nz, maxPoints
         self.net = LisecNet(nx, ny, nz, maxPoints, params=params)
         self.optimizer, self.loss = None, None
+        self._metric_names = []             # "<output>_<metric>" in compile order
+        self._compile_args = None           # compile()'s loss / loss_weights / metrics, unless they are the reference's
+        self._captured = self._eval_captured = None     # (key, step) of the recorded training / evaluation plan
         self.dp = None
         self.stop_training = False          # set by a callback (EarlyStopping): fit ends after the epoch
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -460,9 +486,9 @@ class Model:
         """['loss', 'ClassificationLayer_loss', 'RegressionLayer_loss', <"<output>_<metric>" in compile order>]: the keys of
         History and of evaluate(return_dict=True), the order of evaluate()'s list.  Unlike Keras, which fills it after the
         first batch, it is set by compile() ([] before)."""
-        if getattr(self, "optimizer", None) is None:
+        if self.optimizer is None:
             return []
-        return list(_LOSS_NAMES) + list(getattr(self, "_metric_names", []))
+        return list(_LOSS_NAMES) + list(self._metric_names)
 
     def _as_samples(self, x):
         if isinstance(x, SparseVoxels):
@@ -531,14 +557,8 @@ class Model:
         for cb in callbacks:
             cb.set_model(self)
             cb.set_params(dict(verbose=verbose, epochs=epochs, steps=steps))
-        # targets live on the device for the whole fit when they fit comfortably (1.28 MB per sample)
-        on_dev = n * ycls[0].size * 4 * 8 < (2 << 30)
-        if on_dev:
-            ycls_d = torch.from_numpy(np.ascontiguousarray(ycls[:n])).to(dev)
-            yreg_d = torch.from_numpy(np.ascontiguousarray(yreg[:n])).to(dev)
-        target = (lambda i: (ycls_d[i], yreg_d[i])) if on_dev else (
-            lambda i: (torch.from_numpy(np.ascontiguousarray(ycls[i])).to(dev),
-                       torch.from_numpy(np.ascontiguousarray(yreg[i])).to(dev)))
+        target = _targets(ycls, yreg, range(n), dev)
+        nm = loss_acc_len(self.loss) - 4                    # metrics of the compiled loss
         for cb in callbacks:
             cb.on_train_begin()
         for epoch in range(epochs):
@@ -553,27 +573,22 @@ class Model:
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
             tot_dev = torch.zeros(3, dtype=torch.float64, device=dev)
-            nm = len(getattr(self, "_metric_names", ()))
             met_dev = torch.zeros(nm, dtype=torch.float64, device=dev) if nm else None
             every = max(1, steps // 20)
             t0 = time.time()
-            for st in range(steps):
+
+            def sweep(st, points=captured is not None):
+                """What step st trains on: (points of the sweep for a recorded step, else its voxel sample, y_cls, y_reg)."""
                 i = int(order[st % len(order)])
-                yc, yr = target(i)
-                if captured is not None and hasattr(captured, "prime"):
-                    # ... pipelined: this step also voxelises the sweep of the next one (second stream, under the backward)
-                    if st == 0:
-                        captured.prime(samples[i]._keepalive, yc, yr)
-                    if st + 1 < steps:
-                        j = int(order[(st + 1) % len(order)])
-                        captured.step(samples[j]._keepalive, *target(j))
-                    else:
-                        captured.step()               # (the next epoch draws its own order and primes its first sweep)
-                elif captured is not None:
+                return (samples[i]._keepalive if points else samples[i], *target(i))
+
+            for st in range(steps):
+                if captured is not None:
                     # the whole step (voxelise + forward + backward + update) re-issued from its recorded plan: one C call
-                    captured(samples[i]._keepalive, yc, yr)
+                    # (PipelinedStep: it also voxelises the sweep of the next step, on the second stream)
+                    captured.fit_step(sweep, st, steps)
                 else:
-                    self.net.train_step(samples[i], yc, yr, loss=self.loss, opt=opt,
+                    self.net.train_step(*sweep(st), loss=self.loss, opt=opt,
                                         allreduce=self.dp.bucketed() if self.dp is not None else None)
                 tot_dev += self.net.loss_out
                 if nm:
@@ -601,34 +616,34 @@ class Model:
             cb.on_train_end()
         return hist
 
+    def _plan_request(self, samples):
+        """What a recorded plan for these samples takes: (cache key without the optimizer, the one voxel grid, point
+        dtype, points of the largest sweep, point capacity to record); None when no plan applies (_grid_key)."""
+        grid = _grid_key(samples)
+        if grid is None:
+            return None
+        pts = [s._keepalive for s in samples]
+        dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
+        need = max(int(p.shape[0]) for p in pts)
+        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream)
+        return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096)     # a little head-room for later calls
+
     def _captured_step(self, samples, opt):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
         Otherwise (None) the Python schedule issues every step."""
-        if not _lib.knob("step_plan", True):
+        req = self._plan_request(samples) if _lib.knob("step_plan", True) else None
+        if req is None:
             return None
-        key0 = _grid_key(samples)
-        if key0 is None:
-            return None
-        pts = [s._keepalive for s in samples]
-        dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
-        need = max(int(p.shape[0]) for p in pts)
-        # the full optimizer config: a re-compile with another optimizer records a new plan
-        key = (key0, dtype, self.loss, opt.config, id(self.net), torch.cuda.current_stream().cuda_stream)
-        cur = getattr(self, "_captured", None)
-        if cur is not None and cur[0] == key and cur[1].capacity >= need and cur[1].alloc_gen == _lib.alloc_generation():
-            return cur[1]
-        if cur is not None:
-            # another grid / optimizer / network -- or an eager call since (predict() on a larger sweep, a second model)
-            # reallocated a workspace the plan holds the raw address of: the old plan points at dead buffers
-            cur[1].close()
-        from .network import RecordedStep, PipelinedStep
-        capacity = max(1024, -(-need // 4096) * 4096)        # a little head-room: later fits reuse the plan
-        step = (PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep)(self.net, Voxelizer(*key0[:3], key0[3], *key0[4:], device=self.net.device), capacity,
-                            dtype=dtype, loss=self.loss, opt=opt,
-                            allreduce=self.dp.bucketed() if self.dp is not None else None)
-        self._captured = (key, step)
+        key, grid, dtype, need, capacity = req
+        key += (opt.config,)         # the full optimizer config: a re-compile with another optimizer records a new plan
+        step = _reusable(self._captured, key, need)
+        if step is None:
+            cls = PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep
+            step = cls(self.net, Voxelizer(*grid, device=self.net.device), capacity, dtype=dtype, loss=self.loss,
+                       opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None)
+            self._captured = (key, step)
         return step
 
     def _eval_step(self, samples):
@@ -637,31 +652,21 @@ class Model:
         device points, one grid -- and LISEC_TUNING=eval_plan=1 asks for it.  Otherwise (None) the eager forward evaluates
         each sweep: the default, as the inference forward is GPU-bound (~1.3 ms per Lyft-grid sweep) and the plan, which
         voxelises every sweep again from its points, measured 3-4 % slower (tools/bench_eval.py)."""
-        if not _lib.knob("eval_plan", False):
+        req = self._plan_request(samples) if _lib.knob("eval_plan", False) else None
+        if req is None:
             return None
-        key0 = _grid_key(samples)
-        if key0 is None:
-            return None
-        pts = [s._keepalive for s in samples]
-        dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
-        need = max(int(p.shape[0]) for p in pts)
-        key = (key0, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream)
-        cur = getattr(self, "_eval_captured", None)
-        if cur is not None and cur[0] == key and cur[1].capacity >= need and cur[1].alloc_gen == _lib.alloc_generation():
-            return cur[1]
-        if cur is not None:
-            cur[1].close()
-        from .network import EvalStep
-        # the training step's voxeliser, whose workspace already holds a training sweep: a validation sweep no larger than
-        # the training ones then allocates nothing, and the recorded training step stays valid
-        train = getattr(self, "_captured", None)
-        if train is not None and train[0][0] == key0 and getattr(train[1], "plans", None):
-            vox = train[1].vox
-        else:
-            vox = Voxelizer(*key0[:3], key0[3], *key0[4:], device=self.net.device)
-        capacity = max(1024, -(-need // 4096) * 4096)
-        step = EvalStep(self.net, vox, capacity, dtype=dtype, loss=self.loss)
-        self._eval_captured = (key, step)
+        key, grid, dtype, need, capacity = req
+        step = _reusable(self._eval_captured, key, need)
+        if step is None:
+            # the training step's voxeliser, whose workspace already holds a training sweep: a validation sweep no
+            # larger than the training ones then allocates nothing, and the recorded training step stays valid
+            train = self._captured
+            if train is not None and train[0][0] == grid and train[1].plans:
+                vox = train[1].vox
+            else:
+                vox = Voxelizer(*grid, device=self.net.device)
+            step = EvalStep(self.net, vox, capacity, dtype=dtype, loss=self.loss)
+            self._eval_captured = (key, step)
         return step
 
     def _labels(self, y, n):
@@ -722,7 +727,7 @@ class Model:
         samples[r::world] (every sweep is evaluated once; DataParallel.shard would drop the tail), evaluates with the
         rank-mean BatchNormalization moving statistics (copy, average, evaluate, restore) and the sums are all-reduced."""
         net, dev = self.net, self.net.device
-        idx = list(range(len(samples)))
+        idx = range(len(samples))
         own = None
         if self.dp is not None:
             idx = idx[self.dp.rank::self.dp.world]
@@ -735,28 +740,15 @@ class Model:
                 step.reset()
                 acc = step.acc
             else:
-                acc = torch.zeros(4 + len(getattr(self, "_metric_names", ())), dtype=torch.float64, device=dev)
+                acc = torch.zeros(loss_acc_len(self.loss), dtype=torch.float64, device=dev)
             if idx:
-                on_dev = len(idx) * ycls[0].size * 4 * 8 < (2 << 30)
-                if on_dev:
-                    yc_d = torch.from_numpy(np.ascontiguousarray(ycls[idx])).to(dev)
-                    yr_d = torch.from_numpy(np.ascontiguousarray(yreg[idx])).to(dev)
-                spec = self.loss if isinstance(self.loss, LossSpec) else None
-                kind = None if spec is not None else {"mse": 0, "smoothl1_ce": 1}[self.loss]
-                for k, i in enumerate(idx):
-                    if on_dev:
-                        yc, yr = yc_d[k], yr_d[k]
-                    else:
-                        yc = torch.from_numpy(np.ascontiguousarray(ycls[i])).to(dev)
-                        yr = torch.from_numpy(np.ascontiguousarray(yreg[i])).to(dev)
+                target = _targets(ycls, yreg, idx, dev)
+                for i in idx:
                     if step is not None:
-                        step(samples[i]._keepalive, yc, yr)
+                        step(samples[i]._keepalive, *target(i))
                     else:
                         net.forward(samples[i], training=False)
-                        if spec is not None:
-                            ops.head_loss_eval(net._loss_descriptor(spec), net.act["head"], yc, yr, net.Ho * net.Wo, acc)
-                        else:
-                            ops.rpn_loss_eval(net.act["head"], yc, yr, net.Ho * net.Wo, kind, acc)
+                        net.loss_eval(self.loss, *target(i), acc)
             if self.dp is not None:
                 self.dp.sum_(acc)
             return acc.cpu().numpy().copy()
@@ -832,7 +824,7 @@ class Model:
             for name in o.spec().slots:
                 buf = self.net.slot(name)
                 slots[name] = {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
-        compiled = getattr(self, "_compile_args", None) or {}
+        compiled = self._compile_args or {}
         keras_h5.save_model(path, d, self.nx, self.ny, self.nz, self.maxPoints, optimizer=opt,
                             iterations=self.net.iterations, **compiled, **slots)
 
@@ -938,11 +930,16 @@ def _load_labels(labels_dir='labels3'):
     return outClass, outRegress
 
 
-def train(samples, level5Data, save_path):
-    """train(samples, level5Data, save_path) (model_training.py:260-302)."""
+def _train(samples, level5Data, save_path, model_path=None):
+    """train and train_with_model: one epoch of 180 steps of the reference's SGD on a new model, or on the one saved at
+    model_path."""
     trainPoints = _preprocess(samples, level5Data, Constants.lyft_data_dir)
     outClass, outRegress = _load_labels()
-    model = createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints)
+    if model_path is None:
+        model = createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints)
+    else:
+        model = load_model(model_path, custom_objects={'RepeatLayer': RepeatLayer,
+                                                       'MaxPoolingVFELayer': MaxPoolingVFELayer})
     sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
     model.compile(optimizer=sgd, loss=['mse', 'mse'])
     history = model.fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, verbose=1, epochs=1,
@@ -951,22 +948,16 @@ def train(samples, level5Data, save_path):
         print(history.history)
     model.save(save_path)
     return model
+
+
+def train(samples, level5Data, save_path):
+    """train(samples, level5Data, save_path) (model_training.py:260-302)."""
+    return _train(samples, level5Data, save_path)
 
 
 def train_with_model(samples, level5Data, model_path, save_path):
     """train_with_model(samples, level5Data, model_path, save_path) (model_training.py:305-346)."""
-    trainPoints = _preprocess(samples, level5Data, Constants.lyft_data_dir)
-    outClass, outRegress = _load_labels()
-    model = load_model(model_path, custom_objects={'RepeatLayer': RepeatLayer,
-                                                   'MaxPoolingVFELayer': MaxPoolingVFELayer})
-    sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
-    model.compile(optimizer=sgd, loss=['mse', 'mse'])
-    history = model.fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, verbose=1, epochs=1,
-                        steps_per_epoch=180)
-    if model.dp is None or model.dp.rank == 0:
-        print(history.history)
-    model.save(save_path)
-    return model
+    return _train(samples, level5Data, save_path, model_path)
 
 
 def _lyft_dataset():

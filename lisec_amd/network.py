@@ -26,6 +26,18 @@ from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
 
+LEGACY_LOSS_KINDS = {"mse": 0, "smoothl1_ce": 1}        # the `kind` of lisec_rpn_loss / lisec_rpn_loss_eval
+
+
+def loss_acc_len(loss):
+    """Length of the evaluation accumulator of a step loss, [total, class, regression, metrics..., sweeps]; KeyError
+    for a string that names no legacy loss."""
+    if isinstance(loss, LossSpec):
+        return 4 + loss.n_metrics
+    LEGACY_LOSS_KINDS[loss]                 # refuses an unknown name
+    return 4
+
+
 class OptimizerSpec:
     """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
     per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
@@ -281,6 +293,8 @@ class LisecNet:
         self.side = torch.cuda.Stream(device=dev, priority=0)
 
         self._tail_ok = {}
+        self._loss_descs = {}                            # LossSpec -> its lisec_loss_cfg (_loss_descriptor)
+        self._head_split = None                          # CopyTable of the head gradients, made by the first backward
         self._early = None                               # (lo, OptimizerSpec) of the pending early_update()
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
         self._fwd_events = {}
@@ -756,10 +770,29 @@ class LisecNet:
 
     def _loss_descriptor(self, spec):
         """The lisec_loss_cfg of a LossSpec, built once per spec."""
-        cache = self.__dict__.setdefault("_loss_descs", {})
-        if spec not in cache:
-            cache[spec] = spec.descriptor()
-        return cache[spec]
+        if spec not in self._loss_descs:
+            self._loss_descs[spec] = spec.descriptor()
+        return self._loss_descs[spec]
+
+    def _loss_backward(self, loss, y_cls, y_reg, grad_scale):
+        """The loss of the head map against the targets into loss_out (a LossSpec: and its metrics into metric_out), its
+        gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*) or a LossSpec (lisec_head_loss*):
+        this, loss_eval() and loss_acc_len() are the only code that tells them apart."""
+        head, dhead, M = self.act["head"], self.dact["head"], self.Ho * self.Wo
+        if isinstance(loss, LossSpec):
+            ops.head_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.metric_out,
+                          grad_scale=grad_scale)
+        else:
+            ops.rpn_loss(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], dhead, self.loss_out, grad_scale=grad_scale)
+
+    def loss_eval(self, loss, y_cls, y_reg, acc):
+        """Adds the loss (and a LossSpec's metrics) of the head map against the targets to acc (float64, device,
+        loss_acc_len(loss) long), which counts the sweep in its last element."""
+        head, M = self.act["head"], self.Ho * self.Wo
+        if isinstance(loss, LossSpec):
+            ops.head_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
+        else:
+            ops.rpn_loss_eval(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], acc)
 
     def _tail_supported(self, c, dst_name):
         """Can the Dense data gradient of block dst_name[:-2] ride on the direct data gradient of conv `c`?  (asked of the
@@ -846,16 +879,11 @@ class LisecNet:
             flush_side()
 
         self._mark("bwd:start")
-        if isinstance(loss, LossSpec):
-            ops.head_loss(self._loss_descriptor(loss), a["head"], y_cls, y_reg, M, d["head"], self.loss_out,
-                          self.metric_out, grad_scale=grad_scale)
-        else:
-            kind = {"mse": 0, "smoothl1_ce": 1}[loss]
-            ops.rpn_loss(a["head"], y_cls, y_reg, M, kind, d["head"], self.loss_out, grad_scale=grad_scale)
+        self._loss_backward(loss, y_cls, y_reg, grad_scale)
         # ---- heads (model_training.py:254-255) ---------------------------------------------------
         # only the data gradient is on the way to the rest of the backward pass: the heads' weight and bias gradients and
         # the deconv bias gradients (column sums of the concat gradient) are leaves and go to the second stream
-        if getattr(self, "_head_split", None) is None:     # merged head gradients -> the Keras-shaped slots of G
+        if self._head_split is None:     # merged head gradients -> the Keras-shaped slots of G
             self._head_split = ops.CopyTable([(self.head_dw[:, :2], p.grad_view(G, "cls.kernel")[0, 0]),
                                               (self.head_dw[:, 2:], p.grad_view(G, "reg.kernel")[0, 0]),
                                               (self.head_db[:2], p.grad_view(G, "cls.bias")),
@@ -1255,26 +1283,94 @@ class StalePlanError(RuntimeError):
 
 
 class _StepPlans:
-    """What RecordedStep and PipelinedStep share: `nbuf` sets of (points, targets, voxel sample) buffers and one step plan
-    recorded per set, the eager warm-up and recording steps (LisecNet.train_step), the replay and its bookkeeping.  The
-    two differ in the number of sets and in where a step voxelises its sweep (_voxelise)."""
+    """What everything that records step plans shares (RecordedStep, PipelinedStep, EvalStep): `nbuf` sets of padded
+    (points, targets) buffers and the staging of a sweep into one (_load), the recording of a callable's launches as one
+    more plan (_record), the checks in front of a replay (stream, allocation generation) and the plans' release."""
 
     PAD = 1.0e6          # metres: floor(1e6 / 0.5) is far beyond maxVoxelX, the point is dropped like any other outlier
 
-    def __init__(self, net, voxelizer, capacity, nbuf, dtype, loss, warmup, allreduce, opt):
-        import ctypes
+    def __init__(self, net, voxelizer, capacity, nbuf, dtype, loss):
         self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
+        self.lib = _lib.load()
+        self.plans, self.launches, self.alloc_gen = [], 0, None
+        dev = net.device
+        self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(nbuf)]
+        self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        self.stream_handle = torch.cuda.current_stream().cuda_stream
+
+    def _record(self, enqueue):
+        """Runs enqueue() eagerly while its launches and event edges are recorded as one more plan."""
+        plan = ctypes.c_void_p()
+        _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(plan)))
+        self.plans.append(plan)
+        _lib.check(self.lib.lisec_step_plan_begin(plan))
+        try:
+            enqueue()
+        finally:
+            _lib.check(self.lib.lisec_step_plan_end(plan))
+        self.launches = self.lib.lisec_step_plan_size(self.plans[0])
+
+    def _seal(self):
+        """Ends the constructor: everything it enqueued is done, and the plans hold the addresses of this generation."""
+        torch.cuda.synchronize(self.net.device)
+        self.alloc_gen = _lib.alloc_generation()
+
+    def _check_stream(self):
+        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
+            raise RuntimeError(f"a {type(self).__name__} replays on the stream it was recorded on: make that stream current")
+
+    def _check_fresh(self):
+        if self.alloc_gen != _lib.alloc_generation():
+            raise StalePlanError(
+                f"this {type(self).__name__} was recorded before a workspace of the network / VFE / voxeliser was "
+                "reallocated (an eager call on a larger sweep or grid): replaying it would write through freed "
+                "addresses.  Record a new one (Model.fit and Model.evaluate do so by themselves).")
+
+    def _load(self, j, points, ycls, yreg):
+        """Stages one sweep into buffer set j: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets
+        (Ho,Wo,2|14)."""
+        self._check_stream()
+        pts = torch.as_tensor(points)
+        n = int(pts.shape[0])
+        if n > self.capacity:
+            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
+        self.points[j][:n].copy_(pts[:, :3], non_blocking=True)
+        if n < self.capacity:
+            self.points[j][n:].fill_(self.PAD)
+        self.ycls[j].copy_(torch.as_tensor(ycls).reshape(self.ycls[j].shape), non_blocking=True)
+        self.yreg[j].copy_(torch.as_tensor(yreg).reshape(self.yreg[j].shape), non_blocking=True)
+
+    def close(self):
+        if self.plans:
+            torch.cuda.synchronize(self.net.device)
+            for plan in self.plans:
+                self.lib.lisec_step_plan_destroy(plan)
+            self.plans = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _TrainingPlans(_StepPlans):
+    """What RecordedStep and PipelinedStep share: one voxel sample and one step plan per buffer set, the eager warm-up
+    and recording steps (LisecNet.train_step), the replay and its bookkeeping.  The two differ in the number of sets, in
+    where the step of buffer set j voxelises its sweep (_voxelise(j) issues it, or returns it as the side_filler of the
+    backward pass) and in how a fit() epoch drives them: fit_step(sweep, st, steps) is step st of an epoch of `steps`
+    steps, sweep(k) -> (points, y_cls, y_reg) being what the epoch's step k trains on."""
+
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
+        nbuf = self.NBUF                         # the number of buffer sets, and of plans
+        super().__init__(net, voxelizer, capacity, nbuf, dtype, loss)
         # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
         # lisec_allreduce_grads and its event edges record themselves, a torch.distributed exchange rides as host calls.
         # Every rank records and replays the same sequence (the warm-up and recording steps exchange gradients for real).
         self.allreduce = allreduce
         dev = net.device
-        self.lib = _lib.load()
-        self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(nbuf)]
-        self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(nbuf)]
-        self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(nbuf)]
         self.opt = OptimizerSpec() if opt is None else opt      # the optimizer of the recorded step
-        self.stream_handle = torch.cuda.current_stream().cuda_stream
         torch.cuda.synchronize(dev)
         net._prepare_training()
         for name in self.opt.slots:
@@ -1286,18 +1382,9 @@ class _StepPlans:
         for k in range(nbuf * max(1, warmup)):
             self._enqueue(k % nbuf)
         torch.cuda.synchronize(dev)
-        self.plans = []
         for j in range(nbuf):
-            plan = ctypes.c_void_p()
-            _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(plan)))
-            self.plans.append(plan)
-            _lib.check(self.lib.lisec_step_plan_begin(plan))
-            try:
-                self._enqueue(j)
-            finally:
-                _lib.check(self.lib.lisec_step_plan_end(plan))
+            self._record(lambda: self._enqueue(j))
         torch.cuda.synchronize(dev)
-        self.launches = self.lib.lisec_step_plan_size(self.plans[0])
         # those steps trained on the padding: put every variable back and repack the kernels from them
         self._restore(keep)
         net.params_version += 1
@@ -1305,8 +1392,7 @@ class _StepPlans:
         net.params.touch()
         net._arm_repack()
         self.cur = 0
-        torch.cuda.synchronize(dev)
-        self.alloc_gen = _lib.alloc_generation()
+        self._seal()
 
     def _snapshot(self):
         """The variables, BN state, every optimizer slot, the iteration count and Nadam's momentum_cache, before the
@@ -1325,39 +1411,15 @@ class _StepPlans:
         net._iterations = keep[4]
         net.momentum_cache.copy_(keep[5])
 
-    def _voxelise(self, j):
-        """The voxelisation of buffer set j's step: issued here, or returned as the side_filler of its backward pass."""
-        raise NotImplementedError
-
     def _enqueue(self, j):
         """One eager step on buffer set j (warm-up, or recorded while it runs)."""
         self.net.train_step(self.samples[j], self.ycls[j], self.yreg[j], loss=self.loss, allreduce=self.allreduce,
                             opt=self.opt, side_filler=self._voxelise(j))
 
-    def _check_stream(self):
-        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
-            raise RuntimeError(f"a {type(self).__name__} replays on the stream it was recorded on: make that stream current")
-
-    def _load(self, j, points, ycls, yreg):
-        """Stages one sweep into buffer set j: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets
-        (Ho,Wo,2|14)."""
-        pts = torch.as_tensor(points)
-        n = int(pts.shape[0])
-        if n > self.capacity:
-            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
-        self.points[j][:n].copy_(pts[:, :3], non_blocking=True)
-        if n < self.capacity:
-            self.points[j][n:].fill_(self.PAD)
-        self.ycls[j].copy_(torch.as_tensor(ycls).reshape(self.ycls[j].shape), non_blocking=True)
-        self.yreg[j].copy_(torch.as_tensor(yreg).reshape(self.yreg[j].shape), non_blocking=True)
-
     def _run(self):
         """Replays the plan of the current buffer set; returns net.loss_out (device, [total, class, regression])."""
-        if self.alloc_gen != _lib.alloc_generation():
-            raise StalePlanError(
-                "this step plan was recorded before a workspace of the network / VFE / voxeliser was reallocated (an eager "
-                "call on a larger sweep or grid): replaying it would write through freed addresses.  Record a new one "
-                "(Model.fit does so by itself).")
+        self._check_stream()
+        self._check_fresh()
         net = self.net
         cur = (net.params_version, net.params.version)
         if net._packed_version != cur or net._packed_t_version != cur or not net._pack_pending:
@@ -1371,21 +1433,8 @@ class _StepPlans:
         self.cur = (self.cur + 1) % len(self.plans)
         return net.loss_out
 
-    def close(self):
-        if getattr(self, "plans", None):
-            torch.cuda.synchronize(self.net.device)
-            for plan in self.plans:
-                self.lib.lisec_step_plan_destroy(plan)
-            self.plans = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RecordedStep(_StepPlans):
+class RecordedStep(_TrainingPlans):
     """One whole fit() step -- voxelise, forward, backward (both streams, fork / join events included), the optimizer
     update (opt: an OptimizerSpec, SGD-Nesterov by default), the weight repack for the next step -- recorded ONCE as a
     step plan of the C ABI (lisec_step_plan_*, csrc/plan.hip) and re-issued by one C call per step: the ~250 launches
@@ -1406,8 +1455,7 @@ class RecordedStep(_StepPlans):
     Record and replay on ONE torch stream (the current stream at construction).  Data parallel (allreduce=): the gradient
     exchange is part of the plan."""
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
-        super().__init__(net, voxelizer, capacity, 1, dtype, loss, warmup, allreduce, opt)
+    NBUF = 1
 
     def _voxelise(self, j):
         self.vox(self.points[0], out=self.samples[0])       # at the head of the step
@@ -1415,20 +1463,21 @@ class RecordedStep(_StepPlans):
 
     def load(self, points, ycls, yreg):
         """Stage one sweep: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets (Ho,Wo,2|14)."""
-        self._check_stream()
         self._load(0, points, ycls, yreg)
 
     def replay(self):
         """Runs the recorded step on what load() staged; returns net.loss_out (device, [total, class, regression])."""
-        self._check_stream()
         return self._run()
 
     def __call__(self, points, ycls, yreg):
         self.load(points, ycls, yreg)
         return self.replay()
 
+    def fit_step(self, sweep, st, steps):
+        return self(*sweep(st))
 
-class PipelinedStep(_StepPlans):
+
+class PipelinedStep(_TrainingPlans):
     """RecordedStep with the input pipeline folded in: step k voxelises the sweep of step k + 1 on the second stream, in the
     ~200 us that stream idles at the start of the backward pass, instead of step k + 1 starting with 90 us of seven small
     dependent launches in front of its first contraction.  Two sets of (points, targets, voxel sample) buffers alternate,
@@ -1442,8 +1491,7 @@ class PipelinedStep(_StepPlans):
                                                                           # (no arguments: the staged buffers are reused)
     """
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
-        super().__init__(net, voxelizer, capacity, 2, dtype, loss, warmup, allreduce, opt)
+    NBUF = 2
 
     def _voxelise(self, j):
         # the sweep of this step was voxelised by the step before; this one voxelises the next under its backward pass
@@ -1451,24 +1499,26 @@ class PipelinedStep(_StepPlans):
 
     def prime(self, points, ycls, yreg):
         """Stages the FIRST sweep and voxelises it (outside the plans); the next step() trains on it."""
-        self._check_stream()
         self._load(self.cur, points, ycls, yreg)
         self.vox(self.points[self.cur], out=self.samples[self.cur])
 
     def stage_next(self, points, ycls, yreg):
         """Stages the sweep the next step() voxelises (and the step() after it trains on)."""
-        self._check_stream()
         self._load(1 - self.cur, points, ycls, yreg)
 
     def step(self, next_points=None, next_ycls=None, next_yreg=None):
         """Trains on the current sweep and voxelises the staged next one; returns net.loss_out (device)."""
-        self._check_stream()
         if next_points is not None:
             self._load(1 - self.cur, next_points, next_ycls, next_yreg)
         return self._run()
 
+    def fit_step(self, sweep, st, steps):
+        if st == 0:
+            self.prime(*sweep(0))                 # (every epoch draws its own order and primes its first sweep)
+        return self.step(*sweep(st + 1)) if st + 1 < steps else self.step()
 
-class EvalStep:
+
+class EvalStep(_StepPlans):
     """One evaluation sweep -- voxelise a fixed-capacity padded sweep (as RecordedStep), forward(training=False), add the
     sweep's loss to a device accumulator (lisec_rpn_loss_eval; lisec_head_loss_eval for a LossSpec) -- recorded ONCE as a
     step plan and re-issued by one C call per sweep (Model.evaluate and the validation of Model.fit with
@@ -1493,58 +1543,37 @@ class EvalStep:
 
     Record and replay on ONE torch stream (the current stream at construction)."""
 
-    PAD = _StepPlans.PAD
-
     def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse"):
-        import ctypes
-        self.net, self.vox, self.capacity = net, voxelizer, int(capacity)
-        self.loss = loss
-        # a LossSpec: lisec_head_loss_eval, acc = [total, class, regression, metrics..., sweeps]
-        self.nacc = 4 + (loss.n_metrics if isinstance(loss, LossSpec) else 0)
-        self.kind = None if isinstance(loss, LossSpec) else {"mse": 0, "smoothl1_ce": 1}[loss]
+        self.nacc = loss_acc_len(loss)            # refuses an unknown loss before anything is allocated
+        super().__init__(net, voxelizer, capacity, 1, dtype, loss)
         dev = net.device
-        self.lib = _lib.load()
-        self.points = torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev)
-        self.ycls = torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev)
-        self.yreg = torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev)
         self.acc = torch.zeros(self.nacc, dtype=torch.float64, device=dev)
-        self.stream_handle = torch.cuda.current_stream().cuda_stream
-        self.sample = self.vox(self.points)
+        self._ready = None                        # the (params_version, state_version, params.version) prepare() served
+        self.sample = self.vox(self.points[0])
         self.prepare()
         scratch = torch.zeros(self.nacc, dtype=torch.float64, device=dev)
         self._enqueue(scratch)                    # eager warm-up: lazy workspaces, descriptor tables, events
         torch.cuda.synchronize(dev)
-        self.plan = ctypes.c_void_p()
-        _lib.check(self.lib.lisec_step_plan_create(ctypes.byref(self.plan)))
-        _lib.check(self.lib.lisec_step_plan_begin(self.plan))
-        try:
-            self._enqueue(self.acc)
-        finally:
-            _lib.check(self.lib.lisec_step_plan_end(self.plan))
-        self.launches = self.lib.lisec_step_plan_size(self.plan)
+        self._record(lambda: self._enqueue(self.acc))
         self.acc.zero_()                          # the recording ran on the padding
-        torch.cuda.synchronize(dev)
-        self.alloc_gen = _lib.alloc_generation()
+        self._seal()
 
     def _enqueue(self, acc):
         net = self.net
         pending = net._pack_pending, net._late_pending
         net._pack_pending = net._late_pending = False      # prepare() made every packed kernel current: no waits
         try:
-            self.vox(self.points, out=self.sample)
+            self.vox(self.points[0], out=self.sample)
             net.forward(self.sample, training=False)
         finally:
             net._pack_pending, net._late_pending = pending
-        if self.kind is None:
-            ops.head_loss_eval(net._loss_descriptor(self.loss), net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, acc)
-        else:
-            ops.rpn_loss_eval(net.act["head"], self.ycls, self.yreg, net.Ho * net.Wo, self.kind, acc)
+        net.loss_eval(self.loss, self.ycls[0], self.yreg[0], acc)
 
     def prepare(self):
         """Packed kernels and BatchNormalization folds current for the weights and statistics of now (see the class)."""
         net = self.net
         key = (net.params_version, net.state_version, net.params.version)
-        if getattr(self, "_ready", None) == key:
+        if self._ready == key:
             return                                # nothing moved since the last sweep: the plan's inputs are current
         main = torch.cuda.current_stream()
         if net._pack_pending or net._late_pending:
@@ -1566,32 +1595,9 @@ class EvalStep:
     def __call__(self, points, ycls, yreg):
         """Stages one sweep (points: n <= capacity rows, >= 3 columns; targets (Ho,Wo,2|14)) and replays the plan: its
         loss is added to self.acc."""
-        if torch.cuda.current_stream().cuda_stream != self.stream_handle:
-            raise RuntimeError("an EvalStep replays on the stream it was recorded on: make that stream current")
-        if self.alloc_gen != _lib.alloc_generation():
-            raise StalePlanError("this evaluation plan was recorded before a workspace was reallocated: record a new one")
-        pts = torch.as_tensor(points)
-        n = int(pts.shape[0])
-        if n > self.capacity:
-            raise ValueError(f"sweep of {n} points exceeds the recorded capacity {self.capacity}")
-        self.points[:n].copy_(pts[:, :3], non_blocking=True)
-        if n < self.capacity:
-            self.points[n:].fill_(self.PAD)
-        self.ycls.copy_(torch.as_tensor(ycls).reshape(self.ycls.shape), non_blocking=True)
-        self.yreg.copy_(torch.as_tensor(yreg).reshape(self.yreg.shape), non_blocking=True)
+        self._check_fresh()
+        self._load(0, points, ycls, yreg)
         self.prepare()
-        _lib.check(self.lib.lisec_step_plan_run(self.plan))
+        _lib.check(self.lib.lisec_step_plan_run(self.plans[0]))
         self.sample._host_info = None
         return self.acc
-
-    def close(self):
-        if getattr(self, "plan", None) is not None:
-            torch.cuda.synchronize(self.net.device)
-            self.lib.lisec_step_plan_destroy(self.plan)
-            self.plan = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -291,7 +291,7 @@ def test_reduce_lr_on_plateau_same_plan_and_bits_as_set_by_hand():
 
     class Flat(callbacks.Callback):
         def on_epoch_begin(self, epoch, logs=None):
-            self.step = getattr(self.model, "_captured", (None, None))[1]
+            self.step = (self.model._captured or (None, None))[1]
 
         def on_epoch_end(self, epoch, logs=None):
             logs["val_loss"] = 1.0                  # a plateau from the second epoch on
