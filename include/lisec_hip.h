@@ -389,6 +389,29 @@ int lisec_conv_forward_winograd(const lisec_conv_geom* g, const float* in, const
                                 const float* in_bnstate, int flags, float* out, const lisec_conv_extras* extras,
                                 lisec_stream_t stream);
 
+/* Inference forward on the bf16 matrix cores (csrc/igemm_bf16.hip, v_mfma_f32_32x32x16_bf16): what the 'mixed_bfloat16'
+ * policy runs for the Conv3D blocks behind the first (model_training.py:237-238) and the Conv2Ds of the RPN (:203).
+ *   out[m, n] = sum_tap sum_c bf16(f(in[src(m,tap), c])) * bf16(W[tap][c][n]) + bias[n]
+ * `in`, `out`, bias and in_bnstate are the fp32 buffers of lisec_conv_forward, in the same layouts; f (the affine of
+ * in_bnstate, then ReLU if LISEC_CONV_IN_RELU) is evaluated in fp32 as one fma, its result and the kernel are rounded to
+ * bf16 to nearest-even, products are accumulated in fp32, and bias / LISEC_CONV_OUT_RELU are fp32: relative to the fp32
+ * contraction the result carries the two operand roundings (2^-9 each) and nothing else.  Padding stays exactly zero.
+ *   lisec_conv_packed_bf16_bytes / lisec_conv_pack_weights_bf16: the layout the kernel reads, [tap][K/8][N][8] bf16 with K
+ *       and N zero padded to 64, from src[tap*tap_stride + k*k_stride + n*n_stride] (fp32, as lisec_conv_pack_weights);
+ *       dst 16-byte aligned.
+ *   lisec_conv_forward_bf16: g->mode == 0, no pixel-shuffle store, dense rows, flags within IN_RELU | OUT_RELU (IN_RELU
+ *       needs in_bnstate); LISEC_EINVAL for anything else -- it never runs the fp32 kernels instead.  No statistics.
+ *       workspace: NULL, or lisec_conv_forward_bf16_workspace_bytes(g) bytes under the rules of the lisec_conv_forward
+ *       workspace (zero-filled once, one per stream; it may be the same buffer): layers of fewer tiles than CUs are cut
+ *       into K slices that meet in slice order inside the kernel (deterministic).  A smaller workspace means fewer slices. */
+size_t lisec_conv_packed_bf16_bytes(int ntaps, int K, int N);
+int lisec_conv_pack_weights_bf16(const float* src, int ntaps, int K, int N, long long tap_stride, long long k_stride,
+                                 long long n_stride, void* dst, lisec_stream_t stream);
+size_t lisec_conv_forward_bf16_workspace_bytes(const lisec_conv_geom* g);
+int lisec_conv_forward_bf16(const lisec_conv_geom* g, const float* in, const void* packed_bf16, float* out, const float* bias,
+                            const float* in_bnstate, int flags, void* workspace, size_t workspace_bytes,
+                            lisec_stream_t stream);
+
 /* Winograd F(2x2, 3x3) form of lisec_conv_wgrad (csrc/wino_wgrad.hip) for the 64 -> 64 Conv3D blocks with 3 x 3 (h, w) taps, stride 1
  * and padding 1 along h and w (model_training.py:193, 237-238; what fit() derives for their kernels, :299): dU[kd] = sum over
  * tiles of (B^T d B) (x) (A dY A^T) per transform point, then dW = G^T dU G -- 4 / 9 of the multiplications of the direct weight

@@ -178,6 +178,14 @@ def _declare(lib):
     lib.lisec_conv_pack_weights.argtypes = [P, c_int, c_int, c_int, LL, LL, LL, P, P]
     lib.lisec_conv_pack_weights_batched.restype = c_int
     lib.lisec_conv_pack_weights_batched.argtypes = [P, c_int, LL, P]
+    lib.lisec_conv_packed_bf16_bytes.restype = c_size_t
+    lib.lisec_conv_packed_bf16_bytes.argtypes = [c_int, c_int, c_int]
+    lib.lisec_conv_pack_weights_bf16.restype = c_int
+    lib.lisec_conv_pack_weights_bf16.argtypes = [P, c_int, c_int, c_int, LL, LL, LL, P, P]
+    lib.lisec_conv_forward_bf16_workspace_bytes.restype = c_size_t
+    lib.lisec_conv_forward_bf16_workspace_bytes.argtypes = [POINTER(ConvGeom)]
+    lib.lisec_conv_forward_bf16.restype = c_int
+    lib.lisec_conv_forward_bf16.argtypes = [POINTER(ConvGeom), P, P, P, P, P, c_int, P, c_size_t, P]
     lib.lisec_conv_num_mblocks.restype = c_int
     lib.lisec_conv_num_mblocks.argtypes = [POINTER(ConvGeom)]
     lib.lisec_conv_forward.restype = c_int

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, losses, lr_schedules, metrics, optimizer_table
+from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table
 from .network import EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, host_row_stats
@@ -431,12 +431,21 @@ def _targets(ycls, yreg, rows, dev):
     return lambda i: (upload(ycls[i]), upload(yreg[i]))
 
 
+def _refuse_mixed_training(policy):
+    if policy.compute_dtype != "float32":
+        raise NotImplementedError(
+            f"training under the '{policy.name}' policy is not implemented: it serves predict() and evaluate(); "
+            "build the model under 'float32' to fit() it")
+
+
 class Model:
     """What createModel returns: the subset of the keras.Model interface the reference uses."""
 
     def __init__(self, nx, ny, nz, maxPoints, params=None):
         self.nx, self.ny, self.nz, self.maxPoints = nx, ny, nz, maxPoints
-        self.net = LisecNet(nx, ny, nz, maxPoints, params=params)
+        # tf.keras.mixed_precision: the global policy in force NOW, fixed for the model's life (mixed_precision.py)
+        self.dtype_policy = mixed_precision.global_policy()
+        self.net = LisecNet(nx, ny, nz, maxPoints, params=params, compute_dtype=self.dtype_policy.compute_dtype)
         self.optimizer, self.loss = None, None
         self._metric_names = []             # "<output>_<metric>" in compile order
         self._compile_args = None           # compile()'s loss / loss_weights / metrics, unless they are the reference's
@@ -520,6 +529,7 @@ class Model:
         val_RegressionLayer_loss join the logs of on_epoch_end and History.  The metrics of compile() are logged as epoch
         means under metrics_names, and with validation as val_<name>.  fit ends after any epoch whose callbacks set
         model.stop_training."""
+        _refuse_mixed_training(self.dtype_policy)
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if batch_size != 1:
@@ -625,7 +635,7 @@ class Model:
         pts = [s._keepalive for s in samples]
         dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         need = max(int(p.shape[0]) for p in pts)
-        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream)
+        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
         return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096)     # a little head-room for later calls
 
     def _captured_step(self, samples, opt):
@@ -933,6 +943,7 @@ def _load_labels(labels_dir='labels3'):
 def _train(samples, level5Data, save_path, model_path=None):
     """train and train_with_model: one epoch of 180 steps of the reference's SGD on a new model, or on the one saved at
     model_path."""
+    _refuse_mixed_training(mixed_precision.global_policy())      # before the sweeps are voxelised, not at fit()
     trainPoints = _preprocess(samples, level5Data, Constants.lyft_data_dir)
     outClass, outRegress = _load_labels()
     if model_path is None:

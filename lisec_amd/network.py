@@ -129,11 +129,17 @@ class ConvLayer:
 
 
 class LisecNet:
-    def __init__(self, nx, ny, nz, maxPoints, params=None, device=None, compose_head=True):
-        """compose_head: the three Conv2DTranspose branches and the 1x1 heads run as 16-channel contractions with composite
+    def __init__(self, nx, ny, nz, maxPoints, params=None, device=None, compose_head=True, compute_dtype="float32"):
+        """compute_dtype: 'float32', or 'bfloat16' (the 'mixed_bfloat16' policy of lisec_amd.mixed_precision): the inference
+        forward then runs the Conv3D blocks behind the first and the Conv2Ds of the RPN with bf16 operands
+        (csrc/igemm_bf16.hip), and training is refused.
+        compose_head: the three Conv2DTranspose branches and the 1x1 heads run as 16-channel contractions with composite
         kernels (csrc/head_fused.hip; exact by linearity, the (Ho,Wo,768) concat is never formed).  False keeps the
         layer-by-layer form (256-channel upsampling into the concat, then the 768 -> 16 heads) -- what the tests compare
         the collapsed form against."""
+        if compute_dtype not in ("float32", "bfloat16"):
+            raise ValueError(f"compute_dtype must be 'float32' or 'bfloat16', not {compute_dtype!r}")
+        self.compute_dtype = compute_dtype
         self.device = device or _lib.require_gpu()
         self.compose_head = bool(compose_head)
         self.lib = _lib.load()
@@ -272,6 +278,16 @@ class LisecNet:
                 if (self.winograd & 2 and L["kind"] == "conv") or (self.winograd & 4 and L["kind"] == "mid"):
                     self.packed_wu_t[c.name] = torch.empty(ops.winograd_packed_floats(g.KD, g.Cout, g.Cin), dtype=f32,
                                                            device=dev)
+        # bf16 packs of the layers the bf16 kernel runs in inference (a bf16 net only): the 3x3(x3) contractions behind the
+        # first Conv3D.  The first Conv3D (field form), the Dense(64)s and the composed heads stay fp32
+        self.packed_bf16 = {}
+        if self.compute_dtype == "bfloat16":
+            for L in self.layers:
+                c = L["conv"]
+                if L["kind"] != "deconv" and L["src"] != "grid":
+                    self.packed_bf16[c.name] = torch.empty(ops.packed_bf16_bytes(c.pack[0], c.pack[1], c.pack[2]),
+                                                           dtype=torch.uint8, device=dev)
+        self.bf16_launches = 0                           # calls of the bf16 kernel so far (tests: the feature is on)
         self.head_w = torch.empty(768, 16, dtype=f32, device=dev)
         self.head_b = torch.empty(16, dtype=f32, device=dev)
         self.fused_bias = torch.empty(16, dtype=f32, device=dev)     # b' = head bias + the branch biases through H
@@ -375,6 +391,10 @@ class LisecNet:
             after_main()
         self._pack_table_rest.run()
         wino_packs(False)
+        for L in self.layers:                            # (empty unless the net computes in bf16)
+            c = L["conv"]
+            if c.name in self.packed_bf16:
+                ops.pack_weights_bf16(p.view(c.wname), *c.pack, out=self.packed_bf16[c.name])
         if self.compose_head:
             self._compose_all()
         if self._pack_table_wc is not None:
@@ -431,7 +451,11 @@ class LisecNet:
         p = self.params
         flags = (ops.IN_RELU if c.in_relu else 0) | (ops.OUT_RELU if c.out_relu else 0)
         sink = self._fwd_sink(c) if (c.bn and training) else None
-        if c.name in self.packed_wu:
+        if not training and c.name in self.packed_bf16:
+            ops.conv_forward_bf16(c.g, x, self.packed_bf16[c.name], out, bias=p.view(c.bias) if c.bias else None,
+                                  in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=flags, ws_tag=ws_tag)
+            self.bf16_launches += 1
+        elif c.name in self.packed_wu:
             ops.conv_forward_winograd(c.g, x, self.packed_wu[c.name], out, bias=p.view(c.bias) if c.bias else None,
                                       in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=flags, sink=sink)
         else:
@@ -485,6 +509,8 @@ class LisecNet:
         """sample: VoxelSample of one lidar sweep.  Returns (cls (1,Ho,Wo,2), reg (1,Ho,Wo,14)) device views."""
         if sample.grid_shape != (self.D, self.H, self.W) or sample.cfg.sampleSize != self.T:
             raise ValueError("voxel sample does not match the model's grid")
+        if training:
+            self._refuse_bf16_training()
         prev_pin = _lib.pin_stream(torch.cuda.current_stream().cuda_stream)   # one stream query for the whole schedule
         try:
             return self._forward(sample, training)
@@ -590,6 +616,11 @@ class LisecNet:
 
     # ------------------------------------------------------------------------------------------------
     # training: explicit backward schedule (what Keras' fit() derives by autograd, model_training.py:299)
+    def _refuse_bf16_training(self):
+        if self.compute_dtype != "float32":
+            raise NotImplementedError("a bfloat16-compute network serves inference only: training in mixed precision is not "
+                                      "implemented (build the network with compute_dtype='float32')")
+
     def _prepare_training(self):
         if self._train_ready:
             return

@@ -170,6 +170,46 @@ def conv_forward(g, x, wp, out, bias=None, in_bn=None, flags=0, stats=None, spli
     return out
 
 
+def packed_bf16_bytes(ntaps, K, N):
+    return _lib.load().lisec_conv_packed_bf16_bytes(ntaps, K, N)
+
+
+def pack_weights_bf16(src, ntaps, K, N, tap_stride, k_stride, n_stride, out=None):
+    """Round a Keras-layout fp32 kernel (any strides) to bf16, nearest-even, into the [tap][K/8][N][8] layout of the bf16
+    inference kernel (lisec_conv_pack_weights_bf16); out: uint8 tensor of packed_bf16_bytes(ntaps, K, N)."""
+    n = packed_bf16_bytes(ntaps, K, N)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=src.device)
+    assert out.numel() >= n
+    _lib.check(_lib.load().lisec_conv_pack_weights_bf16(_lib.ptr(src), ntaps, K, N, tap_stride, k_stride, n_stride,
+                                                        _lib.ptr(out), _lib.current_stream()))
+    return out
+
+
+def conv_bf16_workspace(g, device, tag="main"):
+    """The split-K scratch of conv_workspace (same buffers, same zero-counter contract), sized for the bf16 kernel's plan."""
+    need = _lib.load().lisec_conv_forward_bf16_workspace_bytes(ctypes.byref(g))
+    if need == 0:
+        return None
+    key = (str(device), tag)
+    if key not in _SPLITK_WS or _SPLITK_WS[key].numel() < need:
+        if key in _SPLITK_WS:
+            torch.cuda.synchronize(device)
+        _SPLITK_WS[key] = torch.zeros(need, dtype=torch.uint8, device=device)
+        _lib.bump_alloc_generation()
+    return _SPLITK_WS[key]
+
+
+def conv_forward_bf16(g, x, wp, out, bias=None, in_bn=None, flags=0, splitk=True, ws_tag="main"):
+    """conv_forward(...) with bf16 MFMA operands (lisec_conv_forward_bf16): fp32 x / out / bias / in_bn, wp from
+    pack_weights_bf16.  Forward geometries only; anything the kernel does not serve raises LisecError."""
+    ws = conv_bf16_workspace(g, out.device, ws_tag) if splitk else None
+    _lib.check(_lib.load().lisec_conv_forward_bf16(ctypes.byref(g), _lib.ptr(x), _lib.ptr(wp), _lib.ptr(out),
+                                                   _lib.ptr(bias), _lib.ptr(in_bn), flags, _lib.ptr(ws),
+                                                   ws.numel() if ws is not None else 0, _lib.current_stream()))
+    return out
+
+
 def dense_dw_slabs():
     """Slabs (of 64 x 64 floats) a conv_forward(..., dense_dw=) call writes (lisec_dense_dw_slabs)."""
     return _lib.load().lisec_dense_dw_slabs()
