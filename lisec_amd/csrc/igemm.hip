@@ -1575,19 +1575,121 @@ const float* identity_bnstate(int C) {
 // rounds unsplit and only the LAST, partially filled round is K-sliced (otherwise e.g. mid1's 2500 tiles take 4 rounds of
 // 768 resident workgroups for 3.25 rounds of work).  The slices of a tile are combined inside the kernel by the last one
 // to arrive (splitk_arrive): the workspace holds kSplitCounters arrival counters (zero between calls) and the slabs.
-enum { KERN_IGEMM = 0, KERN_HALO2 = 1, KERN_HALO3 = 2, KERN_DENSE64 = 3, KERN_QUEUE = 4, KERN_WIDE = 5 };
+//
+// plan_conv ends by writing the launches the call consists of (at most two: the whole rounds and the K-sliced tail) into
+// ConvCall::launch.  lisec_conv_forward_ex issues that list and lisec_conv_plan_query adds it up; neither decides anything.
+using TileKernel = decltype(&k_igemm<0, false>);            // k_igemm / k_igemm_halo
+using ResidentKernel = decltype(&k_igemm_queue<0, false>);  // k_igemm_queue / k_dense64
+using WideKernel = decltype(&k_igemm_wide<0, false>);
+
+struct ConvLaunch {
+    enum Kind { TILE, RESIDENT, WIDE } kind;     // the signature, i.e. which pointer is live
+    union { TileKernel tile; ResidentKernel resident; WideKernel wide; };
+    dim3 grid, block;
+    size_t lds;
+    int nsplit, tile0;
+    bool partial;                // the workspace is passed as `partial` (nullptr otherwise)
+};
+
 struct ConvCall {
     ConvGeom g;
     int ntiles, nnb;
     int tile0_tail, nsplit;      // first tile of the K-sliced tail (== ntiles: none); slices
     size_t ws_bytes;
-    bool xf, halo, halo3, dense64, half_n, roofline, wide;
+    bool xf;
     bool db;                     // the K-sliced launch runs the two-image (double-buffered) kernels, one workgroup per CU
-    int kernel;                  // KERN_*
-    int launch_tiles;            // workgroups along x of an every-tile launch (half the tiles with plane_pair)
+    int kernel, cols;            // LISEC_KERNEL_*; output channels per workgroup
     double* stats;               // per-tile table (or the dummy that keeps the statistics paths on under a sink)
-    const float* in_bn;
+    ConvLaunch launch[2];
+    int nlaunch;
+
+    ConvLaunch& add(ConvLaunch::Kind kind, dim3 grid, int threads, size_t lds) {
+        ConvLaunch& l = launch[nlaunch++];
+        l.kind = kind; l.grid = grid; l.block = dim3(threads); l.lds = lds;
+        l.nsplit = 1; l.tile0 = 0; l.partial = false;
+        return l;
+    }
 };
+
+// ---- the instantiations of the family.  These helpers name every kernel the library compiles and no other: a variant
+// that is not listed here does not exist, and plan_conv never asks for one.
+// Calls f(M, X) with the gather mode and the transform-on-load switch as integral constants.
+template <typename F>
+auto with_mode_xf(int mode, bool xf, F f) {
+    using M0 = std::integral_constant<int, 0>;
+    using M1 = std::integral_constant<int, 1>;
+    if (mode == 0) return xf ? f(M0{}, std::true_type{}) : f(M0{}, std::false_type{});
+    return xf ? f(M1{}, std::true_type{}) : f(M1{}, std::false_type{});
+}
+
+struct TileVariant {
+    int mode;
+    bool xf;
+    int nseg;                    // 0: k_igemm; 2 / 3: k_igemm_halo with that many lines per tile
+    int cols = 64;               // 32: half-N workgroups (never sliced, so never double-buffered)
+    bool db = false;             // two LDS images
+    bool tail = false;           // second contraction on the stored tile (two-line halo, 64 columns)
+    bool fold = false;           // BatchNormalization backward on load (mode 1, no XF)
+    bool roofline = false;       // the TAG = 1 symbols (no XF; halo with two lines only)
+};
+
+template <int M, bool X>
+TileKernel plain_kernel(int cols, bool db) {
+    if (db) return k_igemm<M, X, 0, 64, true>;
+    if (cols == 32) return k_igemm<M, X, 0, 32>;
+    return k_igemm<M, X>;
+}
+template <int M, bool X, int NSEG>
+TileKernel halo_kernel(int cols, bool db) {
+    if (db) return k_igemm_halo<M, X, 0, NSEG, 64, true>;
+    if (cols == 32) return k_igemm_halo<M, X, 0, NSEG, 32>;
+    return k_igemm_halo<M, X, 0, NSEG>;
+}
+template <int NSEG>
+TileKernel fold_halo_kernel(int cols, bool db) {
+    if (db) return k_igemm_halo<1, false, 0, NSEG, 64, true, false, true>;
+    if (cols == 32) return k_igemm_halo<1, false, 0, NSEG, 32, false, false, true>;
+    return k_igemm_halo<1, false, 0, NSEG, 64, false, false, true>;
+}
+TileKernel fold_kernel(int nseg, int cols, bool db) {
+    switch (nseg) {
+    case 2: return fold_halo_kernel<2>(cols, db);
+    case 3: return fold_halo_kernel<3>(cols, db);
+    }
+    if (db) return k_igemm<1, false, 0, 64, true, true>;
+    if (cols == 32) return k_igemm<1, false, 0, 32, false, true>;
+    return k_igemm<1, false, 0, 64, false, true>;
+}
+TileKernel roofline_kernel(int mode, int nseg) {
+    if (nseg) return mode == 0 ? k_igemm_halo<0, false, 1, 2> : k_igemm_halo<1, false, 1, 2>;
+    return mode == 0 ? k_igemm<0, false, 1> : k_igemm<1, false, 1>;
+}
+TileKernel tile_kernel(const TileVariant& v) {
+    if (v.roofline) return roofline_kernel(v.mode, v.nseg);
+    if (v.fold) return fold_kernel(v.nseg, v.cols, v.db);
+    return with_mode_xf(v.mode, v.xf, [&](auto m, auto x) -> TileKernel {
+        constexpr int M = decltype(m)::value;
+        constexpr bool X = decltype(x)::value;
+        if (v.tail) return k_igemm_halo<M, X, 0, 2, 64, false, true>;
+        switch (v.nseg) {
+        case 2: return halo_kernel<M, X, 2>(v.cols, v.db);
+        case 3: return halo_kernel<M, X, 3>(v.cols, v.db);
+        }
+        return plain_kernel<M, X>(v.cols, v.db);
+    });
+}
+ResidentKernel queue_kernel(int mode, bool xf) {
+    return with_mode_xf(mode, xf, [](auto m, auto x) -> ResidentKernel { return k_igemm_queue<decltype(m)::value, decltype(x)::value>; });
+}
+WideKernel wide_kernel(int mode, bool xf) {
+    return with_mode_xf(mode, xf, [](auto m, auto x) -> WideKernel { return k_igemm_wide<decltype(m)::value, decltype(x)::value>; });
+}
+ResidentKernel dense64_kernel(bool xf, bool bwd, bool dw) {
+    if (dw) return k_dense64<false, true, true>;
+    if (bwd) return xf ? k_dense64<true, true> : k_dense64<false, true>;
+    return xf ? k_dense64<true, false> : k_dense64<false, false>;
+}
+constexpr size_t tile_lds_bytes(int nseg) { return nseg ? halo_lds_bytes(nseg) : (size_t)(A_FLOATS + B_FLOATS) * sizeof(float); }
 
 void plan_slices(const ConvGeom& g, ConvCall* p) {
     const lisec_tuning& tn = tuning();
@@ -1652,6 +1754,7 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
               int row_capacity, ConvCall* p) {
     ConvGeom& g = p->g;
     if (int rc = conv_geom_check(c, &g)) return rc;
+    p->nlaunch = 0; p->cols = 64;
     const lisec_tuning& tn = tuning();
     const float* out_mask = extras ? extras->out_mask : nullptr;
     LISEC_CHECK_ARG(!out_mask || (!c->ps && ((uintptr_t)out_mask & 15) == 0),
@@ -1705,12 +1808,13 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
     }
     plan_slices(g, p);
     const int ntiles = p->ntiles = cdiv(g.M, BM), nnb = p->nnb = g.CoutP / BN;
-    if (!workspace || workspace_bytes < p->ws_bytes) { p->tile0_tail = ntiles; p->nsplit = 1; p->db = false; }
-    p->roofline = (flags & LISEC_CONV_TAG_ROOFLINE) != 0;
+    const auto unsliced = [&] { p->tile0_tail = ntiles; p->nsplit = 1; p->db = false; };
+    if (!workspace || workspace_bytes < p->ws_bytes) unsliced();
+    const bool roofline = (flags & LISEC_CONV_TAG_ROOFLINE) != 0;
     if (row_coords && !g.in_y && extras && extras->queue && nnb == 1 && ntiles >= resident_slots() && !stats_partials && !g.out_mask &&
-        !p->roofline) {
+        !roofline) {
         g.queue = extras->queue;                     // one un-sliced launch of resident workgroups drawing tiles
-        p->tile0_tail = ntiles; p->nsplit = 1;
+        unsliced();
     }
     if (sk) {
         g.sink.acc = static_cast<long long*>(sk->acc);
@@ -1724,11 +1828,11 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
     // 3-tap stride-1 pad-1 contraction along w over full lines: the w-halo kernel (one A tile per (kd, kh) pair)
     const bool halo_geom = !g.row_coords && !g.ps && g.ls_w == 0 && g.KW == 3 && g.pw == 1 && g.Wi == g.Wo &&
                            g.Wo >= 64 && g.in_stride % 4 == 0;       // <= 3 lines per 128-row tile
-    p->halo3 = g.Wo < BM - 2;                                        // more than two lines per tile possible
+    const bool halo3 = g.Wo < BM - 2;                                // more than two lines per tile possible
     // planes that run different numbers of depth taps: one workgroup per PAIR of planes (see k_igemm_halo) when the layer
     // runs as one launch of the halo kernel and the pairs still fill the chip
     if (tn.plane_pair && !g.in_y && halo_geom && g.Do % 2 == 0 && (g.Ho * g.Wo) % BM == 0 && !g.pc_span &&
-        (p->tile0_tail == ntiles || p->roofline) && (long long)(ntiles / 2) * nnb >= resident_slots()) {
+        (p->tile0_tail == ntiles || roofline) && (long long)(ntiles / 2) * nnb >= resident_slots()) {
         int lo = 1 << 30, hi = 0;
         for (int d = 0; d < g.Do; ++d) {
             int live = 0;
@@ -1740,42 +1844,48 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
         }
         if (lo != hi) { g.plane_tiles = g.Ho * g.Wo / BM; g.plane_pair = 1; }
     }
-    p->dense64 = false; p->half_n = false;
-    if (p->roofline && !p->xf && !g.in_y) {          // one launch, every tile, under its own symbol
-        p->halo = halo_geom && !p->halo3;
-        if (!p->halo) g.plane_pair = 0;
-        p->tile0_tail = ntiles; p->nsplit = 1;
-        p->kernel = p->halo ? KERN_HALO2 : KERN_IGEMM;
-        p->launch_tiles = g.plane_pair ? ntiles / 2 : ntiles;
+    // a launch of the tile family over every tile (half as many workgroups with plane_pair), or over the tiles from `tile0`
+    TileVariant v{c->mode, p->xf, 0};
+    const auto add_tile = [&](dim3 grid, int nsplit = 1, int tile0 = 0) {
+        ConvLaunch& l = p->add(ConvLaunch::TILE, grid, kThreads, (v.db ? 2 : 1) * tile_lds_bytes(v.nseg));
+        l.tile = tile_kernel(v);
+        l.nsplit = nsplit; l.tile0 = tile0; l.partial = nsplit > 1;
+    };
+    if (roofline && !p->xf && !g.in_y) {             // one launch, every tile, under its own symbol
+        v.roofline = true;
+        v.nseg = halo_geom && !halo3 ? 2 : 0;
+        if (!v.nseg) g.plane_pair = 0;
+        unsliced();
+        p->kernel = v.nseg ? LISEC_KERNEL_HALO2 : LISEC_KERNEL_IGEMM;
+        add_tile(dim3(g.plane_pair ? ntiles / 2 : ntiles, nnb, 1));
         return LISEC_OK;
     }
-    p->roofline = false;
     if (extras && extras->tail_w) {
         LISEC_CHECK_ARG(!g.in_y, "tail: not together with in_y");
         // second contraction on the stored tile: one un-sliced launch of the two-line halo kernel over 64 columns
         LISEC_CHECK_ARG(extras->tail_out && ((uintptr_t)extras->tail_w & 15) == 0 && ((uintptr_t)extras->tail_out & 15) == 0,
                         "tail: packed 64 x 64 kernel and an output, 16-byte aligned");
-        LISEC_CHECK_ARG(halo_geom && !p->halo3 && g.Cout == 64 && g.out_stride == 64 && !g.pc_span && !table_stats &&
+        LISEC_CHECK_ARG(halo_geom && !halo3 && g.Cout == 64 && g.out_stride == 64 && !g.pc_span && !table_stats &&
                         !(flags & (LISEC_CONV_ACCUMULATE | LISEC_CONV_OUT_RELU)) && (!bwd_stats || sk),
                         "tail: needs the two-line w-halo kernel, Cout = out_stride = 64, no accumulate / ReLU, statistics through a sink");
         g.tail_w = extras->tail_w; g.tail_out = extras->tail_out;
-        p->tile0_tail = ntiles; p->nsplit = 1; p->db = false;
-        p->halo = true; p->dense64 = false; p->half_n = false;
-        p->launch_tiles = g.plane_pair ? ntiles / 2 : ntiles;
-        p->kernel = KERN_HALO2;
+        unsliced();
+        p->kernel = LISEC_KERNEL_HALO2;
+        v.nseg = 2; v.tail = true;
+        add_tile(dim3(g.plane_pair ? ntiles / 2 : ntiles, 1, 1));
         return LISEC_OK;
     }
-    p->wide = false;
     {
         int wns = 1;
         size_t wws = 0;
         if (!table_stats && !g.out_mask && !g.in_y && plan_wide(g, &wns, &wws) && (wns == 1 || (workspace && workspace_bytes >= wws))) {
-            p->wide = true;
-            p->kernel = KERN_WIDE;
+            p->kernel = LISEC_KERNEL_WIDE; p->cols = 128;
             p->nsplit = wns; p->tile0_tail = wns > 1 ? 0 : ntiles; p->ws_bytes = wws; p->db = false;
-            p->halo = true; p->dense64 = false; p->half_n = false; g.plane_pair = 0;
-            p->launch_tiles = ntiles;
+            g.plane_pair = 0;
             if (sk) g.sink.total = (unsigned)ntiles * (unsigned)(g.CoutP / 128);
+            ConvLaunch& l = p->add(ConvLaunch::WIDE, dim3(ntiles, g.CoutP / 128, wns), kWideThreads, wide_lds_bytes());
+            l.wide = wide_kernel(c->mode, p->xf);
+            l.nsplit = wns; l.partial = true;       // (the kernel does not read it when nsplit == 1)
             return LISEC_OK;
         }
     }
@@ -1785,26 +1895,39 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
         !g.out_mask && !(flags & (LISEC_CONV_ACCUMULATE | LISEC_CONV_TAG_ROOFLINE)) && !table_stats &&
         (!sk || (sk->kind == LISEC_SINK_BACKWARD && bwd_stats)) && !(bwd_stats && !sk) &&
         ntiles >= (g.dw_slabs ? dense_dw_slots() : resident_slots())) {
-        p->dense64 = true;
-        p->kernel = KERN_DENSE64;
-        p->tile0_tail = ntiles; p->nsplit = 1; p->halo = false; g.plane_pair = 0;
-        p->launch_tiles = g.dw_slabs ? dense_dw_slots() : resident_slots();
-        if (sk) g.sink.total = (unsigned)p->launch_tiles;
+        p->kernel = LISEC_KERNEL_DENSE64;
+        unsliced(); g.plane_pair = 0;
+        const int wgs = g.dw_slabs ? dense_dw_slots() : resident_slots();
+        if (sk) g.sink.total = (unsigned)wgs;
+        p->add(ConvLaunch::RESIDENT, dim3(wgs), kThreads, tile_lds_bytes(0)).resident = dense64_kernel(p->xf, bwd_stats, g.dw_slabs != nullptr);
         return LISEC_OK;
     }
     LISEC_CHECK_ARG(!g.dw_slabs, "dense_dw: not served by this call");
     // the halo kernel slices K by whole A tiles: (kd, kh, channel slab) entries
     const int nstage = g.KD * g.KH * cdiv(g.Cin, BK);
-    p->halo = halo_geom && p->nsplit <= nstage;
-    if (!p->halo) g.plane_pair = 0;
-    p->launch_tiles = g.plane_pair ? ntiles / 2 : ntiles;
-    p->kernel = g.queue ? KERN_QUEUE : (p->halo ? (p->halo3 ? KERN_HALO3 : KERN_HALO2) : KERN_IGEMM);
+    v.nseg = halo_geom && p->nsplit <= nstage ? (halo3 ? 3 : 2) : 0;
+    v.fold = g.in_y != nullptr;                      // (FOLD instantiations: the same launch shapes as the plain ones)
+    if (!v.nseg) g.plane_pair = 0;
+    if (g.queue) {
+        p->kernel = LISEC_KERNEL_QUEUE;
+        p->add(ConvLaunch::RESIDENT, dim3(resident_slots()), kThreads, tile_lds_bytes(0)).resident = queue_kernel(c->mode, p->xf);
+        return LISEC_OK;
+    }
+    p->kernel = v.nseg == 3 ? LISEC_KERNEL_HALO3 : (v.nseg ? LISEC_KERNEL_HALO2 : LISEC_KERNEL_IGEMM);
     // a layer that would run as two K slices (160-380 tiles): 32-column workgroups over the whole K instead -- as many
     // workgroups, no slabs
-    if (tn.half_n && p->nsplit == 2 && p->tile0_tail == 0 && !g.queue && !p->db) {
-        p->half_n = true;
-        p->nsplit = 1; p->tile0_tail = ntiles;
+    if (tn.half_n && p->nsplit == 2 && p->tile0_tail == 0 && !p->db) {
+        unsliced();
+        v.cols = p->cols = 32;
         if (sk) g.sink.total = (unsigned)ntiles * (unsigned)cdiv(g.Cout, 32);
+        add_tile(dim3(ntiles, cdiv(g.Cout, 32), 1));  // (no workgroups for column blocks beyond Cout: the 16-column heads)
+        return LISEC_OK;
+    }
+    if (p->tile0_tail > 0)                           // whole rounds, single pass
+        add_tile(dim3(g.plane_pair ? ntiles / 2 : p->tile0_tail, nnb, 1));
+    if (p->tile0_tail < ntiles) {                    // K-sliced tail (or the whole small layer), combined inside the kernel
+        v.db = p->db;                                // two LDS images per workgroup (one workgroup per CU)
+        add_tile(dim3(ntiles - p->tile0_tail, nnb, p->nsplit), p->nsplit, p->tile0_tail);
     }
     return LISEC_OK;
 }
@@ -1845,23 +1968,16 @@ extern "C" int lisec_conv_plan_query(const lisec_conv_geom* c, int has_in_bnstat
                            has_row_list ? dummy_rows + 3 : nullptr, row_capacity, &p))
         return rc;
     out->kernel = p.kernel;
-    out->cols = p.wide ? 128 : (p.half_n ? 32 : 64);
+    out->cols = p.cols;
     out->tiles = p.ntiles;
     out->tail_tile0 = p.tile0_tail;
     out->k_slices = p.nsplit;
     out->plane_pair = p.g.plane_pair;
     out->parity_classes = p.g.pc_span ? 1 : 0;
-    out->double_buffered = p.db && p.nsplit > 1 ? 1 : 0;
-    const int ycols = p.half_n ? cdiv(p.g.Cout, 32) : p.nnb;
-    int wgs = 0, launches = 0;
-    if (p.kernel == KERN_DENSE64 || p.kernel == KERN_QUEUE) { wgs = p.kernel == KERN_DENSE64 ? p.launch_tiles : resident_slots(); launches = 1; }
-    else if (p.wide) { wgs = p.ntiles * (p.g.CoutP / 128) * p.nsplit; launches = 1; }
-    else {
-        if (p.tile0_tail > 0) { wgs += (p.g.plane_pair ? p.launch_tiles : p.tile0_tail) * ycols; ++launches; }
-        if (p.tile0_tail < p.ntiles) { wgs += (p.ntiles - p.tile0_tail) * p.nnb * p.nsplit; ++launches; }
-    }
-    out->workgroups = wgs;
-    out->launches = launches;
+    out->double_buffered = p.db ? 1 : 0;
+    out->workgroups = 0;
+    for (int i = 0; i < p.nlaunch; ++i) out->workgroups += (int)(p.launch[i].grid.x * p.launch[i].grid.y * p.launch[i].grid.z);
+    out->launches = p.nlaunch;
     return LISEC_OK;
 }
 
@@ -1903,188 +2019,32 @@ extern "C" int lisec_conv_forward_ex(const lisec_conv_geom* c, const float* in, 
                            row_count, row_capacity, &p))
         return rc;
     const ConvGeom& g = p.g;
-    stats_partials = p.stats;
     LISEC_CHECK_ARG(in && packed_w && out, "NULL tensor pointer");
     LISEC_CHECK_ARG(((uintptr_t)in & 15) == 0 && ((uintptr_t)packed_w & 15) == 0, "in/weights must be 16-byte aligned");
-    const int ntiles = p.ntiles, nnb = p.nnb;
-    const size_t lds = (size_t)(A_FLOATS + B_FLOATS) * sizeof(float);
-    const size_t lds_halo = halo_lds_bytes(p.halo3 ? 3 : 2);
-    hipStream_t st = static_cast<hipStream_t>(stream_);
-    const bool xf = p.xf;
-    if (xf && !in_bnstate) {
+    LISEC_CHECK_ARG(p.nsplit == 1 || ((uintptr_t)workspace & 15) == 0, "split-K needs a 16-byte aligned workspace");
+    if (p.xf && !in_bnstate) {
         // ReLU on load without a BatchNormalization: the kernels always read a (scale, shift) table -- hand them the identity
         in_bnstate = identity_bnstate(g.Cin);
         LISEC_CHECK_ARG(in_bnstate, "LISEC_CONV_IN_RELU without a bnstate supports Cin <= 4096");
     }
-    if (p.roofline) {
-        dim3 grid(p.halo ? p.launch_tiles : ntiles, nnb, 1);
-        if (p.halo) {
-            if (c->mode == 0)
-                LISEC_LAUNCH((k_igemm_halo<0, false, 1, 2>), grid, dim3(kThreads), halo_lds_bytes(2), st, g, in, packed_w,
-                                   bias, in_bnstate, flags, out, stats_partials, 1, (float*)nullptr, 0);
-            else
-                LISEC_LAUNCH((k_igemm_halo<1, false, 1, 2>), grid, dim3(kThreads), halo_lds_bytes(2), st, g, in, packed_w,
-                                   bias, in_bnstate, flags, out, stats_partials, 1, (float*)nullptr, 0);
-        } else if (c->mode == 0) {
-            LISEC_LAUNCH((k_igemm<0, false, 1>), grid, dim3(kThreads), lds, st, g, in, packed_w, bias, in_bnstate,
-                               flags, out, stats_partials, 1, (float*)nullptr, 0);
-        } else {
-            LISEC_LAUNCH((k_igemm<1, false, 1>), grid, dim3(kThreads), lds, st, g, in, packed_w, bias, in_bnstate,
-                               flags, out, stats_partials, 1, (float*)nullptr, 0);
-        }
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (p.dense64) {
-        const int wgs = p.launch_tiles;
-        const bool xf_bn = in_bnstate != nullptr, bwd_stats = g.bwd_y != nullptr;
-#define LISEC_D64(X_, B_) LISEC_LAUNCH((k_dense64<X_, B_>), dim3(wgs), dim3(kThreads), lds, st, g, in, packed_w, bias, \
-        in_bnstate, flags, out)
-        if (g.dw_slabs)
-            LISEC_LAUNCH((k_dense64<false, true, true>), dim3(wgs), dim3(kThreads), lds, st, g, in, packed_w, bias, in_bnstate, flags, out);
-        else if (bwd_stats) { if (xf_bn) LISEC_D64(true, true); else LISEC_D64(false, true); }
-        else           { if (xf_bn) LISEC_D64(true, false); else LISEC_D64(false, false); }
-#undef LISEC_D64
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    const bool halo = p.halo, halo3 = p.halo3;
-#define LISEC_IG(M_, X_, GRID_, NS_, PART_, T0_) LISEC_LAUNCH((k_igemm<M_, X_>), GRID_, dim3(kThreads), lds, st, g, in, \
-        packed_w, bias, in_bnstate, flags, out, stats_partials, NS_, PART_, T0_)
-#define LISEC_IG_ALL(GRID_, NS_, PART_, T0_)                                                                   \
-    do {                                                                                                       \
-        if (c->mode == 0) { if (xf) LISEC_IG(0, true, GRID_, NS_, PART_, T0_); else LISEC_IG(0, false, GRID_, NS_, PART_, T0_); } \
-        else              { if (xf) LISEC_IG(1, true, GRID_, NS_, PART_, T0_); else LISEC_IG(1, false, GRID_, NS_, PART_, T0_); } \
-    } while (0)
-#define LISEC_IH(M_, X_, GRID_, NS_, PART_, T0_)                                                                 \
-    do {                                                                                                         \
-        if (halo3) LISEC_LAUNCH((k_igemm_halo<M_, X_, 0, 3>), GRID_, dim3(kThreads), lds_halo, st, g, in, packed_w, \
-                                      bias, in_bnstate, flags, out, stats_partials, NS_, PART_, T0_);            \
-        else LISEC_LAUNCH((k_igemm_halo<M_, X_, 0, 2>), GRID_, dim3(kThreads), lds_halo, st, g, in, packed_w, bias, \
-                                in_bnstate, flags, out, stats_partials, NS_, PART_, T0_);                        \
-    } while (0)
-#define LISEC_IG_ANY(GRID_, NS_, PART_, T0_)                                                                   \
-    do {                                                                                                       \
-        if (halo) {                                                                                            \
-            if (c->mode == 0) { if (xf) LISEC_IH(0, true, GRID_, NS_, PART_, T0_); else LISEC_IH(0, false, GRID_, NS_, PART_, T0_); } \
-            else              { if (xf) LISEC_IH(1, true, GRID_, NS_, PART_, T0_); else LISEC_IH(1, false, GRID_, NS_, PART_, T0_); } \
-        } else LISEC_IG_ALL(GRID_, NS_, PART_, T0_);                                                           \
-    } while (0)
-    if (g.in_y) {
-        // BatchNormalization backward applied on load (FOLD instantiations; transposed gather): the same launch shapes as below
-#define LISEC_FL(KERNEL_, GRID_, LDS_, NS_, PART_, T0_) LISEC_LAUNCH(KERNEL_, GRID_, dim3(kThreads), LDS_, st, g, in, packed_w, bias, \
-        in_bnstate, flags, out, stats_partials, NS_, PART_, T0_)
-        if (p.half_n) {
-            dim3 grid(ntiles, cdiv(g.Cout, 32), 1);
-            if (!halo) LISEC_FL((k_igemm<1, false, 0, 32, false, true>), grid, lds, 1, (float*)nullptr, 0);
-            else if (halo3) LISEC_FL((k_igemm_halo<1, false, 0, 3, 32, false, false, true>), grid, lds_halo, 1, (float*)nullptr, 0);
-            else LISEC_FL((k_igemm_halo<1, false, 0, 2, 32, false, false, true>), grid, lds_halo, 1, (float*)nullptr, 0);
-            LISEC_LAUNCH_CHECK();
-            return LISEC_OK;
-        }
-        if (p.tile0_tail > 0) {
-            dim3 grid(p.tile0_tail, nnb, 1);
-            if (!halo) LISEC_FL((k_igemm<1, false, 0, 64, false, true>), grid, lds, 1, (float*)nullptr, 0);
-            else if (halo3) LISEC_FL((k_igemm_halo<1, false, 0, 3, 64, false, false, true>), grid, lds_halo, 1, (float*)nullptr, 0);
-            else LISEC_FL((k_igemm_halo<1, false, 0, 2, 64, false, false, true>), grid, lds_halo, 1, (float*)nullptr, 0);
-        }
-        if (p.tile0_tail < ntiles) {
-            LISEC_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "split-K needs a 16-byte aligned workspace");
-            float* partial = static_cast<float*>(workspace);
-            dim3 grid(ntiles - p.tile0_tail, nnb, p.nsplit);
-            if (p.db) {
-                if (!halo) LISEC_FL((k_igemm<1, false, 0, 64, true, true>), grid, 2 * lds, p.nsplit, partial, p.tile0_tail);
-                else if (halo3) LISEC_FL((k_igemm_halo<1, false, 0, 3, 64, true, false, true>), grid, 2 * lds_halo, p.nsplit, partial, p.tile0_tail);
-                else LISEC_FL((k_igemm_halo<1, false, 0, 2, 64, true, false, true>), grid, 2 * lds_halo, p.nsplit, partial, p.tile0_tail);
-            } else {
-                if (!halo) LISEC_FL((k_igemm<1, false, 0, 64, false, true>), grid, lds, p.nsplit, partial, p.tile0_tail);
-                else if (halo3) LISEC_FL((k_igemm_halo<1, false, 0, 3, 64, false, false, true>), grid, lds_halo, p.nsplit, partial, p.tile0_tail);
-                else LISEC_FL((k_igemm_halo<1, false, 0, 2, 64, false, false, true>), grid, lds_halo, p.nsplit, partial, p.tile0_tail);
-            }
-        }
-#undef LISEC_FL
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (p.half_n) {
-        dim3 grid(ntiles, cdiv(g.Cout, 32), 1);       // (no workgroups for column blocks beyond Cout: the 16-column heads)
-#define LISEC_HN(KERNEL_, LDS_) LISEC_LAUNCH(KERNEL_, grid, dim3(kThreads), LDS_, st, g, in, packed_w, bias, in_bnstate, \
-        flags, out, stats_partials, 1, (float*)nullptr, 0)
-#define LISEC_HN_MX(M_, X_)                                                                            \
-        do {                                                                                           \
-            if (!halo) LISEC_HN((k_igemm<M_, X_, 0, 32>), lds);                                        \
-            else if (halo3) LISEC_HN((k_igemm_halo<M_, X_, 0, 3, 32>), lds_halo);                      \
-            else LISEC_HN((k_igemm_halo<M_, X_, 0, 2, 32>), lds_halo);                                 \
-        } while (0)
-        if (c->mode == 0) { if (xf) LISEC_HN_MX(0, true); else LISEC_HN_MX(0, false); }
-        else              { if (xf) LISEC_HN_MX(1, true); else LISEC_HN_MX(1, false); }
-#undef LISEC_HN_MX
-#undef LISEC_HN
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (g.queue) {
-        dim3 grid(resident_slots(), 1, 1);
-#define LISEC_IQ(M_, X_) LISEC_LAUNCH((k_igemm_queue<M_, X_>), grid, dim3(kThreads), lds, st, g, in, packed_w, bias, \
-        in_bnstate, flags, out)
-        if (c->mode == 0) { if (xf) LISEC_IQ(0, true); else LISEC_IQ(0, false); }
-        else              { if (xf) LISEC_IQ(1, true); else LISEC_IQ(1, false); }
-#undef LISEC_IQ
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (p.wide) {
-        LISEC_CHECK_ARG(p.nsplit == 1 || ((uintptr_t)workspace & 15) == 0, "split-K needs a 16-byte aligned workspace");
-        dim3 grid(ntiles, g.CoutP / 128, p.nsplit);
-        float* partial = static_cast<float*>(workspace);
-#define LISEC_IW(M_, X_) LISEC_LAUNCH((k_igemm_wide<M_, X_>), grid, dim3(kWideThreads), wide_lds_bytes(), st, g, in, packed_w, bias, \
-        in_bnstate, flags, out, stats_partials, p.nsplit, partial)
-        if (c->mode == 0) { if (xf) LISEC_IW(0, true); else LISEC_IW(0, false); }
-        else              { if (xf) LISEC_IW(1, true); else LISEC_IW(1, false); }
-#undef LISEC_IW
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (g.tail_w) {                                  // one un-sliced launch of the two-line halo kernel with the tail contraction
-        dim3 grid(g.plane_pair ? p.launch_tiles : ntiles, 1, 1);
-#define LISEC_IT(M_, X_) LISEC_LAUNCH((k_igemm_halo<M_, X_, 0, 2, 64, false, true>), grid, dim3(kThreads), lds_halo, st, g, in, \
-        packed_w, bias, in_bnstate, flags, out, stats_partials, 1, (float*)nullptr, 0)
-        if (c->mode == 0) { if (xf) LISEC_IT(0, true); else LISEC_IT(0, false); }
-        else              { if (xf) LISEC_IT(1, true); else LISEC_IT(1, false); }
-#undef LISEC_IT
-        LISEC_LAUNCH_CHECK();
-        return LISEC_OK;
-    }
-    if (p.tile0_tail > 0) {                          // whole rounds, single pass
-        dim3 grid(g.plane_pair ? p.launch_tiles : p.tile0_tail, nnb, 1);
-        LISEC_IG_ANY(grid, 1, (float*)nullptr, 0);
-    }
-    if (p.tile0_tail < ntiles) {                     // K-sliced tail (or the whole small layer), combined inside the kernel
-        LISEC_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "split-K needs a 16-byte aligned workspace");
-        float* partial = static_cast<float*>(workspace);
-        dim3 grid(ntiles - p.tile0_tail, nnb, p.nsplit);
-        if (p.db) {
-            // two LDS images per workgroup (one workgroup per CU)
-#define LISEC_DBL(KERNEL_, LDS_) LISEC_LAUNCH(KERNEL_, grid, dim3(kThreads), 2 * (LDS_), st, g, in, packed_w, bias, in_bnstate, \
-        flags, out, stats_partials, p.nsplit, partial, p.tile0_tail)
-#define LISEC_DBL_MX(M_, X_)                                                                           \
-            do {                                                                                       \
-                if (!halo) LISEC_DBL((k_igemm<M_, X_, 0, 64, true>), lds);                             \
-                else if (halo3) LISEC_DBL((k_igemm_halo<M_, X_, 0, 3, 64, true>), lds_halo);           \
-                else LISEC_DBL((k_igemm_halo<M_, X_, 0, 2, 64, true>), lds_halo);                      \
-            } while (0)
-            if (c->mode == 0) { if (xf) LISEC_DBL_MX(0, true); else LISEC_DBL_MX(0, false); }
-            else              { if (xf) LISEC_DBL_MX(1, true); else LISEC_DBL_MX(1, false); }
-#undef LISEC_DBL_MX
-#undef LISEC_DBL
-        } else {
-            LISEC_IG_ANY(grid, p.nsplit, partial, p.tile0_tail);
+    hipStream_t st = static_cast<hipStream_t>(stream_);
+    for (int i = 0; i < p.nlaunch; ++i) {
+        const ConvLaunch& l = p.launch[i];
+        float* partial = l.partial ? static_cast<float*>(workspace) : nullptr;
+        switch (l.kind) {
+        case ConvLaunch::TILE:
+            LISEC_LAUNCH(l.tile, l.grid, l.block, l.lds, st, g, in, packed_w, bias, in_bnstate, flags, out, p.stats, l.nsplit,
+                         partial, l.tile0);
+            break;
+        case ConvLaunch::RESIDENT:
+            LISEC_LAUNCH(l.resident, l.grid, l.block, l.lds, st, g, in, packed_w, bias, in_bnstate, flags, out);
+            break;
+        case ConvLaunch::WIDE:
+            LISEC_LAUNCH(l.wide, l.grid, l.block, l.lds, st, g, in, packed_w, bias, in_bnstate, flags, out, p.stats, l.nsplit,
+                         partial);
+            break;
         }
     }
-#undef LISEC_IG_ANY
-#undef LISEC_IH
-#undef LISEC_IG_ALL
-#undef LISEC_IG
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
