@@ -13,15 +13,16 @@
 //
 // One 512-thread workgroup per CU owns 8 x 8 Winograd tiles (16 x 16 outputs) of one output plane x 64 output channels.
 // Wave (half, wm, wn) owns 32 tiles x 32 channels x 8 of the 16 points (half = rows i of M: 128 accumulator registers per
-// lane, two waves per SIMD); waves 0-3 also do ALL of the staging.  K runs in chunks of 8 input channels of one depth tap;
-// per chunk
-//   window          the raw 18 x 18 positions under the block, 16 channels of one depth plane at a time (two chunks), parked
-//                   in LDS: every position is fetched ONCE, as 64 contiguous bytes
-//   V[pt][tile][8]  each staging thread reads the 4 x 4 patch of one (tile, channel pair) from the window, gates it (the
+// lane, two waves per SIMD).  The two waves of a SIMD also share the staging: waves 4-7 MOVE (window and U image, global memory
+// -> registers -> LDS, no VALU), waves 0-3 TRANSFORM (patch reads, gate, B^T d B, V stores).  K runs in chunks of 8 input
+// channels of one depth tap; per chunk
+//   window          (waves 4-7) the raw 18 x 18 positions under the block, 16 channels of one depth plane at a time (two
+//                   chunks), parked in LDS: every position is fetched ONCE, as 64 contiguous bytes
+//   V[pt][tile][8]  (waves 0-3) each thread reads the 4 x 4 patch of one (tile, channel pair) from the window, gates it (the
 //                   BatchNormalization(+ReLU) of the producing layer is applied here, padding stays exactly zero), transforms
 //                   it (32 adds per channel) and stores 16 x 8 bytes
-//   U[pt][n][8]     linear 32 KB copy of the pre-transformed kernel (lisec_conv_pack_weights_winograd writes the LDS image,
-//                   swizzle included)
+//   U[pt][n][8]     (waves 4-7) linear 32 KB copy of the pre-transformed kernel (lisec_conv_pack_weights_winograd writes the
+//                   LDS image, swizzle included)
 //   32 MFMAs per wave: per point one ds_read_b128 of V and one of U (four K steps each).
 // Two LDS stages + the window (153 KB): the image of chunk c + 1 is built while the MFMAs of chunk c read the other stage.
 // Rows of V / U are 32 bytes; the 16-byte half a lane reads is swizzled by bit 3 of the row so that every 16-lane group of a
@@ -63,8 +64,9 @@ __device__ unsigned long long* g_wino_stamps = nullptr;
         if (stamps && threadIdx.x == 0 && stamp_wg < 8192) stamps[(size_t)stamp_wg * 8 + (K_)] = (V_); \
     } while (0)
 
-// EXP: timing-only variants (wrong results; tools/wino_stamps.py): 1 = no side work in the K loop, 2 = no global loads in it,
-// 3 = no LDS stores in it, 4 = no MFMAs in the helper waves, 5 = no MFMAs in the staging waves, 6 = the chunk walks stand still
+// EXP: timing-only variants (wrong results; tools/wino_stamps.py): 1 = no side work in the K loop (neither half), 4 = no MFMAs
+// in waves 4-7 (the moving half; both halves still do their side work), 5 = no MFMAs in waves 0-3 (the transforming half),
+// 6 = the chunk walks stand still.  (2 and 3 were variants of an earlier form and are gone; the numbers are the flag values.)
 // TAG only changes the symbol name: bench.py launches the second middle block's forward through k_wino<false, 0, 1> so that
 // its row in a rocprofv3 --stats summary is that layer alone (same code as TAG 0).
 template <bool XF, int EXP = 0, int TAG = 0>
@@ -75,10 +77,10 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // waves 0-3 (half 0) stage AND multiply, waves 4-7 (half 1) only multiply: wave w and wave w + 4 sit on one SIMD and own
-    // the same 32 tiles x 32 channels, points 0-7 and 8-15
+    // wave w (half 0) and wave w + 4 (half 1) sit on one SIMD and own the same 32 tiles x 32 channels, points 0-7 and 8-15;
+    // both multiply, and they share the side work: half 0 transforms the patches, half 1 moves the window and the U image
     const int half = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-    const int tid = threadIdx.x & 255;               // staging identity (half 0 only)
+    const int tid = threadIdx.x & 255;               // staging identity inside a half: (tile, channel pair) / piece to move
     const int H = g.Ho, W = g.Wo;
     unsigned long long* stamps = g_wino_stamps;
     const unsigned stamp_wg = blockIdx.y * gridDim.x + blockIdx.x;
@@ -232,25 +234,21 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
         t[8 + j].x = d[8 + j].x - d[4 + j].x;   t[8 + j].y = d[8 + j].y - d[4 + j].y;
         t[12 + j].x = d[4 + j].x - d[12 + j].x; t[12 + j].y = d[4 + j].y - d[12 + j].y;
     };
-    auto b_row = [&](int i, float* vp, bool store) { // (B^T d) B, row i, and its four 8-byte stores
+    auto b_row = [&](int i, float* vp) {             // (B^T d) B, row i, and its four 8-byte stores
         float2 v0, v1, v2, v3;
         v0.x = t[4 * i + 0].x - t[4 * i + 2].x; v0.y = t[4 * i + 0].y - t[4 * i + 2].y;
         v1.x = t[4 * i + 1].x + t[4 * i + 2].x; v1.y = t[4 * i + 1].y + t[4 * i + 2].y;
         v2.x = t[4 * i + 2].x - t[4 * i + 1].x; v2.y = t[4 * i + 2].y - t[4 * i + 1].y;
         v3.x = t[4 * i + 1].x - t[4 * i + 3].x; v3.y = t[4 * i + 1].y - t[4 * i + 3].y;
-        if (store) {
-            *reinterpret_cast<float2*>(vp + (4 * i + 0) * (WT * WK)) = v0;
-            *reinterpret_cast<float2*>(vp + (4 * i + 1) * (WT * WK)) = v1;
-            *reinterpret_cast<float2*>(vp + (4 * i + 2) * (WT * WK)) = v2;
-            *reinterpret_cast<float2*>(vp + (4 * i + 3) * (WT * WK)) = v3;
-        } else {                                     // (timing variant: keeps the transform alive without the stores)
-            asm volatile("" :: "v"(v0.x), "v"(v0.y), "v"(v1.x), "v"(v1.y), "v"(v2.x), "v"(v2.y), "v"(v3.x), "v"(v3.y));
-        }
+        *reinterpret_cast<float2*>(vp + (4 * i + 0) * (WT * WK)) = v0;
+        *reinterpret_cast<float2*>(vp + (4 * i + 1) * (WT * WK)) = v1;
+        *reinterpret_cast<float2*>(vp + (4 * i + 2) * (WT * WK)) = v2;
+        *reinterpret_cast<float2*>(vp + (4 * i + 3) * (WT * WK)) = v3;
     };
 
     if (nchunks > 0) {
         // window of group 0 -> LDS, image of chunk 0 -> stage 0 (the loop then prepares chunk c + 1 inside chunk c)
-        if (half == 0) {
+        if (half == 1) {
             const float* wsrc = window_src();
             const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wsrc), 0, 0x7fffffff, 0x00020000);
             WINO_R_LD(rw0, 0); WINO_R_LD(rw1, 1); WINO_R_LD(rw2, 2);
@@ -258,14 +256,19 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
             WINO_R_LD(rw0, 3); WINO_R_LD(rw1, 4); WINO_R_LD(rw2, 5);
             WINO_R_ST(rw0, 3); WINO_R_ST(rw1, 4); WINO_R_ST(rw2, 5);
             advance(w_kd, w_cc, w_left, 2);
-            load_x(tsc, tsh, 0);
         }
+        if (half == 0) load_x(tsc, tsh, 0);
         __syncthreads();
-        if (half == 0) {
+        if (half == 1) {
             const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float*>(U + ((size_t)(u_kd * ncc + u_cc) * nnb + nb) * u_chunk), 0, 16 * WN * WK * 4, 0x00020000);
             float* up = smem + V_FLOATS + tid * 4;
             WINO_U_LD4(0)
+            WINO_U_ST2(ub0, ub1, 0) WINO_U_ST2(ub2, ub3, 2)
+            WINO_U_LD4(4)
+            WINO_U_ST2(ub0, ub1, 4) WINO_U_ST2(ub2, ub3, 6)
+        }
+        if (half == 0) {
             read_rows(0, 0);
             read_rows(2, 0);
 #pragma unroll
@@ -273,13 +276,10 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
 #pragma unroll
             for (int j = 0; j < 4; ++j) bt_col(j);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) b_row(i, smem + vdst, true);
-            WINO_U_ST2(ub0, ub1, 0) WINO_U_ST2(ub2, ub3, 2)
-            WINO_U_LD4(4)
-            WINO_U_ST2(ub0, ub1, 4) WINO_U_ST2(ub2, ub3, 6)
-            advance(u_kd, u_cc, u_left, 1);
-            load_x(tsc, tsh, u_cc);                  // chunk 1's
+            for (int i = 0; i < 4; ++i) b_row(i, smem + vdst);
         }
+        advance(u_kd, u_cc, u_left, 1);              // (both halves walk the U list: half 0 takes its on-load constants from it)
+        if (half == 0) load_x(tsc, tsh, u_cc);       // chunk 1's
     }
     __syncthreads();
     WINO_STAMP(1, __builtin_amdgcn_s_memrealtime());
@@ -287,29 +287,33 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
     // A wave's fp32 MFMA holds its issue slot for the whole 64 cycles: measured on the one-wave-per-SIMD form of this kernel,
     // the issue time of EVERY other instruction of the wave simply added to the MFMA time (4293 cycles per chunk with nothing
     // but MFMAs and fragment reads, 6039 with the staging: profiles/r04_winograd.txt) -- nothing hides in a lone wave.  So a
-    // SIMD holds TWO waves: wave w (half 0) runs 32 MFMAs per chunk and ALL of the staging, wave w + 4 (half 1) runs the other
-    // 32 MFMAs and nothing else; while the one stages, the other's MFMAs keep the pipe busy.  The compiler left alone puts the
-    // whole transform in front of the MFMAs and the loads behind them, so the stager's chunk is cut by hand into 8 groups of
-    // one transform point (two fragment reads, four MFMAs), each carrying two
-    // slices p of the side work for chunk c + 1, pinned by sched_barrier:
+    // SIMD holds TWO waves, 32 MFMAs per chunk each, and the side work for chunk c + 1 is split between them by kind (role
+    // bits of chunk(): 1 transform, 2 with the gate, 4 move): wave w (half 0) reads,
+    // gates and transforms the patches and stores V, wave w + 4 (half 1) carries everything that only passes through registers
+    // on its way from global memory to LDS (window, U image: no VALU, no dependence on the transform) and owns the walks and
+    // buffer descriptors for it.  (Until profiles/wino_staging_ab.txt half 0 did all of it and half 1 waited at the barrier.)
+    // The compiler left alone puts the whole side work in front of the MFMAs and the loads behind them, so each wave's chunk
+    // is cut by hand into 8 groups of one transform point (two fragment reads, four MFMAs), each carrying two slices p of its
+    // side work, pinned by sched_barrier.  Half 0:
     //   p 0-1    the thread's 4 x 4 patch: two rows (eight 8-byte reads from the window) per slice, gated two slices later --
     //            the side work alone is LATENCY-bound (4400 cycles per chunk with read-then-use slices and no MFMA at all)
-    //   p 0, 8   four 16-byte loads of one half of the U image of chunk c + 1;  p 6-7, 14-15  their stores, two per slice
-    //   p 1-2    EVEN chunks: three 16-byte loads each of the window's next 16 channels;  p 12-13  their stores.  The window
-    //            is single: an even chunk reads its second half (p 0-1), ALL waves meet at a barrier after group 3 (p 7), and
-    //            only then is it overwritten; the odd chunk that follows reads the new window after the barrier that ends
-    //            the even one
     //   p 2-5    gate (+ BatchNormalization, ReLU) of patch row i;  p 6  the on-load constants of chunk c + 2
     //   p 6-9    B^T d (column j)
     //   p 10-13  (B^T d) B (row i) and its four 8-byte stores into the other stage
+    // Half 1:
+    //   p 0, 8   four 16-byte loads of one half of the U image of chunk c + 1;  p 6-7, 14-15  their stores, two per slice
+    //   p 1, 9   EVEN chunks: three 16-byte loads each of the window's next 16 channels;  p 8, 15  their stores.  The window
+    //            is single: an even chunk's transform reads its second half (half 0, p 0-1), ALL waves meet at a barrier
+    //            after group 3 (p 7), and only then does half 1 overwrite it; the odd chunk that follows reads the new window
+    //            after the barrier that ends the even one
 #define WINO_MFMA4(P_)                                                                                   \
     acc[P_] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, b0.x, acc[P_], 0, 0, 0);                            \
     acc[P_] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, b0.y, acc[P_], 0, 0, 0);                            \
     acc[P_] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, b0.z, acc[P_], 0, 0, 0);                            \
     acc[P_] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, b0.w, acc[P_], 0, 0, 0);
-    auto chunk = [&](auto par_tag, auto stager_tag) {
-        constexpr int PAR = decltype(par_tag)::value;
-        constexpr bool STAGER = (decltype(stager_tag)::value & 1) != 0, GATE = (decltype(stager_tag)::value & 2) != 0;
+    auto chunk = [&](auto par_tag, auto role_tag) {
+        constexpr int PAR = decltype(par_tag)::value, ROLE = decltype(role_tag)::value;
+        constexpr bool XFORM = (ROLE & 1) != 0, GATE = (ROLE & 2) != 0, MOVE = (ROLE & 4) != 0;
         const float* st = smem + PAR * STAGE_FLOATS;
         float* nx = smem + (PAR ^ 1) * STAGE_FLOATS;
         const float* ap = st + aoff;
@@ -319,7 +323,7 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
         const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<float*>(U + ((size_t)(u_kd * ncc + u_cc) * nnb + nb) * u_chunk), 0, 16 * WN * WK * 4, 0x00020000);
         float* up = nx + V_FLOATS + tid * 4;
-        const float* wsrc = STAGER ? window_src() : in;
+        const float* wsrc = MOVE ? window_src() : in;
         // (a buffer descriptor over the plane: scalar base + one 32-bit lane offset per load, no 64-bit lane addresses)
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wsrc), 0, 0x7fffffff, 0x00020000);
         const int x_next = (u_left > 0) ? (u_cc + 1 == ncc ? 0 : u_cc + 1) : u_cc;      // channel chunk of chunk c + 2
@@ -331,31 +335,37 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
                 a0n = *reinterpret_cast<const float4*>(ap + (pp + 1) * (WT * WK));
                 b0n = *reinterpret_cast<const float4*>(bp + (pp + 1) * (WN * WK));
             }
-            if (STAGER && EXP != 1) {
+            if (EXP != 1) {
 #pragma unroll
                 for (int p = 2 * pp; p < 2 * pp + 2; ++p) {
-                    if (p == 0) WINO_U_LD4(0)
-                    if (p == 0) read_rows(0, PAR ^ 1);           // chunk c + 1 is the OTHER half of the window's 16 channels
-                    if (p == 1) read_rows(2, PAR ^ 1);
-                    if (PAR == 0) {
+                    if (MOVE && p == 0) WINO_U_LD4(0)
+                    if (XFORM) {
+                        if (p == 0) read_rows(0, PAR ^ 1);       // chunk c + 1 is the OTHER half of the window's 16 channels
+                        if (p == 1) read_rows(2, PAR ^ 1);
+                    }
+                    if (MOVE && PAR == 0) {
                         if (p == 1) { WINO_R_LD(rw0, 0); WINO_R_LD(rw1, 1); WINO_R_LD(rw2, 2); }
                         if (p == 8) { WINO_R_ST(rw0, 0); WINO_R_ST(rw1, 1); WINO_R_ST(rw2, 2); }      // (behind the barrier)
                         if (p == 9) { WINO_R_LD(rw0, 3); WINO_R_LD(rw1, 4); WINO_R_LD(rw2, 5); }
                         if (p == 15) { WINO_R_ST(rw0, 3); WINO_R_ST(rw1, 4); WINO_R_ST(rw2, 5); }
                     }
-                    if (p >= 2 && p < 6) gate_row(p - 2, tsc, tsh, GATE);       // (chunk c + 1's constants)
-                    if (p == 6) load_x(tsc, tsh, x_next);                       // chunk c + 2's, once the gate is through
-                    if (p >= 6 && p < 10) bt_col(p - 6);
-                    if (p >= 10 && p < 14) b_row(p - 10, vp, true);
-                    if (p == 6) WINO_U_ST2(ub0, ub1, 0)
-                    if (p == 7) WINO_U_ST2(ub2, ub3, 2)
-                    if (p == 8) WINO_U_LD4(4)
-                    if (p == 14) WINO_U_ST2(ub0, ub1, 4)
-                    if (p == 15) WINO_U_ST2(ub2, ub3, 6)
+                    if (XFORM) {
+                        if (p >= 2 && p < 6) gate_row(p - 2, tsc, tsh, GATE);   // (chunk c + 1's constants)
+                        if (p == 6) load_x(tsc, tsh, x_next);                   // chunk c + 2's, once the gate is through
+                        if (p >= 6 && p < 10) bt_col(p - 6);
+                        if (p >= 10 && p < 14) b_row(p - 10, vp);
+                    }
+                    if (MOVE) {
+                        if (p == 6) WINO_U_ST2(ub0, ub1, 0)
+                        if (p == 7) WINO_U_ST2(ub2, ub3, 2)
+                        if (p == 8) WINO_U_LD4(4)
+                        if (p == 14) WINO_U_ST2(ub0, ub1, 4)
+                        if (p == 15) WINO_U_ST2(ub2, ub3, 6)
+                    }
                 }
             }
-            if (!((EXP == 4 && !STAGER) || (EXP == 5 && STAGER))) { WINO_MFMA4(pp) }
-            if (STAGER) {
+            if (!((EXP == 4 && MOVE) || (EXP == 5 && XFORM))) { WINO_MFMA4(pp) }
+            {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
@@ -368,9 +378,9 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
             if (PAR == 0 && pp == 3 && EXP != 1) __syncthreads();      // every wave has read the window's second half
             a0 = a0n; b0 = b0n;
         }
-        if (STAGER && EXP != 6) {                    // (EXP 6: the walks stand still -- what the scalar work costs)
-            advance(u_kd, u_cc, u_left, 1);
-            if (PAR == 0) advance(w_kd, w_cc, w_left, 2);
+        if (EXP != 6) {                              // (EXP 6: the walks stand still -- what the scalar work costs)
+            advance(u_kd, u_cc, u_left, 1);          // (half 0 too: its on-load constants follow the U list)
+            if (MOVE && PAR == 0) advance(w_kd, w_cc, w_left, 2);
         }
         __syncthreads();
     };
@@ -386,8 +396,8 @@ k_wino(ConvGeom g, int mode, const float* __restrict__ in, const float* __restri
         }
     } else {
         for (int c = 0; c < nchunks; c += 2) {
-            chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-            chunk(std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{});
+            chunk(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
+            chunk(std::integral_constant<int, 1>{}, std::integral_constant<int, 4>{});
         }
     }
 #undef WINO_MFMA4
@@ -731,8 +741,6 @@ extern "C" int lisec_conv_forward_winograd(const lisec_conv_geom* c, const float
         if (!nslots) continue;
         dim3 grid(nslots * BH * BW, nnb, 1);
         if (exp == 1) LISEC_WINO_GO(false, 1);
-        else if (exp == 2) LISEC_WINO_GO(false, 2);
-        else if (exp == 3) LISEC_WINO_GO(false, 3);
         else if (exp == 4) LISEC_WINO_GO(false, 4);
         else if (exp == 5) LISEC_WINO_GO(false, 5);
         else if (exp == 6) LISEC_WINO_GO(false, 6);
