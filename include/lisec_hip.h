@@ -903,6 +903,19 @@ int lisec_rpn_labels(const lisec_rpn_cfg* cfg, const double* fixed_boxes, int n_
                      void* workspace, size_t workspace_bytes, double* valid, double* overlap, double* out_regress,
                      lisec_stream_t stream);
 
+/* calcIntersectAll / calcUnionAll (rpnToRegion.py:202-222), the score of rpnToRegion.py:253-255, for n_samples samples in
+ * one launch.  Sample s owns rows pred_start[s] .. pred_start[s+1] of pred_boxes and label_start[s] .. label_start[s+1]
+ * of label_boxes (device int32[n_samples+1], device double[rows*7]); a footprint is boxToShapely's quadrilateral
+ * (serialize_data.py:151-163) in whatever orientation it comes, a box with l == 0 or w == 0 has none.
+ * out: device double[n_samples*5] = {area((U pred) n (U label)) (the reference's cascaded_union(...).intersection(...).area,
+ * :207-213), area(U pred), area(U label), sum of pred l*w*h, sum of label l*w*h (predictSum, annsSum of :216-221)}.
+ * Exact float64 geometry (a boundary integral over the rectangle edges), summed in a fixed order: bit-identical from run
+ * to run.  The workspace is not needed today (0 bytes; NULL is accepted). */
+size_t lisec_boxes_union_overlap_workspace_bytes(int n_samples, int max_pred, int max_label);
+int lisec_boxes_union_overlap(const double* pred_boxes, const int32_t* pred_start, const double* label_boxes,
+                              const int32_t* label_start, int n_samples, void* workspace, size_t workspace_bytes,
+                              double* out, lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 5b. Step plans: a whole training step recorded once and re-issued by ONE call (csrc/plan.hip).
  *     The reference repeats one static schedule 180 times (model.fit(batch_size=1, steps_per_epoch=180),

@@ -28,6 +28,35 @@ def predictMain(samples, outPath, level5Data, model, dataDir=None):
         np.save(os.path.join(outPath, 'sample' + str(i) + '_regress.npy'), regress)
 
 
+def scoreMain(samples, level5Data, model, dataDir=None):
+    """The check at the end of the reference's rpnToRegion.py (:276-295) for a list of samples, without leaving the
+    device in between: predict, decode + NMS on the head views (boxes.rpnToRegion), the shift to ego-centred metres
+    (:279-280), and ONE launch that scores every sample against its car annotations (boxes.union_overlap).
+    Returns [(reference IoU, bird's-eye IoU)] per sample: calcIoUAll's area / (sum of volumes - area), and
+    boxes.bev_iou's area / area, which is ours."""
+    import torch
+    from . import boxes
+    dataDir = dataDir if dataDir is not None else Constants.lyft_data_dir
+    found, counts, labels = [], [], []
+    for sample in samples:
+        points = combine_lidar_data(sample, dataDir, level5Data)
+        vfe = VFE_preprocessing(points, Constants.voxelx, Constants.voxely, Constants.voxelz, Constants.maxPoints,
+                                Constants.nx // 2, Constants.ny // 2, Constants.nz)
+        for s in model._as_samples(vfe):
+            cls, reg = model.net.forward(s, training=False)
+            b, _, count = boxes.rpnToRegion(cls[0], reg[0], as_device=True)     # before the next forward reuses the head
+            b[:, 0] -= 50
+            b[:, 1] -= 50
+            found.append(b)
+            counts.append(count)
+        labels.append(boxes.annotationBoxes(sample, level5Data))
+    if not found:
+        return []
+    counts = torch.cat(counts).cpu().tolist()
+    out = boxes.union_overlap([b[:k] for b, k in zip(found, counts)], labels)
+    return [(float(r[0]) / (float(r[3]) + float(r[4]) - float(r[0])), boxes._bev(r)) for r in out]
+
+
 if __name__ == '__main__':
     # python -m lisec_amd.Predict [model.h5] [outPath]      (Predict.py:43-59)
     import sys

@@ -146,6 +146,10 @@ def _declare(lib):
     lib.lisec_rpn_labels_workspace_bytes.argtypes = [c_int]
     lib.lisec_rpn_labels.restype = c_int
     lib.lisec_rpn_labels.argtypes = [POINTER(RpnCfg), P, c_int, c_double, c_double, P, c_size_t, P, P, P, P]
+    lib.lisec_boxes_union_overlap_workspace_bytes.restype = c_size_t
+    lib.lisec_boxes_union_overlap_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.lisec_boxes_union_overlap.restype = c_int
+    lib.lisec_boxes_union_overlap.argtypes = [P, P, P, P, c_int, P, c_size_t, P, P]
     lib.lisec_lidar_transform.restype = c_int
     lib.lisec_lidar_transform.argtypes = [P, c_int, c_int, POINTER(c_double), POINTER(c_double), P, P]
     lib.lisec_vfe_grid_from_saved.restype = c_int

@@ -21,7 +21,7 @@ def _cfg():
     return c
 
 
-def rpnToRegion(labelsClass, labelsRegress, maxBoxes=20, overlapThresh=0.):
+def rpnToRegion(labelsClass, labelsRegress, maxBoxes=20, overlapThresh=0., as_device=False):
     """rpnToRegion(labelsClass (100,200,2), labelsRegress (100,200,14)) -> (boxes (k,7), probs (k,))
     (rpnToRegion.py:113-164; the reference hard-codes maxBoxes=20, overlapThresh=0.).  Inputs may be numpy
     arrays or device tensors (e.g. views of LisecNet's head buffer).  Probability ties pick the larger flat
@@ -29,7 +29,9 @@ def rpnToRegion(labelsClass, labelsRegress, maxBoxes=20, overlapThresh=0.):
     Deviation from the reference, on purpose: nonMaxSuppressionFast deletes the suppressed candidates with
     np.delete(idxs, toDelete) where toDelete holds box INDICES (rpnToRegion.py:66-67) -- a positional delete that
     removes unrelated entries and raises IndexError on numpy >= 1.19 for any realistic map.  Here the boxes found to
-    overlap (IoU > overlapThresh) or to lie out of range are the ones suppressed (by value)."""
+    overlap (IoU > overlapThresh) or to lie out of range are the ones suppressed (by value).
+    as_device=True returns (boxes (maxBoxes+1,7), probs (maxBoxes+1,), count (1,) int32) as device tensors, the first `count`
+    rows valid, without waiting for the GPU: what a caller that keeps scoring on the device (Predict.scoreMain) wants."""
     dev = _lib.require_gpu()
     lib = _lib.load()
     cfg = _cfg()
@@ -46,6 +48,8 @@ def rpnToRegion(labelsClass, labelsRegress, maxBoxes=20, overlapThresh=0.):
     _lib.check(lib.lisec_rpn_to_region(ctypes.byref(cfg), _lib.ptr(cls), cls.stride(1), _lib.ptr(reg), reg.stride(1),
                                        float(overlapThresh), int(maxBoxes), _lib.ptr(ws), ws.numel(), _lib.ptr(boxes),
                                        _lib.ptr(probs), _lib.ptr(count), _lib.current_stream()))
+    if as_device:
+        return boxes, probs, count
     k = int(count.item())
     return boxes[:k].cpu().numpy(), probs[:k].cpu().numpy()
 
@@ -100,3 +104,98 @@ def quaternion_yaw(q):
     n = math.sqrt(w * w + x * x + y * y + z * z)
     w, x, y, z = w / n, x / n, y / n, z / n
     return math.atan2(2 * (w * z - x * y), 1 - 2 * (y * y + z * z))
+
+
+# ---- scoring detections against annotations (rpnToRegion.py:202-255) ---------------------------------------------------
+def _pack(box_list, dev):
+    """[(k_s, 7) arrays or device tensors] -> (device (max(rows, 1), 7) float64, device int32 (S+1,) row offsets)."""
+    rows = [b.to(device=dev, dtype=torch.float64).reshape(-1, 7) if torch.is_tensor(b)
+            else torch.from_numpy(np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1, 7))) for b in box_list]
+    start = np.zeros(len(rows) + 1, dtype=np.int32)
+    start[1:] = np.cumsum([len(r) for r in rows])
+    if all(not r.is_cuda for r in rows):                       # host lists: one upload
+        flat = torch.cat(rows + [torch.zeros((1, 7), dtype=torch.float64)]).to(dev)
+    else:
+        flat = torch.cat([r.to(dev) for r in rows] + [torch.zeros((1, 7), dtype=torch.float64, device=dev)])
+    return flat, torch.from_numpy(start).to(dev)
+
+
+def union_overlap(pred_list, label_list):
+    """For S samples at once -- pred_list[s], label_list[s]: (k, 7) rows x,y,z,l,w,h,yaw, numpy or device tensors --
+    returns (S, 5) float64: area((U pred) n (U label)), area(U pred), area(U label), sum of pred l*w*h, sum of label l*w*h
+    (lisec_boxes_union_overlap).  One launch and one device-to-host copy for the whole list."""
+    if len(pred_list) != len(label_list):
+        raise ValueError("union_overlap needs one label set per prediction set")
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    S = len(pred_list)
+    pred, pred_start = _pack(pred_list, dev)
+    label, label_start = _pack(label_list, dev)
+    out = torch.empty((S, 5), dtype=torch.float64, device=dev)
+    nbytes = lib.lisec_boxes_union_overlap_workspace_bytes(S, int(pred.shape[0]), int(label.shape[0]))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    _lib.check(lib.lisec_boxes_union_overlap(_lib.ptr(pred), _lib.ptr(pred_start), _lib.ptr(label), _lib.ptr(label_start),
+                                             S, _lib.ptr(ws), nbytes, _lib.ptr(out), _lib.current_stream()))
+    return out.cpu().numpy()
+
+
+def calcIntersectAll(boxBoxes, annsBoxes):
+    """calcIntersectAll (rpnToRegion.py:202-213): the AREA of (union of the predicted footprints) n (union of the annotated
+    ones) -- cascaded_union(...).intersection(cascaded_union(...)).area there, a GPU boundary integral here."""
+    return float(union_overlap([boxBoxes], [annsBoxes])[0, 0])
+
+
+def calcUnionAll(boxesBoxes, annsBoxes, intersect):
+    """calcUnionAll (rpnToRegion.py:215-222), literally: the sum of the box VOLUMES of both sides minus `intersect` (which
+    calcIoUAll passes as an area -- the reference's quirk, kept)."""
+    annsSum = 0
+    for box in annsBoxes:
+        annsSum += box[3] * box[4] * box[5]
+    predictSum = 0
+    for box in boxesBoxes:
+        predictSum += box[3] * box[4] * box[5]
+    return annsSum + predictSum - intersect
+
+
+def _host_rows(b):
+    return b.detach().cpu().numpy() if torch.is_tensor(b) else np.asarray(b, dtype=np.float64).reshape(-1, 7)
+
+
+def calcIoUAll_boxes(predictBoxes, labelBoxes):
+    """The last three lines of calcIoUAll (rpnToRegion.py:253-255) on two box tables: intersect / union with the
+    reference's mixed units (area over volumes).  Both sides empty: ZeroDivisionError, as the reference's 0.0 / 0."""
+    predictBoxes, labelBoxes = _host_rows(predictBoxes), _host_rows(labelBoxes)
+    intersect = calcIntersectAll(predictBoxes, labelBoxes)
+    union = calcUnionAll(predictBoxes, labelBoxes, intersect)
+    return intersect / union                                   # both empty: 0.0 / 0.0 of Python floats raises
+
+
+def _bev(row):
+    union = row[1] + row[2] - row[0]
+    return float(row[0] / union) if union > 0 else 0.0
+
+
+def bev_iou(predictBoxes, labelBoxes):
+    """Bird's-eye IoU of the two box sets: area((U pred) n (U label)) / area((U pred) u (U label)); 0.0 when both sides are
+    empty.  This one is OURS, not the reference's: calcIoUAll divides the same area by a sum of volumes."""
+    return _bev(union_overlap([predictBoxes], [labelBoxes])[0])
+
+
+def annotationBoxes(sample, dataset):
+    """The label rows of calcIoUAll (rpnToRegion.py:225-251): the sample's annotations moved from global to ego
+    coordinates (translate, then the inverse ego rotation), rows [x, y, z, *size, yaw], cars inside the closed +-50 m
+    window only.  Returns (k, 7) float64.  `dataset` is anything with LyftDataset's get(table, token)."""
+    from .model_training import rotate_points
+    sd = dataset.get('sample_data', sample['data']['LIDAR_TOP'])
+    ego = dataset.get('ego_pose', sd['ego_pose_token'])
+    labels = []
+    for token in sample['anns']:
+        ann = dataset.get('sample_annotation', token)
+        t = np.array(ann['translation'], dtype=np.float64).reshape(1, -1) - np.array(ego['translation'])
+        t = rotate_points(t, np.array(ego['rotation']), True)
+        row = [t[0, 0], t[0, 1], t[0, 2]] + list(ann['size']) + [quaternion_yaw(ann['rotation'])]
+        instance = dataset.get('instance', ann['instance_token'])
+        category = dataset.get('category', instance['category_token'])['name']
+        if category == 'car' and row[0] >= -50 and row[0] <= 50 and row[1] >= -50 and row[1] <= 50:
+            labels.append(row)
+    return np.array(labels, dtype=np.float64).reshape(-1, 7)

@@ -50,3 +50,23 @@ if __name__ == "__main__":
     pi = np.concatenate([cls[0, :, :, a].reshape(-1) for a in range(2)]).astype(np.float64)
     B.nms(bi[:4000], pi[:4000], maxBoxes=20)
     print(f"nms   4 000 candidates (a tenth), maxBoxes 20   CPU oracle  {time.perf_counter() - t0:8.2f} s")
+    # scoring (rpnToRegion.py:202-255): 1000 samples of 20 predictions x 40 labels in one launch, and one sample alone
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from union_overlap_ref import clustered_scene
+
+    def median7(fn):
+        fn()
+        ts = []
+        for _ in range(7):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            ts.append(time.perf_counter() - t0)
+        return sorted(ts)[3]
+    scenes = [clustered_scene(rng, 20, 40, 10) for _ in range(1000)]
+    dev_p = [torch.from_numpy(p).cuda() for p, _ in scenes]
+    dev_l = [torch.from_numpy(l).cuda() for _, l in scenes]
+    t = median7(lambda: boxes.union_overlap(dev_p, dev_l))
+    print(f"union_overlap  1000 samples x (20 pred, 40 label), one launch   GPU {t * 1e3:8.2f} ms  (median of 7, incl. packing + copy back)")
+    t = median7(lambda: boxes.union_overlap(dev_p[:1], dev_l[:1]))
+    print(f"union_overlap  1 sample (20 pred, 40 label)                     GPU {t * 1e3:8.3f} ms  (median of 7)")
