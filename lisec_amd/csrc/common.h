@@ -16,6 +16,7 @@ constexpr int kWave = 64;  // CDNA4 wavefront
 
 void set_error(const char* fmt, ...);
 const lisec_tuning& tuning();      // the process-wide launch-plan knobs (core.hip; lisec_tuning_set)
+int cu_count();                    // compute units of the current device, asked once per process; 256 without a device
 
 #define LISEC_CHECK_ARG(cond, ...)                 \
     do {                                           \

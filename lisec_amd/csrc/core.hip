@@ -15,6 +15,18 @@ void set_error(const char* fmt, ...) {
 
 static lisec_tuning g_tuning = {(int)sizeof(lisec_tuning), 12, 3, 2, 1, 1, 1, -1, 0, 0, 1024, 0, 0, 32, 1024, 1, 2, 1, 0, 0};
 const lisec_tuning& tuning() { return g_tuning; }
+
+int cu_count() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0, v = 0;
+        cus = 256;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+            cus = v;
+    }
+    return cus;
+}
 }  // namespace lisec
 
 extern "C" int lisec_tuning_get(lisec_tuning* t) {

@@ -1520,16 +1520,7 @@ extern "C" int lisec_conv_num_mblocks_bwd(const lisec_conv_geom* c) {
 
 namespace {
 int resident_slots() {
-    static int slots = 0;
-    if (!slots) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-        slots = 3 * cus;         // 51 KB LDS per workgroup -> 3 per CU
-    }
-    return slots;
+    return 3 * cu_count();       // 51 KB LDS per workgroup -> 3 per CU
 }
 
 // k_dense64 with the Dense weight gradient beside the data gradient holds 64 more accumulators: two workgroups per CU

@@ -254,18 +254,6 @@ struct Bf16Plan {
     size_t ws_bytes;
 };
 
-int cu_count() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, v = 0;
-        cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-    }
-    return cus;
-}
-
 // K slices: a layer with fewer than one workgroup per CU is cut until ~3 workgroups per CU exist, no slice shorter than
 // three steps; the workspace on offer caps the count (a smaller workspace only means fewer slices, never another path)
 int plan_bf16(const lisec_conv_geom* c, size_t workspace_bytes, bool sizing, Bf16Plan* p) {

@@ -11,6 +11,9 @@
 // 32x32 accumulator per tap for its whole M range and writes it once to a partial slab
 // [S][tap][Cin][Cout]; a second kernel sums the S slabs in index order (deterministic, no atomics)
 // into the Keras kernel layout.
+// Host side (end of the file): plan_wgrad decides the kernel and its launches from the geometry and the flags alone,
+// bind_wgrad puts the tensors and the workspace in, run_wgrad issues them; the plan query and the workspace sizes read
+// the same plan.
 #include "conv.h"
 
 
@@ -972,147 +975,88 @@ k_wgrad_reduce_lanes(const float* __restrict__ partial, int nsplit, int ntaps, i
     }
 }
 
-struct WgradPlan {
-    int TG, ngroups, nsplit, tiles_per_split, ntiles;
-    int LT;              // halo kernel: rows per tile
-    bool halo;
-    bool combine;        // halo kernel: few slices per cell -> the last one to arrive sums the slabs and writes dW
-    size_t ws_bytes, slab_bytes;
-    LiveGroups live;     // halo kernel: the (kd, kh) groups that get workgroups
+// ---- host side: plan, bind, run ---------------------------------------------------------------------------------------
+// plan_wgrad decides everything a weight-gradient call does before a tensor is known: the kernel (ring, then w-halo, then
+// plain), its argument struct, the launch and the slab sum that follows it.  bind_wgrad puts the tensors and the
+// workspace placement into that plan and run_wgrad issues it.  lisec_conv_wgrad, the batched entry, the workspace sizes
+// and lisec_conv_wgrad_plan_query all read the same WgradCall, so a query reports the plan a call WILL run.
+using PlainKernel = decltype(&k_wgrad<0, 1, false>);
+using HaloKernel = decltype(&k_wgrad_halo<false, 7>);
+using HaloBatchKernel = decltype(&k_wgrad_halo_batch<false, 7>);
+using RingKernel = decltype(&k_wgrad_ring<false, 3>);
+using RingBatchKernel = decltype(&k_wgrad_ring_batch<false, 3>);
+
+struct WgradCall {
+    enum Kind { RING, HALO, PLAIN } kind;        // the order they are tried in
+    enum Reduce { NONE, RING_SUM, LANE_SUM, SLAB_SUM };
+    // the kernel's argument, pointers still empty: RING takes `ring`, HALO takes `it`, PLAIN takes it.g, the operands and
+    // the slab split of `it`, and dy_bn, one by one
+    RingItem ring;
+    WgradItem it;
+    const float* dy_bn;
+    bool xf;                     // the instantiation: BatchNormalization / ReLU on load, ...
+    int np;                      // ... staging passes (ring: 48 rows; halo: 16 rows; plain: its 8 passes of 16 rows)
+    bool mirrored;               // a unit-stride transposed gather run as the plain one with mirrored taps and pads
+    union { RingKernel ring_fn; HaloKernel halo_fn; PlainKernel plain_fn; };
+    dim3 grid, block;
+    size_t lds;
+    Reduce reduce;               // the launch that sums the slabs (NONE: the kernel combines in place)
+    dim3 reduce_grid;
+    unsigned long long dead_taps;    // taps whose groups got no workgroups: the slab sum writes zeros
+    int cells;                   // arrival counters used
+    size_t slab_bytes, ws_bytes; // workspace = [kWgradCounters arrival counters][slabs]
+    // what lisec_conv_wgrad_plan_query reports beside the launches (slabs / tiles_per_slab: the split of the M tiles)
+    int taps_per_group, groups, tile_rows, tiles, slabs, tiles_per_slab, lines_per_run;
 };
 
-WgradPlan make_plan(const ConvGeom& g, int mode = 0, bool dy_xf = false, int blocks_target = 0) {
-    WgradPlan p;
-    p.combine = false;
-    p.TG = g.KW <= 4 ? g.KW : 1;
-    if (g.KW % p.TG) p.TG = 1;
-    p.ngroups = g.KD * g.KH * (g.KW / p.TG);
-    p.ntiles = cdiv(g.M, BMW);
-    // 3 taps along w at stride 1 over every position of the map: the halo kernel (tiles follow the output lines)
-    p.halo = mode == 0 && g.KW == 3 && g.ls_w == 0 && !g.row_coords && !dy_xf && g.Wo >= 8;
-    p.live.n = 0;
-    if (p.halo) {
-        p.TG = 3;
-        p.LT = cdiv(g.Wo, cdiv(g.Wo, BMW));         // equal tiles per line
-        p.ntiles = g.Do * g.Ho * cdiv(g.Wo, p.LT);
-        for (int kd = 0; kd < g.KD; ++kd) {
-            bool dlive = false;
-            for (int d = 0; d < g.Do && !dlive; ++d) { const int sd = (d << g.ls_d) - g.pd + kd; dlive = sd >= 0 && sd < g.Di; }
-            for (int kh = 0; kh < g.KH; ++kh) {
-                bool hlive = false;
-                for (int h = 0; h < g.Ho && !hlive; ++h) { const int sh = (h << g.ls_h) - g.ph + kh; hlive = sh >= 0 && sh < g.Hi; }
-                if (dlive && hlive && p.live.n < 16) p.live.id[p.live.n++] = (unsigned char)(kd * g.KH + kh);
-            }
-        }
-        p.ngroups = p.live.n > 0 ? p.live.n : 1;
+// ---- the instantiations.  These selectors name every kernel the file compiles and no other.
+RingKernel ring_kernel(bool xf, int np) {
+    switch (np) {
+    case 3: return xf ? k_wgrad_ring<true, 3> : k_wgrad_ring<false, 3>;
+    case 5: return xf ? k_wgrad_ring<true, 5> : k_wgrad_ring<false, 5>;
     }
-    int cb = cdiv(g.Cin, BC), nb = cdiv(g.Cout, BC);
-    int base = p.ngroups * cb * nb;
-    const int target = blocks_target > 0 ? blocks_target : tuning().wgrad_blocks;
-    int want = cdiv(target, base);              // 1024: ~2 rounds of the 512 resident workgroups (measured: 512-1024 blocks
-                                                // beat 1536+, whose extra slabs cost more in the reduce than they balance)
-    if (want < 1) want = 1;
-    if (want > p.ntiles) want = p.ntiles;
-    p.tiles_per_split = cdiv(p.ntiles, want);
-    p.nsplit = cdiv(p.ntiles, p.tiles_per_split);
-    // every plan keeps the head of the workspace (kWgradCounters arrival counters) free, so that the counters of the
-    // combining plans stay zero whatever else shares the workspace; p.slab_bytes = what follows the head
-    p.slab_bytes = align_up(sizeof(float) * (size_t)p.nsplit * g.KD * g.KH * g.KW * g.Cin * g.Cout, 256);
-    p.ws_bytes = sizeof(int) * kWgradCounters + p.slab_bytes;
-    if (p.halo && p.nsplit <= tuning().wgrad_combine_max && g.KD * g.KH <= 16 &&
-        (long long)g.KD * g.KH * cb * nb <= kWgradCounters) {
-        // few slices per cell: combined inside the kernel (every group gets workgroups: the cells of a group that reads
-        // nothing must still be written, as zeros)
-        p.combine = true;
-        p.live.n = g.KD * g.KH;
-        for (int i = 0; i < p.live.n; ++i) p.live.id[i] = (unsigned char)i;
-        p.ngroups = p.live.n;
-        p.slab_bytes = align_up((size_t)p.nsplit * p.ngroups * cb * nb * kWSlabF4 * 16, 256);
-        p.ws_bytes = sizeof(int) * kWgradCounters + p.slab_bytes;
+    return xf ? k_wgrad_ring<true, 6> : k_wgrad_ring<false, 6>;
+}
+RingBatchKernel ring_kernel_batch(bool xf, int np) {
+    switch (np) {
+    case 3: return xf ? k_wgrad_ring_batch<true, 3> : k_wgrad_ring_batch<false, 3>;
+    case 5: return xf ? k_wgrad_ring_batch<true, 5> : k_wgrad_ring_batch<false, 5>;
     }
-    return p;
+    return xf ? k_wgrad_ring_batch<true, 6> : k_wgrad_ring_batch<false, 6>;
+}
+HaloKernel halo_kernel(bool xf, int np) {
+    if (np == 7) return xf ? k_wgrad_halo<true, 7> : k_wgrad_halo<false, 7>;
+    return xf ? k_wgrad_halo<true, 9> : k_wgrad_halo<false, 9>;
+}
+HaloBatchKernel halo_kernel_batch(bool xf, int np) {
+    if (np == 7) return xf ? k_wgrad_halo_batch<true, 7> : k_wgrad_halo_batch<false, 7>;
+    return xf ? k_wgrad_halo_batch<true, 9> : k_wgrad_halo_batch<false, 9>;
+}
+template <int MODE, bool RL>
+PlainKernel plain_kernel_tg(int TG) {
+    switch (TG) {
+    case 1: return k_wgrad<MODE, 1, RL>;
+    case 2: return k_wgrad<MODE, 2, RL>;
+    case 3: return k_wgrad<MODE, 3, RL>;
+    }
+    return k_wgrad<MODE, 4, RL>;
+}
+PlainKernel plain_kernel(int mode, int TG, bool rows) {
+    if (mode == 0) return rows ? plain_kernel_tg<0, true>(TG) : plain_kernel_tg<0, false>(TG);
+    return rows ? plain_kernel_tg<1, true>(TG) : plain_kernel_tg<1, false>(TG);
 }
 
-template <int MODE>
-int launch_wgrad(const ConvGeom& g, const WgradPlan& p, const float* in, const float* in_bn, int flags,
-                 const float* dy, const float* dy_bn, float* partial, hipStream_t st) {
-    dim3 grid(p.nsplit * p.ngroups, cdiv(g.Cin, BC), cdiv(g.Cout, BC));
-    const size_t lds = 2 * TILE_FLOATS * sizeof(float);
-#define LISEC_WG(T)                                                                                               \
-    if (g.row_coords)                                                                                             \
-        LISEC_LAUNCH((k_wgrad<MODE, T, true>), grid, dim3(kThreads), lds, st, g, in, in_bn, flags, dy, dy_bn, \
-                           p.nsplit, p.tiles_per_split, partial);                                                 \
-    else                                                                                                          \
-        LISEC_LAUNCH((k_wgrad<MODE, T, false>), grid, dim3(kThreads), lds, st, g, in, in_bn, flags, dy, \
-                                       dy_bn, p.nsplit, p.tiles_per_split, partial)
-    switch (p.TG) {
-        case 1: LISEC_WG(1); break;
-        case 2: LISEC_WG(2); break;
-        case 3: LISEC_WG(3); break;
-        default: LISEC_WG(4); break;
-    }
-#undef LISEC_WG
-    LISEC_LAUNCH_CHECK();
-    return 0;
-}
+int ring_slots() { return tuning().wgrad_ring_slots > 0 ? tuning().wgrad_ring_slots : cu_count(); }   // one ring workgroup per CU
 
-}  // namespace
-}  // namespace lisec
-
-using namespace lisec;
-
-namespace {
-// A halo-kernel call made ready: geometry (mirrored if need be), plan, the item the kernel takes.
-struct HaloCall { WgradItem it; WgradPlan p; bool xf; int np; unsigned long long dead_taps; };
-
-// returns 0 and fills `hc` when the contraction runs on the halo kernel; 1 when it does not; < 0 on error
-int prepare_halo(const lisec_conv_geom* c, const float* in, const float* in_bnstate, int flags, const float* dy,
-                 const float* dy_bnstate, int transpose_out, float* dW, bool has_rows, int blocks_target, HaloCall* hc) {
-    ConvGeom& g = hc->it.g;
-    if (int rc = conv_geom_check(c, &g)) return rc;
-    const bool dy_xf = dy_bnstate != nullptr || (flags & LISEC_CONV_DY_RELU);
-    // a transposed gather with unit strides is the plain gather with mirrored taps and pads K-1-p: the halo kernel
-    // serves it (first deconv: kernel 3, stride 1, 'same')
-    const bool flip = c->mode == 1 && g.ls_d == 0 && g.ls_h == 0 && g.ls_w == 0 && g.KW == 3 && !has_rows && !dy_xf;
-    if (flip) { g.pd = g.KD - 1 - g.pd; g.ph = g.KH - 1 - g.ph; g.pw = g.KW - 1 - g.pw; }
-    if (has_rows) return 1;
-    hc->p = make_plan(g, flip ? 0 : c->mode, dy_xf, blocks_target);
-    if (!hc->p.halo) return 1;
-    const WgradPlan& p = hc->p;
-    WgradItem& it = hc->it;
-    it.in = in; it.in_bn = in_bnstate; it.dy = dy; it.dW = dW;
-    it.flags = flags; it.nsplit = p.nsplit; it.tiles_per_split = p.tiles_per_split; it.flip = flip ? 1 : 0; it.LT = p.LT;
-    it.transpose = transpose_out; it.combine = p.combine ? 1 : 0;
-    it.gx = p.nsplit * p.ngroups; it.gy = cdiv(g.Cin, BC); it.gz = cdiv(g.Cout, BC);
-    it.live = p.live;
-    hc->xf = in_bnstate || (flags & LISEC_CONV_IN_RELU);
-    hc->np = p.LT + 2 <= 7 * 16 ? 7 : 9;
-    hc->dead_taps = 0;
-    unsigned ran = 0;
-    for (int i = 0; i < p.live.n; ++i) ran |= 1u << p.live.id[i];
-    for (int gi = 0; gi < g.KD * g.KH; ++gi) {
-        if ((ran >> gi) & 1) continue;
-        const int kd = gi / g.KH, kh = gi - kd * g.KH;
-        for (int tt = 0; tt < 3; ++tt) {
-            const int tap = flip ? ((g.KD - 1 - kd) * g.KH + (g.KH - 1 - kh)) * g.KW + (2 - tt) : gi * g.KW + tt;
-            hc->dead_taps |= 1ULL << tap;
-        }
-    }
-    return 0;
-}
-
-// workspace = [kWgradCounters arrival counters][slabs]; counter0: first counter of this call, slab_off: bytes into the slabs
-void place_workspace(HaloCall* hc, void* workspace, int counter0, size_t slab_off) {
-    hc->it.counters = static_cast<int*>(workspace) + counter0;
-    hc->it.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + sizeof(int) * kWgradCounters + slab_off);
-}
+// 3 taps along w at stride 1 on a line long enough: the shape the w-halo kernel serves (tiles follow the output lines)
+bool halo_shape(const ConvGeom& g) { return g.KW == 3 && g.ls_w == 0 && g.Wo >= 8; }
 
 // LDS of a halo workgroup.  At LT = 100 that is 53 760 B = 42 of the CU's 128 granules of 1 280 B, and three fit -- which
 // starves the data-gradient chain running beside the weight gradients on the other stream of its 41 granules (measured
 // in the step: 227.7 samples/s with three per CU against 232 with two; alone the three-per-CU launch is 5 % faster).
 // tuning().wgrad_per_cu == 2 (default) therefore asks for 43 granules: two of these + one chain workgroup = 127 of 128.
-size_t halo_lds(const HaloCall& hc) {
-    const int DR = (hc.p.LT + 7) & ~7;
+size_t halo_lds(int LT) {
+    const int DR = (LT + 7) & ~7;
     size_t lds = (size_t)(2 * DR + 2) * BC * sizeof(float);
     // just over a third of 160 KB and not more: LDS is handed out in 1 280-byte granules, 2 x 43 granules leave 53 760 B --
     // room for the 52 224 B of a data-gradient workgroup; a request of 55 637 B (44 granules) left 51 200 and locked the
@@ -1122,38 +1066,14 @@ size_t halo_lds(const HaloCall& hc) {
     return lds;
 }
 
-// ---- ring kernel, host side ------------------------------------------------------------------------------------------
-struct RingCall { RingItem it; bool xf; int np; int lines; size_t slab_bytes, ws_bytes; };
-
-int ring_slots() {
-    if (tuning().wgrad_ring_slots > 0) return tuning().wgrad_ring_slots;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0, v = 0;
-        cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    return cus;                                 // one ring workgroup per CU
-}
-
-// returns 0 and fills `rc` when the contraction runs on the ring kernel; 1 when it does not; < 0 on error.
-// slots: workgroups this call should fill (0: every CU)
-int prepare_ring(const lisec_conv_geom* c, const float* in, const float* in_bnstate, int flags, const float* dy,
-                 const float* dy_bnstate, int transpose_out, float* dW, bool has_rows, int slots, RingCall* rc) {
-    if (!tuning().wgrad_ring || has_rows) return 1;
-    ConvGeom g;
-    if (int e = conv_geom_check(c, &g)) return e;
-    const bool dy_xf = dy_bnstate != nullptr || (flags & LISEC_CONV_DY_RELU);
-    const bool flip = c->mode == 1 && g.ls_d == 0 && g.ls_h == 0 && g.ls_w == 0 && g.KW == 3 && !dy_xf;
-    if (flip) { g.pd = g.KD - 1 - g.pd; g.ph = g.KH - 1 - g.ph; g.pw = g.KW - 1 - g.pw; }
-    if ((c->mode != 0 && !flip) || dy_xf || g.KW != 3 || g.KH != 3 || g.ls_w != 0 || g.ls_h != 0 || g.Wo < 8 ||
-        g.ph < 0 || g.ph > 2 || g.out_stride % 4 || g.Cout % 4)
-        return 1;
-    RingItem& it = rc->it;
+// The ring kernel's plan of the forward gather `g` over every position; false when the kernel does not serve it.
+// slots: workgroups the call should fill (0: one per CU)
+bool plan_ring(const ConvGeom& g, int slots, WgradCall* p) {
+    if (!tuning().wgrad_ring || g.KW != 3 || g.KH != 3 || g.ls_w != 0 || g.ls_h != 0 || g.Wo < 8 || g.ph < 0 || g.ph > 2 ||
+        g.out_stride % 4 || g.Cout % 4)
+        return false;
+    RingItem& it = p->ring;
     it.g = RingGeom{g.Di, g.Hi, g.Wi, g.Do, g.Ho, g.Wo, g.KD, g.ls_d, g.pd, g.ph, g.pw, g.Cin, g.in_stride, g.Cout, g.out_stride};
-    it.in = in; it.in_bn = in_bnstate; it.dy = dy; it.dW = dW; it.slabs = nullptr; it.counters = nullptr;
-    it.flags = flags; it.flip = flip ? 1 : 0; it.transpose = transpose_out;
     it.LT = cdiv(g.Wo, cdiv(g.Wo, BMW));        // equal tiles per line
     it.tpl = cdiv(g.Wo, it.LT);
     it.gy = cdiv(g.Cin, BC); it.gz = cdiv(g.Cout, BC);
@@ -1164,12 +1084,12 @@ int prepare_ring(const lisec_conv_geom* c, const float* in, const float* in_bnst
         for (int d = 0; d < g.Do; ++d) {
             const int sd = (d << g.ls_d) - g.pd + kd;
             if (sd < 0 || sd >= g.Di) continue;
-            if (it.npairs >= 16) return 1;
+            if (it.npairs >= 16) return false;
             it.pair_kd[it.npairs] = (unsigned char)kd; it.pair_d[it.npairs] = (unsigned char)d;
             it.pair_rank[it.npairs] = (unsigned char)planes[kd]++;
             ++it.npairs;
         }
-    if (it.npairs == 0) return 1;
+    if (it.npairs == 0) return false;
     for (int i = it.npairs; i < 16; ++i) it.pair_kd[i] = it.pair_d[i] = it.pair_rank[i] = 0;
     // runs per column: one round of workgroups where possible, the longest runs that balance (a run pays two warm-up
     // lines and one slab: ~ one tile)
@@ -1183,7 +1103,6 @@ int prepare_ring(const lisec_conv_geom* c, const float* in, const float* in_bnst
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_r = r; }
     }
     it.R = best_r;
-    rc->lines = cdiv(g.Ho, it.R);
     it.nblocks = cols * it.R;
     int smax = 0;
     bool dead = false;
@@ -1193,116 +1112,305 @@ int prepare_ring(const lisec_conv_geom* c, const float* in, const float* in_bnst
         if (kd < g.KD && planes[kd] == 0) dead = true;
     }
     it.combine = (!dead && smax <= tuning().wgrad_combine_max && it.ncells <= kWgradCounters) ? 1 : 0;
-    rc->slab_bytes = align_up((size_t)smax * it.ncells * kRSlabF4 * 16, 256);
-    if (rc->slab_bytes >= (1ull << 31)) return 1;
-    rc->ws_bytes = sizeof(int) * kWgradCounters + rc->slab_bytes;
-    rc->xf = in_bnstate || (flags & LISEC_CONV_IN_RELU);
+    p->slab_bytes = align_up((size_t)smax * it.ncells * kRSlabF4 * 16, 256);
+    if (p->slab_bytes >= (1ull << 31)) return false;
+    if ((long long)g.Do * g.Ho * g.Wo * g.out_stride >= (1LL << 31)) return false;   // int32 offsets into dy
+    p->ws_bytes = sizeof(int) * kWgradCounters + p->slab_bytes;
+    p->cells = it.ncells;
     const int DR = (it.LT + 7) & ~7;
-    rc->np = 2 * (DR + 2) <= 3 * 48 ? 3 : (2 * (DR + 2) <= 5 * 48 ? 5 : 6);   // 48-row passes over [x line][x line | dY line]
-    if ((long long)g.Do * g.Ho * g.Wo * g.out_stride >= (1LL << 31)) return 1;   // int32 offsets into dy
+    p->np = 2 * (DR + 2) <= 3 * 48 ? 3 : (2 * (DR + 2) <= 5 * 48 ? 5 : 6);   // 48-row passes over [x line][x line | dY line]
+    p->ring_fn = ring_kernel(p->xf, p->np);
+    p->grid = dim3(it.nblocks); p->block = dim3(kRingThreads);
+    p->lds = (size_t)(3 * (DR + 2) + DR + 2) * BC * sizeof(float);           // x ring, dY tile, scale/shift
+    p->reduce = it.combine ? WgradCall::NONE : WgradCall::RING_SUM;
+    p->reduce_grid = dim3(cdiv((long long)it.ncells * kRSlabF4, 32));
+    p->taps_per_group = 9;
+    p->groups = it.npairs;                      // (kd, d) pairs that read an existing plane
+    p->tile_rows = it.LT;
+    p->tiles = g.Do * g.Ho * it.tpl;
+    p->slabs = smax;
+    p->tiles_per_slab = p->lines_per_run = cdiv(g.Ho, it.R);
+    return true;
+}
+
+// The slab plan of the w-halo (`halo`) and plain kernels: tap groups, M tiles, the ranges of tiles that get a slab each,
+// the workspace.  blocks_target: workgroups the call should fill (0: tuning().wgrad_blocks)
+void plan_tiles(const ConvGeom& g, bool halo, int blocks_target, WgradCall* p) {
+    WgradItem& it = p->it;
+    it.g = g;
+    it.gy = cdiv(g.Cin, BC); it.gz = cdiv(g.Cout, BC);
+    p->taps_per_group = g.KW;                   // the (at most 4) taps of one (kd, kh) share a staged dY tile
+    p->groups = g.KD * g.KH;
+    p->tile_rows = BMW;
+    p->tiles = cdiv(g.M, BMW);
+    it.live.n = 0;
+    if (halo) {
+        it.LT = p->tile_rows = cdiv(g.Wo, cdiv(g.Wo, BMW));     // equal tiles per line
+        p->tiles = g.Do * g.Ho * cdiv(g.Wo, it.LT);
+        for (int kd = 0; kd < g.KD; ++kd) {
+            bool dlive = false;
+            for (int d = 0; d < g.Do && !dlive; ++d) { const int sd = (d << g.ls_d) - g.pd + kd; dlive = sd >= 0 && sd < g.Di; }
+            for (int kh = 0; kh < g.KH; ++kh) {
+                bool hlive = false;
+                for (int h = 0; h < g.Ho && !hlive; ++h) { const int sh = (h << g.ls_h) - g.ph + kh; hlive = sh >= 0 && sh < g.Hi; }
+                if (dlive && hlive && it.live.n < 16) it.live.id[it.live.n++] = (unsigned char)(kd * g.KH + kh);
+            }
+        }
+        p->groups = it.live.n > 0 ? it.live.n : 1;
+    }
+    const int target = blocks_target > 0 ? blocks_target : tuning().wgrad_blocks;
+    int want = cdiv(target, p->groups * it.gy * it.gz);     // 1024: ~2 rounds of the 512 resident workgroups (measured: 512-1024
+                                                // blocks beat 1536+, whose extra slabs cost more in the reduce than they balance)
+    if (want < 1) want = 1;
+    if (want > p->tiles) want = p->tiles;
+    p->tiles_per_slab = cdiv(p->tiles, want);
+    p->slabs = cdiv(p->tiles, p->tiles_per_slab);
+    // every plan keeps the head of the workspace (kWgradCounters arrival counters) free, so that the counters of the
+    // combining plans stay zero whatever else shares the workspace; slab_bytes = what follows the head
+    p->slab_bytes = align_up(sizeof(float) * (size_t)p->slabs * g.KD * g.KH * g.KW * g.Cin * g.Cout, 256);
+    it.combine = 0;
+    if (halo && p->slabs <= tuning().wgrad_combine_max && g.KD * g.KH <= 16 &&
+        (long long)g.KD * g.KH * it.gy * it.gz <= kWgradCounters) {
+        // few slices per cell: combined inside the kernel (every group gets workgroups: the cells of a group that reads
+        // nothing must still be written, as zeros)
+        it.combine = 1;
+        it.live.n = g.KD * g.KH;
+        for (int i = 0; i < it.live.n; ++i) it.live.id[i] = (unsigned char)i;
+        p->groups = it.live.n;
+        p->slab_bytes = align_up((size_t)p->slabs * p->groups * it.gy * it.gz * kWSlabF4 * 16, 256);
+    }
+    p->ws_bytes = sizeof(int) * kWgradCounters + p->slab_bytes;
+    it.nsplit = p->slabs; it.tiles_per_split = p->tiles_per_slab;
+    it.gx = p->slabs * p->groups;
+}
+
+// Plans the weight gradient of `c` from what a plan depends on and nothing else.  share: the part of the chip the call
+// should fill -- workgroups of the halo and plain kernels, slots of the ring; 0: the whole chip.  first: where the order
+// ring, w-halo, plain is entered (the batched entry asks for a launch of halo items after one of ring items failed).
+int plan_wgrad(const lisec_conv_geom* c, int flags, bool has_in_bn, bool has_dy_bn, bool has_rows, int row_capacity,
+               int share, WgradCall::Kind first, WgradCall* p) {
+    *p = WgradCall{};
+    ConvGeom g;
+    if (int rc = conv_geom_check(c, &g)) return rc;
+    LISEC_CHECK_ARG(!has_rows || row_capacity > 0, "row list needs a capacity");
+    if (has_rows) { g.M = row_capacity; g.pointwise = 0; }
+    p->xf = has_in_bn || (flags & LISEC_CONV_IN_RELU);
+    // The ring and w-halo kernels gather forwards, over every position, with dy as it is.  A transposed gather with unit
+    // strides is the forward one with mirrored taps and pads K-1-p (first deconv: kernel 3, stride 1, 'same'), so they
+    // serve it too; the plain kernel gathers either way and gets the geometry as given.
+    const bool dense = !has_rows && !has_dy_bn && !(flags & LISEC_CONV_DY_RELU);
+    const bool flip = dense && c->mode == 1 && g.ls_d == 0 && g.ls_h == 0 && g.ls_w == 0 && g.KW == 3;
+    const bool forward = dense && (c->mode == 0 || flip);
+    ConvGeom m = g;
+    if (flip) { m.pd = g.KD - 1 - g.pd; m.ph = g.KH - 1 - g.ph; m.pw = g.KW - 1 - g.pw; }
+    if (forward && first == WgradCall::RING && plan_ring(m, share, p)) {
+        p->kind = WgradCall::RING;
+        p->ring.flags = flags; p->ring.flip = flip ? 1 : 0;
+        p->mirrored = flip;
+        return LISEC_OK;
+    }
+    const bool halo = forward && halo_shape(g);
+    plan_tiles(halo ? m : g, halo, share, p);
+    WgradItem& it = p->it;
+    it.flags = flags;
+    p->grid = dim3(it.gx, it.gy, it.gz); p->block = dim3(kThreads);
+    if (halo) {
+        p->kind = WgradCall::HALO;
+        it.flip = flip ? 1 : 0;
+        p->mirrored = flip;
+        p->np = it.LT + 2 <= 7 * 16 ? 7 : 9;
+        p->halo_fn = halo_kernel(p->xf, p->np);
+        p->lds = halo_lds(it.LT);
+        p->cells = p->groups * it.gy * it.gz;
+        unsigned ran = 0;
+        for (int i = 0; i < it.live.n; ++i) ran |= 1u << it.live.id[i];
+        for (int gi = 0; gi < g.KD * g.KH; ++gi) {
+            if ((ran >> gi) & 1) continue;
+            const int kd = gi / g.KH, kh = gi - kd * g.KH;
+            for (int tt = 0; tt < 3; ++tt) {
+                const int tap = flip ? ((g.KD - 1 - kd) * g.KH + (g.KH - 1 - kh)) * g.KW + (2 - tt) : gi * g.KW + tt;
+                p->dead_taps |= 1ULL << tap;
+            }
+        }
+    } else {
+        p->kind = WgradCall::PLAIN;
+        p->np = 8;
+        p->plain_fn = plain_kernel(c->mode, p->taps_per_group, has_rows);
+        p->lds = 2 * TILE_FLOATS * sizeof(float);
+    }
+    // many slabs: 32 lane groups per output sum slabs / 32 slabs each (one or two memory round trips instead of
+    // slabs / 8 dependent ones -- the pass runs beside the data-gradient chain and every round trip costs microseconds
+    // there: 22-151 us in the step for the 47 MB of a middle layer, 12 us alone)
+    const long long per4 = (long long)g.KD * g.KH * g.KW * g.Cin * g.Cout / 4;
+    int gb = cdiv(per4, 256);
+    if (gb > 4096) gb = 4096;
+    p->reduce = it.combine ? WgradCall::NONE : p->slabs >= 32 ? WgradCall::LANE_SUM : WgradCall::SLAB_SUM;
+    p->reduce_grid = p->reduce == WgradCall::LANE_SUM ? dim3(cdiv(per4, 32)) : dim3(gb);
+    return LISEC_OK;
+}
+
+// Puts the tensors and the workspace placement into a planned call.
+// workspace = [kWgradCounters arrival counters][slabs]; counter0: first counter of this call, slab_off: bytes into the slabs
+void bind_wgrad(WgradCall* p, const float* in, const float* in_bn, const float* dy, const float* dy_bn, int transpose_out,
+                float* dW, const int32_t* row_coords, const int32_t* row_count, void* workspace, int counter0, size_t slab_off) {
+    int* counters = static_cast<int*>(workspace) + counter0;
+    float* slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + sizeof(int) * kWgradCounters + slab_off);
+    if (p->kind == WgradCall::RING) {
+        RingItem& it = p->ring;
+        it.in = in; it.in_bn = in_bn; it.dy = dy; it.dW = dW; it.transpose = transpose_out;
+        it.counters = counters; it.slabs = slabs;
+    } else {
+        WgradItem& it = p->it;
+        it.in = in; it.in_bn = in_bn; it.dy = dy; it.dW = dW; it.transpose = transpose_out;
+        it.counters = counters; it.partial = slabs;
+        it.g.row_coords = row_coords; it.g.row_count = row_count;
+        p->dy_bn = dy_bn;
+    }
+}
+
+int run_reduce(const WgradCall& p, hipStream_t st) {
+    const WgradItem& it = p.it;
+    switch (p.reduce) {
+    case WgradCall::NONE: return LISEC_OK;
+    case WgradCall::RING_SUM: LISEC_LAUNCH(k_wgrad_ring_reduce, p.reduce_grid, dim3(256), 0, st, p.ring); break;
+    case WgradCall::LANE_SUM:
+    case WgradCall::SLAB_SUM:
+        LISEC_LAUNCH(p.reduce == WgradCall::LANE_SUM ? k_wgrad_reduce_lanes : k_wgrad_reduce, p.reduce_grid, dim3(256), 0, st,
+                     it.partial, it.nsplit, it.g.KD * it.g.KH * it.g.KW, it.g.Cin, it.g.Cout, it.transpose, it.dW, p.dead_taps);
+        break;
+    }
+    LISEC_LAUNCH_CHECK();
+    return LISEC_OK;
+}
+
+// Issues a bound call: the main launch, then its slab sum.
+int run_wgrad(const WgradCall& p, hipStream_t st) {
+    const WgradItem& it = p.it;
+    switch (p.kind) {
+    case WgradCall::RING: LISEC_LAUNCH(p.ring_fn, p.grid, p.block, p.lds, st, p.ring); break;
+    case WgradCall::HALO: LISEC_LAUNCH(p.halo_fn, p.grid, p.block, p.lds, st, it); break;
+    case WgradCall::PLAIN:
+        LISEC_LAUNCH(p.plain_fn, p.grid, p.block, p.lds, st, it.g, it.in, it.in_bn, it.flags, it.dy, p.dy_bn, it.nsplit,
+                     it.tiles_per_split, it.partial);
+        break;
+    }
+    LISEC_LAUNCH_CHECK();
+    return run_reduce(p, st);
+}
+
+// Several weight gradients in one launch (see k_wgrad_halo_batch): every item must take the same kernel -- `kind`, ring or
+// w-halo -- with the same staging variant, as the stride-1 3x3 convolutions of one RPN block do.  The chip is shared in
+// proportion to the items' work: pass one plans every item at full share for its work, pass two re-plans it with its part.
+// Returns 0 and the planned calls when the items share a launch; 1 when they do not; < 0 on error.
+int plan_batch(const lisec_wgrad_item* items, int n, WgradCall::Kind kind, WgradCall* calls, size_t* total) {
+    const bool ring = kind == WgradCall::RING;
+    long long work[kBatchMax], all = 0;
+    size_t off = 0;
+    int cells = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i) {
+            int share = 0;
+            if (pass == 1) {
+                share = ring ? (int)((double)ring_slots() * (double)work[i] / (double)all)
+                             : (int)((double)tuning().wgrad_batch_blocks * (double)work[i] / (double)all + 0.5);
+                if (share < 1) share = 1;
+            }
+            WgradCall& p = calls[i];
+            if (int rc = plan_wgrad(items[i].g, items[i].flags, items[i].in_bnstate != nullptr, false, false, 0, share, kind, &p))
+                return rc;
+            if (p.kind != kind) return 1;
+            if (pass == 0) {
+                const RingItem& r = p.ring;
+                const ConvGeom& g = p.it.g;
+                work[i] = ring ? (long long)r.gy * r.gz * r.tpl * r.npairs * r.g.Ho * (r.LT + 8)
+                               : (long long)g.Do * g.Ho * g.Wo * g.KD * g.KH * cdiv(g.Cin, BC) * cdiv(g.Cout, BC);
+                all += work[i];
+            } else {
+                if (p.xf != calls[0].xf || p.np != calls[0].np) return 1;
+                off += p.slab_bytes;
+                cells += p.cells;
+            }
+        }
+    if (cells > kWgradCounters || (ring && off >= (1ull << 31))) return 1;
+    *total = sizeof(int) * kWgradCounters + off;
     return 0;
 }
 
-size_t ring_lds(const RingCall& rc) {
-    const int DR = (rc.it.LT + 7) & ~7;
-    return (size_t)(3 * (DR + 2) + DR + 2) * BC * sizeof(float);     // x ring, dY tile, scale/shift
-}
-
-void place_ring(RingCall* rc, void* workspace, int counter0, size_t slab_off) {
-    rc->it.counters = static_cast<int*>(workspace) + counter0;
-    rc->it.slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + sizeof(int) * kWgradCounters + slab_off);
-}
-
-int launch_ring_reduce(const RingCall& rc, hipStream_t st) {
-    const long long total = (long long)rc.it.ncells * kRSlabF4;
-    LISEC_LAUNCH(k_wgrad_ring_reduce, dim3(cdiv(total, 32)), dim3(256), 0, st, rc.it);
+// Binds the planned calls of a batch one behind the other in the workspace and issues them: one launch of `kernel` over
+// the items' grids, then the slab sums of the items that do not combine in place.
+template <typename Batch, typename Item>
+int run_batch(void (*kernel)(Batch), Item WgradCall::*item, WgradCall* calls, const lisec_wgrad_item* items, int n,
+              void* workspace, hipStream_t st) {
+    Batch b;
+    b.n = n;
+    size_t lds = 0, off = 0;
+    int blocks = 0, cells = 0;
+    for (int i = 0; i < n; ++i) {
+        LISEC_CHECK_ARG(items[i].in && items[i].dy && items[i].dW && ((uintptr_t)items[i].in & 15) == 0 &&
+                        ((uintptr_t)items[i].dy & 15) == 0, "item %d: NULL or unaligned tensor", i);
+        WgradCall& p = calls[i];
+        bind_wgrad(&p, items[i].in, items[i].in_bnstate, items[i].dy, nullptr, items[i].transpose_out, items[i].dW, nullptr,
+                   nullptr, workspace, cells, off);
+        cells += p.cells;
+        off += p.slab_bytes;
+        b.first[i] = blocks;
+        b.item[i] = p.*item;
+        blocks += (int)(p.grid.x * p.grid.y * p.grid.z);
+        lds = p.lds > lds ? p.lds : lds;
+    }
+    b.first[n] = blocks;
+    LISEC_LAUNCH(kernel, dim3(blocks), calls[0].block, lds, st, b);
     LISEC_LAUNCH_CHECK();
+    for (int i = 0; i < n; ++i)
+        if (int rc = run_reduce(calls[i], st)) return rc;
     return LISEC_OK;
 }
 
-int launch_slab_sum(const ConvGeom& g, const WgradPlan& p, const float* partial, int transpose_out, float* dW,
-                    unsigned long long dead_taps, hipStream_t st) {
-    const int ntaps = g.KD * g.KH * g.KW;
-    long long per = (long long)ntaps * g.Cin * g.Cout;
-    int gb = cdiv(per / 4, 256);
-    if (gb > 4096) gb = 4096;
-    // many slabs: 32 lane groups per output sum nsplit / 32 slabs each (one or two memory round trips instead of
-    // nsplit / 8 dependent ones -- the pass runs beside the data-gradient chain and every round trip costs microseconds
-    // there: 22-151 us in the step for the 47 MB of a middle layer, 12 us alone)
-    if (p.nsplit >= 32)
-        LISEC_LAUNCH(k_wgrad_reduce_lanes, dim3(cdiv(per / 4, 32)), dim3(256), 0, st, partial, p.nsplit, ntaps,
-                           g.Cin, g.Cout, transpose_out, dW, dead_taps);
-    else
-        LISEC_LAUNCH(k_wgrad_reduce, dim3(gb), dim3(256), 0, st, partial, p.nsplit, ntaps, g.Cin, g.Cout,
-                           transpose_out, dW, dead_taps);
-    LISEC_LAUNCH_CHECK();
-    return LISEC_OK;
-}
 }  // namespace
+}  // namespace lisec
+
+using namespace lisec;
 
 extern "C" size_t lisec_conv_wgrad_workspace_bytes(const lisec_conv_geom* c, int row_capacity) {
+    // The caller sizes its workspace before it knows the flags, so this is the largest plan the geometry can get at this
+    // M: the slab plan without and with the w-halo kernel (as given, dy transformed, mirrored), and the ring without a row list
     ConvGeom g;
     if (conv_geom_check(c, &g)) return 0;
     if (row_capacity > 0) g.M = row_capacity;
-    // the plans lisec_conv_wgrad may pick for this geometry: as given, role-swapped (dy transformed), mirrored to mode 0
-    const size_t a = make_plan(g, c->mode, false).ws_bytes, b = make_plan(g, 1, true).ws_bytes,
-                 m0 = make_plan(g, 0, false).ws_bytes;
-    size_t w = a > b ? (a > m0 ? a : m0) : (b > m0 ? b : m0);
-    RingCall rc;
-    if (row_capacity <= 0 && prepare_ring(c, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, false, 0, &rc) == 0 && rc.ws_bytes > w)
-        w = rc.ws_bytes;
+    WgradCall p;
+    plan_tiles(g, false, 0, &p);
+    size_t w = p.ws_bytes;
+    if (halo_shape(g)) {
+        plan_tiles(g, true, 0, &p);
+        w = p.ws_bytes > w ? p.ws_bytes : w;
+    }
+    if (row_capacity <= 0 && plan_wgrad(c, 0, false, false, false, 0, 0, WgradCall::RING, &p) == 0 && p.kind == WgradCall::RING &&
+        p.ws_bytes > w)
+        w = p.ws_bytes;
     return w;
 }
 
 extern "C" int lisec_conv_wgrad_plan_query(const lisec_conv_geom* c, int flags, int has_dy_bnstate, int has_row_list,
                                            int row_capacity, lisec_wgrad_plan* out) {
     LISEC_CHECK_ARG(out, "NULL plan");
-    ConvGeom g;
-    if (int rc = conv_geom_check(c, &g)) return rc;
-    static const int32_t dummy[4] = {0, 0, 0, 0};
-    if (has_row_list) {
-        LISEC_CHECK_ARG(row_capacity > 0, "row list needs a capacity");
-        g.row_coords = dummy; g.row_count = dummy + 3; g.M = row_capacity; g.pointwise = 0;
-    }
-    const bool dy_xf = has_dy_bnstate || (flags & LISEC_CONV_DY_RELU);
-    const bool flip = c->mode == 1 && g.ls_d == 0 && g.ls_h == 0 && g.ls_w == 0 && g.KW == 3 && !has_row_list && !dy_xf;
-    if (flip) { g.pd = g.KD - 1 - g.pd; g.ph = g.KH - 1 - g.ph; g.pw = g.KW - 1 - g.pw; }
-    const WgradPlan p = make_plan(g, flip ? 0 : c->mode, dy_xf);
-    out->halo = p.halo ? 1 : 0;
-    out->mirrored = flip ? 1 : 0;
-    out->taps_per_group = p.TG;
-    out->groups = p.ngroups;
-    out->tile_rows = p.halo ? p.LT : BMW;
-    out->staging_passes = p.halo ? (p.LT + 2 <= 7 * 16 ? 7 : 9) : 8;
-    out->tiles = p.ntiles;
-    out->slabs = p.nsplit;
-    out->tiles_per_slab = p.tiles_per_split;
-    out->workgroups = p.nsplit * p.ngroups * cdiv(g.Cin, BC) * cdiv(g.Cout, BC);
-    out->lane_reduce = (!p.combine && p.nsplit >= 32) ? 1 : 0;
-    out->combine_in_kernel = p.combine ? 1 : 0;
-    out->ring = 0; out->runs_per_column = 0; out->lines_per_run = 0;
-    RingCall rc;
-    static const float dummy_bn[1] = {0.f};
-    const int rk = prepare_ring(c, nullptr, nullptr, flags, nullptr, has_dy_bnstate ? dummy_bn : nullptr, 0, nullptr,
-                                has_row_list != 0, 0, &rc);
-    if (rk < 0) return rk;
-    if (rk == 0) {
-        out->ring = 1; out->halo = 0;
-        out->taps_per_group = 9;
-        out->groups = rc.it.npairs;                    // (kd, d) pairs that read an existing plane
-        out->tile_rows = rc.it.LT;
-        out->staging_passes = rc.np;
-        out->tiles = rc.it.g.Do * rc.it.g.Ho * rc.it.tpl;
-        out->runs_per_column = rc.it.R;
-        out->lines_per_run = rc.lines;
-        int smax = 0;
-        for (int k = 0; k < 4; ++k) smax = rc.it.kd_slices[k] > smax ? rc.it.kd_slices[k] : smax;
-        out->slabs = smax;
-        out->tiles_per_slab = rc.lines;
-        out->workgroups = rc.it.nblocks;
-        out->lane_reduce = rc.it.combine ? 0 : 1;
-        out->combine_in_kernel = rc.it.combine;
-    }
+    WgradCall p;                                // (no reported field depends on the on-load transform of `in`)
+    if (int rc = plan_wgrad(c, flags, false, has_dy_bnstate != 0, has_row_list != 0, row_capacity, 0, WgradCall::RING, &p))
+        return rc;
+    out->ring = p.kind == WgradCall::RING ? 1 : 0;
+    out->halo = p.kind == WgradCall::HALO ? 1 : 0;
+    out->mirrored = p.mirrored ? 1 : 0;
+    out->taps_per_group = p.taps_per_group;
+    out->groups = p.groups;
+    out->tile_rows = p.tile_rows;
+    out->staging_passes = p.np;
+    out->tiles = p.tiles;
+    out->slabs = p.slabs;
+    out->tiles_per_slab = p.tiles_per_slab;
+    out->workgroups = (int)(p.grid.x * p.grid.y * p.grid.z);
+    out->lane_reduce = (p.reduce == WgradCall::RING_SUM || p.reduce == WgradCall::LANE_SUM) ? 1 : 0;
+    out->combine_in_kernel = p.reduce == WgradCall::NONE ? 1 : 0;
+    out->runs_per_column = p.kind == WgradCall::RING ? p.ring.R : 0;
+    out->lines_per_run = p.lines_per_run;
     return LISEC_OK;
 }
 
@@ -1312,142 +1420,28 @@ extern "C" int lisec_conv_wgrad(const lisec_conv_geom* c, const float* in, const
                                 const int32_t* row_count, int row_capacity, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(in && dy && workspace && dW, "NULL pointer");
     LISEC_CHECK_ARG(((uintptr_t)in & 15) == 0 && ((uintptr_t)dy & 15) == 0, "in/dy must be 16-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream_);
-    {
-        RingCall rc;
-        const int rk = prepare_ring(c, in, in_bnstate, flags, dy, dy_bnstate, transpose_out, dW, row_coords != nullptr, 0, &rc);
-        if (rk < 0) return rk;
-        if (rk == 0) {
-            if (workspace_bytes < rc.ws_bytes) {
-                set_error("wgrad workspace too small: %zu < %zu", workspace_bytes, rc.ws_bytes);
-                return LISEC_ENOSPC;
-            }
-            place_ring(&rc, workspace, 0, 0);
-            const size_t lds = ring_lds(rc);
-#define LISEC_WR(X_, NP_) LISEC_LAUNCH((k_wgrad_ring<X_, NP_>), dim3(rc.it.nblocks), dim3(kRingThreads), lds, st, rc.it)
-            if (rc.np == 3)      { if (rc.xf) LISEC_WR(true, 3); else LISEC_WR(false, 3); }
-            else if (rc.np == 5) { if (rc.xf) LISEC_WR(true, 5); else LISEC_WR(false, 5); }
-            else                 { if (rc.xf) LISEC_WR(true, 6); else LISEC_WR(false, 6); }
-#undef LISEC_WR
-            LISEC_LAUNCH_CHECK();
-            return rc.it.combine ? LISEC_OK : launch_ring_reduce(rc, st);
-        }
-    }
-    HaloCall hc;
-    const int kind = prepare_halo(c, in, in_bnstate, flags, dy, dy_bnstate, transpose_out, dW, row_coords != nullptr, 0, &hc);
-    if (kind < 0) return kind;
-    ConvGeom& g = hc.it.g;                      // checked (and mirrored, for a unit-stride transposed gather) by prepare_halo
-    LISEC_CHECK_ARG(g.out_stride % 4 == 0 && g.Cout % 4 == 0, "dY channels/stride must be multiples of 4");
-    if (kind == 0) {
-        if (workspace_bytes < hc.p.ws_bytes) {
-            set_error("wgrad workspace too small: %zu < %zu", workspace_bytes, hc.p.ws_bytes);
-            return LISEC_ENOSPC;
-        }
-        place_workspace(&hc, workspace, 0, 0);
-        dim3 grid(hc.it.gx, hc.it.gy, hc.it.gz);
-        const size_t lds = halo_lds(hc);
-#define LISEC_WH(X_, NP_) LISEC_LAUNCH((k_wgrad_halo<X_, NP_>), grid, dim3(kThreads), lds, st, hc.it)
-        if (hc.np == 7) { if (hc.xf) LISEC_WH(true, 7); else LISEC_WH(false, 7); }
-        else            { if (hc.xf) LISEC_WH(true, 9); else LISEC_WH(false, 9); }
-#undef LISEC_WH
-        LISEC_LAUNCH_CHECK();
-        if (hc.p.combine) return LISEC_OK;
-        return launch_slab_sum(g, hc.p, hc.it.partial, transpose_out, dW, hc.dead_taps, st);
-    }
-    if (row_coords) {
-        LISEC_CHECK_ARG(row_count && row_capacity > 0, "row list needs a device count and a capacity");
-        g.row_coords = row_coords; g.row_count = row_count; g.M = row_capacity; g.pointwise = 0;
-    }
-    const bool dy_xf = dy_bnstate != nullptr || (flags & LISEC_CONV_DY_RELU);
-    WgradPlan p = make_plan(g, c->mode, dy_xf);
+    LISEC_CHECK_ARG(!row_coords || (row_count && row_capacity > 0), "row list needs a device count and a capacity");
+    WgradCall p;
+    if (int rc = plan_wgrad(c, flags, in_bnstate != nullptr, dy_bnstate != nullptr, row_coords != nullptr, row_capacity, 0,
+                            WgradCall::RING, &p))
+        return rc;
+    LISEC_CHECK_ARG(c->out_stride % 4 == 0 && c->Cout % 4 == 0, "dY channels/stride must be multiples of 4");
     if (workspace_bytes < p.ws_bytes) {
         set_error("wgrad workspace too small: %zu < %zu", workspace_bytes, p.ws_bytes);
         return LISEC_ENOSPC;
     }
-    float* partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + sizeof(int) * kWgradCounters);
-    const int rc = c->mode == 0 ? launch_wgrad<0>(g, p, in, in_bnstate, flags, dy, dy_bnstate, partial, st)
-                                : launch_wgrad<1>(g, p, in, in_bnstate, flags, dy, dy_bnstate, partial, st);
-    if (rc) return rc;
-    return launch_slab_sum(g, p, partial, transpose_out, dW, 0, st);
+    bind_wgrad(&p, in, in_bnstate, dy, dy_bnstate, transpose_out, dW, row_coords, row_count, workspace, 0, 0);
+    return run_wgrad(p, static_cast<hipStream_t>(stream_));
 }
 
-// Several weight gradients in one launch (see k_wgrad_halo_batch): every item must take the halo kernel with the same
-// staging variant -- the stride-1 3x3 convolutions of one RPN block do -- otherwise the items run one after the other.
-// The launch aims for tuning.wgrad_blocks workgroups over ALL items, in proportion to their rows.
-namespace {
-int plan_batch(const lisec_wgrad_item* items, int n, HaloCall* hcs, size_t* offsets, size_t* total) {
-    // first pass: rows of work per item at one slice, to share the block target
-    long long work[kBatchMax], all = 0;
-    for (int i = 0; i < n; ++i) {
-        HaloCall probe;
-        const int kind = prepare_halo(items[i].g, items[i].in, items[i].in_bnstate, items[i].flags, items[i].dy, nullptr,
-                                      items[i].transpose_out, items[i].dW, false, 0, &probe);
-        if (kind != 0) return kind < 0 ? kind : 1;
-        const ConvGeom& g = probe.it.g;
-        work[i] = (long long)g.Do * g.Ho * g.Wo * g.KD * g.KH * cdiv(g.Cin, BC) * cdiv(g.Cout, BC);
-        all += work[i];
-    }
-    size_t off = 0;
-    for (int i = 0; i < n; ++i) {
-        int target = (int)((double)tuning().wgrad_batch_blocks * (double)work[i] / (double)all + 0.5);
-        if (target < 1) target = 1;
-        const int kind = prepare_halo(items[i].g, items[i].in, items[i].in_bnstate, items[i].flags, items[i].dy, nullptr,
-                                      items[i].transpose_out, items[i].dW, false, target, &hcs[i]);
-        if (kind != 0) return kind < 0 ? kind : 1;
-        if (hcs[i].xf != hcs[0].xf || hcs[i].np != hcs[0].np) return 1;
-        offsets[i] = off;
-        off += hcs[i].p.slab_bytes;
-    }
-    *total = sizeof(int) * kWgradCounters + off;
-    int cells = 0;
-    for (int i = 0; i < n; ++i) cells += hcs[i].p.ngroups * hcs[i].it.gy * hcs[i].it.gz;
-    if (cells > kWgradCounters) return 1;
-    return 0;
-}
-}  // namespace
-
-namespace {
-// ring kernel: every item on it with the same staging variant; the CUs are shared in proportion to the items' work
-int plan_ring_batch(const lisec_wgrad_item* items, int n, RingCall* rcs, size_t* offsets, size_t* total) {
-    if (!tuning().wgrad_ring) return 1;
-    long long work[kBatchMax], all = 0;
-    for (int i = 0; i < n; ++i) {
-        const int kind = prepare_ring(items[i].g, items[i].in, items[i].in_bnstate, items[i].flags, items[i].dy, nullptr,
-                                      items[i].transpose_out, items[i].dW, false, 0, &rcs[i]);
-        if (kind != 0) return kind < 0 ? kind : 1;
-        const RingItem& it = rcs[i].it;
-        work[i] = (long long)it.gy * it.gz * it.tpl * it.npairs * it.g.Ho * (it.LT + 8);
-        all += work[i];
-    }
-    size_t off = 0;
-    int cells = 0;
-    for (int i = 0; i < n; ++i) {
-        int slots = (int)((double)ring_slots() * (double)work[i] / (double)all);
-        if (slots < 1) slots = 1;
-        const int kind = prepare_ring(items[i].g, items[i].in, items[i].in_bnstate, items[i].flags, items[i].dy, nullptr,
-                                      items[i].transpose_out, items[i].dW, false, slots, &rcs[i]);
-        if (kind != 0) return kind < 0 ? kind : 1;
-        if (rcs[i].xf != rcs[0].xf || rcs[i].np != rcs[0].np) return 1;
-        offsets[i] = off;
-        off += rcs[i].slab_bytes;
-        cells += rcs[i].it.ncells;
-    }
-    if (cells > kWgradCounters || off >= (1ull << 31)) return 1;
-    *total = sizeof(int) * kWgradCounters + off;
-    return 0;
-}
-}  // namespace
-
+// Several weight gradients in one launch: of the ring kernel if every item takes it, else of the w-halo kernel if every
+// item takes that; otherwise the items run one after the other.
 extern "C" size_t lisec_conv_wgrad_batched_workspace_bytes(const lisec_wgrad_item* items, int n) {
     if (!items || n < 1 || n > kBatchMax) return 0;
-    {
-        RingCall rcs[kBatchMax];
-        size_t offsets[kBatchMax], total = 0;
-        if (plan_ring_batch(items, n, rcs, offsets, &total) == 0) return total;
-    }
-    HaloCall hcs[kBatchMax];
-    size_t offsets[kBatchMax], total = 0;
-    if (plan_batch(items, n, hcs, offsets, &total) == 0) return total;
+    WgradCall calls[kBatchMax];
+    size_t total = 0;
+    if (plan_batch(items, n, WgradCall::RING, calls, &total) == 0 || plan_batch(items, n, WgradCall::HALO, calls, &total) == 0)
+        return total;
     size_t worst = 0;                               // not batchable: the items run one by one in the same workspace
     for (int i = 0; i < n; ++i) {
         const size_t w = lisec_conv_wgrad_workspace_bytes(items[i].g, 0);
@@ -1460,47 +1454,10 @@ extern "C" int lisec_conv_wgrad_batched(const lisec_wgrad_item* items, int n, vo
                                         lisec_stream_t stream_) {
     LISEC_CHECK_ARG(items && n >= 1 && n <= kBatchMax && workspace, "1 .. 6 items and a workspace");
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    {
-        RingCall rcs[kBatchMax];
-        size_t roff[kBatchMax], rtotal = 0;
-        const int rk = plan_ring_batch(items, n, rcs, roff, &rtotal);
-        if (rk < 0) return rk;
-        if (rk == 0) {
-            if (workspace_bytes < rtotal) {
-                set_error("batched wgrad workspace too small: %zu < %zu", workspace_bytes, rtotal);
-                return LISEC_ENOSPC;
-            }
-            RingBatch b;
-            b.n = n;
-            size_t lds = 0;
-            int blocks = 0, cells = 0;
-            for (int i = 0; i < n; ++i) {
-                LISEC_CHECK_ARG(items[i].in && items[i].dy && items[i].dW && ((uintptr_t)items[i].in & 15) == 0 &&
-                                ((uintptr_t)items[i].dy & 15) == 0, "item %d: NULL or unaligned tensor", i);
-                place_ring(&rcs[i], workspace, cells, roff[i]);
-                cells += rcs[i].it.ncells;
-                b.first[i] = blocks;
-                b.item[i] = rcs[i].it;
-                blocks += rcs[i].it.nblocks;
-                const size_t l = ring_lds(rcs[i]);
-                lds = l > lds ? l : lds;
-            }
-            b.first[n] = blocks;
-#define LISEC_WRB(X_, NP_) LISEC_LAUNCH((k_wgrad_ring_batch<X_, NP_>), dim3(blocks), dim3(kRingThreads), lds, st, b)
-            if (rcs[0].np == 3)      { if (rcs[0].xf) LISEC_WRB(true, 3); else LISEC_WRB(false, 3); }
-            else if (rcs[0].np == 5) { if (rcs[0].xf) LISEC_WRB(true, 5); else LISEC_WRB(false, 5); }
-            else                     { if (rcs[0].xf) LISEC_WRB(true, 6); else LISEC_WRB(false, 6); }
-#undef LISEC_WRB
-            LISEC_LAUNCH_CHECK();
-            for (int i = 0; i < n; ++i)
-                if (!rcs[i].it.combine)
-                    if (int rc = launch_ring_reduce(rcs[i], st)) return rc;
-            return LISEC_OK;
-        }
-    }
-    HaloCall hcs[kBatchMax];
-    size_t offsets[kBatchMax], total = 0;
-    const int kind = plan_batch(items, n, hcs, offsets, &total);
+    WgradCall calls[kBatchMax];
+    size_t total = 0;
+    int kind = plan_batch(items, n, WgradCall::RING, calls, &total);
+    if (kind == 1) kind = plan_batch(items, n, WgradCall::HALO, calls, &total);
     if (kind < 0) return kind;
     if (kind != 0) {                                // one by one (same stream: they may share the workspace)
         for (int i = 0; i < n; ++i)
@@ -1514,33 +1471,10 @@ extern "C" int lisec_conv_wgrad_batched(const lisec_wgrad_item* items, int n, vo
         set_error("batched wgrad workspace too small: %zu < %zu", workspace_bytes, total);
         return LISEC_ENOSPC;
     }
-    WgradBatch b;
-    b.n = n;
-    size_t lds = 0;
-    int blocks = 0, cells = 0;
-    for (int i = 0; i < n; ++i) {
-        LISEC_CHECK_ARG(items[i].in && items[i].dy && items[i].dW && ((uintptr_t)items[i].in & 15) == 0 &&
-                        ((uintptr_t)items[i].dy & 15) == 0, "item %d: NULL or unaligned tensor", i);
-        place_workspace(&hcs[i], workspace, cells, offsets[i]);
-        cells += hcs[i].p.ngroups * hcs[i].it.gy * hcs[i].it.gz;
-        b.first[i] = blocks;
-        b.item[i] = hcs[i].it;
-        blocks += hcs[i].it.gx * hcs[i].it.gy * hcs[i].it.gz;
-        const size_t l = halo_lds(hcs[i]);
-        lds = l > lds ? l : lds;
-    }
-    b.first[n] = blocks;
-#define LISEC_WB(X_, NP_) LISEC_LAUNCH((k_wgrad_halo_batch<X_, NP_>), dim3(blocks), dim3(kThreads), lds, st, b)
-    if (hcs[0].np == 7) { if (hcs[0].xf) LISEC_WB(true, 7); else LISEC_WB(false, 7); }
-    else                { if (hcs[0].xf) LISEC_WB(true, 9); else LISEC_WB(false, 9); }
-#undef LISEC_WB
-    LISEC_LAUNCH_CHECK();
-    for (int i = 0; i < n; ++i)
-        if (!hcs[i].p.combine)
-            if (int rc = launch_slab_sum(hcs[i].it.g, hcs[i].p, hcs[i].it.partial, items[i].transpose_out, items[i].dW,
-                                         hcs[i].dead_taps, st))
-                return rc;
-    return LISEC_OK;
+    const WgradCall& p0 = calls[0];
+    if (p0.kind == WgradCall::RING)
+        return run_batch<RingBatch>(ring_kernel_batch(p0.xf, p0.np), &WgradCall::ring, calls, items, n, workspace, st);
+    return run_batch<WgradBatch>(halo_kernel_batch(p0.xf, p0.np), &WgradCall::it, calls, items, n, workspace, st);
 }
 
 // Diagnostic: points the weight-gradient kernels' stamp buffer at `buf` (device, 8192*8 uint64) or NULL.

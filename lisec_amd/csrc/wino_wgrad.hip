@@ -371,11 +371,7 @@ int live_taps(const ConvGeom& g, unsigned* kd_list) {
 }
 
 int wgrad_nwg(int nkd) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    const int cus = cu_count();
     return nkd > 0 ? cus / nkd * nkd : cus;          // the same number of workgroups for every tap
 }
 

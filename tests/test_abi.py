@@ -69,6 +69,25 @@ def test_plan_query_needs_no_gpu():
     assert plan["kernel"] == "halo2" and plan["plane_pair"] == 1 and plan["k_slices"] == 1 and plan["workgroups"] == 1250
 
 
+def test_wgrad_plan_query_needs_no_gpu():
+    """lisec_conv_wgrad_plan_query answers on the host from the plan a call runs (256 CUs without a device): the second
+    middle block and the stride-1 layer of RPN block 3 take the ring kernel, the strided first RPN layer the plain one."""
+    from lisec_amd import ops
+
+    def check(plan, **expect):
+        assert {k: plan[k] for k in expect} == expect, plan
+
+    g = ops.geom(0, (4, 200, 400), (2, 200, 400), (3, 3, 3), (1, 1, 1), (0, 1, 1), 64, 64)                  # mid2
+    check(ops.wgrad_plan(g), ring=1, halo=0, mirrored=0, groups=6, tile_rows=100, staging_passes=5, taps_per_group=9,
+          lane_reduce=1, combine_in_kernel=0, runs_per_column=10, lines_per_run=20, slabs=80, workgroups=240)
+    g = ops.geom(0, (1, 25, 50), (1, 25, 50), (1, 3, 3), (1, 1, 1), (0, 1, 1), 256, 256)                    # rpn3.conv1
+    check(ops.wgrad_plan(g, flags=ops.IN_RELU), ring=1, halo=0, groups=1, tile_rows=50, staging_passes=3, lane_reduce=0,
+          combine_in_kernel=1, runs_per_column=13, workgroups=208)
+    g = ops.geom(0, (1, 200, 400), (1, 100, 200), (1, 3, 3), (1, 2, 2), (0, 1, 1), 64, 128)                 # rpn1.conv0
+    check(ops.wgrad_plan(g), ring=0, halo=0, mirrored=0, taps_per_group=3, groups=3, tile_rows=128, staging_passes=8,
+          tiles=157, slabs=157, tiles_per_slab=1, workgroups=942, lane_reduce=1, combine_in_kernel=0)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     from lisec_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)

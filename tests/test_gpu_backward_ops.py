@@ -85,6 +85,26 @@ def test_wgrad_and_dgrad_conv2d_transpose(k, s, cin):
     _close(da, a.grad)
 
 
+@pytest.mark.parametrize("n,mirrored", [(6, 1), (4, 0)])
+def test_wgrad_unit_stride_transposed_gather_with_unequal_pads(n, mirrored):
+    """Mode 1, kernel 3, stride 1, pad 0 (K - 1 - pad = 2): the ring / w-halo kernels run it as the forward gather with
+    mirrored taps and pads when the output line has 8 positions; at 6 the plain kernel runs it and must get the geometry
+    as given.  The plan query says which of the two ran."""
+    from lisec_amd import ops
+    from oracle import conv_ref
+    g = torch.Generator().manual_seed(40 + n)
+    ind, outd, k, s, pad = (1, n, n), (1, n + 2, n + 2), (1, 3, 3), (1, 1, 1), (0, 0, 0)
+    x = torch.randn(*ind, 16, generator=g)
+    dy = torch.randn(*outd, 16, generator=g)
+    geo = ops.geom(1, ind, outd, k, s, pad, 16, 16)
+    plan = ops.wgrad_plan(geo)
+    assert plan["mirrored"] == mirrored and (plan["ring"] or plan["halo"]) == mirrored, plan
+    ws = torch.zeros(ops.wgrad_workspace_bytes(geo), dtype=torch.uint8, device=DEV)   # zero-filled once (arrival counters)
+    dW = torch.full((9, 16, 16), float("nan"), device=DEV)
+    ops.conv_wgrad(geo, x.to(DEV), dy.to(DEV), dW, ws)
+    _close(dW, torch.from_numpy(conv_ref.conv_wgrad(x.numpy(), dy.numpy(), outd, k, s, pad, mode=1)))
+
+
 @pytest.mark.parametrize("C,relu", [(64, False), (128, True), (256, True)])
 def test_bn_backward(C, relu):
     from lisec_amd import ops
