@@ -916,6 +916,49 @@ int lisec_boxes_union_overlap(const double* pred_boxes, const int32_t* pred_star
                               const int32_t* label_start, int n_samples, void* workspace, size_t workspace_bytes,
                               double* out, lisec_stream_t stream);
 
+/* Detection average precision: score-ranked boxes against annotations at IoU thresholds (csrc/detection_ap.hip).  Not in the
+ * reference; the rule is the PASCAL-VOC style one of DESIGN section 7, parity with the Lyft devkit unpinned.
+ *
+ * lisec_boxes_match: the samples are laid out as for lisec_boxes_union_overlap, with pred_start[0] == 0; total_pred =
+ * pred_start[n_samples] and total_pairs = sum over the samples of n_pred * n_label are the sizes the HOST sized the buffers
+ * by.  IoU of a prediction p and a label g, footprints as above (a negative extent mirrors one):
+ *   LISEC_IOU_3D   inter = area(fp_p n fp_g) * max(0, min(z_p + |h_p|/2, z_g + |h_g|/2) - max(z_p - |h_p|/2, z_g - |h_g|/2)),
+ *                  union = |l w h|_p + |l w h|_g - inter, iou = inter / union, 0 when union <= 0 -- geometrically consistent,
+ *                  NOT calculateIoU (serialize_data.py:170-178) with its unclamped z term;
+ *   LISEC_IOU_BEV  the same with areas only;
+ *   a box with l == 0 or w == 0 (or h == 0 under LISEC_IOU_3D) has IoU 0 with everything.
+ * Per prediction: best_label = the row, within its own sample, of the label with the largest IoU (the lowest row among
+ * equals; -1 without labels), best_iou = that IoU.  Per threshold t (HOST double[n_thresholds], 1..16 values in [0, 1)), in
+ * the order of descending score, equal scores by ascending row: a prediction is a true positive when best_iou > t and no
+ * earlier one has taken best_label at t, and then takes it; tp: uint8[n_thresholds][total_pred] in input order, tp_count:
+ * int32[n_samples][n_thresholds].  On return the first total_pairs doubles of the workspace hold the IoU matrices, sample
+ * after sample, each n_pred x n_label row-major.  No size is capped: the pair kernel strides over total_pairs with a bounded
+ * grid, and the workspace the caller can supply is the only limit.  Offsets that disagree with total_pred / total_pairs give
+ * best_iou = NaN, best_label = -1, tp = 0, tp_count = -1 (and NaN matrices).  Integers and float64 in a fixed order:
+ * bit-identical from run to run.
+ *
+ * lisec_boxes_pair_iou: the IoU matrices alone, in the same layout, into out_iou (device double[total_pairs]); NaN throughout
+ * when the offsets disagree with the sizes.  workspace: lisec_boxes_match_workspace_bytes(n_samples, total_pred, 0, 1) bytes.
+ *
+ * lisec_boxes_average_precision: rank[k] = the row of the prediction ranked k-th (device int64[n_pred], e.g. a stable
+ * descending sort of the scores), tp as above, n_labels = G > 0 (LISEC_EINVAL for G <= 0).  With cum_k the true positives
+ * among the first k ranks: rec_k = cum_k / G, prec_k = cum_k / k, mrec = [0, rec.., 1], mpre = [0, prec.., 0] made
+ * non-increasing from the right, out_ap[t] = sum (mrec[i+1] - mrec[i]) * mpre[i+1]; 0 for n_pred == 0.  out_curve, when not
+ * NULL: double[n_thresholds][n_pred][2] = (rec_k, prec_k before the envelope).  One workgroup per threshold. */
+#define LISEC_IOU_3D 0
+#define LISEC_IOU_BEV 1
+size_t lisec_boxes_match_workspace_bytes(int n_samples, int total_pred, long long total_pairs, int n_thresholds);
+int lisec_boxes_match(const double* pred_boxes, const double* pred_scores, const int32_t* pred_start,
+                      const double* label_boxes, const int32_t* label_start, int n_samples, int total_pred,
+                      long long total_pairs, const double* thresholds, int n_thresholds, int mode, void* workspace,
+                      size_t workspace_bytes, double* best_iou, int32_t* best_label, uint8_t* tp, int32_t* tp_count,
+                      lisec_stream_t stream);
+int lisec_boxes_pair_iou(const double* pred_boxes, const int32_t* pred_start, const double* label_boxes,
+                         const int32_t* label_start, int n_samples, int total_pred, long long total_pairs, int mode,
+                         void* workspace, size_t workspace_bytes, double* out_iou, lisec_stream_t stream);
+int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_pred, int n_labels, int n_thresholds,
+                                  double* out_ap, double* out_curve, lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 5b. Step plans: a whole training step recorded once and re-issued by ONE call (csrc/plan.hip).
  *     The reference repeats one static schedule 180 times (model.fit(batch_size=1, steps_per_epoch=180),

@@ -150,6 +150,15 @@ def _declare(lib):
     lib.lisec_boxes_union_overlap_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.lisec_boxes_union_overlap.restype = c_int
     lib.lisec_boxes_union_overlap.argtypes = [P, P, P, P, c_int, P, c_size_t, P, P]
+    lib.lisec_boxes_match_workspace_bytes.restype = c_size_t
+    lib.lisec_boxes_match_workspace_bytes.argtypes = [c_int, c_int, LL, c_int]
+    lib.lisec_boxes_match.restype = c_int
+    lib.lisec_boxes_match.argtypes = [P, P, P, P, P, c_int, c_int, LL, POINTER(c_double), c_int, c_int, P, c_size_t,
+                                      P, P, P, P, P]
+    lib.lisec_boxes_pair_iou.restype = c_int
+    lib.lisec_boxes_pair_iou.argtypes = [P, P, P, P, c_int, c_int, LL, c_int, P, c_size_t, P, P]
+    lib.lisec_boxes_average_precision.restype = c_int
+    lib.lisec_boxes_average_precision.argtypes = [P, P, c_int, c_int, c_int, P, P, P]
     lib.lisec_lidar_transform.restype = c_int
     lib.lisec_lidar_transform.argtypes = [P, c_int, c_int, POINTER(c_double), POINTER(c_double), P, P]
     lib.lisec_vfe_grid_from_saved.restype = c_int

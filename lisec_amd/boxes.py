@@ -107,8 +107,8 @@ def quaternion_yaw(q):
 
 
 # ---- scoring detections against annotations (rpnToRegion.py:202-255) ---------------------------------------------------
-def _pack(box_list, dev):
-    """[(k_s, 7) arrays or device tensors] -> (device (max(rows, 1), 7) float64, device int32 (S+1,) row offsets)."""
+def _pack_counted(box_list, dev):
+    """[(k_s, 7) arrays or device tensors] -> (device (max(rows, 1), 7) float64, host int32 (S+1,) row offsets)."""
     rows = [b.to(device=dev, dtype=torch.float64).reshape(-1, 7) if torch.is_tensor(b)
             else torch.from_numpy(np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1, 7))) for b in box_list]
     start = np.zeros(len(rows) + 1, dtype=np.int32)
@@ -117,6 +117,12 @@ def _pack(box_list, dev):
         flat = torch.cat(rows + [torch.zeros((1, 7), dtype=torch.float64)]).to(dev)
     else:
         flat = torch.cat([r.to(dev) for r in rows] + [torch.zeros((1, 7), dtype=torch.float64, device=dev)])
+    return flat, start
+
+
+def _pack(box_list, dev):
+    """_pack_counted with the row offsets on the device."""
+    flat, start = _pack_counted(box_list, dev)
     return flat, torch.from_numpy(start).to(dev)
 
 
@@ -199,3 +205,125 @@ def annotationBoxes(sample, dataset):
         if category == 'car' and row[0] >= -50 and row[0] <= 50 and row[1] >= -50 and row[1] <= 50:
             labels.append(row)
     return np.array(labels, dtype=np.float64).reshape(-1, 7)
+
+
+# ---- detection average precision (ours; the reference has no counterpart) ----------------------------------------------
+_IOU_MODES = {'3d': 0, 'bev': 1}                               # LISEC_IOU_3D, LISEC_IOU_BEV
+MAX_IOU_THRESHOLDS = 16
+
+
+class DetectionAP:
+    """What average_precision returns: ap (T,), mAP, thresholds (T,), tp (T, N) bool in input order, tp_count (n_samples, T),
+    best_iou (N,), best_label (N,) (row within the sample, -1 without labels), n_predictions, n_labels."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return (f"DetectionAP(mAP={self.mAP:.6f}, n_predictions={self.n_predictions}, n_labels={self.n_labels}, "
+                f"ap={np.array2string(self.ap, precision=4)})")
+
+
+def _iou_mode(mode):
+    if mode not in _IOU_MODES:
+        raise ValueError(f"mode must be one of {sorted(_IOU_MODES)}, not {mode!r}")
+    return _IOU_MODES[mode]
+
+
+def _iou_thresholds(iou_thresholds):
+    thr = np.arange(0.5, 1.0, 0.05) if iou_thresholds is None else np.asarray(iou_thresholds, dtype=np.float64).reshape(-1)
+    if not 1 <= len(thr) <= MAX_IOU_THRESHOLDS:
+        raise ValueError(f"between 1 and {MAX_IOU_THRESHOLDS} IoU thresholds are accepted, not {len(thr)}")
+    if not np.all((thr >= 0) & (thr < 1)):
+        raise ValueError(f"IoU thresholds must lie in [0, 1): {thr.tolist()}")
+    return thr
+
+
+def _rows7(b):
+    return b.reshape(-1, 7) if torch.is_tensor(b) else np.asarray(b, dtype=np.float64).reshape(-1, 7)
+
+
+def _pack_samples(pred_list, label_list, dev):
+    """Both sides of a list of samples on the device: (pred, pred_start, label, label_start) with the offsets as device
+    int32 (S+1,), the host copy of pred_start, and the host counts N, G and total pairs (sum of n_pred * n_label)."""
+    if len(pred_list) != len(label_list):
+        raise ValueError("one label set per prediction set")
+    pred, pred_start = _pack_counted(pred_list, dev)
+    label, label_start = _pack_counted(label_list, dev)
+    pairs = int((np.diff(pred_start).astype(np.int64) * np.diff(label_start).astype(np.int64)).sum())
+    return (pred, torch.from_numpy(pred_start).to(dev), label, torch.from_numpy(label_start).to(dev), pred_start,
+            int(pred_start[-1]), int(label_start[-1]), pairs)
+
+
+def _match(pred_list, score_list, label_list, thr, mode):
+    """lisec_boxes_match on a list of samples.  Returns device tensors (best_iou, best_label, tp (T, N), tp_count (S, T), flat
+    scores) and the host counts N, G."""
+    if len(pred_list) != len(score_list):
+        raise ValueError("one score set per prediction set")
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    S, T = len(pred_list), len(thr)
+    pred, d_pred_start, label, d_label_start, pred_start, N, G, pairs = _pack_samples(pred_list, label_list, dev)
+    flat = [c.to(device=dev, dtype=torch.float64).reshape(-1) if torch.is_tensor(c)
+            else torch.from_numpy(np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1))) for c in score_list]
+    if [len(c) for c in flat] != np.diff(pred_start).tolist():
+        raise ValueError("every prediction needs exactly one score")
+    scores = torch.cat([c.to(dev) for c in flat] + [torch.zeros(1, dtype=torch.float64, device=dev)])
+    ws = torch.empty(max(lib.lisec_boxes_match_workspace_bytes(S, N, pairs, T), 1), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+    best_label = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    tp = torch.empty(T * max(N, 1), dtype=torch.uint8, device=dev)
+    tp_count = torch.empty((max(S, 1), T), dtype=torch.int32, device=dev)
+    _lib.check(lib.lisec_boxes_match(_lib.ptr(pred), _lib.ptr(scores), _lib.ptr(d_pred_start),
+                                     _lib.ptr(label), _lib.ptr(d_label_start), S, N, pairs,
+                                     (ctypes.c_double * T)(*thr.tolist()), T, mode, _lib.ptr(ws), ws.numel(),
+                                     _lib.ptr(best_iou), _lib.ptr(best_label), _lib.ptr(tp), _lib.ptr(tp_count),
+                                     _lib.current_stream()))
+    return best_iou[:N], best_label[:N], tp[:T * N].reshape(T, N), tp_count[:S], scores[:N], N, G
+
+
+def box_iou(predictBoxes, labelBoxes, mode='3d'):
+    """The (n_pred, n_label) float64 IoU matrix of one sample's predictions and labels (rows x, y, z, l, w, h, yaw; arrays or
+    device tensors; lisec_boxes_pair_iou).  mode='3d': inter = footprint overlap area * the CLAMPED z overlap of the two height
+    intervals [z - |h|/2, z + |h|/2], union = |l w h|_p + |l w h|_g - inter; mode='bev': the same with areas only.  A box with
+    l == 0 or w == 0 (or h == 0 in 3D mode) has IoU 0 with everything; a negative extent mirrors the footprint.  This IoU is
+    OURS, as bev_iou is: geometrically consistent, not the reference's calculateIoU (serialize_data.py:170-178), whose z term
+    takes the full height as half extent and is not clamped."""
+    mode = _iou_mode(mode)
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    pred, d_pred_start, label, d_label_start, _, N, G, pairs = _pack_samples([predictBoxes], [labelBoxes], dev)
+    ws = torch.empty(max(lib.lisec_boxes_match_workspace_bytes(1, N, 0, 1), 1), dtype=torch.uint8, device=dev)
+    out = torch.empty(max(pairs, 1), dtype=torch.float64, device=dev)
+    _lib.check(lib.lisec_boxes_pair_iou(_lib.ptr(pred), _lib.ptr(d_pred_start), _lib.ptr(label), _lib.ptr(d_label_start), 1, N,
+                                        pairs, mode, _lib.ptr(ws), ws.numel(), _lib.ptr(out), _lib.current_stream()))
+    return out[:pairs].cpu().numpy().reshape(N, G)
+
+
+def average_precision(pred_list, score_list, label_list, iou_thresholds=None, mode='3d'):
+    """Detection average precision of score-ranked boxes against annotations, over all samples of the lists (pred_list[s]
+    (k, 7), score_list[s] (k,), label_list[s] (m, 7); arrays or device tensors), PASCAL-VOC style:
+    rank all predictions by descending score (ties: sample index, then row); a prediction's candidate is the label of its own
+    sample with the largest box_iou (ties: lowest row); it is a true positive at threshold t when that IoU > t and no
+    earlier-ranked prediction took the label at t; AP(t) = area under the precision envelope over recall; mAP = their mean.
+    iou_thresholds: up to 16 values in [0, 1), default 0.5, 0.55, .., 0.95.  Matching and integration run on the device
+    (lisec_boxes_match, lisec_boxes_average_precision) with one copy back at the end.  Returns a DetectionAP.  No labels at all:
+    ValueError; no predictions: AP 0.  The IoU is ours (see box_iou) and the rule restates what the Lyft devkit is understood
+    to do: parity with it is unpinned."""
+    thr = _iou_thresholds(iou_thresholds)
+    mode = _iou_mode(mode)
+    if sum(len(_rows7(b)) for b in label_list) == 0:
+        raise ValueError("average precision is undefined without labels")
+    best_iou, best_label, tp, tp_count, scores, N, G = _match(pred_list, score_list, label_list, thr, mode)
+    lib = _lib.load()
+    nan = torch.isnan(scores).any()                                       # read with the results: no copy between the stages
+    rank = torch.sort(scores, descending=True, stable=True).indices       # plumbing: ties keep the flat (sample, row) order
+    ap = torch.empty(len(thr), dtype=torch.float64, device=scores.device)
+    _lib.check(lib.lisec_boxes_average_precision(_lib.ptr(rank) if N else None, _lib.ptr(tp) if N else None, N, G, len(thr),
+                                                 _lib.ptr(ap), None, _lib.current_stream()))
+    ap = ap.cpu().numpy()
+    if bool(nan):
+        raise ValueError("scores must not be NaN")
+    return DetectionAP(ap=ap, mAP=float(ap.mean()), thresholds=thr, tp=tp.cpu().numpy().astype(bool),
+                       tp_count=tp_count.cpu().numpy(), best_iou=best_iou.cpu().numpy(), best_label=best_label.cpu().numpy(),
+                       n_predictions=N, n_labels=G)

@@ -13,37 +13,6 @@
 namespace lisec {
 namespace {
 
-// area of the intersection of two convex quadrilaterals (Sutherland-Hodgman + shoelace)
-__device__ double quad_intersection_area(const Pt* pa, const Pt* qa) {
-    Pt p[4], q[4];
-    const bool pf = signed_area(pa, 4) < 0, qf = signed_area(qa, 4) < 0;
-    for (int i = 0; i < 4; ++i) { p[i] = pa[pf ? 3 - i : i]; q[i] = qa[qf ? 3 - i : i]; }
-    Pt bufA[10], bufB[10];
-    Pt* in = bufA;
-    Pt* out = bufB;
-    int n = 4;
-    for (int i = 0; i < 4; ++i) out[i] = p[i];
-    for (int e = 0; e < 4 && n > 0; ++e) {
-        Pt* t = in; in = out; out = t;
-        const int nin = n;
-        n = 0;
-        const Pt a = q[e], b = q[(e + 1) & 3];
-        const double ex = b.x - a.x, ey = b.y - a.y;
-        for (int j = 0; j < nin; ++j) {
-            const Pt c = in[j], d = in[j + 1 == nin ? 0 : j + 1];
-            const double sc = ex * (c.y - a.y) - ey * (c.x - a.x);
-            const double sd = ex * (d.y - a.y) - ey * (d.x - a.x);
-            if (sc >= 0) out[n++] = c;
-            if ((sc >= 0) != (sd >= 0)) {
-                const double t = sc / (sc - sd);
-                out[n++] = {c.x + t * (d.x - c.x), c.y + t * (d.y - c.y)};
-            }
-        }
-    }
-    if (n < 3) return 0.0;
-    return fabs(signed_area(out, n));
-}
-
 // calculateIoU (serialize_data.py:170-178): z overlap with the FULL height as half extent, not clamped
 __device__ double rot_iou(const double* b1, const double* b2) {
     // rectangles further apart than the sum of their circumradii: polygon area 0 -> IoU exactly 0

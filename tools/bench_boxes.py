@@ -70,3 +70,9 @@ if __name__ == "__main__":
     print(f"union_overlap  1000 samples x (20 pred, 40 label), one launch   GPU {t * 1e3:8.2f} ms  (median of 7, incl. packing + copy back)")
     t = median7(lambda: boxes.union_overlap(dev_p[:1], dev_l[:1]))
     print(f"union_overlap  1 sample (20 pred, 40 label)                     GPU {t * 1e3:8.3f} ms  (median of 7)")
+    # detection average precision (boxes.average_precision): the same 1000 samples with scores, and one sample alone
+    dev_s = [torch.from_numpy(rng.uniform(0.01, 0.99, 20)).cuda() for _ in scenes]
+    t = median7(lambda: boxes.average_precision(dev_p, dev_s, dev_l))
+    print(f"average_precision  1000 samples x (20 pred, 40 label), 10 thresholds   GPU {t * 1e3:8.2f} ms  (median of 7, incl. packing + copy back)")
+    t = median7(lambda: boxes.average_precision(dev_p[:1], dev_s[:1], dev_l[:1]))
+    print(f"average_precision  1 sample (20 pred, 40 label), 10 thresholds         GPU {t * 1e3:8.3f} ms  (median of 7)")
