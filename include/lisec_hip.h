@@ -960,6 +960,64 @@ int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_
                                   double* out_ap, double* out_curve, lisec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 5c. Training-time augmentation of a sweep with its boxes (VoxelNet section 3.3) and the label maps of the moved boxes,
+ *     on the device (csrc/augment.hip).  Not in the reference, which trains on fixed sweeps and precomputed labels.
+ *     Box rows are (x, y, z, l, w, h, yaw) float64 in ego-centred metres as boxes.annotationBoxes returns them; z is the box
+ *     CENTRE, the z extent [z - h/2, z + h/2].  The footprint is boxToShapely's (section 5): axes u = (cos yaw, -sin yaw)
+ *     with half extent w/2 and v = (sin yaw, cos yaw) with half extent l/2.  A point is inside a box iff |d.u| <= w/2,
+ *     |d.v| <= l/2 and z lies in the z extent (all closed); a point inside several boxes belongs to the lowest index.
+ *     Random numbers: Philox4x32-10, key = seed (low word, high word), counter = (stream, item, epoch, index), stream 0 =
+ *     global, 1 = per box, 2 = balance; uniform = (u32 + 0.5) * 2^-32 and Box-Muller normals (z0 = r cos t, z1 = r sin t,
+ *     r = sqrt(-2 ln u1), t = 2 pi u2), both in double.  Every entry only enqueues on `stream`: no host synchronisation.
+ *
+ * lisec_augment_draw, one workgroup.  Global: words w = Philox(0, item, epoch, 0): s = scale_lo + (scale_hi - scale_lo) *
+ *   u(w0), alpha = rot_global * (2 u(w1) - 1), a counter-clockwise rotation about the z axis through the origin.  Box b, in
+ *   index order, attempt a < attempts: w = Philox(1, item, epoch, 2 (b * LISEC_AUG_MAX_ATTEMPTS + a)), w' = the same at
+ *   index + 1; dyaw = rot_box * (2 u(w0) - 1), (dx, dy) = sigma[0..1] * BoxMuller(w1, w2), dz = sigma[2] * z0 of
+ *   BoxMuller(w'0, w'1).  The first attempt whose footprint (centre + (dx, dy), yaw + dyaw) has intersection area exactly
+ *   0 with the CURRENT footprint of every other box (perturbed for lower indices, original for higher ones) is accepted;
+ *   with none the box stays put.  Outputs (device): transforms double[n_boxes][4] = (dx, dy, dz, dyaw); global double[2] =
+ *   (s, alpha); boxes_out double[n_boxes][7] = the rows after both stages (centre moved, rotated and scaled; l, w, h
+ *   scaled; yaw + dyaw - alpha: with these axes a counter-clockwise turn lowers yaw); attempt int32[n_boxes] = the accepted
+ *   attempt or -1; draws uint32[4 + 8 n_boxes] = the global words, then per box the eight words (w, w') of the accepted
+ *   attempt (0 without one).  A parameter of 0 (attempts 0, scale_lo = scale_hi = 1) makes its stage the identity bit for
+ *   bit.  n_boxes > LISEC_AUG_MAX_BOXES or attempts > LISEC_AUG_MAX_ATTEMPTS: LISEC_EINVAL, nothing enqueued.
+ *
+ * lisec_augment_apply: points (n rows of `stride` elements, 3 used; dtype 0 = float32, 1 = float64) -> points_out (n x 3
+ *   dense, same dtype, may not alias), in double: a point inside box b of boxes_before keeps its (d.u, d.v, dz) in the
+ *   box's frame while the box takes transforms[b] (an all-zero row leaves its points bit for bit); then every point takes global (rotate, scale x, y and z).  Rows with
+ *   |x| >= pad_limit (the pad rows of a recorded step's point buffer) are copied untouched.  The point count is unchanged.
+ *
+ * lisec_rpn_targets: the label maps of one sweep.  boxes in ego metres; x, l are multiplied by scale_x and y, w by scale_y
+ *   (fixBoxScaling, serialize_data.py:181-191) on the device, lisec_rpn_labels sweeps anchors x boxes, and y_cls
+ *   float[outX*outY*2] = valid + overlap, y_reg float[outX*outY*14] = out_regress + repeat(overlap, 7) are written at the
+ *   caller's addresses.  balance != 0: the balancing of serialize_data.py:310-325 (at most max_regions/2 positives; when
+ *   negatives + kept positives exceed max_regions, as many negatives as positives kept) with, instead of random.sample,
+ *   the key (Philox(2, item, epoch, flat index)[0] << 32 | flat index) per candidate, flat index = (x * outY + y) * 2 +
+ *   anchor: the `keep` smallest keys of a class survive.  balance == 0: float32(preprocessLabels(balance=False)) bit for
+ *   bit. */
+#define LISEC_AUG_MAX_BOXES 512
+#define LISEC_AUG_MAX_ATTEMPTS 32
+typedef struct {
+    double rot_box;          /* per-box yaw noise: U[-rot_box, rot_box]                     (pi/10) */
+    double sigma[3];         /* per-box translation noise: N(0, sigma^2) per axis            (1, 1, 0) */
+    double scale_lo, scale_hi; /* global scale: U[scale_lo, scale_hi]                        (0.95, 1.05) */
+    double rot_global;       /* global rotation: U[-rot_global, rot_global]                 (pi/4) */
+    int attempts;            /* candidates per box                                          (10) */
+} lisec_augment_params;
+int lisec_augment_draw(const double* boxes, int n_boxes, const lisec_augment_params* params, unsigned long long seed,
+                       unsigned int item, unsigned int epoch, double* transforms, double* global, double* boxes_out,
+                       int32_t* attempt, uint32_t* draws, lisec_stream_t stream);
+int lisec_augment_apply(const void* points, int dtype, int n, int stride, const double* boxes_before, int n_boxes,
+                        const double* transforms, const double* global, double pad_limit, void* points_out,
+                        lisec_stream_t stream);
+size_t lisec_rpn_targets_workspace_bytes(const lisec_rpn_cfg* cfg, int n_boxes);
+int lisec_rpn_targets(const lisec_rpn_cfg* cfg, const double* boxes, int n_boxes, double scale_x, double scale_y,
+                      double iou_lo, double iou_hi, int balance, int max_regions, unsigned long long seed, unsigned int item,
+                      unsigned int epoch, void* workspace, size_t workspace_bytes, float* y_cls, float* y_reg,
+                      lisec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 5b. Step plans: a whole training step recorded once and re-issued by ONE call (csrc/plan.hip).
  *     The reference repeats one static schedule 180 times (model.fit(batch_size=1, steps_per_epoch=180),
  *     model_training.py:299).  Between lisec_step_plan_begin and lisec_step_plan_end every launch the CALLING THREAD makes

@@ -31,6 +31,15 @@ class RpnCfg(Structure):
                 ("anchors", (c_double * 4) * 2)]
 
 
+class AugmentParams(Structure):                # lisec_augment_params
+    _fields_ = [("rot_box", c_double), ("sigma", c_double * 3), ("scale_lo", c_double), ("scale_hi", c_double),
+                ("rot_global", c_double), ("attempts", c_int)]
+
+
+AUG_MAX_BOXES = 512                            # LISEC_AUG_MAX_BOXES
+AUG_MAX_ATTEMPTS = 32                          # LISEC_AUG_MAX_ATTEMPTS
+
+
 class BnSinkDesc(ctypes.Structure):           # lisec_bn_sink
     _fields_ = [("acc", c_void_p), ("kind", c_int), ("unbiased_moving", c_int), ("n_rows", c_double),
                 ("gamma", c_void_p), ("beta", c_void_p), ("moving_mean", c_void_p), ("moving_var", c_void_p),
@@ -159,6 +168,16 @@ def _declare(lib):
     lib.lisec_boxes_pair_iou.argtypes = [P, P, P, P, c_int, c_int, LL, c_int, P, c_size_t, P, P]
     lib.lisec_boxes_average_precision.restype = c_int
     lib.lisec_boxes_average_precision.argtypes = [P, P, c_int, c_int, c_int, P, P, P]
+    ULL, UI = ctypes.c_ulonglong, ctypes.c_uint
+    lib.lisec_augment_draw.restype = c_int
+    lib.lisec_augment_draw.argtypes = [P, c_int, POINTER(AugmentParams), ULL, UI, UI, P, P, P, P, P, P]
+    lib.lisec_augment_apply.restype = c_int
+    lib.lisec_augment_apply.argtypes = [P, c_int, c_int, c_int, P, c_int, P, P, c_double, P, P]
+    lib.lisec_rpn_targets_workspace_bytes.restype = c_size_t
+    lib.lisec_rpn_targets_workspace_bytes.argtypes = [POINTER(RpnCfg), c_int]
+    lib.lisec_rpn_targets.restype = c_int
+    lib.lisec_rpn_targets.argtypes = [POINTER(RpnCfg), P, c_int, c_double, c_double, c_double, c_double, c_int, c_int, ULL,
+                                      UI, UI, P, c_size_t, P, P, P]
     lib.lisec_lidar_transform.restype = c_int
     lib.lisec_lidar_transform.argtypes = [P, c_int, c_int, POINTER(c_double), POINTER(c_double), P, P]
     lib.lisec_vfe_grid_from_saved.restype = c_int

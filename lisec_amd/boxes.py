@@ -83,6 +83,44 @@ def preprocessLabels(data, seed=0, balance=True):
     return [valid + overlap, outreg + np.repeat(overlap, 7, axis=2)]
 
 
+_TARGET_WS = {}
+
+
+def rpnTargets(boxes, seed=0, item=0, epoch=0, balance=True, out=None):
+    """The label maps of one sweep made on the device (lisec_rpn_targets; ours, not the reference's): boxes (B, 7) rows
+    x, y, z, l, w, h, yaw in ego metres, numpy or a device tensor -> [y_cls (outX, outY, 2), y_reg (outX, outY, 14)] device
+    float32, written into `out` = [y_cls, y_reg] when given (the target buffers of a recorded step).  No copy to the host
+    and no wait.  balance=False equals float32(preprocessLabels(boxes, balance=False)) bit for bit; balance=True keeps at
+    most maxRegions/2 positives and, when there are too many, as many negatives as positives (serialize_data.py:310-325)
+    by the smallest Philox keys of (seed, item, epoch, anchor) -- reproducible, unlike the reference's random.sample."""
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    cfg = _cfg()
+    if torch.is_tensor(boxes):
+        d_boxes = boxes.to(device=dev, dtype=torch.float64).reshape(-1, 7).contiguous()
+    else:
+        d_boxes = torch.from_numpy(np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, 7))).to(dev)
+    B = int(d_boxes.shape[0])
+    if out is None:
+        out = [torch.empty((cfg.outX, cfg.outY, 2), dtype=torch.float32, device=dev),
+               torch.empty((cfg.outX, cfg.outY, 14), dtype=torch.float32, device=dev)]
+    y_cls, y_reg = out
+    for t, c in ((y_cls, 2), (y_reg, 14)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != cfg.outX * cfg.outY * c:
+            raise ValueError(f"out must be dense float32 maps of {cfg.outX} x {cfg.outY} x (2, 14)")
+    key = (str(dev), cfg.outX, cfg.outY)
+    need = lib.lisec_rpn_targets_workspace_bytes(ctypes.byref(cfg), max(B, 64))
+    if key not in _TARGET_WS or _TARGET_WS[key].numel() < need:
+        _TARGET_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _TARGET_WS[key]
+    _lib.check(lib.lisec_rpn_targets(ctypes.byref(cfg), _lib.ptr(d_boxes) if B else None, B, cfg.outX / Constants.nx,
+                                     cfg.outY / Constants.ny, float(Constants.iouLowerBound),
+                                     float(Constants.iouUpperBound), 1 if balance else 0, int(Constants.maxRegions),
+                                     int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff, int(epoch) & 0xffffffff,
+                                     _lib.ptr(ws), ws.numel(), _lib.ptr(y_cls), _lib.ptr(y_reg), _lib.current_stream()))
+    return [y_cls, y_reg]
+
+
 def _balance(valid, overlap, max_regions, seed):
     """serialize_data.py:310-325: keep <= maxRegions/2 positives and as many negatives as positives."""
     rng = random.Random(seed)

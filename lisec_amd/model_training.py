@@ -431,6 +431,12 @@ def _targets(ycls, yreg, rows, dev):
     return lambda i: (upload(ycls[i]), upload(yreg[i]))
 
 
+def _is_sequence(x):
+    """keras.utils.Sequence by its interface; lists, arrays and voxelised sweeps are not."""
+    return (not isinstance(x, (list, tuple, np.ndarray)) and all(callable(getattr(x, m, None))
+            for m in ("__getitem__", "__len__", "on_epoch_end")))
+
+
 def _refuse_mixed_training(policy):
     if policy.compute_dtype != "float32":
         raise NotImplementedError(
@@ -513,7 +519,7 @@ class Model:
             raise ValueError("expected SparseVoxels / list of them / dense (n,D,H,W,T,6) array")
         return [dense_to_sample(a, self.net.device) for a in arr]
 
-    def fit(self, x, y, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None,
+    def fit(self, x, y=None, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None,
             validation_split=0.0, validation_data=None, validation_steps=None, validation_freq=1):
         """fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, epochs=1, steps_per_epoch=180)
         (model_training.py:299).  batch_size must be 1 (the reference's setting: BatchNormalization
@@ -528,18 +534,32 @@ class Model:
         (validation_steps of them at most) with on_test_begin / on_test_end, and val_loss, val_ClassificationLayer_loss and
         val_RegressionLayer_loss join the logs of on_epoch_end and History.  The metrics of compile() are logged as epoch
         means under metrics_names, and with validation as val_<name>.  fit ends after any epoch whose callbacks set
-        model.stop_training."""
+        model.stop_training.
+        x may be a keras.utils.Sequence-like object (__len__, __getitem__(i) -> (points (n, >= 3), [y_cls, y_reg]),
+        on_epoch_end()), e.g. augment.AugmentedSweeps, with y=None: step st trains on item order[st], made when the step
+        stages its sweep, and on_epoch_end() is called after every epoch.  y given with it is a ValueError, as in Keras;
+        validation_split is refused (pass validation_data).  Everything else works as for lists."""
         _refuse_mixed_training(self.dtype_policy)
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if batch_size != 1:
             raise NotImplementedError("only batch_size=1, the reference's setting, is implemented")
-        samples = self._as_samples(x)
-        ycls = np.asarray(y[0], dtype=np.float32)
-        yreg = np.asarray(y[1], dtype=np.float32)
-        n = len(samples)
-        if len(ycls) < n or len(yreg) < n:
-            raise ValueError("fewer label maps than samples")
+        seq = x if _is_sequence(x) else None
+        if seq is not None:
+            if y is not None:
+                raise ValueError("`y` argument is not supported when using `keras.utils.Sequence` as input.")
+            if validation_split:
+                raise ValueError("`validation_split` is only supported for lists and arrays: pass validation_data")
+            samples, ycls, yreg, n = None, None, None, len(seq)
+        else:
+            if y is None:
+                raise ValueError("y=[outClass, outRegress] is required unless x is a Sequence")
+            samples = self._as_samples(x)
+            ycls = np.asarray(y[0], dtype=np.float32)
+            yreg = np.asarray(y[1], dtype=np.float32)
+            n = len(samples)
+            if len(ycls) < n or len(yreg) < n:
+                raise ValueError("fewer label maps than samples")
         val = None
         if validation_data is not None:
             if len(validation_data) > 2 and validation_data[2] is not None:
@@ -567,7 +587,8 @@ class Model:
         for cb in callbacks:
             cb.set_model(self)
             cb.set_params(dict(verbose=verbose, epochs=epochs, steps=steps))
-        target = _targets(ycls, yreg, range(n), dev)
+        target = _targets(ycls, yreg, range(n), dev) if seq is None else None
+        seq_req = self._sequence_request(seq) if seq is not None else None
         nm = loss_acc_len(self.loss) - 4                    # metrics of the compiled loss
         for cb in callbacks:
             cb.on_train_begin()
@@ -577,7 +598,7 @@ class Model:
             opt = self.optimizer.spec(device_lr=bool(callbacks))
             # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
             # the descriptor on this stream, behind the previous epoch's last update
-            captured = self._captured_step(samples, opt)
+            captured = self._captured_step(samples, opt, seq_req)
             self.net._sync_lr(opt)
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
@@ -590,6 +611,8 @@ class Model:
             def sweep(st, points=captured is not None):
                 """What step st trains on: (points of the sweep for a recorded step, else its voxel sample, y_cls, y_reg)."""
                 i = int(order[st % len(order)])
+                if seq is not None:
+                    return self._sequence_item(seq, i, points)
                 return (samples[i]._keepalive if points else samples[i], *target(i))
 
             for st in range(steps):
@@ -620,11 +643,43 @@ class Model:
                 cb.on_epoch_end(epoch, logs)
             for key, v in logs.items():
                 hist.history.setdefault(key, []).append(v)
+            if seq is not None:
+                seq.on_epoch_end()
             if self.stop_training:
                 break
         for cb in callbacks:
             cb.on_train_end()
         return hist
+
+    def _sequence_grid(self):
+        """The voxel grid of this model's input under the reference's voxel edges (what _preprocess voxelises with)."""
+        return (float(Constants.voxelx), float(Constants.voxely), float(Constants.voxelz), int(self.maxPoints),
+                self.nx // 2, self.ny // 2, self.nz)
+
+    def _sequence_request(self, seq):
+        """_plan_request for a Sequence of raw sweeps: the capacity is its largest point count (`max_points`; augmentation
+        keeps the count), the point dtype its `dtype`; a Sequence without them is walked once to find them."""
+        need, dtype = getattr(seq, "max_points", None), getattr(seq, "dtype", None)
+        if need is None or dtype is None:
+            pts = [torch.as_tensor(seq[i][0]) for i in range(len(seq))]
+            need = max((int(p.shape[0]) for p in pts), default=0)
+            dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
+        grid = self._sequence_grid()
+        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
+        return key, grid, dtype, int(need), max(1024, -(-int(need) // 4096) * 4096)
+
+    def _sequence_item(self, seq, i, recorded):
+        """What a step trains on when x is a Sequence: for a recorded step the item as something that stages itself into
+        the step's buffers (AugmentedSweeps.staged) or its (points, y_cls, y_reg); for the Python schedule the voxelised
+        sweep and its targets."""
+        if recorded and hasattr(seq, "staged"):
+            return seq.staged(i), None, None
+        pts, (y_cls, y_reg) = seq[i]
+        if recorded:
+            return pts, y_cls, y_reg
+        dev = self.net.device
+        vox = VFE_preprocessing(pts, *self._sequence_grid()).sample
+        return (vox, torch.as_tensor(y_cls, dtype=torch.float32).to(dev), torch.as_tensor(y_reg, dtype=torch.float32).to(dev))
 
     def _plan_request(self, samples):
         """What a recorded plan for these samples takes: (cache key without the optimizer, the one voxel grid, point
@@ -638,12 +693,14 @@ class Model:
         key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
         return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096)     # a little head-room for later calls
 
-    def _captured_step(self, samples, opt):
+    def _captured_step(self, samples, opt, seq_req=None):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
         Otherwise (None) the Python schedule issues every step."""
-        req = self._plan_request(samples) if _lib.knob("step_plan", True) else None
+        req = None
+        if _lib.knob("step_plan", True):
+            req = self._plan_request(samples) if seq_req is None else seq_req
         if req is None:
             return None
         key, grid, dtype, need, capacity = req
@@ -969,6 +1026,26 @@ def train(samples, level5Data, save_path):
 def train_with_model(samples, level5Data, model_path, save_path):
     """train_with_model(samples, level5Data, model_path, save_path) (model_training.py:305-346)."""
     return _train(samples, level5Data, save_path, model_path)
+
+
+def train_augmented(samples, level5Data, save_path, epochs=1, seed=0):
+    """OURS, not the reference's: train() on sweeps that are augmented anew at every step (augment.AugmentedSweeps: per-box
+    noise with collision rejection, one global scale and rotation, VoxelNet section 3.3) with the label maps of the moved
+    boxes made on the device (boxes.rpnTargets) instead of the precomputed labels3/*.npy.  The sweeps come from
+    combine_lidar_data_gpu, the boxes from boxes.annotationBoxes; one pass over the samples per epoch, the reference's
+    SGD.  Returns the model, saved at save_path."""
+    from . import augment, boxes
+    _refuse_mixed_training(mixed_precision.global_policy())
+    points = [combine_lidar_data_gpu(s, Constants.lyft_data_dir, level5Data) for s in samples]
+    rows = [boxes.annotationBoxes(s, level5Data) for s in samples]
+    model = createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints)
+    sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
+    model.compile(optimizer=sgd, loss=['mse', 'mse'])
+    history = model.fit(x=augment.AugmentedSweeps(points, rows, seed=seed), batch_size=1, verbose=1, epochs=epochs)
+    if model.dp is None or model.dp.rank == 0:
+        print(history.history)
+    model.save(save_path)
+    return model
 
 
 def _lyft_dataset():

@@ -1360,8 +1360,16 @@ class _StepPlans:
 
     def _load(self, j, points, ycls, yreg):
         """Stages one sweep into buffer set j: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets
-        (Ho,Wo,2|14)."""
+        (Ho,Wo,2|14) -- or `points` an object with stage_into(points, y_cls, y_reg) -> n that fills the buffers itself."""
         self._check_stream()
+        stage = getattr(points, "stage_into", None)
+        if stage is not None:
+            # an item of a Sequence that makes its sweep on the device (augment.AugmentedSweeps): its kernels write the
+            # points and both target maps of this buffer set themselves, on this stream, in front of the replay
+            n = stage(self.points[j], self.ycls[j], self.yreg[j])
+            if n < self.capacity:
+                self.points[j][n:].fill_(self.PAD)
+            return
         pts = torch.as_tensor(points)
         n = int(pts.shape[0])
         if n > self.capacity:

@@ -1,6 +1,7 @@
 """Thin Python wrappers over the dense-contraction entry points of the C ABI (include/lisec_hip.h
 section 3).  Tensors are torch CUDA tensors used purely as device memory."""
 import ctypes
+import math
 
 import torch
 
@@ -654,3 +655,45 @@ class HeadShuffle:
     def run(self, head, backward=False):
         _lib.check(_lib.load().lisec_head_shuffle(_lib.ptr(head), self.Ho, self.Wo, self.n, self.T, self.ps,
                                                   1 if backward else 0, _lib.current_stream()))
+
+
+# ---- training-time augmentation (include/lisec_hip.h section 5c) ----------------------------------------------------------
+def augment_params(rot_box=math.pi / 10, sigma=(1.0, 1.0, 0.0), scale=(0.95, 1.05), rot_global=math.pi / 4, attempts=10):
+    """lisec_augment_params with VoxelNet's defaults (section 3.3 of the paper; z noise 0: the grid is 2 m tall)."""
+    p = _lib.AugmentParams()
+    p.rot_box, p.rot_global, p.attempts = float(rot_box), float(rot_global), int(attempts)
+    p.scale_lo, p.scale_hi = float(scale[0]), float(scale[1])
+    for i in range(3):
+        p.sigma[i] = float(sigma[i])
+    return p
+
+
+def augment_draw(boxes, params, seed=0, item=0, epoch=0):
+    """lisec_augment_draw on device rows boxes (B, 7) float64.  Returns device tensors (transforms (B, 4), global (2,),
+    boxes_out (B, 7), attempt (B,) int32, draws (4 + 8 B,) uint32 held as int32 bits)."""
+    B, dev = int(boxes.shape[0]), boxes.device
+    transforms = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    glob = torch.empty(2, dtype=torch.float64, device=dev)
+    boxes_out = torch.empty((B, 7), dtype=torch.float64, device=dev)
+    attempt = torch.empty(B, dtype=torch.int32, device=dev)
+    draws = torch.empty(4 + 8 * B, dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().lisec_augment_draw(_lib.ptr(boxes) if B else None, B, ctypes.byref(params),
+                                              int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff, int(epoch) & 0xffffffff,
+                                              _lib.ptr(transforms) if B else None, _lib.ptr(glob),
+                                              _lib.ptr(boxes_out) if B else None, _lib.ptr(attempt) if B else None,
+                                              _lib.ptr(draws), _lib.current_stream()))
+    return transforms, glob, boxes_out, attempt, draws
+
+
+def augment_apply(points, boxes, transforms, glob, out, pad_limit):
+    """lisec_augment_apply: device points (n, >= 3) float32 / float64 with unit element stride -> out (n, 3) dense, same dtype."""
+    n, B = int(points.shape[0]), int(boxes.shape[0])
+    if points.dtype != out.dtype or points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("points and out must share one of float32 / float64")
+    if n and (points.stride(1) != 1 or not out.is_contiguous() or tuple(out.shape) != (n, 3)):
+        raise ValueError("points need unit element stride, out must be dense (n, 3)")
+    _lib.check(_lib.load().lisec_augment_apply(_lib.ptr(points) if n else None, 0 if points.dtype == torch.float32 else 1, n,
+                                               int(points.stride(0)) if n else 3, _lib.ptr(boxes) if B else None, B,
+                                               _lib.ptr(transforms) if B else None, _lib.ptr(glob), float(pad_limit),
+                                               _lib.ptr(out) if n else None, _lib.current_stream()))
+    return out

@@ -1,9 +1,11 @@
 """Throughput of the reference-named surface: Model.fit(batch_size=1) on voxelised sweeps (GPU box only).
 
-    python tools/bench_fit.py [--lr constant|cosine]
+    python tools/bench_fit.py [--lr constant|cosine] [--cloud u20k|r200k] [--augment]
 
 --lr cosine trains with optimizers.schedules.CosineDecay (the update kernels read lr_t from the device descriptor)
-instead of the reference's constant rate."""
+instead of the reference's constant rate.  --augment adds, beside plain fit on the same sweeps, fit(x=AugmentedSweeps) with
+about 50 boxes per sweep (augmentation, label maps and balancing made on the device at every step), fit on the same Sequence
+with augment=False (the label kernels alone), and the stand-alone device times of the three entries."""
 import argparse
 import os
 import sys
@@ -12,16 +14,19 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from bench import synthetic_targets, u20k_cloud
+from bench import event_time_ms, r200k_cloud, synthetic_targets, u20k_cloud
 from lisec_amd import Constants
 from lisec_amd import model_training as mt
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--lr", choices=("constant", "cosine"), default="constant")
+    ap.add_argument("--cloud", choices=("u20k", "r200k"), default="u20k")
+    ap.add_argument("--augment", action="store_true")
     args = ap.parse_args()
     n = 4
-    pts = [u20k_cloud(i).astype(np.float64) for i in range(n)]
+    cloud = u20k_cloud if args.cloud == "u20k" else r200k_cloud
+    pts = [cloud(i).astype(np.float64) for i in range(n)]
     samples = [mt.VFE_preprocessing(p, Constants.voxelx, Constants.voxely, Constants.voxelz, Constants.maxPoints,
                                     Constants.nx // 2, Constants.ny // 2, Constants.nz) for p in pts]
     tg = [synthetic_targets(i, Constants.nx // 2, Constants.ny // 2) for i in range(n)]
@@ -37,4 +42,43 @@ if __name__ == "__main__":
     hist = model.fit(x=samples, y=[ycls, yreg], batch_size=1, verbose=0, epochs=1, steps_per_epoch=steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(f"Model.fit (lr {args.lr}): {steps / dt:.1f} steps/s ({1e3 * dt / steps:.2f} ms/step), loss {hist.history['loss'][-1]:.4f}")
+    print(f"Model.fit (lr {args.lr}, {args.cloud}): {steps / dt:.1f} steps/s ({1e3 * dt / steps:.2f} ms/step), "
+          f"loss {hist.history['loss'][-1]:.4f}")
+    if args.augment:
+        from lisec_amd import augment, boxes, ops
+        rng = np.random.default_rng(0)
+        bxs = []
+        for i in range(n):                      # ~50 cars on a jittered 12 m lattice inside +-45 m
+            cells = rng.permutation(49)[:50 - i]
+            bxs.append(np.array([[-42 + 12 * (c % 7) + rng.uniform(-2, 2), -42 + 12 * (c // 7) + rng.uniform(-2, 2), 1.0,
+                                  rng.uniform(3.8, 4.8), rng.uniform(1.7, 2.0), 1.6, rng.uniform(-3.1, 3.1)] for c in cells]))
+        for label, kw in (("augmented", {}), ("labels only (augment=False)", dict(augment=False))):
+            seq = augment.AugmentedSweeps(pts, bxs, seed=1, **kw)
+            model.fit(x=seq, batch_size=1, verbose=0, epochs=1, steps_per_epoch=20)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            hist = model.fit(x=seq, batch_size=1, verbose=0, epochs=1, steps_per_epoch=steps)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"Model.fit on AugmentedSweeps, {label}: {steps / dt:.1f} steps/s ({1e3 * dt / steps:.2f} ms/step), "
+                  f"loss {hist.history['loss'][-1]:.4f}")
+        seq = augment.AugmentedSweeps(pts, bxs, seed=1)
+        src, bx = seq.points[0], seq.boxes[0]
+        out = torch.empty((src.shape[0], 3), dtype=src.dtype, device=src.device)
+        tr, glob, bx_out, _, _ = ops.augment_draw(bx, seq.params, 1, 0, 0)
+        maps = boxes.rpnTargets(bx_out)
+        seq.stage(0, out, *maps)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(200):
+            seq.stage(0, out, *maps)
+        host = time.perf_counter() - t0          # the enqueue alone: read before the device is waited for
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t0
+        print(f"one staged item (draw + apply + targets): host enqueue {1e3 * host / 200:.3f} ms, "
+              f"device-bound {1e3 * total / 200:.3f} ms")
+        print(f"lisec_augment_draw  ({len(bx)} boxes): {1e3 * event_time_ms(lambda: ops.augment_draw(bx, seq.params, 1, 0, 0), 50):.1f} us")
+        print(f"lisec_augment_apply ({src.shape[0]} points): "
+              f"{1e3 * event_time_ms(lambda: ops.augment_apply(src, bx, tr, glob, out, augment.PAD_LIMIT), 50):.1f} us")
+        for bal in (False, True):
+            print(f"lisec_rpn_targets   (balance={bal}): {1e3 * event_time_ms(lambda: boxes.rpnTargets(bx_out, balance=bal, out=maps), 50):.1f} us")
