@@ -967,7 +967,7 @@ int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_
  *     with half extent w/2 and v = (sin yaw, cos yaw) with half extent l/2.  A point is inside a box iff |d.u| <= w/2,
  *     |d.v| <= l/2 and z lies in the z extent (all closed); a point inside several boxes belongs to the lowest index.
  *     Random numbers: Philox4x32-10, key = seed (low word, high word), counter = (stream, item, epoch, index), stream 0 =
- *     global, 1 = per box, 2 = balance; uniform = (u32 + 0.5) * 2^-32 and Box-Muller normals (z0 = r cos t, z1 = r sin t,
+ *     global, 1 = per box, 2 = balance, 3 = object sampling; uniform = (u32 + 0.5) * 2^-32 and Box-Muller normals (z0 = r cos t, z1 = r sin t,
  *     r = sqrt(-2 ln u1), t = 2 pi u2), both in double.  Every entry only enqueues on `stream`: no host synchronisation.
  *
  * lisec_augment_draw, one workgroup.  Global: words w = Philox(0, item, epoch, 0): s = scale_lo + (scale_hi - scale_lo) *
@@ -995,9 +995,43 @@ int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_
  *   negatives + kept positives exceed max_regions, as many negatives as positives kept) with, instead of random.sample,
  *   the key (Philox(2, item, epoch, flat index)[0] << 32 | flat index) per candidate, flat index = (x * outY + y) * 2 +
  *   anchor: the `keep` smallest keys of a class survive.  balance == 0: float32(preprocessLabels(balance=False)) bit for
- *   bit. */
+ *   bit.
+ *
+ * Ground-truth object sampling (Yan et al., SECOND, 2018, section 3.2): objects cut out of other training sweeps are pasted
+ *   into the current one, collision-checked, BEFORE the noise above is applied.
+ *   Database: a flat list of M objects.  Object m is a box row in the ego frame of its source sweep plus the points that box
+ *   OWNS under the rule above (closed slab test, lowest box index), in the source sweep's point order and dtype, as absolute
+ *   coordinates: db_boxes double[M][7], db_points [P][3], db_offsets int32[M + 1] (object m owns rows db_offsets[m] ..
+ *   db_offsets[m + 1]).  Objects are pasted at their original pose (the lidar sampling pattern depends on range and
+ *   bearing).  Which objects enter the database (a minimum point count) is the builder's business.
+ * lisec_augment_owner: owner int32[n] = the lowest box index holding the point, -1 for none and for pad rows
+ *   (|x| >= pad_limit).  What the database is cut out with; the grouping after it is the caller's.
+ * lisec_augment_sample, one workgroup.  Philox stream 3: candidate k < n_samples draws w = Philox(3, item, epoch, k) and has
+ *   database index (uint64(w0) * M) >> 32 (integer arithmetic).  Candidate k is ACCEPTED iff its footprint has intersection
+ *   area exactly 0 with every scene box and with every candidate m < k that was itself accepted: a candidate that collides
+ *   only with a rejected earlier one is accepted; the same index drawn twice rejects the second draw by itself; an object
+ *   from the item's own sweep collides with its original.  No special cases.  Outputs (device): index int32[n_samples] = the
+ *   database index or -1 when rejected; n_boxes_out int32[1] = n_boxes + accepted; boxes_all double[n_boxes + n_samples][7]
+ *   = the scene rows, then the accepted rows compacted in order of k, rows past n_boxes_out zero; point_offset
+ *   int32[n_samples + 1] = the exclusive prefix of the accepted objects' point counts (a rejected candidate counts 0), the
+ *   last entry n_add; draws uint32[4 n_samples] = the words.  M == 0 accepts nothing.  n_samples > LISEC_AUG_MAX_SAMPLES or
+ *   n_boxes + n_samples > LISEC_AUG_MAX_BOXES: LISEC_EINVAL, nothing enqueued (refused, not truncated).
+ * lisec_augment_paste: points_out has `cap` rows of 3 in the points' dtype (db_points has the same dtype), cap >= n + n_add --
+ *   the caller sizes it by the sum of the n_samples largest point counts of the database, which needs no readback; rows past
+ *   cap are never written.  Rows [0, n): the scene point (3 of `stride` elements); a live one (|x| < pad_limit) inside an
+ *   accepted pasted box (rows n_scene_boxes .. *n_boxes_dev of boxes_all, the closed test) becomes (pad, pad, pad), pad = 2 *
+ *   pad_limit; input pad rows are copied untouched.  Rows [n, n + n_add): the accepted objects in order of k, each object's
+ *   points in database order, copied bit for bit.  Rows [n + n_add, cap): (pad, pad, pad).  May not alias the input.
+ * lisec_augment_draw_n, lisec_augment_apply_n, lisec_rpn_targets_n: the entries above with the box count read from the
+ *   device (n_boxes_dev int32[1], what lisec_augment_sample wrote: the number of accepted objects is known only there);
+ *   max_boxes >= that count sizes the workspaces and the launch geometry, the kernels bound their loops by min(*n_boxes_dev,
+ *   max_boxes).  Rows past the count are neither read nor written.  For equal counts the results equal the host-count
+ *   entries' bit for bit.  lisec_rpn_targets_workspace_bytes(cfg, max_boxes) serves both.
+ *   The pipeline of one training item: sample, paste into a scratch buffer, draw_n (pasted boxes take the per-box noise too),
+ *   apply_n from the scratch into the step's point buffer, rpn_targets_n. */
 #define LISEC_AUG_MAX_BOXES 512
 #define LISEC_AUG_MAX_ATTEMPTS 32
+#define LISEC_AUG_MAX_SAMPLES 64
 typedef struct {
     double rot_box;          /* per-box yaw noise: U[-rot_box, rot_box]                     (pi/10) */
     double sigma[3];         /* per-box translation noise: N(0, sigma^2) per axis            (1, 1, 0) */
@@ -1016,6 +1050,26 @@ int lisec_rpn_targets(const lisec_rpn_cfg* cfg, const double* boxes, int n_boxes
                       double iou_lo, double iou_hi, int balance, int max_regions, unsigned long long seed, unsigned int item,
                       unsigned int epoch, void* workspace, size_t workspace_bytes, float* y_cls, float* y_reg,
                       lisec_stream_t stream);
+int lisec_augment_owner(const void* points, int dtype, int n, int stride, const double* boxes, int n_boxes,
+                        double pad_limit, int32_t* owner, lisec_stream_t stream);
+int lisec_augment_sample(const double* boxes, int n_boxes, const double* db_boxes, const int32_t* db_offsets, int n_objects,
+                         int n_samples, unsigned long long seed, unsigned int item, unsigned int epoch, int32_t* index,
+                         int32_t* n_boxes_out, double* boxes_all, int32_t* point_offset, uint32_t* draws,
+                         lisec_stream_t stream);
+int lisec_augment_paste(const void* points, int dtype, int n, int stride, const void* db_points, const int32_t* db_offsets,
+                        const int32_t* index, const int32_t* point_offset, const double* boxes_all, int n_scene_boxes,
+                        const int32_t* n_boxes_dev, int n_samples, double pad_limit, void* points_out, int cap,
+                        lisec_stream_t stream);
+int lisec_augment_draw_n(const double* boxes, const int32_t* n_boxes_dev, int max_boxes, const lisec_augment_params* params,
+                         unsigned long long seed, unsigned int item, unsigned int epoch, double* transforms, double* global,
+                         double* boxes_out, int32_t* attempt, uint32_t* draws, lisec_stream_t stream);
+int lisec_augment_apply_n(const void* points, int dtype, int n, int stride, const double* boxes_before,
+                          const int32_t* n_boxes_dev, int max_boxes, const double* transforms, const double* global,
+                          double pad_limit, void* points_out, lisec_stream_t stream);
+int lisec_rpn_targets_n(const lisec_rpn_cfg* cfg, const double* boxes, const int32_t* n_boxes_dev, int max_boxes,
+                        double scale_x, double scale_y, double iou_lo, double iou_hi, int balance, int max_regions,
+                        unsigned long long seed, unsigned int item, unsigned int epoch, void* workspace,
+                        size_t workspace_bytes, float* y_cls, float* y_reg, lisec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * 5b. Step plans: a whole training step recorded once and re-issued by ONE call (csrc/plan.hip).

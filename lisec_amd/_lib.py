@@ -38,6 +38,7 @@ class AugmentParams(Structure):                # lisec_augment_params
 
 AUG_MAX_BOXES = 512                            # LISEC_AUG_MAX_BOXES
 AUG_MAX_ATTEMPTS = 32                          # LISEC_AUG_MAX_ATTEMPTS
+AUG_MAX_SAMPLES = 64                           # LISEC_AUG_MAX_SAMPLES
 
 
 class BnSinkDesc(ctypes.Structure):           # lisec_bn_sink
@@ -178,6 +179,19 @@ def _declare(lib):
     lib.lisec_rpn_targets.restype = c_int
     lib.lisec_rpn_targets.argtypes = [POINTER(RpnCfg), P, c_int, c_double, c_double, c_double, c_double, c_int, c_int, ULL,
                                       UI, UI, P, c_size_t, P, P, P]
+    lib.lisec_augment_owner.restype = c_int
+    lib.lisec_augment_owner.argtypes = [P, c_int, c_int, c_int, P, c_int, c_double, P, P]
+    lib.lisec_augment_sample.restype = c_int
+    lib.lisec_augment_sample.argtypes = [P, c_int, P, P, c_int, c_int, ULL, UI, UI, P, P, P, P, P, P]
+    lib.lisec_augment_paste.restype = c_int
+    lib.lisec_augment_paste.argtypes = [P, c_int, c_int, c_int, P, P, P, P, P, c_int, P, c_int, c_double, P, c_int, P]
+    lib.lisec_augment_draw_n.restype = c_int
+    lib.lisec_augment_draw_n.argtypes = [P, P, c_int, POINTER(AugmentParams), ULL, UI, UI, P, P, P, P, P, P]
+    lib.lisec_augment_apply_n.restype = c_int
+    lib.lisec_augment_apply_n.argtypes = [P, c_int, c_int, c_int, P, P, c_int, P, P, c_double, P, P]
+    lib.lisec_rpn_targets_n.restype = c_int
+    lib.lisec_rpn_targets_n.argtypes = [POINTER(RpnCfg), P, P, c_int, c_double, c_double, c_double, c_double, c_int, c_int,
+                                        ULL, UI, UI, P, c_size_t, P, P, P]
     lib.lisec_lidar_transform.restype = c_int
     lib.lisec_lidar_transform.argtypes = [P, c_int, c_int, POINTER(c_double), POINTER(c_double), P, P]
     lib.lisec_vfe_grid_from_saved.restype = c_int

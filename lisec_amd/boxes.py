@@ -86,13 +86,15 @@ def preprocessLabels(data, seed=0, balance=True):
 _TARGET_WS = {}
 
 
-def rpnTargets(boxes, seed=0, item=0, epoch=0, balance=True, out=None):
+def rpnTargets(boxes, seed=0, item=0, epoch=0, balance=True, out=None, n_boxes=None):
     """The label maps of one sweep made on the device (lisec_rpn_targets; ours, not the reference's): boxes (B, 7) rows
     x, y, z, l, w, h, yaw in ego metres, numpy or a device tensor -> [y_cls (outX, outY, 2), y_reg (outX, outY, 14)] device
     float32, written into `out` = [y_cls, y_reg] when given (the target buffers of a recorded step).  No copy to the host
     and no wait.  balance=False equals float32(preprocessLabels(boxes, balance=False)) bit for bit; balance=True keeps at
     most maxRegions/2 positives and, when there are too many, as many negatives as positives (serialize_data.py:310-325)
-    by the smallest Philox keys of (seed, item, epoch, anchor) -- reproducible, unlike the reference's random.sample."""
+    by the smallest Philox keys of (seed, item, epoch, anchor) -- reproducible, unlike the reference's random.sample.
+    n_boxes: a device int32 (1,) holding the number of rows of `boxes` that count (lisec_rpn_targets_n: the count
+    augment.sample_objects leaves on the device); the rows past it are ignored."""
     dev = _lib.require_gpu()
     lib = _lib.load()
     cfg = _cfg()
@@ -113,11 +115,15 @@ def rpnTargets(boxes, seed=0, item=0, epoch=0, balance=True, out=None):
     if key not in _TARGET_WS or _TARGET_WS[key].numel() < need:
         _TARGET_WS[key] = torch.empty(need, dtype=torch.uint8, device=dev)
     ws = _TARGET_WS[key]
-    _lib.check(lib.lisec_rpn_targets(ctypes.byref(cfg), _lib.ptr(d_boxes) if B else None, B, cfg.outX / Constants.nx,
-                                     cfg.outY / Constants.ny, float(Constants.iouLowerBound),
-                                     float(Constants.iouUpperBound), 1 if balance else 0, int(Constants.maxRegions),
-                                     int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff, int(epoch) & 0xffffffff,
-                                     _lib.ptr(ws), ws.numel(), _lib.ptr(y_cls), _lib.ptr(y_reg), _lib.current_stream()))
+    tail = (cfg.outX / Constants.nx, cfg.outY / Constants.ny, float(Constants.iouLowerBound), float(Constants.iouUpperBound),
+            1 if balance else 0, int(Constants.maxRegions), int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff,
+            int(epoch) & 0xffffffff, _lib.ptr(ws), ws.numel(), _lib.ptr(y_cls), _lib.ptr(y_reg), _lib.current_stream())
+    if n_boxes is None:
+        _lib.check(lib.lisec_rpn_targets(ctypes.byref(cfg), _lib.ptr(d_boxes) if B else None, B, *tail))
+    else:
+        if n_boxes.dtype != torch.int32 or n_boxes.numel() != 1 or n_boxes.device != d_boxes.device:
+            raise ValueError("n_boxes must be one int32 on the device")
+        _lib.check(lib.lisec_rpn_targets_n(ctypes.byref(cfg), _lib.ptr(d_boxes) if B else None, _lib.ptr(n_boxes), B, *tail))
     return [y_cls, y_reg]
 
 

@@ -167,12 +167,14 @@ __device__ __forceinline__ size_t wrapped_index(const lisec_rpn_cfg& cfg, int xV
 }
 
 // one thread per anchor, boxes visited in order (the per-anchor state machine of :235-294)
-__global__ void k_label_anchors(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B, double iou_lo,
-                                double iou_hi, double* __restrict__ valid, double* __restrict__ overlap,
+// (every label kernel: n_dev, when given, is the box count on the device and B only its upper bound)
+__global__ void k_label_anchors(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B, const int* __restrict__ n_dev,
+                                double iou_lo, double iou_hi, double* __restrict__ valid, double* __restrict__ overlap,
                                 double* __restrict__ out_reg, unsigned long long* __restrict__ best_iou_bits,
                                 int* __restrict__ count) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * cfg.outX * cfg.outY) return;
+    if (n_dev) B = min(B, max(*n_dev, 0));
     const Anchor A = make_anchor(cfg, i);
     if (!A.in_range) return;
     int type = 0;                                             // 0 neg, 1 neutral, 2 pos
@@ -199,11 +201,12 @@ __global__ void k_label_anchors(lisec_rpn_cfg cfg, const double* __restrict__ fi
 }
 
 // first anchor (in loop order) attaining each box's best IoU: `iou > bestIouForBox` keeps the first (:266-269)
-__global__ void k_label_best_order(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B,
+__global__ void k_label_best_order(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B, const int* __restrict__ n_dev,
                                    const unsigned long long* __restrict__ best_iou_bits,
                                    int* __restrict__ best_order) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * cfg.outX * cfg.outY) return;
+    if (n_dev) B = min(B, max(*n_dev, 0));
     const Anchor A = make_anchor(cfg, i);
     if (!A.in_range) return;
     for (int b = 0; b < B; ++b) {
@@ -215,11 +218,12 @@ __global__ void k_label_best_order(lisec_rpn_cfg cfg, const double* __restrict__
 }
 
 // boxes without a positive anchor get their best one (:297-307), in box order like the reference loop
-__global__ void k_label_fixup(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B,
+__global__ void k_label_fixup(lisec_rpn_cfg cfg, const double* __restrict__ fixed, int B, const int* __restrict__ n_dev,
                               const unsigned long long* __restrict__ best_iou_bits,
                               const int* __restrict__ best_order, const int* __restrict__ count,
                               double* __restrict__ valid, double* __restrict__ overlap, double* __restrict__ out_reg) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (n_dev) B = min(B, max(*n_dev, 0));
     for (int b = 0; b < B; ++b) {
         if (count[b] != 0 || best_iou_bits[b] == 0ull) continue;
         const Anchor A = make_anchor(cfg, best_order[b]);
@@ -320,6 +324,15 @@ extern "C" size_t lisec_rpn_labels_workspace_bytes(int n_boxes) {
 extern "C" int lisec_rpn_labels(const lisec_rpn_cfg* cfg, const double* fixed_boxes, int n_boxes, double iou_lo,
                                 double iou_hi, void* workspace, size_t workspace_bytes, double* valid,
                                 double* overlap, double* out_regress, lisec_stream_t stream_) {
+    return rpn_labels_counted(cfg, fixed_boxes, n_boxes, nullptr, iou_lo, iou_hi, workspace, workspace_bytes, valid, overlap,
+                              out_regress, stream_);
+}
+
+// lisec_rpn_labels, and the same with the box count on the device (n_dev; n_boxes is then its upper bound, which sizes the
+// workspace and decides the launches: lisec_rpn_targets_n)
+int lisec::rpn_labels_counted(const lisec_rpn_cfg* cfg, const double* fixed_boxes, int n_boxes, const int32_t* n_dev,
+                              double iou_lo, double iou_hi, void* workspace, size_t workspace_bytes, double* valid,
+                              double* overlap, double* out_regress, lisec_stream_t stream_) {
     if (int rc = check_cfg(cfg)) return rc;
     LISEC_CHECK_ARG(n_boxes >= 0 && workspace && valid && overlap && out_regress && (n_boxes == 0 || fixed_boxes),
                     "bad arguments");
@@ -340,13 +353,13 @@ extern "C" int lisec_rpn_labels(const lisec_rpn_cfg* cfg, const double* fixed_bo
     LISEC_HIP_TRY(hipMemsetAsync(count, 0, sizeof(int) * (n_boxes + 1), st));
     LISEC_HIP_TRY(hipMemsetAsync(best_order, 0x7f, sizeof(int) * (n_boxes + 1), st));
     const int n = 2 * (int)cells;
-    LISEC_LAUNCH(k_label_anchors, dim3(cdiv(n, 128)), dim3(128), 0, st, *cfg, fixed_boxes, n_boxes, iou_lo, iou_hi,
-                       valid, overlap, out_regress, best_bits, count);
+    LISEC_LAUNCH(k_label_anchors, dim3(cdiv(n, 128)), dim3(128), 0, st, *cfg, fixed_boxes, n_boxes, n_dev, iou_lo,
+                 iou_hi, valid, overlap, out_regress, best_bits, count);
     if (n_boxes > 0) {
-        LISEC_LAUNCH(k_label_best_order, dim3(cdiv(n, 128)), dim3(128), 0, st, *cfg, fixed_boxes, n_boxes, best_bits,
-                           best_order);
-        LISEC_LAUNCH(k_label_fixup, dim3(1), dim3(64), 0, st, *cfg, fixed_boxes, n_boxes, best_bits, best_order,
-                           count, valid, overlap, out_regress);
+        LISEC_LAUNCH(k_label_best_order, dim3(cdiv(n, 128)), dim3(128), 0, st, *cfg, fixed_boxes, n_boxes, n_dev,
+                     best_bits, best_order);
+        LISEC_LAUNCH(k_label_fixup, dim3(1), dim3(64), 0, st, *cfg, fixed_boxes, n_boxes, n_dev, best_bits,
+                     best_order, count, valid, overlap, out_regress);
     }
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;

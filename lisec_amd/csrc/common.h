@@ -69,6 +69,11 @@ inline void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, 
 }
 #define LISEC_LAUNCH(...) ::lisec::launch(__VA_ARGS__)
 
+// lisec_rpn_labels with the box count optionally on the device (boxes.hip; n_dev == nullptr: n_boxes is the count)
+int rpn_labels_counted(const lisec_rpn_cfg* cfg, const double* fixed_boxes, int n_boxes, const int32_t* n_dev, double iou_lo,
+                       double iou_hi, void* workspace, size_t workspace_bytes, double* valid, double* overlap,
+                       double* out_regress, lisec_stream_t stream);
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 

@@ -657,8 +657,9 @@ class Model:
                 self.nx // 2, self.ny // 2, self.nz)
 
     def _sequence_request(self, seq):
-        """_plan_request for a Sequence of raw sweeps: the capacity is its largest point count (`max_points`; augmentation
-        keeps the count), the point dtype its `dtype`; a Sequence without them is walked once to find them."""
+        """_plan_request for a Sequence of raw sweeps: the capacity is its largest row count (`max_points`; augmentation
+        keeps the count, object sampling adds its bound), the point dtype its `dtype`; a Sequence without them is walked
+        once to find them."""
         need, dtype = getattr(seq, "max_points", None), getattr(seq, "dtype", None)
         if need is None or dtype is None:
             pts = [torch.as_tensor(seq[i][0]) for i in range(len(seq))]
@@ -1028,12 +1029,13 @@ def train_with_model(samples, level5Data, model_path, save_path):
     return _train(samples, level5Data, save_path, model_path)
 
 
-def train_augmented(samples, level5Data, save_path, epochs=1, seed=0):
+def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0):
     """OURS, not the reference's: train() on sweeps that are augmented anew at every step (augment.AugmentedSweeps: per-box
     noise with collision rejection, one global scale and rotation, VoxelNet section 3.3) with the label maps of the moved
     boxes made on the device (boxes.rpnTargets) instead of the precomputed labels3/*.npy.  The sweeps come from
     combine_lidar_data_gpu, the boxes from boxes.annotationBoxes; one pass over the samples per epoch, the reference's
-    SGD.  Returns the model, saved at save_path."""
+    SGD.  sample_to > 0: ground-truth object sampling (augment.ObjectDatabase, built from the same sweeps and boxes) fills
+    every sweep up towards that many boxes before the noise.  Returns the model, saved at save_path."""
     from . import augment, boxes
     _refuse_mixed_training(mixed_precision.global_policy())
     points = [combine_lidar_data_gpu(s, Constants.lyft_data_dir, level5Data) for s in samples]
@@ -1041,7 +1043,9 @@ def train_augmented(samples, level5Data, save_path, epochs=1, seed=0):
     model = createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints)
     sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
     model.compile(optimizer=sgd, loss=['mse', 'mse'])
-    history = model.fit(x=augment.AugmentedSweeps(points, rows, seed=seed), batch_size=1, verbose=1, epochs=epochs)
+    database = augment.ObjectDatabase(points, rows) if sample_to > 0 else None
+    seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to)
+    history = model.fit(x=seq, batch_size=1, verbose=1, epochs=epochs)
     if model.dp is None or model.dp.rank == 0:
         print(history.history)
     model.save(save_path)

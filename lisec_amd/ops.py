@@ -668,32 +668,106 @@ def augment_params(rot_box=math.pi / 10, sigma=(1.0, 1.0, 0.0), scale=(0.95, 1.0
     return p
 
 
-def augment_draw(boxes, params, seed=0, item=0, epoch=0):
+def _int32_count(n_boxes):
+    if n_boxes.dtype != torch.int32 or n_boxes.numel() != 1 or not n_boxes.is_cuda:
+        raise ValueError("a device-side box count is one int32 on the device")
+    return _lib.ptr(n_boxes)
+
+
+def augment_draw(boxes, params, seed=0, item=0, epoch=0, n_boxes=None):
     """lisec_augment_draw on device rows boxes (B, 7) float64.  Returns device tensors (transforms (B, 4), global (2,),
-    boxes_out (B, 7), attempt (B,) int32, draws (4 + 8 B,) uint32 held as int32 bits)."""
+    boxes_out (B, 7), attempt (B,) int32, draws (4 + 8 B,) uint32 held as int32 bits).  n_boxes: a device int32 (1,) holding
+    the number of rows that count (lisec_augment_draw_n; B bounds it): the outputs are zero past it."""
     B, dev = int(boxes.shape[0]), boxes.device
-    transforms = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    new = torch.empty if n_boxes is None else torch.zeros
+    transforms = new((B, 4), dtype=torch.float64, device=dev)
     glob = torch.empty(2, dtype=torch.float64, device=dev)
-    boxes_out = torch.empty((B, 7), dtype=torch.float64, device=dev)
-    attempt = torch.empty(B, dtype=torch.int32, device=dev)
-    draws = torch.empty(4 + 8 * B, dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().lisec_augment_draw(_lib.ptr(boxes) if B else None, B, ctypes.byref(params),
-                                              int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff, int(epoch) & 0xffffffff,
-                                              _lib.ptr(transforms) if B else None, _lib.ptr(glob),
-                                              _lib.ptr(boxes_out) if B else None, _lib.ptr(attempt) if B else None,
-                                              _lib.ptr(draws), _lib.current_stream()))
+    boxes_out = new((B, 7), dtype=torch.float64, device=dev)
+    attempt = new(B, dtype=torch.int32, device=dev)
+    draws = new(4 + 8 * B, dtype=torch.int32, device=dev)
+    seeds = (int(seed) & (2 ** 64 - 1), int(item) & 0xffffffff, int(epoch) & 0xffffffff)
+    outs = (_lib.ptr(transforms) if B else None, _lib.ptr(glob), _lib.ptr(boxes_out) if B else None,
+            _lib.ptr(attempt) if B else None, _lib.ptr(draws), _lib.current_stream())
+    if n_boxes is None:
+        _lib.check(_lib.load().lisec_augment_draw(_lib.ptr(boxes) if B else None, B, ctypes.byref(params), *seeds, *outs))
+    else:
+        _lib.check(_lib.load().lisec_augment_draw_n(_lib.ptr(boxes) if B else None, _int32_count(n_boxes), B,
+                                                    ctypes.byref(params), *seeds, *outs))
     return transforms, glob, boxes_out, attempt, draws
 
 
-def augment_apply(points, boxes, transforms, glob, out, pad_limit):
-    """lisec_augment_apply: device points (n, >= 3) float32 / float64 with unit element stride -> out (n, 3) dense, same dtype."""
+def _point_args(points):
+    """(address, dtype code, n, row stride) of device points (n, >= 3) float32 / float64 with unit element stride."""
+    n = int(points.shape[0])
+    if points.dtype not in (torch.float32, torch.float64):
+        raise ValueError("points must be float32 or float64")
+    if n and points.stride(1) != 1:
+        raise ValueError("points need unit element stride")
+    return (_lib.ptr(points) if n else None, 0 if points.dtype == torch.float32 else 1, n, int(points.stride(0)) if n else 3)
+
+
+def augment_apply(points, boxes, transforms, glob, out, pad_limit, n_boxes=None):
+    """lisec_augment_apply: device points (n, >= 3) float32 / float64 with unit element stride -> out (n, 3) dense, same dtype.
+    n_boxes: a device int32 (1,) holding the number of box rows that count (lisec_augment_apply_n)."""
     n, B = int(points.shape[0]), int(boxes.shape[0])
     if points.dtype != out.dtype or points.dtype not in (torch.float32, torch.float64):
         raise ValueError("points and out must share one of float32 / float64")
     if n and (points.stride(1) != 1 or not out.is_contiguous() or tuple(out.shape) != (n, 3)):
         raise ValueError("points need unit element stride, out must be dense (n, 3)")
-    _lib.check(_lib.load().lisec_augment_apply(_lib.ptr(points) if n else None, 0 if points.dtype == torch.float32 else 1, n,
-                                               int(points.stride(0)) if n else 3, _lib.ptr(boxes) if B else None, B,
-                                               _lib.ptr(transforms) if B else None, _lib.ptr(glob), float(pad_limit),
-                                               _lib.ptr(out) if n else None, _lib.current_stream()))
+    tail = (_lib.ptr(transforms) if B else None, _lib.ptr(glob), float(pad_limit), _lib.ptr(out) if n else None,
+            _lib.current_stream())
+    if n_boxes is None:
+        _lib.check(_lib.load().lisec_augment_apply(*_point_args(points), _lib.ptr(boxes) if B else None, B, *tail))
+    else:
+        _lib.check(_lib.load().lisec_augment_apply_n(*_point_args(points), _lib.ptr(boxes) if B else None,
+                                                     _int32_count(n_boxes), B, *tail))
+    return out
+
+
+def augment_owner(points, boxes, pad_limit):
+    """lisec_augment_owner: device points (n, >= 3), boxes (B, 7) float64 -> owner (n,) int32, the lowest box index holding
+    each point, -1 for none and for pad rows."""
+    n, B = int(points.shape[0]), int(boxes.shape[0])
+    owner = torch.empty(n, dtype=torch.int32, device=points.device)
+    _lib.check(_lib.load().lisec_augment_owner(*_point_args(points), _lib.ptr(boxes) if B else None, B, float(pad_limit),
+                                               _lib.ptr(owner) if n else None, _lib.current_stream()))
+    return owner
+
+
+def augment_sample(boxes, db_boxes, db_offsets, n_samples, seed=0, item=0, epoch=0):
+    """lisec_augment_sample: scene rows boxes (B, 7), the database's rows db_boxes (M, 7) and point offsets db_offsets
+    (M + 1,) int32, K = n_samples candidates.  Returns device tensors (index (K,) int32, n_boxes (1,) int32, boxes_all
+    (B + K, 7), point_offset (K + 1,) int32, draws (4 K,) uint32 held as int32 bits)."""
+    B, M, K, dev = int(boxes.shape[0]), int(db_boxes.shape[0]), int(n_samples), boxes.device
+    if db_offsets.dtype != torch.int32 or db_offsets.numel() != M + 1:
+        raise ValueError("db_offsets must be int32 (M + 1,)")
+    index = torch.empty(K, dtype=torch.int32, device=dev)
+    n_boxes = torch.empty(1, dtype=torch.int32, device=dev)
+    boxes_all = torch.empty((B + max(K, 0), 7), dtype=torch.float64, device=dev)
+    point_offset = torch.empty(max(K, 0) + 1, dtype=torch.int32, device=dev)
+    draws = torch.empty(4 * max(K, 0), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().lisec_augment_sample(_lib.ptr(boxes) if B else None, B, _lib.ptr(db_boxes) if M else None,
+                                                _lib.ptr(db_offsets), M, K, int(seed) & (2 ** 64 - 1),
+                                                int(item) & 0xffffffff, int(epoch) & 0xffffffff,
+                                                _lib.ptr(index) if K else None, _lib.ptr(n_boxes),
+                                                _lib.ptr(boxes_all) if B + K else None, _lib.ptr(point_offset),
+                                                _lib.ptr(draws) if K else None, _lib.current_stream()))
+    return index, n_boxes, boxes_all, point_offset, draws
+
+
+def augment_paste(points, db_points, db_offsets, index, point_offset, boxes_all, n_boxes, out, pad_limit):
+    """lisec_augment_paste: the scene points (n, >= 3) and the accepted objects of lisec_augment_sample -> out (cap, 3) dense
+    in the points' dtype, which db_points (P, 3) shares: scene rows (those inside a pasted box as pad rows), the pasted
+    points, pad rows up to cap."""
+    n, K, cap = int(points.shape[0]), int(index.shape[0]), int(out.shape[0])
+    B = int(boxes_all.shape[0]) - K
+    if points.dtype != out.dtype or (db_points.numel() and db_points.dtype != out.dtype):
+        raise ValueError("points, db_points and out must share one dtype")
+    if not out.is_contiguous() or out.dim() != 2 or out.shape[1] != 3 or (db_points.numel() and not db_points.is_contiguous()):
+        raise ValueError("out and db_points must be dense (rows, 3)")
+    _lib.check(_lib.load().lisec_augment_paste(*_point_args(points), _lib.ptr(db_points) if db_points.numel() else None,
+                                               _lib.ptr(db_offsets), _lib.ptr(index) if K else None, _lib.ptr(point_offset),
+                                               _lib.ptr(boxes_all) if B + K else None, B, _int32_count(n_boxes), K,
+                                               float(pad_limit), _lib.ptr(out) if cap else None, cap,
+                                               _lib.current_stream()))
     return out

@@ -1,11 +1,13 @@
 """Throughput of the reference-named surface: Model.fit(batch_size=1) on voxelised sweeps (GPU box only).
 
-    python tools/bench_fit.py [--lr constant|cosine] [--cloud u20k|r200k] [--augment]
+    python tools/bench_fit.py [--lr constant|cosine] [--cloud u20k|r200k] [--augment [--sample-to N]]
 
 --lr cosine trains with optimizers.schedules.CosineDecay (the update kernels read lr_t from the device descriptor)
 instead of the reference's constant rate.  --augment adds, beside plain fit on the same sweeps, fit(x=AugmentedSweeps) with
 about 50 boxes per sweep (augmentation, label maps and balancing made on the device at every step), fit on the same Sequence
-with augment=False (the label kernels alone), and the stand-alone device times of the three entries."""
+with augment=False (the label kernels alone), and the stand-alone device times of the three entries.  --sample-to N adds
+the same stream with ground-truth object sampling from a database of the sweeps' own objects (each sweep filled up towards
+N boxes) and the device times of lisec_augment_sample / lisec_augment_paste."""
 import argparse
 import os
 import sys
@@ -23,6 +25,7 @@ if __name__ == "__main__":
     ap.add_argument("--lr", choices=("constant", "cosine"), default="constant")
     ap.add_argument("--cloud", choices=("u20k", "r200k"), default="u20k")
     ap.add_argument("--augment", action="store_true")
+    ap.add_argument("--sample-to", type=int, default=0)
     args = ap.parse_args()
     n = 4
     cloud = u20k_cloud if args.cloud == "u20k" else r200k_cloud
@@ -52,7 +55,14 @@ if __name__ == "__main__":
             cells = rng.permutation(49)[:50 - i]
             bxs.append(np.array([[-42 + 12 * (c % 7) + rng.uniform(-2, 2), -42 + 12 * (c // 7) + rng.uniform(-2, 2), 1.0,
                                   rng.uniform(3.8, 4.8), rng.uniform(1.7, 2.0), 1.6, rng.uniform(-3.1, 3.1)] for c in cells]))
-        for label, kw in (("augmented", {}), ("labels only (augment=False)", dict(augment=False))):
+        runs = [("augmented", {}), ("labels only (augment=False)", dict(augment=False))]
+        if args.sample_to > 0:
+            # objects need points: every box gets 40 of its own before the database is cut out
+            pts = [np.concatenate([p[:, :3], np.concatenate([b[None, :3] + rng.uniform(-0.4, 0.4, (40, 3)) for b in bx])])
+                   for p, bx in zip(pts, bxs)]
+            db = augment.ObjectDatabase(pts, bxs)
+            runs.append((f"sampled to {args.sample_to} boxes from {len(db)} objects", dict(database=db, sample_to=args.sample_to)))
+        for label, kw in runs:
             seq = augment.AugmentedSweeps(pts, bxs, seed=1, **kw)
             model.fit(x=seq, batch_size=1, verbose=0, epochs=1, steps_per_epoch=20)
             torch.cuda.synchronize()
@@ -82,3 +92,14 @@ if __name__ == "__main__":
               f"{1e3 * event_time_ms(lambda: ops.augment_apply(src, bx, tr, glob, out, augment.PAD_LIMIT), 50):.1f} us")
         for bal in (False, True):
             print(f"lisec_rpn_targets   (balance={bal}): {1e3 * event_time_ms(lambda: boxes.rpnTargets(bx_out, balance=bal, out=maps), 50):.1f} us")
+        if args.sample_to > 0:
+            K = augment._sample_count(len(bx), args.sample_to)
+            smp = lambda: ops.augment_sample(bx, db.boxes, db.offsets, K, 1, 0, 0)
+            index, n_boxes, boxes_all, point_offset, _ = smp()
+            dbp = db.points_as(src.dtype)
+            pasted = torch.empty((src.shape[0] + db.bound(K), 3), dtype=src.dtype, device=src.device)
+            paste = lambda: ops.augment_paste(src, dbp, db.offsets, index, point_offset, boxes_all, n_boxes, pasted,
+                                              augment.PAD_LIMIT)
+            print(f"lisec_augment_sample ({len(bx)} boxes, {K} candidates, {int(n_boxes.item()) - len(bx)} accepted): "
+                  f"{1e3 * event_time_ms(smp, 50):.1f} us")
+            print(f"lisec_augment_paste  ({pasted.shape[0]} rows): {1e3 * event_time_ms(paste, 50):.1f} us")
