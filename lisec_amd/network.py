@@ -128,6 +128,340 @@ class ConvLayer:
         self.nmb = ops.num_mblocks(g)
 
 
+class _SideQueue:
+    """The fork protocol between the stream a pass is issued on (main) and the net's second stream (side).  Closures are
+    queued (defer) and cross to the second stream together, behind ONE event of the main stream (flush; run = defer +
+    flush).  Events are made, recorded and waited for through the net (_new_event, _record, _wait): a step plan sees
+    them, and tools/ override those three."""
+
+    def __init__(self, net, main, side):
+        self.net, self.main, self.side = net, main, side
+        self.events = []                       # fork events, reused pass after pass: recorded step plans hold them
+        self.nfork = 0                         # how many of them this pass has recorded
+        self.pending = []                      # (closure, torch_ops) that the next flush() runs
+        self.marked = []                       # events recorded ahead of the flush() that waits for them
+
+    def begin(self, main=None):
+        """Starts a pass, on `main` if given: the pool's events are handed out from the first again."""
+        if main is not None:
+            self.main = main
+        self.nfork = 0
+        del self.pending[:], self.marked[:]
+
+    def mark_fork(self, ev=None):
+        """Records the fork event NOW (ev; None: the pool's next); the next flush() waits for this one instead of recording
+        its own.  Lets the chain's next kernel be ENQUEUED before the second stream's work although that work does not
+        depend on it."""
+        if ev is None:
+            if self.nfork == len(self.events):
+                self.events.append(self.net._new_event())
+            ev = self.events[self.nfork]
+            self.nfork += 1
+        self.net._record(ev, self.main)
+        self.marked.append(ev)
+
+    def defer(self, fn, torch_ops=False):
+        """Queues fn for the next flush().  C-ABI launches take the pinned handle; only a fn that also issues torch /
+        torch.distributed work (torch_ops) needs torch's (slow) stream context."""
+        self.pending.append((fn, torch_ops))
+
+    def flush(self):
+        """Records ONE event on the main stream (unless one is marked) and runs every pending closure on the second
+        stream behind it.  Nothing pending: nothing happens, and a mark stays for the next flush."""
+        if not self.pending:
+            return
+        if not self.marked:
+            self.mark_fork()
+        self.net._wait(self.marked.pop(), self.side)
+        pin = _lib.pin_stream(self.side.cuda_stream)
+        try:
+            for fn, torch_ops in self.pending:
+                if torch_ops:
+                    with torch.cuda.stream(self.side):
+                        fn()
+                else:
+                    fn()
+        finally:
+            _lib.pin_stream(pin)
+            del self.pending[:]
+
+    def run(self, fn, torch_ops=False):
+        """Runs fn's launches on the second stream after everything issued so far on the main one."""
+        self.defer(fn, torch_ops)
+        self.flush()
+
+    def join(self, ev):
+        """The main stream waits for everything issued so far on the second one."""
+        self.net._record(ev, self.side)
+        self.net._wait(ev, self.main)
+
+
+class _BackwardPass:
+    """One call of LisecNet._backward: what the pass has done so far, and one method per layer kind, called last layer
+    first.  The data-gradient chain runs on the main stream; the leaves (weight and bias gradients, the early upsampling
+    branches) go through the _SideQueue `q`.  With collapsed heads, heads() and early_branches() only queue (q.defer):
+    the first q.run of the chain, in deconv(), carries them across behind its one event.  finish() queues the late
+    reduces and flushes them itself.  Every other leaf crosses where it is issued (q.run)."""
+
+    def __init__(self, net, q, sample, rpn_grads_ready, side_filler):
+        self.net, self.q, self.sample = net, q, sample
+        self.rpn_grads_ready, self.side_filler = rpn_grads_ready, side_filler
+        self.rcap = max(sample.cap, 1)         # an empty sweep still needs a non-zero row-list capacity
+        self.branches_left = len(DECONVS)      # collapsed branches whose rows of the head-kernel gradient are still missing
+        self.batched_convs = set().union(*[names for _, names in net.wgrad_batches.values()])
+        self.first_write = set()               # gradient buffers that already hold a contribution
+        self.writes = {}                       # gradient buffer -> contributions stored so far
+        self.bwd_ready = {}                    # gradient buffer -> partial rows of its BN-backward statistics
+        self.early_dst = {}                    # gradient buffer -> event behind a contribution made on the second stream
+        self.fused_dense = {}                  # middle block -> backward sink of a Dense data gradient that rode on a tile
+        self.late_reduces = []                 # slab sums of the carried Dense weight gradients
+        self.early_layers = set()              # upsampling branches that early_branches() has already differentiated
+
+    def dgrad_into(self, c, dy, dst_name, ws_tag="main"):
+        net, a, d = self.net, self.net.act, self.net.dact
+        ev = self.early_dst.pop(dst_name, None) if ws_tag == "main" else None
+        if ev is not None:
+            net._wait(ev, self.q.main)         # the branch's contribution is stored before this one accumulates onto it
+        flags = ops.ACCUMULATE if dst_name in self.first_write else 0
+        # the output of a middle block went through Dense(relu) (model_training.py:195): its gradient is gated
+        # by that activation while the data gradient is stored (single consumer, so no ACCUMULATE there)
+        mask = a[dst_name] if dst_name.endswith(".u") else None
+        # the LAST contribution to the gradient of a conv output also reduces the statistics its
+        # BatchNormalization backward needs (pass 1 of bn_backward folded into the store)
+        self.writes[dst_name] = self.writes.get(dst_name, 0) + 1
+        bwd = sink = tail = None
+        if dst_name in net.bn_of and self.writes[dst_name] == net.consumers[dst_name]:
+            bn_name, C = net.bn_of[dst_name]
+            bwd, sink = (a[dst_name], net.bnstate[bn_name], True), net._bwd_sink(bn_name, C, a[dst_name].numel() // C)
+            self.bwd_ready[dst_name] = sink
+        use_w = c.name in net.packed_wu_t
+        if mask is not None and not use_w and net._tail_supported(c, dst_name):
+            # the Dense(64, relu) of the block BELOW (model_training.py:195) rides on this tile: its data gradient
+            # dz = (gated gradient) @ Wd^T and the statistics of the BatchNormalization under it come out of the same
+            # launch (lisec_conv_extras.tail_w); the separate Dense data-gradient launch is skipped further down
+            n = dst_name[:-2]
+            Ln = next(L for L in net.layers if L["name"] == n)
+            cn, dn = Ln["conv"], Ln["dense"]
+            sink = net._bwd_sink(cn.bn, 64, cn.M)
+            bwd = (a[n + ".y"], net.bnstate[cn.bn], False)
+            tail = (net.packed_t[dn.name][0], d[n + ".z"])
+            self.fused_dense[n] = sink
+        if use_w:
+            ops.conv_forward_winograd(net.dgeom[c.name], dy, net.packed_wu_t[c.name], d[dst_name], flags=flags,
+                                      out_mask=mask, bwd=bwd, sink=sink, tail=tail)
+        else:
+            ops.conv_forward(net.dgeom[c.name], dy, net.packed_t[c.name][0], d[dst_name], flags=flags, out_mask=mask,
+                             bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail)
+        self.first_write.add(dst_name)
+
+    def branch_dy(self, L):
+        """The gradient a branch's contraction produced: a concat slice, or (collapsed form) the head gradient / its
+        (tap, j) columns."""
+        d = self.net.dact
+        if not self.net.compose_head:
+            return d["concat"][:, :, 256 * L["slot"]:]
+        return d["head"] if L["dT"] is None else L["dT"]
+
+    def deconv_wgrad(self, L):
+        net, a, p, G = self.net, self.net.act, self.net.params, self.net.grad
+        c = L["conv"]
+        if net.compose_head:
+            b, (ts, cs) = L["slot"], L["wc_strides"]
+            ops.conv_wgrad(c.g, a[L["src"]], self.branch_dy(L), L["G"], net.wgrad_ws, in_bn=net.bnstate[c.in_bn],
+                           flags=ops.IN_RELU)
+            ops.head_compose_backward(L["G"], ts, cs, p.view(L["up_kernel"]), p.view(L["up_bias"]),
+                                      net.head_w[256 * b:256 * (b + 1)],
+                                      net.head_db, L["k"] * L["k"], L["cin"], 256, p.grad_view(G, L["up_kernel"]),
+                                      p.grad_view(G, L["up_bias"]), net.head_dw[256 * b:256 * (b + 1)])
+            self.branches_left -= 1
+            if self.branches_left == 0:
+                net._head_split.run()          # every row of dH is final: merged (768,16) -> the Keras-shaped slots
+            return
+        dy = self.branch_dy(L)
+        if "wgeom" in L:
+            ops.conv_wgrad(L["wgeom"], dy, a[L["src"]], p.grad_view(G, c.wname), net.wgrad_ws,
+                           flags=ops.DY_RELU, dy_bn=net.bnstate[c.in_bn])
+        else:
+            ops.conv_wgrad(c.g, a[L["src"]], dy, p.grad_view(G, c.wname), net.wgrad_ws,
+                           in_bn=net.bnstate[c.in_bn], flags=ops.IN_RELU, transpose_out=True)
+
+    def heads(self):
+        """The 1x1 heads (model_training.py:254-255).  Only the data gradient is on the way to the rest of the backward
+        pass: the heads' weight and bias gradients and the deconv bias gradients (column sums of the concat gradient) are
+        leaves and go to the second stream."""
+        net, q, a, d = self.net, self.q, self.net.act, self.net.dact
+        M = net.Ho * net.Wo
+        if net.compose_head:
+            # collapsed branches + heads: the head gradient feeds the three 16-channel contractions directly; its column
+            # sums (the heads' bias gradient, and through H the branch biases) are the only pass over it
+            net._dshuffle.run(d["head"], backward=True)
+            # (queued, not flushed: the leaves and branches that hang off the head gradient cross to the second stream
+            # behind ONE event, with the first of them that is issued through q.run)
+            q.defer(lambda: ops.colsum(d["head"], 16, M, 16, net.head_db, ws_tag="side"))
+            return
+
+        def head_leaves():
+            ops.conv_wgrad(net.head_geom, a["concat"], d["head"], net.head_dw, net.wgrad_ws)
+            ops.colsum(d["head"], 16, M, 16, net.head_db, ws_tag="side")
+            net._head_split.run()
+
+        def concat_leaves():
+            # the three deconv bias gradients are the column sums of the concat gradient: one pass over it
+            ops.colsum(d["concat"], 768, M, 768, net.up_db, ws_tag="side")
+            net._up_bias_split.run()
+
+        q.run(head_leaves)
+        ops.conv_forward(net.head_dgeom, d["head"], net.packed_t["head"][0], d["concat"])
+        q.run(concat_leaves)
+
+    def early_branches(self):
+        """The Conv2DTranspose branches of blocks 1 and 2 hang off the concat gradient, which is complete now: both of
+        their gradients go to the second stream at once, beside the small layers of blocks 3 and 2, instead of waiting
+        on the chain for their turn; the chain picks their contribution up where it reaches the block's last conv."""
+        net, q = self.net, self.q
+        for L in net.layers:
+            if L["kind"] == "deconv" and L["slot"] < len(DECONVS) - 1:
+                ev = net._event("bwd_branch%d" % L["slot"])
+
+                def branch(L=L, ev=ev):
+                    self.deconv_wgrad(L)
+                    self.dgrad_into(L["conv"], self.branch_dy(L), L["src"], ws_tag="side")
+                    net._record(ev, q.side)
+                q.defer(branch)
+                if not net.compose_head:
+                    q.flush()
+                self.early_dst[L["src"]] = ev
+                self.early_layers.add(L["name"])
+
+    def deconv(self, L):
+        q = self.q
+        if L["name"] in self.early_layers:
+            return
+        # the chain's contraction goes into its queue BEFORE the leaves that hang off the same gradient: the
+        # second stream's queue is served first (priority) and its kernels fill every CU's LDS, so a chain
+        # kernel enqueued behind them waited for the whole leaf sequence (r03 timeline: 214 us)
+        q.mark_fork()
+        self.dgrad_into(L["conv"], self.branch_dy(L), L["src"])
+        q.run(lambda: self.deconv_wgrad(L))
+        if self.side_filler is not None:
+            q.run(self.side_filler)
+            self.side_filler = None
+
+    def conv(self, L):
+        net, q, a, d, p, G = self.net, self.q, self.net.act, self.net.dact, self.net.params, self.net.grad
+        c, dst = L["conv"], L["dst"]
+        C = c.g.Cout
+        if dst in self.bwd_ready:
+            # dgamma / dbeta / coefficients were finalised inside the data-gradient call that stored d[dst]
+            ops.bn_backward_apply_coef(d[dst], C, a[dst], net.bnstate[c.bn], c.M, C, True,
+                                       self.bwd_ready.pop(dst).coef, d[dst])
+        else:
+            ops.bn_backward(d[dst], C, a[dst], net.bnstate[c.bn], c.M, C, True,
+                            p.grad_view(G, c.bn + ".gamma"), p.grad_view(G, c.bn + ".beta"), d[dst])
+        # the bias of a conv feeding a training-mode BN has gradient sum(dy) == 0 identically (BN removes
+        # the mean); Keras' autograd returns rounding noise there -- the exact 0 stays in net.grad
+        if L["name"] in self.batched_convs:
+            # one launch for the block's stride-1 convolutions, issued when the LAST of their output gradients
+            # (conv1's: the layers are walked back to front) is final
+            if L["name"] in net.wgrad_batches:
+                q.run(lambda: net.wgrad_batches[L["name"]][0].run(net.wgrad_ws))
+        else:
+            q.run(lambda: ops.conv_wgrad(
+                c.g, a[L["src"]], d[dst], p.grad_view(G, c.wname), net.wgrad_ws,
+                in_bn=net.bnstate[c.in_bn] if c.in_bn else None, flags=ops.IN_RELU if c.in_relu else 0))
+        if L["name"] == "rpn1.conv0" and self.rpn_grads_ready is not None:
+            lo = p.offsets["rpn1.conv0.kernel"][1]
+            q.run(lambda: self.rpn_grads_ready(lo, p.n_theta), torch_ops=True)
+        self.dgrad_into(c, d[dst], L["src"])
+        if L["src"] == "fold":
+            # back through Permute + Reshape, gated by the ReLU of the last middle block's Dense (:195)
+            ops.fold_depth(d["fold"], d[net.fold_src], net.dprime, net.H * net.W, 64, inverse=True,
+                           mask=a[net.fold_src])
+
+    def mid(self, L):
+        """A middle block: conv3d -> BN -> Dense(relu)."""
+        net, q, a, d, p, G = self.net, self.q, self.net.act, self.net.dact, self.net.params, self.net.grad
+        c, n, dn = L["conv"], L["name"], L["dense"]
+
+        def dense_wg():
+            ops.conv_wgrad(dn.g, a[n + ".y"], d[n + ".u"], p.grad_view(G, dn.wname), net.wgrad_ws,
+                           in_bn=net.bnstate[dn.in_bn])
+        # the Dense weight gradient (HBM-bound, 52 granules of LDS) finds no room beside three data-gradient
+        # workgroups per CU and waited 474 us in the queue IN FRONT of the block's ring weight gradient: behind it
+        # the ring kernel starts as soon as its gradient exists
+        late_dense = L["src"] != "grid"
+        # the Dense data gradient below reads both operands of the Dense weight gradient: it carries it
+        # (lisec_conv_extras.dense_dw)
+        carried = n not in self.fused_dense and n in net.dense_dw_slabs
+        if carried:
+            late_dense = False
+        elif not late_dense:
+            q.run(dense_wg)
+        # Dense data gradient; its store also reduces the statistics of the BatchNormalization under it
+        if n in self.fused_dense:
+            msink = self.fused_dense.pop(n)    # done inside the data gradient of the block above (dgrad_into)
+        else:
+            msink = net._bwd_sink(c.bn, 64, c.M)
+            ops.conv_forward(net.dgeom[dn.name], d[n + ".u"], net.packed_t[dn.name][0], d[n + ".z"],
+                             bwd=(a[n + ".y"], net.bnstate[c.bn], False), sink=msink,
+                             dense_dw=net.dense_dw_slabs[n] if carried else None)
+            if carried:
+                # the 8 MB slab sum finds no registers beside the Winograd workgroups (46 - 60 us in the step for 6 us of
+                # work) and the second stream is in order: enqueued right here it held the block's weight gradient back;
+                # nothing reads the result before the optimizer, so the three sums go behind the last weight gradient
+                self.late_reduces.append(lambda: ops.dense_dw_reduce(net.dense_dw_slabs[n], p.grad_view(G, dn.wname)))
+        if L["src"] == "grid":
+            self.first_conv3d(L, msink)
+            return
+        ops.bn_backward_apply_coef(d[n + ".z"], 64, a[n + ".y"], net.bnstate[c.bn], c.M, 64, False, msink.coef,
+                                   d[n + ".z"])
+        # the weight gradient (second stream) is enqueued BEFORE the block's data gradient: measured 1 % faster
+        # than the other order
+        if c.name in net.wino_wgrad_ws:
+            # Winograd-domain weight gradient (csrc/wino_wgrad.hip): 4 / 9 of the ring kernel's MFMAs
+            q.run(lambda: ops.conv_wgrad_winograd(c.g, a[L["src"]], d[n + ".z"], p.grad_view(G, c.wname),
+                                                  net.wino_wgrad_ws[c.name]))
+        else:
+            q.run(lambda: ops.conv_wgrad(c.g, a[L["src"]], d[n + ".z"], p.grad_view(G, c.wname), net.wgrad_ws))
+        if late_dense:
+            q.run(dense_wg)
+        self.dgrad_into(c, d[n + ".z"], L["src"])
+
+    def first_conv3d(self, L, msink):
+        """The sparse first Conv3D.  The grid is a constant on the empty cells + V voxel rows: both gradients reduce to
+        V-row contractions plus sums of dy over boundary-trimmed boxes (exact; csrc/sparse_grid.hip)."""
+        net, a, p, sample = self.net, self.net.act, self.net.params, self.sample
+        c, n = L["conv"], L["name"]
+        dz = net.dact[n + ".z"]
+        rows = (sample.coords, sample.info, self.rcap)
+        dg = net.dgeom[c.name]
+        dW = p.grad_view(net.grad, c.wname)
+        # the apply pass of this block's BatchNormalization backward runs inside the line sums (one pass
+        # over the 82 MB gradient instead of two)
+        ops.tap_sums_bn(c.g, dz, a[n + ".y"], net.bnstate[c.bn], msink.coef, dz, net.mid1_S, net.tapsum_ws)
+        ops.const_field_grads(p.view(c.wname), net.mid1_S, None, 27, 64, 64, g_all=net.g_all)
+        vout, delta = net.vfe.saved_field("vout"), net.vfe.saved_field("delta")
+
+        def sparse_wgrad():
+            ops.conv_wgrad(dg, dz, delta, dW, net.wgrad_ws, transpose_out=True, rows=rows)
+            ops.const_field_grads(None, net.mid1_S, vout, 27, 64, 64, dW=dW, cvec_row=sample.info,
+                                  cvec_row_max=sample.cap)
+        self.q.run(sparse_wgrad)
+        ops.conv_forward(dg, dz, net.packed_t[c.name][0], net.dout_rows, rows=rows, queue=net.rows_queue)
+
+    def finish(self):
+        """The late reduces behind the last weight gradient, the VFE, and the join of the two streams."""
+        net, q = self.net, self.q
+        net._mark("bwd:before vfe")
+        for fn in self.late_reduces:
+            q.defer(fn)
+        q.flush()
+        net.vfe.backward(None, net.grad, dout_rows=net.dout_rows, g_all=net.g_all)
+        net._mark("bwd:vfe done")
+        q.join(net._event("bwd_join"))         # every weight gradient has landed before the optimizer reads G
+        net._mark("bwd:joined")
+
+
 class LisecNet:
     def __init__(self, nx, ny, nz, maxPoints, params=None, device=None, compose_head=True, compute_dtype="float32"):
         """compute_dtype: 'float32', or 'bfloat16' (the 'mixed_bfloat16' policy of lisec_amd.mixed_precision): the inference
@@ -307,10 +641,10 @@ class LisecNet:
         # of its own, and that is the faster arrangement: the high-priority queue was served first whenever it held a ready
         # packet, which starved the chain during the head phase; one rank through RCCL 5.13 -> 4.25 ms, one GPU +0.8 %.)
         self.side = torch.cuda.Stream(device=dev, priority=0)
+        self.side_queue = _SideQueue(self, None, self.side)     # each pass names its main stream (begin)
 
         self._tail_ok = {}
         self._loss_descs = {}                            # LossSpec -> its lisec_loss_cfg (_loss_descriptor)
-        self._head_split = None                          # CopyTable of the head gradients, made by the first backward
         self._early = None                               # (lo, OptimizerSpec) of the pending early_update()
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
         self._fwd_events = {}
@@ -544,6 +878,8 @@ class LisecNet:
             self._wait(self._pack_done, torch.cuda.current_stream())
             self._pack_pending = False
         side_used = False
+        q = self.side_queue
+        q.begin(torch.cuda.current_stream())
         self._mark("fwd:start")
         for L in self.layers:
             self._mark("fwd:before " + L["name"])
@@ -583,15 +919,8 @@ class LisecNet:
                         self._run_conv(L["conv"], a[L["src"]], a["concat"][:, :, 256 * b:], training, ws_tag=ws_tag)
                 if b < len(DECONVS) - 1:
                     # an upsampling branch that is not the last: beside the next block, on the second stream
-                    main = torch.cuda.current_stream()
-                    fork = self._event("fwd_fork%d" % b)
-                    self._record(fork, main)
-                    self._wait(fork, self.side)
-                    pin = _lib.pin_stream(self.side.cuda_stream)
-                    try:
-                        run("side")
-                    finally:
-                        _lib.pin_stream(pin)
+                    q.mark_fork(self._event("fwd_fork%d" % b))
+                    q.run(lambda: run("side"))
                     side_used = True
                 else:
                     if self._late_pending:
@@ -604,9 +933,7 @@ class LisecNet:
             self._wait(self._pack_late, torch.cuda.current_stream())
             self._late_pending = False
         if side_used:
-            join = self._event("fwd_join")
-            self._record(join, self.side)
-            self._wait(join, torch.cuda.current_stream())
+            q.join(self._event("fwd_join"))
         if self.compose_head:
             self._shuffle.run(a["head"])
         else:
@@ -697,7 +1024,6 @@ class LisecNet:
                                                       if L["kind"] == "deconv" and L["dT"] is not None])
         self.head_dw = torch.empty(768, 16, dtype=f32, device=dev)
         self.up_db = torch.empty(768, dtype=f32, device=dev)
-        self._fork_events, self._join_event = [], None
         # conv outputs that sit under a BatchNormalization(+ReLU), and how many layers read each of them
         self.bn_of, self.consumers = {}, {}
         nparts = 1
@@ -712,6 +1038,17 @@ class LisecNet:
                 nparts = max(nparts, ops.num_mblocks_bwd(self.dgeom[L["dense"].name]) * 2 * 64)
         self.bparts = torch.empty(nparts, dtype=torch.float64, device=dev)
         self.head_db = torch.empty(16, dtype=f32, device=dev)
+        # merged head gradients -> the Keras-shaped slots of the gradient buffer.  Made here and not in the pass: a table is
+        # uploaded where it is made, which must not happen while a plan records -- _TrainingPlans prepares the net first
+        G = self.grad
+        self._head_split = ops.CopyTable([(self.head_dw[:, :2], p.grad_view(G, "cls.kernel")[0, 0]),
+                                          (self.head_dw[:, 2:], p.grad_view(G, "reg.kernel")[0, 0]),
+                                          (self.head_db[:2], p.grad_view(G, "cls.bias")),
+                                          (self.head_db[2:], p.grad_view(G, "reg.bias"))], self.device)
+        if not self.compose_head:
+            self._up_bias_split = ops.CopyTable(
+                [(self.up_db[256 * L["slot"]:256 * (L["slot"] + 1)], p.grad_view(G, L["conv"].bias))
+                 for L in self.layers if L["kind"] == "deconv"], self.device)
         # the stride-1 convolutions of an RPN block (model_training.py:210-214) share ONE weight-gradient launch: maps of
         # 1 250 - 20 000 positions fill a fraction of the chip each, and as leaves of the backward pass they can wait for each
         # other (lisec_conv_wgrad_batched)
@@ -847,325 +1184,37 @@ class LisecNet:
             self._tail_ok[c.name] = ok
         return ok
 
-    def _backward(self, y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler=None):
-        self._prepare_training()
-        self._pack_all_t()
-        p, a, d, G = self.params, self.act, self.dact, self.grad
-        M = self.Ho * self.Wo
-        sample = self.vfe._sample
+    def _size_backward_scratch(self, sample):
+        """(Re)sizes the scratch that depends on the cloud's capacity: the weight-gradient workspace and the row-list
+        gradient rows of the first Conv3D."""
         first = self.layers[0]["conv"]
-        rcap = max(sample.cap, 1)                 # an empty sweep still needs a non-zero row-list capacity
-        need = ops.wgrad_workspace_bytes(self.dgeom[first.name], rcap)
+        need = ops.wgrad_workspace_bytes(self.dgeom[first.name], max(sample.cap, 1))
         if need > self.wgrad_ws.numel() or self.dout_rows is None or self.dout_rows.shape[0] < sample.cap + 1:
-            torch.cuda.synchronize()               # (re)size scratch that depends on the cloud's capacity
+            torch.cuda.synchronize()
             if need > self.wgrad_ws.numel():
                 self.wgrad_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
             self.dout_rows = torch.empty((sample.cap + 1, 64), dtype=torch.float32, device=self.device)
             _lib.bump_alloc_generation()           # recorded step plans hold the old addresses
-        main = torch.cuda.current_stream()
 
-        side_handle = self.side.cuda_stream
-        events = self._fork_events
-        nfork = [0]
-
-        pending = []
-
-        marked = []
-
-        def mark_fork():
-            """Records the fork event NOW; the next flush_side() waits for this one instead of recording its own.  Lets the
-            chain's next kernel be ENQUEUED before the second stream's work although that work does not depend on it."""
-            if nfork[0] == len(events):
-                events.append(self._new_event())
-            ev = events[nfork[0]]                       # events are reused step after step
-            nfork[0] += 1
-            self._record(ev, main)
-            marked.append(ev)
-
-        def flush_side():
-            """Records ONE event on the main stream and runs every pending closure on the second stream behind it."""
-            if not pending:
-                return
-            if not marked:
-                mark_fork()
-            ev = marked.pop()
-            self._wait(ev, self.side)
-            pin = _lib.pin_stream(side_handle)
-            try:
-                for fn, torch_ops in pending:
-                    if torch_ops:
-                        with torch.cuda.stream(self.side):
-                            fn()
-                    else:
-                        fn()
-            finally:
-                _lib.pin_stream(pin)
-                del pending[:]
-
-        def on_side(fn, torch_ops=False):
-            """Runs fn's launches on the second stream after everything issued so far on the main one.  C-ABI launches
-            take the pinned handle; only a fn that also issues torch / torch.distributed work needs torch's (slow)
-            stream context."""
-            pending.append((fn, torch_ops))
-            flush_side()
-
+    def _backward(self, y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler=None):
+        """The driver of the backward schedule: the loss, then the layers last to first (_BackwardPass), the leaves of
+        the graph beside the chain on the second stream (_SideQueue)."""
+        self._prepare_training()
+        self._pack_all_t()
+        sample = self.vfe._sample
+        self._size_backward_scratch(sample)
+        q = self.side_queue
+        q.begin(torch.cuda.current_stream())
+        bp = _BackwardPass(self, q, sample, rpn_grads_ready, side_filler)
         self._mark("bwd:start")
         self._loss_backward(loss, y_cls, y_reg, grad_scale)
-        # ---- heads (model_training.py:254-255) ---------------------------------------------------
-        # only the data gradient is on the way to the rest of the backward pass: the heads' weight and bias gradients and
-        # the deconv bias gradients (column sums of the concat gradient) are leaves and go to the second stream
-        if self._head_split is None:     # merged head gradients -> the Keras-shaped slots of G
-            self._head_split = ops.CopyTable([(self.head_dw[:, :2], p.grad_view(G, "cls.kernel")[0, 0]),
-                                              (self.head_dw[:, 2:], p.grad_view(G, "reg.kernel")[0, 0]),
-                                              (self.head_db[:2], p.grad_view(G, "cls.bias")),
-                                              (self.head_db[2:], p.grad_view(G, "reg.bias"))], self.device)
-            if not self.compose_head:
-                self._up_bias_split = ops.CopyTable(
-                    [(self.up_db[256 * L["slot"]:256 * (L["slot"] + 1)], p.grad_view(G, L["conv"].bias))
-                     for L in self.layers if L["kind"] == "deconv"], self.device)
-
-        def head_leaves():
-            ops.conv_wgrad(self.head_geom, a["concat"], d["head"], self.head_dw, self.wgrad_ws)
-            ops.colsum(d["head"], 16, M, 16, self.head_db, ws_tag="side")
-            self._head_split.run()
-
-        def concat_leaves():
-            # the three deconv bias gradients are the column sums of the concat gradient: one pass over it
-            ops.colsum(d["concat"], 768, M, 768, self.up_db, ws_tag="side")
-            self._up_bias_split.run()
-
-        if self.compose_head:
-            # collapsed branches + heads: the head gradient feeds the three 16-channel contractions directly; its column
-            # sums (the heads' bias gradient, and through H the branch biases) are the only pass over it
-            self._dshuffle.run(d["head"], backward=True)
-            # (queued, not flushed: the leaves and branches that hang off the head gradient cross to the second stream
-            # behind ONE event, with the first of them that is issued through on_side below)
-            pending.append((lambda: ops.colsum(d["head"], 16, M, 16, self.head_db, ws_tag="side"), False))
-        else:
-            on_side(head_leaves)
-            ops.conv_forward(self.head_dgeom, d["head"], self.packed_t["head"][0], d["concat"])
-            on_side(concat_leaves)
-        layers = self.layers
-        branches_left = [len(DECONVS)]
-        batched_convs = set().union(*[names for _, names in self.wgrad_batches.values()]) if self.wgrad_batches else set()
-        first_write = set()                    # gradient buffers that already hold a contribution
-
-        # ---- RPN blocks, last to first -------------------------------------------------------------
-        writes = {}                            # gradient buffer -> contributions stored so far
-        bwd_ready = {}                         # gradient buffer -> partial rows of its BN-backward statistics
-
-        early_dst = {}                         # gradient buffer -> event behind a contribution made on the second stream
-        fused_dense = {}                       # middle block -> backward sink of a Dense data gradient that rode on a tile
-        late_reduces = []                      # slab sums of the carried Dense weight gradients
-
-        def dgrad_into(c, dy, dst_name, ws_tag="main"):
-            ev = early_dst.pop(dst_name, None) if ws_tag == "main" else None
-            if ev is not None:
-                self._wait(ev, main)           # the branch's contribution is stored before this one accumulates onto it
-            flags = ops.ACCUMULATE if dst_name in first_write else 0
-            # the output of a middle block went through Dense(relu) (model_training.py:195): its gradient is gated
-            # by that activation while the data gradient is stored (single consumer, so no ACCUMULATE there)
-            mask = a[dst_name] if dst_name.endswith(".u") else None
-            # the LAST contribution to the gradient of a conv output also reduces the statistics its
-            # BatchNormalization backward needs (pass 1 of bn_backward folded into the store)
-            writes[dst_name] = writes.get(dst_name, 0) + 1
-            bwd = sink = tail = None
-            if dst_name in self.bn_of and writes[dst_name] == self.consumers[dst_name]:
-                bn_name, C = self.bn_of[dst_name]
-                bwd, sink = (a[dst_name], self.bnstate[bn_name], True), self._bwd_sink(bn_name, C, a[dst_name].numel() // C)
-                bwd_ready[dst_name] = sink
-            use_w = c.name in self.packed_wu_t
-            if mask is not None and not use_w and self._tail_supported(c, dst_name):
-                # the Dense(64, relu) of the block BELOW (model_training.py:195) rides on this tile: its data gradient
-                # dz = (gated gradient) @ Wd^T and the statistics of the BatchNormalization under it come out of the same
-                # launch (lisec_conv_extras.tail_w); the separate Dense data-gradient launch is skipped further down
-                n = dst_name[:-2]
-                Ln = next(L for L in self.layers if L["name"] == n)
-                cn, dn = Ln["conv"], Ln["dense"]
-                sink = self._bwd_sink(cn.bn, 64, cn.M)
-                bwd = (a[n + ".y"], self.bnstate[cn.bn], False)
-                tail = (self.packed_t[dn.name][0], d[n + ".z"])
-                fused_dense[n] = sink
-            if use_w:
-                ops.conv_forward_winograd(self.dgeom[c.name], dy, self.packed_wu_t[c.name], d[dst_name], flags=flags,
-                                          out_mask=mask, bwd=bwd, sink=sink, tail=tail)
-            else:
-                ops.conv_forward(self.dgeom[c.name], dy, self.packed_t[c.name][0], d[dst_name], flags=flags, out_mask=mask,
-                                 bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail)
-            first_write.add(dst_name)
-
-        def branch_dy(L):
-            """The gradient a branch's contraction produced: a concat slice, or (collapsed form) the head gradient / its
-            (tap, j) columns."""
-            if not self.compose_head:
-                return d["concat"][:, :, 256 * L["slot"]:]
-            return d["head"] if L["dT"] is None else L["dT"]
-
-        def deconv_wgrad(L):
-            c = L["conv"]
-            if self.compose_head:
-                b, (ts, cs) = L["slot"], L["wc_strides"]
-                ops.conv_wgrad(c.g, a[L["src"]], branch_dy(L), L["G"], self.wgrad_ws, in_bn=self.bnstate[c.in_bn],
-                               flags=ops.IN_RELU)
-                ops.head_compose_backward(L["G"], ts, cs, p.view(L["up_kernel"]), p.view(L["up_bias"]),
-                                          self.head_w[256 * b:256 * (b + 1)],
-                                          self.head_db, L["k"] * L["k"], L["cin"], 256, p.grad_view(G, L["up_kernel"]),
-                                          p.grad_view(G, L["up_bias"]), self.head_dw[256 * b:256 * (b + 1)])
-                branches_left[0] -= 1
-                if branches_left[0] == 0:
-                    self._head_split.run()         # every row of dH is final: merged (768,16) -> the Keras-shaped slots
-                return
-            dy = d["concat"][:, :, 256 * L["slot"]:]
-            if "wgeom" in L:
-                ops.conv_wgrad(L["wgeom"], dy, a[L["src"]], p.grad_view(G, c.wname), self.wgrad_ws,
-                               flags=ops.DY_RELU, dy_bn=self.bnstate[c.in_bn])
-            else:
-                ops.conv_wgrad(c.g, a[L["src"]], dy, p.grad_view(G, c.wname), self.wgrad_ws,
-                               in_bn=self.bnstate[c.in_bn], flags=ops.IN_RELU, transpose_out=True)
-
-        # the Conv2DTranspose branches of blocks 1 and 2 hang off the concat gradient, which is complete now: both of
-        # their gradients go to the second stream at once, beside the small layers of blocks 3 and 2, instead of waiting
-        # on the chain for their turn; the chain picks their contribution up where it reaches the block's last conv
-        early_layers = set()
-        for L in layers:
-            if L["kind"] == "deconv" and L["slot"] < len(DECONVS) - 1:
-                ev = self._event("bwd_branch%d" % L["slot"])
-
-                def branch(L=L, ev=ev):
-                    deconv_wgrad(L)
-                    dgrad_into(L["conv"], branch_dy(L), L["src"], ws_tag="side")
-                    self._record(ev, self.side)
-                pending.append((branch, False))
-                if not self.compose_head:
-                    flush_side()
-                early_dst[L["src"]] = ev
-                early_layers.add(L["name"])
-
-        for L in reversed(layers):
-            c = L["conv"]
+        bp.heads()
+        bp.early_branches()
+        step = {"deconv": bp.deconv, "conv": bp.conv, "mid": bp.mid}
+        for L in reversed(self.layers):            # RPN blocks, then the middle blocks
             self._mark("bwd:before " + L["name"])
-            if L["kind"] == "deconv":
-                if L["name"] in early_layers:
-                    continue
-                # the chain's contraction goes into its queue BEFORE the leaves that hang off the same gradient: the
-                # second stream's queue is served first (priority) and its kernels fill every CU's LDS, so a chain
-                # kernel enqueued behind them waited for the whole leaf sequence (r03 timeline: 214 us)
-                mark_fork()
-                dgrad_into(c, branch_dy(L), L["src"])
-                on_side(lambda L=L: deconv_wgrad(L))
-                if side_filler is not None:
-                    pending.append((side_filler, False))
-                    flush_side()
-                    side_filler = None
-            elif L["kind"] == "conv":
-                dst = L["dst"]
-                C = c.g.Cout
-                is_first_rpn = L["name"] == "rpn1.conv0"
-                if dst in bwd_ready:
-                    # dgamma / dbeta / coefficients were finalised inside the data-gradient call that stored d[dst]
-                    ops.bn_backward_apply_coef(d[dst], C, a[dst], self.bnstate[c.bn], c.M, C, True,
-                                               bwd_ready.pop(dst).coef, d[dst])
-                else:
-                    ops.bn_backward(d[dst], C, a[dst], self.bnstate[c.bn], c.M, C, True,
-                                    p.grad_view(G, c.bn + ".gamma"), p.grad_view(G, c.bn + ".beta"), d[dst])
-                # the bias of a conv feeding a training-mode BN has gradient sum(dy) == 0 identically (BN removes
-                # the mean); Keras' autograd returns rounding noise there -- the exact 0 stays in self.grad
-                if L["name"] in batched_convs:
-                    # one launch for the block's stride-1 convolutions, issued when the LAST of their output gradients
-                    # (conv1's: the layers are walked back to front) is final
-                    if L["name"] in self.wgrad_batches:
-                        on_side(lambda batch=self.wgrad_batches[L["name"]][0]: batch.run(self.wgrad_ws))
-                else:
-                    on_side(lambda L=L, c=c, dst=dst: ops.conv_wgrad(
-                        c.g, a[L["src"]], d[dst], p.grad_view(G, c.wname), self.wgrad_ws,
-                        in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=ops.IN_RELU if c.in_relu else 0))
-                if is_first_rpn and rpn_grads_ready is not None:
-                    lo = p.offsets["rpn1.conv0.kernel"][1]
-                    on_side(lambda lo=lo: rpn_grads_ready(lo, p.n_theta), torch_ops=True)
-                dgrad_into(c, d[dst], L["src"])
-                if L["src"] == "fold":
-                    # back through Permute + Reshape, gated by the ReLU of the last middle block's Dense (:195)
-                    ops.fold_depth(d["fold"], d[self.fold_src], self.dprime, self.H * self.W, 64, inverse=True,
-                                   mask=a[self.fold_src])
-            else:   # mid layer: conv3d -> BN -> Dense(relu)
-                n, dn = L["name"], L["dense"]
-                dense_wg = lambda n=n, dn=dn: ops.conv_wgrad(dn.g, a[n + ".y"], d[n + ".u"], p.grad_view(G, dn.wname),
-                                                             self.wgrad_ws, in_bn=self.bnstate[dn.in_bn])
-                # the Dense weight gradient (HBM-bound, 52 granules of LDS) finds no room beside three data-gradient
-                # workgroups per CU and waited 474 us in the queue IN FRONT of the block's ring weight gradient: behind it
-                # the ring kernel starts as soon as its gradient exists
-                late_dense = L["src"] != "grid"
-                # the Dense data gradient below reads both operands of the Dense weight gradient: it carries it
-                # (lisec_conv_extras.dense_dw)
-                carried = n not in fused_dense and n in self.dense_dw_slabs
-                if carried:
-                    late_dense = False
-                elif not late_dense:
-                    on_side(dense_wg)
-                # Dense data gradient; its store also reduces the statistics of the BatchNormalization under it
-                if n in fused_dense:
-                    msink = fused_dense.pop(n)         # done inside the data gradient of the block above (dgrad_into)
-                else:
-                    msink = self._bwd_sink(c.bn, 64, c.M)
-                    ops.conv_forward(self.dgeom[dn.name], d[n + ".u"], self.packed_t[dn.name][0], d[n + ".z"],
-                                     bwd=(a[n + ".y"], self.bnstate[c.bn], False), sink=msink,
-                                     dense_dw=self.dense_dw_slabs[n] if carried else None)
-                    if carried:
-                        # the 8 MB slab sum finds no registers beside the Winograd workgroups (46 - 60 us in the step for 6 us of
-                        # work) and the second stream is in order: enqueued right here it held the block's weight gradient back;
-                        # nothing reads the result before the optimizer, so the three sums go behind the last weight gradient
-                        late_reduces.append(lambda n=n, dn=dn: ops.dense_dw_reduce(self.dense_dw_slabs[n],
-                                                                                   p.grad_view(G, dn.wname)))
-                if L["src"] != "grid":
-                    ops.bn_backward_apply_coef(d[n + ".z"], 64, a[n + ".y"], self.bnstate[c.bn], c.M, 64, False, msink.coef,
-                                               d[n + ".z"])
-                if L["src"] == "grid":
-                    # the grid is a constant on the empty cells + V voxel rows: both gradients reduce to V-row
-                    # contractions plus sums of dy over boundary-trimmed boxes (exact; csrc/sparse_grid.hip)
-                    rows = (sample.coords, sample.info, rcap)
-                    dg = self.dgeom[c.name]
-                    dW = p.grad_view(G, c.wname)
-                    # the apply pass of this block's BatchNormalization backward runs inside the line sums (one pass
-                    # over the 82 MB gradient instead of two)
-                    ops.tap_sums_bn(c.g, d[n + ".z"], a[n + ".y"], self.bnstate[c.bn], msink.coef, d[n + ".z"], self.mid1_S,
-                                    self.tapsum_ws)
-                    ops.const_field_grads(p.view(c.wname), self.mid1_S, None, 27, 64, 64, g_all=self.g_all)
-                    vout, delta = self.vfe.saved_field("vout"), self.vfe.saved_field("delta")
-
-                    def sparse_wgrad(dg=dg, dW=dW, dz=d[n + ".z"], rows=rows, vout=vout, delta=delta):
-                        ops.conv_wgrad(dg, dz, delta, dW, self.wgrad_ws, transpose_out=True, rows=rows)
-                        ops.const_field_grads(None, self.mid1_S, vout, 27, 64, 64, dW=dW, cvec_row=sample.info,
-                                              cvec_row_max=sample.cap)
-                    on_side(sparse_wgrad)
-                    ops.conv_forward(dg, d[n + ".z"], self.packed_t[c.name][0], self.dout_rows, rows=rows,
-                                     queue=self.rows_queue)
-                else:
-                    # the weight gradient (second stream) is enqueued BEFORE the block's data gradient: measured 1 % faster
-                    # than the other order
-                    if c.name in self.wino_wgrad_ws:
-                        # Winograd-domain weight gradient (csrc/wino_wgrad.hip): 4 / 9 of the ring kernel's MFMAs
-                        wg = lambda L=L, c=c, n=n: ops.conv_wgrad_winograd(c.g, a[L["src"]], d[n + ".z"],
-                                                                           p.grad_view(G, c.wname), self.wino_wgrad_ws[c.name])
-                    else:
-                        wg = lambda L=L, c=c, n=n: ops.conv_wgrad(c.g, a[L["src"]], d[n + ".z"], p.grad_view(G, c.wname),
-                                                                  self.wgrad_ws)
-                    on_side(wg)
-                    if late_dense:
-                        pending.append((dense_wg, False))
-                        flush_side()
-                    dgrad_into(c, d[n + ".z"], L["src"])
-        # ---- VFE -----------------------------------------------------------------------------------
-        self._mark("bwd:before vfe")
-        for fn in late_reduces:
-            pending.append((fn, False))
-        flush_side()
-        self.vfe.backward(None, G, dout_rows=self.dout_rows, g_all=self.g_all)
-        if self._join_event is None:
-            self._join_event = self._new_event()
-        self._mark("bwd:vfe done")
-        self._record(self._join_event, self.side)
-        self._wait(self._join_event, main)     # every weight gradient has landed before the optimizer reads G
-        self._mark("bwd:joined")
+            step[L["kind"]](L)
+        bp.finish()                                # ... and the VFE
         return self.loss_out
 
     def slot(self, name):

@@ -798,3 +798,33 @@ def test_collapsed_head_equals_layered_head(grid):
     for n, e in worst.items():
         tight = n.startswith(("up", "cls", "reg"))
         assert e < (2e-5 if tight else 5e-3), f"{n}: relative L2 {e:.2e}"
+
+
+@pytest.mark.parametrize("compose_head", [True, False])
+def test_backward_passes_reuse_their_fork_events_and_repeat_their_gradients(compose_head):
+    """Three forward(training=True) + backward passes on one net.  The pool of fork events between the two streams does
+    not grow from the second pass to the third (a recorded step plan holds the events of the pass it recorded), and the
+    backward schedule is bit-reproducible: the batch statistics do not depend on the moving ones, so passes 2 and 3
+    differentiate the same function of the same variables and give the same bits."""
+    from lisec_amd.network import LisecNet
+    from lisec_amd.params import ParamStore
+    from lisec_amd.voxelizer import Voxelizer
+    from oracle import model_ref as M
+
+    dev = torch.device("cuda")
+    net = LisecNet(16, 32, 8, 35, params=ParamStore(dev, init=M.glorot_params(seed=21, randomize_bn=True)),
+                   compose_head=compose_head)
+    sample = Voxelizer(**SMALL)(small_cloud())
+    rng = np.random.default_rng(8)
+    y_cls = torch.from_numpy(rng.integers(0, 3, (8, 16, 2)).astype(np.float32)).to(dev)
+    y_reg = torch.from_numpy(rng.normal(0, 1, (8, 16, 14)).astype(np.float32)).to(dev)
+    grads, pool = [], []
+    for _ in range(3):
+        net.forward(sample, training=True)
+        net.backward(y_cls, y_reg)
+        torch.cuda.synchronize()
+        grads.append(net.grad.clone())
+        pool.append(len(net.side_queue.events))
+    assert pool[1] == pool[2] > 0
+    assert torch.isfinite(grads[1]).all() and grads[1].abs().max() > 0
+    assert torch.equal(grads[1], grads[2])
