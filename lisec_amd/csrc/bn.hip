@@ -72,8 +72,10 @@ k_bn_finalize(const double* __restrict__ parts, int nparts, int C, double N,
     st[3 * C + c] = (float)inv;
     if (mmean) {
         double v = unbiased && N > 1.0 ? var * (N / (N - 1.0)) : var;
-        mmean[c] = (float)((double)mmean[c] * (double)kBnMomentum + mean * (1.0 - (double)kBnMomentum));
-        mvar[c] = (float)((double)mvar[c] * (double)kBnMomentum + v * (1.0 - (double)kBnMomentum));
+        // 0.99 itself, as the in-kernel finaliser of a lisec_bn_sink (conv.h) has it: (double)kBnMomentum is 0.99f widened,
+        // 9.5e-9 off, which a moving mean whose two terms nearly cancel shows as several fp32 ulps
+        mmean[c] = (float)((double)mmean[c] * 0.99 + mean * (1.0 - 0.99));
+        mvar[c] = (float)((double)mvar[c] * 0.99 + v * (1.0 - 0.99));
     }
 }
 

@@ -9,7 +9,8 @@ per geometry, each with a tolerance that does not come from the kernel:
      x applied after affine + ReLU) -- a truncating conversion misses it by ~2^-9;
   3. against the unrounded fp64 result: |got - ref| <= (2u + u^2) (|x| conv |w|) + 1e-4 max|ref|, u = 2^-9 (each operand
      carries one relative rounding of at most u, so each product at most 2u + u^2).
-Geometries: those of test_gpu_conv.py::test_conv3d_mid_layers / ::test_conv2d_rpn_layers plus Lyft-sized RPN maps."""
+Geometries: those of test_gpu_conv.py::test_conv3d_mid_layers / ::test_conv2d_rpn_layers plus Lyft-sized RPN maps, and two
+with a channel count that is no multiple of 64 (RAGGED_CASES).  Every kernel is packed over a NaN-filled buffer."""
 import numpy as np
 import pytest
 import torch
@@ -33,6 +34,14 @@ CASES = [
 ]
 IDS = ["mid_s2", "mid_p0_orelu", "mid_ragged_nobias", "rpn_s2_64", "rpn_128_bn", "rpn_s2_256_bn_orelu", "rpn_256_bn_nobias",
        "lyft_rpn2", "lyft_rpn3"]
+# Channel counts that are no multiple of 64: the only reason the packed kernel is zero padded.  They go through the three
+# operand checks below (the list above is also indexed by position).
+RAGGED_CASES = [
+    (2, 6, 20, 80, 64, (3, 3, 3), (2, 1, 1), (1, 1, 1), True, False, True, 8),           # Cin 80: the second 64-channel slab is a quarter full
+    (1, 9, 21, 64, 40, (1, 3, 3), (1, 1, 1), (0, 1, 1), False, True, True, 9),           # Cout 40: the second 32-column accumulator is partly dead
+]
+RAGGED_IDS = ["mid_cin80_bn", "rpn_cout40_orelu"]
+ALL_CASES, ALL_IDS = CASES + RAGGED_CASES, IDS + RAGGED_IDS
 
 
 def _bf16(t):
@@ -72,30 +81,34 @@ def _draw(case, exact_affine):
     return x, w, b, ((sc, sh) if in_bn else None)
 
 
-def _run(case, x, w, b, bn, splitk=True):
+def _run(case, x, w, b, bn, splitk=True, in_relu=None):
+    """in_relu: LISEC_CONV_IN_RELU; by default it goes with in_bn, as in the network."""
     from lisec_amd import ops
     D, H, W, Cin, Cout, k, stride, pad, in_bn, out_relu, bias, seed = case
     Do, Ho, Wo = ((n + 2 * p - kk) // s + 1 for n, p, kk, s in zip((D, H, W), pad, k, stride))
     geo = ops.geom(0, (D, H, W), (Do, Ho, Wo), k, stride, pad, Cin, Cout)
     ntaps = k[0] * k[1] * k[2]
-    wp = ops.pack_weights_bf16(w.to(DEV), ntaps, Cin, Cout, Cin * Cout, Cout, 1)
+    # packed over NaNs (bf16 0xFFFF): the zero padding of ragged Cin / Cout is the pack's to write
+    wp = torch.full((ops.packed_bf16_bytes(ntaps, Cin, Cout),), 0xFF, dtype=torch.uint8, device=DEV)
+    ops.pack_weights_bf16(w.to(DEV), ntaps, Cin, Cout, Cin * Cout, Cout, 1, out=wp)
     out = torch.full((Do, Ho, Wo, Cout), float("nan"), device=DEV)
     bnstate = None if bn is None else torch.cat([bn[0], bn[1], torch.zeros(2 * Cin)]).to(DEV)
-    flags = (ops.IN_RELU if in_bn else 0) | (ops.OUT_RELU if out_relu else 0)
+    flags = (ops.IN_RELU if (in_bn if in_relu is None else in_relu) else 0) | (ops.OUT_RELU if out_relu else 0)
     ops.conv_forward_bf16(geo, x.to(DEV), wp, out, bias=None if b is None else b.to(DEV), in_bn=bnstate, flags=flags,
                           splitk=splitk)
     torch.cuda.synchronize()
     return out
 
 
-def _activated(x, bn):
+def _activated(x, bn, relu=True):
     """The fp32 value the kernel rounds: relu(fma(x, scale, shift)); fp64 here, compared where that is exact or bounded."""
     if bn is None:
         return x.double()
-    return F.relu(x.double() * bn[0].double() + bn[1].double())
+    a = x.double() * bn[0].double() + bn[1].double()
+    return F.relu(a) if relu else a
 
 
-@pytest.mark.parametrize("case", [c for c in CASES if not c[8]], ids=[i for c, i in zip(CASES, IDS) if not c[8]])
+@pytest.mark.parametrize("case", [c for c in ALL_CASES if not c[8]], ids=[i for c, i in zip(ALL_CASES, ALL_IDS) if not c[8]])
 def test_representable_operands_leave_only_fp32_summation(case):
     x, w, b, bn = _draw(case, True)
     x, w = _bf16(x), _bf16(w)
@@ -105,7 +118,7 @@ def test_representable_operands_leave_only_fp32_summation(case):
     _close(_run(case, x, w, b, bn), ref, "bf16-representable operands")
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", ALL_CASES, ids=ALL_IDS)
 def test_operands_are_rounded_to_nearest_even(case):
     x, w, b, bn = _draw(case, True)
     a = _activated(x, bn)
@@ -118,7 +131,7 @@ def test_operands_are_rounded_to_nearest_even(case):
     _close(_run(case, x, w, b, bn), ref, "RNE-rounded operands")
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", ALL_CASES, ids=ALL_IDS)
 def test_a_priori_bound_against_the_unrounded_result(case):
     x, w, b, bn = _draw(case, False)
     a = _activated(x, bn)
@@ -132,6 +145,18 @@ def test_a_priori_bound_against_the_unrounded_result(case):
     print(f"a-priori bound: max err {err.max().item():.3e}, max err/bound {(err / bound).max().item():.3f}, "
           f"max|ref| {ref.abs().max().item():.3e}")
     assert (err <= bound).all(), f"max err/bound {(err / bound).max().item():.3f}"
+
+
+def test_in_bn_without_in_relu_is_the_affine_alone():
+    """in_bnstate without LISEC_CONV_IN_RELU (relu_lo = -inf): every other case sets the two together.  The exact-affine draw
+    on the rpn_128_bn geometry: about half of the affine's values are negative and must reach the contraction."""
+    case = CASES[4]
+    x, w, b, bn = _draw(case, True)
+    a = _activated(x, bn, relu=False)
+    assert torch.equal(a.float().double(), a) and 0.3 < (a < 0).float().mean() < 0.7
+    assert (_bf16(a.float()).double() != a).float().mean() > 0.05
+    ref = _conv64(_bf16(a.float()), _bf16(w), b, case[6], case[7])
+    _close(_run(case, x, w, b, bn, in_relu=False), ref, "RNE-rounded operands, affine without ReLU")
 
 
 @pytest.mark.parametrize("case", [CASES[0], CASES[4], CASES[7], CASES[8]], ids=["mid_s2", "rpn_128_bn", "lyft_rpn2", "lyft_rpn3"])
