@@ -91,6 +91,29 @@ int lisec_voxelize(const lisec_voxel_cfg* cfg, const void* points, int dtype, in
                    int32_t* npts, int32_t* row_start, float* rows, int32_t* row_point,
                    int64_t* row_stats, lisec_stream_t stream);
 
+/* 1b. The reference's random subsample of a crowded voxel (np.random.choice(bucket, size=35, replace=False),
+ *     model_training.py:131-132; VoxelNet section 2.1.1), seeded.  lisec_voxelize_draw is lisec_voxelize with one rule
+ *     changed, for voxels with count > sampleSize only.  Random numbers are those of section 5c: Philox4x32-10, key = seed
+ *     (low word, high word), counter = (stream, item, epoch, index); this draw is stream 4 and `index` is the point's row
+ *     index in `points`.  Point i of such a voxel has the 64-bit key (Philox(4, item, epoch, i)[0] << 32) | i; the
+ *     sampleSize points with the smallest keys are kept (the low word breaks equal Philox words, so the rule is total) and
+ *     emitted in ASCENDING POINT INDEX, as lisec_voxelize emits its rows.  Centroid, feature rows, row_point and row_stats
+ *     follow from the kept points exactly as there.  Voxels with count <= sampleSize, and coords, counts, npts,
+ *     row_start, cell_voxel and info, are those of lisec_voxelize bit for bit.  The key depends on the point index alone
+ *     -- not on the order the points reach their voxel, not on rows behind the sweep -- so the result is deterministic
+ *     and the same for a sweep padded to a fixed capacity with rows outside the grid as for the bare sweep.
+ *   draw  dev  uint32[4] = seed low word, seed high word, item, epoch, READ BY THE KERNEL when it runs: a recorded step plan
+ *     (section 5b) replays with whatever the words hold then.  lisec_voxel_draw_set writes them with a one-thread kernel
+ *     on `stream` (scalar arguments, no host synchronisation; recorded like any launch when the thread records a plan).
+ *     draw == NULL: LISEC_EINVAL, nothing enqueued.  The workspace is that of lisec_voxelize. */
+int lisec_voxelize_draw(const lisec_voxel_cfg* cfg, const void* points, int dtype, int n_points,
+                        int point_stride, void* workspace, size_t workspace_bytes, int cap_voxels,
+                        int32_t* info, int32_t* cell_voxel, int32_t* coords, int32_t* counts,
+                        int32_t* npts, int32_t* row_start, float* rows, int32_t* row_point,
+                        int64_t* row_stats, const uint32_t* draw, lisec_stream_t stream);
+int lisec_voxel_draw_set(uint32_t* draw, unsigned long long seed, unsigned int item, unsigned int epoch,
+                         lisec_stream_t stream);
+
 /* Expands compact rows into the zero padded (V, T, 6) block layout the reference's
  * SparseTensor / dense tensor uses (model_training.py:141-152).  padded: float32[V*T*6]. */
 int lisec_voxel_rows_to_padded(const int32_t* info, const int32_t* npts, const int32_t* row_start,
@@ -967,7 +990,7 @@ int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_
  *     with half extent w/2 and v = (sin yaw, cos yaw) with half extent l/2.  A point is inside a box iff |d.u| <= w/2,
  *     |d.v| <= l/2 and z lies in the z extent (all closed); a point inside several boxes belongs to the lowest index.
  *     Random numbers: Philox4x32-10, key = seed (low word, high word), counter = (stream, item, epoch, index), stream 0 =
- *     global, 1 = per box, 2 = balance, 3 = object sampling; uniform = (u32 + 0.5) * 2^-32 and Box-Muller normals (z0 = r cos t, z1 = r sin t,
+ *     global, 1 = per box, 2 = balance, 3 = object sampling, 4 = the voxeliser's per-voxel subsample (section 1b); uniform = (u32 + 0.5) * 2^-32 and Box-Muller normals (z0 = r cos t, z1 = r sin t,
  *     r = sqrt(-2 ln u1), t = 2 pi u2), both in double.  Every entry only enqueues on `stream`: no host synchronisation.
  *
  * lisec_augment_draw, one workgroup.  Global: words w = Philox(0, item, epoch, 0): s = scale_lo + (scale_hi - scale_lo) *

@@ -141,6 +141,10 @@ def _declare(lib):
     lib.lisec_voxelize.restype = c_int
     lib.lisec_voxelize.argtypes = [POINTER(VoxelCfg), P, c_int, c_int, c_int, P, c_size_t, c_int,
                                    P, P, P, P, P, P, P, P, P, P]
+    lib.lisec_voxelize_draw.restype = c_int
+    lib.lisec_voxelize_draw.argtypes = lib.lisec_voxelize.argtypes[:-1] + [P, P]
+    lib.lisec_voxel_draw_set.restype = c_int
+    lib.lisec_voxel_draw_set.argtypes = [P, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, P]
     lib.lisec_voxel_rows_to_padded.restype = c_int
     lib.lisec_voxel_rows_to_padded.argtypes = [P, P, P, P, c_int, c_int, P, P]
     lib.lisec_vfe_saved_floats.restype = c_size_t

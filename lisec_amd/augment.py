@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, boxes as _boxes, ops
+from .voxelizer import check_subsample
 
 PAD_LIMIT = 0.5e6             # rows at |x| >= this are the pad rows of a recorded step's point buffer (_StepPlans.PAD / 2)
 
@@ -165,6 +166,8 @@ class _Staged:
 
     def __init__(self, seq, i):
         self.seq, self.i = seq, i
+        # (seed, item, epoch) of the voxeliser's per-voxel subsample, None for subsample='first'
+        self.draw = (seq.seed, i, seq.epoch) if seq.subsample == "random" else None
 
     def stage_into(self, points, y_cls, y_reg):
         return self.seq.stage(self.i, points, y_cls, y_reg)
@@ -179,11 +182,17 @@ class AugmentedSweeps:
     it: the augmentation and the label kernels run where fit() stages a sweep, and write the step's buffers directly.
     database: an ObjectDatabase; every item is then filled up towards sample_to boxes with sampled objects before the
     noise (with augment=False: sampled and pasted only).  Item i then has n_i + database.bound(K_i) rows, pad rows at 1e6
-    included -- the voxeliser drops them --, and max_points covers the largest."""
+    included -- the voxeliser drops them --, and max_points covers the largest.
+    subsample='random': fit() voxelises item i with the reference's random per-voxel subsample as the draw of (seed, i,
+    epoch) (Voxelizer(subsample='random')), so a crowded voxel keeps other points every epoch; 'first' (the default) keeps
+    the lowest point indices.  The draw goes by the item index, not by the rank that trains on it: data parallel needs
+    nothing more.  The items themselves -- points and label maps -- do not depend on it."""
 
-    def __init__(self, points_list, boxes_list, seed=0, augment=True, balance=True, database=None, sample_to=15, **params):
+    def __init__(self, points_list, boxes_list, seed=0, augment=True, balance=True, database=None, sample_to=15,
+                 subsample="first", **params):
         if len(points_list) != len(boxes_list):
             raise ValueError("one box set per sweep")
+        self.subsample = check_subsample(subsample)
         dev = _lib.require_gpu()
         self.params = _params(params)
         self.seed, self.augment, self.balance, self.epoch = int(seed), bool(augment), bool(balance), 0

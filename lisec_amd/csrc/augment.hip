@@ -17,13 +17,14 @@
 // with half extent w/2 and v = (sin yaw, cos yaw) with half extent l/2.
 //
 // Random numbers: Philox4x32-10 (Salmon et al., SC'11), key = the 64-bit seed (low word, high word), counter =
-// (stream, item, epoch, index).  Streams: 0 global, 1 per-box, 2 balance, 3 sampling.  Integer-exact, so a numpy restatement
+// (stream, item, epoch, index).  Streams: 0 global, 1 per-box, 2 balance, 3 sampling (4: voxelize.hip).  Integer-exact, so a numpy restatement
 // reproduces every draw bit for bit; uniform = (u32 + 0.5) * 2^-32, normals by Box-Muller, both in double.
 // Integer / latency-bound work in float64: no MFMA.
 #include <algorithm>
 
 #include "common.h"
 #include "box_geom.h"
+#include "philox.h"
 
 namespace lisec {
 namespace {
@@ -33,18 +34,6 @@ constexpr int kMaxAttempts = LISEC_AUG_MAX_ATTEMPTS;
 constexpr int kMaxSamples = LISEC_AUG_MAX_SAMPLES;
 constexpr int kChunk = 128;                        // boxes staged in LDS at a time by k_augment_apply
 constexpr double kTwoPi = 6.283185307179586476925286766559;
-
-struct U4 { uint32_t v[4]; };
-
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return U4{{c0, c1, c2, c3}};
-}
 
 __device__ __forceinline__ double uniform01(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
 

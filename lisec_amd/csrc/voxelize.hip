@@ -14,15 +14,30 @@
 //   k_cell_assign  /  row offset -> voxels come out sorted by cell = (z*NX + x)*NY + y
 //   k_place          1 thread / point       bucket[pt_start[v] + rank] = point index
 //   k_features       1 wave / voxel         keeps the `sampleSize` lowest point indices in
-//                                           ascending order (deterministic stand-in for the
-//                                           unseeded np.random.choice, model_training.py:132),
+//                                           ascending order (the default: a deterministic stand-in
+//                                           for the unseeded np.random.choice, model_training.py:132)
+//                                           or, for lisec_voxelize_draw, the `sampleSize` smallest
+//                                           Philox keys of (seed, item, epoch, point index) -- the
+//                                           random subsample, seeded -- also in ascending order;
 //                                           centroid = sequential fp64 sum / s (np.mean order,
 //                                           :135), rows [x,y,z,x-cx,y-cy,z-cz] rounded to fp32;
 //                                           on the side the 6 + 21 first / second moments of the
 //                                           rows it writes (row_stats: what the VFE's first
 //                                           BatchNormalization needs, see lisec_hip.h)
 // All of it is HBM/latency-bound integer work: no MFMA, LDS only as per-wave scratch.
+//
+// The seeded draw (kDraw, lisec_hip.h section 1b) only touches voxels with count > sampleSize.  Point i has the key
+// (Philox(4, item, epoch, i)[0] << 32) | i; the sampleSize smallest keys survive.  count <= 64: one key per lane, ranked
+// against the others by shuffles.  count > 64: a radix select by byte from the top of the key -- a 256-bin histogram per
+// wave in LDS, a wave scan over it finds the bin holding the sampleSize-th key, the next pass looks only at keys with
+// that prefix -- which stops as soon as the bin is taken whole: two or three passes on random words, eight (the key
+// width) at the most, since the low word is unique.  The Philox words of a voxel of up to kKeyCache points wait in
+// per-wave LDS between the passes; a larger voxel computes them again in every pass.  Histogram and cache borrow the
+// feature scratch of the wave, which is idle during the select: the draw adds no LDS.  The survivors are compacted with
+// 64-bit ballots and sorted by index as the count <= 64 branch sorts.  (seed, item, epoch) are read from device memory,
+// so a recorded launch draws with whatever the words hold when it is replayed.
 #include "common.h"
+#include "philox.h"
 
 namespace lisec {
 namespace {
@@ -30,6 +45,7 @@ namespace {
 constexpr int kScanThreads = 256;
 constexpr int kCellsPerThread = 8;
 constexpr int kCellsPerBlock = kScanThreads * kCellsPerThread;
+constexpr int kKeyCache = 384;           // Philox words per wave kept in LDS between the passes of the select (sfeat[w])
 
 struct GridDims {
     int nx, ny, nz, ncells, T;
@@ -230,12 +246,19 @@ __global__ void k_place(const int* __restrict__ key, const int* __restrict__ ran
     bucket[pt_start[v] + rank[i]] = i;
 }
 
-template <typename T>
+__global__ void k_draw_set(uint32_t* __restrict__ draw, uint32_t k0, uint32_t k1, uint32_t item, uint32_t epoch) {
+    draw[0] = k0; draw[1] = k1; draw[2] = item; draw[3] = epoch;
+}
+
+// kDraw: the seeded subsample of voxels with more than Tmax points (draw: seed lo, seed hi, item, epoch); without it the
+// kernel is the deterministic one and `draw` is not read
+template <typename T, bool kDraw>
 __global__ void __launch_bounds__(256)
 k_features(const T* __restrict__ pts, int stride, const int* __restrict__ info, int cap_voxels,
            int Tmax, const int* __restrict__ counts, const int* __restrict__ pt_start,
            const int* __restrict__ row_start, const int* __restrict__ bucket,
-           float* __restrict__ rows, int* __restrict__ row_point, long long* __restrict__ row_stats) {
+           float* __restrict__ rows, int* __restrict__ row_point, long long* __restrict__ row_stats,
+           const uint32_t* __restrict__ draw) {
     __shared__ double spt[4][64][3];
     __shared__ int ssel[4][64];
     const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -252,6 +275,8 @@ k_features(const T* __restrict__ pts, int stride, const int* __restrict__ info, 
     }
     int V = info[LISEC_VI_NVOX];
     if (V > cap_voxels) V = cap_voxels;
+    uint32_t dk0 = 0, dk1 = 0, ditem = 0, depoch = 0;
+    if constexpr (kDraw) { dk0 = draw[0]; dk1 = draw[1]; ditem = draw[2]; depoch = draw[3]; }
     const int nwaves = gridDim.x * 4;
     for (int v = blockIdx.x * 4 + w; v < V; v += nwaves) {
         const int c = counts[v], b0 = pt_start[v];
@@ -259,9 +284,99 @@ k_features(const T* __restrict__ pts, int stride, const int* __restrict__ info, 
         int mine = -1;                       // lane t < s ends up with the t-th smallest index
         if (c <= 64) {
             int my = lane < c ? bucket[b0 + lane] : 0x7fffffff;
+            if constexpr (kDraw) {
+                if (c > s) {                 // a lane whose key is not among the s smallest gives its point up
+                    const uint32_t h = lane < c ? philox4x32_10(4u, ditem, depoch, (uint32_t)my, dk0, dk1).v[0] : 0u;
+                    int rk = 0;
+                    for (int j = 0; j < c; ++j) {
+                        const uint32_t hj = (uint32_t)__shfl((int)h, j, 64);
+                        const int ij = __shfl(my, j, 64);
+                        rk += hj < h || (hj == h && ij < my);
+                    }
+                    if (rk >= s) my = 0x7fffffff;
+                }
+            }
             int r = 0;
             for (int j = 0; j < c; ++j) r += __shfl(my, j, 64) < my;
             if (lane < c && r < s) ssel[w][r] = my;
+            __threadfence_block();
+            if (lane < s) mine = ssel[w][lane];
+        } else if constexpr (kDraw) {
+            // the select is over before the feature rows are made: its 256-bin histogram lives in this wave's spt
+            // slice and its key cache in this wave's sfeat slice (fences stand between the two uses), so the draw costs no
+            // LDS and the kernel keeps the deterministic one's workgroups per CU
+            static_assert(sizeof(double) * 64 * 3 >= sizeof(int) * 256 && sizeof(float) * 64 * 6 >= sizeof(uint32_t) * kKeyCache,
+                          "the select's scratch does not fit the feature scratch");
+            int* const hist = reinterpret_cast<int*>(&spt[w][0][0]);
+            uint32_t* const keyc = reinterpret_cast<uint32_t*>(&sfeat[w][0][0]);
+            const bool cached = c <= kKeyCache;      // wave-uniform
+            if (cached) {
+                for (int j = lane; j < c; j += 64)
+                    keyc[j] = philox4x32_10(4u, ditem, depoch, (uint32_t)bucket[b0 + j], dk0, dk1).v[0];
+                __threadfence_block();
+            }
+            auto key_of = [&](int j, int idx) -> unsigned long long {
+                const uint32_t h = cached ? keyc[j] : philox4x32_10(4u, ditem, depoch, (uint32_t)idx, dk0, dk1).v[0];
+                return ((unsigned long long)h << 32) | (uint32_t)idx;
+            };
+            // radix select: after the pass at `shift` the keys to keep are those with (key >> shift) below the prefix,
+            // plus the `need` smallest of those equal to it
+            unsigned long long prefix = 0;
+            int need = s, shift = 56;
+            for (;; shift -= 8) {                    // at most 8 passes: the key width
+#pragma unroll
+                for (int q = 0; q < 4; ++q) hist[4 * lane + q] = 0;
+                __threadfence_block();
+                for (int j = lane; j < c; j += 64) {
+                    const unsigned long long k = key_of(j, bucket[b0 + j]);
+                    if (shift == 56 || (k >> (shift + 8)) == (prefix >> (shift + 8)))
+                        atomicAdd(&hist[(int)(k >> shift) & 255], 1);
+                }
+                __threadfence_block();
+                const int4 hb = make_int4(hist[4 * lane], hist[4 * lane + 1], hist[4 * lane + 2],
+                                          hist[4 * lane + 3]);                 // lane owns bins 4 lane .. 4 lane + 3
+                const int sum = hb.x + hb.y + hb.z + hb.w;
+                int inc = sum;
+                for (int o = 1; o < 64; o <<= 1) {
+                    const int y = __shfl_up(inc, o, 64);
+                    if (lane >= o) inc += y;
+                }
+                const int excl = inc - sum;
+                // the bin of the need-th candidate: in the last lane whose bins start below it (excl never decreases)
+                const int L = __popcll(__ballot(excl < need)) - 1;
+                int rem = need - excl, bin = 4 * lane, cnt = hb.x;
+                if (rem > hb.x) {
+                    rem -= hb.x; bin += 1; cnt = hb.y;
+                    if (rem > hb.y) {
+                        rem -= hb.y; bin += 1; cnt = hb.z;
+                        if (rem > hb.z) { rem -= hb.z; bin += 1; cnt = hb.w; }
+                    }
+                }
+                bin = __shfl(bin, L, 64); need = __shfl(rem, L, 64); cnt = __shfl(cnt, L, 64);
+                prefix |= (unsigned long long)bin << shift;
+                if (cnt <= need || shift == 0) break;    // the bin is taken whole (keys are unique: at shift 0 it holds one)
+            }
+            // the survivors in bucket order, then sorted by index as above
+            int base = 0;
+            for (int j0 = 0; j0 < c; j0 += 64) {
+                const int j = j0 + lane;
+                int idx = 0;
+                bool sel = false;
+                if (j < c) {
+                    idx = bucket[b0 + j];
+                    sel = (key_of(j, idx) >> shift) <= (prefix >> shift);
+                }
+                const unsigned long long m = __ballot(sel);
+                const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+                if (sel && pos < 64) ssel[w][pos] = idx;
+                base += __popcll(m);
+            }
+            __threadfence_block();
+            const int my = lane < s ? ssel[w][lane] : 0x7fffffff;
+            int r = 0;
+            for (int j = 0; j < s; ++j) r += __shfl(my, j, 64) < my;
+            __threadfence_block();
+            if (lane < s) ssel[w][r] = my;
             __threadfence_block();
             if (lane < s) mine = ssel[w][lane];
         } else {
@@ -384,12 +499,11 @@ extern "C" size_t lisec_voxelize_workspace_bytes(const lisec_voxel_cfg* cfg, int
     return carve(nullptr, g, n_points, n_points).bytes;
 }
 
-extern "C" int lisec_voxelize(const lisec_voxel_cfg* cfg, const void* points, int dtype,
-                              int n_points, int point_stride, void* workspace,
-                              size_t workspace_bytes, int cap_voxels, int32_t* info,
-                              int32_t* cell_voxel, int32_t* coords, int32_t* counts,
-                              int32_t* npts, int32_t* row_start, float* rows, int32_t* row_point,
-                              int64_t* row_stats, lisec_stream_t stream_) {
+// lisec_voxelize (draw == nullptr: the deterministic k_features) and lisec_voxelize_draw share everything else
+static int voxelize(const lisec_voxel_cfg* cfg, const void* points, int dtype, int n_points, int point_stride,
+                    void* workspace, size_t workspace_bytes, int cap_voxels, int32_t* info, int32_t* cell_voxel,
+                    int32_t* coords, int32_t* counts, int32_t* npts, int32_t* row_start, float* rows,
+                    int32_t* row_point, int64_t* row_stats, const uint32_t* draw, lisec_stream_t stream_) {
     GridDims g;
     if (int rc = make_dims(cfg, &g)) return rc;
     LISEC_CHECK_ARG(n_points >= 0 && point_stride >= 3, "n_points/point_stride invalid");
@@ -434,15 +548,44 @@ extern "C" int lisec_voxelize(const lisec_voxel_cfg* cfg, const void* points, in
         int fb = cdiv(cap_voxels, 4);
         if (fb > 2048) fb = 2048;
         if (dtype == 0)
-            LISEC_LAUNCH(k_features<float>, dim3(fb), dim3(256), 0, st, (const float*)points,
-                               point_stride, info, cap_voxels, g.T, counts, w.pt_start, row_start,
-                               w.bucket, rows, row_point, stats);
+            LISEC_LAUNCH(draw ? k_features<float, true> : k_features<float, false>, dim3(fb), dim3(256), 0, st,
+                               (const float*)points, point_stride, info, cap_voxels, g.T, counts, w.pt_start,
+                               row_start, w.bucket, rows, row_point, stats, draw);
         else
-            LISEC_LAUNCH(k_features<double>, dim3(fb), dim3(256), 0, st, (const double*)points,
-                               point_stride, info, cap_voxels, g.T, counts, w.pt_start, row_start,
-                               w.bucket, rows, row_point, stats);
+            LISEC_LAUNCH(draw ? k_features<double, true> : k_features<double, false>, dim3(fb), dim3(256), 0, st,
+                               (const double*)points, point_stride, info, cap_voxels, g.T, counts, w.pt_start,
+                               row_start, w.bucket, rows, row_point, stats, draw);
         LISEC_LAUNCH_CHECK();
     }
+    return LISEC_OK;
+}
+
+extern "C" int lisec_voxelize(const lisec_voxel_cfg* cfg, const void* points, int dtype,
+                              int n_points, int point_stride, void* workspace,
+                              size_t workspace_bytes, int cap_voxels, int32_t* info,
+                              int32_t* cell_voxel, int32_t* coords, int32_t* counts,
+                              int32_t* npts, int32_t* row_start, float* rows, int32_t* row_point,
+                              int64_t* row_stats, lisec_stream_t stream_) {
+    return voxelize(cfg, points, dtype, n_points, point_stride, workspace, workspace_bytes, cap_voxels, info, cell_voxel,
+                    coords, counts, npts, row_start, rows, row_point, row_stats, nullptr, stream_);
+}
+
+extern "C" int lisec_voxelize_draw(const lisec_voxel_cfg* cfg, const void* points, int dtype, int n_points,
+                                   int point_stride, void* workspace, size_t workspace_bytes, int cap_voxels,
+                                   int32_t* info, int32_t* cell_voxel, int32_t* coords, int32_t* counts,
+                                   int32_t* npts, int32_t* row_start, float* rows, int32_t* row_point,
+                                   int64_t* row_stats, const uint32_t* draw, lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(draw, "draw is NULL (lisec_voxelize is the deterministic entry)");
+    return voxelize(cfg, points, dtype, n_points, point_stride, workspace, workspace_bytes, cap_voxels, info, cell_voxel,
+                    coords, counts, npts, row_start, rows, row_point, row_stats, draw, stream_);
+}
+
+extern "C" int lisec_voxel_draw_set(uint32_t* draw, unsigned long long seed, unsigned int item, unsigned int epoch,
+                                    lisec_stream_t stream_) {
+    LISEC_CHECK_ARG(draw, "draw is NULL");
+    LISEC_LAUNCH(k_draw_set, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream_), draw, (uint32_t)seed,
+                 (uint32_t)(seed >> 32), (uint32_t)item, (uint32_t)epoch);
+    LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
 

@@ -26,7 +26,7 @@ from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table
 from .network import EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len
 from .params import ParamStore
-from .voxelizer import VoxelSample, Voxelizer, host_row_stats
+from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -40,14 +40,29 @@ def get_voxel(point, xSize, ySize, zSize):
 _VOXELIZERS = {}
 
 
-def VFE_preprocessing(points, xSize, ySize, zSize, sampleSize, maxVoxelX, maxVoxelY, maxVoxelZ):
+def VFE_preprocessing(points, xSize, ySize, zSize, sampleSize, maxVoxelX, maxVoxelY, maxVoxelZ, seed=None, item=0, epoch=0):
     """points (n, >=3) -> SparseVoxels, the stand-in for the tf.SparseTensor of dense_shape
     [maxVoxelZ, 2*maxVoxelX, 2*maxVoxelY, sampleSize, 6] the reference returns (model_training.py:112-152).
-    Deterministic: a voxel holding more than sampleSize points keeps the lowest point indices."""
+    Deterministic: a voxel holding more than sampleSize points keeps the lowest point indices (seed=None) or, with a
+    seed, the reference's random sampleSize of them as the draw of (seed, item, epoch) (Voxelizer(subsample='random'));
+    the slots stay in ascending point index."""
     key = (float(xSize), float(ySize), float(zSize), int(sampleSize), int(maxVoxelX), int(maxVoxelY), int(maxVoxelZ))
+    if seed is not None:
+        rkey = key + ("random",)
+        if rkey not in _VOXELIZERS:
+            _VOXELIZERS[rkey] = Voxelizer(*key[:3], key[3], *key[4:], subsample="random")
+        vox = _VOXELIZERS[rkey]
+        vox.seed = int(seed)
+        return SparseVoxels(vox(points, draw=(item, epoch)))
     if key not in _VOXELIZERS:
         _VOXELIZERS[key] = Voxelizer(*key[:3], key[3], *key[4:])
     return SparseVoxels(_VOXELIZERS[key](points))
+
+
+def _sequence_subsample(seq):
+    """The voxeliser's subsample mode for a Sequence of raw sweeps: its `subsample` when its items carry their draw into a
+    recorded step (AugmentedSweeps.staged), else 'first'."""
+    return check_subsample(getattr(seq, "subsample", "first")) if hasattr(seq, "staged") else "first"
 
 
 class SparseVoxels:
@@ -666,8 +681,9 @@ class Model:
             need = max((int(p.shape[0]) for p in pts), default=0)
             dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         grid = self._sequence_grid()
-        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
-        return key, grid, dtype, int(need), max(1024, -(-int(need) // 4096) * 4096)
+        mode = _sequence_subsample(seq)
+        key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype, mode)
+        return key, grid, dtype, int(need), max(1024, -(-int(need) // 4096) * 4096), mode
 
     def _sequence_item(self, seq, i, recorded):
         """What a step trains on when x is a Sequence: for a recorded step the item as something that stages itself into
@@ -679,7 +695,10 @@ class Model:
         if recorded:
             return pts, y_cls, y_reg
         dev = self.net.device
-        vox = VFE_preprocessing(pts, *self._sequence_grid()).sample
+        draw = {}
+        if _sequence_subsample(seq) == "random":       # the draw the recorded step's buffer set is given
+            draw = dict(seed=seq.seed, item=i, epoch=seq.epoch)
+        vox = VFE_preprocessing(pts, *self._sequence_grid(), **draw).sample
         return (vox, torch.as_tensor(y_cls, dtype=torch.float32).to(dev), torch.as_tensor(y_reg, dtype=torch.float32).to(dev))
 
     def _plan_request(self, samples):
@@ -692,7 +711,7 @@ class Model:
         dtype = torch.float64 if any(p.dtype == torch.float64 for p in pts) else torch.float32
         need = max(int(p.shape[0]) for p in pts)
         key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
-        return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096)     # a little head-room for later calls
+        return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096), "first"     # a little head-room for later calls
 
     def _captured_step(self, samples, opt, seq_req=None):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
@@ -704,12 +723,12 @@ class Model:
             req = self._plan_request(samples) if seq_req is None else seq_req
         if req is None:
             return None
-        key, grid, dtype, need, capacity = req
+        key, grid, dtype, need, capacity, mode = req
         key += (opt.config,)         # the full optimizer config: a re-compile with another optimizer records a new plan
         step = _reusable(self._captured, key, need)
         if step is None:
             cls = PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep
-            step = cls(self.net, Voxelizer(*grid, device=self.net.device), capacity, dtype=dtype, loss=self.loss,
+            step = cls(self.net, Voxelizer(*grid, device=self.net.device, subsample=mode), capacity, dtype=dtype, loss=self.loss,
                        opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None)
             self._captured = (key, step)
         return step
@@ -723,13 +742,13 @@ class Model:
         req = self._plan_request(samples) if _lib.knob("eval_plan", False) else None
         if req is None:
             return None
-        key, grid, dtype, need, capacity = req
+        key, grid, dtype, need, capacity, _ = req
         step = _reusable(self._eval_captured, key, need)
         if step is None:
             # the training step's voxeliser, whose workspace already holds a training sweep: a validation sweep no
             # larger than the training ones then allocates nothing, and the recorded training step stays valid
             train = self._captured
-            if train is not None and train[0][0] == grid and train[1].plans:
+            if train is not None and train[0][0] == grid and train[1].plans and train[1].vox.subsample == "first":
                 vox = train[1].vox
             else:
                 vox = Voxelizer(*grid, device=self.net.device)
@@ -1029,13 +1048,15 @@ def train_with_model(samples, level5Data, model_path, save_path):
     return _train(samples, level5Data, save_path, model_path)
 
 
-def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0):
+def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0, subsample='first'):
     """OURS, not the reference's: train() on sweeps that are augmented anew at every step (augment.AugmentedSweeps: per-box
     noise with collision rejection, one global scale and rotation, VoxelNet section 3.3) with the label maps of the moved
     boxes made on the device (boxes.rpnTargets) instead of the precomputed labels3/*.npy.  The sweeps come from
     combine_lidar_data_gpu, the boxes from boxes.annotationBoxes; one pass over the samples per epoch, the reference's
     SGD.  sample_to > 0: ground-truth object sampling (augment.ObjectDatabase, built from the same sweeps and boxes) fills
-    every sweep up towards that many boxes before the noise.  Returns the model, saved at save_path."""
+    every sweep up towards that many boxes before the noise.  subsample='random': a voxel holding more than maxPoints
+    points keeps the reference's random subsample, drawn anew per (seed, item, epoch), instead of the lowest point indices
+    (AugmentedSweeps).  Returns the model, saved at save_path."""
     from . import augment, boxes
     _refuse_mixed_training(mixed_precision.global_policy())
     points = [combine_lidar_data_gpu(s, Constants.lyft_data_dir, level5Data) for s in samples]
@@ -1044,7 +1065,7 @@ def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=
     sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
     model.compile(optimizer=sgd, loss=['mse', 'mse'])
     database = augment.ObjectDatabase(points, rows) if sample_to > 0 else None
-    seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to)
+    seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to, subsample=subsample)
     history = model.fit(x=seq, batch_size=1, verbose=1, epochs=epochs)
     if model.dp is None or model.dp.rank == 0:
         print(history.history)

@@ -1418,6 +1418,12 @@ class _StepPlans:
             n = stage(self.points[j], self.ycls[j], self.yreg[j])
             if n < self.capacity:
                 self.points[j][n:].fill_(self.PAD)
+            draw = getattr(points, "draw", None)
+            if draw is not None:
+                # the per-voxel subsample of this item (a subsample='random' voxeliser): (seed, item, epoch) go into
+                # the draw words of THIS buffer set's sample, which the recorded voxeliser launches read when they run
+                seed, item, epoch = draw
+                self.vox.set_draw(self.samples[j], item, epoch, seed=seed)
             return
         pts = torch.as_tensor(points)
         n = int(pts.shape[0])

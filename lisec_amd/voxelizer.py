@@ -24,14 +24,16 @@ class VoxelSample:
     rows        float32[n,6]      compact feature rows
     row_point   int32[n]          original point index per row
     row_stats   int64[LISEC_ROW_STATS_WORDS]  first / second moments of the rows (fixed point) + VFE scratch
+    draw        int32[4] or None  (seed low word, seed high word, item, epoch) of the per-voxel subsample, read by the
+                kernel when it runs; only a sample of a Voxelizer(subsample='random') has it
     """
 
     def __init__(self, cfg, n_points, cap, info, cell_voxel, coords, counts, npts, row_start, rows,
-                 row_point, row_stats=None):
+                 row_point, row_stats=None, draw=None):
         self.cfg, self.n_points, self.cap = cfg, n_points, cap
         self.info, self.cell_voxel, self.coords = info, cell_voxel, coords
         self.counts, self.npts, self.row_start = counts, npts, row_start
-        self.rows, self.row_point, self.row_stats = rows, row_point, row_stats
+        self.rows, self.row_point, self.row_stats, self.draw = rows, row_point, row_stats, draw
         self._host_info = None
 
     @property
@@ -88,10 +90,27 @@ def host_row_stats(rows):
     return out
 
 
-class Voxelizer:
-    """Reusable voxeliser for one grid; owns its workspace (grown on demand)."""
+SUBSAMPLE_MODES = ("first", "random")
 
-    def __init__(self, xSize, ySize, zSize, sampleSize, maxVoxelX, maxVoxelY, maxVoxelZ, device=None):
+
+def check_subsample(mode):
+    if mode not in SUBSAMPLE_MODES:
+        raise ValueError(f"subsample must be one of {', '.join(SUBSAMPLE_MODES)}, not {mode!r}")
+    return mode
+
+
+class Voxelizer:
+    """Reusable voxeliser for one grid; owns its workspace (grown on demand).
+
+    subsample: which points a voxel holding more than sampleSize keeps.  'first' (the default, lisec_voxelize): the lowest
+    point indices.  'random' (lisec_voxelize_draw, include/lisec_hip.h section 1b): the reference's random choice, as a
+    seeded draw that is a pure function of (seed, item, epoch) and the point's row index -- the same whatever the arrival
+    order, the padding behind the sweep or the rank that voxelises it (data parallel: the draw goes by the item index).
+    The slots of a voxel stay in ascending point index either way."""
+
+    def __init__(self, xSize, ySize, zSize, sampleSize, maxVoxelX, maxVoxelY, maxVoxelZ, device=None, subsample="first",
+                 seed=0):
+        self.subsample, self.seed = check_subsample(subsample), int(seed)
         self.device = device or _lib.require_gpu()
         self.lib = _lib.load()
         self.cfg = VoxelCfg(float(xSize), float(ySize), float(zSize), int(maxVoxelX), int(maxVoxelY),
@@ -108,10 +127,36 @@ class Voxelizer:
             _lib.bump_alloc_generation()           # recorded step plans hold the old address
         return self._ws
 
-    def __call__(self, points, out=None):
+    def set_draw(self, sample, item, epoch, seed=None):
+        """Writes (seed, item, epoch) into the draw words of `sample` on the current stream: a one-thread kernel with
+        scalar arguments, so nothing waits for the GPU.  seed: this voxeliser's unless given."""
+        if sample.draw is None:
+            raise ValueError("the sample has no draw words: it was not made by a Voxelizer(subsample='random')")
+        seed = self.seed if seed is None else int(seed)
+        _lib.check(self.lib.lisec_voxel_draw_set(_lib.ptr(sample.draw), seed & (2 ** 64 - 1), int(item) & 0xffffffff,
+                                                 int(epoch) & 0xffffffff, _lib.current_stream()))
+
+    def _enqueue(self, pts, n, stride, ws, cap, s):
+        args = (ctypes.byref(self.cfg), _lib.ptr(pts), 0 if pts.dtype == torch.float32 else 1, n, stride,
+                _lib.ptr(ws), ws.numel(), cap, _lib.ptr(s.info), _lib.ptr(s.cell_voxel), _lib.ptr(s.coords),
+                _lib.ptr(s.counts), _lib.ptr(s.npts), _lib.ptr(s.row_start), _lib.ptr(s.rows),
+                _lib.ptr(s.row_point), _lib.ptr(s.row_stats))
+        if self.subsample == "random":
+            if s.draw is None:
+                raise ValueError("out: a sample without draw words (made by a subsample='first' voxeliser)")
+            _lib.check(self.lib.lisec_voxelize_draw(*args, _lib.ptr(s.draw), _lib.current_stream()))
+        else:
+            _lib.check(self.lib.lisec_voxelize(*args, _lib.current_stream()))
+
+    def __call__(self, points, out=None, draw=None):
         """points: (N, >=3) float32/float64 numpy array or torch tensor (host or device).
         out: a VoxelSample of an earlier call with the same number of points whose buffers are written again (a recorded
-        step plan points at fixed addresses)."""
+        step plan points at fixed addresses).
+        draw: (item, epoch) of a subsample='random' voxeliser, written into the sample's draw words in front of the
+        launches.  None leaves the words of `out` alone -- a call made while a step plan is recorded bakes in their
+        address, not their values, and whoever replays the plan sets them (set_draw) -- and gives a new sample (0, 0)."""
+        if draw is not None and self.subsample != "random":
+            raise ValueError("draw: only a Voxelizer(subsample='random') draws")
         if isinstance(points, np.ndarray):
             if points.dtype not in (np.float32, np.float64):
                 points = points.astype(np.float64)
@@ -128,11 +173,9 @@ class Voxelizer:
         if out is not None:
             if out.n_points != n or out.cap != cap:
                 raise ValueError("out: a sample of another size")
-            _lib.check(self.lib.lisec_voxelize(
-                ctypes.byref(self.cfg), _lib.ptr(pts), 0 if pts.dtype == torch.float32 else 1, n, stride,
-                _lib.ptr(ws), ws.numel(), cap, _lib.ptr(out.info), _lib.ptr(out.cell_voxel), _lib.ptr(out.coords),
-                _lib.ptr(out.counts), _lib.ptr(out.npts), _lib.ptr(out.row_start), _lib.ptr(out.rows),
-                _lib.ptr(out.row_point), _lib.ptr(out.row_stats), _lib.current_stream()))
+            if draw is not None:
+                self.set_draw(out, *draw)
+            self._enqueue(pts, n, stride, ws, cap, out)
             out._keepalive, out._host_info = pts, None
             return out
         info = torch.empty(8, dtype=i32, device=dev)
@@ -144,12 +187,11 @@ class Voxelizer:
         rows = torch.empty((max(n, 1), 6), dtype=torch.float32, device=dev)
         row_point = torch.empty(max(n, 1), dtype=i32, device=dev)
         row_stats = torch.empty(_lib.ROW_STATS_WORDS, dtype=torch.int64, device=dev)
-        _lib.check(self.lib.lisec_voxelize(
-            ctypes.byref(self.cfg), _lib.ptr(pts), 0 if pts.dtype == torch.float32 else 1, n, stride,
-            _lib.ptr(ws), ws.numel(), cap, _lib.ptr(info), _lib.ptr(cell_voxel), _lib.ptr(coords),
-            _lib.ptr(counts), _lib.ptr(npts), _lib.ptr(row_start), _lib.ptr(rows), _lib.ptr(row_point),
-            _lib.ptr(row_stats), _lib.current_stream()))
         s = VoxelSample(self.cfg, n, cap, info, cell_voxel, coords, counts, npts, row_start, rows,
                         row_point, row_stats)
+        if self.subsample == "random":
+            s.draw = torch.empty(4, dtype=i32, device=dev)
+            self.set_draw(s, *(draw or (0, 0)))
+        self._enqueue(pts, n, stride, ws, cap, s)
         s._keepalive = pts
         return s

@@ -1,13 +1,15 @@
 """Throughput of the reference-named surface: Model.fit(batch_size=1) on voxelised sweeps (GPU box only).
 
-    python tools/bench_fit.py [--lr constant|cosine] [--cloud u20k|r200k] [--augment [--sample-to N]]
+    python tools/bench_fit.py [--lr constant|cosine] [--cloud u20k|r200k] [--augment [--sample-to N] [--subsample random]]
 
 --lr cosine trains with optimizers.schedules.CosineDecay (the update kernels read lr_t from the device descriptor)
 instead of the reference's constant rate.  --augment adds, beside plain fit on the same sweeps, fit(x=AugmentedSweeps) with
 about 50 boxes per sweep (augmentation, label maps and balancing made on the device at every step), fit on the same Sequence
 with augment=False (the label kernels alone), and the stand-alone device times of the three entries.  --sample-to N adds
 the same stream with ground-truth object sampling from a database of the sweeps' own objects (each sweep filled up towards
-N boxes) and the device times of lisec_augment_sample / lisec_augment_paste."""
+N boxes) and the device times of lisec_augment_sample / lisec_augment_paste.  --subsample random adds the augmented stream
+with the voxeliser's seeded random per-voxel subsample against the same stream with 'first', in alternating windows of one
+process (each window records its own step plan in a warm-up fit): the mean and the spread of the windows per mode."""
 import argparse
 import os
 import sys
@@ -26,6 +28,7 @@ if __name__ == "__main__":
     ap.add_argument("--cloud", choices=("u20k", "r200k"), default="u20k")
     ap.add_argument("--augment", action="store_true")
     ap.add_argument("--sample-to", type=int, default=0)
+    ap.add_argument("--subsample", choices=("first", "random"), default="first")
     args = ap.parse_args()
     n = 4
     cloud = u20k_cloud if args.cloud == "u20k" else r200k_cloud
@@ -72,6 +75,22 @@ if __name__ == "__main__":
             dt = time.perf_counter() - t0
             print(f"Model.fit on AugmentedSweeps, {label}: {steps / dt:.1f} steps/s ({1e3 * dt / steps:.2f} ms/step), "
                   f"loss {hist.history['loss'][-1]:.4f}")
+        if args.subsample == "random":
+            ms = {"first": [], "random": []}
+            label, kw = runs[2] if len(runs) > 2 else runs[0]           # with object sampling when it was asked for
+            for _ in range(4):
+                for mode in ms:
+                    seq = augment.AugmentedSweeps(pts, bxs, seed=1, subsample=mode, **kw)
+                    model.fit(x=seq, batch_size=1, verbose=0, epochs=1, steps_per_epoch=20)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    model.fit(x=seq, batch_size=1, verbose=0, epochs=1, steps_per_epoch=100)
+                    torch.cuda.synchronize()
+                    ms[mode].append(1e3 * (time.perf_counter() - t0) / 100)
+            for mode, a in ms.items():
+                print(f"Model.fit on AugmentedSweeps ({label}), subsample={mode}: {np.mean(a):.3f} ms/step "
+                      f"(windows {min(a):.3f} .. {max(a):.3f}, 4 x 100 steps)")
+            print(f"random / first = {np.mean(ms['random']) / np.mean(ms['first']):.4f}")
         seq = augment.AugmentedSweeps(pts, bxs, seed=1)
         src, bx = seq.points[0], seq.boxes[0]
         out = torch.empty((src.shape[0], 3), dtype=src.dtype, device=src.device)
