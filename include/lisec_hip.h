@@ -699,6 +699,42 @@ int lisec_head_loss_eval(const lisec_loss_cfg* cfg, const float* head, const flo
                          double* acc, void* workspace, size_t workspace_bytes, lisec_stream_t stream);
 size_t lisec_head_loss_workspace_bytes(void);
 
+/* The VoxelNet detection loss (paper section 2.2; csrc/detection_loss.hip): one joint loss of both outputs on the label
+ * code of lisec_rpn_labels / lisec_rpn_targets.  head (M,16): head[:, a] is the class logit z of anchor a (A = 2),
+ * head[:, 2+7a+k] its regression output r.  y_cls (M,2): pos = code > 1.5, neg = 0.5 < code <= 1.5, anything else (0, a
+ * NaN) is ignored.  y_reg (M,14): the targets, with the reference's +1 on positives (target_offset).  N_pos and N_neg are
+ * the counts over the sweep; a count of 0 divides as 1.  With p = sigmoid(z), sp(x) = max(x,0) + log1p(exp(-|x|)):
+ *   L_cls = alpha/N_pos sum_pos (1-p)^gamma sp(-z) + beta/N_neg sum_neg p^gamma sp(z)
+ *   L_reg = 1/N_pos sum_pos sum_k S(r - (y_reg - target_offset)),  S(d) = |d| < b ? d*d/(2b) : |d| - b/2, b = smooth_l1_beta
+ *   total = weight[0]*L_cls + weight[1]*L_reg
+ * gamma = 0 is the paper's loss (the factor is exactly 1), gamma > 0 the focal form.  Every element is evaluated in double
+ * from the fp32 inputs -- finite for every finite logit; a NaN logit gives NaN -- and summed in double over a fixed
+ * partition with one finalize: no atomics, the same bits on every run. */
+typedef struct lisec_detection_loss_cfg {
+    int struct_bytes;           /* sizeof(lisec_detection_loss_cfg), checked */
+    int reserved;               /* 0 */
+    double alpha, beta, gamma;  /* >= 0 */
+    double smooth_l1_beta;      /* > 0 */
+    double target_offset;
+    double weight[2];           /* loss_weights: class, regression */
+} lisec_detection_loss_cfg;
+
+/* dhead (M,16) = grad_scale * d total / d head -- exactly 0.0f on ignored anchors and on every regression channel of an
+ * anchor that is not positive --, loss_out[3] = {total, L_cls, L_reg} (fp32) and counts_out[2] = {N_pos, N_neg} (device).
+ * The counts come from a launch of their own over y_cls, ahead of the gradient they scale.  Fixed addresses, no host
+ * reads: every launch records into a step plan.  LISEC_EINVAL: a NULL pointer, M <= 0, a negative alpha, beta or gamma,
+ * smooth_l1_beta <= 0, a struct_bytes of another size, a workspace below lisec_detection_loss_workspace_bytes(). */
+int lisec_detection_loss(const lisec_detection_loss_cfg* cfg, const float* head, const float* y_cls, const float* y_reg,
+                         long long M, float grad_scale, float* dhead, float* loss_out, long long* counts_out,
+                         void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+/* The evaluation form: the same launches without the gradient store, so a sweep's {total, L_cls, L_reg} are the fp32 bits
+ * lisec_detection_loss writes.  They are ADDED, as doubles, to acc[0..2] and acc[3] counts the sweep (double[4], device,
+ * zeroed by the caller), like lisec_rpn_loss_eval. */
+int lisec_detection_loss_eval(const lisec_detection_loss_cfg* cfg, const float* head, const float* y_cls,
+                              const float* y_reg, long long M, double* acc, void* workspace, size_t workspace_bytes,
+                              lisec_stream_t stream);
+size_t lisec_detection_loss_workspace_bytes(void);
+
 /* optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (:295) on the flat parameter buffer:
  * v <- m*v - lr_t*g;  w <- w + m*v - lr_t*g;  lr_t = lr/(1 + decay*iterations) is computed by the caller. */
 int lisec_sgd_nesterov_step(float* theta, const float* grad, float* velocity, long long n, float lr_t,

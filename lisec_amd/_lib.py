@@ -109,6 +109,11 @@ class LossCfg(Structure):                      # lisec_loss_cfg
                 ("metric", (LossTerm * LOSS_MAX_METRICS) * 2)]
 
 
+class DetectionLossCfg(Structure):             # lisec_detection_loss_cfg
+    _fields_ = [("struct_bytes", c_int), ("reserved", c_int), ("alpha", c_double), ("beta", c_double), ("gamma", c_double),
+                ("smooth_l1_beta", c_double), ("target_offset", c_double), ("weight", c_double * 2)]
+
+
 class ConvGeom(Structure):
     _fields_ = [(n, c_int) for n in ("mode", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "KD", "KH", "KW",
                                      "sd", "sh", "sw", "pd", "ph", "pw", "Cin", "in_stride", "Cout",
@@ -299,6 +304,12 @@ def _declare(lib):
     lib.lisec_head_loss_eval.argtypes = [POINTER(LossCfg), P, P, P, LL, P, P, c_size_t, P]
     lib.lisec_head_loss_workspace_bytes.restype = c_size_t
     lib.lisec_head_loss_workspace_bytes.argtypes = []
+    lib.lisec_detection_loss.restype = c_int
+    lib.lisec_detection_loss.argtypes = [POINTER(DetectionLossCfg), P, P, P, LL, c_float, P, P, P, P, c_size_t, P]
+    lib.lisec_detection_loss_eval.restype = c_int
+    lib.lisec_detection_loss_eval.argtypes = [POINTER(DetectionLossCfg), P, P, P, LL, P, P, c_size_t, P]
+    lib.lisec_detection_loss_workspace_bytes.restype = c_size_t
+    lib.lisec_detection_loss_workspace_bytes.argtypes = []
     lib.lisec_sgd_nesterov_step.restype = c_int
     lib.lisec_sgd_nesterov_step.argtypes = [P, P, P, LL, c_float, c_float, P]
     lib.lisec_sgd_nesterov_step_dev.restype = c_int

@@ -178,7 +178,8 @@ class AugmentedSweeps:
     device float32), on_epoch_end() moves on to the next epoch's draws.  The same (seed, epoch, i) always gives the same
     item.  points_list[i]: (n, >= 3) numpy or device tensor, boxes_list[i]: (B, 7) rows as boxes.annotationBoxes returns
     them; both are uploaded once.  augment=False yields the sweeps as they are, with device-made labels; balance=False
-    skips the region balancing of the label maps.  params: as augment_sweep.  Model.fit(x=AugmentedSweeps(...)) trains on
+    skips the region balancing of the label maps -- the natural setting under losses.VoxelNetLoss, which normalises
+    positives and negatives separately and needs no sampled subset.  params: as augment_sweep.  Model.fit(x=AugmentedSweeps(...)) trains on
     it: the augmentation and the label kernels run where fit() stages a sweep, and write the step's buffers directly.
     database: an ObjectDatabase; every item is then filled up towards sample_to boxes with sampled objects before the
     noise (with augment=False: sampled and pasted only).  Item i then has n_i + database.bound(K_i) rows, pad rows at 1e6

@@ -1,12 +1,17 @@
 """tf.keras 2.4 losses (tf.keras.losses), exposed as lisec_amd.model_training.losses, and what Model.compile makes of its
 loss / loss_weights / metrics arguments: a LossSpec, the descriptor (lisec_loss_cfg, include/lisec_hip.h) of the kernels
 that evaluate it (csrc/losses.hip).
+VoxelNetLoss is the one loss here that Keras does not have: the detection loss of VoxelNet section 2.2, a joint loss of both
+outputs, compiled to a DetectionLossSpec (lisec_detection_loss_cfg, csrc/detection_loss.hip).
 
 Same names, constructor arguments, defaults, get_config / from_config and serialize / deserialize as Keras.  Every loss is
 Keras' mean over the last axis and then over the cells (SUM_OVER_BATCH_SIZE): the mean over all M*C elements of an output.
 A loss of one's own -- a Python callable, or a subclass with its own call() -- cannot run in the kernels and is refused
 (NotImplementedError), as are the Keras losses the kernels do not implement (hinge family, categorical and sparse
 cross-entropy, KL divergence, cosine similarity).  Importable and fully validated without the HIP library."""
+import ctypes
+import math
+
 from . import _lib
 
 EPSILON = 1e-7                                   # K.epsilon()
@@ -120,6 +125,45 @@ class Poisson(Loss):
         super().__init__(reduction, name)
 
 
+class VoxelNetLoss(Loss):
+    """The detection loss of VoxelNet section 2.2 on the label code of preprocessLabels / rpnTargets (y_cls 0 ignore, 1
+    negative, 2 positive; y_reg non-zero on positives only, carrying the reference's +1): classification normalised
+    separately over positives and negatives, SmoothL1 regression over positives only, neutral anchors ignored.  With p =
+    sigmoid(logit):  L_cls = alpha/N_pos sum_pos (1-p)^gamma softplus(-z) + beta/N_neg sum_neg p^gamma softplus(z),
+    L_reg = 1/N_pos sum_pos sum_k SmoothL1_b(r - (y_reg - target_offset)).  gamma=0 is the paper's loss, gamma=2 (with,
+    say, alpha=0.25*2, beta=0.75*2) the focal form of SECOND / PointPillars.  Not a Keras loss: it is ONE loss of BOTH
+    outputs (the class map decides where the regression counts), so compile() takes it only as loss=VoxelNetLoss(...) or
+    loss='voxelnet', never per output; lisec_detection_loss (csrc/detection_loss.hip) evaluates it."""
+
+    def __init__(self, alpha=1.5, beta=1.0, gamma=0.0, smooth_l1_beta=1.0, target_offset=1.0, reduction="auto",
+                 name="voxelnet_loss"):
+        super().__init__(reduction, name)
+        self.alpha, self.beta, self.gamma = alpha, beta, gamma
+        self.smooth_l1_beta, self.target_offset = smooth_l1_beta, target_offset
+        for key in ("alpha", "beta", "gamma"):
+            if not float(getattr(self, key)) >= 0:
+                raise ValueError(f"VoxelNetLoss: {key} must be >= 0, got {getattr(self, key)}")
+        if not float(smooth_l1_beta) > 0:
+            raise ValueError(f"VoxelNetLoss: smooth_l1_beta must be > 0, got {smooth_l1_beta}")
+        if not math.isfinite(float(target_offset)):
+            raise ValueError(f"VoxelNetLoss: target_offset must be finite, got {target_offset}")
+
+    def term(self):
+        raise ValueError("VoxelNetLoss is a joint loss of both outputs (the class labels decide which cells the regression "
+                         "counts), not a per-output loss: pass it as compile(loss=VoxelNetLoss(...)) or loss='voxelnet', "
+                         "not inside a list or dict")
+
+    def params(self):
+        return tuple(float(getattr(self, k)) for k in DETECTION_PARAMS)
+
+    def get_config(self):
+        return dict(super().get_config(), **{k: getattr(self, k) for k in DETECTION_PARAMS})
+
+
+DETECTION_PARAMS = ("alpha", "beta", "gamma", "smooth_l1_beta", "target_offset")
+JOINT_FUNCTIONS = {"voxelnet": VoxelNetLoss, "voxelnet_loss": VoxelNetLoss}      # names of the joint losses
+
+
 class _NotImplementedLoss(Loss):
     """A Keras loss the kernels do not implement: it can be built and serialized, compile() refuses it."""
 
@@ -205,7 +249,7 @@ def serialize(loss):
 def deserialize(config, custom_objects=None):
     if isinstance(config, str):
         return config
-    classes = dict(_BUILTIN, **_NOT_IMPLEMENTED, **(custom_objects or {}))
+    classes = dict(_BUILTIN, VoxelNetLoss=VoxelNetLoss, **_NOT_IMPLEMENTED, **(custom_objects or {}))
     name = config.get("class_name") if isinstance(config, dict) else None
     if name not in classes:
         raise ValueError(f"Unknown loss function: {name}")
@@ -221,6 +265,8 @@ def loss_term(identifier):
         key = identifier.lower()
         if key in FUNCTIONS:
             return FUNCTIONS[key]
+        if key in JOINT_FUNCTIONS:
+            return JOINT_FUNCTIONS[key]().term()        # refuses: a joint loss is no per-output loss
         if key in NOT_IMPLEMENTED_FUNCTIONS or identifier in _NOT_IMPLEMENTED:
             raise NotImplementedError(f"loss {identifier!r} is not implemented: the kernels evaluate "
                                       f"{', '.join(sorted(set(FUNCTIONS)))}")
@@ -282,6 +328,42 @@ class LossSpec:
         return f"LossSpec{self.config}"
 
 
+class DetectionLossSpec:
+    """The VoxelNet detection loss of a training step as lisec_detection_loss sees it: the five parameters of a
+    VoxelNetLoss and the loss_weights; hashable, so that it keys recorded step plans, like a LossSpec.  It has no
+    metrics."""
+
+    n_metrics = 0
+
+    def __init__(self, params, weights=(1.0, 1.0)):
+        self.params = tuple(float(v) for v in params)
+        self.weights = tuple(float(w) for w in weights)
+        if len(self.params) != len(DETECTION_PARAMS) or len(self.weights) != 2:
+            raise ValueError("a DetectionLossSpec has five parameters and two weights")
+
+    @property
+    def config(self):
+        return (self.params, self.weights)
+
+    def descriptor(self):
+        """The lisec_detection_loss_cfg (an _lib.DetectionLossCfg)."""
+        d = _lib.DetectionLossCfg()
+        d.struct_bytes = ctypes.sizeof(_lib.DetectionLossCfg)
+        for k, v in zip(DETECTION_PARAMS, self.params):
+            setattr(d, k, v)
+        d.weight[0], d.weight[1] = self.weights
+        return d
+
+    def __eq__(self, other):
+        return isinstance(other, DetectionLossSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(("detection",) + self.config)
+
+    def __repr__(self):
+        return f"DetectionLossSpec{self.config}"
+
+
 LEGACY = {"mse": ((MSE, 0, 0.0, 0.0), (MSE, 0, 0.0, 0.0)),
           "smoothl1_ce": ((SIGMOID_CE_CLAMPED, 0, 0.0, 0.0), (SMOOTH_L1, 0, 0.0, 0.0))}
 
@@ -321,15 +403,33 @@ def _legacy_key(loss):
     return None
 
 
+def _joint_loss(loss):
+    """The VoxelNetLoss when compile()'s loss argument as a whole is one (an object, its name or its serialized dict),
+    else None."""
+    if isinstance(loss, dict) and "class_name" in loss:
+        loss = deserialize(loss)
+    if isinstance(loss, str) and loss.lower() in JOINT_FUNCTIONS:
+        return JOINT_FUNCTIONS[loss.lower()]()
+    return loss if isinstance(loss, VoxelNetLoss) else None
+
+
 def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     """Model.compile's loss arguments -> (step loss, metric names).  The step loss is the plain string 'mse' or
     'smoothl1_ce' -- lisec_rpn_loss, the reference's step unchanged -- when the loss is MSE on both outputs, or the legacy
-    'smoothl1_ce' spelling, with neither loss_weights nor metrics; otherwise a LossSpec (lisec_head_loss).  Every refusal
-    is raised here: ValueError (unknown name, unknown output key, a list of the wrong length), NotImplementedError (a Keras
-    loss or metric the kernels do not implement, one's own callable, loss=None for an output, weighted_metrics)."""
+    'smoothl1_ce' spelling, with neither loss_weights nor metrics; a DetectionLossSpec (lisec_detection_loss) for a
+    VoxelNetLoss or 'voxelnet'; otherwise a LossSpec (lisec_head_loss).  Every refusal is raised here: ValueError (unknown
+    name, unknown output key, a list of the wrong length, a VoxelNetLoss given per output), NotImplementedError (a Keras
+    loss or metric the kernels do not implement, one's own callable, loss=None for an output, weighted_metrics, metrics
+    with a VoxelNetLoss)."""
     from . import metrics as metrics_mod
     if weighted_metrics is not None:
         raise NotImplementedError("weighted_metrics is not implemented (there are no sample weights)")
+    joint = _joint_loss(loss)
+    if joint is not None:
+        if metrics:
+            raise NotImplementedError("metrics= with the VoxelNet detection loss is not implemented: the Keras metrics "
+                                      "average over every cell of a label map that codes ignore / negative / positive")
+        return DetectionLossSpec(joint.params(), _weights(loss_weights)), []
     legacy = _legacy_key(loss)
     if legacy is not None:
         terms = LEGACY[legacy]

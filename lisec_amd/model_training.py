@@ -487,7 +487,9 @@ class Model:
         iteration count, as re-compiling does in the reference (:339-340).
         loss: a tf.keras 2.4 loss (a name or a losses.* object; see lisec_amd/losses.py) for both outputs, a list of two in
         output order or a dict keyed by 'ClassificationLayer' / 'RegressionLayer'; also the project's 'smoothl1_ce' (=
-        ['cross_entropy', 'smooth_l1']: sigmoid cross-entropy on labels clamped to [0, 1] + SmoothL1).  loss_weights: a list
+        ['cross_entropy', 'smooth_l1']: sigmoid cross-entropy on labels clamped to [0, 1] + SmoothL1), or -- as the whole
+        argument only -- losses.VoxelNetLoss(...) / 'voxelnet', the detection loss the 0/1/2 label code was made for (one
+        loss of both outputs; loss_weights apply, metrics are refused).  loss_weights: a list
         or dict of floats (default 1): the step minimises w_c*L_c + w_r*L_r, History's `loss`; the per-output losses are
         logged unweighted.  metrics: a list (for each output), a list of two lists or a dict per output name; logged as
         "<output>_<name>" (see metrics_names).  weighted_metrics: not implemented (there are no sample weights).
@@ -1048,7 +1050,8 @@ def train_with_model(samples, level5Data, model_path, save_path):
     return _train(samples, level5Data, save_path, model_path)
 
 
-def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0, subsample='first'):
+def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0, subsample='first', balance=True,
+                    loss=None):
     """OURS, not the reference's: train() on sweeps that are augmented anew at every step (augment.AugmentedSweeps: per-box
     noise with collision rejection, one global scale and rotation, VoxelNet section 3.3) with the label maps of the moved
     boxes made on the device (boxes.rpnTargets) instead of the precomputed labels3/*.npy.  The sweeps come from
@@ -1056,16 +1059,19 @@ def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=
     SGD.  sample_to > 0: ground-truth object sampling (augment.ObjectDatabase, built from the same sweeps and boxes) fills
     every sweep up towards that many boxes before the noise.  subsample='random': a voxel holding more than maxPoints
     points keeps the reference's random subsample, drawn anew per (seed, item, epoch), instead of the lowest point indices
-    (AugmentedSweeps).  Returns the model, saved at save_path."""
+    (AugmentedSweeps).  loss: compile()'s (None: the reference's ['mse','mse']); with loss='voxelnet' (losses.VoxelNetLoss, which normalises positives and
+    negatives separately) balance=False is the natural setting: the label maps then keep every negative instead of a
+    sample of them.  Returns the model, saved at save_path."""
     from . import augment, boxes
     _refuse_mixed_training(mixed_precision.global_policy())
     points = [combine_lidar_data_gpu(s, Constants.lyft_data_dir, level5Data) for s in samples]
     rows = [boxes.annotationBoxes(s, level5Data) for s in samples]
     model = createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints)
     sgd = optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True)
-    model.compile(optimizer=sgd, loss=['mse', 'mse'])
+    model.compile(optimizer=sgd, loss=['mse', 'mse'] if loss is None else loss)
     database = augment.ObjectDatabase(points, rows) if sample_to > 0 else None
-    seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to, subsample=subsample)
+    seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to, subsample=subsample,
+                                  balance=balance)
     history = model.fit(x=seq, batch_size=1, verbose=1, epochs=epochs)
     if model.dp is None or model.dp.rank == 0:
         print(history.history)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, lr_schedules, ops, optimizer_table
-from .losses import LossSpec
+from .losses import DetectionLossSpec, LossSpec
 from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
@@ -34,6 +34,8 @@ def loss_acc_len(loss):
     for a string that names no legacy loss."""
     if isinstance(loss, LossSpec):
         return 4 + loss.n_metrics
+    if isinstance(loss, DetectionLossSpec):
+        return 4
     LEGACY_LOSS_KINDS[loss]                 # refuses an unknown name
     return 4
 
@@ -644,7 +646,7 @@ class LisecNet:
         self.side_queue = _SideQueue(self, None, self.side)     # each pass names its main stream (begin)
 
         self._tail_ok = {}
-        self._loss_descs = {}                            # LossSpec -> its lisec_loss_cfg (_loss_descriptor)
+        self._loss_descs = {}                            # LossSpec / DetectionLossSpec -> its descriptor (_loss_descriptor)
         self._early = None                               # (lo, OptimizerSpec) of the pending early_update()
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
         self._fwd_events = {}
@@ -671,6 +673,8 @@ class LisecNet:
         self.loss_out = torch.zeros(3, dtype=f32, device=dev)
         # the metrics of a LossSpec loss (lisec_head_loss), class output's first; fixed address, like loss_out
         self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
+        # [N_pos, N_neg] of a DetectionLossSpec loss (lisec_detection_loss); fixed address, like loss_out
+        self.loss_counts = torch.zeros(2, dtype=torch.int64, device=dev)
 
     @property
     def iterations(self):
@@ -1123,7 +1127,8 @@ class LisecNet:
         """y_cls (Ho,Wo,2), y_reg (Ho,Wo,14): float32 device tensors.  Fills self.grad (layout of theta)
         and self.loss_out = [total, class, regression].  Must follow forward(training=True).
         loss: 'mse' (loss=['mse','mse'], the reference's) or 'smoothl1_ce' -- lisec_rpn_loss -- or a LossSpec (Keras losses,
-        loss_weights and metrics: lisec_head_loss, which also fills self.metric_out[:loss.n_metrics]).
+        loss_weights and metrics: lisec_head_loss, which also fills self.metric_out[:loss.n_metrics]) or a
+        DetectionLossSpec (the VoxelNet detection loss: lisec_detection_loss, which also fills self.loss_counts).
         side_filler: optional callable issued on the second stream behind the head-phase leaves, where that stream has
         nothing to do for ~200 us (the weight gradients of the last RPN block wait for its chain): independent work such as
         the NEXT sweep's voxelisation (PipelinedStep).
@@ -1137,19 +1142,23 @@ class LisecNet:
             _lib.pin_stream(prev_pin)
 
     def _loss_descriptor(self, spec):
-        """The lisec_loss_cfg of a LossSpec, built once per spec."""
+        """The lisec_loss_cfg of a LossSpec / lisec_detection_loss_cfg of a DetectionLossSpec, built once per spec."""
         if spec not in self._loss_descs:
             self._loss_descs[spec] = spec.descriptor()
         return self._loss_descs[spec]
 
     def _loss_backward(self, loss, y_cls, y_reg, grad_scale):
         """The loss of the head map against the targets into loss_out (a LossSpec: and its metrics into metric_out), its
-        gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*) or a LossSpec (lisec_head_loss*):
-        this, loss_eval() and loss_acc_len() are the only code that tells them apart."""
+        gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*), a LossSpec (lisec_head_loss*) or a
+        DetectionLossSpec (lisec_detection_loss*, its counts into loss_counts): this, loss_eval() and loss_acc_len() are the
+        only code that tells them apart."""
         head, dhead, M = self.act["head"], self.dact["head"], self.Ho * self.Wo
         if isinstance(loss, LossSpec):
             ops.head_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.metric_out,
                           grad_scale=grad_scale)
+        elif isinstance(loss, DetectionLossSpec):
+            ops.detection_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.loss_counts,
+                               grad_scale=grad_scale)
         else:
             ops.rpn_loss(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], dhead, self.loss_out, grad_scale=grad_scale)
 
@@ -1159,6 +1168,8 @@ class LisecNet:
         head, M = self.act["head"], self.Ho * self.Wo
         if isinstance(loss, LossSpec):
             ops.head_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
+        elif isinstance(loss, DetectionLossSpec):
+            ops.detection_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
         else:
             ops.rpn_loss_eval(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], acc)
 
@@ -1614,7 +1625,7 @@ class PipelinedStep(_TrainingPlans):
 
 class EvalStep(_StepPlans):
     """One evaluation sweep -- voxelise a fixed-capacity padded sweep (as RecordedStep), forward(training=False), add the
-    sweep's loss to a device accumulator (lisec_rpn_loss_eval; lisec_head_loss_eval for a LossSpec) -- recorded ONCE as a
+    sweep's loss to a device accumulator (lisec_rpn_loss_eval; lisec_head_loss_eval for a LossSpec, lisec_detection_loss_eval for a DetectionLossSpec) -- recorded ONCE as a
     step plan and re-issued by one C call per sweep (Model.evaluate and the validation of Model.fit with
     LISEC_TUNING=eval_plan=1; by default they run the eager forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps] -- with a LossSpec
     [total, class, regression, metrics..., sweeps] -- (float64, device) is read by the host once per evaluation.  Invariants:

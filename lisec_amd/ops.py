@@ -443,6 +443,29 @@ def head_loss_eval(cfg, head, y_cls, y_reg, M, acc):
                                                 _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
 
 
+def _detection_workspace(device):
+    ws = _ew_workspace(device)
+    assert ws.numel() >= _lib.load().lisec_detection_loss_workspace_bytes()
+    return ws
+
+
+def detection_loss(cfg, head, y_cls, y_reg, M, dhead, loss_out, counts_out, grad_scale=1.0):
+    """The VoxelNet detection loss of cfg (an _lib.DetectionLossCfg, lisec_detection_loss_cfg): dhead, loss_out = [total,
+    class, regression] and counts_out = [N_pos, N_neg] (int64 device tensor)."""
+    ws = _detection_workspace(head.device)
+    _lib.check(_lib.load().lisec_detection_loss(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                                                grad_scale, _lib.ptr(dhead), _lib.ptr(loss_out), _lib.ptr(counts_out),
+                                                _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
+def detection_loss_eval(cfg, head, y_cls, y_reg, M, acc):
+    """Adds the [total, class, regression] detection_loss would write (the same fp32 bits) to acc[0:3] and counts the
+    sweep in acc[3] (float64[4] device tensor); no gradient."""
+    ws = _detection_workspace(head.device)
+    _lib.check(_lib.load().lisec_detection_loss_eval(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg),
+                                                     M, _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
 def sgd_nesterov_step(theta, grad, velocity, lr_t, momentum):
     _lib.check(_lib.load().lisec_sgd_nesterov_step(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity),
                                                    theta.numel(), lr_t, momentum, _lib.current_stream()))

@@ -1,15 +1,21 @@
 """The loss kernels on the Lyft head (M = 100*200 cells): the legacy pair (k_loss + k_loss_finalize, lisec_rpn_loss) against
-lisec_head_loss (k_head_loss + k_head_loss_finalize, csrc/losses.hip) for the configurations of Model.compile below, each
+lisec_head_loss (k_head_loss + k_head_loss_finalize, csrc/losses.hip) and lisec_detection_loss (k_det_count + k_det_loss +
+k_det_finalize, csrc/detection_loss.hip) for the configurations of Model.compile below, each
 timed over back-to-back launches with device events; then a short Model.fit on U20k sweeps under each, timed per step
 (GPU box only).  Run it under `rocprofv3 --kernel-trace --stats` for the kernel times: --config restricts the run to
 one configuration, so that the per-kernel statistics of a profile hold that configuration alone.
 
-    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics] [--iters 500] [--fit-steps 20]
+    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics|voxelnet|voxelnet_focal] [--iters 500]
+                                  [--fit-steps 20] [--repeats 1]
 
   mse             loss=['mse','mse']                          lisec_rpn_loss kind 0 (the reference's step)
   smoothl1_ce     loss='smoothl1_ce'                          lisec_rpn_loss kind 1
   keras           [BinaryCrossentropy(from_logits=True), Huber()]            lisec_head_loss, no metrics
-  keras_metrics   the same with metrics [[BinaryAccuracy(threshold=0), 'accuracy'], ['mae', 'mse']]"""
+  keras_metrics   the same with metrics [[BinaryAccuracy(threshold=0), 'accuracy'], ['mae', 'mse']]
+  voxelnet        loss='voxelnet' (VoxelNetLoss(): gamma 0)           lisec_detection_loss
+  voxelnet_focal  VoxelNetLoss(alpha=0.5, beta=1.5, gamma=2.0)        lisec_detection_loss, the pow() path
+
+--repeats N times the fit N times per configuration and prints each: the run-to-run spread."""
 import argparse
 import os
 import sys
@@ -32,6 +38,8 @@ def _configs():
         "keras": dict(loss=[K.BinaryCrossentropy(from_logits=True), K.Huber()]),
         "keras_metrics": dict(loss=[K.BinaryCrossentropy(from_logits=True), K.Huber()],
                               metrics=[[Mx.BinaryAccuracy(threshold=0.0), "accuracy"], ["mae", "mse"]]),
+        "voxelnet": dict(loss="voxelnet"),
+        "voxelnet_focal": dict(loss=K.VoxelNetLoss(alpha=0.5, beta=1.5, gamma=2.0)),
     }
 
 
@@ -44,6 +52,10 @@ def _kernel_time(step_loss, head, yc, yr, M, iters):
     if isinstance(step_loss, K.LossSpec):
         desc = step_loss.descriptor()
         call = lambda: ops.head_loss(desc, head, yc, yr, M, dhead, loss_out, met)          # noqa: E731
+    elif isinstance(step_loss, getattr(K, "DetectionLossSpec", ())):
+        desc = step_loss.descriptor()
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        call = lambda: ops.detection_loss(desc, head, yc, yr, M, dhead, loss_out, counts)  # noqa: E731
     else:
         kind = {"mse": 0, "smoothl1_ce": 1}[step_loss]
         call = lambda: ops.rpn_loss(head, yc, yr, M, kind, dhead, loss_out)                 # noqa: E731
@@ -65,6 +77,7 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=500)
     ap.add_argument("--fit-steps", type=int, default=20)
     ap.add_argument("--sweeps", type=int, default=8)
+    ap.add_argument("--repeats", type=int, default=1)
     args = ap.parse_args()
     configs = _configs() if args.config == "all" else {args.config: _configs()[args.config]}
     dev = torch.device("cuda")
@@ -86,9 +99,10 @@ if __name__ == "__main__":
         us, lo = _kernel_time(step_loss, head, yc, yr, M, args.iters)
         model.compile(optimizer=mt.optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True), **kw)
         model.fit(x=x, y=y, verbose=0, epochs=1, steps_per_epoch=4)                       # records the step plan
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        model.fit(x=x, y=y, verbose=0, epochs=1, steps_per_epoch=args.fit_steps)
-        torch.cuda.synchronize()
-        ms = 1e3 * (time.perf_counter() - t0) / args.fit_steps
-        print(f"{name:<15}{us:>22.2f}{ms:>14.3f}  {np.array2string(lo, precision=5)}", flush=True)
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model.fit(x=x, y=y, verbose=0, epochs=1, steps_per_epoch=args.fit_steps)
+            torch.cuda.synchronize()
+            ms = 1e3 * (time.perf_counter() - t0) / args.fit_steps
+            print(f"{name:<15}{us:>22.2f}{ms:>14.3f}  {np.array2string(lo, precision=5)}", flush=True)
