@@ -735,6 +735,54 @@ int lisec_detection_loss_eval(const lisec_detection_loss_cfg* cfg, const float* 
                               lisec_stream_t stream);
 size_t lisec_detection_loss_workspace_bytes(void);
 
+/* Metrics that read the label code of the detection loss (csrc/detection_metrics.hip; ours, not Keras').  Inputs and the
+ * meaning of pos / neg / ignored as for lisec_detection_loss.  Every metric is a pair {num, den} of sums over the 2M
+ * anchors of a sweep; its value is num/den over whatever sweeps the caller pools (0 when den == 0).  With p = sigmoid(z) in
+ * double, "predicted" = p > threshold (a NaN logit compares false), t = y_reg - target_offset:
+ *   ANCHOR_PRECISION  num #(pos and predicted)                             den #((pos or neg) and predicted)
+ *   ANCHOR_RECALL     num #(pos and predicted)                             den N_pos
+ *   ANCHOR_ACCURACY   num #(pos and predicted) + #(neg and not predicted)  den N_pos + N_neg
+ *   POSITIVE_MAE      num sum_pos sum_k |r_k - t_k|                        den 7 N_pos
+ *   POSITIVE_IOU      num sum_pos IoU(decode(r), decode(t))                den N_pos
+ * decode is lisec_rpn_decode's arithmetic for the anchor of the channel block, without the anchor centre that both boxes
+ * share: centre (r0 l_a, r1 w_a, r2 h_a), extents exp(r3..5) (l_a, w_a, h_a), yaw r6 + yaw_a; IoU is LISEC_IOU_3D /
+ * LISEC_IOU_BEV of lisec_boxes_match (below).  A positive whose decoded offsets or extents are not all finite (exp
+ * overflows beyond r = 709), or whose IoU is not finite (a yaw that is not finite), contributes IoU 0 and still counts in
+ * den.
+ * Every anchor is evaluated in double from the fp32 inputs by one thread; per-workgroup fp64 partials in a fixed
+ * partition and one finalize in index order: no atomics, the same bits on every run.  Counts are exact integers held in
+ * doubles (pooled counts pass 2^24 within a few hundred sweeps). */
+#define LISEC_DET_MAX_METRICS 8
+enum {
+    LISEC_DET_METRIC_ANCHOR_PRECISION = 0,
+    LISEC_DET_METRIC_ANCHOR_RECALL = 1,
+    LISEC_DET_METRIC_ANCHOR_ACCURACY = 2,
+    LISEC_DET_METRIC_POSITIVE_MAE = 3,
+    LISEC_DET_METRIC_POSITIVE_IOU = 4
+};
+typedef struct lisec_detection_metric {
+    int kind;                   /* LISEC_DET_METRIC_* */
+    int mode;                   /* POSITIVE_IOU: LISEC_IOU_3D / LISEC_IOU_BEV; 0 otherwise */
+    double threshold;           /* the three ANCHOR_* kinds: in the open interval (0, 1) */
+} lisec_detection_metric;
+typedef struct lisec_detection_metrics_cfg {
+    int struct_bytes;           /* sizeof(lisec_detection_metrics_cfg), checked */
+    int n_metrics;              /* 1 .. LISEC_DET_MAX_METRICS */
+    double target_offset;       /* the VoxelNetLoss's */
+    double anchors[2][4];       /* l, w, h, yaw: lisec_rpn_cfg's */
+    lisec_detection_metric metric[LISEC_DET_MAX_METRICS];
+} lisec_detection_metrics_cfg;
+
+/* out[2*n_metrics] = {num0, den0, num1, den1, ...} (device doubles).  accumulate == 0 stores them (the training step: out
+ * is a fixed address), accumulate != 0 adds them (evaluation: out is part of the fp64 accumulator).  Fixed addresses, no
+ * host reads, no allocation: the two launches record into a step plan.  LISEC_EINVAL, with nothing enqueued: a NULL
+ * pointer, M <= 0, a struct_bytes of another size, n_metrics outside 1..LISEC_DET_MAX_METRICS, an unknown kind or mode, a
+ * threshold outside (0, 1), a workspace below lisec_detection_metrics_workspace_bytes(). */
+int lisec_detection_metrics(const lisec_detection_metrics_cfg* cfg, const float* head, const float* y_cls,
+                            const float* y_reg, long long M, double* out, int accumulate, void* workspace,
+                            size_t workspace_bytes, lisec_stream_t stream);
+size_t lisec_detection_metrics_workspace_bytes(void);
+
 /* optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True) (:295) on the flat parameter buffer:
  * v <- m*v - lr_t*g;  w <- w + m*v - lr_t*g;  lr_t = lr/(1 + decay*iterations) is computed by the caller. */
 int lisec_sgd_nesterov_step(float* theta, const float* grad, float* velocity, long long n, float lr_t,

@@ -114,6 +114,18 @@ class DetectionLossCfg(Structure):             # lisec_detection_loss_cfg
                 ("smooth_l1_beta", c_double), ("target_offset", c_double), ("weight", c_double * 2)]
 
 
+DET_MAX_METRICS = 8                            # LISEC_DET_MAX_METRICS
+
+
+class DetectionMetric(Structure):              # lisec_detection_metric
+    _fields_ = [("kind", c_int), ("mode", c_int), ("threshold", c_double)]
+
+
+class DetectionMetricsCfg(Structure):          # lisec_detection_metrics_cfg
+    _fields_ = [("struct_bytes", c_int), ("n_metrics", c_int), ("target_offset", c_double),
+                ("anchors", (c_double * 4) * 2), ("metric", DetectionMetric * DET_MAX_METRICS)]
+
+
 class ConvGeom(Structure):
     _fields_ = [(n, c_int) for n in ("mode", "Di", "Hi", "Wi", "Do", "Ho", "Wo", "KD", "KH", "KW",
                                      "sd", "sh", "sw", "pd", "ph", "pw", "Cin", "in_stride", "Cout",
@@ -310,6 +322,10 @@ def _declare(lib):
     lib.lisec_detection_loss_eval.argtypes = [POINTER(DetectionLossCfg), P, P, P, LL, P, P, c_size_t, P]
     lib.lisec_detection_loss_workspace_bytes.restype = c_size_t
     lib.lisec_detection_loss_workspace_bytes.argtypes = []
+    lib.lisec_detection_metrics.restype = c_int
+    lib.lisec_detection_metrics.argtypes = [POINTER(DetectionMetricsCfg), P, P, P, LL, P, c_int, P, c_size_t, P]
+    lib.lisec_detection_metrics_workspace_bytes.restype = c_size_t
+    lib.lisec_detection_metrics_workspace_bytes.argtypes = []
     lib.lisec_sgd_nesterov_step.restype = c_int
     lib.lisec_sgd_nesterov_step.argtypes = [P, P, P, LL, c_float, c_float, P]
     lib.lisec_sgd_nesterov_step_dev.restype = c_int

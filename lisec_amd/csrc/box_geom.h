@@ -1,5 +1,5 @@
-// The rectangle footprint shared by the box kernels (boxes.hip, union_overlap.hip, detection_ap.hip): boxToShapely's vertices,
-// the shoelace sum and the clipped area of two footprints.
+// The rectangle footprint shared by the box kernels (boxes.hip, union_overlap.hip, detection_ap.hip,
+// detection_metrics.hip): boxToShapely's vertices, the shoelace sum, the clipped area of two footprints and their IoU.
 #pragma once
 #include "common.h"
 
@@ -56,6 +56,31 @@ __device__ inline double quad_intersection_area(const Pt* pa, const Pt* qa) {
     }
     if (n < 3) return 0.0;
     return fabs(signed_area(out, n));
+}
+
+// IoU of two boxes (x, y, z, l, w, h, yaw) under LISEC_IOU_3D / LISEC_IOU_BEV (include/lisec_hip.h, lisec_boxes_match): the
+// clipped footprints, times the clamped height overlap in 3D; 0 for a zero extent.  Shared by detection_ap.hip and
+// detection_metrics.hip.
+__device__ inline double pair_iou(const double* p, const double* g, int mode) {
+    if (p[3] == 0.0 || p[4] == 0.0 || g[3] == 0.0 || g[4] == 0.0) return 0.0;
+    if (mode == LISEC_IOU_3D && (p[5] == 0.0 || g[5] == 0.0)) return 0.0;
+    // footprints further apart than the sum of their circumradii do not meet: area 0, IoU exactly 0
+    const double dx = p[0] - g[0], dy = p[1] - g[1];
+    const double r = 0.5 * (hypot(p[3], p[4]) + hypot(g[3], g[4]));
+    if (dx * dx + dy * dy > r * r * 1.0000001) return 0.0;
+    Pt cp[4], cg[4];
+    box_corners(p, cp);
+    box_corners(g, cg);
+    double inter = quad_intersection_area(cp, cg);             // flips a mirrored (negative extent) footprint itself
+    double sp = fabs(p[3] * p[4]), sg = fabs(g[3] * g[4]);
+    if (mode == LISEC_IOU_3D) {
+        const double hp = 0.5 * fabs(p[5]), hg = 0.5 * fabs(g[5]);
+        inter *= fmax(0.0, fmin(p[2] + hp, g[2] + hg) - fmax(p[2] - hp, g[2] - hg));
+        sp = fabs(p[3] * p[4] * p[5]);
+        sg = fabs(g[3] * g[4] * g[5]);
+    }
+    const double uni = sp + sg - inter;
+    return uni > 0.0 ? inter / uni : 0.0;
 }
 
 }  // namespace lisec

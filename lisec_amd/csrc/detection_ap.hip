@@ -9,7 +9,8 @@
 //   3d   inter = area(fp_p n fp_g) * max(0, min(z_p + |h_p|/2, z_g + |h_g|/2) - max(z_p - |h_p|/2, z_g - |h_g|/2))
 //        union = |l w h|_p + |l w h|_g - inter,  iou = inter / union, 0 when union <= 0
 //   bev  the same with areas only.
-// The footprint is box_corners' quadrilateral, the clipping quad_intersection_area (box_geom.h), a pair per thread.
+// The footprint is box_corners' quadrilateral, the clipping quad_intersection_area, the IoU pair_iou (all box_geom.h), a pair
+// per thread.
 //
 // The take-or-miss walk without a serial part.  In rank order a prediction is a true positive at t when its candidate's IoU
 // exceeds t and the candidate is still free at t.  A label is taken at t by the FIRST prediction in rank order that has it as
@@ -51,28 +52,6 @@ struct MatchWs {
         bytes = c.off;
     }
 };
-
-__device__ double pair_iou(const double* p, const double* g, int mode) {
-    if (p[3] == 0.0 || p[4] == 0.0 || g[3] == 0.0 || g[4] == 0.0) return 0.0;
-    if (mode == LISEC_IOU_3D && (p[5] == 0.0 || g[5] == 0.0)) return 0.0;
-    // footprints further apart than the sum of their circumradii do not meet: area 0, IoU exactly 0
-    const double dx = p[0] - g[0], dy = p[1] - g[1];
-    const double r = 0.5 * (hypot(p[3], p[4]) + hypot(g[3], g[4]));
-    if (dx * dx + dy * dy > r * r * 1.0000001) return 0.0;
-    Pt cp[4], cg[4];
-    box_corners(p, cp);
-    box_corners(g, cg);
-    double inter = quad_intersection_area(cp, cg);             // flips a mirrored (negative extent) footprint itself
-    double sp = fabs(p[3] * p[4]), sg = fabs(g[3] * g[4]);
-    if (mode == LISEC_IOU_3D) {
-        const double hp = 0.5 * fabs(p[5]), hg = 0.5 * fabs(g[5]);
-        inter *= fmax(0.0, fmin(p[2] + hp, g[2] + hg) - fmax(p[2] - hp, g[2] - hg));
-        sp = fabs(p[3] * p[4] * p[5]);
-        sg = fabs(g[3] * g[4] * g[5]);
-    }
-    const double uni = sp + sg - inter;
-    return uni > 0.0 ? inter / uni : 0.0;
-}
 
 // the last s in [0, n) with start[s] <= q (start ascending, start[0] <= q): the sample that owns row / pair q
 template <typename T>

@@ -330,20 +330,39 @@ class LossSpec:
 
 class DetectionLossSpec:
     """The VoxelNet detection loss of a training step as lisec_detection_loss sees it: the five parameters of a
-    VoxelNetLoss and the loss_weights; hashable, so that it keys recorded step plans, like a LossSpec.  It has no
-    metrics."""
+    VoxelNetLoss and the loss_weights; hashable, so that it keys recorded step plans, like a LossSpec.  Its metrics are
+    the detection metrics (lisec_amd/metrics.py; lisec_detection_metrics): (kind, mode, threshold) terms in the order of
+    metric_names, and the anchors (l, w, h, yaw) PositiveIoU decodes against (Constants.anchors unless given).  The
+    terms and anchors are part of the key -- the recorded plan contains their launch --, metric_names are not.  Without
+    metrics the key is the one of a spec built from parameters and weights alone."""
 
-    n_metrics = 0
-
-    def __init__(self, params, weights=(1.0, 1.0)):
+    def __init__(self, params, weights=(1.0, 1.0), metrics=(), metric_names=(), anchors=None):
         self.params = tuple(float(v) for v in params)
         self.weights = tuple(float(w) for w in weights)
+        self.metrics = tuple((int(k), int(m), float(t)) for k, m, t in metrics)
+        self.metric_names = tuple(metric_names)
         if len(self.params) != len(DETECTION_PARAMS) or len(self.weights) != 2:
             raise ValueError("a DetectionLossSpec has five parameters and two weights")
+        if len(self.metrics) > _lib.DET_MAX_METRICS:
+            raise ValueError(f"at most {_lib.DET_MAX_METRICS} detection metrics are implemented")
+        self.anchors = ()
+        if self.metrics:
+            if anchors is None:
+                from . import Constants
+                anchors = Constants.anchors
+            self.anchors = tuple(tuple(float(v) for v in a) for a in anchors)
+            if len(self.anchors) != 2 or any(len(a) != 4 for a in self.anchors):
+                raise ValueError("a DetectionLossSpec with metrics has two anchors (l, w, h, yaw)")
 
     @property
     def config(self):
-        return (self.params, self.weights)
+        if not self.metrics:
+            return (self.params, self.weights)
+        return (self.params, self.weights, self.metrics, self.anchors)
+
+    @property
+    def n_metrics(self):
+        return len(self.metrics)
 
     def descriptor(self):
         """The lisec_detection_loss_cfg (an _lib.DetectionLossCfg)."""
@@ -352,6 +371,21 @@ class DetectionLossSpec:
         for k, v in zip(DETECTION_PARAMS, self.params):
             setattr(d, k, v)
         d.weight[0], d.weight[1] = self.weights
+        return d
+
+    def metrics_descriptor(self):
+        """The lisec_detection_metrics_cfg (an _lib.DetectionMetricsCfg) of the metrics; None without any."""
+        if not self.metrics:
+            return None
+        d = _lib.DetectionMetricsCfg()
+        d.struct_bytes = ctypes.sizeof(_lib.DetectionMetricsCfg)
+        d.n_metrics = len(self.metrics)
+        d.target_offset = self.params[DETECTION_PARAMS.index("target_offset")]
+        for a in range(2):
+            for k in range(4):
+                d.anchors[a][k] = self.anchors[a][k]
+        for i, (kind, mode, threshold) in enumerate(self.metrics):
+            d.metric[i].kind, d.metric[i].mode, d.metric[i].threshold = kind, mode, threshold
         return d
 
     def __eq__(self, other):
@@ -417,19 +451,20 @@ def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     """Model.compile's loss arguments -> (step loss, metric names).  The step loss is the plain string 'mse' or
     'smoothl1_ce' -- lisec_rpn_loss, the reference's step unchanged -- when the loss is MSE on both outputs, or the legacy
     'smoothl1_ce' spelling, with neither loss_weights nor metrics; a DetectionLossSpec (lisec_detection_loss) for a
-    VoxelNetLoss or 'voxelnet'; otherwise a LossSpec (lisec_head_loss).  Every refusal is raised here: ValueError (unknown
-    name, unknown output key, a list of the wrong length, a VoxelNetLoss given per output), NotImplementedError (a Keras
-    loss or metric the kernels do not implement, one's own callable, loss=None for an output, weighted_metrics, metrics
-    with a VoxelNetLoss)."""
+    VoxelNetLoss or 'voxelnet'; otherwise a LossSpec (lisec_head_loss).  With the detection loss, metrics takes the
+    detection metrics of lisec_amd/metrics.py and only those (metrics.compile_detection_metrics: a flat list routes each
+    metric to its own output); with every other loss, the Keras metrics and only those.  Every refusal is raised here:
+    ValueError (unknown name, unknown output key, a list of the wrong length, a VoxelNetLoss given per output, a
+    detection metric on the wrong output, too many of them), NotImplementedError (a Keras loss or metric the kernels do
+    not implement, one's own callable, loss=None for an output, weighted_metrics, a Keras metric with a VoxelNetLoss, a
+    detection metric without one)."""
     from . import metrics as metrics_mod
     if weighted_metrics is not None:
         raise NotImplementedError("weighted_metrics is not implemented (there are no sample weights)")
     joint = _joint_loss(loss)
     if joint is not None:
-        if metrics:
-            raise NotImplementedError("metrics= with the VoxelNet detection loss is not implemented: the Keras metrics "
-                                      "average over every cell of a label map that codes ignore / negative / positive")
-        return DetectionLossSpec(joint.params(), _weights(loss_weights)), []
+        mterms, names = metrics_mod.compile_detection_metrics(metrics)
+        return DetectionLossSpec(joint.params(), _weights(loss_weights), mterms, names), list(names)
     legacy = _legacy_key(loss)
     if legacy is not None:
         terms = LEGACY[legacy]

@@ -24,7 +24,8 @@ import torch
 
 from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table
-from .network import EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len
+from .network import (EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len, loss_acc_logs,
+                      loss_acc_split)
 from .params import ParamStore
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
@@ -489,7 +490,9 @@ class Model:
         output order or a dict keyed by 'ClassificationLayer' / 'RegressionLayer'; also the project's 'smoothl1_ce' (=
         ['cross_entropy', 'smooth_l1']: sigmoid cross-entropy on labels clamped to [0, 1] + SmoothL1), or -- as the whole
         argument only -- losses.VoxelNetLoss(...) / 'voxelnet', the detection loss the 0/1/2 label code was made for (one
-        loss of both outputs; loss_weights apply, metrics are refused).  loss_weights: a list
+        loss of both outputs; loss_weights apply; metrics: the detection metrics of lisec_amd/metrics.py -- 'anchor_precision',
+        'anchor_recall', 'anchor_accuracy', 'positive_mae', 'positive_iou' or their objects -- and only those, a flat list
+        routing each to the output it belongs to, unlike Keras).  loss_weights: a list
         or dict of floats (default 1): the step minimises w_c*L_c + w_r*L_r, History's `loss`; the per-output losses are
         logged unweighted.  metrics: a list (for each output), a list of two lists or a dict per output name; logged as
         "<output>_<name>" (see metrics_names).  weighted_metrics: not implemented (there are no sample weights).
@@ -550,7 +553,8 @@ class Model:
         int: every validation_freq-th epoch; a container: those 1-based epochs), evaluate() runs on the validation sweeps
         (validation_steps of them at most) with on_test_begin / on_test_end, and val_loss, val_ClassificationLayer_loss and
         val_RegressionLayer_loss join the logs of on_epoch_end and History.  The metrics of compile() are logged as epoch
-        means under metrics_names, and with validation as val_<name>.  fit ends after any epoch whose callbacks set
+        means under metrics_names, and with validation as val_<name>; the detection metrics as the ratio of their two sums
+        pooled over the epoch's sweeps, summed on the device in float64 and divided once.  fit ends after any epoch whose callbacks set
         model.stop_training.
         x may be a keras.utils.Sequence-like object (__len__, __getitem__(i) -> (points (n, >= 3), [y_cls, y_reg]),
         on_epoch_end()), e.g. augment.AugmentedSweeps, with y=None: step st trains on item order[st], made when the step
@@ -606,7 +610,7 @@ class Model:
             cb.set_params(dict(verbose=verbose, epochs=epochs, steps=steps))
         target = _targets(ycls, yreg, range(n), dev) if seq is None else None
         seq_req = self._sequence_request(seq) if seq is not None else None
-        nm = loss_acc_len(self.loss) - 4                    # metrics of the compiled loss
+        nm = loss_acc_len(self.loss) - 4                    # metric words of the compiled loss (loss_acc_len's layout)
         for cb in callbacks:
             cb.on_train_begin()
         for epoch in range(epochs):
@@ -622,6 +626,7 @@ class Model:
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
             tot_dev = torch.zeros(3, dtype=torch.float64, device=dev)
             met_dev = torch.zeros(nm, dtype=torch.float64, device=dev) if nm else None
+            met_step = self.net.step_metrics(self.loss)     # where a step leaves its metric words; None without metrics
             every = max(1, steps // 20)
             t0 = time.time()
 
@@ -642,7 +647,7 @@ class Model:
                                         allreduce=self.dp.bucketed() if self.dp is not None else None)
                 tot_dev += self.net.loss_out
                 if nm:
-                    met_dev += self.net.metric_out[:nm]
+                    met_dev += met_step
                 if verbose and ((st + 1) % every == 0 or st + 1 == steps):
                     print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / (st + 1):.4f}", end="", flush=True)
             tot = tot_dev.cpu().numpy()
@@ -650,7 +655,7 @@ class Model:
                 print(f" - {time.time() - t0:.1f}s")
             if nm:
                 tot = np.concatenate([tot, met_dev.cpu().numpy()])
-            logs = {key: float(v) for key, v in zip(self.metrics_names, tot / max(steps, 1))}
+            logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, tot, max(steps, 1))))
             if val is not None and _should_validate(epoch, validation_freq):
                 vlogs = self._evaluate(*val, callbacks=callbacks, verbose=0)
                 logs.update({"val_" + key: v for key, v in vlogs.items()})
@@ -773,7 +778,7 @@ class Model:
                  return_dict=False):
         """model.evaluate(x, [y_cls, y_reg]) -> [loss, ClassificationLayer_loss, RegressionLayer_loss, metrics...] in the
         order of metrics_names (a dict with those keys with return_dict=True): the compiled loss and metrics with inference BatchNormalization (the moving statistics), as a mean
-        over the evaluated sweeps.  The sweeps are independent, so every batch_size gives that value -- Keras' mean
+        over the evaluated sweeps (the detection metrics of loss='voxelnet': the ratio of their two sums pooled over the sweeps).  The sweeps are independent, so every batch_size gives that value -- Keras' mean
         weighted by batch size; batch_size (Keras' default 32) only sets what `steps` counts: steps * batch_size sweeps.
         callbacks get on_test_begin / on_test_end.  Each sweep runs the eager forward(training=False), or, with
         LISEC_TUNING=eval_plan=1 and voxelised sweeps, the recorded evaluation step (EvalStep), which pads every sweep to
@@ -801,9 +806,8 @@ class Model:
         for cb in callbacks:
             cb.on_test_begin()
         t0 = time.time()
-        sums = self._eval_sums(samples, ycls, yreg)
-        count = sums[-1]
-        logs = {k: (float(v / count) if count else float("nan")) for k, v in zip(self.metrics_names, sums[:-1])}
+        sums, count = loss_acc_split(self.loss, self._eval_sums(samples, ycls, yreg))
+        logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, sums, count)))
         if verbose:
             print(f"{int(count)}/{int(count)} - {time.time() - t0:.1f}s - " +
                   " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
@@ -812,7 +816,7 @@ class Model:
         return logs
 
     def _eval_sums(self, samples, ycls, yreg):
-        """float64 [total, class, regression, metrics..., sweeps] summed over the sweeps, read back once.  Data parallel: rank r takes
+        """The float64 accumulator of loss_acc_len's layout summed over the sweeps, read back once.  Data parallel: rank r takes
         samples[r::world] (every sweep is evaluated once; DataParallel.shard would drop the tail), evaluates with the
         rank-mean BatchNormalization moving statistics (copy, average, evaluate, restore) and the sums are all-reduced."""
         net, dev = self.net, self.net.device

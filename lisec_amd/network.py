@@ -30,14 +30,37 @@ LEGACY_LOSS_KINDS = {"mse": 0, "smoothl1_ce": 1}        # the `kind` of lisec_rp
 
 
 def loss_acc_len(loss):
-    """Length of the evaluation accumulator of a step loss, [total, class, regression, metrics..., sweeps]; KeyError
-    for a string that names no legacy loss."""
+    """Length of the evaluation accumulator of a step loss; KeyError for a string that names no legacy loss.  The layout:
+        legacy string      [total, class, regression, sweeps]
+        LossSpec           [total, class, regression, metrics..., sweeps]     (per-sweep values, summed)
+        DetectionLossSpec  [total, class, regression, sweeps, num0, den0, num1, den1, ...]
+    A DetectionLossSpec keeps the sweep count in acc[3], where lisec_detection_loss_eval writes it, and appends the
+    {num, den} pairs of its metrics (lisec_detection_metrics with accumulate): sums pooled over the sweeps."""
     if isinstance(loss, LossSpec):
         return 4 + loss.n_metrics
     if isinstance(loss, DetectionLossSpec):
-        return 4
+        return 4 + 2 * loss.n_metrics
     LEGACY_LOSS_KINDS[loss]                 # refuses an unknown name
     return 4
+
+
+def loss_acc_logs(loss, sums, count):
+    """[total, class, regression, metrics...] in the order of Model.metrics_names from sums, laid out as [total, class,
+    regression, the metric words of loss_acc_len's layout...] (numpy float64), over `count` sweeps: the losses and a
+    LossSpec's metrics are means over the sweeps (NaN without any); a DetectionLossSpec's metrics are num/den of the
+    pooled pairs, 0.0 when den == 0 (Keras' div_no_nan)."""
+    mean = [float(v / count) if count else float("nan") for v in sums[:3]]
+    if isinstance(loss, DetectionLossSpec):
+        pairs = sums[3:3 + 2 * loss.n_metrics]
+        return mean + [float(n / d) if d != 0 else 0.0 for n, d in zip(pairs[0::2], pairs[1::2])]
+    return mean + [float(v / count) if count else float("nan") for v in sums[3:]]
+
+
+def loss_acc_split(loss, acc):
+    """An evaluation accumulator (numpy, loss_acc_len's layout) -> (sums as loss_acc_logs takes them, sweeps)."""
+    if isinstance(loss, DetectionLossSpec):
+        return np.concatenate([acc[:3], acc[4:]]), acc[3]
+    return acc[:-1], acc[-1]
 
 
 class OptimizerSpec:
@@ -675,6 +698,8 @@ class LisecNet:
         self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
         # [N_pos, N_neg] of a DetectionLossSpec loss (lisec_detection_loss); fixed address, like loss_out
         self.loss_counts = torch.zeros(2, dtype=torch.int64, device=dev)
+        # [num0, den0, num1, den1, ...] of a DetectionLossSpec's metrics (lisec_detection_metrics); fixed address
+        self.metric_pairs = torch.zeros(2 * _lib.DET_MAX_METRICS, dtype=torch.float64, device=dev)
 
     @property
     def iterations(self):
@@ -1128,7 +1153,8 @@ class LisecNet:
         and self.loss_out = [total, class, regression].  Must follow forward(training=True).
         loss: 'mse' (loss=['mse','mse'], the reference's) or 'smoothl1_ce' -- lisec_rpn_loss -- or a LossSpec (Keras losses,
         loss_weights and metrics: lisec_head_loss, which also fills self.metric_out[:loss.n_metrics]) or a
-        DetectionLossSpec (the VoxelNet detection loss: lisec_detection_loss, which also fills self.loss_counts).
+        DetectionLossSpec (the VoxelNet detection loss: lisec_detection_loss, which also fills self.loss_counts; its
+        metrics: lisec_detection_metrics, into self.metric_pairs[:2 * loss.n_metrics]).
         side_filler: optional callable issued on the second stream behind the head-phase leaves, where that stream has
         nothing to do for ~200 us (the weight gradients of the last RPN block wait for its chain): independent work such as
         the NEXT sweep's voxelisation (PipelinedStep).
@@ -1147,11 +1173,29 @@ class LisecNet:
             self._loss_descs[spec] = spec.descriptor()
         return self._loss_descs[spec]
 
+    def _metrics_descriptor(self, spec):
+        """The lisec_detection_metrics_cfg of a DetectionLossSpec with metrics, built once per spec."""
+        key = ("metrics", spec)
+        if key not in self._loss_descs:
+            self._loss_descs[key] = spec.metrics_descriptor()
+        return self._loss_descs[key]
+
+    def step_metrics(self, loss):
+        """What the last training step left of the metrics of its loss, as the words fit() sums over an epoch (the metric
+        words of loss_acc_len's layout): a LossSpec's fp32 values in metric_out, a DetectionLossSpec's fp64 pairs in
+        metric_pairs; None without metrics."""
+        if isinstance(loss, LossSpec) and loss.n_metrics:
+            return self.metric_out[:loss.n_metrics]
+        if isinstance(loss, DetectionLossSpec) and loss.n_metrics:
+            return self.metric_pairs[:2 * loss.n_metrics]
+        return None
+
     def _loss_backward(self, loss, y_cls, y_reg, grad_scale):
         """The loss of the head map against the targets into loss_out (a LossSpec: and its metrics into metric_out), its
         gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*), a LossSpec (lisec_head_loss*) or a
-        DetectionLossSpec (lisec_detection_loss*, its counts into loss_counts): this, loss_eval() and loss_acc_len() are the
-        only code that tells them apart."""
+        DetectionLossSpec (lisec_detection_loss*, its counts into loss_counts, and lisec_detection_metrics, its metric
+        pairs into metric_pairs): this, loss_eval(), step_metrics() and loss_acc_len() with its two readers (loss_acc_logs,
+        loss_acc_split) are the only code that tells them apart."""
         head, dhead, M = self.act["head"], self.dact["head"], self.Ho * self.Wo
         if isinstance(loss, LossSpec):
             ops.head_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.metric_out,
@@ -1159,17 +1203,21 @@ class LisecNet:
         elif isinstance(loss, DetectionLossSpec):
             ops.detection_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.loss_counts,
                                grad_scale=grad_scale)
+            if loss.n_metrics:
+                ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, self.metric_pairs)
         else:
             ops.rpn_loss(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], dhead, self.loss_out, grad_scale=grad_scale)
 
     def loss_eval(self, loss, y_cls, y_reg, acc):
-        """Adds the loss (and a LossSpec's metrics) of the head map against the targets to acc (float64, device,
-        loss_acc_len(loss) long), which counts the sweep in its last element."""
+        """Adds the loss (and the metrics of a LossSpec or DetectionLossSpec) of the head map against the targets to acc
+        (float64, device, loss_acc_len(loss) long, in the layout stated there) and counts the sweep in it."""
         head, M = self.act["head"], self.Ho * self.Wo
         if isinstance(loss, LossSpec):
             ops.head_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
         elif isinstance(loss, DetectionLossSpec):
             ops.detection_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
+            if loss.n_metrics:
+                ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, acc[4:], accumulate=True)
         else:
             ops.rpn_loss_eval(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], acc)
 
@@ -1627,8 +1675,8 @@ class EvalStep(_StepPlans):
     """One evaluation sweep -- voxelise a fixed-capacity padded sweep (as RecordedStep), forward(training=False), add the
     sweep's loss to a device accumulator (lisec_rpn_loss_eval; lisec_head_loss_eval for a LossSpec, lisec_detection_loss_eval for a DetectionLossSpec) -- recorded ONCE as a
     step plan and re-issued by one C call per sweep (Model.evaluate and the validation of Model.fit with
-    LISEC_TUNING=eval_plan=1; by default they run the eager forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps] -- with a LossSpec
-    [total, class, regression, metrics..., sweeps] -- (float64, device) is read by the host once per evaluation.  Invariants:
+    LISEC_TUNING=eval_plan=1; by default they run the eager forward, measured faster: DESIGN.md).  The accumulator acc = [total, class, regression, sweeps] -- with metrics
+    in the layout of loss_acc_len -- (float64, device) is read by the host once per evaluation.  Invariants:
 
       BN fold   inference scale/shift come from ops.bn_fold (LisecNet._bn_after), cached per (params_version,
                 state_version, params.version); a training step overwrites bnstate with batch statistics and moves the

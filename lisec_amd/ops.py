@@ -466,6 +466,16 @@ def detection_loss_eval(cfg, head, y_cls, y_reg, M, acc):
                                                      M, _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
 
 
+def detection_metrics(cfg, head, y_cls, y_reg, M, out, accumulate=False):
+    """The detection metrics of cfg (an _lib.DetectionMetricsCfg, lisec_detection_metrics_cfg) as pairs of sums over the
+    sweep's anchors: out (float64 device tensor) = [num0, den0, num1, den1, ...], stored, or added with accumulate."""
+    ws = _ew_workspace(head.device)
+    assert ws.numel() >= _lib.load().lisec_detection_metrics_workspace_bytes()
+    _lib.check(_lib.load().lisec_detection_metrics(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                                                   _lib.ptr(out), 1 if accumulate else 0, _lib.ptr(ws), ws.numel(),
+                                                   _lib.current_stream()))
+
+
 def sgd_nesterov_step(theta, grad, velocity, lr_t, momentum):
     _lib.check(_lib.load().lisec_sgd_nesterov_step(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity),
                                                    theta.numel(), lr_t, momentum, _lib.current_stream()))

@@ -1,11 +1,12 @@
 """The loss kernels on the Lyft head (M = 100*200 cells): the legacy pair (k_loss + k_loss_finalize, lisec_rpn_loss) against
 lisec_head_loss (k_head_loss + k_head_loss_finalize, csrc/losses.hip) and lisec_detection_loss (k_det_count + k_det_loss +
-k_det_finalize, csrc/detection_loss.hip) for the configurations of Model.compile below, each
+k_det_finalize, csrc/detection_loss.hip; with metrics also lisec_detection_metrics: k_detm_anchors + k_detm_finalize,
+csrc/detection_metrics.hip) for the configurations of Model.compile below, each
 timed over back-to-back launches with device events; then a short Model.fit on U20k sweeps under each, timed per step
 (GPU box only).  Run it under `rocprofv3 --kernel-trace --stats` for the kernel times: --config restricts the run to
 one configuration, so that the per-kernel statistics of a profile hold that configuration alone.
 
-    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics|voxelnet|voxelnet_focal] [--iters 500]
+    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics|voxelnet|voxelnet_focal|voxelnet_metrics] [--iters 500]
                                   [--fit-steps 20] [--repeats 1]
 
   mse             loss=['mse','mse']                          lisec_rpn_loss kind 0 (the reference's step)
@@ -14,6 +15,7 @@ one configuration, so that the per-kernel statistics of a profile hold that conf
   keras_metrics   the same with metrics [[BinaryAccuracy(threshold=0), 'accuracy'], ['mae', 'mse']]
   voxelnet        loss='voxelnet' (VoxelNetLoss(): gamma 0)           lisec_detection_loss
   voxelnet_focal  VoxelNetLoss(alpha=0.5, beta=1.5, gamma=2.0)        lisec_detection_loss, the pow() path
+  voxelnet_metrics  loss='voxelnet' with the five detection metrics   lisec_detection_loss + lisec_detection_metrics
 
 --repeats N times the fit N times per configuration and prints each: the run-to-run spread."""
 import argparse
@@ -40,6 +42,8 @@ def _configs():
                               metrics=[[Mx.BinaryAccuracy(threshold=0.0), "accuracy"], ["mae", "mse"]]),
         "voxelnet": dict(loss="voxelnet"),
         "voxelnet_focal": dict(loss=K.VoxelNetLoss(alpha=0.5, beta=1.5, gamma=2.0)),
+        "voxelnet_metrics": dict(loss="voxelnet", metrics=["anchor_precision", "anchor_recall", "anchor_accuracy",
+                                                           "positive_mae", "positive_iou"]),
     }
 
 
@@ -55,7 +59,13 @@ def _kernel_time(step_loss, head, yc, yr, M, iters):
     elif isinstance(step_loss, getattr(K, "DetectionLossSpec", ())):
         desc = step_loss.descriptor()
         counts = torch.zeros(2, dtype=torch.int64, device=dev)
-        call = lambda: ops.detection_loss(desc, head, yc, yr, M, dhead, loss_out, counts)  # noqa: E731
+        mdesc = step_loss.metrics_descriptor()
+        pairs = torch.zeros(16, dtype=torch.float64, device=dev)
+
+        def call():
+            ops.detection_loss(desc, head, yc, yr, M, dhead, loss_out, counts)
+            if mdesc is not None:
+                ops.detection_metrics(mdesc, head, yc, yr, M, pairs)
     else:
         kind = {"mse": 0, "smoothl1_ce": 1}[step_loss]
         call = lambda: ops.rpn_loss(head, yc, yr, M, kind, dhead, loss_out)                 # noqa: E731
