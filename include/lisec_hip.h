@@ -463,7 +463,7 @@ typedef struct lisec_wgrad_plan {
     int taps_per_group;  /* taps that share one staged dy tile                                                           */
     int groups;          /* tap groups that get workgroups (groups no output line can read are left out)                  */
     int tile_rows;       /* rows per staged tile (halo: equal tiles per output line)                                      */
-    int staging_passes;  /* halo: 7 (tiles of <= 110 rows, three workgroups per CU) or 9                                  */
+    int staging_passes;  /* halo: 7 (tiles of <= 104 rows, three workgroups per CU) or 9                                  */
     int tiles, slabs, tiles_per_slab;   /* M tiles, partial slabs (= ranges of tiles), tiles per range                   */
     int workgroups;
     int lane_reduce;     /* >= 32 slabs summed by a separate launch: the lane-strided slab sum                            */

@@ -274,8 +274,10 @@ struct WgradItem {
 constexpr int kWSlabF4 = 4 * 12 * 64;
 constexpr int kWgradCounters = 4096;
 
-// NP: staging passes of 16 rows.  7 (tiles of <= 110 rows: the 400-wide middle layers run 4 x 100) needs 12 registers
-// fewer than 9 and, with the fragment reads software-pipelined by hand, fits three workgroups per CU.
+// NP: staging passes of 16 rows.  7 (tiles of <= 104 rows: the 400-wide middle layers run 4 x 100) needs 12 registers
+// fewer than 9 and, with the fragment reads software-pipelined by hand, fits three workgroups per CU.  The bound is on DR,
+// not on LT: the last 8-row chunk reads the A image up to row DR + 1, so the passes must cover DR + 2 <= NP * 16 rows
+// (LT = 105 .. 110 has DR = 112: rows 112 and 113 lie beyond seven passes and would be read as stale LDS).
 template <bool XF, int NP>
 __device__ __forceinline__ void
 wgrad_halo_body(const WgradItem& it, const int bx, const int by, const int bz, float* smem, unsigned long long* stamps,
@@ -1218,7 +1220,8 @@ int plan_wgrad(const lisec_conv_geom* c, int flags, bool has_in_bn, bool has_dy_
         p->kind = WgradCall::HALO;
         it.flip = flip ? 1 : 0;
         p->mirrored = flip;
-        p->np = it.LT + 2 <= 7 * 16 ? 7 : 9;
+        const int DR = (it.LT + 7) & ~7;
+        p->np = DR + 2 <= 7 * 16 ? 7 : 9;                // the passes stage every row of the A image the chunks read
         p->halo_fn = halo_kernel(p->xf, p->np);
         p->lds = halo_lds(it.LT);
         p->cells = p->groups * it.gy * it.gz;
