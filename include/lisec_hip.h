@@ -224,6 +224,10 @@ typedef struct {
                                      (lisec_conv_forward_winograd: k_wino<false,0,1>), so a rocprofv3 --stats row
                                      shows this layer alone (bench.py roofline)                                    */
 #define LISEC_CONV_DY_RELU 8     /* wgrad only: ReLU on the (optionally affine-transformed) dy operand     */
+#define LISEC_CONV_SMALL_TILE 16 /* lisec_conv_forward*: a small K-sliced layer may run as 64-row tiles, two workgroups per CU
+                                    (k_igemm_small; lisec_tuning.small_tile).  Same output and statistics, bit for bit (with a
+                                    sink the call needs the workspace).  Ignored where the kernel does not serve the call:
+                                    see lisec_conv_plan.tile_rows                                                      */
 
 /* Packed weight layout the kernels read: [tap][K/4][N][4] fp32, K and N zero padded to 64.
  * src element (tap, k, n) is read at src[tap*tap_stride + k*k_stride + n*n_stride], so any Keras
@@ -359,13 +363,14 @@ enum { LISEC_KERNEL_IGEMM = 0,   /* generic gather, 128 x 64 tile               
 typedef struct lisec_conv_plan {
     int kernel;          /* LISEC_KERNEL_*                                                                    */
     int cols;            /* output columns per workgroup: 64, 32 (instead of two K slices) or 128 (wide tile) */
-    int tiles;           /* 128-row tiles of the call (parity-class order pads every class to whole tiles)    */
+    int tiles;           /* tiles of the call, of tile_rows rows (parity-class order pads every class to whole tiles) */
     int tail_tile0;      /* first tile of the K-sliced tail (0: the whole layer is sliced, == tiles: none)    */
     int k_slices;        /* K slices of the tail, combined in-kernel by the last slice to arrive              */
     int plane_pair;      /* one workgroup per pair of depth planes                                            */
     int parity_classes;  /* rows visited in (h & 1, w & 1) classes (data gradient of a stride-2 Conv2D)       */
     int workgroups, launches;
     int double_buffered; /* the K-sliced launch runs the two-image kernels, one workgroup per CU              */
+    int tile_rows;       /* rows per tile: 128, or 64 (LISEC_CONV_SMALL_TILE honoured: two workgroups per CU)   */
 } lisec_conv_plan;
 int lisec_conv_plan_query(const lisec_conv_geom* g, int has_in_bnstate, int flags, const lisec_conv_extras* extras,
                           int has_stats_table, size_t workspace_bytes, int has_row_list, int row_capacity,
@@ -1235,6 +1240,7 @@ typedef struct lisec_tuning {
     int wgrad_ring_slots;   /* workgroups a ring launch fills, 0 = one per CU                      (0)         */
     int wide_tile;          /* 128 x 128 tiles (512-thread workgroups) for 128-channel w-halo layers of few tiles (0:  */
                             /* measured equal to the 128 x 32 plan alone, 0.8 % slower in the step -- kept for study)   */
+    int small_tile;         /* calls that pass LISEC_CONV_SMALL_TILE run small K-sliced layers as 64-row tiles     (1)  */
 } lisec_tuning;
 int lisec_tuning_get(lisec_tuning* t);        /* fills *t with the current record (t->struct_bytes set)          */
 int lisec_tuning_set(const lisec_tuning* t);  /* t->struct_bytes must be sizeof(lisec_tuning); every field is range-checked */

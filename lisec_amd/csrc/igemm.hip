@@ -17,6 +17,8 @@
 //   64 MFMAs per wave (4096 SIMD cycles at the 64-cycle issue rate of the f32 MFMA).
 // The next slab is prefetched into registers while the MFMAs run and written to LDS between two
 // barriers (single LDS buffer, 51 KB => 3 workgroups per CU cover each other's staging).
+// The tile height is a template parameter TM of igemm_tile / halo_tile / store_tile: 128 as above, or 64 (k_igemm_small, below)
+// for the K-sliced layers of few tiles -- one 32 x 32 accumulator per wave, two double-buffered workgroups per CU.
 // fp32 in / fp32 accumulate: bit-for-bit an fmaf chain, so parity with the fp32 oracle holds to
 // summation-order noise (no reduced precision anywhere).
 #include "conv.h"
@@ -49,16 +51,28 @@ __device__ unsigned long long* g_igemm_stamps = nullptr;
 // partial sums.  C layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
 // mw: first of the 32 rows this wave holds; storer: false for a wave that holds no rows of its own -- it only takes part
 // in the statistics reduction, with zeros.
+// TM = 64 (the 64 x 64 tile): wave w holds ONE accumulator, rows mw = m0 + (w & 1) * 32 .. and columns n0 + (w >> 1) * 32 ..;
+// acc1 is not read.  The fp32 partial per 32-row group is what it is for TM = 128; the fp64 sum above it adds the two row
+// halves of a column block -- and, under a sink, the two 64-row tiles of one 128-row tile MEET (pair_ws: the workspace whose
+// head holds the counters, pair_buf: 256 floats per workgroup) so that the sink receives the addend the 128-row tile would
+// have sent, ((r0 + r1) + r2) + r3 in fp64 over its four 32-row groups: the fixed-point sink rounds every addend to 2^-40,
+// and a gradient's sums are small enough for two addends to round differently from one.  The first tile of a pair to finish
+// leaves its two fp32 partials per column (sc1 stores, wait, barrier, one agent-scope add: the hand-off of splitk_arrive), the
+// second one reads them (sc1), sums in row order and adds; both take their sink ticket.  A tile without a partner (the
+// last 64 rows of an odd count) adds alone: the missing groups are the zeros of the 128-row tile's rows beyond M.
+constexpr int kPairCounter0 = 2048;              // pair counters: the upper half of the workspace's kSplitCounters
+template <int TM = 128>
 __device__ __forceinline__ void store_tile(const ConvGeom& g, const f32x16& acc0, const f32x16& acc1, float* smem,
                                            int mw, int n0, int mb, int mlimit, int wave, int lane, int tid,
                                            const float* __restrict__ bias, int flags, float* __restrict__ out,
                                            double* __restrict__ stats, bool storer = true, bool half = false,
-                                           int phase = 0, float* lds_tile = nullptr) {
+                                           int phase = 0, float* lds_tile = nullptr, float* pair_ws = nullptr,
+                                           float* pair_buf = nullptr) {
     // phase (calls with g.tail_w): 1 = the gated first output, no statistics, the stored values also go to lds_tile
     // ([128][LDA], the A operand of the tail contraction); 2 = the tail's output: no gate, the backward statistics
     // half: the workgroup computed a 32-column slab (acc1 is unused): the second 32 columns are treated as outside Cout
     const int col = lane & 31;
-    const int nA = n0 + col, nB = half ? g.Cout : n0 + 32 + col;
+    const int nA = n0 + (TM == 64 ? (wave >> 1) * 32 : 0) + col, nB = half || TM == 64 ? g.Cout : n0 + 32 + col;
     // pixel-shuffle store (kernel == stride transposed conv): the 64-column slab lies inside one tap
     const int ps_tap = g.ps ? n0 / g.ps_channels : 0;
     const int ps_kh = g.ps ? ps_tap / g.ps : 0, ps_kw = g.ps ? ps_tap - ps_kh * g.ps : 0;
@@ -157,7 +171,46 @@ __device__ __forceinline__ void store_tile(const ConvGeom& g, const f32x16& acc0
             red[(wave * 4 + 2) * 32 + lane] = sumB; red[(wave * 4 + 3) * 32 + lane] = sqB;
         }
         __syncthreads();
-        if (tid < 128) {
+        if (TM == 64) {
+            const int q = tid >> 5, c = tid & 31;            // (tid < 128) q: 0 sum, 1 sq of columns 0-31; 2, 3 of columns 32-63
+            const int w0 = q & 2;                            // column block q >> 1 is held by waves (q & 2) and (q & 2) + 1
+            float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;    // the two 32-row groups of this tile / of the other half of its 128 rows
+            const int hf = mb & 1;
+            if (tid < 128) { a0 = red[(w0 * 4 + (q & 1)) * 32 + c]; a1 = red[((w0 + 1) * 4 + (q & 1)) * 32 + c]; }
+            bool add = true;
+            if (g.sink.acc && pair_ws && (mb ^ 1) * 64 < g.M) {          // (workgroup-uniform)
+                __shared__ int pair_second;
+                const int slot = (mb >> 1) * gridDim.y + blockIdx.y;
+                int* counter = reinterpret_cast<int*>(pair_ws) + kPairCounter0 + slot;
+                float* mine = pair_buf + ((size_t)slot * 2 + hf) * 256;
+                const float* theirs = pair_buf + ((size_t)slot * 2 + (hf ^ 1)) * 256;
+                if (tid < 128) {
+                    __hip_atomic_store(mine + tid, a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(mine + 128 + tid, a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                if (tid == 0) pair_second = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __syncthreads();
+                add = pair_second == 1;
+                if (add) {
+                    if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (tid < 128) {
+                        b0 = __hip_atomic_load(theirs + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        b1 = __hip_atomic_load(theirs + 128 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+            }
+            if (add && tid < 128) {
+                double v = 0.0;                              // row order, as the 128-row tile sums its four groups
+                v += (double)(hf ? b0 : a0); v += (double)(hf ? b1 : a1); v += (double)(hf ? a0 : b0); v += (double)(hf ? a1 : b1);
+                const int n = n0 + (q >> 1) * 32 + c;
+                if (n < g.Cout) {
+                    if (g.sink.acc) sink_add(g.sink, q & 1, n, v);
+                    else stats[((size_t)mb * 2 + (q & 1)) * g.Cout + n] = v;
+                }
+            }
+        } else if (tid < 128) {
             const int q = tid >> 5, c = tid & 31;            // q: 0 sumA, 1 sqA, 2 sumB, 3 sqB
             double v = 0.0;
 #pragma unroll
@@ -183,18 +236,21 @@ __device__ __forceinline__ void store_tile(const ConvGeom& g, const f32x16& acc0
 // backward -- dy = scale (gate(y) g - mean(dz) - yhat mean(dz yhat)), k_bn_bwd_apply -- runs on load, from g (`in`), the
 // layer's raw output y (g.in_y, same layout) and the per-channel constants (g.fold_bn = its bnstate, g.fold_coef = the
 // backward sink's means): the chain of data gradients of the RPN no longer stops for a launch between every two of them.
-template <int MODE, bool XF, int NW = 64, bool DB = false, bool FOLD = false>
+template <int MODE, bool XF, int NW = 64, bool DB = false, bool FOLD = false, int TM = BM>
 __device__ __forceinline__ void
 igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restrict__ wp,
            const float* __restrict__ bias, const float* __restrict__ in_bn, int flags,
            float* __restrict__ out, double* __restrict__ stats, int nsplit, float* __restrict__ partial, int tile0,
            int mb, float* smem, unsigned long long* stamps, unsigned stamp_wg) {
+    static_assert(TM == 128 || (TM == 64 && NW == 64), "tile height");
+    constexpr int TA_FLOATS = TM * LDA, NP = TM / 16;          // A image; staged rows per thread
+    constexpr bool TWO = NW == 64 && TM == 128;                // two accumulators per wave
     float* sA = smem;
-    float* sB = smem + A_FLOATS;
+    float* sB = smem + TA_FLOATS;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m0 = mb * BM;
+    const int m0 = mb * TM;
     const int n0 = blockIdx.y * NW;
     const int mlimit = row_limit(g);
     if (m0 >= mlimit) return;                     // row list shorter than its capacity (whole workgroup)
@@ -202,25 +258,25 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
 
     // ---- rows this thread stages: r = p*16 + tid/16, 16-byte piece tid%16 ----------------------
     const int piece = tid & 15;
-    RowGather rows[8];
+    RowGather rows[NP];
     int tile_mask = 0;
     {
         // each gather descriptor is computed ONCE (thread r < 128 owns row r: two integer divisions + three axis masks) and
         // handed to the 16 threads that stage that row through LDS, instead of 8 descriptors per thread
         int2* shared_rows = reinterpret_cast<int2*>(smem);
-        int* tile_or = reinterpret_cast<int*>(shared_rows + BM);     // OR of the rows' validity bits
+        int* tile_or = reinterpret_cast<int*>(shared_rows + TM);     // OR of the rows' validity bits
         if (g.row_coords) {                                          // (wave-uniform branch)
             if (tid == 0) *tile_or = 0;
             __syncthreads();
         }
-        if (tid < BM) {
+        if (tid < TM) {
             const RowGather r = row_gather(g, m0 + tid, MODE, 0);
             shared_rows[tid] = make_int2(r.off, r.mask);
             if (g.row_coords && r.mask) atomicOr(tile_or, r.mask);
         }
         __syncthreads();
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int p = 0; p < NP; ++p) {
             const int2 v = shared_rows[p * 16 + (tid >> 4)];
             rows[p].off = v.x + piece * 4;
             rows[p].mask = v.y;
@@ -229,7 +285,7 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
         __syncthreads();
     }
     // tile-uniform depth range for whole-tap skipping
-    const int mlast = (m0 + BM - 1 < g.M ? m0 + BM - 1 : g.M - 1);
+    const int mlast = (m0 + TM - 1 < g.M ? m0 + TM - 1 : g.M - 1);
     const int d_first = g.pc_span ? 0 : m0 / HW, d_last = g.pc_span ? 0 : mlast / HW;
     int dmask_first;
     {
@@ -260,8 +316,8 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
         return (dmask_first >> t.kd) & 1;
     };
 
-    float4 ra[8];
-    float4 ry[FOLD ? 8 : 1];
+    float4 ra[NP];
+    float4 ry[FOLD ? NP : 1];
     float4 fmu = make_float4(0, 0, 0, 0), fis = fmu, fm1 = fmu, fm2 = fmu;     // FOLD: mean, 1/std, mean(dz), mean(dz yhat)
     float4 rb0, rb1, rb2, rb3;
     float4 tsc = make_float4(1, 1, 1, 1), tsh = make_float4(0, 0, 0, 0);
@@ -276,7 +332,7 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
         const int tbits = cok ? tap_bits(kd, kh, kw) : 0x7fffffff;      // channel slab beyond Cin: nothing valid
         valid_mask = 0;
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int p = 0; p < NP; ++p) {
             const bool ok = (rows[p].mask & tbits) == tbits;
             const int off = ok ? rows[p].off + soff : 0;                // branch-free: invalid rows read element 0
             ra[p] = *reinterpret_cast<const float4*>(in + off);
@@ -317,7 +373,7 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
     auto store_lds = [&]() {
         // branch-free: without an affine tsc = 1, tsh = 0 (x*1 + 0 is exact); padding stays 0
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
+        for (int p = 0; p < NP; ++p) {
             float4 v = ra[p];
             const bool ok = (valid_mask >> p) & 1;
             if (FOLD) {
@@ -354,7 +410,9 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
     };
 
     f32x16 acc0 = {0}, acc1 = {0};
-    const int aoff = (wave * 32 + (lane & 31)) * LDA + 4 * (lane >> 5), boff = ((lane >> 5) * NW + (lane & 31)) * 4;
+    // TM = 64: wave w owns rows (w & 1) * 32 .. and columns (w >> 1) * 32 .. of the 64-column W slab
+    const int aoff = ((TM == 64 ? wave & 1 : wave) * 32 + (lane & 31)) * LDA + 4 * (lane >> 5);
+    const int boff = ((lane >> 5) * NW + (TM == 64 ? (wave >> 1) * 32 : 0) + (lane & 31)) * 4;
     const float* aRow = sA + aoff;
     const float* bCol = sB + boff;
 
@@ -405,19 +463,19 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
     __syncthreads();
     IGEMM_STAMP(2);
     int stamp_steps = 0, img = 0;
-    constexpr int IMG = A_FLOATS + B_FLOATS;
+    constexpr int IMG = TA_FLOATS + B_FLOATS;
     while (cur.s < nsteps) {
         ++stamp_steps;
         if (DB) {
             // image of step nxt -> the OTHER image (its loads went out a step ago); then the loads of the step after it
-            sA = smem + (img ^ 1) * IMG; sB = sA + A_FLOATS;
+            sA = smem + (img ^ 1) * IMG; sB = sA + TA_FLOATS;
             TStep nn = nxt;
             if (nxt.s < nsteps) {
                 store_lds();
                 nn = next_of(nxt);
                 if (nn.s < nsteps) issue_loads(nn);
             }
-            aRow = smem + img * IMG + aoff; bCol = smem + img * IMG + A_FLOATS + boff;
+            aRow = smem + img * IMG + aoff; bCol = smem + img * IMG + TA_FLOATS + boff;
             img ^= 1;
             cur = nxt; nxt = nn;
         } else {
@@ -432,24 +490,24 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
         // -- lgkmcnt(0), the reads of the NEXT chunk included -- before each group of MFMAs instead of the older ones only
         float4 a = *reinterpret_cast<const float4*>(aRow);
         float4 b0 = *reinterpret_cast<const float4*>(bCol);
-        float4 b1 = NW == 64 ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
+        float4 b1 = TWO ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
 #pragma unroll
         for (int kc = 0; kc < BK / 8; ++kc) {
             float4 an = a, b0n = b0, b1n = b1;
             if (kc + 1 < BK / 8) {
                 an = *reinterpret_cast<const float4*>(aRow + (kc + 1) * 8);
                 b0n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4);
-                if (NW == 64) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
+                if (TWO) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
             }
             __builtin_amdgcn_sched_barrier(0);                        // reads of chunk kc+1 stay above ...
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);                        // ... the 8 MFMAs of chunk kc
             a = an; b0 = b0n; b1 = b1n;
         }
@@ -463,12 +521,14 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
     IGEMM_STAMP(3);
     if (stamps && threadIdx.x == 0 && stamp_wg < 8192) stamps[(size_t)stamp_wg * 8 + 5] = (unsigned long long)stamp_steps;
     if (nsplit > 1) {
-        const bool last = splitk_arrive<DB>(acc0, acc1, partial, nsplit, (mb - tile0) * gridDim.y + blockIdx.y,
+        const bool last = splitk_arrive<DB, TM == 64 ? 4 : 8>(acc0, acc1, partial, nsplit, (mb - tile0) * gridDim.y + blockIdx.y,
                                         gridDim.x * gridDim.y, wave, lane);
         IGEMM_STAMP(7);
         if (!last) { IGEMM_STAMP(4); return; }
     }
-    store_tile(g, acc0, acc1, smem, m0 + wave * 32, n0, mb, mlimit, wave, lane, tid, bias, flags, out, stats, true, NW == 32);
+    store_tile<TM>(g, acc0, acc1, smem, m0 + (TM == 64 ? wave & 1 : wave) * 32, n0, mb, mlimit, wave, lane, tid, bias, flags, out, stats,
+                   true, NW == 32, 0, nullptr, TM == 64 ? partial : nullptr,
+                   TM == 64 && partial ? partial + kSplitCounters + (nsplit > 1 ? (size_t)nsplit * gridDim.x * gridDim.y * (64 * 64) : 0) : nullptr);
     IGEMM_STAMP(4);
 }
 
@@ -532,38 +592,41 @@ k_igemm_queue(ConvGeom g, const float* __restrict__ in, const float* __restrict_
 //     halo row j >= a + 2 : line L0 + k, w_in = (j - (a + 2)) % (Wo + 2) - 1,   k = 1 + (j - (a + 2)) / (Wo + 2)
 // and output row r (on segment k) reads halo row  r + 2k + f(kw),  f = kw (mode 0) or 2 - kw (mode 1).  Zero padding
 // in w is simply a zero halo row; the (kd, kh) validity is per line, i.e. wave-uniform.  K slices are whole A tiles.
-constexpr int halo_rows(int nseg) { return BM + 2 * nseg; }     // segments + two halo columns each
-constexpr size_t halo_lds_bytes(int nseg) { return (size_t)(halo_rows(nseg) * LDA + B_FLOATS) * sizeof(float); }   // <= 52 832 B: 3 per CU
+constexpr int halo_rows(int nseg, int tm = BM) { return tm + 2 * nseg; }     // segments + two halo columns each
+constexpr size_t halo_lds_bytes(int nseg, int tm = BM) { return (size_t)(halo_rows(nseg, tm) * LDA + B_FLOATS) * sizeof(float); }   // <= 52 832 B: 3 per CU
 
-template <int MODE, bool XF, int NSEG, int NW = 64, bool DB = false, bool TAIL = false, bool FOLD = false>
+template <int MODE, bool XF, int NSEG, int NW = 64, bool DB = false, bool TAIL = false, bool FOLD = false, int TM = BM>
 __device__ __forceinline__ void
 halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restrict__ wp,
           const float* __restrict__ bias, const float* __restrict__ in_bn, int flags,
           float* __restrict__ out, double* __restrict__ stats, int nsplit, float* __restrict__ partial, int tile0,
           int mb, float* smem, unsigned long long* stamps, unsigned stamp_wg) {
-    constexpr int HALO_MAX_ROWS = halo_rows(NSEG);
+    static_assert(TM == 128 || (TM == 64 && NW == 64 && NSEG == 2 && !TAIL), "tile height");
+    constexpr int HALO_MAX_ROWS = halo_rows(NSEG, TM);
+    constexpr int NP = (HALO_MAX_ROWS + 15) / 16;              // staged halo rows per thread
+    constexpr bool TWO = NW == 64 && TM == 128;                // two accumulators per wave
     float* sA = smem;
     float* sB = smem + HALO_MAX_ROWS * LDA;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int m0 = mb * BM;
+    const int m0 = mb * TM;
     const int n0 = blockIdx.y * NW;
     const int mlimit = g.M;
 
     // ---- the (at most NSEG) output lines of this tile ----------------------------------------------
     const int L0 = m0 / g.Wo, w0 = m0 - L0 * g.Wo;
-    const int a = g.Wo - w0 < BM ? g.Wo - w0 : BM;               // rows on line L0
+    const int a = g.Wo - w0 < TM ? g.Wo - w0 : TM;               // rows on line L0
     const int nlines = g.Do * g.Ho;
-    const int nseg = a < BM ? 1 + (BM - a + g.Wo - 1) / g.Wo : 1;
-    const int nrows = BM + 2 * nseg;                             // staged halo rows
+    const int nseg = a < TM ? 1 + (TM - a + g.Wo - 1) / g.Wo : 1;
+    const int nrows = TM + 2 * nseg;                             // staged halo rows
 
     // ---- staging map of this thread: halo row j = p*16 + tid/16, 16-byte piece tid%16 ----------------
     const int piece = tid & 15;
-    int woff[9];                                                 // w_in * in_stride + piece*4, < 0: never valid
+    int woff[NP];                                                 // w_in * in_stride + piece*4, < 0: never valid
     unsigned segbits = 0;                                        // 2 bits per p: the segment of row p
 #pragma unroll
-    for (int p = 0; p < 9; ++p) {
+    for (int p = 0; p < NP; ++p) {
         const int j = p * 16 + (tid >> 4);
         int sg = 0, w_in = w0 - 1 + j;
         if (j >= a + 2) {
@@ -609,8 +672,8 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
         return any;
     };
 
-    float4 ra[9];
-    float4 ry[FOLD ? 9 : 1];
+    float4 ra[NP];
+    float4 ry[FOLD ? NP : 1];
     float4 fmu = make_float4(0, 0, 0, 0), fis = fmu, fm1 = fmu, fm2 = fmu;     // FOLD (see igemm_tile)
     float4 rb0, rb1, rb2, rb3;
     float4 tsc = make_float4(1, 1, 1, 1), tsh = make_float4(0, 0, 0, 0);
@@ -626,7 +689,7 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
             const int sb0 = seg_base(0, kd, kh), sb1 = seg_base(1, kd, kh), sb2 = NSEG > 2 ? seg_base(2, kd, kh) : -1;
             valid_mask = 0;
 #pragma unroll
-            for (int p = 0; p < 9; ++p) {
+            for (int p = 0; p < NP; ++p) {
                 const unsigned sg = (segbits >> (2 * p)) & 3u;
                 const int lb = sg == 0 ? sb0 : (sg == 1 || NSEG == 2 ? sb1 : sb2);
                 const bool ok = cok && woff[p] >= 0 && lb >= 0;
@@ -669,7 +732,7 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
     auto store_lds = [&]() {
         if (staged_a) {
 #pragma unroll
-            for (int p = 0; p < 9; ++p) {
+            for (int p = 0; p < NP; ++p) {
                 float4 v = ra[p];
                 const bool ok = (valid_mask >> p) & 1;
                 if (FOLD) {
@@ -708,9 +771,9 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
     };
 
     f32x16 acc0 = {0}, acc1 = {0};
-    const int r_lane = wave * 32 + (lane & 31);
+    const int r_lane = (TM == 64 ? wave & 1 : wave) * 32 + (lane & 31);      // TM = 64: see igemm_tile
     const int seg_lane = r_lane < a ? 0 : 1 + (r_lane - a) / g.Wo;
-    const int aoff = (r_lane + 2 * seg_lane) * LDA + 4 * (lane >> 5), boff = ((lane >> 5) * NW + (lane & 31)) * 4;
+    const int aoff = (r_lane + 2 * seg_lane) * LDA + 4 * (lane >> 5), boff = ((lane >> 5) * NW + (TM == 64 ? (wave >> 1) * 32 : 0) + (lane & 31)) * 4;
     const float* aLane = sA + aoff;
     const float* bCol = sB + boff;
 
@@ -787,24 +850,24 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
         const float* aRow = aLane + (MODE == 0 ? kw : 2 - kw) * LDA;
         float4 av = *reinterpret_cast<const float4*>(aRow);
         float4 b0 = *reinterpret_cast<const float4*>(bCol);
-        float4 b1 = NW == 64 ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
+        float4 b1 = TWO ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
 #pragma unroll
         for (int kc = 0; kc < BK / 8; ++kc) {
             float4 an = av, b0n = b0, b1n = b1;
             if (kc + 1 < BK / 8) {
                 an = *reinterpret_cast<const float4*>(aRow + (kc + 1) * 8);
                 b0n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4);
-                if (NW == 64) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
+                if (TWO) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
             }
             __builtin_amdgcn_sched_barrier(0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b0.y, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b0.z, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, acc1, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, acc0, 0, 0, 0);
-            if (NW == 64) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, acc1, 0, 0, 0);
+            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, acc1, 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             av = an; b0 = b0n; b1 = b1n;
         }
@@ -818,7 +881,7 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
     IGEMM_STAMP(3);
     if (stamps && threadIdx.x == 0 && stamp_wg < 8192) stamps[(size_t)stamp_wg * 8 + 5] = (unsigned long long)stamp_steps;
     if (nsplit > 1) {
-        const bool last = splitk_arrive<DB>(acc0, acc1, partial, nsplit, (mb - tile0) * gridDim.y + blockIdx.y,
+        const bool last = splitk_arrive<DB, TM == 64 ? 4 : 8>(acc0, acc1, partial, nsplit, (mb - tile0) * gridDim.y + blockIdx.y,
                                         gridDim.x * gridDim.y, wave, lane);
         IGEMM_STAMP(7);
         if (!last) { IGEMM_STAMP(4); return; }
@@ -864,7 +927,9 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
         IGEMM_STAMP(4);
         return;
     }
-    store_tile(g, acc0, acc1, smem, m0 + wave * 32, n0, mb, mlimit, wave, lane, tid, bias, flags, out, stats, true, NW == 32);
+    store_tile<TM>(g, acc0, acc1, smem, m0 + (TM == 64 ? wave & 1 : wave) * 32, n0, mb, mlimit, wave, lane, tid, bias, flags, out, stats,
+                   true, NW == 32, 0, nullptr, TM == 64 ? partial : nullptr,
+                   TM == 64 && partial ? partial + kSplitCounters + (nsplit > 1 ? (size_t)nsplit * gridDim.x * gridDim.y * (64 * 64) : 0) : nullptr);
     IGEMM_STAMP(4);
 }
 
@@ -894,6 +959,33 @@ k_igemm_halo(ConvGeom g, const float* __restrict__ in, const float* __restrict__
     __syncthreads();                                  // the epilogue's statistics scratch is the next tile's staging area
     halo_tile<MODE, XF, NSEG, NW, false, TAIL>(g, in, wp, bias, in_bn, flags, out, stats, nsplit, partial, tile0,
                                                (2 * q + 1) * g.plane_tiles + i, smem, stamps, stamp_wg);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Small tile: 64 positions x 64 channels per workgroup on the two-image (DB) loop, for the K-sliced layers of few tiles
+// (RPN blocks 2 and 3, 5 000 x 128 and 1 250 x 256: forward layers and stride-1 data gradients).  As 128-row tiles those run one workgroup per
+// CU, one wave per SIMD, and nothing covers a workgroup's prologue, staging, slab store or combine.  With 64 rows the map
+// gives twice the tiles at the SAME K slicing: two workgroups per CU (69 760 B of LDS each at most), a second wave on
+// every SIMD, slabs of half the size.  Every wave holds one 32 x 32 accumulator (32 MFMAs per step).  Each element's fmaf
+// chain and the slice-order sum are those of the 128-row tile: the output is bit for bit the same.
+// NSEG = 0: igemm_tile; 2: halo_tile (Wo >= 64: a 64-row tile touches at most two lines).  A kernel of its own so that the
+// launch bounds of k_igemm / k_igemm_halo stay what they are.
+template <int MODE, bool XF, int NSEG>
+__global__ void __launch_bounds__(kThreads, 2)          // two workgroups per CU = two waves per SIMD: <= 256 registers
+k_igemm_small(ConvGeom g, const float* __restrict__ in, const float* __restrict__ wp,
+              const float* __restrict__ bias, const float* __restrict__ in_bn, int flags,
+              float* __restrict__ out, double* __restrict__ stats, int nsplit, float* __restrict__ partial, int tile0) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    unsigned long long* stamps = g_igemm_stamps;
+    const unsigned stamp_wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    IGEMM_STAMP(0);
+    const int v = tile0 + xcd_remap(blockIdx.x, gridDim.x);
+    if constexpr (NSEG != 0)
+        halo_tile<MODE, XF, NSEG, 64, true, false, false, 64>(g, in, wp, bias, in_bn, flags, out, stats, nsplit, partial,
+                                                                         tile0, v, smem, stamps, stamp_wg);
+    else
+        igemm_tile<MODE, XF, 64, true, false, 64>(g, in, wp, bias, in_bn, flags, out, stats, nsplit, partial, tile0, v, smem,
+                                                  stamps, stamp_wg);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1589,6 +1681,7 @@ struct ConvCall {
     size_t ws_bytes;
     bool xf;
     bool db;                     // the K-sliced launch runs the two-image (double-buffered) kernels, one workgroup per CU
+    int tm;                      // rows per tile: BM, or 64 (k_igemm_small; ntiles then counts 64-row tiles)
     int kernel, cols;            // LISEC_KERNEL_*; output channels per workgroup
     double* stats;               // per-tile table (or the dummy that keeps the statistics paths on under a sink)
     ConvLaunch launch[2];
@@ -1622,6 +1715,7 @@ struct TileVariant {
     bool tail = false;           // second contraction on the stored tile (two-line halo, 64 columns)
     bool fold = false;           // BatchNormalization backward on load (mode 1, no XF)
     bool roofline = false;       // the TAG = 1 symbols (no XF; halo with two lines only)
+    int tm = BM;                 // 64: k_igemm_small (two images, 64 columns, nseg 0 or 2, none of the switches above)
 };
 
 template <int M, bool X>
@@ -1655,7 +1749,15 @@ TileKernel roofline_kernel(int mode, int nseg) {
     if (nseg) return mode == 0 ? k_igemm_halo<0, false, 1, 2> : k_igemm_halo<1, false, 1, 2>;
     return mode == 0 ? k_igemm<0, false, 1> : k_igemm<1, false, 1>;
 }
+TileKernel small_kernel(int mode, bool xf, int nseg) {
+    return with_mode_xf(mode, xf, [&](auto m, auto x) -> TileKernel {
+        constexpr int M = decltype(m)::value;
+        constexpr bool X = decltype(x)::value;
+        return nseg ? k_igemm_small<M, X, 2> : k_igemm_small<M, X, 0>;
+    });
+}
 TileKernel tile_kernel(const TileVariant& v) {
+    if (v.tm == 64) return small_kernel(v.mode, v.xf, v.nseg);
     if (v.roofline) return roofline_kernel(v.mode, v.nseg);
     if (v.fold) return fold_kernel(v.nseg, v.cols, v.db);
     return with_mode_xf(v.mode, v.xf, [&](auto m, auto x) -> TileKernel {
@@ -1680,12 +1782,14 @@ ResidentKernel dense64_kernel(bool xf, bool bwd, bool dw) {
     if (bwd) return xf ? k_dense64<true, true> : k_dense64<false, true>;
     return xf ? k_dense64<true, false> : k_dense64<false, false>;
 }
-constexpr size_t tile_lds_bytes(int nseg) { return nseg ? halo_lds_bytes(nseg) : (size_t)(A_FLOATS + B_FLOATS) * sizeof(float); }
+constexpr size_t tile_lds_bytes(int nseg, int tm = BM) {
+    return nseg ? halo_lds_bytes(nseg, tm) : (size_t)(tm * LDA + B_FLOATS) * sizeof(float);
+}
 
 void plan_slices(const ConvGeom& g, ConvCall* p) {
     const lisec_tuning& tn = tuning();
     const int ntiles = cdiv(g.M, BM), nnb = g.CoutP / BN;
-    p->tile0_tail = ntiles; p->nsplit = 1; p->ws_bytes = 0; p->db = false;
+    p->tile0_tail = ntiles; p->nsplit = 1; p->ws_bytes = 0; p->db = false; p->tm = BM;
     const int nsteps = g.KD * g.KH * g.KW * cdiv(g.Cin, BK);
     if (g.ps || g.Cout % 4 != 0 || g.out_stride % 4 != 0 || nsteps < 6) return;
     const int slots = resident_slots();
@@ -1712,12 +1816,24 @@ void plan_slices(const ConvGeom& g, ConvCall* p) {
         int nd = (int)((slots / 3) / tail_blocks);
         if (nd > nsteps / tn.splitk_min_steps) nd = nsteps / tn.splitk_min_steps;
         if (nd > tn.max_splitk) nd = tn.max_splitk;
+        if (tn.force_splitk > 0) nd = ns;           // measurement aid: holds for the lone form too
         if (nd >= 2) { ns = nd; p->db = true; }
+        // 64-row tiles (k_igemm_small) for such a layer: the SAME slices -- so every element keeps its sum order -- over
+        // twice the tiles, two workgroups per CU.  A candidate here; plan_conv keeps it for the calls the kernel serves
+        if (tn.small_tile && g.Cout % BN == 0 && !g.pc_span) p->tm = 64;
     }
-    if (ns < 2 || ns < tn.min_splitk) { p->db = false; return; }
+    // a 64-row candidate: room for whichever tile height plan_conv settles on, and 256 floats per 64-row workgroup where the
+    // two halves of a 128-row tile meet for the statistics sink (store_tile)
+    const size_t pair_floats = p->tm == 64 ? (size_t)cdiv(g.M, 64) * nnb * 256 : 0;
+    if (ns < 2 || ns < tn.min_splitk) {
+        p->db = false;
+        if (p->tm == 64) p->ws_bytes = align_up(sizeof(int) * kSplitCounters + sizeof(float) * pair_floats, 256);
+        return;
+    }
     p->tile0_tail = ntiles - tail_tiles;
     p->nsplit = ns;
-    p->ws_bytes = align_up(sizeof(int) * kSplitCounters + sizeof(float) * (size_t)ns * tail_tiles * nnb * BM * BN, 256);
+    const size_t rows = p->tm == 64 && cdiv(g.M, 64) * 64 > tail_tiles * BM ? (size_t)cdiv(g.M, 64) * 64 : (size_t)tail_tiles * BM;
+    p->ws_bytes = align_up(sizeof(int) * kSplitCounters + sizeof(float) * ((size_t)ns * rows * nnb * BN + pair_floats), 256);
 }
 
 // The 128 x 128 tile (k_igemm_wide): layers of 128 (256, ...) output channels on the two-line w-halo geometry whose 128-row
@@ -1800,8 +1916,15 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
     plan_slices(g, p);
     const int ntiles = p->ntiles = cdiv(g.M, BM), nnb = p->nnb = g.CoutP / BN;
     const auto unsliced = [&] { p->tile0_tail = ntiles; p->nsplit = 1; p->db = false; };
-    if (!workspace || workspace_bytes < p->ws_bytes) unsliced();
+    const bool ws_ok = workspace && workspace_bytes >= p->ws_bytes;
+    if (!ws_ok) unsliced();
     const bool roofline = (flags & LISEC_CONV_TAG_ROOFLINE) != 0;
+    // 64-row tiles: asked for by the caller (LISEC_CONV_SMALL_TILE), a candidate of plan_slices, and none of what
+    // k_igemm_small does not serve: the per-tile statistics table (laid out for 128-row tiles), BatchNormalization backward
+    // on load, the tail contraction, row lists, parity classes, pixel-shuffle stores, the roofline symbols
+    const bool small = (flags & LISEC_CONV_SMALL_TILE) && p->tm == 64 && !table_stats && !g.in_y && !(extras && extras->tail_w) &&
+                       !row_coords && !g.pc_span && !g.ps && !roofline && (!sk || ws_ok);   // (a sink: the tile pairs meet in the workspace)
+    p->tm = BM;
     if (row_coords && !g.in_y && extras && extras->queue && nnb == 1 && ntiles >= resident_slots() && !stats_partials && !g.out_mask &&
         !roofline) {
         g.queue = extras->queue;                     // one un-sliced launch of resident workgroups drawing tiles
@@ -1838,7 +1961,7 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
     // a launch of the tile family over every tile (half as many workgroups with plane_pair), or over the tiles from `tile0`
     TileVariant v{c->mode, p->xf, 0};
     const auto add_tile = [&](dim3 grid, int nsplit = 1, int tile0 = 0) {
-        ConvLaunch& l = p->add(ConvLaunch::TILE, grid, kThreads, (v.db ? 2 : 1) * tile_lds_bytes(v.nseg));
+        ConvLaunch& l = p->add(ConvLaunch::TILE, grid, kThreads, (v.db ? 2 : 1) * tile_lds_bytes(v.nseg, v.tm));
         l.tile = tile_kernel(v);
         l.nsplit = nsplit; l.tile0 = tile0; l.partial = nsplit > 1;
     };
@@ -1904,6 +2027,20 @@ int plan_conv(const lisec_conv_geom* c, bool has_in_bn, int flags, const lisec_c
         p->add(ConvLaunch::RESIDENT, dim3(resident_slots()), kThreads, tile_lds_bytes(0)).resident = queue_kernel(c->mode, p->xf);
         return LISEC_OK;
     }
+    if (small) {
+        // one launch of every 64-row tile on the two-image loop, K sliced as the 128-row plan would be (or not at all)
+        const int nt64 = cdiv(g.M, 64);
+        p->tm = 64; p->ntiles = nt64; p->db = true;
+        p->tile0_tail = p->nsplit > 1 ? 0 : nt64;
+        g.plane_pair = 0;
+        if (sk) g.sink.total = (unsigned)nt64 * (unsigned)nnb;
+        v.tm = 64; v.db = true; v.fold = false;
+        v.nseg = v.nseg ? 2 : 0;                     // Wo >= 64: at most two lines per 64-row tile
+        p->kernel = v.nseg ? LISEC_KERNEL_HALO2 : LISEC_KERNEL_IGEMM;
+        add_tile(dim3(nt64, nnb, p->nsplit), p->nsplit, 0);
+        if (sk) p->launch[p->nlaunch - 1].partial = true;
+        return LISEC_OK;
+    }
     p->kernel = v.nseg == 3 ? LISEC_KERNEL_HALO3 : (v.nseg ? LISEC_KERNEL_HALO2 : LISEC_KERNEL_IGEMM);
     // a layer that would run as two K slices (160-380 tiles): 32-column workgroups over the whole K instead -- as many
     // workgroups, no slabs
@@ -1966,6 +2103,7 @@ extern "C" int lisec_conv_plan_query(const lisec_conv_geom* c, int has_in_bnstat
     out->plane_pair = p.g.plane_pair;
     out->parity_classes = p.g.pc_span ? 1 : 0;
     out->double_buffered = p.db ? 1 : 0;
+    out->tile_rows = p.tm;
     out->workgroups = 0;
     for (int i = 0; i < p.nlaunch; ++i) out->workgroups += (int)(p.launch[i].grid.x * p.launch[i].grid.y * p.launch[i].grid.z);
     out->launches = p.nlaunch;

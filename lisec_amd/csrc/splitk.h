@@ -1,5 +1,5 @@
-// Internal: the in-kernel meeting point of the K slices of one 128 x 64 tile, shared by the implicit-GEMM kernels
-// (igemm.hip, igemm_bf16.hip).
+// Internal: the in-kernel meeting point of the K slices of one 128 x 64 (or 64 x 64) tile, shared by the implicit-GEMM
+// kernels (igemm.hip, igemm_bf16.hip).
 #pragma once
 #include "common.h"
 
@@ -22,19 +22,22 @@ constexpr int kSplitCounters = 4096;             // arrival counters at the head
 constexpr int kSlabF4 = 4 * 8 * 64;              // float4 per (slice, tile, column block): 128 x 64 floats
 
 // DEEP: three slabs in flight in the last arriver's combine (the two-image kernels: one workgroup per CU, registers to spare)
-template <bool DEEP = false>
+// NQ: sixteen-byte stores per lane and slab.  8 = both accumulators of a wave (128 x 64 tile); 4 = acc0 alone (the 64 x 64
+// tile: slab[z][slot][wave][q][lane] with q < 4, half the slab, stride and combine traffic); acc1 is then not touched.
+template <bool DEEP = false, int NQ = 8>
 __device__ __forceinline__ bool splitk_arrive(f32x16& acc0, f32x16& acc1, float* partial, int nsplit, int slot, int nslots,
                                               int wave, int lane) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     __shared__ int splitk_last;
     int* counters = reinterpret_cast<int*>(partial);
     float* slabs = partial + kSplitCounters;
-    const size_t bytes = (size_t)nsplit * nslots * kSlabF4 * 16;
+    constexpr int kSlab = 4 * NQ * 64;           // float4 per (slice, tile, column block): kSlabF4 for NQ = 8
+    const size_t bytes = (size_t)nsplit * nslots * kSlab * 16;
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slabs, 0, (int)bytes, 0x00020000);
-    const unsigned lane_off = (unsigned)((wave * 8) * 64 + lane) * 16u;
-    const unsigned mine = (unsigned)(((size_t)blockIdx.z * nslots + slot) * kSlabF4 * 16) + lane_off;
+    const unsigned lane_off = (unsigned)((wave * NQ) * 64 + lane) * 16u;
+    const unsigned mine = (unsigned)(((size_t)blockIdx.z * nslots + slot) * kSlab * 16) + lane_off;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    for (int q = 0; q < NQ; ++q) {
         const f32x16& a = q < 4 ? acc0 : acc1;
         const int r = (q & 3) * 4;
         u32x4 v;
@@ -49,36 +52,37 @@ __device__ __forceinline__ bool splitk_arrive(f32x16& acc0, f32x16& acc1, float*
     if (!splitk_last) return false;
     if (threadIdx.x == 0) __hip_atomic_store(counters + slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     f32x16 s0 = {0}, s1 = {0};
-    const unsigned zstride = (unsigned)((size_t)nslots * kSlabF4 * 16);
-    unsigned off = (unsigned)((size_t)slot * kSlabF4 * 16) + lane_off;
+    const unsigned zstride = (unsigned)((size_t)nslots * kSlab * 16);
+    unsigned off = (unsigned)((size_t)slot * kSlab * 16) + lane_off;
     // three slabs in flight at a time (24 sixteen-byte loads), added in slice order: one memory round trip per three slices
     // instead of one per slice -- the combine sits on the serial chain of every K-sliced RPN layer
     int z = 0;
     for (; DEEP && z + 3 <= nsplit; z += 3, off += 3 * zstride) {
-        u32x4 v[24];
+        u32x4 v[3 * NQ];
 #pragma unroll
-        for (int q = 0; q < 24; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + (q >> 3) * zstride + (q & 7) * 64 * 16, 0, 16);
+        for (int q = 0; q < 3 * NQ; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + (q / NQ) * zstride + (q % NQ) * 64 * 16, 0, 16);
 #pragma unroll
-        for (int q = 0; q < 24; ++q) {
-            f32x16& a = (q & 7) < 4 ? s0 : s1;
+        for (int q = 0; q < 3 * NQ; ++q) {
+            f32x16& a = (q % NQ) < 4 ? s0 : s1;
             const int r = (q & 3) * 4;
             a[r] += __uint_as_float(v[q].x); a[r + 1] += __uint_as_float(v[q].y);
             a[r + 2] += __uint_as_float(v[q].z); a[r + 3] += __uint_as_float(v[q].w);
         }
     }
     for (; z < nsplit; ++z, off += zstride) {
-        u32x4 v[8];
+        u32x4 v[NQ];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + q * 64 * 16, 0, 16);
+        for (int q = 0; q < NQ; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + q * 64 * 16, 0, 16);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
+        for (int q = 0; q < NQ; ++q) {
             f32x16& a = q < 4 ? s0 : s1;
             const int r = (q & 3) * 4;
             a[r] += __uint_as_float(v[q].x); a[r + 1] += __uint_as_float(v[q].y);
             a[r + 2] += __uint_as_float(v[q].z); a[r + 3] += __uint_as_float(v[q].w);
         }
     }
-    acc0 = s0; acc1 = s1;
+    acc0 = s0;
+    if (NQ == 8) acc1 = s1;
     return true;
 }
 

@@ -275,8 +275,8 @@ class _BackwardPass:
             ops.conv_forward_winograd(net.dgeom[c.name], dy, net.packed_wu_t[c.name], d[dst_name], flags=flags,
                                       out_mask=mask, bwd=bwd, sink=sink, tail=tail)
         else:
-            ops.conv_forward(net.dgeom[c.name], dy, net.packed_t[c.name][0], d[dst_name], flags=flags, out_mask=mask,
-                             bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail)
+            ops.conv_forward(net.dgeom[c.name], dy, net.packed_t[c.name][0], d[dst_name], flags=flags | ops.SMALL_TILE,
+                             out_mask=mask, bwd=bwd, sink=sink, ws_tag=ws_tag, tail=tail)
         self.first_write.add(dst_name)
 
     def branch_dy(self, L):
@@ -823,7 +823,8 @@ class LisecNet:
                                       in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=flags, sink=sink)
         else:
             ops.conv_forward(c.g, x, self.packed[c.name], out, bias=p.view(c.bias) if c.bias else None,
-                             in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=flags, sink=sink, ws_tag=ws_tag)
+                             in_bn=self.bnstate[c.in_bn] if c.in_bn else None, flags=flags | ops.SMALL_TILE, sink=sink,
+                             ws_tag=ws_tag)
         if c.bn:
             self._bn_after(c, training)
 

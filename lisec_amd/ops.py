@@ -8,7 +8,9 @@ import torch
 from . import _lib
 from ._lib import ConvGeom
 
-IN_RELU, OUT_RELU, ACCUMULATE, DY_RELU, TAG_ROOFLINE = 1, 2, 4, 8, 32
+IN_RELU, OUT_RELU, ACCUMULATE, DY_RELU, SMALL_TILE, TAG_ROOFLINE = 1, 2, 4, 8, 16, 32
+# SMALL_TILE (conv_forward / conv_plan): a small K-sliced layer may run as 64-row tiles, two workgroups per CU
+# (LISEC_CONV_SMALL_TILE; the plan reports tile_rows).  Same output bit for bit.
 
 
 def geom(mode, in_dims, out_dims, kernel, stride, pad, cin, cout, in_stride=None, out_stride=None, ps=0,

@@ -1,5 +1,8 @@
 """Phase timing inside the contraction kernels on the small RPN maps (100 MHz stamps of every workgroup), launched the
-way the training forward launches them: BatchNormalization(+ReLU) on load, batch statistics into a sink, default plan."""
+way the training forward launches them: BatchNormalization(+ReLU) on load, batch statistics into a sink, default plan
+(LISEC_CONV_SMALL_TILE passed, as the training step passes it).
+`python tools/rpn_stamps.py ab`: the stride-1 layers of RPN blocks 2 and 3, forward and data gradient, with
+lisec_tuning.small_tile = 0 (128-row tiles) against 1 (64-row tiles) in one process."""
 import ctypes
 import os
 import sys
@@ -26,7 +29,9 @@ def case(name, mode, ind, outd, k, s, p, cin, cout, in_bn=True, sink=True, iters
     if sink:
         gam, bet = torch.ones(cout, device=dev), torch.zeros(cout, device=dev)
         sk = ops.BnSink(cout, M, dev, gamma=gam, beta=bet, bnstate=torch.zeros(4 * cout, device=dev))
-    fl = ops.IN_RELU if in_bn else 0
+    fl = (ops.IN_RELU if in_bn else 0) | ops.SMALL_TILE
+    plan = ops.conv_plan(g, in_bn=in_bn, flags=fl, sink=sk)
+    print(f"{name}: plan {plan['kernel']} tile_rows {plan['tile_rows']} k_slices {plan['k_slices']} workgroups {plan['workgroups']}")
     run = lambda: ops.conv_forward(g, x, wp, out, in_bn=bn, flags=fl, sink=sk)
     for _ in range(3):
         run()
@@ -100,6 +105,19 @@ def case(name, mode, ind, outd, k, s, p, cin, cout, in_bn=True, sink=True, iters
 
 if __name__ == "__main__":
     only = sys.argv[1:]
+    if only == ["ab"]:
+        for rep in range(2):                             # each setting twice, alternating
+            for small in (0, 1):
+                _lib.set_tuning(small_tile=small)
+                print(f"==== small_tile={small} (pass {rep})")
+                case("rpn2.conv1 128->128 (5000)", 0, (1, 50, 100), (1, 50, 100), (1, 3, 3), (1, 1, 1), (0, 1, 1), 128, 128)
+                case("rpn3.conv1 256->256 (1250)", 0, (1, 25, 50), (1, 25, 50), (1, 3, 3), (1, 1, 1), (0, 1, 1), 256, 256)
+                case("rpn2.conv1 dgrad (5000)", 1, (1, 50, 100), (1, 50, 100), (1, 3, 3), (1, 1, 1), (0, 1, 1), 128, 128, in_bn=False, sink=False)
+                case("rpn3.conv1 dgrad (1250)", 1, (1, 25, 50), (1, 25, 50), (1, 3, 3), (1, 1, 1), (0, 1, 1), 256, 256, in_bn=False, sink=False)
+                # the stride-2 layers that open the blocks: sliced as a whole too, so the planner moves them as well
+                case("rpn2.conv0 s2 128->128 (5000)", 0, (1, 100, 200), (1, 50, 100), (1, 3, 3), (1, 2, 2), (0, 1, 1), 128, 128)
+                case("rpn3.conv0 s2 128->256 (1250)", 0, (1, 50, 100), (1, 25, 50), (1, 3, 3), (1, 2, 2), (0, 1, 1), 128, 256)
+        sys.exit(0)
     if only:
         _case = case
         case = lambda name, *a, **k: _case(name, *a, **k) if any(o in name for o in only) else None
