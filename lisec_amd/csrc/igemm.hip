@@ -21,8 +21,12 @@
 // for the K-sliced layers of few tiles -- one 32 x 32 accumulator per wave, two double-buffered workgroups per CU.
 // fp32 in / fp32 accumulate: bit-for-bit an fmaf chain, so parity with the fp32 oracle holds to
 // summation-order noise (no reduced precision anywhere).
+// Where the pieces live: this file holds the kernels' step walkers, staging maps, the epilogue (store_tile) and the host
+// side (plan_conv and the launch list); tile_parts.h the on-load transforms of a staged float4 (affine_relu, bn_fold), the
+// W-slab copy (wslab_load / wslab_store) and the 64-deep MFMA step (mfma_step64), shared with wgrad.hip; splitk.h the
+// meeting of the K slices (slab_store, slice_ticket, slab_sum; splitk_arrive for a tile); conv.h the gather geometry.
 #include "conv.h"
-#include "splitk.h"
+#include "tile_parts.h"
 
 
 namespace lisec {
@@ -356,18 +360,7 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
             tsh = *reinterpret_cast<const float4*>(in_bn + g.Cin + cs);
         }
         const float* wb = wp + ((size_t)(tap * KpQ + cc * (BK / 4)) * g.CoutP + n0) * 4;
-        if (NW == 64) {
-            const float* wl = wb + (size_t)(tid >> 6) * g.CoutP * 4 + (tid & 63) * 4;
-            const size_t wstep = (size_t)4 * g.CoutP * 4;
-            rb0 = *reinterpret_cast<const float4*>(wl);
-            rb1 = *reinterpret_cast<const float4*>(wl + wstep);
-            rb2 = *reinterpret_cast<const float4*>(wl + 2 * wstep);
-            rb3 = *reinterpret_cast<const float4*>(wl + 3 * wstep);
-        } else {                                                     // 16 k-quads x 32 columns: two float4 per thread
-            const float* wl = wb + (size_t)(tid >> 5) * g.CoutP * 4 + (tid & 31) * 4;
-            rb0 = *reinterpret_cast<const float4*>(wl);
-            rb1 = *reinterpret_cast<const float4*>(wl + (size_t)8 * g.CoutP * 4);
-        }
+        wslab_load<NW>(wb, g.CoutP, tid, rb0, rb1, rb2, rb3);
     };
     const float relu_lo = (flags & LISEC_CONV_IN_RELU) ? 0.f : -INFINITY;
     auto store_lds = [&]() {
@@ -376,37 +369,12 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
         for (int p = 0; p < NP; ++p) {
             float4 v = ra[p];
             const bool ok = (valid_mask >> p) & 1;
-            if (FOLD) {
-                const float4 y = ry[p];
-#define LISEC_FOLD(f)                                                                                          \
-                {                                                                                              \
-                    float dz = v.f;                                                                            \
-                    if (g.fold_relu && !(fmaf(y.f, tsc.f, tsh.f) > 0.f)) dz = 0.f;                             \
-                    v.f = ok ? tsc.f * (dz - fm1.f - (y.f - fmu.f) * fis.f * fm2.f) : 0.f;                     \
-                }
-                LISEC_FOLD(x) LISEC_FOLD(y) LISEC_FOLD(z) LISEC_FOLD(w)
-#undef LISEC_FOLD
-            } else if (XF) {
-                v.x = ok ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-                v.y = ok ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-                v.z = ok ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-                v.w = ok ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
-            } else {
-                v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-            }
+            if (FOLD) bn_fold(v, ry[p], tsc, tsh, fmu, fis, fm1, fm2, g.fold_relu, ok);
+            else if (XF) affine_relu(v, tsc, tsh, relu_lo, ok);
+            else masked(v, ok);
             *reinterpret_cast<float4*>(sA + (p * 16 + (tid >> 4)) * LDA + piece * 4) = v;
         }
-        if (NW == 64) {
-            float* bl = sB + ((tid >> 6) * BN + (tid & 63)) * 4;
-            *reinterpret_cast<float4*>(bl) = rb0;
-            *reinterpret_cast<float4*>(bl + 4 * BN * 4) = rb1;
-            *reinterpret_cast<float4*>(bl + 8 * BN * 4) = rb2;
-            *reinterpret_cast<float4*>(bl + 12 * BN * 4) = rb3;
-        } else {
-            float* bl = sB + ((tid >> 5) * 32 + (tid & 31)) * 4;
-            *reinterpret_cast<float4*>(bl) = rb0;
-            *reinterpret_cast<float4*>(bl + 8 * 32 * 4) = rb1;
-        }
+        wslab_store<NW>(sB, tid, rb0, rb1, rb2, rb3);
     };
 
     f32x16 acc0 = {0}, acc1 = {0};
@@ -482,35 +450,7 @@ igemm_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restr
             nxt = next_of(cur);
             if (nxt.s < nsteps) issue_loads(nxt);
         }
-        // software-pipelined fragment reads: the ds_reads of chunk kc+1 are issued BEFORE the 8 MFMAs of chunk kc
-        // (sched_barrier pins that order; left alone hipcc reuses the fragment registers and issues the reads
-        // after the MFMAs, exposing ~100 cycles of LDS latency per 512 MFMA cycles)
-        // no scalar load may be pending when the fragment reads start: LDS returns in order, scalar memory does not, and with
-        // an s_load in flight (the geometry lives in the kernel-argument segment) the compiler must wait for EVERY LDS read
-        // -- lgkmcnt(0), the reads of the NEXT chunk included -- before each group of MFMAs instead of the older ones only
-        float4 a = *reinterpret_cast<const float4*>(aRow);
-        float4 b0 = *reinterpret_cast<const float4*>(bCol);
-        float4 b1 = TWO ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
-#pragma unroll
-        for (int kc = 0; kc < BK / 8; ++kc) {
-            float4 an = a, b0n = b0, b1n = b1;
-            if (kc + 1 < BK / 8) {
-                an = *reinterpret_cast<const float4*>(aRow + (kc + 1) * 8);
-                b0n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4);
-                if (TWO) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
-            }
-            __builtin_amdgcn_sched_barrier(0);                        // reads of chunk kc+1 stay above ...
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b0.x, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b1.x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b0.y, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b1.y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b0.z, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b1.z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b0.w, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b1.w, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);                        // ... the 8 MFMAs of chunk kc
-            a = an; b0 = b0n; b1 = b1n;
-        }
+        mfma_step64<TWO, NW>(aRow, bCol, acc0, acc1);
         __syncthreads();
         if (!DB) {
             if (nxt.s < nsteps) store_lds();
@@ -715,18 +655,7 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
         }
         const int tap = (kd * g.KH + kh) * 3 + kw;
         const float* wb = wp + ((size_t)(tap * KpQ + cc * (BK / 4)) * g.CoutP + n0) * 4;
-        if (NW == 64) {
-            const float* wl = wb + (size_t)(tid >> 6) * g.CoutP * 4 + (tid & 63) * 4;
-            const size_t wstep = (size_t)4 * g.CoutP * 4;
-            rb0 = *reinterpret_cast<const float4*>(wl);
-            rb1 = *reinterpret_cast<const float4*>(wl + wstep);
-            rb2 = *reinterpret_cast<const float4*>(wl + 2 * wstep);
-            rb3 = *reinterpret_cast<const float4*>(wl + 3 * wstep);
-        } else {                                                     // 16 k-quads x 32 columns: two float4 per thread
-            const float* wl = wb + (size_t)(tid >> 5) * g.CoutP * 4 + (tid & 31) * 4;
-            rb0 = *reinterpret_cast<const float4*>(wl);
-            rb1 = *reinterpret_cast<const float4*>(wl + (size_t)8 * g.CoutP * 4);
-        }
+        wslab_load<NW>(wb, g.CoutP, tid, rb0, rb1, rb2, rb3);
     };
     const float relu_lo = (flags & LISEC_CONV_IN_RELU) ? 0.f : -INFINITY;
     auto store_lds = [&]() {
@@ -735,39 +664,14 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
             for (int p = 0; p < NP; ++p) {
                 float4 v = ra[p];
                 const bool ok = (valid_mask >> p) & 1;
-                if (FOLD) {
-                    const float4 y = ry[p];
-#define LISEC_FOLD(f)                                                                                          \
-                    {                                                                                          \
-                        float dz = v.f;                                                                        \
-                        if (g.fold_relu && !(fmaf(y.f, tsc.f, tsh.f) > 0.f)) dz = 0.f;                         \
-                        v.f = ok ? tsc.f * (dz - fm1.f - (y.f - fmu.f) * fis.f * fm2.f) : 0.f;                 \
-                    }
-                    LISEC_FOLD(x) LISEC_FOLD(y) LISEC_FOLD(z) LISEC_FOLD(w)
-#undef LISEC_FOLD
-                } else if (XF) {
-                    v.x = ok ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-                    v.y = ok ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-                    v.z = ok ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-                    v.w = ok ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
-                } else {
-                    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-                }
+                if (FOLD) bn_fold(v, ry[p], tsc, tsh, fmu, fis, fm1, fm2, g.fold_relu, ok);
+                else if (XF) affine_relu(v, tsc, tsh, relu_lo, ok);
+                else masked(v, ok);
                 const int j = p * 16 + (tid >> 4);
                 if (j < HALO_MAX_ROWS) *reinterpret_cast<float4*>(sA + j * LDA + piece * 4) = v;
             }
         }
-        if (NW == 64) {
-            float* bl = sB + ((tid >> 6) * BN + (tid & 63)) * 4;
-            *reinterpret_cast<float4*>(bl) = rb0;
-            *reinterpret_cast<float4*>(bl + 4 * BN * 4) = rb1;
-            *reinterpret_cast<float4*>(bl + 8 * BN * 4) = rb2;
-            *reinterpret_cast<float4*>(bl + 12 * BN * 4) = rb3;
-        } else {
-            float* bl = sB + ((tid >> 5) * 32 + (tid & 31)) * 4;
-            *reinterpret_cast<float4*>(bl) = rb0;
-            *reinterpret_cast<float4*>(bl + 8 * 32 * 4) = rb1;
-        }
+        wslab_store<NW>(sB, tid, rb0, rb1, rb2, rb3);
     };
 
     f32x16 acc0 = {0}, acc1 = {0};
@@ -847,30 +751,7 @@ halo_tile(const ConvGeom& g, const float* __restrict__ in, const float* __restri
             nxt = next_of(cur);
             if (nxt.s < nsteps) issue_loads(nxt);
         }
-        const float* aRow = aLane + (MODE == 0 ? kw : 2 - kw) * LDA;
-        float4 av = *reinterpret_cast<const float4*>(aRow);
-        float4 b0 = *reinterpret_cast<const float4*>(bCol);
-        float4 b1 = TWO ? *reinterpret_cast<const float4*>(bCol + 32 * 4) : b0;
-#pragma unroll
-        for (int kc = 0; kc < BK / 8; ++kc) {
-            float4 an = av, b0n = b0, b1n = b1;
-            if (kc + 1 < BK / 8) {
-                an = *reinterpret_cast<const float4*>(aRow + (kc + 1) * 8);
-                b0n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4);
-                if (TWO) b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * NW * 4 + 32 * 4);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b0.y, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b0.z, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, acc0, 0, 0, 0);
-            if (TWO) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            av = an; b0 = b0n; b1 = b1n;
-        }
+        mfma_step64<TWO, NW>(aLane + (MODE == 0 ? kw : 2 - kw) * LDA, bCol, acc0, acc1);
         __syncthreads();
         if (!DB) {
             if (nxt.s < nsteps) store_lds();
@@ -995,55 +876,11 @@ k_igemm_small(ConvGeom g, const float* __restrict__ in, const float* __restrict_
 // latency per step (80 us for 5.9 GFLOP, 0.47).  Here eight waves share one A tile: wave (rg, ch) owns rows 32 rg .. and
 // columns 64 ch .. (two accumulators, the inner loop of halo_tile), the W slab is 64 x 128, and two workgroups per CU
 // (68 KB of LDS each) put four waves on every SIMD, so one wave's staging hides behind the others' MFMAs.  K is sliced by
-// whole A tiles as in halo_tile; the slices meet through splitk_arrive_wide.
+// whole A tiles as in halo_tile; the slices meet through splitk_arrive with eight waves.
 constexpr int kWideThreads = 512;
 constexpr int WB_FLOATS = BK * 128;
 constexpr int kWideSlabF4 = 8 * 8 * 64;          // float4 per (slice, tile): 8 waves x 8 x 64 lanes = 128 x 128 floats
 constexpr size_t wide_lds_bytes() { return (size_t)(halo_rows(2) * LDA + WB_FLOATS) * sizeof(float); }   // 68 672 B: 2 per CU
-
-__device__ __forceinline__ bool splitk_arrive_wide(f32x16& acc0, f32x16& acc1, float* partial, int nsplit, int slot, int nslots,
-                                                   int wave, int lane) {
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    __shared__ int splitk_last_w;
-    int* counters = reinterpret_cast<int*>(partial);
-    float* slabs = partial + kSplitCounters;
-    const size_t bytes = (size_t)nsplit * nslots * kWideSlabF4 * 16;
-    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(slabs, 0, (int)bytes, 0x00020000);
-    const unsigned lane_off = (unsigned)((wave * 8) * 64 + lane) * 16u;
-    const unsigned mine = (unsigned)(((size_t)blockIdx.z * nslots + slot) * kWideSlabF4 * 16) + lane_off;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const f32x16& a = q < 4 ? acc0 : acc1;
-        const int r = (q & 3) * 4;
-        u32x4 v;
-        v.x = __float_as_uint(a[r]); v.y = __float_as_uint(a[r + 1]); v.z = __float_as_uint(a[r + 2]); v.w = __float_as_uint(a[r + 3]);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, mine + q * 64 * 16, 0, 16);          // aux 16 = sc1
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        splitk_last_w = __hip_atomic_fetch_add(counters + slot, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsplit - 1;
-    __syncthreads();
-    if (!splitk_last_w) return false;
-    if (threadIdx.x == 0) __hip_atomic_store(counters + slot, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f32x16 s0 = {0}, s1 = {0};
-    const unsigned zstride = (unsigned)((size_t)nslots * kWideSlabF4 * 16);
-    unsigned off = (unsigned)((size_t)slot * kWideSlabF4 * 16) + lane_off;
-    for (int z = 0; z < nsplit; ++z, off += zstride) {
-        u32x4 v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + q * 64 * 16, 0, 16);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            f32x16& a = q < 4 ? s0 : s1;
-            const int r = (q & 3) * 4;
-            a[r] += __uint_as_float(v[q].x); a[r + 1] += __uint_as_float(v[q].y);
-            a[r + 2] += __uint_as_float(v[q].z); a[r + 3] += __uint_as_float(v[q].w);
-        }
-    }
-    acc0 = s0; acc1 = s1;
-    return true;
-}
 
 template <int MODE, bool XF>
 __global__ void __launch_bounds__(kWideThreads, 4)      // two workgroups per CU = four waves per SIMD: <= 128 registers
@@ -1147,14 +984,8 @@ k_igemm_wide(ConvGeom g, const float* __restrict__ in, const float* __restrict__
             for (int p = 0; p < 5; ++p) {
                 float4 v = ra[p];
                 const bool ok = (valid_mask >> p) & 1;
-                if (XF) {
-                    v.x = ok ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-                    v.y = ok ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-                    v.z = ok ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-                    v.w = ok ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
-                } else {
-                    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-                }
+                if (XF) affine_relu(v, tsc, tsh, relu_lo, ok);
+                else masked(v, ok);
                 const int j = p * 32 + (tid >> 4);
                 if (j < HALO_MAX_ROWS) *reinterpret_cast<float4*>(sA + j * LDA + piece * 4) = v;
             }
@@ -1210,30 +1041,7 @@ k_igemm_wide(ConvGeom g, const float* __restrict__ in, const float* __restrict__
         const int kw = cur.kw;
         const HStep nxt = next_of(cur);
         if (nxt.s < nsteps) issue_loads(nxt);
-        const float* aRow = aLane + (MODE == 0 ? kw : 2 - kw) * LDA;
-        float4 av = *reinterpret_cast<const float4*>(aRow);
-        float4 b0 = *reinterpret_cast<const float4*>(bCol);
-        float4 b1 = *reinterpret_cast<const float4*>(bCol + 32 * 4);
-#pragma unroll
-        for (int kc = 0; kc < BK / 8; ++kc) {
-            float4 an = av, b0n = b0, b1n = b1;
-            if (kc + 1 < BK / 8) {
-                an = *reinterpret_cast<const float4*>(aRow + (kc + 1) * 8);
-                b0n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * 128 * 4);
-                b1n = *reinterpret_cast<const float4*>(bCol + (kc + 1) * 2 * 128 * 4 + 32 * 4);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b0.x, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, b1.x, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b0.y, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, b1.y, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b0.z, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, b1.z, acc1, 0, 0, 0);
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b0.w, acc0, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, b1.w, acc1, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            av = an; b0 = b0n; b1 = b1n;
-        }
+        mfma_step64<true, 128>(aLane + (MODE == 0 ? kw : 2 - kw) * LDA, bCol, acc0, acc1);
         __syncthreads();
         if (nxt.s < nsteps) store_lds();
         __syncthreads();
@@ -1242,7 +1050,7 @@ k_igemm_wide(ConvGeom g, const float* __restrict__ in, const float* __restrict__
     IGEMM_STAMP(3);
     if (stamps && threadIdx.x == 0 && stamp_wg < 8192) stamps[(size_t)stamp_wg * 8 + 5] = (unsigned long long)stamp_steps;
     if (nsplit > 1) {
-        const bool last = splitk_arrive_wide(acc0, acc1, partial, nsplit, mb * gridDim.y + blockIdx.y, gridDim.x * gridDim.y, wave, lane);
+        const bool last = splitk_arrive<false, 8, 8>(acc0, acc1, partial, nsplit, mb * gridDim.y + blockIdx.y, gridDim.x * gridDim.y, wave, lane);
         IGEMM_STAMP(7);
         if (!last) { IGEMM_STAMP(4); return; }
     }
@@ -1318,10 +1126,7 @@ k_dense64(ConvGeom g, const float* __restrict__ in, const float* __restrict__ wp
 #pragma unroll
         for (int p = 0; p < 8; ++p) {
             float4 v = make_float4(__uint_as_float(ra[p].x), __uint_as_float(ra[p].y), __uint_as_float(ra[p].z), __uint_as_float(ra[p].w));
-            if (XF) {
-                v.x = fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo); v.y = fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo);
-                v.z = fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo); v.w = fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo);
-            }
+            if (XF) affine_relu(v, tsc, tsh, relu_lo, true);
             *reinterpret_cast<float4*>(sA + (p * 16 + (tid >> 4)) * LDA + piece * 4) = v;
         }
     };

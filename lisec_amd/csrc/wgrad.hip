@@ -15,12 +15,11 @@
 // bind_wgrad puts the tensors and the workspace in, run_wgrad issues them; the plan query and the workspace sizes read
 // the same plan.
 #include "conv.h"
+#include "tile_parts.h"
 
 
 namespace lisec {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BMW = 128, BC = 64;                // rows per M tile, channel block
 constexpr int kThreads = 256;
@@ -136,10 +135,7 @@ k_wgrad(ConvGeom g, const float* __restrict__ in, const float* __restrict__ in_b
         for (int p = 0; p < 8; ++p) {
             float4 v = ra[p];
             const bool ok = (valid_mask >> p) & 1;
-            v.x = ok ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-            v.y = ok ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-            v.z = ok ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-            v.w = ok ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
+            affine_relu(v, tsc, tsh, relu_lo, ok);
             *reinterpret_cast<float4*>(sA + (p * 16 + (tid >> 4)) * BC + piece * 4) = v;
         }
     };
@@ -148,10 +144,7 @@ k_wgrad(ConvGeom g, const float* __restrict__ in, const float* __restrict__ in_b
         for (int p = 0; p < 8; ++p) {
             float4 v = rd[p];
             const bool ok = (dvalid >> p) & 1;
-            v.x = ok ? fmaxf(fmaf(v.x, dsc.x, dsh.x), drelu_lo) : 0.f;
-            v.y = ok ? fmaxf(fmaf(v.y, dsc.y, dsh.y), drelu_lo) : 0.f;
-            v.z = ok ? fmaxf(fmaf(v.z, dsc.z, dsh.z), drelu_lo) : 0.f;
-            v.w = ok ? fmaxf(fmaf(v.w, dsc.w, dsh.w), drelu_lo) : 0.f;
+            affine_relu(v, dsc, dsh, drelu_lo, ok);
             *reinterpret_cast<float4*>(sD + (p * 16 + (tid >> 4)) * BC + piece * 4) = v;
         }
     };
@@ -370,14 +363,8 @@ wgrad_halo_body(const WgradItem& it, const int bx, const int by, const int bz, f
             if (s_ < DR + 2) {
                 float4 v = ra[p];
                 const bool ok = (amask >> p) & 1;
-                if (XF) {
-                    v.x = ok ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-                    v.y = ok ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-                    v.z = ok ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-                    v.w = ok ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
-                } else {
-                    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-                }
+                if (XF) affine_relu(v, tsc, tsh, relu_lo, ok);
+                else masked(v, ok);
                 *reinterpret_cast<float4*>(sA + s_ * BC + piece * 4) = v;
             }
         }
@@ -401,47 +388,7 @@ wgrad_halo_body(const WgradItem& it, const int bx, const int by, const int bz, f
         const int ntile = next_live(tile + 1);
         if (ntile < t_end) issue(ntile);
         const int nk = (cur_len + 7) >> 3;             // rows beyond len are zero in sD: whole 8-row chunks only
-        // software-pipelined by hand: the ten fragment reads of chunk kk + 1 are issued BEFORE the twelve MFMAs of chunk kk
-        // (sched_barrier pins that; left alone the reads follow the MFMAs and every chunk waits out the LDS latency)
-        float fa[2][6], fb[2][4];
-#define LISEC_WG_READ(S_, KK_)                                                                                          \
-        do {                                                                                                            \
-            const float* ap = aCol + (KK_) * 8 * BC;                                                                    \
-            const float* dp = dCol + (KK_) * 8 * BC;                                                                    \
-            fb[S_][0] = dp[0]; fb[S_][1] = dp[BC]; fb[S_][2] = dp[2 * BC]; fb[S_][3] = dp[3 * BC];                      \
-            fa[S_][0] = ap[0]; fa[S_][1] = ap[BC]; fa[S_][2] = ap[2 * BC]; fa[S_][3] = ap[3 * BC];                      \
-            fa[S_][4] = ap[4 * BC]; fa[S_][5] = ap[5 * BC];                                                             \
-        } while (0)
-#define LISEC_WG_MFMA(S_)                                                                                               \
-        do {                                                                                                            \
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][0], fb[S_][0], acc0, 0, 0, 0);                           \
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][1], fb[S_][0], acc1, 0, 0, 0);                           \
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][0], acc2, 0, 0, 0);                           \
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][1], fb[S_][1], acc0, 0, 0, 0);                           \
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][1], acc1, 0, 0, 0);                           \
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][1], acc2, 0, 0, 0);                           \
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][2], acc0, 0, 0, 0);                           \
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][2], acc1, 0, 0, 0);                           \
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][4], fb[S_][2], acc2, 0, 0, 0);                           \
-            acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][3], acc0, 0, 0, 0);                           \
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][4], fb[S_][3], acc1, 0, 0, 0);                           \
-            acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][5], fb[S_][3], acc2, 0, 0, 0);                           \
-        } while (0)
-        int kk = 0;
-        if (nk > 0) LISEC_WG_READ(0, 0);
-        for (; kk + 1 < nk; kk += 2) {
-            LISEC_WG_READ(1, kk + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            LISEC_WG_MFMA(0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 2 < nk) LISEC_WG_READ(0, kk + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            LISEC_WG_MFMA(1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (kk < nk) LISEC_WG_MFMA(0);
-#undef LISEC_WG_READ
-#undef LISEC_WG_MFMA
+        wgrad_chunks<BC>(aCol, dCol, nk, acc0, acc1, acc2);
         __syncthreads();
         if (ntile < t_end) store();
         __syncthreads();
@@ -461,46 +408,15 @@ wgrad_halo_body(const WgradItem& it, const int bx, const int by, const int bz, f
         // the register layout (write-through), every wave waits for its stores, barrier, ONE lane's agent-scope ticket; the
         // last slice to arrive adds the slabs in slice order (deterministic) and writes the finished gradient -- no slab-sum
         // launch.  Used when a cell has few slices (the RPN maps); many slices (the middle layers) keep the slab-sum kernel.
-        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-        // (in the dynamic LDS, free by now: a static word on top of LT = 100's 53 760 B rounds the allocation past a third
-        // of the CU's 160 KB and the kernel drops from three to two workgroups per CU)
-        volatile int* wg_last_p = reinterpret_cast<volatile int*>(smem);
+        // (the "last" word in the dynamic LDS, free by now: a static word on top of LT = 100's 53 760 B rounds the allocation
+        // past a third of the CU's 160 KB and the kernel drops from three to two workgroups per CU)
         const int ncell = ngroups * it.gy * it.gz, cell = (gslot * it.gy + by) * it.gz + bz;
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(partial, 0, (int)((size_t)it.nsplit * ncell * kWSlabF4 * 16),
                                                                       0x00020000);
         const unsigned lane_off = (unsigned)((wave * 12) * 64 + lane) * 16u;
-        const unsigned mine = (unsigned)(((size_t)split * ncell + cell) * kWSlabF4 * 16) + lane_off;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            const f32x16& a = q < 4 ? acc0 : (q < 8 ? acc1 : acc2);
-            const int r = (q & 3) * 4;
-            u32x4 v;
-            v.x = __float_as_uint(a[r]); v.y = __float_as_uint(a[r + 1]); v.z = __float_as_uint(a[r + 2]); v.w = __float_as_uint(a[r + 3]);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs, mine + q * 64 * 16, 0, 16);          // aux 16 = sc1
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0)
-            *wg_last_p = __hip_atomic_fetch_add(it.counters + cell, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == it.nsplit - 1;
-        __syncthreads();
-        if (!*wg_last_p) { WGRAD_STAMP(3); return; }
-        if (threadIdx.x == 0) __hip_atomic_store(it.counters + cell, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        f32x16 s0 = {0}, s1 = {0}, s2 = {0};
-        const unsigned zstride = (unsigned)((size_t)ncell * kWSlabF4 * 16);
-        unsigned off = (unsigned)((size_t)cell * kWSlabF4 * 16) + lane_off;
-        for (int z = 0; z < it.nsplit; ++z, off += zstride) {
-            u32x4 v[12];
-#pragma unroll
-            for (int q = 0; q < 12; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + q * 64 * 16, 0, 16);
-#pragma unroll
-            for (int q = 0; q < 12; ++q) {
-                f32x16& a = q < 4 ? s0 : (q < 8 ? s1 : s2);
-                const int r = (q & 3) * 4;
-                a[r] += __uint_as_float(v[q].x); a[r + 1] += __uint_as_float(v[q].y);
-                a[r + 2] += __uint_as_float(v[q].z); a[r + 3] += __uint_as_float(v[q].w);
-            }
-        }
-        acc0 = s0; acc1 = s1; acc2 = s2;
+        slab_store<12>(acc0, acc1, acc2, rs, (unsigned)(((size_t)split * ncell + cell) * kWSlabF4 * 16) + lane_off);
+        if (!slice_ticket(it.counters + cell, it.nsplit, reinterpret_cast<int*>(smem))) { WGRAD_STAMP(3); return; }
+        slab_sum<false, 12>(acc0, acc1, acc2, rs, (unsigned)((size_t)cell * kWSlabF4 * 16) + lane_off, (unsigned)((size_t)ncell * kWSlabF4 * 16), it.nsplit);
         out_base = it.dW; out_split = 0; transpose = it.transpose != 0;
     }
 #pragma unroll
@@ -651,7 +567,6 @@ wgrad_ring_body(const RingItem& it, const int bx, float* smem, unsigned long lon
     // 100-row tiles.  Buffer loads against a descriptor that covers exactly ONE line (x) / one tile (dY): rows before
     // the line (negative offset), beyond its end, beyond the tile's rows and channel pieces beyond Cin / Cout read as
     // zeros -- no predicates, no masks, no 64-bit lane addresses.
-    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     u32x4 rr[NP];
     const int XR = DR + 2;
     const int strideX4 = g.in_stride * 4, strideD4 = g.out_stride * 4;                   // bytes per row
@@ -699,10 +614,7 @@ wgrad_ring_body(const RingItem& it, const int bx, float* smem, unsigned long lon
                     // zeroed again (rows beyond the tile only meet zero dY rows: any finite value does)
                     const int sw = w0 - g.pw + s_;
                     const bool keep = sw >= 0 && sw < g.Wi;
-                    v.x = keep ? fmaxf(fmaf(v.x, tsc.x, tsh.x), relu_lo) : 0.f;
-                    v.y = keep ? fmaxf(fmaf(v.y, tsc.y, tsh.y), relu_lo) : 0.f;
-                    v.z = keep ? fmaxf(fmaf(v.z, tsc.z, tsh.z), relu_lo) : 0.f;
-                    v.w = keep ? fmaxf(fmaf(v.w, tsc.w, tsh.w), relu_lo) : 0.f;
+                    affine_relu(v, tsc, tsh, relu_lo, keep);
                 }
                 *reinterpret_cast<float4*>((first ? dA : dB) + s_ * BC + piece * 4) = v;
             }
@@ -726,47 +638,7 @@ wgrad_ring_body(const RingItem& it, const int bx, float* smem, unsigned long lon
         const int sh = h - g.ph + kh;                  // this wave's input line (wave-uniform)
         if (sh >= 0 && sh < g.Hi) {
             const float* aCol = sX + ((sh + 3) % 3) * SLOT + aoff;
-            // software-pipelined by hand as in the halo kernel: the ten fragment reads of chunk kk + 1 are issued BEFORE
-            // the twelve MFMAs of chunk kk
-            float fa[2][6], fb[2][4];
-#define LISEC_WG_READ(S_, KK_)                                                                                          \
-            do {                                                                                                        \
-                const float* ap = aCol + (KK_) * 8 * BC;                                                                \
-                const float* dp = dCol + (KK_) * 8 * BC;                                                                \
-                fb[S_][0] = dp[0]; fb[S_][1] = dp[BC]; fb[S_][2] = dp[2 * BC]; fb[S_][3] = dp[3 * BC];                  \
-                fa[S_][0] = ap[0]; fa[S_][1] = ap[BC]; fa[S_][2] = ap[2 * BC]; fa[S_][3] = ap[3 * BC];                  \
-                fa[S_][4] = ap[4 * BC]; fa[S_][5] = ap[5 * BC];                                                         \
-            } while (0)
-#define LISEC_WG_MFMA(S_)                                                                                               \
-            do {                                                                                                        \
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][0], fb[S_][0], acc0, 0, 0, 0);                       \
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][1], fb[S_][0], acc1, 0, 0, 0);                       \
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][0], acc2, 0, 0, 0);                       \
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][1], fb[S_][1], acc0, 0, 0, 0);                       \
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][1], acc1, 0, 0, 0);                       \
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][1], acc2, 0, 0, 0);                       \
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][2], fb[S_][2], acc0, 0, 0, 0);                       \
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][2], acc1, 0, 0, 0);                       \
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][4], fb[S_][2], acc2, 0, 0, 0);                       \
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][3], fb[S_][3], acc0, 0, 0, 0);                       \
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][4], fb[S_][3], acc1, 0, 0, 0);                       \
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[S_][5], fb[S_][3], acc2, 0, 0, 0);                       \
-            } while (0)
-            int kk = 0;
-            if (nk > 0) LISEC_WG_READ(0, 0);
-            for (; kk + 1 < nk; kk += 2) {
-                LISEC_WG_READ(1, kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                LISEC_WG_MFMA(0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (kk + 2 < nk) LISEC_WG_READ(0, kk + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                LISEC_WG_MFMA(1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (kk < nk) LISEC_WG_MFMA(0);
-#undef LISEC_WG_READ
-#undef LISEC_WG_MFMA
+            wgrad_chunks<BC>(aCol, dCol, nk, acc0, acc1, acc2);
         }
         __syncthreads();
         if (more) store2(h + 3 - g.ph, false, h + 1);                // the slot of line h - ph: no tile reads it again
@@ -785,44 +657,15 @@ wgrad_ring_body(const RingItem& it, const int bx, float* smem, unsigned long lon
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(it.slabs, 0, (int)((size_t)smax * it.ncells * kRSlabF4 * 16),
                                                                   0x00020000);
     const unsigned lane_off = (unsigned)((wave * 12) * 64 + lane) * 16u;
-    const unsigned mine = (unsigned)(((size_t)slice * it.ncells + cell) * kRSlabF4 * 16) + lane_off;
+    slab_store<12>(acc0, acc1, acc2, rs, (unsigned)(((size_t)slice * it.ncells + cell) * kRSlabF4 * 16) + lane_off);
+    if (!it.combine) { WGRAD_STAMP(3); return; }
+    // few slices per cell: they meet here as the K slices of a tile do in igemm.hip; the last one to arrive adds the slabs
+    // in slice order and writes the finished gradient (the "last" word: the dynamic LDS, free by now)
+    if (!slice_ticket(it.counters + cell, nsl, reinterpret_cast<int*>(smem))) { WGRAD_STAMP(3); return; }
+    slab_sum<false, 12>(acc0, acc1, acc2, rs, (unsigned)((size_t)cell * kRSlabF4 * 16) + lane_off, (unsigned)((size_t)it.ncells * kRSlabF4 * 16), nsl);
 #pragma unroll
     for (int q = 0; q < 12; ++q) {
         const f32x16& a = q < 4 ? acc0 : (q < 8 ? acc1 : acc2);
-        const int r = (q & 3) * 4;
-        u32x4 v;
-        v.x = __float_as_uint(a[r]); v.y = __float_as_uint(a[r + 1]); v.z = __float_as_uint(a[r + 2]); v.w = __float_as_uint(a[r + 3]);
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, mine + q * 64 * 16, 0, 16);              // aux 16 = sc1
-    }
-    if (!it.combine) { WGRAD_STAMP(3); return; }
-    // few slices per cell: they meet here as the K slices of a tile do in igemm.hip (stores waited for, barrier, one
-    // agent-scope ticket); the last one to arrive adds the slabs in slice order and writes the finished gradient
-    volatile int* wg_last_p = reinterpret_cast<volatile int*>(smem);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0)
-        *wg_last_p = __hip_atomic_fetch_add(it.counters + cell, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsl - 1;
-    __syncthreads();
-    if (!*wg_last_p) { WGRAD_STAMP(3); return; }
-    if (threadIdx.x == 0) __hip_atomic_store(it.counters + cell, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    f32x16 s0 = {0}, s1 = {0}, s2 = {0};
-    const unsigned zstride = (unsigned)((size_t)it.ncells * kRSlabF4 * 16);
-    unsigned off = (unsigned)((size_t)cell * kRSlabF4 * 16) + lane_off;
-    for (int z = 0; z < nsl; ++z, off += zstride) {
-        u32x4 v[12];
-#pragma unroll
-        for (int q = 0; q < 12; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + q * 64 * 16, 0, 16);
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            f32x16& a = q < 4 ? s0 : (q < 8 ? s1 : s2);
-            const int r = (q & 3) * 4;
-            a[r] += __uint_as_float(v[q].x); a[r + 1] += __uint_as_float(v[q].y);
-            a[r + 2] += __uint_as_float(v[q].z); a[r + 3] += __uint_as_float(v[q].w);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 12; ++q) {
-        const f32x16& a = q < 4 ? s0 : (q < 8 ? s1 : s2);
         const int r = (q & 3) * 4;
         ring_store_out(it, kd, c0, n0, wave, q, lane, make_float4(a[r], a[r + 1], a[r + 2], a[r + 3]));
     }
