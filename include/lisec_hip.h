@@ -740,6 +740,41 @@ int lisec_detection_loss_eval(const lisec_detection_loss_cfg* cfg, const float* 
                               lisec_stream_t stream);
 size_t lisec_detection_loss_workspace_bytes(void);
 
+/* The detection loss with a rotated-box IoU term beside SmoothL1 (csrc/detection_iou_loss.hip; ours).  Everything as for
+ * lisec_detection_loss, except
+ *   L_reg = 1/N_pos sum_pos [ sum_k S(r_k - t_k) + iou_weight (1 - IoU(decode(r), decode(t))) ],  t = y_reg - target_offset
+ * with the decode and the IoU of the POSITIVE_IOU metric below: centre (r0 l_a, r1 w_a, r2 h_a), extents exp(r3..5) (l_a,
+ * w_a, h_a), yaw r6 + yaw_a for the anchor (l_a, w_a, h_a, yaw_a) of the channel block; LISEC_IOU_BEV is the IoU of the
+ * footprints, LISEC_IOU_3D multiplies by the clamped height overlap and divides by the volume of the union.  The target
+ * box is a constant; the gradient of the term goes to the seven r of the positive anchor (under LISEC_IOU_BEV r2 and r5
+ * get none) and is the exact derivative of the clipped area, added to the SmoothL1 derivative in double before the one
+ * rounding.  IoU 0 -- a decoded box that is not finite, footprints or height intervals that do not meet -- adds
+ * iou_weight to the sum and exactly +0.0 to the gradient, so such an anchor gets lisec_detection_loss's bits, and
+ * iou_weight = 0 gives them everywhere.  The class channels, the counts and every anchor that is not positive are those
+ * of lisec_detection_loss. */
+typedef struct lisec_detection_iou_loss_cfg {
+    int struct_bytes;               /* sizeof(lisec_detection_iou_loss_cfg), checked */
+    int reserved;                   /* 0 */
+    lisec_detection_loss_cfg det;   /* its own struct_bytes = sizeof(lisec_detection_loss_cfg), checked */
+    double iou_weight;              /* >= 0, finite */
+    int iou_mode;                   /* LISEC_IOU_3D / LISEC_IOU_BEV (lisec_boxes_match, below) */
+    int reserved2;                  /* 0 */
+    double anchors[2][4];           /* l, w, h, yaw: lisec_rpn_cfg's; extents > 0 */
+} lisec_detection_iou_loss_cfg;
+
+/* The argument lists of lisec_detection_loss*; one more launch (a thread per anchor) between the element pass and the
+ * finalize.  loss_out[3] = {total, L_cls, L_reg} with the IoU term inside L_reg.  LISEC_EINVAL, with nothing enqueued:
+ * lisec_detection_loss's refusals, a struct_bytes of another size, iou_weight negative or not finite, an unknown iou_mode,
+ * an anchor that is not finite or has an extent <= 0. */
+int lisec_detection_iou_loss(const lisec_detection_iou_loss_cfg* cfg, const float* head, const float* y_cls,
+                             const float* y_reg, long long M, float grad_scale, float* dhead, float* loss_out,
+                             long long* counts_out, void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+/* Adds the fp32 bits lisec_detection_iou_loss writes to acc[0..2], as doubles, and counts the sweep in acc[3]. */
+int lisec_detection_iou_loss_eval(const lisec_detection_iou_loss_cfg* cfg, const float* head, const float* y_cls,
+                                  const float* y_reg, long long M, double* acc, void* workspace, size_t workspace_bytes,
+                                  lisec_stream_t stream);
+size_t lisec_detection_iou_loss_workspace_bytes(void);     /* = lisec_detection_loss_workspace_bytes() */
+
 /* Metrics that read the label code of the detection loss (csrc/detection_metrics.hip; ours, not Keras').  Inputs and the
  * meaning of pos / neg / ignored as for lisec_detection_loss.  Every metric is a pair {num, den} of sums over the 2M
  * anchors of a sweep; its value is num/den over whatever sweeps the caller pools (0 when den == 0).  With p = sigmoid(z) in

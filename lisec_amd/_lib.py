@@ -114,6 +114,11 @@ class DetectionLossCfg(Structure):             # lisec_detection_loss_cfg
                 ("smooth_l1_beta", c_double), ("target_offset", c_double), ("weight", c_double * 2)]
 
 
+class DetectionIoULossCfg(Structure):          # lisec_detection_iou_loss_cfg
+    _fields_ = [("struct_bytes", c_int), ("reserved", c_int), ("det", DetectionLossCfg), ("iou_weight", c_double),
+                ("iou_mode", c_int), ("reserved2", c_int), ("anchors", (c_double * 4) * 2)]
+
+
 DET_MAX_METRICS = 8                            # LISEC_DET_MAX_METRICS
 
 
@@ -322,6 +327,12 @@ def _declare(lib):
     lib.lisec_detection_loss_eval.argtypes = [POINTER(DetectionLossCfg), P, P, P, LL, P, P, c_size_t, P]
     lib.lisec_detection_loss_workspace_bytes.restype = c_size_t
     lib.lisec_detection_loss_workspace_bytes.argtypes = []
+    lib.lisec_detection_iou_loss.restype = c_int
+    lib.lisec_detection_iou_loss.argtypes = [POINTER(DetectionIoULossCfg), P, P, P, LL, c_float, P, P, P, P, c_size_t, P]
+    lib.lisec_detection_iou_loss_eval.restype = c_int
+    lib.lisec_detection_iou_loss_eval.argtypes = [POINTER(DetectionIoULossCfg), P, P, P, LL, P, P, c_size_t, P]
+    lib.lisec_detection_iou_loss_workspace_bytes.restype = c_size_t
+    lib.lisec_detection_iou_loss_workspace_bytes.argtypes = []
     lib.lisec_detection_metrics.restype = c_int
     lib.lisec_detection_metrics.argtypes = [POINTER(DetectionMetricsCfg), P, P, P, LL, P, c_int, P, c_size_t, P]
     lib.lisec_detection_metrics_workspace_bytes.restype = c_size_t

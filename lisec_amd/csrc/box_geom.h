@@ -1,5 +1,6 @@
 // The rectangle footprint shared by the box kernels (boxes.hip, union_overlap.hip, detection_ap.hip,
-// detection_metrics.hip): boxToShapely's vertices, the shoelace sum, the clipped area of two footprints and their IoU.
+// detection_metrics.hip, detection_iou_loss.hip): boxToShapely's vertices, the shoelace sum, the clipped area of two
+// footprints, their IoU, and the anchor decode of the detection metrics and the IoU loss.
 #pragma once
 #include "common.h"
 
@@ -81,6 +82,35 @@ __device__ inline double pair_iou(const double* p, const double* g, int mode) {
     }
     const double uni = sp + sg - inter;
     return uni > 0.0 ? inter / uni : 0.0;
+}
+
+__device__ __forceinline__ bool finite7(const double* b) {
+    return isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]) && isfinite(b[4]) && isfinite(b[5]) &&
+           isfinite(b[6]);
+}
+
+// The decode of k_rpn_decode (csrc/boxes.hip) for the prediction r and target t of one anchor an = (l, w, h, yaw), without
+// the anchor centre both boxes share; false when either box is not finite.
+__device__ __forceinline__ bool decode_pair(const double* r, const double* t, const double* an, double* p, double* g) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p[k] = r[k] * an[k];
+        g[k] = t[k] * an[k];
+        p[3 + k] = exp(r[3 + k]) * an[k];
+        g[3 + k] = exp(t[3 + k]) * an[k];
+    }
+    p[6] = r[6] + an[3];
+    g[6] = t[6] + an[3];
+    return finite7(p) && finite7(g);
+}
+
+// IoU of the decoded prediction and target of one anchor; 0 for anything that is not finite (a yaw that is not finite has
+// no footprint, hence no finite IoU)
+__device__ inline double decoded_iou(const double* r, const double* t, const double* an, int mode) {
+    double p[7], g[7];
+    if (!decode_pair(r, t, an, p, g)) return 0.0;
+    const double iou = pair_iou(p, g, mode);
+    return isfinite(iou) ? iou : 0.0;
 }
 
 }  // namespace lisec

@@ -1,184 +1,11 @@
 // The VoxelNet detection loss (section 2.2 of the paper; focal form with gamma > 0) on the (M,16) head against the
-// 0 / 1 / 2 label code of lisec_rpn_labels (include/lisec_hip.h, lisec_detection_loss*).  Three launches:
-//   k_det_count     one workgroup over y_cls (M*2 floats): N_pos and N_neg, exact integers, before any gradient is scaled
-//   k_det_loss      the element layout of k_head_loss (csrc/losses.hip): thread i holds element i of the flat head; every
-//                   element in double from the fp32 inputs, the gradient rounded once; per-workgroup fp64 partials of
-//                   {sum_pos class, sum_neg class, sum_pos regression}, not yet normalised
-//   k_det_finalize  one workgroup: the partials summed in index order, normalised by the counts
-// No atomics and a fixed partition: the same bits on every run.  The evaluation entry is the same three launches with a
-// NULL gradient, so a sweep's values are the training entry's bits.  Every address is fixed and nothing is read back:
-// the launches record into a step plan as they are.
-#include "common.h"
+// 0 / 1 / 2 label code of lisec_rpn_labels (include/lisec_hip.h, lisec_detection_loss*): the three launches of
+// detection_loss_parts.h.  The evaluation entry is the same three launches with a NULL gradient, so a sweep's values are
+// the training entry's bits.
+#include "detection_loss_parts.h"
 
 namespace lisec {
 namespace {
-
-constexpr int kDetThreads = 256;             // 16 cells of 16 lanes
-constexpr int kDetBlocks = 1024;             // lisec_head_loss's partition
-constexpr int kDetVals = 3;                  // partials per workgroup: S_pos (class), S_neg (class), S_reg
-constexpr int kCountThreads = 1024;
-constexpr int kCountUnroll = 16;
-
-__device__ __forceinline__ bool is_pos(float code) { return code > 1.5f; }
-__device__ __forceinline__ bool is_neg(float code) { return code > 0.5f && code <= 1.5f; }
-
-// counts[0] = N_pos, counts[1] = N_neg over the 2M codes; a NaN code compares false twice: ignored
-__global__ void __launch_bounds__(kCountThreads)
-k_det_count(const float* __restrict__ ycls, long long n, long long* __restrict__ counts, long long* __restrict__ counts_out) {
-    __shared__ long long red[2][kCountThreads / 64];
-    long long np = 0, nn = 0;
-    // one workgroup is latency-bound: kCountUnroll independent loads in flight per lane, so the Lyft map (40 000 codes)
-    // is 3 round trips to memory, not 40
-    for (long long base = 0; base < n; base += (long long)kCountThreads * kCountUnroll) {
-        float c[kCountUnroll];
-#pragma unroll
-        for (int u = 0; u < kCountUnroll; ++u) {
-            const long long i = base + (long long)u * kCountThreads + threadIdx.x;
-            c[u] = i < n ? ycls[i] : 0.f;                    // 0: ignored
-        }
-#pragma unroll
-        for (int u = 0; u < kCountUnroll; ++u) {
-            np += is_pos(c[u]) ? 1 : 0;
-            nn += is_neg(c[u]) ? 1 : 0;
-        }
-    }
-    np = wave_sum(np);
-    nn = wave_sum(nn);
-    if (lane_id() == 0) {
-        red[0][threadIdx.x >> 6] = np;
-        red[1][threadIdx.x >> 6] = nn;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        long long a = 0;
-        for (int w = 0; w < kCountThreads / 64; ++w) a += red[threadIdx.x][w];
-        counts[threadIdx.x] = a;
-        if (counts_out) counts_out[threadIdx.x] = a;
-    }
-}
-
-// sp(x) = max(x,0) + log1p(exp(-|x|)) with e = exp(-|x|) given; the maximum is a comparison, so a NaN stays a NaN (in e)
-__device__ __forceinline__ double softplus_e(double x, double e) { return (x > 0.0 ? x : 0.0) + log1p(e); }
-
-// dhead == nullptr: values only (the evaluation entry)
-__global__ void __launch_bounds__(kDetThreads)
-k_det_loss(lisec_detection_loss_cfg cfg, const float* __restrict__ head, const float* __restrict__ ycls,
-           const float* __restrict__ yreg, long long M, float gscale, const long long* __restrict__ counts,
-           float* __restrict__ dhead, double* __restrict__ parts) {
-    __shared__ double red[kDetVals][kDetThreads / 64];
-    const int c = threadIdx.x & 15;
-    const bool grad = dhead != nullptr;
-    const long long cp = counts[0], cn = counts[1];
-    const double npos = cp > 0 ? (double)cp : 1.0, nneg = cn > 0 ? (double)cn : 1.0;
-    const double gs = (double)gscale;
-    const double wpos = gs * cfg.weight[0] * cfg.alpha / npos, wneg = gs * cfg.weight[0] * cfg.beta / nneg;
-    const double wreg = gs * cfg.weight[1] / npos;
-    const double g = cfg.gamma, b = cfg.smooth_l1_beta;
-    double spos = 0.0, sneg = 0.0, sreg = 0.0;
-    const long long n = M * 16;
-    for (long long base = blockIdx.x * (long long)kDetThreads; base < n; base += (long long)gridDim.x * kDetThreads) {
-        const long long i = base + threadIdx.x;
-        if (i >= n) break;
-        const long long m = i >> 4;
-        float gout = 0.f;                                    // +0.0f wherever the loss does not look
-        if (c < 2) {
-            const float code = ycls[m * 2 + c];
-            const bool pos = is_pos(code);
-            if (pos || is_neg(code)) {
-                const double z = head[i];
-                const double e = exp(-fabs(z));              // in (0, 1]: no overflow for any finite logit
-                const double lo = e / (1.0 + e), hi = 1.0 / (1.0 + e);
-                const double p = z >= 0.0 ? hi : lo, q = z >= 0.0 ? lo : hi;     // sigmoid(z), 1 - sigmoid(z)
-                // a positive looks at -z: the roles of p and q swap
-                const double x = pos ? -z : z, s = softplus_e(x, e);
-                const double px = pos ? q : p, qx = pos ? p : q;                 // sigmoid(x), 1 - sigmoid(x)
-                double v = s, dv = px;                                           // gamma == 0: sp(x), d sp / dx
-                if (g != 0.0) {
-                    const double f = pow(px, g);
-                    v = f * s;
-                    dv = f * (g * qx * s + px);
-                }
-                if (pos) spos += v; else sneg += v;
-                if (grad) gout = (float)(pos ? -(wpos * dv) : wneg * dv);        // dx/dz = -1 on a positive
-            }
-        } else {
-            const int a = c < 9 ? 0 : 1;
-            if (is_pos(ycls[m * 2 + a])) {
-                const double d = (double)head[i] - ((double)yreg[m * 14 + (c - 2)] - cfg.target_offset);
-                const double ad = fabs(d);
-                const bool quad = ad < b;
-                sreg += quad ? d * d / (2.0 * b) : ad - 0.5 * b;
-                if (grad) gout = (float)(wreg * (quad ? d / b : (d > 0.0 ? 1.0 : (d < 0.0 ? -1.0 : d))));
-            }
-        }
-        if (grad) dhead[i] = gout;
-    }
-    double v[kDetVals] = {spos, sneg, sreg};
-#pragma unroll
-    for (int k = 0; k < kDetVals; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kDetVals) {
-        double a = 0.0;
-        for (int w = 0; w < kDetThreads / 64; ++w) a += red[threadIdx.x][w];
-        parts[(size_t)blockIdx.x * kDetVals + threadIdx.x] = a;
-    }
-}
-
-// Training (acc == nullptr): loss_out[3]; evaluation: the same fp32 values added, as doubles, to acc, the sweep counted.
-__global__ void __launch_bounds__(256)
-k_det_finalize(lisec_detection_loss_cfg cfg, const double* __restrict__ parts, int nparts,
-               const long long* __restrict__ counts, float* __restrict__ loss_out, double* __restrict__ acc) {
-    __shared__ double red[kDetVals][256];
-    double a[kDetVals] = {0.0, 0.0, 0.0};
-    for (int p = threadIdx.x; p < nparts; p += 256) {
-#pragma unroll
-        for (int k = 0; k < kDetVals; ++k) a[k] += parts[(size_t)p * kDetVals + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kDetVals; ++k) red[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int k = 0; k < kDetVals; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    const long long cp = counts[0], cn = counts[1];
-    const double npos = cp > 0 ? (double)cp : 1.0, nneg = cn > 0 ? (double)cn : 1.0;
-    const double lc = cfg.alpha * red[0][0] / npos + cfg.beta * red[1][0] / nneg, lr = red[2][0] / npos;
-    const float tot = (float)(cfg.weight[0] * lc + cfg.weight[1] * lr), fc = (float)lc, fr = (float)lr;
-    if (acc) {
-        acc[0] += (double)tot; acc[1] += (double)fc; acc[2] += (double)fr; acc[3] += 1.0;
-    } else {
-        loss_out[0] = tot; loss_out[1] = fc; loss_out[2] = fr;
-    }
-}
-
-int det_blocks(long long M) {
-    const long long b = (M * 16 + kDetThreads - 1) / kDetThreads;
-    return (int)(b < 1 ? 1 : (b > kDetBlocks ? kDetBlocks : b));
-}
-
-int check_det(const lisec_detection_loss_cfg* cfg, long long M, const void* workspace, size_t workspace_bytes) {
-    LISEC_CHECK_ARG(cfg, "detection loss: NULL descriptor");
-    LISEC_CHECK_ARG(cfg->struct_bytes == (int)sizeof(lisec_detection_loss_cfg),
-                    "detection loss: descriptor of %d bytes, this library's has %d", cfg->struct_bytes,
-                    (int)sizeof(lisec_detection_loss_cfg));
-    LISEC_CHECK_ARG(cfg->alpha >= 0.0 && cfg->beta >= 0.0 && cfg->gamma >= 0.0,
-                    "detection loss: alpha, beta and gamma must be >= 0 (got %g, %g, %g)", cfg->alpha, cfg->beta, cfg->gamma);
-    LISEC_CHECK_ARG(cfg->smooth_l1_beta > 0.0, "detection loss: smooth_l1_beta must be > 0 (got %g)", cfg->smooth_l1_beta);
-    LISEC_CHECK_ARG(M > 0, "detection loss: M must be > 0 (got %lld)", M);
-    LISEC_CHECK_ARG(workspace, "detection loss: NULL workspace");
-    LISEC_CHECK_ARG(workspace_bytes >= lisec_detection_loss_workspace_bytes(),
-                    "detection loss: workspace of %zu bytes, %zu needed", workspace_bytes,
-                    lisec_detection_loss_workspace_bytes());
-    return LISEC_OK;
-}
 
 int run_det(const lisec_detection_loss_cfg& cfg, const float* head, const float* y_cls, const float* y_reg, long long M,
             float grad_scale, float* dhead, float* loss_out, long long* counts_out, double* acc, void* workspace,

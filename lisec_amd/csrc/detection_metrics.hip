@@ -11,7 +11,7 @@
 // Positives are ~1 % of the anchors, so the clipping branch is rare and divergent: a wave that holds one positive pays for
 // it alone.  At 40 000 anchors (the Lyft grid) that is 157 workgroups of 4 waves, under one per compute unit, and the launch
 // is bound by its latency, not by the lanes idle in the branch; no compaction pass is worth a third launch.  256 threads,
-// four waves, per workgroup: the compiler reports 194 VGPRs (2 waves per SIMD), 528 bytes of scratch per lane for the clipping
+// four waves, per workgroup: the compiler reports 196 VGPRs (2 waves per SIMD), 528 bytes of scratch per lane for the clipping
 // buffers of quad_intersection_area and 16.5 KiB of LDS (a per-thread array it moves there, and 512 bytes of partials) -- one
 // workgroup per compute unit fits with room to spare, and that is all this launch asks for.
 #include "box_geom.h"
@@ -26,29 +26,6 @@ constexpr int kDetmVals = 2 * LISEC_DET_MAX_METRICS;           // partials per w
 // is_pos / is_neg of detection_loss.hip: a NaN code compares false twice and is ignored
 __device__ __forceinline__ bool is_pos(float code) { return code > 1.5f; }
 __device__ __forceinline__ bool is_neg(float code) { return code > 0.5f && code <= 1.5f; }
-
-__device__ __forceinline__ bool finite7(const double* b) {
-    return isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]) && isfinite(b[4]) && isfinite(b[5]) &&
-           isfinite(b[6]);
-}
-
-// IoU of the decoded prediction r and target t of one anchor an = (l, w, h, yaw); 0 for anything that is not finite (a yaw
-// that is not finite has no footprint, hence no finite IoU)
-__device__ double decoded_iou(const double* r, const double* t, const double* an, int mode) {
-    double p[7], g[7];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p[k] = r[k] * an[k];
-        g[k] = t[k] * an[k];
-        p[3 + k] = exp(r[3 + k]) * an[k];
-        g[3 + k] = exp(t[3 + k]) * an[k];
-    }
-    p[6] = r[6] + an[3];
-    g[6] = t[6] + an[3];
-    if (!finite7(p) || !finite7(g)) return 0.0;
-    const double iou = pair_iou(p, g, mode);
-    return isfinite(iou) ? iou : 0.0;
-}
 
 __global__ void __launch_bounds__(kDetmThreads)
 k_detm_anchors(lisec_detection_metrics_cfg cfg, const float* __restrict__ head, const float* __restrict__ ycls,

@@ -2,7 +2,8 @@
 loss / loss_weights / metrics arguments: a LossSpec, the descriptor (lisec_loss_cfg, include/lisec_hip.h) of the kernels
 that evaluate it (csrc/losses.hip).
 VoxelNetLoss is the one loss here that Keras does not have: the detection loss of VoxelNet section 2.2, a joint loss of both
-outputs, compiled to a DetectionLossSpec (lisec_detection_loss_cfg, csrc/detection_loss.hip).
+outputs, compiled to a DetectionLossSpec (lisec_detection_loss_cfg, csrc/detection_loss.hip); VoxelNetIoULoss adds a
+rotated-box IoU term to its regression part (DetectionIoULossSpec, lisec_detection_iou_loss_cfg, csrc/detection_iou_loss.hip).
 
 Same names, constructor arguments, defaults, get_config / from_config and serialize / deserialize as Keras.  Every loss is
 Keras' mean over the last axis and then over the cells (SUM_OVER_BATCH_SIZE): the mean over all M*C elements of an output.
@@ -160,8 +161,32 @@ class VoxelNetLoss(Loss):
         return dict(super().get_config(), **{k: getattr(self, k) for k in DETECTION_PARAMS})
 
 
+class VoxelNetIoULoss(VoxelNetLoss):
+    """VoxelNetLoss with a rotated-box IoU term beside SmoothL1, so that training pulls on what the Lyft metric scores:
+    L_reg = 1/N_pos sum_pos [sum_k SmoothL1_b(r_k - t_k) + iou_weight (1 - IoU(decode(r), decode(t)))], with the decode and
+    the IoU of metrics.PositiveIoU (iou_mode 'bev': footprints; '3d': times the clamped height overlap, over the volume of
+    the union) against the anchors of the compiled spec (Constants.anchors).  The target box is a constant; a positive
+    whose boxes do not overlap, or are not finite, has IoU 0 and gets no gradient from the term -- SmoothL1 still pulls it.
+    iou_weight=0 is VoxelNetLoss bit for bit.  A joint loss like VoxelNetLoss: compile(loss=VoxelNetIoULoss(...)) or
+    loss='voxelnet_iou', never per output; lisec_detection_iou_loss (csrc/detection_iou_loss.hip) evaluates it."""
+
+    def __init__(self, alpha=1.5, beta=1.0, gamma=0.0, smooth_l1_beta=1.0, target_offset=1.0, iou_weight=1.0,
+                 iou_mode="bev", reduction="auto", name="voxelnet_iou_loss"):
+        super().__init__(alpha, beta, gamma, smooth_l1_beta, target_offset, reduction, name)
+        self.iou_weight, self.iou_mode = iou_weight, iou_mode
+        if not (float(iou_weight) >= 0 and math.isfinite(float(iou_weight))):
+            raise ValueError(f"VoxelNetIoULoss: iou_weight must be finite and >= 0, got {iou_weight}")
+        if iou_mode not in IOU_MODES:
+            raise ValueError(f"VoxelNetIoULoss: iou_mode must be one of {sorted(IOU_MODES)}, got {iou_mode!r}")
+
+    def get_config(self):
+        return dict(super().get_config(), iou_weight=self.iou_weight, iou_mode=self.iou_mode)
+
+
 DETECTION_PARAMS = ("alpha", "beta", "gamma", "smooth_l1_beta", "target_offset")
-JOINT_FUNCTIONS = {"voxelnet": VoxelNetLoss, "voxelnet_loss": VoxelNetLoss}      # names of the joint losses
+IOU_MODES = {"3d": 0, "bev": 1}                  # LISEC_IOU_3D, LISEC_IOU_BEV
+JOINT_FUNCTIONS = {"voxelnet": VoxelNetLoss, "voxelnet_loss": VoxelNetLoss,      # names of the joint losses
+                   "voxelnet_iou": VoxelNetIoULoss, "voxelnet_iou_loss": VoxelNetIoULoss}
 
 
 class _NotImplementedLoss(Loss):
@@ -249,7 +274,8 @@ def serialize(loss):
 def deserialize(config, custom_objects=None):
     if isinstance(config, str):
         return config
-    classes = dict(_BUILTIN, VoxelNetLoss=VoxelNetLoss, **_NOT_IMPLEMENTED, **(custom_objects or {}))
+    classes = dict(_BUILTIN, VoxelNetLoss=VoxelNetLoss, VoxelNetIoULoss=VoxelNetIoULoss, **_NOT_IMPLEMENTED,
+                   **(custom_objects or {}))
     name = config.get("class_name") if isinstance(config, dict) else None
     if name not in classes:
         raise ValueError(f"Unknown loss function: {name}")
@@ -398,6 +424,51 @@ class DetectionLossSpec:
         return f"DetectionLossSpec{self.config}"
 
 
+class DetectionIoULossSpec(DetectionLossSpec):
+    """The step loss of a VoxelNetIoULoss as lisec_detection_iou_loss sees it: a DetectionLossSpec -- params, weights and
+    metrics are its own, and the step treats it as one -- plus iou_weight, iou_mode ('3d' / 'bev') and the anchors the term
+    decodes against, which it always has (Constants.anchors unless given).  All of them are part of the key, so no
+    DetectionIoULossSpec equals a DetectionLossSpec."""
+
+    def __init__(self, params, weights=(1.0, 1.0), metrics=(), metric_names=(), anchors=None, iou_weight=1.0,
+                 iou_mode="bev"):
+        super().__init__(params, weights, metrics, metric_names, anchors)
+        self.iou_weight, self.iou_mode = float(iou_weight), iou_mode
+        if not (self.iou_weight >= 0 and math.isfinite(self.iou_weight)) or iou_mode not in IOU_MODES:
+            raise ValueError("a DetectionIoULossSpec has a finite iou_weight >= 0 and the iou_mode '3d' or 'bev'")
+        if not self.anchors:
+            if anchors is None:
+                from . import Constants
+                anchors = Constants.anchors
+            self.anchors = tuple(tuple(float(v) for v in a) for a in anchors)
+        if len(self.anchors) != 2 or any(len(a) != 4 for a in self.anchors):
+            raise ValueError("a DetectionIoULossSpec has two anchors (l, w, h, yaw)")
+
+    @property
+    def config(self):
+        return (self.params, self.weights, self.metrics, self.anchors, self.iou_weight, self.iou_mode)
+
+    def descriptor(self):
+        """The lisec_detection_iou_loss_cfg (an _lib.DetectionIoULossCfg)."""
+        d = _lib.DetectionIoULossCfg()
+        d.struct_bytes = ctypes.sizeof(_lib.DetectionIoULossCfg)
+        d.det = super().descriptor()
+        d.iou_weight, d.iou_mode = self.iou_weight, IOU_MODES[self.iou_mode]
+        for a in range(2):
+            for k in range(4):
+                d.anchors[a][k] = self.anchors[a][k]
+        return d
+
+    def __eq__(self, other):
+        return isinstance(other, DetectionIoULossSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(("detection_iou",) + self.config)
+
+    def __repr__(self):
+        return f"DetectionIoULossSpec{self.config}"
+
+
 LEGACY = {"mse": ((MSE, 0, 0.0, 0.0), (MSE, 0, 0.0, 0.0)),
           "smoothl1_ce": ((SIGMOID_CE_CLAMPED, 0, 0.0, 0.0), (SMOOTH_L1, 0, 0.0, 0.0))}
 
@@ -444,14 +515,15 @@ def _joint_loss(loss):
         loss = deserialize(loss)
     if isinstance(loss, str) and loss.lower() in JOINT_FUNCTIONS:
         return JOINT_FUNCTIONS[loss.lower()]()
-    return loss if isinstance(loss, VoxelNetLoss) else None
+    return loss if isinstance(loss, VoxelNetLoss) else None         # a VoxelNetIoULoss is one
 
 
 def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     """Model.compile's loss arguments -> (step loss, metric names).  The step loss is the plain string 'mse' or
     'smoothl1_ce' -- lisec_rpn_loss, the reference's step unchanged -- when the loss is MSE on both outputs, or the legacy
     'smoothl1_ce' spelling, with neither loss_weights nor metrics; a DetectionLossSpec (lisec_detection_loss) for a
-    VoxelNetLoss or 'voxelnet'; otherwise a LossSpec (lisec_head_loss).  With the detection loss, metrics takes the
+    VoxelNetLoss or 'voxelnet', a DetectionIoULossSpec (lisec_detection_iou_loss) for a VoxelNetIoULoss or
+    'voxelnet_iou'; otherwise a LossSpec (lisec_head_loss).  With the detection loss, metrics takes the
     detection metrics of lisec_amd/metrics.py and only those (metrics.compile_detection_metrics: a flat list routes each
     metric to its own output); with every other loss, the Keras metrics and only those.  Every refusal is raised here:
     ValueError (unknown name, unknown output key, a list of the wrong length, a VoxelNetLoss given per output, a
@@ -464,6 +536,9 @@ def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     joint = _joint_loss(loss)
     if joint is not None:
         mterms, names = metrics_mod.compile_detection_metrics(metrics)
+        if isinstance(joint, VoxelNetIoULoss):
+            return DetectionIoULossSpec(joint.params(), _weights(loss_weights), mterms, names,
+                                        iou_weight=joint.iou_weight, iou_mode=joint.iou_mode), list(names)
         return DetectionLossSpec(joint.params(), _weights(loss_weights), mterms, names), list(names)
     legacy = _legacy_key(loss)
     if legacy is not None:

@@ -489,7 +489,8 @@ class Model:
         loss: a tf.keras 2.4 loss (a name or a losses.* object; see lisec_amd/losses.py) for both outputs, a list of two in
         output order or a dict keyed by 'ClassificationLayer' / 'RegressionLayer'; also the project's 'smoothl1_ce' (=
         ['cross_entropy', 'smooth_l1']: sigmoid cross-entropy on labels clamped to [0, 1] + SmoothL1), or -- as the whole
-        argument only -- losses.VoxelNetLoss(...) / 'voxelnet', the detection loss the 0/1/2 label code was made for (one
+        argument only -- losses.VoxelNetLoss(...) / 'voxelnet', the detection loss the 0/1/2 label code was made for, or
+        losses.VoxelNetIoULoss(...) / 'voxelnet_iou', the same with a rotated-box IoU term in its regression part (one
         loss of both outputs; loss_weights apply; metrics: the detection metrics of lisec_amd/metrics.py -- 'anchor_precision',
         'anchor_recall', 'anchor_accuracy', 'positive_mae', 'positive_iou' or their objects -- and only those, a flat list
         routing each to the output it belongs to, unlike Keras).  loss_weights: a list

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, lr_schedules, ops, optimizer_table
-from .losses import DetectionLossSpec, LossSpec
+from .losses import DetectionIoULossSpec, DetectionLossSpec, LossSpec
 from .params import DECONVS, MID, RPN_BLOCKS, ParamStore, fold_depth
 from .vfe import VFEStack
 
@@ -1194,16 +1194,18 @@ class LisecNet:
     def _loss_backward(self, loss, y_cls, y_reg, grad_scale):
         """The loss of the head map against the targets into loss_out (a LossSpec: and its metrics into metric_out), its
         gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*), a LossSpec (lisec_head_loss*) or a
-        DetectionLossSpec (lisec_detection_loss*, its counts into loss_counts, and lisec_detection_metrics, its metric
-        pairs into metric_pairs): this, loss_eval(), step_metrics() and loss_acc_len() with its two readers (loss_acc_logs,
+        DetectionLossSpec (lisec_detection_loss*, or lisec_detection_iou_loss* for the DetectionIoULossSpec among them; its
+        counts into loss_counts, and lisec_detection_metrics, its metric pairs into metric_pairs): this, loss_eval(),
+        step_metrics() and loss_acc_len() with its two readers (loss_acc_logs,
         loss_acc_split) are the only code that tells them apart."""
         head, dhead, M = self.act["head"], self.dact["head"], self.Ho * self.Wo
         if isinstance(loss, LossSpec):
             ops.head_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.metric_out,
                           grad_scale=grad_scale)
         elif isinstance(loss, DetectionLossSpec):
-            ops.detection_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.loss_counts,
-                               grad_scale=grad_scale)
+            run = ops.detection_iou_loss if isinstance(loss, DetectionIoULossSpec) else ops.detection_loss
+            run(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.loss_counts,
+                grad_scale=grad_scale)
             if loss.n_metrics:
                 ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, self.metric_pairs)
         else:
@@ -1216,7 +1218,8 @@ class LisecNet:
         if isinstance(loss, LossSpec):
             ops.head_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
         elif isinstance(loss, DetectionLossSpec):
-            ops.detection_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
+            run = ops.detection_iou_loss_eval if isinstance(loss, DetectionIoULossSpec) else ops.detection_loss_eval
+            run(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
             if loss.n_metrics:
                 ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, acc[4:], accumulate=True)
         else:

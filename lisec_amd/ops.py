@@ -468,6 +468,27 @@ def detection_loss_eval(cfg, head, y_cls, y_reg, M, acc):
                                                      M, _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
 
 
+def detection_iou_loss(cfg, head, y_cls, y_reg, M, dhead, loss_out, counts_out, grad_scale=1.0):
+    """The detection loss with the IoU term of cfg (an _lib.DetectionIoULossCfg, lisec_detection_iou_loss_cfg): the
+    outputs of detection_loss, the IoU term inside the regression value and gradient."""
+    ws = _ew_workspace(head.device)
+    assert ws.numel() >= _lib.load().lisec_detection_iou_loss_workspace_bytes()
+    _lib.check(_lib.load().lisec_detection_iou_loss(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                                                    grad_scale, _lib.ptr(dhead), _lib.ptr(loss_out),
+                                                    _lib.ptr(counts_out), _lib.ptr(ws), ws.numel(),
+                                                    _lib.current_stream()))
+
+
+def detection_iou_loss_eval(cfg, head, y_cls, y_reg, M, acc):
+    """Adds the [total, class, regression] detection_iou_loss would write (the same fp32 bits) to acc[0:3] and counts the
+    sweep in acc[3] (float64[4] device tensor); no gradient."""
+    ws = _ew_workspace(head.device)
+    assert ws.numel() >= _lib.load().lisec_detection_iou_loss_workspace_bytes()
+    _lib.check(_lib.load().lisec_detection_iou_loss_eval(ctypes.byref(cfg), _lib.ptr(head), _lib.ptr(y_cls),
+                                                         _lib.ptr(y_reg), M, _lib.ptr(acc), _lib.ptr(ws), ws.numel(),
+                                                         _lib.current_stream()))
+
+
 def detection_metrics(cfg, head, y_cls, y_reg, M, out, accumulate=False):
     """The detection metrics of cfg (an _lib.DetectionMetricsCfg, lisec_detection_metrics_cfg) as pairs of sums over the
     sweep's anchors: out (float64 device tensor) = [num0, den0, num1, den1, ...], stored, or added with accumulate."""

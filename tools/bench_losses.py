@@ -1,13 +1,14 @@
 """The loss kernels on the Lyft head (M = 100*200 cells): the legacy pair (k_loss + k_loss_finalize, lisec_rpn_loss) against
 lisec_head_loss (k_head_loss + k_head_loss_finalize, csrc/losses.hip) and lisec_detection_loss (k_det_count + k_det_loss +
 k_det_finalize, csrc/detection_loss.hip; with metrics also lisec_detection_metrics: k_detm_anchors + k_detm_finalize,
-csrc/detection_metrics.hip) for the configurations of Model.compile below, each
+csrc/detection_metrics.hip) and lisec_detection_iou_loss (the same with k_det_iou ahead of the finalize,
+csrc/detection_iou_loss.hip) for the configurations of Model.compile below, each
 timed over back-to-back launches with device events; then a short Model.fit on U20k sweeps under each, timed per step
 (GPU box only).  Run it under `rocprofv3 --kernel-trace --stats` for the kernel times: --config restricts the run to
 one configuration, so that the per-kernel statistics of a profile hold that configuration alone.
 
-    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics|voxelnet|voxelnet_focal|voxelnet_metrics] [--iters 500]
-                                  [--fit-steps 20] [--repeats 1]
+    python tools/bench_losses.py [--config all|mse|smoothl1_ce|keras|keras_metrics|voxelnet|voxelnet_focal|voxelnet_metrics|
+                                            voxelnet_iou] [--iters 500] [--fit-steps 20] [--repeats 1]
 
   mse             loss=['mse','mse']                          lisec_rpn_loss kind 0 (the reference's step)
   smoothl1_ce     loss='smoothl1_ce'                          lisec_rpn_loss kind 1
@@ -16,6 +17,7 @@ one configuration, so that the per-kernel statistics of a profile hold that conf
   voxelnet        loss='voxelnet' (VoxelNetLoss(): gamma 0)           lisec_detection_loss
   voxelnet_focal  VoxelNetLoss(alpha=0.5, beta=1.5, gamma=2.0)        lisec_detection_loss, the pow() path
   voxelnet_metrics  loss='voxelnet' with the five detection metrics   lisec_detection_loss + lisec_detection_metrics
+  voxelnet_iou    VoxelNetIoULoss(iou_mode='3d')                      lisec_detection_iou_loss
 
 --repeats N times the fit N times per configuration and prints each: the run-to-run spread."""
 import argparse
@@ -34,7 +36,7 @@ K, Mx = mt.losses, mt.metrics
 
 
 def _configs():
-    return {
+    configs = {
         "mse": dict(loss=["mse", "mse"]),
         "smoothl1_ce": dict(loss="smoothl1_ce"),
         "keras": dict(loss=[K.BinaryCrossentropy(from_logits=True), K.Huber()]),
@@ -45,6 +47,9 @@ def _configs():
         "voxelnet_metrics": dict(loss="voxelnet", metrics=["anchor_precision", "anchor_recall", "anchor_accuracy",
                                                            "positive_mae", "positive_iou"]),
     }
+    if hasattr(K, "VoxelNetIoULoss"):                # absent from a parent commit the tool is run against
+        configs["voxelnet_iou"] = dict(loss=K.VoxelNetIoULoss(iou_mode="3d"))
+    return configs
 
 
 def _kernel_time(step_loss, head, yc, yr, M, iters):
@@ -62,8 +67,11 @@ def _kernel_time(step_loss, head, yc, yr, M, iters):
         mdesc = step_loss.metrics_descriptor()
         pairs = torch.zeros(16, dtype=torch.float64, device=dev)
 
+        with_iou = isinstance(step_loss, getattr(K, "DetectionIoULossSpec", ()))
+        run = ops.detection_iou_loss if with_iou else ops.detection_loss
+
         def call():
-            ops.detection_loss(desc, head, yc, yr, M, dhead, loss_out, counts)
+            run(desc, head, yc, yr, M, dhead, loss_out, counts)
             if mdesc is not None:
                 ops.detection_metrics(mdesc, head, yc, yr, M, pairs)
     else:
