@@ -1107,6 +1107,51 @@ int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_
                                   double* out_ap, double* out_curve, lisec_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 5b. Many-box detection output (csrc/detect.hip): score cut, exact top-N, greedy rotated NMS over those N, capped.
+ *     Not in the reference, whose rpnToRegion loop (lisec_rpn_to_region, section 5) stays what it is; this is the path a
+ *     lidar detector's users expect (VoxelNet, SECOND, PointPillars post-processing).  cls, reg, the anchor grid and the
+ *     candidate order are lisec_rpn_decode's: candidate i = a * M + m (anchor a, cell m = ix * outY + iy, M = outX * outY)
+ *     reads the score cls[m * cls_stride + a] and the seven values reg[m * reg_stride + 7 a ..], and decodes to the row
+ *     lisec_rpn_decode writes at i (the same expression; csrc/box_geom.h).
+ *
+ *  1. Filter and key, one thread per candidate.  A candidate passes when its raw score s (float32) is not NaN and
+ *     (double)s > score_threshold, its seven decoded values are finite, its three extents are > 0 and, with inside_only,
+ *     0 <= x <= outX * vx and 0 <= y <= outY * vy.  A passing candidate gets the 64-bit key (o(s) << 32) | i, where o maps
+ *     the bits u of s to ~u for a set sign bit and to u | 0x80000000 otherwise: unsigned order of o = numeric order of s
+ *     (-0.0 below +0.0).  Keys are distinct; equal scores rank the LARGER flat index first (rpnToRegion's tie rule).
+ *     A failing candidate gets key 0, which no passing one has.
+ *  2. Exact top-N: with P = the number of passing candidates, the L = min(pre_nms_top_n, P) largest keys, found by radix
+ *     selection (8-bit digits, integer histograms) and sorted by descending key; rank r = the r-th of them.  Ranks are
+ *     decoded to float64 rows; their score is (double)s, or 1 / (1 + exp(-(double)s)) with sigmoid_scores.
+ *  3. Suppression matrix: bit b of mask[i][w] is set iff j = 64 w + b satisfies i < j < L and
+ *     IoU(box_i, box_j) > iou_threshold, IoU = that of lisec_boxes_match under iou_mode.
+ *  4. Greedy reduce in rank order: rank i is kept iff no kept rank before it has bit i set in its row; it stops after
+ *     max_boxes kept ranks or at L.  Kept rank number k writes out_boxes[7 k ..], out_scores[k] and out_index[k] = its flat
+ *     candidate index i; out_count = {kept, P}.  Nothing past the kept entries is written.
+ *  Integers and float64 in a fixed order, no floating-point atomics: bit-identical from run to run.  Four launches on
+ *  `stream`, no host synchronisation.  LISEC_EINVAL, nothing enqueued: a NULL pointer, a bad grid, cls_stride < 2,
+ *  reg_stride < 14, pre_nms_top_n outside 1..LISEC_DETECT_MAX_TOP_N (one wave64 holds the removed set of the greedy reduce:
+ *  64 lanes x 64 bits), max_boxes outside 1..pre_nms_top_n, iou_threshold outside [0, 1) or NaN, a NaN score_threshold, an
+ *  iou_mode, sigmoid_scores or inside_only that is none of its values.  LISEC_ENOSPC: workspace_bytes below
+ *  lisec_detect_workspace_bytes (0 for arguments that would be refused). */
+#define LISEC_DETECT_MAX_TOP_N 4096
+typedef struct {
+    double score_threshold;  /* compared with the RAW head value: kept iff (double)raw > score_threshold; -INFINITY: none */
+    int    sigmoid_scores;   /* 1: out_scores = 1/(1+exp(-raw)) in fp64, 0: raw.  Ranking is always by raw. */
+    int    pre_nms_top_n;    /* 1..4096 */
+    int    max_boxes;        /* 1..pre_nms_top_n */
+    double iou_threshold;    /* [0,1): a candidate is suppressed when IoU with a KEPT higher-ranked box > this */
+    int    iou_mode;         /* LISEC_IOU_BEV | LISEC_IOU_3D: pair_iou of csrc/box_geom.h, the IoU the AP uses */
+    int    inside_only;      /* 1: drop candidates whose decoded centre lies outside [0,outX*vx] x [0,outY*vy] */
+} lisec_detect_cfg;
+size_t lisec_detect_workspace_bytes(const lisec_rpn_cfg* cfg, const lisec_detect_cfg* det);
+int lisec_detect(const lisec_rpn_cfg* cfg, const lisec_detect_cfg* det, const float* cls, int cls_stride, const float* reg,
+                 int reg_stride, void* workspace, size_t workspace_bytes, double* out_boxes /* [max_boxes*7] */,
+                 double* out_scores /* [max_boxes] */, int32_t* out_index /* [max_boxes] flat candidate index a*M+m */,
+                 int32_t* out_count /* [2]: kept, candidates that passed the filters before the top-N cut */,
+                 lisec_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * 5c. Training-time augmentation of a sweep with its boxes (VoxelNet section 3.3) and the label maps of the moved boxes,
  *     on the device (csrc/augment.hip).  Not in the reference, which trains on fixed sweeps and precomputed labels.
  *     Box rows are (x, y, z, l, w, h, yaw) float64 in ego-centred metres as boxes.annotationBoxes returns them; z is the box

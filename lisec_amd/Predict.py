@@ -28,12 +28,15 @@ def predictMain(samples, outPath, level5Data, model, dataDir=None):
         np.save(os.path.join(outPath, 'sample' + str(i) + '_regress.npy'), regress)
 
 
-def _detect(samples, level5Data, model, dataDir=None, maxBoxes=20, overlapThresh=0.):
-    """The per-sample loop scoreMain and detectionAP share, without leaving the device: predict, decode + NMS on the head
-    views (boxes.rpnToRegion), the shift to ego-centred metres (rpnToRegion.py:279-280).  Returns ([boxes (k, 7)],
-    [probabilities (k,)]) as device tensors and [annotationBoxes] -- the counts come back in ONE copy at the end."""
+def _detect(samples, level5Data, model, dataDir=None, maxBoxes=20, overlapThresh=0., detector=None, with_labels=True):
+    """The per-sample loop scoreMain, detectionAP and detectMain share, without leaving the device: predict, decode + NMS on
+    the head views, the shift to ego-centred metres (rpnToRegion.py:279-280).  detector=None: boxes.rpnToRegion, the
+    reference's loop, with maxBoxes and overlapThresh; a dict: boxes.detect with these keyword arguments.  Returns
+    ([boxes (k, 7)], [scores (k,)]) as device tensors and [annotationBoxes] -- the counts come back in ONE copy at the end."""
     import torch
     from . import boxes
+    if detector is not None and "as_device" in detector:
+        raise ValueError("the detector's results stay on the device here: as_device is not one of its arguments")
     dataDir = dataDir if dataDir is not None else Constants.lyft_data_dir
     found, probs, counts, labels = [], [], [], []
     for sample in samples:
@@ -42,14 +45,19 @@ def _detect(samples, level5Data, model, dataDir=None, maxBoxes=20, overlapThresh
                                 Constants.nx // 2, Constants.ny // 2, Constants.nz)
         for s in model._as_samples(vfe):
             cls, reg = model.net.forward(s, training=False)
-            b, p, count = boxes.rpnToRegion(cls[0], reg[0], maxBoxes=maxBoxes, overlapThresh=overlapThresh,
-                                            as_device=True)              # before the next forward reuses the head
+            if detector is None:
+                b, p, count = boxes.rpnToRegion(cls[0], reg[0], maxBoxes=maxBoxes, overlapThresh=overlapThresh,
+                                                as_device=True)          # before the next forward reuses the head
+            else:
+                b, p, _, count = boxes.detect(cls[0], reg[0], as_device=True, **detector)
+                count = count[:1]
             b[:, 0] -= 50
             b[:, 1] -= 50
             found.append(b)
             probs.append(p)
             counts.append(count)
-        labels.append(boxes.annotationBoxes(sample, level5Data))
+        if with_labels:
+            labels.append(boxes.annotationBoxes(sample, level5Data))
     counts = torch.cat(counts).cpu().tolist() if counts else []
     return [b[:k] for b, k in zip(found, counts)], [p[:k] for p, k in zip(probs, counts)], labels
 
@@ -68,13 +76,34 @@ def scoreMain(samples, level5Data, model, dataDir=None):
     return [(float(r[0]) / (float(r[3]) + float(r[4]) - float(r[0])), boxes._bev(r)) for r in out]
 
 
-def detectionAP(samples, level5Data, model, iou_thresholds=None, mode='3d', maxBoxes=20, overlapThresh=0., dataDir=None):
+def detectMain(samples, level5Data, model, dataDir=None, **detector):
+    """The detections of a list of samples: predict, then boxes.detect on the head views with the keyword arguments given
+    (score_threshold, pre_nms_top_n, max_boxes, iou_threshold, iou_mode, from_logits, inside_only), in ego-centred metres
+    (the same -50 shift as scoreMain).  Returns [(boxes (k, 7), scores (k,))] per sample, float64 arrays in descending
+    score.  Nothing waits for the GPU inside the loop: the counts come back in one copy at the end, then the rows."""
+    import torch
+    found, scores, _ = _detect(samples, level5Data, model, dataDir, detector=detector, with_labels=False)
+    if not found:
+        return []
+    rows = torch.cat([torch.cat([b, s[:, None]], dim=1) for b, s in zip(found, scores)]).cpu().numpy()
+    out, at = [], 0
+    for b in found:
+        out.append((rows[at:at + len(b), :7].copy(), rows[at:at + len(b), 7].copy()))
+        at += len(b)
+    return out
+
+
+def detectionAP(samples, level5Data, model, iou_thresholds=None, mode='3d', maxBoxes=20, overlapThresh=0., dataDir=None,
+                detector=None):
     """The data set's detection metric for a list of samples: the same loop as scoreMain with the class probabilities kept
     as scores, then ONE boxes.average_precision call over all samples -- average precision of the score-ranked boxes
     against the car annotations at the 3D IoU thresholds 0.5, 0.55, .., 0.95 and their mean (mAP).  Returns
-    boxes.DetectionAP.  Ours: the reference has no such check, and parity with the Lyft devkit is unpinned."""
+    boxes.DetectionAP.  Ours: the reference has no such check, and parity with the Lyft devkit is unpinned.
+    detector=None ranks the maxBoxes boxes of boxes.rpnToRegion, the reference's loop; a dict of boxes.detect's keyword
+    arguments (e.g. dict(score_threshold=0.3, from_logits=True, max_boxes=300)) ranks that path's detections instead, and
+    maxBoxes and overlapThresh are not used."""
     from . import boxes
-    found, probs, labels = _detect(samples, level5Data, model, dataDir, maxBoxes, overlapThresh)
+    found, probs, labels = _detect(samples, level5Data, model, dataDir, maxBoxes, overlapThresh, detector)
     return boxes.average_precision(found, probs, labels, iou_thresholds=iou_thresholds, mode=mode)
 
 

@@ -31,6 +31,14 @@ class RpnCfg(Structure):
                 ("anchors", (c_double * 4) * 2)]
 
 
+class DetectCfg(Structure):                    # lisec_detect_cfg
+    _fields_ = [("score_threshold", c_double), ("sigmoid_scores", c_int), ("pre_nms_top_n", c_int), ("max_boxes", c_int),
+                ("iou_threshold", c_double), ("iou_mode", c_int), ("inside_only", c_int)]
+
+
+DETECT_MAX_TOP_N = 4096                        # LISEC_DETECT_MAX_TOP_N
+
+
 class AugmentParams(Structure):                # lisec_augment_params
     _fields_ = [("rot_box", c_double), ("sigma", c_double * 3), ("scale_lo", c_double), ("scale_hi", c_double),
                 ("rot_global", c_double), ("attempts", c_int)]
@@ -195,6 +203,10 @@ def _declare(lib):
     lib.lisec_boxes_pair_iou.argtypes = [P, P, P, P, c_int, c_int, LL, c_int, P, c_size_t, P, P]
     lib.lisec_boxes_average_precision.restype = c_int
     lib.lisec_boxes_average_precision.argtypes = [P, P, c_int, c_int, c_int, P, P, P]
+    lib.lisec_detect_workspace_bytes.restype = c_size_t
+    lib.lisec_detect_workspace_bytes.argtypes = [POINTER(RpnCfg), POINTER(DetectCfg)]
+    lib.lisec_detect.restype = c_int
+    lib.lisec_detect.argtypes = [POINTER(RpnCfg), POINTER(DetectCfg), P, c_int, P, c_int, P, c_size_t, P, P, P, P, P]
     ULL, UI = ctypes.c_ulonglong, ctypes.c_uint
     lib.lisec_augment_draw.restype = c_int
     lib.lisec_augment_draw.argtypes = [P, c_int, POINTER(AugmentParams), ULL, UI, UI, P, P, P, P, P, P]

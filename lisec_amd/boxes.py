@@ -54,6 +54,58 @@ def rpnToRegion(labelsClass, labelsRegress, maxBoxes=20, overlapThresh=0., as_de
     return boxes[:k].cpu().numpy(), probs[:k].cpu().numpy()
 
 
+def _count(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= value <= hi:
+        raise ValueError(f"{name} must be an integer in {lo}..{hi}, not {value!r}")
+    return int(value)
+
+
+def detect(labelsClass, labelsRegress, score_threshold=None, pre_nms_top_n=1000, max_boxes=100, iou_threshold=0.1,
+           iou_mode='bev', from_logits=False, inside_only=True, as_device=False):
+    """detect(labelsClass (100,200,2), labelsRegress (100,200,14)) -> (boxes (k,7) float64, scores (k,)) in descending score:
+    the many-box path from the head to detections (lisec_detect; ours, rpnToRegion is the reference's).  The candidates
+    above score_threshold whose decoded box is finite with positive extents (and, with inside_only, centred inside the
+    grid) are cut to the pre_nms_top_n best, equal scores by the larger flat index as in rpnToRegion; greedy rotated NMS
+    over those keeps a candidate unless a KEPT better one overlaps it with box_iou(mode=iou_mode) > iou_threshold, and stops
+    at max_boxes.  Inputs are numpy arrays or device tensors, as for rpnToRegion.
+    from_logits=False: the head is the reference's linear one; score_threshold is compared with the raw values, which are
+    the scores returned.  from_logits=True: a head trained with VoxelNetLoss; score_threshold is a probability in (0, 1)
+    (compared as the logit log(t / (1 - t)) with the raw values) and the scores returned are sigmoids.  None: no threshold.
+    as_device=True returns (boxes (max_boxes,7), scores (max_boxes,), index (max_boxes,) int32 flat candidate index a*M+m,
+    count (2,) int32 = kept, candidates that passed the filters) as device tensors, zero past the first `kept` rows,
+    without waiting for the GPU.  pre_nms_top_n is at most 4096, max_boxes at most pre_nms_top_n."""
+    from . import ops
+    top_n = _count(pre_nms_top_n, "pre_nms_top_n", 1, _lib.DETECT_MAX_TOP_N)
+    cap = _count(max_boxes, "max_boxes", 1, top_n)
+    try:
+        iou_t = float(iou_threshold)
+        score_t = -math.inf if score_threshold is None else float(score_threshold)
+    except (TypeError, ValueError):
+        raise ValueError("score_threshold and iou_threshold must be numbers") from None
+    if not 0.0 <= iou_t < 1.0:
+        raise ValueError(f"iou_threshold must lie in [0, 1), not {iou_threshold!r}")
+    if from_logits and score_threshold is not None:
+        if not 0.0 < score_t < 1.0:
+            raise ValueError(f"with from_logits the score_threshold is a probability in (0, 1), not {score_threshold!r}")
+        score_t = math.log(score_t / (1.0 - score_t))
+    if math.isnan(score_t):
+        raise ValueError("score_threshold must not be NaN")
+    det = ops.detect_params(score_t, bool(from_logits), top_n, cap, iou_t, _iou_mode(iou_mode), bool(inside_only))
+    dev = _lib.require_gpu()
+    cfg = _cfg()
+    cls = torch.as_tensor(labelsClass, dtype=torch.float32).to(dev)
+    reg = torch.as_tensor(labelsRegress, dtype=torch.float32).to(dev)
+    cls = cls.reshape(cfg.outX, cfg.outY, -1)
+    reg = reg.reshape(cfg.outX, cfg.outY, -1)
+    if cls.stride(-1) != 1 or reg.stride(-1) != 1:
+        cls, reg = cls.contiguous(), reg.contiguous()
+    boxes, scores, index, count = ops.detect(cfg, det, cls, reg)
+    if as_device:
+        return boxes, scores, index, count
+    k = int(count[0].item())
+    return boxes[:k].cpu().numpy(), scores[:k].cpu().numpy()
+
+
 def preprocessLabels(data, seed=0, balance=True):
     """preprocessLabels(data (B,7) rows x,y,z,l,w,h,yaw) -> [outClass (100,200,2), outRegress (100,200,14)]
     float64 (serialize_data.py:194-338).  The anchors x boxes IoU sweep runs on the GPU; the region balancing of

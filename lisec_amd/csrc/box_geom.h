@@ -84,6 +84,26 @@ __device__ inline double pair_iou(const double* p, const double* g, int mode) {
     return uni > 0.0 ? inter / uni : 0.0;
 }
 
+// Candidate i = a * M + m of the anchor grid (anchor a, cell m = ix * outY + iy) decoded to its box b[7]: the anchor at the
+// cell centre with applyRegrssion on top (rpnToRegion.py:75-150).  k_rpn_decode (boxes.hip) and the detection output
+// (detect.hip) share it.
+__device__ __forceinline__ void rpn_decode_box(const lisec_rpn_cfg& cfg, const float* __restrict__ reg, int reg_stride, int i,
+                                               double* __restrict__ b) {
+    const int M = cfg.outX * cfg.outY;
+    const int a = i / M, m = i - a * M;
+    const int ix = m / cfg.outY, iy = m - ix * cfg.outY;
+    const double* an = cfg.anchors[a];
+    const float* t = reg + (size_t)m * reg_stride + a * 7;
+    const double x = ix * cfg.vx + cfg.vx / 2, y = iy * cfg.vy + cfg.vy / 2;
+    b[0] = (double)t[0] * an[0] + x;
+    b[1] = (double)t[1] * an[1] + y;
+    b[2] = (double)t[2] * an[2] + 1.0;
+    b[3] = exp((double)t[3]) * an[0];
+    b[4] = exp((double)t[4]) * an[1];
+    b[5] = exp((double)t[5]) * an[2];
+    b[6] = (double)t[6] + an[3];
+}
+
 __device__ __forceinline__ bool finite7(const double* b) {
     return isfinite(b[0]) && isfinite(b[1]) && isfinite(b[2]) && isfinite(b[3]) && isfinite(b[4]) && isfinite(b[5]) &&
            isfinite(b[6]);

@@ -63,18 +63,8 @@ __global__ void k_rpn_decode(const float* __restrict__ cls, int cls_stride, cons
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * M) return;
     const int a = i / M, m = i - a * M;
-    const int ix = m / cfg.outY, iy = m - ix * cfg.outY;
-    const double* an = cfg.anchors[a];
-    const float* t = reg + (size_t)m * reg_stride + a * 7;
-    const double x = ix * cfg.vx + cfg.vx / 2, y = iy * cfg.vy + cfg.vy / 2;
     double* b = boxes + (size_t)i * 7;
-    b[0] = (double)t[0] * an[0] + x;
-    b[1] = (double)t[1] * an[1] + y;
-    b[2] = (double)t[2] * an[2] + 1.0;
-    b[3] = exp((double)t[3]) * an[0];
-    b[4] = exp((double)t[4]) * an[1];
-    b[5] = exp((double)t[5]) * an[2];
-    b[6] = (double)t[6] + an[3];
+    rpn_decode_box(cfg, reg, reg_stride, i, b);
     probs[i] = (double)cls[(size_t)m * cls_stride + a];
     alive[i] = !(b[3] < 0 || b[4] < 0 || b[5] < 0);          // "remove illegal boxes" (rpnToRegion.py:155-158)
 }

@@ -713,6 +713,36 @@ class HeadShuffle:
                                                   1 if backward else 0, _lib.current_stream()))
 
 
+# ---- many-box detection output (include/lisec_hip.h section 5b) -----------------------------------------------------------
+def detect_params(score_threshold=-math.inf, sigmoid_scores=False, pre_nms_top_n=1000, max_boxes=100, iou_threshold=0.1,
+                  iou_mode=1, inside_only=True):
+    """lisec_detect_cfg; iou_mode 0 = LISEC_IOU_3D, 1 = LISEC_IOU_BEV.  Nothing is checked here: lisec_detect refuses."""
+    d = _lib.DetectCfg()
+    d.score_threshold, d.iou_threshold = float(score_threshold), float(iou_threshold)
+    d.sigmoid_scores, d.inside_only, d.iou_mode = int(bool(sigmoid_scores)), int(bool(inside_only)), int(iou_mode)
+    d.pre_nms_top_n, d.max_boxes = int(pre_nms_top_n), int(max_boxes)
+    return d
+
+
+def detect(cfg, det, cls, reg):
+    """lisec_detect on device maps cls (outX, outY, >= 2) and reg (outX, outY, >= 14) float32 with unit element stride.
+    Returns device tensors (boxes (max_boxes, 7) float64, scores (max_boxes,) float64, index (max_boxes,) int32, count (2,)
+    int32 = kept, passing), zero past the kept rows, without waiting for the GPU."""
+    lib, dev = _lib.load(), cls.device
+    nbytes = lib.lisec_detect_workspace_bytes(ctypes.byref(cfg), ctypes.byref(det))
+    if nbytes == 0:
+        raise _lib.LisecError(f"lisec C ABI error -1: {lib.lisec_last_error().decode()}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    boxes = torch.zeros((det.max_boxes, 7), dtype=torch.float64, device=dev)
+    scores = torch.zeros(det.max_boxes, dtype=torch.float64, device=dev)
+    index = torch.zeros(det.max_boxes, dtype=torch.int32, device=dev)
+    count = torch.zeros(2, dtype=torch.int32, device=dev)
+    _lib.check(lib.lisec_detect(ctypes.byref(cfg), ctypes.byref(det), _lib.ptr(cls), cls.stride(1), _lib.ptr(reg),
+                                reg.stride(1), _lib.ptr(ws), nbytes, _lib.ptr(boxes), _lib.ptr(scores), _lib.ptr(index),
+                                _lib.ptr(count), _lib.current_stream()))
+    return boxes, scores, index, count
+
+
 # ---- training-time augmentation (include/lisec_hip.h section 5c) ----------------------------------------------------------
 def augment_params(rot_box=math.pi / 10, sigma=(1.0, 1.0, 0.0), scale=(0.95, 1.05), rot_global=math.pi / 4, attempts=10):
     """lisec_augment_params with VoxelNet's defaults (section 3.3 of the paper; z noise 0: the grid is 2 m tall)."""

@@ -1,6 +1,7 @@
 """Timing of the two "next" rows around the hot path: label generation (serialize_data.py:194-338) and RPN decode +
 rotated NMS (rpnToRegion.py:18-164) on the GPU, with the CPU oracle (the reference's algorithm with the shapely polygon
-clipping restated) beside it on a reduced case.  GPU box only."""
+clipping restated) beside it on a reduced case, and the many-box path (boxes.detect) beside rpnToRegion on the same maps with a
+per-kernel breakdown.  GPU box only.  `--detect` prints the decode + NMS rows alone."""
 import os
 import sys
 import time
@@ -30,8 +31,53 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def kernel_breakdown(fn, reps=20):
+    """Mean device time per call of each k_detect_* kernel (microseconds), from the profiler's kernel records."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+    rows = {}
+    for e in prof.key_averages():
+        if "k_detect_" in e.key:
+            name = e.key[e.key.index("k_detect_"):].split("(")[0]
+            rows[name] = rows.get(name, 0.0) + e.device_time_total / reps
+    if len(rows) != 4:
+        raise RuntimeError(f"the profiler recorded {sorted(rows)} instead of the four k_detect_* kernels")
+    return rows
+
+
+def detect_lines(cls, reg):
+    """boxes.detect beside rpnToRegion on the same 40 000-candidate maps, both timed by `timed` in this run."""
+    base = {}
+    for mb in (20, 100):
+        base[mb] = timed(lambda: boxes.rpnToRegion(cls, reg, maxBoxes=mb), 5)
+        print(f"rpnToRegion  40 000 candidates, maxBoxes {mb:3d}   GPU {base[mb] * 1e3:8.2f} ms")
+    for top_n, mb in ((1000, 20), (1000, 100), (1000, 300), (4096, 300)):
+        t = timed(lambda: boxes.detect(cls, reg, pre_nms_top_n=top_n, max_boxes=mb), 20)
+        beside = f"   ({base[mb] / t:5.1f} x rpnToRegion maxBoxes {mb})" if mb in base else ""
+        print(f"detect       40 000 candidates, top-N {top_n:4d}, max_boxes {mb:3d}   GPU {t * 1e3:8.3f} ms{beside}")
+    d_cls, d_reg = torch.from_numpy(cls[0]).cuda(), torch.from_numpy(reg[0]).cuda()
+    for top_n, mb in ((1000, 100), (4096, 300)):
+        call = lambda: boxes.detect(d_cls, d_reg, pre_nms_top_n=top_n, max_boxes=mb, as_device=True)
+        t = timed(call, 50)
+        rows = kernel_breakdown(call)
+        print(f"detect       device maps, as_device, top-N {top_n:4d}, max_boxes {mb:3d}   GPU {t * 1e3:8.3f} ms per call;  kernels: "
+              + ", ".join(f"{k} {v:.1f} us" for k, v in sorted(rows.items())) + f", sum {sum(rows.values()):.1f} us")
+
+
 if __name__ == "__main__":
     rng = np.random.default_rng(0)
+    if "--detect" in sys.argv:                                 # the decode + NMS rows alone, on the maps the full run uses
+        for n in (10, 40, 10):
+            scene(rng, n)
+        cls = rng.uniform(0, 1, (1, 100, 200, 2)).astype(np.float32)
+        reg = rng.normal(0, 0.1, (1, 100, 200, 14)).astype(np.float32)
+        detect_lines(cls, reg)
+        sys.exit(0)
     for n in (10, 40):
         data = scene(rng, n)
         t = timed(lambda: boxes.preprocessLabels(data, seed=1), 5)
@@ -42,9 +88,7 @@ if __name__ == "__main__":
     print(f"preprocess_labels  10 boxes   CPU oracle (python, circumradius pre-test)  {time.perf_counter() - t0:8.2f} s")
     cls = rng.uniform(0, 1, (1, 100, 200, 2)).astype(np.float32)
     reg = rng.normal(0, 0.1, (1, 100, 200, 14)).astype(np.float32)
-    for mb in (20, 100):
-        t = timed(lambda: boxes.rpnToRegion(cls, reg, maxBoxes=mb), 5)
-        print(f"rpnToRegion  40 000 candidates, maxBoxes {mb:3d}   GPU {t * 1e3:8.2f} ms")
+    detect_lines(cls, reg)
     t0 = time.perf_counter()
     bi = B.decode_boxes(reg[0].astype(np.float64))
     pi = np.concatenate([cls[0, :, :, a].reshape(-1) for a in range(2)]).astype(np.float64)
