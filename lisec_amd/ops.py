@@ -144,7 +144,7 @@ def _fold_fields(fold):
 
 
 def conv_forward(g, x, wp, out, bias=None, in_bn=None, flags=0, stats=None, splitk=True, rows=None, out_mask=None,
-                 bwd=None, sink=None, ws_tag="main", queue=None, tail=None, fold=None, dense_dw=None):
+                 bwd=None, sink=None, ws_tag="main", queue=None, tail=None, fold=None, dense_dw=None, workspace=None):
     """rows: optional (row_coords int32 (cap,3), row_count int32 device scalar, capacity) row list.
     out_mask: optional tensor laid out like `out`; values are stored as 0 where out_mask <= 0.
     bwd: optional (y, bnstate, relu): `out` is a gradient about to cross that BatchNormalization(+ReLU) backwards and
@@ -157,9 +157,14 @@ def conv_forward(g, x, wp, out, bias=None, in_bn=None, flags=0, stats=None, spli
     fold: optional (y, bnstate, coef, relu): x is a gradient about to cross that BatchNormalization(+ReLU) backwards and the
     apply pass runs on load (lisec_conv_extras.in_y).
     dense_dw: optional float32 tensor of dense_dw_slabs() * 4096 elements: the call is a Dense(64)'s data gradient (bwd + sink)
-    and also leaves the per-workgroup slabs of the Dense's weight gradient there (lisec_conv_extras.dense_dw; dense_dw_reduce)."""
+    and also leaves the per-workgroup slabs of the Dense's weight gradient there (lisec_conv_extras.dense_dw; dense_dw_reduce).
+    workspace: optional uint8 tensor the call uses as its split-K scratch instead of the shared conv_workspace() buffer; its
+    head (the arrival counters) must be zero, and the plan is made for its size."""
     rc, rn, cap = rows if rows is not None else (None, None, 0)
-    ws = conv_workspace(g, out.device, cap, ws_tag) if splitk else None
+    if workspace is not None:
+        ws = workspace
+    else:
+        ws = conv_workspace(g, out.device, cap, ws_tag) if splitk else None
     ex = _lib.ConvExtras(_lib.ptr(out_mask), _lib.ptr(bwd[0]) if bwd is not None else None,
                          _lib.ptr(bwd[1]) if bwd is not None else None, 1 if (bwd is not None and bwd[2]) else 0,
                          sink.ref if sink is not None else None, _lib.ptr(queue),
