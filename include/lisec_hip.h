@@ -976,6 +976,40 @@ int lisec_nadam_step_sched(float* theta, const float* grad, float* m, float* v, 
                            const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon, float schedule_decay,
                            long long* state, int advance, lisec_stream_t stream);
 
+/* Weight regularizers (tf.keras 2.4 regularizers.L1L2; csrc/regularize.hip), run in front of an optimizer entry on the
+ * same range and stream.  The host cuts each regularised variable into ceil(n / LISEC_REG_CHUNK) chunks; a chunk never
+ * crosses a variable, so it carries that variable's (l1, l2).  offset and count are in floats, multiples of 4, offset
+ * relative to the theta / grad pointers given, count <= LISEC_REG_CHUNK.  The table is device memory and is NOT checked:
+ * every [offset, offset + count) must lie inside both buffers.
+ *   grad[i] <- grad[i] + 2*l2*w + l1*sign(w) in fp32 (c2 = 2.0f*l2, sign(0) = 0) for every element of every chunk
+ *   (grad == NULL: the penalty alone); the elements of a (0, 0) chunk and those outside every chunk keep their bits.
+ *   P = sum over chunks of l1*sum|w| + l2*sum w^2: fp64 per thread, wave, workgroup and chunk; the per-chunk partials
+ *   (the workspace) are added by a second one-workgroup launch in an order fixed by n_chunks alone.  No atomics: grad
+ *   and P have the same bits from run to run.
+ *   *penalty = P (accumulate == 0) or *penalty += P (accumulate == 1: the second call of a step whose variables are
+ *   updated in two parts); then, with loss_total != NULL, *loss_total = (float)((double)*loss_total + *penalty), once.
+ * n_chunks == 0 is valid: the penalty is stored as 0 or kept, the fold still happens, only the second launch is made.
+ * Fixed addresses, no host reads, no allocation: both launches record into a step plan.  LISEC_EINVAL, nothing
+ * enqueued: NULL theta, chunks, penalty or workspace, n_chunks < 0, accumulate not 0/1, a workspace below
+ * lisec_regularize_workspace_bytes(n_chunks), theta or grad not 16-byte aligned.
+ * flags = LISEC_REG_GRAD_IS_ZERO: the variable's gradient is identically 0 and NO backward pass writes its slot of grad
+ * (here: the bias of a convolution that feeds a training-mode BatchNormalization), so the slot still holds what the
+ * step before left there; for such a chunk grad[i] <- 2*l2*w + l1*sign(w) is STORED, not added, and grad is not read.
+ * Other bits of flags must be 0 and are ignored. */
+#define LISEC_REG_CHUNK 4096
+#define LISEC_REG_GRAD_IS_ZERO 1
+typedef struct lisec_reg_chunk {
+    long long offset;
+    int count;
+    float l1;
+    float l2;
+    int flags;      /* 0, or LISEC_REG_GRAD_IS_ZERO */
+} lisec_reg_chunk;
+size_t lisec_regularize_workspace_bytes(int n_chunks);
+int lisec_regularize(const float* theta, float* grad /* NULL: penalty only */, const lisec_reg_chunk* chunks /* device */,
+                     int n_chunks, double* penalty /* device [1] */, int accumulate, float* loss_total /* NULL, or device */,
+                     void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+
 /* x *= s  (gradient averaging after the data-parallel all-reduce) */
 int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);
 

@@ -105,6 +105,14 @@ class LrSchedule(Structure):                   # lisec_lr_schedule
                 + [("boundaries", c_double * LR_MAX_BOUNDARIES), ("values", c_double * (LR_MAX_BOUNDARIES + 1))])
 
 
+REG_CHUNK = 4096                               # LISEC_REG_CHUNK
+REG_GRAD_IS_ZERO = 1                           # LISEC_REG_GRAD_IS_ZERO
+
+
+class RegChunk(Structure):                     # lisec_reg_chunk
+    _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("l1", c_float), ("l2", c_float), ("flags", c_int)]
+
+
 LOSS_MAX_METRICS = 4                           # LISEC_LOSS_MAX_METRICS
 
 
@@ -388,6 +396,10 @@ def _declare(lib):
     lib.lisec_nadam_step_dev.argtypes = [P, P, P, P, P, LL, c_double, c_float, c_float, c_float, c_float, P, c_int, P]
     lib.lisec_nadam_step_sched.restype = c_int
     lib.lisec_nadam_step_sched.argtypes = [P, P, P, P, P, LL, P, c_float, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_regularize_workspace_bytes.restype = c_size_t
+    lib.lisec_regularize_workspace_bytes.argtypes = [c_int]
+    lib.lisec_regularize.restype = c_int
+    lib.lisec_regularize.argtypes = [P, P, P, c_int, P, c_int, P, P, c_size_t, P]
     lib.lisec_fold_depth.restype = c_int
     lib.lisec_fold_depth.argtypes = [P, P, c_int, LL, c_int, c_int, P, P]
     lib.lisec_scale.restype = c_int

@@ -15,7 +15,9 @@ Predict.py:51-52).  A Keras `.h5` holds
 This module rebuilds the layer list that createModel (model_training.py:222-257) produces -- with the names Keras
 assigns automatically (dense, dense_1, batch_normalization_7, conv2d_transpose_2 ...) and the order of
 Model.layers (decreasing depth, ties in traversal order) -- maps every Keras variable onto the flat ParamStore
-names of lisec_amd.params, and reads / writes the file through lisec_amd.hdf5_lite.
+names of lisec_amd.params, and reads / writes the file through lisec_amd.hdf5_lite.  Weight regularizers travel where
+Keras keeps them, in the layer configs of model_config (kernel_regularizer / bias_regularizer of Dense, Conv3D, Conv2D and
+Conv2DTranspose, beta_regularizer / gamma_regularizer of BatchNormalization), per variable.
 
 PARITY UNPINNED against Keras itself (TensorFlow is not installed here): the HDF5 container is cross-checked
 against h5py/libhdf5 in tests/test_hdf5_lite.py; the Keras naming rules are restated from Keras' public behaviour.
@@ -26,6 +28,7 @@ import re
 import numpy as np
 
 from . import hdf5_lite, optimizer_table
+from . import regularizers as regularizers_mod
 from .params import DECONVS, MID, RPN_BLOCKS
 
 KERAS_VERSION = "2.4.0"
@@ -184,11 +187,29 @@ def _model_layers_order(layers, outputs):
     return sorted(layers, key=lambda L: (-depth[L["name"]], index[L["name"]]))
 
 
-def model_config(nx, ny, nz, maxPoints):
+REGULARIZED_WEIGHTS = ("kernel", "bias", "gamma", "beta")     # Keras' <weight>_regularizer keys of a layer config
+
+
+def model_config(nx, ny, nz, maxPoints, regularizers=None):
+    """regularizers: {ParamStore name: (l1, l2)} or None.  A layer's config gains "<weight>_regularizer" ({"class_name":
+    "L2", "config": {"l2": ...}}, the shortest of L1 / L2 / L1L2 that says it) only for a variable with a pair other
+    than (0, 0): the config of an unregularised model keeps the bytes it always had.  (Keras itself writes the key
+    with null for a layer without one; load_model reads both.)  KeyError: a name the network does not have; ValueError:
+    a variable that is not trainable (a moving statistic), as ops.reg_chunks refuses it."""
     layers, outs = keras_layers(nx, ny, nz, maxPoints)
+    known = {pname: w for L in layers for w, pname in L["weights"]}
+    for name in regularizers or {}:
+        if name not in known:
+            raise KeyError(f"regularizers: the network has no variable {name!r}")
+        if known[name] not in REGULARIZED_WEIGHTS:
+            raise ValueError(f"regularizers: {name} is not a trainable variable: it cannot be regularised")
     cfg_layers = []
     for L in layers:
         inbound = [[[src, 0, 0, {}] for src in L["inbound"]]] if L["inbound"] else []
+        for w, pname in L["weights"]:
+            reg = regularizers_mod.from_pair(*regularizers[pname]) if pname in (regularizers or {}) else None
+            if w in REGULARIZED_WEIGHTS and reg is not None:
+                L["config"][f"{w}_regularizer"] = regularizers_mod.serialize(reg)
         cfg_layers.append({"class_name": L["class_name"], "config": L["config"], "name": L["name"],
                            "inbound_nodes": inbound})
     return {"class_name": "Functional",
@@ -234,7 +255,7 @@ SLOT_KEYS = optimizer_table.SLOT_NAMES
 
 # ---------------------------------------------------------------------------------------------------
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, loss=None, loss_weights=None,
-               metrics=None, momentum_cache=1.0, **given):
+               metrics=None, momentum_cache=1.0, regularizers=None, **given):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
@@ -245,6 +266,7 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
     (Nadam's decay: schedule_decay); momentum_cache: Nadam's scalar.  optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
     loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
     as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics.
+    regularizers: {ParamStore name: (l1, l2)} or None, written into the layer configs (model_config).
     **given: the slots, by the names of SLOT_KEYS (any other keyword: TypeError)."""
     for k in given:
         if k not in SLOT_KEYS:
@@ -253,7 +275,7 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
     with hdf5_lite.File(path, "w") as f:
         f.attrs["keras_version"] = KERAS_VERSION.encode()
         f.attrs["backend"] = b"tensorflow"
-        f.attrs["model_config"] = json.dumps(model_config(nx, ny, nz, maxPoints)).encode("utf8")
+        f.attrs["model_config"] = json.dumps(model_config(nx, ny, nz, maxPoints, regularizers)).encode("utf8")
         if optimizer is not None:
             f.attrs["training_config"] = json.dumps(_training_config(optimizer, loss, loss_weights,
                                                                      metrics)).encode("utf8")
@@ -319,12 +341,34 @@ def _suffix_number(name, base):
     return int(rest[1:]) if rest else 0
 
 
+def _layer_regularizers(layer_cfg, weights):
+    """{ParamStore name: (l1, l2)} of one layer of a model_config (weights: the layer's [(keras weight, ParamStore
+    name)]).  null or an absent key: none.  NotImplementedError, naming the layer: an activity_regularizer, or a
+    regularizer class other than L1, L2 and L1L2."""
+    c, out = layer_cfg.get("config", {}), {}
+    lname = layer_cfg.get("name", c.get("name"))
+    if c.get("activity_regularizer") is not None:
+        raise NotImplementedError(f"layer {lname}: activity_regularizer is not implemented")
+    for w, pname in weights:
+        ser = c.get(f"{w}_regularizer")
+        if ser is None:
+            continue
+        try:
+            pair = regularizers_mod.deserialize(ser).pair()
+        except (ValueError, TypeError, NotImplementedError) as e:
+            raise NotImplementedError(f"layer {lname}: {w}_regularizer {ser!r} is not implemented ({e})") from None
+        if pair != (0.0, 0.0):
+            out[pname] = pair
+    return out
+
+
 def load_model(path, grid=None):
     """Reads a Keras `.h5` written by the reference (or by save_model).  Returns dict(params, nx, ny, nz, maxPoints,
     iterations, optimizer (dict or None, as save_model takes it), loss, loss_weights, metrics (training_config's, as
     serialized there; None without one), the slots of SLOT_KEYS (each a dict of trainable ParamStore name -> array, or
     None; mapped per optimizer class, so "momentum" is SGD's velocity in an SGD file) and momentum_cache (Nadam's, or
-    None)).  Slots are matched by name, not by position.
+    None)) and regularizers ({ParamStore name: (l1, l2)}, read from each layer's config; {} without any).  Slots are
+    matched by name, not by position.
 
     Layers are matched by class and creation order (the numeric suffix of Keras' automatic names), not by the exact
     suffix: a model built as the second one of a Python session carries shifted suffixes."""
@@ -359,20 +403,26 @@ def load_model(path, grid=None):
             if L["weights"]:
                 base = _base_of(L["name"])
                 want.setdefault(base, []).append((_suffix_number(L["name"], base), L))
-        params, keras_to_param = {}, {}
+        params, keras_to_param, regs = {}, {}, {}
+        file_cfg = {L.get("name", L.get("config", {}).get("name")): L for L in cfg["config"]["layers"]} if cfg else {}
+        for L in file_cfg.values():                   # any layer, with weights or without, may carry one
+            _layer_regularizers(L, ())
         for base, lst in want.items():
             lst.sort(key=lambda t: t[0])
             have = found.get(base, [])
             if len(have) != len(lst):
                 raise hdf5_lite.H5Error(f"{path}: {len(have)} {base} layers with weights, the network has {len(lst)}")
             for (_, L), (_, lname, vals) in zip(lst, have):
+                if lname in file_cfg:
+                    regs.update(_layer_regularizers(file_cfg[lname], L["weights"]))
                 for w, pname in L["weights"]:
                     if w not in vals:
                         raise hdf5_lite.H5Error(f"{path}: layer {lname} lacks {w}")
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
         out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, optimizer=None,
-                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, **{k: None for k in SLOT_KEYS})
+                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, regularizers=regs,
+                   **{k: None for k in SLOT_KEYS})
         if "training_config" in f.attrs:
             tc = json.loads(_text(f.attrs["training_config"]))
             out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))

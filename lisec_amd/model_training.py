@@ -5,7 +5,8 @@
 
 and, for Model.fit / Model.evaluate, the tf.keras 2.4 learning-rate schedules (optimizers.schedules), callbacks
 (callbacks.Callback, LearningRateScheduler, EarlyStopping, ModelCheckpoint, ReduceLROnPlateau), losses and metrics
-(losses.MeanSquaredError, ..., BinaryCrossentropy, Huber; metrics.BinaryAccuracy, ...) of compile().
+(losses.MeanSquaredError, ..., BinaryCrossentropy, Huber; metrics.BinaryAccuracy, ...) of compile(), and the weight
+regularizers (regularizers.l1, l2, l1_l2; createModel(..., kernel_regularizer=...)).
 
 The Keras graph is replaced by lisec_amd.network.LisecNet (HIP kernels behind the C ABI); lidar sweeps
 stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacked in host RAM
@@ -23,10 +24,10 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table
+from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table, regularizers
 from .network import (EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len, loss_acc_logs,
                       loss_acc_split)
-from .params import ParamStore
+from .params import ParamStore, fold_depth, param_specs
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
 
@@ -463,11 +464,27 @@ def _refuse_mixed_training(policy):
 class Model:
     """What createModel returns: the subset of the keras.Model interface the reference uses."""
 
-    def __init__(self, nx, ny, nz, maxPoints, params=None):
+    def __init__(self, nx, ny, nz, maxPoints, params=None, kernel_regularizer=None, bias_regularizer=None,
+                 gamma_regularizer=None, beta_regularizer=None, activity_regularizer=None, variable_regularizers=None):
+        """<kind>_regularizer: anything regularizers.get accepts (None, regularizers.l2(1e-4), 'l2', a {"class_name",
+        "config"} dict), applied to every variable of that kind in params.param_specs() -- what passing it to every layer
+        of the reference's createModel does.  variable_regularizers: {ParamStore name: (l1, l2)}, the per-variable form
+        (what load_model reads from a file whose layers differ); it overrides the per-kind one for the variables it
+        names.  The model keeps the merged dict as self.regularizers (pairs other than (0, 0) only).  The penalty is part of `loss`
+        (not of the per-output losses, not scaled by loss_weights) in fit, evaluate and val_loss.
+        activity_regularizer: NotImplementedError."""
+        if activity_regularizer is not None:
+            raise NotImplementedError("activity_regularizer is not implemented: only the weights can be penalised")
         self.nx, self.ny, self.nz, self.maxPoints = nx, ny, nz, maxPoints
+        coeffs = regularizers.coefficients(param_specs(fold_depth(nz)), kernel=kernel_regularizer, bias=bias_regularizer,
+                                           gamma=gamma_regularizer, beta=beta_regularizer)
+        for name, (a, b) in (variable_regularizers or {}).items():
+            coeffs[name] = regularizers.L1L2(a, b).pair()
+        self.regularizers = {n: p for n, p in coeffs.items() if p != (0.0, 0.0)}
         # tf.keras.mixed_precision: the global policy in force NOW, fixed for the model's life (mixed_precision.py)
         self.dtype_policy = mixed_precision.global_policy()
-        self.net = LisecNet(nx, ny, nz, maxPoints, params=params, compute_dtype=self.dtype_policy.compute_dtype)
+        self.net = LisecNet(nx, ny, nz, maxPoints, params=params, compute_dtype=self.dtype_policy.compute_dtype,
+                            regularizers=self.regularizers)
         self.optimizer, self.loss = None, None
         self._metric_names = []             # "<output>_<metric>" in compile order
         self._compile_args = None           # compile()'s loss / loss_weights / metrics, unless they are the reference's
@@ -786,7 +803,8 @@ class Model:
         its point capacity: the values of the eager path bit for bit on sweeps already padded to that capacity, and
         equal within rounding on others (kernels that plan per capacity may sum in another order).  Data parallel: every
         rank evaluates its share samples[rank::world] with the rank-mean moving statistics (what save() writes) and all
-        ranks return the same values.  Changes no variable, slot or iteration count."""
+        ranks return the same values.  Changes no variable, slot or iteration count.  With weight regularizers `loss`
+        includes their penalty P (the per-output losses do not), computed once per evaluation on the device."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
         if sample_weight is not None:
@@ -845,7 +863,13 @@ class Model:
                         net.loss_eval(self.loss, *target(i), acc)
             if self.dp is not None:
                 self.dp.sum_(acc)
-            return acc.cpu().numpy().copy()
+            # the weight penalty, once per evaluation and enqueued behind the sweeps: every sweep's `loss` includes it
+            # (theta is the same on every rank), so the sum over the sweeps gains sweeps * P
+            pen = net.penalty()
+            out = acc.cpu().numpy().copy()
+            if pen is not None:
+                out[0] += loss_acc_split(self.loss, out)[1] * float(pen.item())
+            return out
         finally:
             if own is not None:
                 net.params.state.copy_(own)
@@ -878,7 +902,8 @@ class Model:
         <layer>/<weight>:0 with Keras' automatic layer names, training_config and the optimizer's iteration count + slots
         -- SGD momentum accumulators, Adam moments, ..., Nadam's momentum_cache -- under optimizer_weights), written by lisec_amd.hdf5_lite -- see
         lisec_amd/keras_h5.py.  A path ending in .npz gets a plain numpy archive with the names of
-        lisec_amd.params.param_specs() instead."""
+        lisec_amd.params.param_specs() instead.  The weight regularizers go into the layer configs of the .h5, where
+        load_model finds them; an .npz does not carry them (a model loaded from one has none)."""
         p = self.net.params
         if self.dp is not None:
             # data parallel: theta is identical on every rank, the BatchNormalization moving statistics are per
@@ -920,7 +945,7 @@ class Model:
                 slots[name] = {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
         compiled = self._compile_args or {}
         keras_h5.save_model(path, d, self.nx, self.ny, self.nz, self.maxPoints, optimizer=opt,
-                            iterations=self.net.iterations, **compiled, **slots)
+                            iterations=self.net.iterations, regularizers=self.regularizers or None, **compiled, **slots)
 
     def summary(self):
         n = self.net.params.n_trainable()
@@ -954,9 +979,15 @@ def _compile_saved(m, opt, ck):
         m.compile(optimizer=opt, loss=['mse', 'mse'])
 
 
-def createModel(nx, ny, nz, maxPoints):
-    """createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints) (model_training.py:222-257)."""
-    return Model(nx, ny, nz, maxPoints)
+def createModel(nx, ny, nz, maxPoints, kernel_regularizer=None, bias_regularizer=None, gamma_regularizer=None,
+                beta_regularizer=None, activity_regularizer=None):
+    """createModel(Constants.nx, Constants.ny, Constants.nz, Constants.maxPoints) (model_training.py:222-257).
+    kernel_regularizer / bias_regularizer / gamma_regularizer / beta_regularizer: a tf.keras 2.4 weight regularizer
+    (lisec_amd/regularizers.py: regularizers.l2(1e-4), 'l1', ...) for every variable of that kind, as if each layer of
+    the reference's createModel had been given it; see Model.  activity_regularizer: NotImplementedError."""
+    return Model(nx, ny, nz, maxPoints, kernel_regularizer=kernel_regularizer, bias_regularizer=bias_regularizer,
+                 gamma_regularizer=gamma_regularizer, beta_regularizer=beta_regularizer,
+                 activity_regularizer=activity_regularizer)
 
 
 def load_model(path, custom_objects=None):
@@ -978,7 +1009,8 @@ def load_model(path, custom_objects=None):
         return m
     from . import keras_h5
     ck = keras_h5.load_model(path)
-    m = Model(ck["nx"], ck["ny"], ck["nz"], ck["maxPoints"], params=ParamStore(dev, init=ck["params"]))
+    m = Model(ck["nx"], ck["ny"], ck["nz"], ck["maxPoints"], params=ParamStore(dev, init=ck["params"]),
+              variable_regularizers=ck["regularizers"])
     o = ck["optimizer"]
     if o is not None:
         lr = o["lr"]

@@ -13,6 +13,7 @@ model_training.py:299):
     up_b  : concat[..., 256b:256(b+1)] = deconv(relu(bn(y_{b,q})))
     head  : (M,16) = concat @ [W_cls | W_reg] + bias     (cls = [:, :2], reg = [:, 2:])
 """
+import bisect
 import ctypes
 import json
 import os
@@ -488,8 +489,11 @@ class _BackwardPass:
 
 
 class LisecNet:
-    def __init__(self, nx, ny, nz, maxPoints, params=None, device=None, compose_head=True, compute_dtype="float32"):
-        """compute_dtype: 'float32', or 'bfloat16' (the 'mixed_bfloat16' policy of lisec_amd.mixed_precision): the inference
+    def __init__(self, nx, ny, nz, maxPoints, params=None, device=None, compose_head=True, compute_dtype="float32",
+                 regularizers=None):
+        """regularizers: {ParamStore name: (l1, l2)} (lisec_amd.regularizers.coefficients), the weight penalties of the
+        training step (see _regularize); None or empty: no penalty, and not one launch more than before.
+        compute_dtype: 'float32', or 'bfloat16' (the 'mixed_bfloat16' policy of lisec_amd.mixed_precision): the inference
         forward then runs the Conv3D blocks behind the first and the Conv2Ds of the RPN with bf16 operands
         (csrc/igemm_bf16.hip), and training is refused.
         compose_head: the three Conv2DTranspose branches and the 1x1 heads run as 16-channel contractions with composite
@@ -700,6 +704,21 @@ class LisecNet:
         self.loss_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         # [num0, den0, num1, den1, ...] of a DetectionLossSpec's metrics (lisec_detection_metrics); fixed address
         self.metric_pairs = torch.zeros(2 * _lib.DET_MAX_METRICS, dtype=torch.float64, device=dev)
+        # weight regularizers (csrc/regularize.hip): the chunk table (ascending offsets into theta), the penalty of the
+        # step and the per-chunk partials, at fixed addresses like loss_out; fixed for the net's life (id(net) keys the
+        # recorded plans)
+        self.regularizers = {n: (float(a), float(b)) for n, (a, b) in (regularizers or {}).items() if a != 0 or b != 0}
+        # the bias of a convolution that feeds a training-mode BatchNormalization has an identically zero gradient, and
+        # the backward pass never writes its slot of grad (_BackwardPass.conv): the penalty pass must store its term
+        # there, or the slot would carry the terms of every step so far
+        self.unwritten_grads = tuple(L["conv"].bias for L in self.layers
+                                     if L["kind"] in ("mid", "conv") and L["conv"].bias and L["conv"].bn)
+        self._reg_rows = ops.reg_chunks(self.params, self.regularizers, unwritten=self.unwritten_grads)
+        self._reg_offsets = [r[0] for r in self._reg_rows]
+        if self._reg_rows:
+            self._reg_table = ops.reg_table(self._reg_rows, dev)
+            self._reg_ws = ops.reg_workspace(len(self._reg_rows), dev)
+            self.reg_penalty = torch.zeros(1, dtype=torch.float64, device=dev)
 
     @property
     def iterations(self):
@@ -1310,10 +1329,33 @@ class LisecNet:
             ops.lr_schedule_set(self._lr_dev, opt.lr_descriptor)
             self._lr_host = opt.lr_descriptor                 # kept alive: the source of the copy
 
-    def _update(self, opt, lo, hi, advance):
+    def _regularize(self, lo, hi, accumulate=False, fold=False, grad=True):
+        """The weight penalties of the variables in theta[lo:hi] (lo: a variable boundary), on the current stream: grad +=
+        2*l2*w + l1*sign(w) on the weights as they are now, reg_penalty = P of the range (accumulate: += P), and with fold
+        loss_out[0] = float32(loss_out[0] + reg_penalty) -- Keras adds the penalty to `loss` alone.  grad=False: P only.
+        Nothing at all for a net without regularizers."""
+        if not self._reg_rows:
+            return
+        first = bisect.bisect_left(self._reg_offsets, lo)
+        last = bisect.bisect_left(self._reg_offsets, hi)
+        ops.regularize(self.params.theta, self.grad if grad else None, self._reg_table, last - first, self.reg_penalty,
+                       self._reg_ws, first=first, accumulate=accumulate, loss_total=self.loss_out if fold else None)
+
+    def penalty(self):
+        """Enqueues P = sum over the regularised variables of l1*sum|w| + l2*sum w^2 of the weights as they are now into
+        reg_penalty (device float64[1]) and returns it; None for a net without regularizers.  No gradient is touched."""
+        if not self._reg_rows:
+            return None
+        self._regularize(0, self.params.n_theta, grad=False)
+        return self.reg_penalty
+
+    def _update(self, opt, lo, hi, advance, second=False):
         """One optimizer update of theta[lo:hi] on the device iteration count (advance: this call ends the step), by the
         entry of ops that the optimizer's record names: lr_t by value -- (lr, decay) are kernel arguments --, or with
-        device_lr from the descriptor (a schedule, or a rate a callback may change)."""
+        device_lr from the descriptor (a schedule, or a rate a callback may change).  With regularizers the penalty pass
+        over the same range runs directly in front of it, on the same stream (second: the step's other part has stored
+        its share of the penalty already); the call that ends the step folds the penalty into loss_out[0]."""
+        self._regularize(lo, hi, accumulate=second, fold=advance)
         rec = opt.record
         entry, names, args = opt.launch
         bufs = [None if name is None else self.slot(name)[lo:hi] for name in names]
@@ -1348,9 +1390,15 @@ class LisecNet:
     def apply_gradients(self, opt=None):
         """`opt` (an OptimizerSpec; None: optimizers.SGD(lr=0.01, decay=1e-6, momentum=0.9, nesterov=True),
         model_training.py:295) of every variable that early_update() did not update in this step.  Raises RuntimeError,
-        before any launch, when the pending early update was made with another spec."""
+        before any launch, when the pending early update was made with another spec.
+        A net with regularizers: the update is made with grad + 2*l2*w + l1*sign(w), taken on the weights before the
+        update, so after a step net.grad holds the REGULARISED gradient and loss_out[0] includes the penalty, which
+        reg_penalty holds on its own.  backward() alone leaves the plain gradient, except in the slots it never writes
+        (unwritten_grads: the conv biases in front of a training-mode BatchNormalization, whose gradient is identically
+        0): those keep the term the last update stored, which the next update replaces, never adds to."""
         opt = OptimizerSpec() if opt is None else opt
         hi = self.params.theta.numel()
+        second = self._early is not None
         if self._early is not None:
             lo, early_opt = self._early
             if early_opt != opt or (opt.device_lr and bytes(early_opt.lr_descriptor) != bytes(opt.lr_descriptor)):
@@ -1359,7 +1407,7 @@ class LisecNet:
             hi = lo                              # the tail of the buffer was updated during the backward pass
             self._early = None
         # lr_t = lr / (1 + decay * iterations), derived on the device from its own iteration counter
-        self._update(opt, 0, hi, advance=True)
+        self._update(opt, 0, hi, advance=True, second=second)
         self._mark("step:updated")
         self._iterations += 1
         self.params_version += 1

@@ -504,6 +504,55 @@ def detection_metrics(cfg, head, y_cls, y_reg, M, out, accumulate=False):
                                                    _lib.current_stream()))
 
 
+def reg_chunks(params, coeffs, unwritten=()):
+    """The chunk table of lisec_regularize as a host list [(offset, count, l1, l2, flags)], ascending in offset: every
+    variable of coeffs ({ParamStore name: (l1, l2)}) with a pair other than (0, 0), cut into ceil(n / REG_CHUNK) chunks
+    over its padded length (the padding floats of theta are 0 and add nothing).  params: a ParamStore, or anything with
+    its `offsets` ({name: ("theta", offset, shape)}).  unwritten: the names of the variables whose gradient slot no
+    backward pass writes (the gradient is identically 0); their chunks carry REG_GRAD_IS_ZERO, so that the term is
+    stored into the slot, not added to what the step before left there.  Pure host arithmetic: no device, no library.
+    KeyError: a name the network does not have; ValueError: a variable that is not trainable."""
+    rows, unwritten = [], set(unwritten)
+    for name, (l1, l2) in coeffs.items():
+        which, off, shape = params.offsets[name]
+        if which != "theta":
+            raise ValueError(f"{name} is not a trainable variable: it cannot be regularised")
+        if l1 == 0 and l2 == 0:
+            continue
+        n = (math.prod(shape) + 3) // 4 * 4
+        flags = _lib.REG_GRAD_IS_ZERO if name in unwritten else 0
+        for start in range(0, n, _lib.REG_CHUNK):
+            rows.append((off + start, min(_lib.REG_CHUNK, n - start), float(l1), float(l2), flags))
+    rows.sort()
+    return rows
+
+
+def reg_table(chunks, device):
+    """reg_chunks' list as the device table of lisec_regularize (uint8 tensor of len(chunks) lisec_reg_chunk records);
+    a row may leave the flags out (0)."""
+    arr = (_lib.RegChunk * max(len(chunks), 1))()
+    for rec, (off, count, l1, l2, *flags) in zip(arr, chunks):
+        rec.offset, rec.count, rec.l1, rec.l2, rec.flags = off, count, l1, l2, (flags[0] if flags else 0)
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def reg_workspace(n_chunks, device):
+    return torch.empty(_lib.load().lisec_regularize_workspace_bytes(int(n_chunks)), dtype=torch.uint8, device=device)
+
+
+def regularize(theta, grad, table, n_chunks, penalty, workspace, first=0, accumulate=False, loss_total=None):
+    """lisec_regularize over chunks [first, first + n_chunks) of `table` (reg_table; offsets relative to theta / grad as
+    given): grad += 2*l2*w + l1*sign(w) (grad None: the penalty alone), penalty (float64[1] device tensor) = P, or += P
+    with accumulate, and loss_total[0] (float32 device tensor, or None) = float32(loss_total[0] + penalty)."""
+    if first < 0 or (n_chunks > 0 and (first + n_chunks) * ctypes.sizeof(_lib.RegChunk) > table.numel()):
+        raise ValueError(f"regularize: chunks [{first}, {first + n_chunks}) outside a table of "
+                         f"{table.numel() // ctypes.sizeof(_lib.RegChunk)}")
+    chunks = ctypes.c_void_p(table.data_ptr() + first * ctypes.sizeof(_lib.RegChunk))
+    _lib.check(_lib.load().lisec_regularize(_lib.ptr(theta), _lib.ptr(grad), chunks, int(n_chunks), _lib.ptr(penalty),
+                                            1 if accumulate else 0, _lib.ptr(loss_total), _lib.ptr(workspace),
+                                            workspace.numel(), _lib.current_stream()))
+
+
 def sgd_nesterov_step(theta, grad, velocity, lr_t, momentum):
     _lib.check(_lib.load().lisec_sgd_nesterov_step(_lib.ptr(theta), _lib.ptr(grad), _lib.ptr(velocity),
                                                    theta.numel(), lr_t, momentum, _lib.current_stream()))
