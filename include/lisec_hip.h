@@ -1140,6 +1140,64 @@ int lisec_boxes_pair_iou(const double* pred_boxes, const int32_t* pred_start, co
 int lisec_boxes_average_precision(const int64_t* rank, const uint8_t* tp, int n_pred, int n_labels, int n_thresholds,
                                   double* out_ap, double* out_curve, lisec_stream_t stream);
 
+/* Detection evaluation (csrc/detection_eval.hip): the matcher and integrator above with ignored labels and predictions, a
+ * heading-aware score, the true-positive errors and the best-F1 operating point.  Not in the reference; DESIGN section 7.
+ * The entries above keep their results bit for bit; without flags, best_iou, best_label, tp_count, state == tp and the AP
+ * word here equal theirs bit for bit.  An addition changes no signature: the ABI version stays.
+ *
+ * lisec_boxes_evaluate: layout, sizes, IoU, thresholds, mode and the consistency word are lisec_boxes_match's.  pred_ignore:
+ * device uint8[total_pred] or NULL, label_ignore: device uint8[total_labels] or NULL (NULL: no flag set); non-zero = ignored.
+ *   Candidate.  best_label[i] = the row, within the prediction's own sample, of the NON-ignored label with the largest IoU
+ *     (the lowest row among equals; -1 when the sample has none), best_iou[i] = that IoU (0 without one); ignored_iou[i] =
+ *     the largest IoU with an ignored label of its sample (0 without one).
+ *   State at threshold t, in the order of descending score, equal scores by ascending flat row:
+ *     1 (TP) when best_iou > t and no earlier-ranked prediction of the sample with the same candidate has best_iou > t;
+ *     else 2 (ignored) when ignored_iou > t or pred_ignore[i]; else 0 (FP).
+ *     An ignored label absorbs any number of predictions; a prediction with pred_ignore set can still be a TP and then takes
+ *     its label.  state: uint8[n_thresholds][total_pred] in input order, tp_count: int32[n_samples][n_thresholds] (the 1s).
+ *   geom[i] = (sim, dist, scale, yaw) against the candidate, all NaN when best_label == -1 (double[total_pred][4]):
+ *     sim = (1 + cos(yaw_p - yaw_g)) / 2;  dist = sqrt(dx^2 + dy^2) of the centres;
+ *     scale = 1 - v / (V_p + V_g - v) with V = |l w h| and v = min|l| * min|w| * min|h| (one minus the IoU of the two boxes
+ *     made concentric and parallel; 1 when the denominator is <= 0);  yaw = |atan2(sin d, cos d)| in [0, pi], d = yaw_p - yaw_g.
+ *   Offsets that disagree with total_pred / total_pairs give best_iou = NaN, best_label = -1, state = 0, tp_count = -1 (and
+ *   NaN ignored_iou, geom and IoU matrices).  workspace: lisec_boxes_evaluate_workspace_bytes bytes (0 for sizes it refuses);
+ *   on return its first total_pairs doubles hold the IoU matrices.
+ *   LISEC_EINVAL, nothing launched: a NULL output, 0 or more than 16 thresholds, a threshold outside [0, 1), an unknown mode,
+ *   too small a workspace, a buffer misaligned for its element type.
+ *
+ * lisec_boxes_evaluate_integrate: rank as for lisec_boxes_average_precision, state / geom / scores as above (scores =
+ * pred_scores), n_labels = G = the number of NON-ignored labels (> 0, else LISEC_EINVAL).  Ignored ranks (state 2) are
+ * skipped.  With cumTP, cumFP and cumSim (the sum of sim over the TPs) up to rank k: rec = cumTP / G, prec = cumTP / (cumTP
+ * + cumFP), os = cumSim / (cumTP + cumFP).  out: double[n_thresholds][LISEC_EVAL_WORDS]:
+ *   LISEC_EVAL_AP             the recall-weighted sum of the precision envelope from the right: lisec_boxes_average_precision's
+ *                             rule on the sequence with the ignored ranks removed;
+ *   LISEC_EVAL_AOS            the same sum with the envelope of os (os <= prec pointwise, so AOS <= AP);
+ *   LISEC_EVAL_ATE/ASE/AOE    the means of dist / scale / yaw over the TPs at t, summed in flat-row order by a fixed tree; NaN
+ *                             without a TP;
+ *   LISEC_EVAL_BEST_F1        the maximum of 2 cumTP / (cumTP + cumFP + G) over the non-ignored ranks (0 without one);
+ *   LISEC_EVAL_BEST_F1_SCORE  the score of the lowest rank that attains it (NaN without a TP): the score_threshold to hand
+ *                             to lisec_detect for that operating point.
+ * out_curve, when not NULL: double[n_thresholds][n_pred][3] = (rec, prec, os) per rank before the envelopes, NaN at ignored
+ * ranks.  One workgroup per threshold; float64 and integers in a fixed order: bit-identical from run to run. */
+#define LISEC_EVAL_WORDS 7
+#define LISEC_EVAL_AP 0
+#define LISEC_EVAL_AOS 1
+#define LISEC_EVAL_ATE 2
+#define LISEC_EVAL_ASE 3
+#define LISEC_EVAL_AOE 4
+#define LISEC_EVAL_BEST_F1 5
+#define LISEC_EVAL_BEST_F1_SCORE 6
+size_t lisec_boxes_evaluate_workspace_bytes(int n_samples, int total_pred, long long total_pairs, int n_thresholds);
+int lisec_boxes_evaluate(const double* pred_boxes, const double* pred_scores, const int32_t* pred_start,
+                         const uint8_t* pred_ignore, const double* label_boxes, const int32_t* label_start,
+                         const uint8_t* label_ignore, int n_samples, int total_pred, long long total_pairs,
+                         const double* thresholds, int n_thresholds, int mode, void* workspace, size_t workspace_bytes,
+                         double* best_iou, int32_t* best_label, double* ignored_iou, double* geom, uint8_t* state,
+                         int32_t* tp_count, lisec_stream_t stream);
+int lisec_boxes_evaluate_integrate(const int64_t* rank, const uint8_t* state, const double* geom, const double* scores,
+                                   int n_pred, int n_labels, int n_thresholds, double* out, double* out_curve,
+                                   lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 5b. Many-box detection output (csrc/detect.hip): score cut, exact top-N, greedy rotated NMS over those N, capped.
  *     Not in the reference, whose rpnToRegion loop (lisec_rpn_to_region, section 5) stays what it is; this is the path a

@@ -28,38 +28,64 @@ def predictMain(samples, outPath, level5Data, model, dataDir=None):
         np.save(os.path.join(outPath, 'sample' + str(i) + '_regress.npy'), regress)
 
 
-def _detect(samples, level5Data, model, dataDir=None, maxBoxes=20, overlapThresh=0., detector=None, with_labels=True):
-    """The per-sample loop scoreMain, detectionAP and detectMain share, without leaving the device: predict, decode + NMS on
-    the head views, the shift to ego-centred metres (rpnToRegion.py:279-280).  detector=None: boxes.rpnToRegion, the
-    reference's loop, with maxBoxes and overlapThresh; a dict: boxes.detect with these keyword arguments.  Returns
-    ([boxes (k, 7)], [scores (k,)]) as device tensors and [annotationBoxes] -- the counts come back in ONE copy at the end."""
-    import torch
-    from . import boxes
+def _check_detector(detector):
     if detector is not None and "as_device" in detector:
         raise ValueError("the detector's results stay on the device here: as_device is not one of its arguments")
+
+
+def _detect_sweep(points, model, detector=None, maxBoxes=20, overlapThresh=0.):
+    """From the points of one sweep onward, without leaving the device: voxelise, the inference forward, decode + NMS on the
+    head views, the shift to ego-centred metres (rpnToRegion.py:279-280).  detector=None: boxes.rpnToRegion, the reference's
+    loop, with maxBoxes and overlapThresh; a dict: boxes.detect with these keyword arguments.  Returns [(boxes, scores, count
+    (1,) int32)] as device tensors, the first `count` rows valid -- nothing waits for the GPU.  _detect and
+    callbacks.DetectionEvaluation share it."""
+    from . import boxes
+    vfe = VFE_preprocessing(points, Constants.voxelx, Constants.voxely, Constants.voxelz, Constants.maxPoints,
+                            Constants.nx // 2, Constants.ny // 2, Constants.nz)
+    out = []
+    for s in model._as_samples(vfe):
+        cls, reg = model.net.forward(s, training=False)
+        if detector is None:
+            b, p, count = boxes.rpnToRegion(cls[0], reg[0], maxBoxes=maxBoxes, overlapThresh=overlapThresh,
+                                            as_device=True)          # before the next forward reuses the head
+        else:
+            b, p, _, count = boxes.detect(cls[0], reg[0], as_device=True, **detector)
+            count = count[:1]
+        b[:, 0] -= 50
+        b[:, 1] -= 50
+        out.append((b, p, count))
+    return out
+
+
+def _cut_to_counts(found, probs, counts):
+    """The valid rows of every sweep's detections: the counts come back in ONE copy."""
+    import torch
+    counts = torch.cat(counts).cpu().tolist() if counts else []
+    return [b[:k] for b, k in zip(found, counts)], [p[:k] for p, k in zip(probs, counts)]
+
+
+def _detect(samples, level5Data, model, dataDir=None, maxBoxes=20, overlapThresh=0., detector=None, with_labels=True,
+            min_points=0):
+    """The per-sample loop scoreMain, detectionAP, detectionEval and detectMain share: the sweep of every sample through
+    _detect_sweep.  Returns ([boxes (k, 7)], [scores (k,)]) as device tensors and [annotationBoxes] -- the counts come back in
+    ONE copy at the end.  With min_points > 0 a fourth list follows: per sample, the device int64 (m,) number of points of
+    its own sweep each annotation owns (boxes.points_in_boxes)."""
+    from . import boxes
+    _check_detector(detector)
     dataDir = dataDir if dataDir is not None else Constants.lyft_data_dir
-    found, probs, counts, labels = [], [], [], []
+    found, probs, counts, labels, owned = [], [], [], [], []
     for sample in samples:
         points = combine_lidar_data(sample, dataDir, level5Data)
-        vfe = VFE_preprocessing(points, Constants.voxelx, Constants.voxely, Constants.voxelz, Constants.maxPoints,
-                                Constants.nx // 2, Constants.ny // 2, Constants.nz)
-        for s in model._as_samples(vfe):
-            cls, reg = model.net.forward(s, training=False)
-            if detector is None:
-                b, p, count = boxes.rpnToRegion(cls[0], reg[0], maxBoxes=maxBoxes, overlapThresh=overlapThresh,
-                                                as_device=True)          # before the next forward reuses the head
-            else:
-                b, p, _, count = boxes.detect(cls[0], reg[0], as_device=True, **detector)
-                count = count[:1]
-            b[:, 0] -= 50
-            b[:, 1] -= 50
+        for b, p, count in _detect_sweep(points, model, detector, maxBoxes, overlapThresh):
             found.append(b)
             probs.append(p)
             counts.append(count)
         if with_labels:
             labels.append(boxes.annotationBoxes(sample, level5Data))
-    counts = torch.cat(counts).cpu().tolist() if counts else []
-    return [b[:k] for b, k in zip(found, counts)], [p[:k] for p, k in zip(probs, counts)], labels
+            if min_points > 0:
+                owned.append(boxes.points_in_boxes(points, labels[-1], as_device=True))
+    found, probs = _cut_to_counts(found, probs, counts)
+    return (found, probs, labels, owned) if min_points > 0 else (found, probs, labels)
 
 
 def scoreMain(samples, level5Data, model, dataDir=None):
@@ -105,6 +131,29 @@ def detectionAP(samples, level5Data, model, iou_thresholds=None, mode='3d', maxB
     from . import boxes
     found, probs, labels = _detect(samples, level5Data, model, dataDir, maxBoxes, overlapThresh, detector)
     return boxes.average_precision(found, probs, labels, iou_thresholds=iou_thresholds, mode=mode)
+
+
+def detectionEval(samples, level5Data, model, iou_thresholds=None, mode='3d', detector=None, maxBoxes=20, overlapThresh=0.,
+                  min_points=0, ranges=None, dataDir=None):
+    """detectionAP's loop scored by boxes.evaluate_detections: AP, the heading-weighted AOS, the true-positive errors and
+    the best-F1 operating point per IoU threshold (boxes.DetectionEval).  min_points > 0: an annotation that owns fewer
+    points of its own sweep (boxes.points_in_boxes on what combine_lidar_data returned) is ignored -- neither a hit nor a
+    miss, as KITTI's "don't care" and nuScenes' boxes without points are.  ranges: distance bins ((lo, hi), ...) in metres;
+    the result is then boxes.evaluate_by_range's dict, one DetectionEval (or None) per bin.  detector, maxBoxes and
+    overlapThresh are detectionAP's."""
+    import torch
+    from . import boxes
+    got = _detect(samples, level5Data, model, dataDir, maxBoxes, overlapThresh, detector, min_points=max(int(min_points), 0))
+    found, probs, labels = got[:3]
+    ignore = None
+    if min_points > 0 and labels:
+        few = (torch.cat(got[3]) < int(min_points)).cpu().numpy()            # one copy for all samples
+        at = np.cumsum([0] + [len(g) for g in labels])
+        ignore = [few[at[i]:at[i + 1]] for i in range(len(labels))]
+    if ranges is not None:
+        return boxes.evaluate_by_range(found, probs, labels, ranges=ranges, label_ignore=ignore, iou_thresholds=iou_thresholds,
+                                       mode=mode)
+    return boxes.evaluate_detections(found, probs, labels, label_ignore=ignore, iou_thresholds=iou_thresholds, mode=mode)
 
 
 if __name__ == '__main__':

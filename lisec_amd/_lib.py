@@ -211,6 +211,13 @@ def _declare(lib):
     lib.lisec_boxes_pair_iou.argtypes = [P, P, P, P, c_int, c_int, LL, c_int, P, c_size_t, P, P]
     lib.lisec_boxes_average_precision.restype = c_int
     lib.lisec_boxes_average_precision.argtypes = [P, P, c_int, c_int, c_int, P, P, P]
+    lib.lisec_boxes_evaluate_workspace_bytes.restype = c_size_t
+    lib.lisec_boxes_evaluate_workspace_bytes.argtypes = [c_int, c_int, LL, c_int]
+    lib.lisec_boxes_evaluate.restype = c_int
+    lib.lisec_boxes_evaluate.argtypes = [P, P, P, P, P, P, P, c_int, c_int, LL, POINTER(c_double), c_int, c_int, P, c_size_t,
+                                         P, P, P, P, P, P, P]
+    lib.lisec_boxes_evaluate_integrate.restype = c_int
+    lib.lisec_boxes_evaluate_integrate.argtypes = [P, P, P, P, c_int, c_int, c_int, P, P, P]
     lib.lisec_detect_workspace_bytes.restype = c_size_t
     lib.lisec_detect_workspace_bytes.argtypes = [POINTER(RpnCfg), POINTER(DetectCfg)]
     lib.lisec_detect.restype = c_int

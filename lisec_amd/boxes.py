@@ -351,6 +351,15 @@ def _pack_samples(pred_list, label_list, dev):
             int(pred_start[-1]), int(label_start[-1]), pairs)
 
 
+def _pack_scores(score_list, pred_start, dev):
+    """The scores of all samples as one device float64 row (one pad element); one score per prediction, else ValueError."""
+    flat = [c.to(device=dev, dtype=torch.float64).reshape(-1) if torch.is_tensor(c)
+            else torch.from_numpy(np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1))) for c in score_list]
+    if [len(c) for c in flat] != np.diff(pred_start).tolist():
+        raise ValueError("every prediction needs exactly one score")
+    return torch.cat([c.to(dev) for c in flat] + [torch.zeros(1, dtype=torch.float64, device=dev)])
+
+
 def _match(pred_list, score_list, label_list, thr, mode):
     """lisec_boxes_match on a list of samples.  Returns device tensors (best_iou, best_label, tp (T, N), tp_count (S, T), flat
     scores) and the host counts N, G."""
@@ -360,11 +369,7 @@ def _match(pred_list, score_list, label_list, thr, mode):
     lib = _lib.load()
     S, T = len(pred_list), len(thr)
     pred, d_pred_start, label, d_label_start, pred_start, N, G, pairs = _pack_samples(pred_list, label_list, dev)
-    flat = [c.to(device=dev, dtype=torch.float64).reshape(-1) if torch.is_tensor(c)
-            else torch.from_numpy(np.ascontiguousarray(np.asarray(c, dtype=np.float64).reshape(-1))) for c in score_list]
-    if [len(c) for c in flat] != np.diff(pred_start).tolist():
-        raise ValueError("every prediction needs exactly one score")
-    scores = torch.cat([c.to(dev) for c in flat] + [torch.zeros(1, dtype=torch.float64, device=dev)])
+    scores = _pack_scores(score_list, pred_start, dev)
     ws = torch.empty(max(lib.lisec_boxes_match_workspace_bytes(S, N, pairs, T), 1), dtype=torch.uint8, device=dev)
     best_iou = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
     best_label = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
@@ -423,3 +428,150 @@ def average_precision(pred_list, score_list, label_list, iou_thresholds=None, mo
     return DetectionAP(ap=ap, mAP=float(ap.mean()), thresholds=thr, tp=tp.cpu().numpy().astype(bool),
                        tp_count=tp_count.cpu().numpy(), best_iou=best_iou.cpu().numpy(), best_label=best_label.cpu().numpy(),
                        n_predictions=N, n_labels=G)
+
+
+# ---- detection evaluation: ignored labels, heading score, true-positive errors (ours; the reference has no counterpart) ----
+EVAL_WORDS = 7                                                 # LISEC_EVAL_WORDS
+_EVAL_FIELDS = ('ap', 'aos', 'ate', 'ase', 'aoe', 'best_f1', 'best_f1_score')      # LISEC_EVAL_AP .. LISEC_EVAL_BEST_F1_SCORE
+
+
+class DetectionEval:
+    """What evaluate_detections returns: ap, aos, ate, ase, aoe, best_f1, best_f1_score (each (T,)), mAP, mAOS, thresholds
+    (T,), state (T, N) uint8 in input order (0 false positive, 1 true positive, 2 ignored), tp (T, N) bool = state == 1,
+    tp_count (n_samples, T), best_iou (N,), best_label (N,) (row within the sample among ALL its labels, -1 without a
+    non-ignored one), ignored_iou (N,), geom (N, 4) = (sim, dist, scale, yaw) against the candidate, n_predictions,
+    n_labels (non-ignored), n_ignored_labels, and curve (T, N, 3) = (rec, prec, os) per rank when asked for."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return (f"DetectionEval(mAP={self.mAP:.6f}, mAOS={self.mAOS:.6f}, n_predictions={self.n_predictions}, "
+                f"n_labels={self.n_labels}, n_ignored_labels={self.n_ignored_labels}, "
+                f"ap={np.array2string(self.ap, precision=4)})")
+
+
+def points_in_boxes(points, boxes, as_device=False):
+    """The number of points each box owns: points (n, >= 3), boxes (m, 7) rows x, y, z, l, w, h, yaw, arrays or device
+    tensors -> (m,) int64 (a device tensor with as_device=True, without waiting for the GPU).  ObjectDatabase's rule
+    (lisec_augment_owner): the closed slab test, and a point inside several boxes belongs to the lowest index; counting
+    the owners is plumbing."""
+    from . import augment, ops
+    dev = _lib.require_gpu()
+    pts, rows = augment._device_points(points, dev), augment._device_boxes(boxes, dev)
+    m = int(rows.shape[0])
+    if m == 0:
+        per_box = torch.zeros(0, dtype=torch.int64, device=dev)
+    else:
+        own = ops.augment_owner(pts, rows, augment.PAD_LIMIT).long()
+        per_box = torch.bincount(own + 1, minlength=m + 1)[1:]
+    return per_box if as_device else per_box.cpu().numpy()
+
+
+def _flags(flag_list, box_list, what):
+    """One host bool array per sample, as long as its boxes; None: nothing flagged."""
+    sizes = [len(_rows7(b)) for b in box_list]
+    if flag_list is None:
+        return [np.zeros(n, dtype=bool) for n in sizes]
+    if len(flag_list) != len(sizes):
+        raise ValueError(f"{what} needs one flag array per sample")
+    out = [(f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)).reshape(-1).astype(bool) for f in flag_list]
+    if [len(f) for f in out] != sizes:
+        raise ValueError(f"{what} needs exactly one flag per box")
+    return out
+
+
+def _device_flags(flags, dev):
+    """The flags of all samples as one device uint8 row (one pad element), or None when none is set (NULL to the kernel)."""
+    flat = np.concatenate(flags + [np.zeros(1, dtype=bool)])
+    return torch.from_numpy(flat.astype(np.uint8)).to(dev) if flat.any() else None
+
+
+def evaluate_detections(pred_list, score_list, label_list, label_ignore=None, pred_ignore=None, iou_thresholds=None,
+                        mode='3d', curve=False):
+    """average_precision with what a lidar benchmark adds to it (lisec_boxes_evaluate, lisec_boxes_evaluate_integrate; the
+    definition is include/lisec_hip.h's).  label_ignore[s] (m,) / pred_ignore[s] (k,): truthy = ignored, None: none is.
+    An ignored label is neither a hit nor a miss: it is no candidate and does not count in G, and a prediction that is no
+    true positive but overlaps one with IoU > t, or carries pred_ignore, is left out of the ranking at t instead of
+    counting as a false positive.  Returns a DetectionEval: AP and the heading-weighted AOS per threshold and their means,
+    the true-positive errors ATE (centre distance, m), ASE (1 - aligned IoU) and AOE (|yaw difference|, rad) per threshold,
+    the best F1 over the ranking and the score that attains it (the score_threshold to hand to detect).  Without flags
+    ap, tp, tp_count, best_iou and best_label are average_precision's bit for bit.  Packing, the NaN-score check and the
+    rank (a stable descending sort) are average_precision's.  ValueError: flag lists that do not match their boxes, no
+    non-ignored label at all, NaN scores."""
+    thr = _iou_thresholds(iou_thresholds)
+    mode = _iou_mode(mode)
+    if len(pred_list) != len(score_list):
+        raise ValueError("one score set per prediction set")
+    if len(pred_list) != len(label_list):
+        raise ValueError("one label set per prediction set")
+    l_flags = _flags(label_ignore, label_list, "label_ignore")
+    p_flags = _flags(pred_ignore, pred_list, "pred_ignore")
+    n_ignored = int(sum(int(f.sum()) for f in l_flags))
+    G = int(sum(len(f) for f in l_flags)) - n_ignored
+    if G <= 0:
+        raise ValueError("the evaluation is undefined without a label that is not ignored")
+    dev = _lib.require_gpu()
+    lib = _lib.load()
+    S, T = len(pred_list), len(thr)
+    pred, d_pred_start, label, d_label_start, pred_start, N, _, pairs = _pack_samples(pred_list, label_list, dev)
+    scores = _pack_scores(score_list, pred_start, dev)
+    d_label_ignore, d_pred_ignore = _device_flags(l_flags, dev), _device_flags(p_flags, dev)
+    ws = torch.empty(max(lib.lisec_boxes_evaluate_workspace_bytes(S, N, pairs, T), 1), dtype=torch.uint8, device=dev)
+    best_iou = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+    best_label = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
+    ignored_iou = torch.empty(max(N, 1), dtype=torch.float64, device=dev)
+    geom = torch.empty((max(N, 1), 4), dtype=torch.float64, device=dev)
+    state = torch.empty(T * max(N, 1), dtype=torch.uint8, device=dev)
+    tp_count = torch.empty((max(S, 1), T), dtype=torch.int32, device=dev)
+    st = _lib.current_stream()
+    _lib.check(lib.lisec_boxes_evaluate(_lib.ptr(pred), _lib.ptr(scores), _lib.ptr(d_pred_start), _lib.ptr(d_pred_ignore),
+                                        _lib.ptr(label), _lib.ptr(d_label_start), _lib.ptr(d_label_ignore), S, N, pairs,
+                                        (ctypes.c_double * T)(*thr.tolist()), T, mode, _lib.ptr(ws), ws.numel(),
+                                        _lib.ptr(best_iou), _lib.ptr(best_label), _lib.ptr(ignored_iou), _lib.ptr(geom),
+                                        _lib.ptr(state), _lib.ptr(tp_count), st))
+    nan = torch.isnan(scores[:N]).any()                                   # read with the results: no copy between the stages
+    rank = torch.sort(scores[:N], descending=True, stable=True).indices   # plumbing: ties keep the flat (sample, row) order
+    out = torch.empty((T, EVAL_WORDS), dtype=torch.float64, device=dev)
+    d_curve = torch.empty((T, max(N, 1), 3), dtype=torch.float64, device=dev) if curve else None
+    _lib.check(lib.lisec_boxes_evaluate_integrate(_lib.ptr(rank) if N else None, _lib.ptr(state) if N else None,
+                                                  _lib.ptr(geom) if N else None, _lib.ptr(scores) if N else None, N, G, T,
+                                                  _lib.ptr(out), _lib.ptr(d_curve), st))
+    out = out.cpu().numpy()
+    if bool(nan):
+        raise ValueError("scores must not be NaN")
+    state = state[:T * N].reshape(T, N).cpu().numpy()
+    fields = {name: out[:, i].copy() for i, name in enumerate(_EVAL_FIELDS)}
+    if curve:
+        fields['curve'] = d_curve[:, :N].cpu().numpy()
+    return DetectionEval(mAP=float(fields['ap'].mean()), mAOS=float(fields['aos'].mean()), thresholds=thr, state=state,
+                         tp=state == 1, tp_count=tp_count[:S].cpu().numpy(), best_iou=best_iou[:N].cpu().numpy(),
+                         best_label=best_label[:N].cpu().numpy(), ignored_iou=ignored_iou[:N].cpu().numpy(),
+                         geom=geom[:N].cpu().numpy(), n_predictions=N, n_labels=G, n_ignored_labels=n_ignored, **fields)
+
+
+def _centre_distance(b):
+    """hypot(x, y) of box rows, on the host (flags travel as host arrays)."""
+    rows = b.detach().cpu().numpy().reshape(-1, 7) if torch.is_tensor(b) else np.asarray(b, dtype=np.float64).reshape(-1, 7)
+    return np.hypot(rows[:, 0], rows[:, 1])
+
+
+def evaluate_by_range(pred_list, score_list, label_list, ranges=((0, 30), (30, 50), (50, math.inf)), label_ignore=None, **kw):
+    """evaluate_detections once per distance bin: {(lo, hi): DetectionEval}.  Within a bin a label whose centre distance
+    hypot(x, y) lies outside [lo, hi) is ignored (ORed with label_ignore) and a prediction outside it carries pred_ignore
+    (ORed with the one given): what lies in another bin is neither a hit nor a miss here.  A bin without a non-ignored label
+    maps to None.  The other keyword arguments are evaluate_detections'."""
+    l_flags = _flags(label_ignore, label_list, "label_ignore")
+    p_flags = _flags(kw.pop('pred_ignore', None), pred_list, "pred_ignore")
+    l_dist = [_centre_distance(b) for b in label_list]
+    p_dist = [_centre_distance(b) for b in pred_list]
+    out = {}
+    for lo, hi in ranges:
+        lo, hi = float(lo), float(hi)
+        l_bin = [f | ~((d >= lo) & (d < hi)) for f, d in zip(l_flags, l_dist)]
+        p_bin = [f | ~((d >= lo) & (d < hi)) for f, d in zip(p_flags, p_dist)]
+        if all(f.all() for f in l_bin):
+            out[(lo, hi)] = None
+            continue
+        out[(lo, hi)] = evaluate_detections(pred_list, score_list, label_list, label_ignore=l_bin, pred_ignore=p_bin, **kw)
+    return out

@@ -1,7 +1,7 @@
 """tf.keras 2.4 callbacks for Model.fit(callbacks=...) and Model.evaluate(callbacks=...), exposed as
 lisec_amd.model_training.callbacks: the Callback base class (set_model, set_params, on_train_begin / on_train_end,
 on_epoch_begin / on_epoch_end, on_test_begin / on_test_end), LearningRateScheduler, EarlyStopping, ModelCheckpoint and
-ReduceLROnPlateau.  A learning rate set between epochs reaches the update kernels through the device descriptor of
+ReduceLROnPlateau; and DetectionEvaluation (ours), which logs the detection metric for them to monitor.  A learning rate set between epochs reaches the update kernels through the device descriptor of
 LisecNet, written on the stream of the step: the recorded step plan is not recorded again.  There are no per-batch hooks:
 the fit loop reads nothing back from the device inside an epoch."""
 import warnings
@@ -283,3 +283,86 @@ class LearningRateScheduler(Callback):
     def on_epoch_end(self, epoch, logs=None):
         logs = logs if logs is not None else {}
         logs["lr"] = float(self.model.optimizer.lr)
+
+
+class DetectionEvaluation(Callback):
+    """Puts the data set's detection metric into the epoch logs, so that EarlyStopping and ModelCheckpoint can select on it
+    (ours: Keras has no counterpart).  sweeps: a list of (n, >= 3) point arrays in ego metres; boxes: a list of (m, 7) rows
+    x, y, z, l, w, h, yaw as boxes.annotationBoxes returns them, one per sweep.
+
+    At the end of every `every`-th epoch (1-based, like validation_freq) each sweep runs what Predict.detectionEval runs --
+    voxelise, forward(training=False), boxes.detect(**detector) (None: boxes.rpnToRegion with its defaults), the -50 shift --
+    and ONE boxes.evaluate_detections call covers all sweeps.  logs[prefix + 'mAP'], 'mAOS', 'ATE', 'ASE', 'AOE' and
+    'best_f1' are set, the last four at the lowest IoU threshold; the whole result stays in `last`.  On the other epochs the
+    keys are absent: a monitoring callback then warns and skips, as it does for any missing key.  min_points > 0: a box
+    owning fewer points of its sweep (boxes.points_in_boxes) is ignored.  Place it in the callbacks list BEFORE the
+    callbacks that monitor its keys: fit hands one logs dict to the callbacks in list order.
+
+    Changes no variable, BatchNormalization statistic, optimizer slot or iteration count, and records nothing into a step
+    plan: eager inference forwards between epochs, as fit's own validation runs them.  Data parallel: every rank evaluates
+    every sweep with the rank-mean moving statistics (what save() writes), so the logs are identical on all ranks."""
+
+    KEYS = ("mAP", "mAOS", "ATE", "ASE", "AOE", "best_f1")
+
+    def __init__(self, sweeps, boxes, detector=None, iou_thresholds=None, mode="3d", min_points=0, every=1, prefix="val_"):
+        super().__init__()
+        from .Predict import _check_detector
+        sweeps, boxes = list(sweeps), [np.asarray(b, dtype=np.float64).reshape(-1, 7) for b in boxes]
+        if len(sweeps) != len(boxes):
+            raise ValueError(f"DetectionEvaluation needs one box set per sweep, not {len(boxes)} for {len(sweeps)}")
+        if sum(len(b) for b in boxes) == 0:
+            raise ValueError("DetectionEvaluation needs at least one box: the evaluation is undefined without labels")
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+            raise ValueError(f"every must be an integer >= 1, not {every!r}")
+        _check_detector(detector)
+        self.sweeps, self.boxes, self.detector = sweeps, boxes, None if detector is None else dict(detector)
+        self.iou_thresholds, self.mode, self.min_points = iou_thresholds, mode, int(min_points)
+        self.every, self.prefix = int(every), str(prefix)
+        self.last = None
+        self._ignore = None
+
+    def _label_ignore(self):
+        """The min_points flags, counted once (sweeps and boxes do not change)."""
+        if self.min_points <= 0:
+            return None
+        if self._ignore is None:
+            from . import boxes as _boxes
+            self._ignore = [_boxes.points_in_boxes(p, b) < self.min_points for p, b in zip(self.sweeps, self.boxes)]
+        return self._ignore
+
+    def evaluate(self):
+        """The evaluation of the model's current weights: a boxes.DetectionEval."""
+        from . import boxes as _boxes
+        from .Predict import _cut_to_counts, _detect_sweep
+        model = self.model
+        net, dp = model.net, getattr(model, "dp", None)
+        own = None
+        if dp is not None:                               # as Model._eval_sums: copy, average, evaluate, restore
+            own = net.params.state.clone()
+            dp.average_(net.params.state)
+            net.state_version += 1
+        try:
+            found, probs, counts = [], [], []
+            for points in self.sweeps:
+                for b, p, count in _detect_sweep(points, model, self.detector):
+                    found.append(b)
+                    probs.append(p)
+                    counts.append(count)
+            found, probs = _cut_to_counts(found, probs, counts)
+        finally:
+            if own is not None:
+                net.params.state.copy_(own)
+                net.state_version += 1
+        return _boxes.evaluate_detections(found, probs, self.boxes, label_ignore=self._label_ignore(),
+                                          iou_thresholds=self.iou_thresholds, mode=self.mode)
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.every != 0:
+            return
+        r = self.last = self.evaluate()
+        if logs is None:
+            return
+        lowest = int(np.argmin(r.thresholds))
+        values = (r.mAP, r.mAOS, r.ate[lowest], r.ase[lowest], r.aoe[lowest], r.best_f1[lowest])
+        for key, v in zip(self.KEYS, values):
+            logs[self.prefix + key] = float(v)

@@ -1,4 +1,4 @@
-// The rectangle footprint shared by the box kernels (boxes.hip, union_overlap.hip, detection_ap.hip,
+// The rectangle footprint shared by the box kernels (boxes.hip, union_overlap.hip, detection_ap.hip, detection_eval.hip,
 // detection_metrics.hip, detection_iou_loss.hip): boxToShapely's vertices, the shoelace sum, the clipped area of two
 // footprints, their IoU, and the anchor decode of the detection metrics and the IoU loss.
 #pragma once

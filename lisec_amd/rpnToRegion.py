@@ -5,6 +5,7 @@ calcIoUAll takes it as an optional last argument and falls back to the module gl
 import numpy as np
 
 from .boxes import annotationBoxes, average_precision, calcIntersectAll, calcIoUAll_boxes, calcUnionAll   # noqa: F401
+from .boxes import evaluate_by_range, evaluate_detections, points_in_boxes                                # noqa: F401
 from .boxes import rpnToRegion as _rpn_to_region
 
 level5Data = None            # rpnToRegion.py:265-269 builds a LyftDataset here
