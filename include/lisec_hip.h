@@ -1013,6 +1013,28 @@ int lisec_regularize(const float* theta, float* grad /* NULL: penalty only */, c
 /* x *= s  (gradient averaging after the data-parallel all-reduce) */
 int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);
 
+/* Gradient accumulation of a mini-batch (fit(batch_size=B); csrc/grad_accumulate.hip): one pass over n floats of the
+ * flat gradient buffer `grad` and a second buffer `acc` of the same layout (the caller offsets both pointers to the
+ * start of its range [lo, hi) and passes n = hi - lo).
+ *   LISEC_ACC_BEGIN  acc[i] = grad[i]                        grad is only read, scale is ignored (may be NULL)
+ *   LISEC_ACC_ADD    acc[i] = acc[i] + grad[i]               grad is only read, scale is ignored (may be NULL)
+ *   LISEC_ACC_END    grad[i] = (acc[i] + grad[i]) * *scale   acc is only read; scale: device float[1], read by the kernel
+ * THE ARITHMETIC IS A CONTRACT (tests pin it bit for bit): after BEGIN on g1, ADD on g2 .. g(B-1) and END on gB,
+ *   grad = ((((g1 + g2) + g3) + ... ) + gB) * s
+ * with every add and then the ONE multiply an IEEE fp32 round-to-nearest-even operation of its own: the add is never
+ * contracted into the multiply, nothing is reassociated, denormals are kept, the sign of a zero follows IEEE.  Floats
+ * outside [0, n) keep their bits, and so does the buffer a form only reads.  No atomics, one thread per element: the
+ * same bits from run to run.  The scale is read from the device (not passed by value) so that a recorded step plan
+ * serves batches of any size: the host rewrites the float between replays, stream-ordered.
+ * Fixed addresses, no host reads, no allocation: the launch records into a step plan.  n == 0 is valid (nothing is
+ * enqueued).  LISEC_EINVAL, nothing enqueued: NULL grad or acc, grad == acc, n < 0 or n % 4 != 0, an unknown mode,
+ * LISEC_ACC_END without scale, grad or acc not 16-byte aligned, scale not 4-byte aligned. */
+#define LISEC_ACC_BEGIN 0
+#define LISEC_ACC_ADD 1
+#define LISEC_ACC_END 2
+int lisec_grad_accumulate(float* grad, float* acc, long long n, int mode, const float* scale /* device [1] */,
+                          lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4b. Data-parallel gradient exchange.  The reference trains in ONE process
  *     (model.fit, model_training.py:299); here whole samples are sharded over one process per GPU and the

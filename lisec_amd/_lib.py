@@ -107,6 +107,7 @@ class LrSchedule(Structure):                   # lisec_lr_schedule
 
 REG_CHUNK = 4096                               # LISEC_REG_CHUNK
 REG_GRAD_IS_ZERO = 1                           # LISEC_REG_GRAD_IS_ZERO
+ACC_BEGIN, ACC_ADD, ACC_END = 0, 1, 2          # LISEC_ACC_*: the forms of lisec_grad_accumulate
 
 
 class RegChunk(Structure):                     # lisec_reg_chunk
@@ -411,6 +412,8 @@ def _declare(lib):
     lib.lisec_fold_depth.argtypes = [P, P, c_int, LL, c_int, c_int, P, P]
     lib.lisec_scale.restype = c_int
     lib.lisec_scale.argtypes = [P, LL, c_float, P]
+    lib.lisec_grad_accumulate.restype = c_int
+    lib.lisec_grad_accumulate.argtypes = [P, P, LL, c_int, P, P]
     lib.lisec_comm_unique_id.restype = c_int
     lib.lisec_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.lisec_comm_init.restype = c_int

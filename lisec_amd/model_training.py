@@ -414,6 +414,39 @@ def _should_validate(epoch, validation_freq):
     raise ValueError(f"Expected `validation_freq` to be a list or int. Received: validation_freq={validation_freq!r}")
 
 
+def _check_batch_size(batch_size):
+    """fit(batch_size=): an integer >= 1 (numpy integers included), returned as an int.  Anything else -- a bool, as
+    boxes._count refuses it, a float, a string, 0 or a negative number -- is a ValueError."""
+    if isinstance(batch_size, bool) or not isinstance(batch_size, numbers.Integral) or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size!r}")
+    return int(batch_size)
+
+
+def _epoch_batches(n, batch_size, steps_per_epoch=None):
+    """The batches of one epoch over an order of n sweeps, as lists of positions into that order; one update each.
+    steps_per_epoch=None: ceil(n / B) batches, batch k = positions k*B .. (k+1)*B - 1, the last one possibly shorter.
+    steps_per_epoch given: that many batches of B sweeps each, sweep j of batch k at position (k*B + j) % n -- the
+    wrap-around of the batch-1 loop."""
+    B = batch_size
+    if steps_per_epoch is None:
+        return [list(range(k, min(k + B, n))) for k in range(0, n, B)]
+    if n < 1:
+        raise ValueError("no sweeps to train on")
+    return [[(k * B + j) % n for j in range(B)] for k in range(int(steps_per_epoch))]
+
+
+def _add_sweep_logs(tot, loss_out, b, last, penalty=None):
+    """Adds one sweep's [total, class, regression] (loss_out) to the epoch sums `tot` (float64; numpy arrays or device
+    tensors alike) so that tot / sweeps is Keras' batch-size-weighted epoch mean.  A batch's `loss` is the mean of its b
+    sweeps' losses plus the weight penalty P once, and weighs b in the epoch mean: b*P in the sums.  The step that ends
+    a batch (`last`) has folded P into its own total once; the other b - 1 shares are added here, from `penalty` (the
+    float64[1] P of that update; None without regularizers)."""
+    tot[:3] += loss_out
+    if last and penalty is not None and b > 1:
+        tot[0] += (b - 1) * penalty[0]
+    return tot
+
+
 def _grid_key(samples):
     """The voxel grid every sample shares, when each is a voxelised sweep that still holds its device points; else None
     (e.g. dense arrays turned into samples: no point cloud to voxelise again)."""
@@ -560,9 +593,17 @@ class Model:
     def fit(self, x, y=None, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None,
             validation_split=0.0, validation_data=None, validation_steps=None, validation_freq=1):
         """fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, epochs=1, steps_per_epoch=180)
-        (model_training.py:299).  batch_size must be 1 (the reference's setting: BatchNormalization
-        statistics are per sample).  With WORLD_SIZE > 1 whole samples are sharded over the ranks and the
-        gradients averaged with one RCCL all-reduce per step.
+        (model_training.py:299).  batch_size=B (an integer >= 1; anything else is a ValueError before any launch): every
+        update is made with the mean gradient of B sweeps, each run at batch 1 -- BatchNormalization statistics and
+        moving averages stay per sweep, the loss is normalised per sweep and then averaged: Keras' MirroredStrategy over
+        B replicas at per-replica batch 1 without SyncBatchNorm, NOT one replica's batch of B with pooled statistics
+        (INTEGRATION.md).  An epoch is ceil(n / B) updates over order[k*B : (k+1)*B] (the last batch may be shorter and is
+        divided by its own size); steps_per_epoch counts updates of B sweeps, sweep j of batch k being
+        order[(k*B + j) % n].  iterations, learning-rate schedules and decay count updates.  The epoch logs are Keras'
+        batch-size-weighted means: sums over sweeps divided by the sweeps trained on, a batch's weight penalty weighted
+        by its size.  batch_size=1 is the reference's setting and the step as it always was.
+        With WORLD_SIZE > 1 whole samples are sharded over the ranks, each rank forms its batches from its own shard
+        (global batch B * world) and the gradients are averaged with one exchange per update.
         callbacks: a list of callbacks.Callback (LearningRateScheduler, or one's own), called as Keras does.  With
         callbacks the update kernels read the learning rate from the device descriptor, so that a rate set between
         epochs reaches the recorded step without recording it again.
@@ -578,11 +619,10 @@ class Model:
         on_epoch_end()), e.g. augment.AugmentedSweeps, with y=None: step st trains on item order[st], made when the step
         stages its sweep, and on_epoch_end() is called after every epoch.  y given with it is a ValueError, as in Keras;
         validation_split is refused (pass validation_data).  Everything else works as for lists."""
+        B = _check_batch_size(batch_size)        # first of all: nothing of the model or the GPU is touched before it
         _refuse_mixed_training(self.dtype_policy)
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
-        if batch_size != 1:
-            raise NotImplementedError("only batch_size=1, the reference's setting, is implemented")
         seq = x if _is_sequence(x) else None
         if seq is not None:
             if y is not None:
@@ -610,16 +650,18 @@ class Model:
             val_samples, val_y = samples[at:], (ycls[at:n], yreg[at:n])
             samples, n = samples[:at], at
         if validation_data is not None or validation_split:
-            vn = len(val_samples) if validation_steps is None else min(len(val_samples), int(validation_steps) * batch_size)
+            vn = len(val_samples) if validation_steps is None else min(len(val_samples), int(validation_steps) * B)
             val = (val_samples[:vn],) + self._labels(val_y, vn)
             _should_validate(0, validation_freq)           # a malformed validation_freq is refused before any step
         self.stop_training = False
         idx = list(range(n))
         if self.dp is not None:
             idx = self.dp.shard(idx)
-        steps = steps_per_epoch if steps_per_epoch is not None else len(idx)
+        steps = steps_per_epoch if steps_per_epoch is not None else -(-len(idx) // B)     # updates per epoch
         if self.dp is not None and steps_per_epoch is not None:
             steps = max(1, steps_per_epoch // self.dp.world)
+        batches = _epoch_batches(len(idx), B, None if steps_per_epoch is None else steps)
+        sweeps = sum(len(b) for b in batches)               # sweeps trained on per epoch
         dev = self.net.device
         hist = History()
         callbacks = list(callbacks or [])
@@ -637,7 +679,7 @@ class Model:
             opt = self.optimizer.spec(device_lr=bool(callbacks))
             # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
             # the descriptor on this stream, behind the previous epoch's last update
-            captured = self._captured_step(samples, opt, seq_req)
+            captured = self._captured_step(samples, opt, seq_req, batch=B)
             self.net._sync_lr(opt)
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
@@ -648,32 +690,40 @@ class Model:
             every = max(1, steps // 20)
             t0 = time.time()
 
-            def sweep(st, points=captured is not None):
-                """What step st trains on: (points of the sweep for a recorded step, else its voxel sample, y_cls, y_reg)."""
-                i = int(order[st % len(order)])
+            def sweep(t, points=captured is not None):
+                """What sweep t of the epoch trains on: (points of the sweep for a recorded step, else its voxel sample,
+                y_cls, y_reg).  The batches are consecutive runs of the order, so sweep t is order[t % n]."""
+                i = int(order[t % len(order)])
                 if seq is not None:
                     return self._sequence_item(seq, i, points)
                 return (samples[i]._keepalive if points else samples[i], *target(i))
 
-            for st in range(steps):
-                if captured is not None:
-                    # the whole step (voxelise + forward + backward + update) re-issued from its recorded plan: one C call
-                    # (PipelinedStep: it also voxelises the sweep of the next step, on the second stream)
-                    captured.fit_step(sweep, st, steps)
-                else:
-                    self.net.train_step(*sweep(st), loss=self.loss, opt=opt,
-                                        allreduce=self.dp.bucketed() if self.dp is not None else None)
-                tot_dev += self.net.loss_out
-                if nm:
-                    met_dev += met_step
+            penalty = self.net.reg_penalty if self.net._reg_rows else None
+            t = 0                                           # sweeps trained on so far in this epoch
+            for st, batch in enumerate(batches):
+                b = len(batch)
+                if b > 1:
+                    self.net.set_batch_divisor(b)           # the short last batch of an epoch is divided by its own size
+                for position in LisecNet.batch_positions(b):
+                    if captured is not None:
+                        # the whole step (voxelise + forward + backward + update) re-issued from its recorded plan: one C
+                        # call (PipelinedStep: it also voxelises the next sweep, on the second stream)
+                        captured.fit_step(sweep, t, sweeps, position=position)
+                    else:
+                        self.net.train_micro_step(*sweep(t), position, loss=self.loss, opt=opt,
+                                                  allreduce=self.dp.bucketed() if self.dp is not None else None)
+                    _add_sweep_logs(tot_dev, self.net.loss_out, b, position in ("single", "last"), penalty)
+                    if nm:
+                        met_dev += met_step
+                    t += 1
                 if verbose and ((st + 1) % every == 0 or st + 1 == steps):
-                    print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / (st + 1):.4f}", end="", flush=True)
+                    print(f"\r{st + 1}/{steps} - loss: {float(tot_dev[0].item()) / t:.4f}", end="", flush=True)
             tot = tot_dev.cpu().numpy()
             if verbose:
                 print(f" - {time.time() - t0:.1f}s")
             if nm:
                 tot = np.concatenate([tot, met_dev.cpu().numpy()])
-            logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, tot, max(steps, 1))))
+            logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, tot, max(sweeps, 1))))
             if val is not None and _should_validate(epoch, validation_freq):
                 vlogs = self._evaluate(*val, callbacks=callbacks, verbose=0)
                 logs.update({"val_" + key: v for key, v in vlogs.items()})
@@ -738,7 +788,7 @@ class Model:
         key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
         return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096), "first"     # a little head-room for later calls
 
-    def _captured_step(self, samples, opt, seq_req=None):
+    def _captured_step(self, samples, opt, seq_req=None, batch=1):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
@@ -749,12 +799,14 @@ class Model:
         if req is None:
             return None
         key, grid, dtype, need, capacity, mode = req
-        key += (opt.config,)         # the full optimizer config: a re-compile with another optimizer records a new plan
+        # the full optimizer config: a re-compile with another optimizer records a new plan; the batch size: a fit with
+        # another one records its own plans (those of a batch's micro-steps exist for batch_size > 1 only)
+        key += (opt.config, int(batch))
         step = _reusable(self._captured, key, need)
         if step is None:
             cls = PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep
             step = cls(self.net, Voxelizer(*grid, device=self.net.device, subsample=mode), capacity, dtype=dtype, loss=self.loss,
-                       opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None)
+                       opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None, batch=batch)
             self._captured = (key, step)
         return step
 
@@ -1088,7 +1140,7 @@ def train_with_model(samples, level5Data, model_path, save_path):
 
 
 def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=0, subsample='first', balance=True,
-                    loss=None):
+                    loss=None, batch_size=1):
     """OURS, not the reference's: train() on sweeps that are augmented anew at every step (augment.AugmentedSweeps: per-box
     noise with collision rejection, one global scale and rotation, VoxelNet section 3.3) with the label maps of the moved
     boxes made on the device (boxes.rpnTargets) instead of the precomputed labels3/*.npy.  The sweeps come from
@@ -1098,8 +1150,10 @@ def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=
     points keeps the reference's random subsample, drawn anew per (seed, item, epoch), instead of the lowest point indices
     (AugmentedSweeps).  loss: compile()'s (None: the reference's ['mse','mse']); with loss='voxelnet' (losses.VoxelNetLoss, which normalises positives and
     negatives separately) balance=False is the natural setting: the label maps then keep every negative instead of a
-    sample of them.  Returns the model, saved at save_path."""
+    sample of them.  batch_size: fit()'s (the mean gradient of that many augmented sweeps per update; 1: the reference's).
+    Returns the model, saved at save_path."""
     from . import augment, boxes
+    batch_size = _check_batch_size(batch_size)
     _refuse_mixed_training(mixed_precision.global_policy())
     points = [combine_lidar_data_gpu(s, Constants.lyft_data_dir, level5Data) for s in samples]
     rows = [boxes.annotationBoxes(s, level5Data) for s in samples]
@@ -1109,7 +1163,7 @@ def train_augmented(samples, level5Data, save_path, epochs=1, seed=0, sample_to=
     database = augment.ObjectDatabase(points, rows) if sample_to > 0 else None
     seq = augment.AugmentedSweeps(points, rows, seed=seed, database=database, sample_to=sample_to, subsample=subsample,
                                   balance=balance)
-    history = model.fit(x=seq, batch_size=1, verbose=1, epochs=epochs)
+    history = model.fit(x=seq, batch_size=batch_size, verbose=1, epochs=epochs)
     if model.dp is None or model.dp.rank == 0:
         print(history.history)
     model.save(save_path)

@@ -675,6 +675,10 @@ class LisecNet:
         self._tail_ok = {}
         self._loss_descs = {}                            # LossSpec / DetectionLossSpec -> its descriptor (_loss_descriptor)
         self._early = None                               # (lo, OptimizerSpec) of the pending early_update()
+        # mini-batches (train_micro_step): the gradient accumulator, shaped like theta, and the device float 1/b the
+        # kernel that ends a batch reads; made by _batch_buffers() when a batch larger than 1 is first used
+        self._acc = self._acc_scale = None
+        self._acc_div = 1
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
         self._fwd_events = {}
         # a repack enqueued on the second stream is pending (_arm_repack, apply_gradients): the forward waits for
@@ -1447,6 +1451,110 @@ class LisecNet:
         self._packed_version = self._packed_t_version = (self.params_version, self.params.version)
         self._pack_pending = self._late_pending = True
 
+    def _replayed_micro(self):
+        """Host bookkeeping of one replayed plan of a micro-step that only accumulates: no update, so the iteration
+        count, params_version and the packed copies stand; the BatchNormalization statistics moved.  The plan's forward
+        waited for the pack events of the last update, which stay signalled, and the next plan's forward will again."""
+        self.state_version += 1
+        self._pack_pending = self._late_pending = True
+
+    # ------------------------------------------------------------------------------------------------
+    # mini-batches: fit(batch_size=B) as B sweeps at batch 1 whose gradients are averaged before ONE update
+    BATCH_POSITIONS = ("single", "first", "middle", "last")
+    _ACC_MODE = {"first": _lib.ACC_BEGIN, "middle": _lib.ACC_ADD, "last": _lib.ACC_END}
+
+    def _batch_buffers(self):
+        """The gradient accumulator (zero when first asked for) and the device divisor (1), at fixed addresses from
+        then on: recorded step plans point at them."""
+        self._prepare_training()
+        if self._acc is None:
+            self._acc = torch.zeros_like(self.params.theta)
+            self._acc_scale = torch.ones(1, dtype=torch.float32, device=self.device)
+            self._acc_div = 1
+            torch.cuda.synchronize(self.device)   # zero before any stream of the step (the second one included) uses it
+        return self._acc
+
+    def set_batch_divisor(self, b):
+        """Makes the device divisor hold float32(1) / float32(b) for the batch that starts now: a fill on the current
+        stream, behind every step already enqueued, when b differs from the last one written (as _sync_lr, a recorded
+        plan does not re-issue it)."""
+        self._batch_buffers()
+        b = int(b)
+        if b < 1:
+            raise ValueError(f"a batch holds at least one sweep, not {b}")
+        if b != self._acc_div:
+            self._acc_scale.fill_(float(np.float32(1.0) / np.float32(b)))
+            self._acc_div = b
+
+    def _accumulate(self, lo, hi, mode):
+        ops.grad_accumulate(self.grad[lo:hi], self._acc[lo:hi], mode, self._acc_scale)
+
+    def train_micro_step(self, sample, y_cls, y_reg, position, loss="mse", allreduce=None, opt=None, side_filler=None):
+        """Sweep `position` ('first', 'middle' or 'last'; 'single': train_step, a batch of one) of a mini-batch whose
+        divisor set_batch_divisor() wrote: the forward (batch statistics of THIS sweep; the moving statistics move once
+        per sweep, in order) and the backward of train_step, unchanged, then
+          first / middle   acc = grad / acc += grad (lisec_grad_accumulate), and nothing else: no penalty, no update,
+                           no iteration count, no repack, no gradient exchange;
+          last             grad = (acc + grad) * (1/b), the mean in sweep order, and then everything train_step does behind
+                           its backward, once: the data-parallel exchange, the penalty pass, the update, iterations += 1,
+                           the repack for the next forward.
+        The overlap of train_step is kept: the RPN + head tail of theta has final gradients at backward's
+        rpn_grads_ready hook, so its pass -- and, in the last sweep, its early update or the start of its exchange --
+        runs there on the second stream, under the rest of the backward; the head of theta follows the join.
+        The slots of grad no backward pass writes (unwritten_grads) go through the passes like any other: they hold 0,
+        or the term the last regularised update stored, which the penalty pass of this batch's update REPLACES (it
+        stores into LISEC_REG_GRAD_IS_ZERO chunks), so a regularised bias gets its term once per update."""
+        if position == "single":
+            return self.train_step(sample, y_cls, y_reg, loss=loss, allreduce=allreduce, opt=opt, side_filler=side_filler)
+        if position not in self._ACC_MODE:
+            raise ValueError(f"position must be one of {self.BATCH_POSITIONS}, not {position!r}")
+        self._batch_buffers()
+        mode, last, n = self._ACC_MODE[position], position == "last", self.params.n_theta
+        bucketed = allreduce is not None and hasattr(allreduce, "start_tail")
+        head = [n]                                 # where the range the hook has served starts
+
+        def tail(lo, hi):
+            if lo % 4 or hi != n:
+                return
+            self._accumulate(lo, hi, mode)
+            head[0] = lo
+            if last and bucketed:
+                allreduce.start_tail(self.grad, lo, hi)
+            elif last and allreduce is None:
+                self.early_update(lo, hi, opt=opt)
+
+        self.forward(sample, training=True)
+        self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, rpn_grads_ready=tail)
+        self._accumulate(0, head[0], mode)
+        if last:
+            if bucketed:
+                allreduce.finish(self.grad)
+            elif allreduce is not None:
+                allreduce(self.grad)
+            self.apply_gradients(opt=opt)
+        return self.loss_out
+
+    @staticmethod
+    def batch_positions(b):
+        """The positions of the b sweeps of one batch, in order."""
+        return ["single"] if b == 1 else ["first"] + ["middle"] * (b - 2) + ["last"]
+
+    def train_batch(self, samples, y_cls, y_reg, loss="mse", allreduce=None, opt=None):
+        """One update on the mean gradient of len(samples) sweeps (eager): y_cls[i], y_reg[i] are the targets of
+        samples[i].  Returns [total, class, regression] of the batch as a float64 device tensor: the mean of the sweeps'
+        losses, the total plus the weight penalty P once.  net.loss_out holds the last sweep's."""
+        b = len(samples)
+        if b < 1:
+            raise ValueError("train_batch needs at least one sweep")
+        if b > 1:
+            self.set_batch_divisor(b)
+        tot = torch.zeros(3, dtype=torch.float64, device=self.device)
+        for s_, yc, yr, pos in zip(samples, y_cls, y_reg, self.batch_positions(b)):
+            tot += self.train_micro_step(s_, yc, yr, pos, loss=loss, allreduce=allreduce, opt=opt)
+        if self._reg_rows and b > 1:
+            tot[0] += (b - 1) * self.reg_penalty[0]     # the last sweep's total holds P once; the mean keeps it whole
+        return tot / b
+
     def train_step(self, sample, y_cls, y_reg, loss="mse", allreduce=None, opt=None, side_filler=None):
         """One fit() step at batch_size=1: forward (batch statistics) + backward + the update by `opt` (an OptimizerSpec;
         None: the reference's SGD-Nesterov).  side_filler: see backward().
@@ -1565,10 +1673,17 @@ class _TrainingPlans(_StepPlans):
     and recording steps (LisecNet.train_step), the replay and its bookkeeping.  The two differ in the number of sets, in
     where the step of buffer set j voxelises its sweep (_voxelise(j) issues it, or returns it as the side_filler of the
     backward pass) and in how a fit() epoch drives them: fit_step(sweep, st, steps) is step st of an epoch of `steps`
-    steps, sweep(k) -> (points, y_cls, y_reg) being what the epoch's step k trains on."""
+    steps, sweep(k) -> (points, y_cls, y_reg) being what the epoch's step k trains on.
+    batch=B > 1 (fit(batch_size=B)): more plans per buffer set, recorded behind the batch-1 plans, which are recorded
+    exactly as without it: a micro-step that only accumulates, in its two forms ('first': acc = grad, and for B > 2
+    'middle': acc += grad), and the micro-step that ends a batch ('last': the mean, the exchange, the update, the
+    repack) -- LisecNet.train_micro_step.  fit_step(..., position=) picks the plan; the divisor 1/b is device data that
+    LisecNet.set_batch_divisor rewrites between replays, so one set of plans serves a short last batch too (a batch of
+    one is the batch-1 plan)."""
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None):
-        nbuf = self.NBUF                         # the number of buffer sets, and of plans
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None,
+                 batch=1):
+        nbuf = self.NBUF                         # the number of buffer sets, and of batch-1 plans
         super().__init__(net, voxelizer, capacity, nbuf, dtype, loss)
         # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
         # lisec_allreduce_grads and its event edges record themselves, a torch.distributed exchange rides as host calls.
@@ -1580,6 +1695,10 @@ class _TrainingPlans(_StepPlans):
         net._prepare_training()
         for name in self.opt.slots:
             net.slot(name)                       # made before the plan records their addresses
+        self.micro = {}                          # (position, buffer set) -> plan of a micro-step of a batch
+        batch = int(batch)
+        if batch > 1:
+            net._batch_buffers()                 # likewise: the accumulator and the divisor
         keep = self._snapshot()
         self.samples = [self.vox(pts) for pts in self.points]
         # eager warm-up (lazy workspaces, descriptor tables, events; it leaves the next step's repack pending, which is
@@ -1590,6 +1709,8 @@ class _TrainingPlans(_StepPlans):
         for j in range(nbuf):
             self._record(lambda: self._enqueue(j))
         torch.cuda.synchronize(dev)
+        if batch > 1:
+            self._record_micro_plans(("first", "middle", "last") if batch > 2 else ("first", "last"))
         # those steps trained on the padding: put every variable back and repack the kernels from them
         self._restore(keep)
         net.params_version += 1
@@ -1604,7 +1725,26 @@ class _TrainingPlans(_StepPlans):
         warm-up / recording steps."""
         net, p = self.net, self.net.params
         return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
-                net._iterations, net.momentum_cache.clone())
+                net._iterations, net.momentum_cache.clone(),
+                None if net._acc is None else (net._acc.clone(), net._acc_scale.clone(), net._acc_div))
+
+    def _record_micro_plans(self, positions):
+        """The plans of the micro-steps of a batch, per buffer set: one eager batch of len(positions) sweeps (first,
+        middle if any batch has one, last) as a warm-up, one more that is recorded while it runs.  Every plan is recorded with the repack of the last
+        update pending, as the batch-1 plans are: its forward waits for the two pack events, which an update several
+        micro-steps back has signalled long since (LisecNet._replayed_micro keeps the flags set between replays)."""
+        net = self.net
+        net.set_batch_divisor(len(positions))
+        for record in (False, True):
+            for j in range(self.NBUF):
+                for position in positions:
+                    net._pack_pending = net._late_pending = True
+                    if record:
+                        self._record(lambda: self._enqueue(j, position))
+                        self.micro[position, j] = self.plans[-1]
+                    else:
+                        self._enqueue(j, position)
+            torch.cuda.synchronize(net.device)
 
     def _restore(self, keep):
         net, p = self.net, self.net.params
@@ -1615,27 +1755,42 @@ class _TrainingPlans(_StepPlans):
         net._iter_dev.copy_(keep[3])
         net._iterations = keep[4]
         net.momentum_cache.copy_(keep[5])
+        if keep[6] is not None:
+            net._acc.copy_(keep[6][0])
+            net._acc_scale.copy_(keep[6][1])
+            net._acc_div = keep[6][2]
 
-    def _enqueue(self, j):
+    def _enqueue(self, j, position="single"):
         """One eager step on buffer set j (warm-up, or recorded while it runs)."""
-        self.net.train_step(self.samples[j], self.ycls[j], self.yreg[j], loss=self.loss, allreduce=self.allreduce,
-                            opt=self.opt, side_filler=self._voxelise(j))
+        self.net.train_micro_step(self.samples[j], self.ycls[j], self.yreg[j], position, loss=self.loss,
+                                  allreduce=self.allreduce, opt=self.opt, side_filler=self._voxelise(j))
 
-    def _run(self):
-        """Replays the plan of the current buffer set; returns net.loss_out (device, [total, class, regression])."""
+    def _run(self, position="single"):
+        """Replays the plan of the current buffer set (position: of the micro-step of a batch, see LisecNet.
+        train_micro_step); returns net.loss_out (device, [total, class, regression])."""
         self._check_stream()
         self._check_fresh()
         net = self.net
+        if position == "single":
+            plan = self.plans[self.cur]
+        else:
+            plan = self.micro.get((position, self.cur))
+            if plan is None:
+                raise RuntimeError(f"this {type(self).__name__} holds no plan for the {position!r} sweep of a batch: it was "
+                                   f"recorded for a smaller batch size (batch=)")
         cur = (net.params_version, net.params.version)
         if net._packed_version != cur or net._packed_t_version != cur or not net._pack_pending:
             # the variables were changed since the last step (params.load_dict / touch, an eager step): the recorded
             # forward contains no repack, so it is made now on the replay stream
             net._arm_repack()
-        _lib.check(self.lib.lisec_step_plan_run(self.plans[self.cur]))
-        net._replayed()
+        _lib.check(self.lib.lisec_step_plan_run(plan))
+        if position in ("single", "last"):
+            net._replayed()
+        else:
+            net._replayed_micro()
         for s_ in self.samples:
             s_._host_info = None
-        self.cur = (self.cur + 1) % len(self.plans)
+        self.cur = (self.cur + 1) % self.NBUF
         return net.loss_out
 
 
@@ -1670,16 +1825,16 @@ class RecordedStep(_TrainingPlans):
         """Stage one sweep: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets (Ho,Wo,2|14)."""
         self._load(0, points, ycls, yreg)
 
-    def replay(self):
+    def replay(self, position="single"):
         """Runs the recorded step on what load() staged; returns net.loss_out (device, [total, class, regression])."""
-        return self._run()
+        return self._run(position)
 
-    def __call__(self, points, ycls, yreg):
+    def __call__(self, points, ycls, yreg, position="single"):
         self.load(points, ycls, yreg)
-        return self.replay()
+        return self.replay(position)
 
-    def fit_step(self, sweep, st, steps):
-        return self(*sweep(st))
+    def fit_step(self, sweep, st, steps, position="single"):
+        return self(*sweep(st), position=position)
 
 
 class PipelinedStep(_TrainingPlans):
@@ -1711,16 +1866,18 @@ class PipelinedStep(_TrainingPlans):
         """Stages the sweep the next step() voxelises (and the step() after it trains on)."""
         self._load(1 - self.cur, points, ycls, yreg)
 
-    def step(self, next_points=None, next_ycls=None, next_yreg=None):
+    def step(self, next_points=None, next_ycls=None, next_yreg=None, position="single"):
         """Trains on the current sweep and voxelises the staged next one; returns net.loss_out (device)."""
         if next_points is not None:
             self._load(1 - self.cur, next_points, next_ycls, next_yreg)
-        return self._run()
+        return self._run(position)
 
-    def fit_step(self, sweep, st, steps):
+    def fit_step(self, sweep, st, steps, position="single"):
+        """Sweep st of an epoch of `steps` sweeps: the next sweep is voxelised under this one's backward whatever the
+        two are to their batches, so the pipeline runs across micro-step and batch boundaries."""
         if st == 0:
             self.prime(*sweep(0))                 # (every epoch draws its own order and primes its first sweep)
-        return self.step(*sweep(st + 1)) if st + 1 < steps else self.step()
+        return self.step(*sweep(st + 1), position=position) if st + 1 < steps else self.step(position=position)
 
 
 class EvalStep(_StepPlans):

@@ -695,6 +695,17 @@ def scale_(x, s):
     _lib.check(_lib.load().lisec_scale(_lib.ptr(x), x.numel(), s, _lib.current_stream()))
 
 
+def grad_accumulate(grad, acc, mode, scale=None):
+    """lisec_grad_accumulate over the whole of `grad` and `acc` (float32 device tensors of one length, a multiple of 4;
+    slices of the flat gradient buffer and of the accumulator at the same offset): mode _lib.ACC_BEGIN acc = grad,
+    ACC_ADD acc = acc + grad, ACC_END grad = (acc + grad) * scale[0] with scale a float32 device tensor the kernel
+    reads.  fp32 adds in call order, then one fp32 multiply, never contracted (include/lisec_hip.h)."""
+    if grad.numel() != acc.numel():
+        raise ValueError(f"grad_accumulate: {grad.numel()} gradient floats, {acc.numel()} accumulator floats")
+    _lib.check(_lib.load().lisec_grad_accumulate(_lib.ptr(grad), _lib.ptr(acc), grad.numel(), int(mode), _lib.ptr(scale),
+                                                 _lib.current_stream()))
+
+
 def conv_field_forward_workspace_bytes(g, row_capacity):
     return _lib.load().lisec_conv_field_forward_workspace_bytes(ctypes.byref(g), row_capacity)
 
