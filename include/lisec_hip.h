@@ -1035,6 +1035,50 @@ int lisec_scale(float* x, long long n, float s, lisec_stream_t stream);
 int lisec_grad_accumulate(float* grad, float* acc, long long n, int mode, const float* scale /* device [1] */,
                           lisec_stream_t stream);
 
+/* Weight averaging (optimizers.MovingAverage / optimizers.SWA; csrc/weight_average.hip): one pass per optimizer UPDATE
+ * over n floats of the flat parameter buffer `theta` (only read) and a second buffer `avg` of the same layout.  The
+ * definition is this project's own restatement of tfa.optimizers.MovingAverage / SWA (parity unpinned).
+ * s = state[0] + state_bias is the iteration count BEFORE the update, read by the kernel from the device (state: where
+ * the update entries keep the count; state_bias 0 when the pass is enqueued in front of the update that advances the
+ * count, -1 behind it), w = theta[i] after the update, a = avg[i]:
+ *   LISEC_AVG_EMA   decay_s = 0                                   for s < start
+ *                           = min(decay, (1 + k) / (10 + k))       with dynamic != 0, k = s - start
+ *                           = decay                                otherwise
+ *                   c = (float)(1.0 - decay_s), computed in double once per workgroup and rounded once
+ *                   c == 1.0f:  a <- w                 a store, not arithmetic (a - (a - w) is not w in fp32)
+ *                   otherwise   a <- a - (a - w) * c
+ *   LISEC_AVG_SWA   m = max(0, (s - start) / period) (integer division); a snapshot iff s >= start and
+ *                   s == start + m*period
+ *                   not a snapshot: a keeps its bits (the launch is made, every thread returns: the host does not know s)
+ *                   m == 0:     a <- w
+ *                   otherwise   a <- (a * (float)m + w) / (float)(m + 1)
+ * THE ARITHMETIC IS A CONTRACT (tests pin it bit for bit): each subtraction, multiply, add and divide above is an IEEE
+ * fp32 round-to-nearest-even operation of its own, never contracted into an fma, never reassociated, the divide never
+ * replaced by a reciprocal multiply; denormals are kept, the sign of a zero follows IEEE.  theta, the floats outside
+ * [0, n) and, off a snapshot, avg keep their bits.  No atomics, one thread per element: the same bits from run to run.
+ * *desc is a HOST pointer, validated and copied into the launch.  Fixed addresses, no host reads of device memory, no
+ * allocation: the launch records into a step plan and replays correctly at every count.  n == 0 is valid (nothing is
+ * enqueued).  LISEC_EINVAL, nothing enqueued: NULL theta, avg, desc or state, theta == avg, n < 0 or n % 4 != 0, theta
+ * or avg not 16-byte aligned, state not 8-byte aligned, an unknown kind, start < 0, decay outside [0, 1] or NaN (EMA),
+ * period < 1 (SWA).  Fields a kind does not use are ignored.
+ * lisec_weight_swap: a[i] <-> b[i], bit for bit, for i < n (same argument checks; a == b is refused).
+ * lisec_weight_average_eval: for j < k, at s = state[0] + j: EMA c_out[j] = c; SWA m_out[j] = m, or -1 off a snapshot
+ * (device pointers; the output of the other kind may be NULL and is not written): the device function of the pass, for
+ * tests. */
+enum { LISEC_AVG_EMA = 0, LISEC_AVG_SWA = 1 };
+typedef struct lisec_weight_average_desc {
+    int kind;            /* LISEC_AVG_* */
+    int dynamic;         /* EMA: dynamic_decay */
+    long long start;     /* EMA: start_step; SWA: start_averaging */
+    long long period;    /* SWA: average_period */
+    double decay;        /* EMA: average_decay */
+} lisec_weight_average_desc;
+int lisec_weight_average(const float* theta, float* avg, long long n, const lisec_weight_average_desc* desc /* host, copied */,
+                         const long long* state /* device */, long long state_bias, lisec_stream_t stream);
+int lisec_weight_swap(float* a, float* b, long long n, lisec_stream_t stream);
+int lisec_weight_average_eval(const lisec_weight_average_desc* desc /* host, copied */, const long long* state /* device */,
+                              long long k, float* c_out, long long* m_out, lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4b. Data-parallel gradient exchange.  The reference trains in ONE process
  *     (model.fit, model_training.py:299); here whole samples are sharded over one process per GPU and the

@@ -110,6 +110,14 @@ REG_GRAD_IS_ZERO = 1                           # LISEC_REG_GRAD_IS_ZERO
 ACC_BEGIN, ACC_ADD, ACC_END = 0, 1, 2          # LISEC_ACC_*: the forms of lisec_grad_accumulate
 
 
+AVG_EMA, AVG_SWA = 0, 1                        # LISEC_AVG_*: the kinds of lisec_weight_average
+
+
+class WeightAverage(Structure):                # lisec_weight_average_desc
+    _fields_ = [("kind", c_int), ("dynamic", c_int), ("start", ctypes.c_longlong), ("period", ctypes.c_longlong),
+                ("decay", c_double)]
+
+
 class RegChunk(Structure):                     # lisec_reg_chunk
     _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("l1", c_float), ("l2", c_float), ("flags", c_int)]
 
@@ -414,6 +422,12 @@ def _declare(lib):
     lib.lisec_scale.argtypes = [P, LL, c_float, P]
     lib.lisec_grad_accumulate.restype = c_int
     lib.lisec_grad_accumulate.argtypes = [P, P, LL, c_int, P, P]
+    lib.lisec_weight_average.restype = c_int
+    lib.lisec_weight_average.argtypes = [P, P, LL, POINTER(WeightAverage), P, LL, P]
+    lib.lisec_weight_swap.restype = c_int
+    lib.lisec_weight_swap.argtypes = [P, P, LL, P]
+    lib.lisec_weight_average_eval.restype = c_int
+    lib.lisec_weight_average_eval.argtypes = [POINTER(WeightAverage), P, LL, P, P, P]
     lib.lisec_comm_unique_id.restype = c_int
     lib.lisec_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.lisec_comm_init.restype = c_int

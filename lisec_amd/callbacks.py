@@ -174,7 +174,38 @@ class ModelCheckpoint(Callback):
             self.best = current
         elif self.verbose > 0:
             print(f"\nEpoch {epoch + 1:05d}: saving model to {filepath}")
+        self._save(filepath)
+
+    def _save(self, filepath):
         self.model.save(filepath)
+
+
+class AverageModelCheckpoint(ModelCheckpoint):
+    """tfa.callbacks.AverageModelCheckpoint: a ModelCheckpoint, with its keywords and rules, for a model compiled with
+    optimizers.MovingAverage or optimizers.SWA (anything else: ValueError when training begins).
+    update_weights=False: the file is written inside Model.average_weights() -- its model weights are the averages, its
+    `average` slot the live weights of that moment -- and training goes on with the live weights, bit for bit as without
+    the callback.  update_weights=True: optimizer.assign_average_vars(model) first -- training goes on FROM the averages --
+    then the file is written, model weights and average both the averages."""
+
+    def __init__(self, update_weights, filepath, monitor="val_loss", verbose=0, save_best_only=False,
+                 save_weights_only=False, mode="auto", save_freq="epoch", **kwargs):
+        super().__init__(filepath, monitor=monitor, verbose=verbose, save_best_only=save_best_only,
+                         save_weights_only=save_weights_only, mode=mode, save_freq=save_freq, **kwargs)
+        self.update_weights = bool(update_weights)
+
+    def on_train_begin(self, logs=None):
+        if not hasattr(self.model.optimizer, "assign_average_vars"):
+            raise ValueError("AverageModelCheckpoint is only used when training with MovingAverage or SWA")
+        super().on_train_begin(logs)
+
+    def _save(self, filepath):
+        if self.update_weights:
+            self.model.optimizer.assign_average_vars(self.model)
+            self.model.save(filepath)
+        else:
+            with self.model.average_weights():
+                self.model.save(filepath)
 
 
 class ReduceLROnPlateau(Callback):
@@ -298,13 +329,17 @@ class DetectionEvaluation(Callback):
     owning fewer points of its sweep (boxes.points_in_boxes) is ignored.  Place it in the callbacks list BEFORE the
     callbacks that monitor its keys: fit hands one logs dict to the callbacks in list order.
 
+    average_weights=True (a model compiled with optimizers.MovingAverage / SWA; otherwise ValueError at the first
+    evaluation): the averages are evaluated, so val_mAP is their score and EarlyStopping / ModelCheckpoint select on it;
+    the variables and their average are swapped back afterwards, bit for bit.
     Changes no variable, BatchNormalization statistic, optimizer slot or iteration count, and records nothing into a step
     plan: eager inference forwards between epochs, as fit's own validation runs them.  Data parallel: every rank evaluates
     every sweep with the rank-mean moving statistics (what save() writes), so the logs are identical on all ranks."""
 
     KEYS = ("mAP", "mAOS", "ATE", "ASE", "AOE", "best_f1")
 
-    def __init__(self, sweeps, boxes, detector=None, iou_thresholds=None, mode="3d", min_points=0, every=1, prefix="val_"):
+    def __init__(self, sweeps, boxes, detector=None, iou_thresholds=None, mode="3d", min_points=0, every=1, prefix="val_",
+                 average_weights=False):
         super().__init__()
         from .Predict import _check_detector
         sweeps, boxes = list(sweeps), [np.asarray(b, dtype=np.float64).reshape(-1, 7) for b in boxes]
@@ -318,6 +353,7 @@ class DetectionEvaluation(Callback):
         self.sweeps, self.boxes, self.detector = sweeps, boxes, None if detector is None else dict(detector)
         self.iou_thresholds, self.mode, self.min_points = iou_thresholds, mode, int(min_points)
         self.every, self.prefix = int(every), str(prefix)
+        self.average_weights = bool(average_weights)
         self.last = None
         self._ignore = None
 
@@ -331,7 +367,14 @@ class DetectionEvaluation(Callback):
         return self._ignore
 
     def evaluate(self):
-        """The evaluation of the model's current weights: a boxes.DetectionEval."""
+        """The evaluation of the model's current weights -- with average_weights, of their averages (inside
+        Model.average_weights(); the BatchNormalization moving statistics as they stand) --: a boxes.DetectionEval."""
+        if self.average_weights:
+            with self.model.average_weights():
+                return self._evaluate()
+        return self._evaluate()
+
+    def _evaluate(self):
         from . import boxes as _boxes
         from .Predict import _cut_to_counts, _detect_sweep
         model = self.model

@@ -235,7 +235,13 @@ def _serialize_nested(x):
     return x
 
 
-def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
+# the optimizer wrappers that keep a weight average (model_training.optimizers.MovingAverage / SWA): their
+# optimizer_config nests the wrapped optimizer's under "optimizer", their one slot kind follows the wrapped optimizer's
+WRAPPER_CLASSES = ("MovingAverage", "SWA")
+AVERAGE_KIND = "average"
+
+
+def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrapper=None):
     """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
     loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote).  optimizer_config holds Keras'
     keys in Keras' order, a key the dict lacks at Keras' default (optimizer_table)."""
@@ -244,6 +250,10 @@ def _training_config(optimizer, loss=None, loss_weights=None, metrics=None):
     oc = {"class_name": rec.class_name, "config": {
         "name": rec.class_name, "learning_rate": _rate(o.get("lr", rec.lr)), "decay": float(o.get("decay", rec.decay)),
         **rec.values(o)}}
+    if wrapper is not None:
+        c = dict(wrapper["config"])
+        oc = {"class_name": wrapper["class_name"], "config": {"name": c.pop("name", wrapper["class_name"]),
+                                                              "optimizer": oc, **c}}
     return {"loss": ["mse", "mse"] if loss is None else _serialize_nested(loss), "metrics": _serialize_nested(metrics),
             "weighted_metrics": None, "loss_weights": _serialize_nested(loss_weights), "optimizer_config": oc}
 
@@ -255,7 +265,7 @@ SLOT_KEYS = optimizer_table.SLOT_NAMES
 
 # ---------------------------------------------------------------------------------------------------
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, loss=None, loss_weights=None,
-               metrics=None, momentum_cache=1.0, regularizers=None, **given):
+               metrics=None, momentum_cache=1.0, regularizers=None, wrapper=None, average=None, **given):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
@@ -267,7 +277,15 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
     loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
     as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics.
     regularizers: {ParamStore name: (l1, l2)} or None, written into the layer configs (model_config).
+    wrapper: {"class_name": "MovingAverage" | "SWA", "config": its own keys, without "optimizer"} or None: the
+    optimizer_config becomes the wrapper's, with the optimizer's nested under "optimizer"; average: the weight average,
+    a dict like a slot, written as <wrapper class>/<variable>/average:0 behind the optimizer's own slot kinds.  Without a
+    wrapper the file has the bytes it always had.
     **given: the slots, by the names of SLOT_KEYS (any other keyword: TypeError)."""
+    if wrapper is not None and wrapper.get("class_name") not in WRAPPER_CLASSES:
+        raise ValueError(f"save_model: optimizer wrapper class {wrapper.get('class_name')!r} is not implemented")
+    if wrapper is not None and optimizer is None:
+        raise ValueError("save_model: a wrapper needs the optimizer it wraps")
     for k in given:
         if k not in SLOT_KEYS:
             raise TypeError(f"save_model() got an unexpected keyword argument {k!r}")
@@ -277,8 +295,8 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
         f.attrs["backend"] = b"tensorflow"
         f.attrs["model_config"] = json.dumps(model_config(nx, ny, nz, maxPoints, regularizers)).encode("utf8")
         if optimizer is not None:
-            f.attrs["training_config"] = json.dumps(_training_config(optimizer, loss, loss_weights,
-                                                                     metrics)).encode("utf8")
+            f.attrs["training_config"] = json.dumps(_training_config(optimizer, loss, loss_weights, metrics,
+                                                                     wrapper)).encode("utf8")
         g = f.create_group("model_weights")
         g.attrs["layer_names"] = [L["name"].encode("utf8") for L in layers]
         g.attrs["backend"] = b"tensorflow"
@@ -300,6 +318,8 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
             return
         # Keras' order: iter, the optimizer's own scalar, then one slot kind for every variable before the next kind
         entries = [(f"{cls}/{var}/{s.kind}:0", given[s.name][pname]) for s in kept for var, pname in slots]
+        if wrapper is not None and average is not None:
+            entries += [(f"{wrapper['class_name']}/{var}/{AVERAGE_KIND}:0", average[pname]) for var, pname in slots]
         head = [f"{cls}/iter:0"] + ([f"{cls}/{rec.scalar}:0"] if rec.scalar else [])
         og = f.create_group("optimizer_weights")
         og.attrs["weight_names"] = [n.encode() for n in head] + [n.encode("utf8") for n, _ in entries]
@@ -368,7 +388,9 @@ def load_model(path, grid=None):
     serialized there; None without one), the slots of SLOT_KEYS (each a dict of trainable ParamStore name -> array, or
     None; mapped per optimizer class, so "momentum" is SGD's velocity in an SGD file) and momentum_cache (Nadam's, or
     None)) and regularizers ({ParamStore name: (l1, l2)}, read from each layer's config; {} without any).  Slots are
-    matched by name, not by position.
+    matched by name, not by position.  A file of an averaging wrapper: wrapper ({"class_name", "config" without
+    "optimizer"}; else None), `optimizer` the wrapped one's, and average (like a slot, or None).  An optimizer_config that
+    nests an "optimizer" under a class that is not one of WRAPPER_CLASSES is refused by name (ValueError).
 
     Layers are matched by class and creation order (the numeric suffix of Keras' automatic names), not by the exact
     suffix: a model built as the second one of a Python session carries shifted suffixes."""
@@ -421,20 +443,27 @@ def load_model(path, grid=None):
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
         out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, optimizer=None,
-                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, regularizers=regs,
+                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, regularizers=regs, wrapper=None,
+                   average=None,
                    **{k: None for k in SLOT_KEYS})
         if "training_config" in f.attrs:
             tc = json.loads(_text(f.attrs["training_config"]))
             out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))
             oc = tc.get("optimizer_config", {})
             c = oc.get("config", {})
+            if isinstance(c.get("optimizer"), dict):              # a wrapper: the optimizer is the one it nests
+                if oc.get("class_name") not in WRAPPER_CLASSES:
+                    raise ValueError(f"{path}: optimizer wrapper class {oc.get('class_name')!r} is not implemented")
+                out["wrapper"] = {"class_name": oc["class_name"], "config": {k: v for k, v in c.items() if k != "optimizer"}}
+                oc = c["optimizer"]
+                c = oc.get("config", {})
             rec = optimizer_table.BY_CLASS.get(oc.get("class_name"))
             if rec is not None:               # another optimizer class: no optimizer, the model comes back uncompiled
                 out["optimizer"] = rec.as_dict(c.get("learning_rate", c.get("lr", rec.lr)), c.get("decay", rec.decay),
                                                {h.name: c.get(h.name, h.default) for h in rec.hyper})
         if "optimizer_weights" in f:
             og = f["optimizer_weights"]
-            slot_dataset = re.compile(r"([^/]+)/(.+)/(%s):0" % "|".join(optimizer_table.SLOT_KINDS))
+            slot_dataset = re.compile(r"([^/]+)/(.+)/(%s):0" % "|".join(optimizer_table.SLOT_KINDS + (AVERAGE_KIND,)))
             found_slots = {}
             for w in _attr_list(og, "weight_names"):
                 a = og[w][()]

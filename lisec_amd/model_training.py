@@ -13,6 +13,7 @@ stay sparse on the GPU instead of being densified to (8,200,400,35,6) and stacke
 (reference model_training.py:279,285).  There is no CPU fallback.
 """
 import collections.abc
+import contextlib
 import json
 import math
 import numbers
@@ -25,7 +26,7 @@ import torch
 
 from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table, regularizers
-from .network import (EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len, loss_acc_logs,
+from .network import (AverageSpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len, loss_acc_logs,
                       loss_acc_split)
 from .params import ParamStore, fold_depth, param_specs
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
@@ -297,6 +298,68 @@ class _Optimizer:
         return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper}
 
 
+class _AveragingOptimizer(_Optimizer):
+    """What optimizers.MovingAverage and optimizers.SWA share: the wrapped optimizer, to which lr, decay and every
+    hyper-parameter read and write through (ReduceLROnPlateau and LearningRateScheduler assign optimizer.lr), the spec --
+    the wrapped optimizer's with an AverageSpec --, the nested config and the calls that use the averages."""
+
+    _OWN = ("name",)                     # the wrapper's own attributes; every other one is the wrapped optimizer's
+
+    def _wrap(self, optimizer, name):
+        if isinstance(optimizer, _AveragingOptimizer):
+            raise ValueError(f"{type(self).__name__} cannot wrap {type(optimizer).__name__}: one averaging wrapper at most")
+        if not isinstance(optimizer, (str, _Optimizer)):
+            raise ValueError(f"{type(self).__name__}: optimizer must be an optimizer object or 'sgd' / 'adam', "
+                             f"not {optimizer!r}")
+        object.__setattr__(self, "_optimizer", optimizers.get(optimizer))
+        self.name = name
+
+    @property
+    def record(self):
+        return self._optimizer.record
+
+    def __getattr__(self, attr):             # only reached for what the wrapper does not have itself
+        if attr.startswith("_"):
+            raise AttributeError(attr)
+        return getattr(self._optimizer, attr)
+
+    def __setattr__(self, attr, value):
+        if attr in self._OWN or attr.startswith("_"):
+            object.__setattr__(self, attr, value)
+        else:
+            setattr(self._optimizer, attr, value)
+
+    def spec(self, device_lr=False):
+        inner = self._optimizer
+        return OptimizerSpec(inner.record.kind, inner.lr, inner.decay, device_lr=device_lr, average=self.average_spec(),
+                             **inner.hyper)
+
+    def _nested(self):
+        inner = self._optimizer
+        return {"class_name": type(inner).__name__, "config": inner.get_config()}
+
+    @staticmethod
+    def _net_of(model):
+        if not isinstance(getattr(model, "optimizer", None), _AveragingOptimizer):
+            raise ValueError("the model is not compiled with an averaging optimizer (optimizers.MovingAverage / SWA)")
+        return model.net
+
+    def assign_average_vars(self, model):
+        """theta <- average on `model` (a Model compiled with this optimizer); the average is kept.  Training that
+        follows goes on from the averages."""
+        self._net_of(model).assign_average()
+
+    def swap_weights(self, model):
+        """theta <-> average on `model`, by content (LisecNet.swap_average); a second call swaps back, bit for bit."""
+        self._net_of(model).swap_average()
+
+
+def _step_number(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, not {value!r}")
+    return int(value)
+
+
 def _momentum_in_unit_interval(momentum):
     """Keras' own check of SGD and RMSprop (OptimizerSpec only asks for momentum >= 0)."""
     if not 0.0 <= float(momentum) <= 1.0:
@@ -363,6 +426,87 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
                      schedule_decay=0.004, decay=None, **kwargs):
             self._set(name, lr if lr is not None else learning_rate, schedule_decay if decay is None else decay, kwargs,
                       beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
+
+    class MovingAverage(_AveragingOptimizer):
+        """tfa.optimizers.MovingAverage as this project restates it (parity unpinned): after every update
+        average <- average - (average - w)*(1 - decay_s), decay_s = 0 before iteration start_step, then average_decay, or
+        with dynamic_decay min(average_decay, (1 + k)/(10 + k)), k = iterations - start_step.  num_updates folds into
+        average_decay once, here: min(average_decay, (1 + num_updates)/(10 + num_updates)).  Only the trainable
+        variables are averaged, not the BatchNormalization moving statistics.  ValueError: wrapping a wrapper,
+        sequential_update=False, average_decay outside [0, 1], start_step < 0 or not an integer."""
+
+        _OWN = ("name", "average_decay", "num_updates", "start_step", "dynamic_decay", "sequential_update")
+
+        def __init__(self, optimizer, sequential_update=True, average_decay=0.99, num_updates=None, start_step=0,
+                     dynamic_decay=False, name="MovingAverage"):
+            self._wrap(optimizer, name)
+            if sequential_update is not True:
+                raise ValueError("MovingAverage(sequential_update=False) is not implemented: the average is updated "
+                                 "after the variables")
+            if not 0.0 <= float(average_decay) <= 1.0:
+                raise ValueError(f"average_decay must lie in [0, 1], not {average_decay!r}")
+            self.sequential_update, self.average_decay = True, float(average_decay)
+            self.num_updates = None if num_updates is None else _step_number("num_updates", num_updates)
+            if self.num_updates is not None and self.num_updates < 0:
+                raise ValueError(f"num_updates must be >= 0, not {num_updates}")
+            self.start_step, self.dynamic_decay = _step_number("start_step", start_step), bool(dynamic_decay)
+            self.average_spec()                  # the range checks, before any launch
+
+        def average_spec(self):
+            decay = self.average_decay
+            if self.num_updates is not None:
+                decay = min(decay, (1.0 + self.num_updates) / (10.0 + self.num_updates))
+            return AverageSpec("ema", decay=decay, dynamic=self.dynamic_decay, start=self.start_step)
+
+        def get_config(self):
+            return {"name": self.name, "optimizer": self._nested(), "sequential_update": True,
+                    "average_decay": self.average_decay, "num_updates": self.num_updates, "start_step": self.start_step,
+                    "dynamic_decay": self.dynamic_decay}
+
+    class SWA(_AveragingOptimizer):
+        """tfa.optimizers.SWA as this project restates it (parity unpinned): at the iterations
+        start_averaging + m*average_period, m = 0, 1, ..., average <- (average*m + w)/(m + 1) on the variables after that
+        update (m = 0: average <- w); at every other iteration the average keeps its bits.  ValueError: wrapping a
+        wrapper, start_averaging < 0, average_period < 1, either not an integer."""
+
+        _OWN = ("name", "start_averaging", "average_period")
+
+        def __init__(self, optimizer, start_averaging=0, average_period=10, name="SWA"):
+            self._wrap(optimizer, name)
+            self.start_averaging = _step_number("start_averaging", start_averaging)
+            self.average_period = _step_number("average_period", average_period)
+            self.average_spec()                  # the range checks, before any launch
+
+        def average_spec(self):
+            return AverageSpec("swa", start=self.start_averaging, period=self.average_period)
+
+        def get_config(self):
+            return {"name": self.name, "optimizer": self._nested(), "start_averaging": self.start_averaging,
+                    "average_period": self.average_period}
+
+    WRAPPERS = ("MovingAverage", "SWA")
+
+    @staticmethod
+    def serialize(optimizer):
+        """{"class_name", "config"} of an optimizer object; a wrapper nests the wrapped optimizer's under "optimizer"."""
+        return {"class_name": type(optimizer).__name__, "config": optimizer.get_config()}
+
+    @staticmethod
+    def deserialize(config):
+        """The optimizer of a {"class_name", "config"} dict (optimizers.serialize, or a checkpoint's optimizer_config).
+        ValueError, naming the class, for one that is not implemented."""
+        cls, c = config.get("class_name"), dict(config.get("config", {}))
+        if cls in optimizers.WRAPPERS:
+            inner = optimizers.deserialize(c.pop("optimizer"))
+            return getattr(optimizers, cls)(inner, **c)
+        rec = optimizer_table.BY_CLASS.get(cls)
+        if rec is None:
+            raise ValueError(f"optimizer class {cls!r} is not implemented")
+        lr = c.get("learning_rate", c.get("lr", rec.lr))
+        if isinstance(lr, dict):
+            lr = lr_schedules.deserialize(lr)
+        return getattr(optimizers, cls)(learning_rate=lr, decay=c.get("decay", rec.decay), name=c.get("name", cls),
+                                        **{h.name: c.get(h.name, h.default) for h in rec.hyper})
 
     @staticmethod
     def get(identifier):
@@ -566,6 +710,22 @@ class Model:
                 self.net.slot(name).fill_(getattr(optimizer, start))
         self.net.momentum_cache.fill_(1.0)
         self.net.iterations = 0
+        self.net.restart_average()               # a fresh averaging wrapper starts from the variables as they then are
+
+    @contextlib.contextmanager
+    def average_weights(self):
+        """with model.average_weights(): ... -- inside the block the variables ARE their averages (theta <-> average by
+        content, LisecNet.swap_average): predict, evaluate and save see the averaged model, with the BatchNormalization
+        moving statistics as they stand.  On leaving, also by an exception, they are swapped back: theta, the average
+        and every later step are bit for bit those of a run that never entered.  Do not train inside the block.
+        ValueError on a model whose optimizer is not optimizers.MovingAverage / SWA."""
+        if not isinstance(self.optimizer, _AveragingOptimizer):
+            raise ValueError("average_weights() needs a model compiled with optimizers.MovingAverage or optimizers.SWA")
+        self.net.swap_average()
+        try:
+            yield self
+        finally:
+            self.net.swap_average()
 
     @property
     def metrics_names(self):
@@ -677,6 +837,8 @@ class Model:
             for cb in callbacks:
                 cb.on_epoch_begin(epoch, {})
             opt = self.optimizer.spec(device_lr=bool(callbacks))
+            if opt.average is not None:
+                self.net.average                 # started from the variables as they are now, if compile() asked for it
             # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
             # the descriptor on this stream, behind the previous epoch's last update
             captured = self._captured_step(samples, opt, seq_req, batch=B)
@@ -935,6 +1097,7 @@ class Model:
 
     def _restore_weights(self, w):
         p = self.net.params
+        torch.cuda.current_stream().wait_stream(self.net.side)   # behind what the last update left there to read theta
         p.theta.copy_(w[0])
         p.state.copy_(w[1])
         p.touch()                                   # every packed copy and fold is stale
@@ -981,11 +1144,19 @@ class Model:
         if str(path).endswith(".npz"):
             meta = dict(format="lisec_amd-npz-1", nx=self.nx, ny=self.ny, nz=self.nz, maxPoints=self.maxPoints,
                         iterations=self.net.iterations)
-            with open(path, "wb") as f:
-                np.savez(f, __meta__=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8), **d)
+            average = None
+            if isinstance(self.optimizer, _AveragingOptimizer):
+                # (only then: the archive of a model without a wrapper keeps its bytes)
+                meta["optimizer"] = optimizers.serialize(self.optimizer)
+                average = self._average_arrays()
+            _npz_write(path, meta, d, average)
             return
         from . import keras_h5
-        opt, slots = None, {}
+        opt, slots, wrapper = None, {}, {}
+        if isinstance(self.optimizer, _AveragingOptimizer):
+            own = {k: v for k, v in self.optimizer.get_config().items() if k != "optimizer"}
+            wrapper = dict(wrapper={"class_name": type(self.optimizer).__name__, "config": own},
+                           average=self._average_arrays())
         if self.optimizer is not None:
             o, scalar = self.optimizer, self.optimizer.record.scalar
             opt = o.record.as_dict(_serialize_rate(o.lr), o.decay, o.hyper)
@@ -997,12 +1168,39 @@ class Model:
                 slots[name] = {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
         compiled = self._compile_args or {}
         keras_h5.save_model(path, d, self.nx, self.ny, self.nz, self.maxPoints, optimizer=opt,
-                            iterations=self.net.iterations, regularizers=self.regularizers or None, **compiled, **slots)
+                            iterations=self.net.iterations, regularizers=self.regularizers or None, **compiled, **slots,
+                            **wrapper)
+
+    def _average_arrays(self):
+        """{trainable ParamStore name: array} of the weight average, as the slots travel."""
+        p, buf = self.net.params, self.net.average
+        torch.cuda.current_stream().wait_stream(self.net.side)       # behind the last update's averaging pass
+        return {n: p.view(n, buf=buf).detach().cpu().numpy() for n in p.trainable_names()}
 
     def summary(self):
         n = self.net.params.n_trainable()
         print(f"LisecNet grid ({self.nz},{self.nx},{self.ny},{self.maxPoints},6) -> "
               f"({self.nx // 2},{self.ny // 2},2) / ({self.nx // 2},{self.ny // 2},14); trainable params: {n:,}")
+
+
+_NPZ_AVERAGE = "__average__/"              # the key of a variable's average in an .npz archive: this, then its name
+
+
+def _npz_write(path, meta, params, average=None):
+    """The .npz form of a checkpoint: __meta__ (JSON), the variables by their ParamStore names and, for a model with an
+    averaging wrapper, {trainable name: array} of the average under "__average__/<name>"."""
+    extra = {_NPZ_AVERAGE + n: a for n, a in (average or {}).items()}
+    with open(path, "wb") as f:
+        np.savez(f, __meta__=np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8), **params, **extra)
+
+
+def _npz_read(path):
+    """-> (meta, {name: array} of the variables, {name: array} of the average: empty without one)."""
+    z = np.load(path, allow_pickle=False)
+    meta = json.loads(bytes(z["__meta__"]).decode())
+    params = {k: z[k] for k in z.files if k != "__meta__" and not k.startswith(_NPZ_AVERAGE)}
+    average = {k[len(_NPZ_AVERAGE):]: z[k] for k in z.files if k.startswith(_NPZ_AVERAGE)}
+    return meta, params, average
 
 
 def _deserialize_nested(x, deserialize):
@@ -1053,11 +1251,16 @@ def load_model(path, custom_objects=None):
         magic = f.read(8)
     dev = _lib.require_gpu()
     if magic[:4] != b"\x89HDF":
-        z = np.load(path, allow_pickle=False)
-        meta = json.loads(bytes(z["__meta__"]).decode())
-        params = ParamStore(dev, init={k: z[k] for k in z.files if k != "__meta__"})
+        meta, variables, average = _npz_read(path)
+        params = ParamStore(dev, init=variables)
         m = Model(meta["nx"], meta["ny"], meta["nz"], meta["maxPoints"], params=params)
         m.net.iterations = int(meta.get("iterations", 0))
+        if meta.get("optimizer") is not None:
+            # an averaging wrapper (the only optimizer an archive carries): compiled with the reference's loss, and the
+            # average restored; the wrapped optimizer's slots do not travel in an .npz and start at zero
+            m.compile(optimizer=optimizers.deserialize(meta["optimizer"]), loss=['mse', 'mse'])
+            m.net.iterations = int(meta.get("iterations", 0))
+            _load_average(m, average)
         return m
     from . import keras_h5
     ck = keras_h5.load_model(path)
@@ -1071,6 +1274,11 @@ def load_model(path, custom_objects=None):
         rec = optimizer_table.record_of(o)
         opt = getattr(optimizers, rec.class_name)(learning_rate=lr, decay=o["decay"],
                                                   **{h.name: o[h.name] for h in rec.hyper})
+        w = ck.get("wrapper")
+        if w is not None:
+            if w["class_name"] not in optimizers.WRAPPERS:
+                raise ValueError(f"{path}: optimizer wrapper class {w['class_name']!r} is not implemented")
+            opt = getattr(optimizers, w["class_name"])(opt, **w["config"])
         _compile_saved(m, opt, ck)
         m.net.iterations = ck["iterations"]
         p = m.net.params
@@ -1084,7 +1292,18 @@ def load_model(path, custom_objects=None):
                     p.view(n, buf=buf).copy_(torch.from_numpy(np.ascontiguousarray(saved[n])))
         if rec.scalar is not None and ck.get(rec.scalar) is not None:
             getattr(m.net, rec.scalar).fill_(float(ck[rec.scalar]))
+        if w is not None and ck.get("average") is not None:
+            _load_average(m, ck["average"])
     return m
+
+
+def _load_average(m, saved):
+    """Restores the weight average of a loaded model from {trainable ParamStore name: array}; a variable the file lacks
+    keeps the copy of theta the average starts from."""
+    p, buf = m.net.params, m.net.average
+    for n in p.trainable_names():
+        if n in saved:
+            p.view(n, buf=buf).copy_(torch.from_numpy(np.ascontiguousarray(saved[n], dtype=np.float32)))
 
 
 # ---------------------------------------------------------------------------------------------------

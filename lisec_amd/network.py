@@ -64,6 +64,48 @@ def loss_acc_split(loss, acc):
     return acc[:-1], acc[-1]
 
 
+class AverageSpec:
+    """The weight averaging of a step (optimizers.MovingAverage / optimizers.SWA; csrc/weight_average.hip): after every
+    update one pass folds theta into LisecNet.average.  kind 'ema': a <- a - (a - w)*(1 - decay_s), decay_s = 0 before
+    iteration `start`, then `decay`, or with `dynamic` min(decay, (1 + k)/(10 + k)), k = iterations - start; kind
+    'swa': a <- (a*m + w)/(m + 1) at the iterations start + m*period, nothing at the others.  Every refusal of the
+    library (include/lisec_hip.h) is a ValueError here, before any launch."""
+
+    KINDS = {"ema": _lib.AVG_EMA, "swa": _lib.AVG_SWA}
+
+    def __init__(self, kind, decay=0.0, dynamic=False, start=0, period=1):
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown averaging kind {kind!r}")
+        for name, v in (("start", start), ("period", period)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"the averaging {name} must be an integer, not {v!r}")
+        self.kind, self.decay, self.dynamic = kind, float(decay), bool(dynamic)
+        self.start, self.period = int(start), int(period)
+        if kind == "ema" and not 0.0 <= self.decay <= 1.0:       # (NaN fails both comparisons)
+            raise ValueError(f"average_decay must lie in [0, 1], not {decay!r}")
+        if self.start < 0:
+            raise ValueError(f"averaging cannot start at the negative iteration {start}")
+        if kind == "swa" and self.period < 1:
+            raise ValueError(f"average_period must be >= 1, not {period}")
+        self.descriptor = _lib.WeightAverage(self.KINDS[kind], int(self.dynamic), self.start, self.period, self.decay)
+
+    @property
+    def config(self):
+        """Hashable; part of OptimizerSpec.config, the key of the recorded plans (the descriptor is a launch argument)."""
+        if self.kind == "ema":
+            return ("ema", self.decay, self.dynamic, self.start)
+        return ("swa", self.start, self.period)
+
+    def __eq__(self, other):
+        return isinstance(other, AverageSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(self.config)
+
+    def __repr__(self):
+        return f"AverageSpec{self.config}"
+
+
 class OptimizerSpec:
     """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
     per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
@@ -82,15 +124,21 @@ class OptimizerSpec:
     number that may change between steps, e.g. from a LearningRateScheduler callback), the update kernels read lr_t from
     LisecNet's device descriptor (lisec_lr_schedule), which holds `lr_descriptor`; otherwise (lr, decay) are kernel
     arguments, as they always were.  Nadam's `decay` is its momentum-schedule decay (schedule_decay): its rate is not
-    divided by 1 + decay*it, its descriptor is built with decay = 0, and a schedule is refused as in tf.keras 2.4."""
+    divided by 1 + decay*it, its descriptor is built with decay = 0, and a schedule is refused as in tf.keras 2.4.
+    average: an AverageSpec, or None (no averaging: the step issues exactly the launches it always did, and `config`
+    is the tuple it always was)."""
 
     KINDS = tuple(optimizer_table.BY_KIND)
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1):
+                 epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1,
+                 average=None):
         rec = self.record = optimizer_table.BY_KIND.get(kind)
         if rec is None:
             raise ValueError(f"unknown optimizer kind {kind!r}")
+        if average is not None and not isinstance(average, AverageSpec):
+            raise ValueError(f"average must be an AverageSpec or None, not {average!r}")
+        self.average = average
         self.schedule = lr if isinstance(lr, lr_schedules.LearningRateSchedule) else None
         if self.schedule is not None and not rec.takes_schedule:
             raise ValueError(f"The {rec.class_name} optimizer does not support tf.keras.optimizers.LearningRateSchedules "
@@ -121,14 +169,15 @@ class OptimizerSpec:
     def config(self):
         """Every hyper-parameter, hashable: two specs with equal configs issue the same launches.  A schedule enters with
         its whole Keras config; a number read from the device descriptor (device_lr) does not enter at all -- like the
-        iteration count, it is data of the step, not of its launches."""
+        iteration count, it is data of the step, not of its launches.  The averaging joins only when there is one."""
         if self.schedule is not None:
             rate = ("schedule", json.dumps(lr_schedules.serialize(self.schedule), sort_keys=True))
         elif self.device_lr:
             rate = ("device",)
         else:
             rate = self.lr
-        return (self.kind, rate, self.decay, *self.hyper.values())
+        base = (self.kind, rate, self.decay, *self.hyper.values())
+        return base if self.average is None else base + (("average",) + self.average.config,)
 
     @property
     def slots(self):
@@ -679,6 +728,10 @@ class LisecNet:
         # kernel that ends a batch reads; made by _batch_buffers() when a batch larger than 1 is first used
         self._acc = self._acc_scale = None
         self._acc_div = 1
+        # weight averaging (OptimizerSpec.average): the average, shaped like theta, made by `average` when first used;
+        # not live: it is to be started again as a copy of theta at its next use (Model.compile)
+        self._average = None
+        self._average_live = False
         self.dense_dw_slabs = {}                         # middle block -> slabs of lisec_conv_extras.dense_dw
         self._fwd_events = {}
         # a repack enqueued on the second stream is pending (_arm_repack, apply_gradients): the forward waits for
@@ -1388,6 +1441,8 @@ class LisecNet:
         if lo % 4 or hi != self.params.n_theta:
             return
         opt = OptimizerSpec() if opt is None else opt
+        if opt.average is not None:
+            self.average                         # started from theta BEFORE any part of it is updated
         self._update(opt, lo, lo + (hi - lo) // 4 * 4, advance=False)
         self._early = (lo, opt)
 
@@ -1403,6 +1458,7 @@ class LisecNet:
         opt = OptimizerSpec() if opt is None else opt
         hi = self.params.theta.numel()
         second = self._early is not None
+        avg = self.average if opt.average is not None else None      # (made before the first launch of the update)
         if self._early is not None:
             lo, early_opt = self._early
             if early_opt != opt or (opt.device_lr and bytes(early_opt.lr_descriptor) != bytes(opt.lr_descriptor)):
@@ -1426,11 +1482,65 @@ class LisecNet:
             try:
                 self._pack_all(after_main=lambda: self._record(self._pack_done, self.side))
                 self._pack_all_t()
+                if avg is not None:
+                    # the averaging pass, behind the repacks on the second stream: off the critical path (nothing reads
+                    # the average during training), behind the update that advanced the count (state_bias -1), and in
+                    # front of _pack_late, which every later writer of theta is ordered behind -- the next early update
+                    # through this stream, the next apply_gradients through the forward's wait for _pack_late
+                    ops.weight_average(self.params.theta, avg, opt.average.descriptor, self._iter_dev, state_bias=-1)
             finally:
                 _lib.pin_stream(pin)
             self._record(self._pack_late, self.side)
             self._pack_pending = True
             self._late_pending = True
+
+    @property
+    def average(self):
+        """The weight average (OptimizerSpec.average): a buffer shaped like theta that holds a copy of theta when it is
+        made -- as a tfa slot starts at the variable's value -- and when it is first used after Model.compile; at a fixed
+        address from then on (recorded step plans point at it)."""
+        self._prepare_training()
+        if not self._average_live:
+            torch.cuda.current_stream().wait_stream(self.side)
+            if self._average is None:
+                self._average = self.params.theta.clone()
+            else:
+                self._average.copy_(self.params.theta)
+            self._average_live = True
+            torch.cuda.synchronize(self.device)   # whole before any stream of the step (the second one included) uses it
+        return self._average
+
+    def restart_average(self):
+        """The average starts again as a copy of theta at its next use (a fresh optimizer: Model.compile)."""
+        self._average_live = False
+
+    def _exchange_average(self, swap):
+        if self._early is not None:
+            raise RuntimeError("the variables cannot be exchanged with their average while an early update is pending: "
+                               "apply_gradients() ends the step first")
+        avg = self.average
+        # behind the repack and the averaging pass that the last update left pending on the second stream
+        torch.cuda.current_stream().wait_stream(self.side)
+        if swap:
+            ops.weight_swap(self.params.theta, avg)
+        else:
+            self.params.theta.copy_(avg)
+        self.params_version += 1
+        self.params.touch()                       # the packed and transposed copies, the folds, the composed head, bf16
+        if self._pack_done is not None:
+            self._arm_repack()                    # a recorded step that follows waits for these events
+
+    def swap_average(self):
+        """theta <-> average BY CONTENT (lisec_weight_swap), on the current stream: recorded step plans hold both
+        addresses, so the buffers themselves never change places.  Everything keyed on the variables' version -- the
+        packed and transposed copies, the folded inference weights, the composed head, the bf16 packs -- is made again
+        from the new theta, and the repack events are armed again for a recorded step that follows.  Two swaps restore
+        both buffers bit for bit.  RuntimeError while an early update is pending."""
+        self._exchange_average(True)
+
+    def assign_average(self):
+        """theta <- average (the average is kept); otherwise as swap_average()."""
+        self._exchange_average(False)
 
     def _arm_repack(self):
         """Repacks the variables now, on the current stream, and arms the two events the forward of a recorded step waits
@@ -1509,6 +1619,8 @@ class LisecNet:
         if position not in self._ACC_MODE:
             raise ValueError(f"position must be one of {self.BATCH_POSITIONS}, not {position!r}")
         self._batch_buffers()
+        if opt is not None and opt.average is not None:
+            self.average                           # made before the first launch of a step that averages
         mode, last, n = self._ACC_MODE[position], position == "last", self.params.n_theta
         bucketed = allreduce is not None and hasattr(allreduce, "start_tail")
         head = [n]                                 # where the range the hook has served starts
@@ -1559,7 +1671,11 @@ class LisecNet:
         """One fit() step at batch_size=1: forward (batch statistics) + backward + the update by `opt` (an OptimizerSpec;
         None: the reference's SGD-Nesterov).  side_filler: see backward().
         allreduce: optional data-parallel gradient average -- with start_tail (parallel._BucketedAverage) in two buckets,
-        otherwise a callable(grad) run after the backward pass."""
+        otherwise a callable(grad) run after the backward pass.
+        opt.average (an AverageSpec): one averaging pass over theta follows the update, on the second stream behind the
+        repacks (apply_gradients); the update itself is untouched."""
+        if opt is not None and opt.average is not None:
+            self.average                           # made before the first launch of a step that averages
         self.forward(sample, training=True)
         if allreduce is not None and hasattr(allreduce, "start_tail"):
             # two buckets: the RPN + head gradients (the tail of theta) are reduced under the rest of the backward
@@ -1699,6 +1815,8 @@ class _TrainingPlans(_StepPlans):
         batch = int(batch)
         if batch > 1:
             net._batch_buffers()                 # likewise: the accumulator and the divisor
+        if self.opt.average is not None:
+            net.average                          # likewise: the weight average
         keep = self._snapshot()
         self.samples = [self.vox(pts) for pts in self.points]
         # eager warm-up (lazy workspaces, descriptor tables, events; it leaves the next step's repack pending, which is
@@ -1726,7 +1844,8 @@ class _TrainingPlans(_StepPlans):
         net, p = self.net, self.net.params
         return (p.theta.clone(), p.state.clone(), {k: t.clone() for k, t in net.slots().items()}, net._iter_dev.clone(),
                 net._iterations, net.momentum_cache.clone(),
-                None if net._acc is None else (net._acc.clone(), net._acc_scale.clone(), net._acc_div))
+                None if net._acc is None else (net._acc.clone(), net._acc_scale.clone(), net._acc_div),
+                net._average.clone() if net._average_live else None)
 
     def _record_micro_plans(self, positions):
         """The plans of the micro-steps of a batch, per buffer set: one eager batch of len(positions) sweeps (first,
@@ -1759,6 +1878,8 @@ class _TrainingPlans(_StepPlans):
             net._acc.copy_(keep[6][0])
             net._acc_scale.copy_(keep[6][1])
             net._acc_div = keep[6][2]
+        if keep[7] is not None:
+            net._average.copy_(keep[7])
 
     def _enqueue(self, j, position="single"):
         """One eager step on buffer set j (warm-up, or recorded while it runs)."""

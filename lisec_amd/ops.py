@@ -706,6 +706,31 @@ def grad_accumulate(grad, acc, mode, scale=None):
                                                  _lib.current_stream()))
 
 
+def weight_average(theta, avg, desc, state, state_bias=0):
+    """One averaging pass of lisec_weight_average over the whole of `theta` (read) and `avg` (float32 device tensors of
+    one length, a multiple of 4): desc an _lib.WeightAverage (host; copied into the launch), state the device iteration
+    count, read as state[0] + state_bias -- 0 in front of the update that advances it, -1 behind it.  EMA: a <- a -
+    (a - w)*c, SWA: a <- (a*m + w)/(m + 1) on a snapshot step, every op rounded to fp32 on its own (include/lisec_hip.h)."""
+    if theta.numel() != avg.numel():
+        raise ValueError(f"weight_average: {theta.numel()} variables, {avg.numel()} averages")
+    _lib.check(_lib.load().lisec_weight_average(_lib.ptr(theta), _lib.ptr(avg), theta.numel(), ctypes.byref(desc),
+                                                _lib.ptr(state), int(state_bias), _lib.current_stream()))
+
+
+def weight_swap(a, b):
+    """a <-> b by content, bit for bit (lisec_weight_swap; float32 device tensors of one length, a multiple of 4)."""
+    if a.numel() != b.numel():
+        raise ValueError(f"weight_swap: {a.numel()} and {b.numel()} floats")
+    _lib.check(_lib.load().lisec_weight_swap(_lib.ptr(a), _lib.ptr(b), a.numel(), _lib.current_stream()))
+
+
+def weight_average_eval(desc, state, k, c_out=None, m_out=None):
+    """For j < k, at iteration state[0] + j: EMA c_out[j] = c (float32), SWA m_out[j] = m or -1 off a snapshot (int64)
+    (lisec_weight_average_eval; state is not advanced)."""
+    _lib.check(_lib.load().lisec_weight_average_eval(ctypes.byref(desc), _lib.ptr(state), int(k), _lib.ptr(c_out),
+                                                     _lib.ptr(m_out), _lib.current_stream()))
+
+
 def conv_field_forward_workspace_bytes(g, row_capacity):
     return _lib.load().lisec_conv_field_forward_workspace_bytes(ctypes.byref(g), row_capacity)
 
