@@ -1079,6 +1079,41 @@ int lisec_weight_swap(float* a, float* b, long long n, lisec_stream_t stream);
 int lisec_weight_average_eval(const lisec_weight_average_desc* desc /* host, copied */, const long long* state /* device */,
                               long long k, float* c_out, long long* m_out, lisec_stream_t stream);
 
+/* Decoupled weight decay (optimizers.AdamW / SGDW / extend_with_decoupled_weight_decay; csrc/weight_decay.hip): one
+ * streaming pass over the flat parameter buffer `theta`, run IN FRONT of an optimizer entry on the same range and the
+ * same stream -- the order of tfa.optimizers.DecoupledWeightDecayExtension, which decays the variable first and then
+ * updates the decayed variable.  The host cuts every DECAYED variable into chunks by the rules of lisec_reg_chunk:
+ * offset and count in floats and multiples of 4, offset relative to the theta pointer given, count <= LISEC_REG_CHUNK, a
+ * chunk never crosses a variable, ascending.  Only the decayed variables are in the table: an excluded variable costs
+ * no traffic.  The table is device memory and is NOT checked: every [offset, offset + count) must lie inside theta.
+ * coeff: a lisec_lr_schedule in DEVICE memory (written by lisec_lr_schedule_set; its `decay` must be 0).  With s =
+ * state[0], the iteration count before the update -- read from the device, NEVER advanced, no ticket taken --
+ *     wd_t = (float)schedule(s)     in double, once per workgroup, rounded once (the formulas of the table above)
+ * As the coefficient is always read from the device, a recorded step plan replays correctly at every count, the host
+ * may rewrite the coefficient between steps without recording again, and both parts of a split update (they read the
+ * same count) decay with the same wd_t.  As in tfa, wd_t is NOT multiplied by the learning rate.
+ * THE ARITHMETIC IS A CONTRACT (tests pin it bit for bit): for every element w of every chunk
+ *     p = wd_t * w;   w <- w - p
+ * each an IEEE fp32 round-to-nearest-even operation of its own, never contracted into an fma, never rewritten as
+ * w*(1 - wd_t); denormals are kept.  wd_t == 0.0f: every thread returns and theta keeps its bits (the sign of a -0
+ * included; the launch is made all the same: the host does not know s).  The floats outside every chunk keep their
+ * bits.  No atomics, one thread per element: the same bits from run to run.
+ * Fixed addresses, no host reads, no allocation: the launch records into a step plan.  n_chunks == 0 is valid (nothing
+ * is enqueued).  LISEC_EINVAL, nothing enqueued: NULL theta, chunks, coeff or state, n_chunks < 0, theta not 16-byte
+ * aligned, state not 8-byte aligned.
+ * lisec_weight_decay_eval: wd_out[j] = wd_t at s = state[0] + j, j < k (device pointers; state is read, never
+ * advanced): the device function of the pass, for tests. */
+typedef struct lisec_decay_chunk {
+    long long offset;
+    int count;
+    int reserved;   /* 0 */
+} lisec_decay_chunk;
+int lisec_weight_decay(float* theta, const lisec_decay_chunk* chunks /* device */, int n_chunks,
+                       const lisec_lr_schedule* coeff /* device */, const long long* state /* device */,
+                       lisec_stream_t stream);
+int lisec_weight_decay_eval(const lisec_lr_schedule* coeff /* device */, const long long* state /* device */, long long k,
+                            float* wd_out, lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4b. Data-parallel gradient exchange.  The reference trains in ONE process
  *     (model.fit, model_training.py:299); here whole samples are sharded over one process per GPU and the

@@ -122,6 +122,10 @@ class RegChunk(Structure):                     # lisec_reg_chunk
     _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("l1", c_float), ("l2", c_float), ("flags", c_int)]
 
 
+class DecayChunk(Structure):                   # lisec_decay_chunk
+    _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("reserved", c_int)]
+
+
 LOSS_MAX_METRICS = 4                           # LISEC_LOSS_MAX_METRICS
 
 
@@ -428,6 +432,10 @@ def _declare(lib):
     lib.lisec_weight_swap.argtypes = [P, P, LL, P]
     lib.lisec_weight_average_eval.restype = c_int
     lib.lisec_weight_average_eval.argtypes = [POINTER(WeightAverage), P, LL, P, P, P]
+    lib.lisec_weight_decay.restype = c_int
+    lib.lisec_weight_decay.argtypes = [P, P, c_int, P, P, P]
+    lib.lisec_weight_decay_eval.restype = c_int
+    lib.lisec_weight_decay_eval.argtypes = [P, P, LL, P, P]
     lib.lisec_comm_unique_id.restype = c_int
     lib.lisec_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.lisec_comm_init.restype = c_int

@@ -241,15 +241,29 @@ WRAPPER_CLASSES = ("MovingAverage", "SWA")
 AVERAGE_KIND = "average"
 
 
+def written_class(optimizer):
+    """The class name an optimizer dict is written under: its record's (optimizer_table.record_of), or <Base>W for the
+    decoupled-weight-decay class of <Base> (model_training.optimizers.extend_with_decoupled_weight_decay), whose record,
+    kernels and slot kinds are <Base>'s.  The spelling of that config -- Keras' keys of <Base>, then "weight_decay" and
+    "decay_var_list" -- is this project's restatement of tfa's: tfa is not installed, parity unpinned."""
+    rec, cls = optimizer_table.record_of(optimizer), optimizer.get("class_name")
+    return cls if cls != rec.class_name and optimizer_table.base_class(cls) == rec.class_name else rec.class_name
+
+
 def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrapper=None):
     """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
     loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote).  optimizer_config holds Keras'
     keys in Keras' order, a key the dict lacks at Keras' default (optimizer_table)."""
     o = optimizer or {}
     rec = optimizer_table.record_of(o)
-    oc = {"class_name": rec.class_name, "config": {
-        "name": rec.class_name, "learning_rate": _rate(o.get("lr", rec.lr)), "decay": float(o.get("decay", rec.decay)),
+    cls = written_class(o)
+    oc = {"class_name": cls, "config": {
+        "name": cls, "learning_rate": _rate(o.get("lr", rec.lr)), "decay": float(o.get("decay", rec.decay)),
         **rec.values(o)}}
+    if cls != rec.class_name:                     # <Base>W: the coefficient (a number or a serialized schedule) and,
+        oc["config"]["weight_decay"] = _rate(o.get("weight_decay", 0.0))          # only when given, the decayed variables
+        if o.get("decay_var_list") is not None:
+            oc["config"]["decay_var_list"] = list(o["decay_var_list"])
     if wrapper is not None:
         c = dict(wrapper["config"])
         oc = {"class_name": wrapper["class_name"], "config": {"name": c.pop("name", wrapper["class_name"]),
@@ -313,7 +327,7 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
         if optimizer is None:
             return
         rec = optimizer_table.record_of(optimizer)
-        cls, kept = rec.class_name, rec.active_slots(rec.values(optimizer))
+        cls, kept = written_class(optimizer), rec.active_slots(rec.values(optimizer))
         if any(given.get(s.name) is None for s in kept):
             return
         # Keras' order: iter, the optimizer's own scalar, then one slot kind for every variable before the next kind
@@ -457,10 +471,15 @@ def load_model(path, grid=None):
                 out["wrapper"] = {"class_name": oc["class_name"], "config": {k: v for k, v in c.items() if k != "optimizer"}}
                 oc = c["optimizer"]
                 c = oc.get("config", {})
-            rec = optimizer_table.BY_CLASS.get(oc.get("class_name"))
+            base = optimizer_table.base_class(oc.get("class_name"))
+            rec = optimizer_table.BY_CLASS.get(base)
             if rec is not None:               # another optimizer class: no optimizer, the model comes back uncompiled
                 out["optimizer"] = rec.as_dict(c.get("learning_rate", c.get("lr", rec.lr)), c.get("decay", rec.decay),
                                                {h.name: c.get(h.name, h.default) for h in rec.hyper})
+                if base != oc["class_name"]:  # <Base>W: the record is <Base>'s, the dict carries the class and the decay
+                    out["optimizer"].update(class_name=oc["class_name"], weight_decay=c.get("weight_decay", 0.0))
+                    if c.get("decay_var_list") is not None:
+                        out["optimizer"]["decay_var_list"] = list(c["decay_var_list"])
         if "optimizer_weights" in f:
             og = f["optimizer_weights"]
             slot_dataset = re.compile(r"([^/]+)/(.+)/(%s):0" % "|".join(optimizer_table.SLOT_KINDS + (AVERAGE_KIND,)))

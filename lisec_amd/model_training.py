@@ -26,8 +26,8 @@ import torch
 
 from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table, regularizers
-from .network import (AverageSpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len, loss_acc_logs,
-                      loss_acc_split)
+from .network import (AverageSpec, DecaySpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len,
+                      loss_acc_logs, loss_acc_split)
 from .params import ParamStore, fold_depth, param_specs
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
@@ -274,7 +274,11 @@ class _Optimizer:
 
     @property
     def record(self):
-        return optimizer_table.BY_CLASS[type(self).__name__]
+        return optimizer_table.BY_CLASS[optimizer_table.base_class(type(self).__name__)]
+
+    def decay_spec(self):
+        """The DecaySpec of the optimizer's decoupled weight decay; None for an optimizer without one."""
+        return None
 
     def _set(self, name, lr, decay, kwargs, **hyper):
         _no_clipping(type(self).__name__, kwargs)
@@ -292,10 +296,38 @@ class _Optimizer:
     def spec(self, device_lr=False):
         """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
         callbacks, which may change it between epochs)."""
-        return OptimizerSpec(self.record.kind, self.lr, self.decay, device_lr=device_lr, **self.hyper)
+        return OptimizerSpec(self.record.kind, self.lr, self.decay, device_lr=device_lr, weight_decay=self.decay_spec(),
+                             **self.hyper)
 
     def get_config(self):
         return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper}
+
+
+class _DecoupledWeightDecay:
+    """What the classes of optimizers.extend_with_decoupled_weight_decay put in front of their base optimizer: the
+    first argument weight_decay -- a number or a built-in LearningRateSchedule, a plain attribute that a callback may
+    assign between epochs, like lr --, the keyword decay_var_list, the DecaySpec in spec() and both in get_config().
+    The record, the kernels and the slots are the base class's."""
+
+    def _set_decay(self, weight_decay, decay_var_list):
+        if not isinstance(weight_decay, lr_schedules.LearningRateSchedule):
+            DecaySpec(weight_decay)                 # ValueError for anything but a finite number >= 0
+            weight_decay = float(weight_decay)
+        self.weight_decay = weight_decay
+        if decay_var_list is not None:
+            decay_var_list = [decay_var_list] if isinstance(decay_var_list, str) else list(decay_var_list)
+        self.decay_var_list = decay_var_list
+        self.decay_spec()           # the range checks; a schedule the kernel cannot evaluate is refused here
+
+    def decay_spec(self):
+        return DecaySpec(self.weight_decay, self.decay_var_list)
+
+    def get_config(self):
+        config = super().get_config()
+        config["weight_decay"] = _serialize_rate(self.weight_decay)
+        if self.decay_var_list is not None:
+            config["decay_var_list"] = list(self.decay_var_list)
+        return config
 
 
 class _AveragingOptimizer(_Optimizer):
@@ -332,7 +364,10 @@ class _AveragingOptimizer(_Optimizer):
     def spec(self, device_lr=False):
         inner = self._optimizer
         return OptimizerSpec(inner.record.kind, inner.lr, inner.decay, device_lr=device_lr, average=self.average_spec(),
-                             **inner.hyper)
+                             weight_decay=inner.decay_spec(), **inner.hyper)
+
+    def decay_spec(self):
+        return self._optimizer.decay_spec()
 
     def _nested(self):
         inner = self._optimizer
@@ -427,6 +462,63 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
             self._set(name, lr if lr is not None else learning_rate, schedule_decay if decay is None else decay, kwargs,
                       beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
 
+    class AdamW(_DecoupledWeightDecay, Adam):
+        """tfa.optimizers.AdamW as this project restates it (parity unpinned): Adam with DECOUPLED weight
+        decay.  Directly in front of every update w <- w - wd_t*w (a float32 multiply and a float32 subtraction;
+        csrc/weight_decay.hip), then Adam updates the decayed variable.  weight_decay: a number or one of the built-in
+        schedules of optimizers.schedules, evaluated at the iteration count before the update; a plain attribute that a
+        callback may assign between epochs.  As in tfa, the decay is NOT multiplied by the learning rate: who
+        schedules the one must schedule the other.  decay_var_list: the variables to decay -- ParamStore names and / or
+        the kinds 'kernel', 'bias', 'gamma', 'beta'; None: every trainable variable, tfa's default.  It is a
+        constructor keyword here: tfa passes it to minimize(), which this API does not have.  lr=, decay= and the
+        clipping keywords behave as in Adam (clipping is refused).  ValueError: a weight_decay that is not a finite
+        number >= 0; NotImplementedError: a schedule of one's own."""
+
+        def __init__(self, weight_decay, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False,
+                     name="AdamW", decay_var_list=None, **kwargs):
+            self._set_decay(weight_decay, decay_var_list)
+            optimizers.Adam.__init__(self, learning_rate=learning_rate, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon,
+                                     amsgrad=amsgrad, name=name, **kwargs)
+
+    class SGDW(_DecoupledWeightDecay, SGD):
+        """tfa.optimizers.SGDW as this project restates it (parity unpinned): SGD (momentum, Nesterov) on the variables
+        after w <- w - wd_t*w.  Arguments as in AdamW; tfa's default learning rate of 0.001, not SGD's 0.01."""
+
+        def __init__(self, weight_decay, learning_rate=0.001, momentum=0.0, nesterov=False, name="SGDW",
+                     decay_var_list=None, **kwargs):
+            self._set_decay(weight_decay, decay_var_list)
+            lr = kwargs.pop("lr", None)
+            optimizers.SGD.__init__(self, lr=lr if lr is not None else learning_rate, momentum=momentum,
+                                    nesterov=nesterov, name=name, **kwargs)
+
+    _DECOUPLED = {SGD: SGDW, Adam: AdamW}       # base class -> its class with decoupled weight decay, made once
+
+    @staticmethod
+    def extend_with_decoupled_weight_decay(base_class):
+        """tfa.optimizers.extend_with_decoupled_weight_decay: the class <Base>W of one of the seven optimizer classes
+        above -- its first argument is weight_decay, the others are the base class's, plus the keyword decay_var_list
+        (see AdamW).  AdamW and SGDW are the classes of Adam and SGD.  The same class object at every call.
+        ValueError for anything but one of the seven."""
+        made = optimizers._DECOUPLED.get(base_class)
+        if made is not None:
+            return made
+        name = getattr(base_class, "__name__", None)
+        if name not in optimizer_table.BY_CLASS or getattr(optimizers, name, None) is not base_class:
+            raise ValueError(f"extend_with_decoupled_weight_decay takes one of the optimizer classes "
+                             f"{', '.join(optimizer_table.BY_CLASS)}, not {base_class!r}")
+
+        def __init__(self, weight_decay, *args, decay_var_list=None, **kwargs):
+            self._set_decay(weight_decay, decay_var_list)
+            kwargs.setdefault("name", name + "W")
+            base_class.__init__(self, *args, **kwargs)
+
+        made = type(name + "W", (_DecoupledWeightDecay, base_class), {
+            "__init__": __init__,
+            "__doc__": f"{name} with decoupled weight decay: w <- w - wd_t*w directly in front of every update "
+                       f"(optimizers.AdamW describes weight_decay and decay_var_list); the other arguments are {name}'s."})
+        optimizers._DECOUPLED[base_class] = made
+        return made
+
     class MovingAverage(_AveragingOptimizer):
         """tfa.optimizers.MovingAverage as this project restates it (parity unpinned): after every update
         average <- average - (average - w)*(1 - decay_s), decay_s = 0 before iteration start_step, then average_decay, or
@@ -499,14 +591,22 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
         if cls in optimizers.WRAPPERS:
             inner = optimizers.deserialize(c.pop("optimizer"))
             return getattr(optimizers, cls)(inner, **c)
-        rec = optimizer_table.BY_CLASS.get(cls)
+        base = optimizer_table.base_class(cls)   # <Base>W: <Base> with decoupled weight decay
+        rec = optimizer_table.BY_CLASS.get(base)
         if rec is None:
             raise ValueError(f"optimizer class {cls!r} is not implemented")
         lr = c.get("learning_rate", c.get("lr", rec.lr))
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
-        return getattr(optimizers, cls)(learning_rate=lr, decay=c.get("decay", rec.decay), name=c.get("name", cls),
-                                        **{h.name: c.get(h.name, h.default) for h in rec.hyper})
+        given = dict(learning_rate=lr, decay=c.get("decay", rec.decay), name=c.get("name", cls),
+                     **{h.name: c.get(h.name, h.default) for h in rec.hyper})
+        if base == cls:
+            return getattr(optimizers, cls)(**given)
+        wd = c.get("weight_decay", 0.0)
+        if isinstance(wd, dict):
+            wd = lr_schedules.deserialize(wd)
+        return optimizers.extend_with_decoupled_weight_decay(getattr(optimizers, base))(
+            wd, decay_var_list=c.get("decay_var_list"), **given)
 
     @staticmethod
     def get(identifier):
@@ -693,6 +793,11 @@ class Model:
         "<output>_<name>" (see metrics_names).  weighted_metrics: not implemented (there are no sample weights).
         Every refusal (ValueError, NotImplementedError) is raised here, before any launch."""
         optimizer = optimizers.get(optimizer)
+        wd = optimizer.decay_spec()
+        if wd is not None:
+            # a decay_var_list this network cannot serve: KeyError for an unknown name, ValueError for a variable
+            # that is not trainable (ops.decay_chunks)
+            self.net.decay_table(wd.variables)
         step_loss, names = losses.compile_loss(loss, loss_weights, metrics, weighted_metrics)
         self.optimizer, self.loss = optimizer, step_loss
         self._metric_names = names
@@ -843,6 +948,7 @@ class Model:
             # the descriptor on this stream, behind the previous epoch's last update
             captured = self._captured_step(samples, opt, seq_req, batch=B)
             self.net._sync_lr(opt)
+            self.net._sync_wd(opt)               # likewise the coefficient of a decoupled weight decay
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
@@ -1160,7 +1266,13 @@ class Model:
         if self.optimizer is not None:
             o, scalar = self.optimizer, self.optimizer.record.scalar
             opt = o.record.as_dict(_serialize_rate(o.lr), o.decay, o.hyper)
-            if scalar is not None:                                   # Nadam's momentum_cache
+            inner = o._optimizer if isinstance(o, _AveragingOptimizer) else o
+            if isinstance(inner, _DecoupledWeightDecay):
+                # (only then: the file of an optimizer without decoupled decay keeps its bytes)
+                opt.update(class_name=type(inner).__name__, weight_decay=_serialize_rate(inner.weight_decay))
+                if inner.decay_var_list is not None:
+                    opt["decay_var_list"] = list(inner.decay_var_list)
+            if scalar is not None:                                 # Nadam's momentum_cache
                 slots[scalar] = float(getattr(self.net, scalar).item())
             p = self.net.params
             for name in o.spec().slots:
@@ -1272,8 +1384,15 @@ def load_model(path, custom_objects=None):
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
         rec = optimizer_table.record_of(o)
-        opt = getattr(optimizers, rec.class_name)(learning_rate=lr, decay=o["decay"],
-                                                  **{h.name: o[h.name] for h in rec.hyper})
+        given = dict(learning_rate=lr, decay=o["decay"], **{h.name: o[h.name] for h in rec.hyper})
+        if o.get("weight_decay") is None:
+            opt = getattr(optimizers, rec.class_name)(**given)
+        else:                                                        # <Base>W: decoupled weight decay
+            wd = o["weight_decay"]
+            if isinstance(wd, dict):
+                wd = lr_schedules.deserialize(wd)
+            opt = optimizers.extend_with_decoupled_weight_decay(getattr(optimizers, rec.class_name))(
+                wd, decay_var_list=o.get("decay_var_list"), **given)
         w = ck.get("wrapper")
         if w is not None:
             if w["class_name"] not in optimizers.WRAPPERS:

@@ -16,6 +16,7 @@ model_training.py:299):
 import bisect
 import ctypes
 import json
+import math
 import os
 
 import numpy as np
@@ -106,6 +107,62 @@ class AverageSpec:
         return f"AverageSpec{self.config}"
 
 
+class DecaySpec:
+    """The decoupled weight decay of a step (optimizers.AdamW / SGDW / extend_with_decoupled_weight_decay;
+    csrc/weight_decay.hip): directly in front of every optimizer update, w <- w - wd_t*w on the decayed variables, wd_t
+    the coefficient at the iteration count before the update -- NOT multiplied by the learning rate.
+    weight_decay: a number (finite, >= 0, finite in float32; else ValueError) or one of the built-in
+    LearningRateSchedules (one of the user's own: NotImplementedError, from lr_schedules.descriptor).
+    variables: None -- every trainable variable, tfa's default --, or an iterable of ParamStore names and / or the kinds
+    'kernel', 'bias', 'gamma', 'beta'; the names are resolved by the network that runs the step (ops.decay_chunks)."""
+
+    def __init__(self, weight_decay, variables=None):
+        self.schedule = weight_decay if isinstance(weight_decay, lr_schedules.LearningRateSchedule) else None
+        if self.schedule is None:
+            try:
+                value = None if isinstance(weight_decay, bool) else float(weight_decay)
+            except (TypeError, ValueError):
+                value = None
+            if value is None or not 0 <= value <= float(np.finfo(np.float32).max):       # (NaN fails both comparisons)
+                raise ValueError(f"weight_decay must be a finite number >= 0 (finite in float32) or a "
+                                 f"LearningRateSchedule, not {weight_decay!r}")
+            weight_decay = value
+        self.weight_decay = weight_decay
+        if variables is not None:
+            if isinstance(variables, str):
+                variables = (variables,)
+            variables = tuple(variables)
+            if not all(isinstance(v, str) for v in variables):
+                raise ValueError(f"the decayed variables must be given by name or kind, not {variables!r}")
+        self.variables = variables
+        # validates a schedule: NotImplementedError for one of the user's own, ValueError past the device's limits
+        self.descriptor = lr_schedules.descriptor(weight_decay, 0.0)
+
+    @property
+    def is_zero(self):
+        """The constant number 0: no decay at all."""
+        return self.schedule is None and self.weight_decay == 0
+
+    @property
+    def config(self):
+        """Hashable; part of OptimizerSpec.config.  A schedule enters with its whole Keras config; a number does not
+        enter at all -- ("device",), as with device_lr: it is data of the step, not of its launches."""
+        if self.schedule is not None:
+            rate = ("schedule", json.dumps(lr_schedules.serialize(self.schedule), sort_keys=True))
+        else:
+            rate = ("device",)
+        return (rate, self.variables)
+
+    def __eq__(self, other):
+        return isinstance(other, DecaySpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(self.config)
+
+    def __repr__(self):
+        return f"DecaySpec({self.weight_decay!r}, variables={self.variables!r})"
+
+
 class OptimizerSpec:
     """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
     per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
@@ -126,19 +183,24 @@ class OptimizerSpec:
     arguments, as they always were.  Nadam's `decay` is its momentum-schedule decay (schedule_decay): its rate is not
     divided by 1 + decay*it, its descriptor is built with decay = 0, and a schedule is refused as in tf.keras 2.4.
     average: an AverageSpec, or None (no averaging: the step issues exactly the launches it always did, and `config`
-    is the tuple it always was)."""
+    is the tuple it always was).
+    weight_decay: a DecaySpec, or None; the constant number 0 is the same as None (no decay: no launch, and the base
+    optimizer's `config`)."""
 
     KINDS = tuple(optimizer_table.BY_KIND)
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
                  epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1,
-                 average=None):
+                 average=None, weight_decay=None):
         rec = self.record = optimizer_table.BY_KIND.get(kind)
         if rec is None:
             raise ValueError(f"unknown optimizer kind {kind!r}")
         if average is not None and not isinstance(average, AverageSpec):
             raise ValueError(f"average must be an AverageSpec or None, not {average!r}")
         self.average = average
+        if weight_decay is not None and not isinstance(weight_decay, DecaySpec):
+            raise ValueError(f"weight_decay must be a DecaySpec or None, not {weight_decay!r}")
+        self.weight_decay = None if weight_decay is None or weight_decay.is_zero else weight_decay
         self.schedule = lr if isinstance(lr, lr_schedules.LearningRateSchedule) else None
         if self.schedule is not None and not rec.takes_schedule:
             raise ValueError(f"The {rec.class_name} optimizer does not support tf.keras.optimizers.LearningRateSchedules "
@@ -169,7 +231,8 @@ class OptimizerSpec:
     def config(self):
         """Every hyper-parameter, hashable: two specs with equal configs issue the same launches.  A schedule enters with
         its whole Keras config; a number read from the device descriptor (device_lr) does not enter at all -- like the
-        iteration count, it is data of the step, not of its launches.  The averaging joins only when there is one."""
+        iteration count, it is data of the step, not of its launches.  The averaging joins only when there is one, and
+        so does the decoupled weight decay."""
         if self.schedule is not None:
             rate = ("schedule", json.dumps(lr_schedules.serialize(self.schedule), sort_keys=True))
         elif self.device_lr:
@@ -177,7 +240,11 @@ class OptimizerSpec:
         else:
             rate = self.lr
         base = (self.kind, rate, self.decay, *self.hyper.values())
-        return base if self.average is None else base + (("average",) + self.average.config,)
+        if self.average is not None:
+            base += (("average",) + self.average.config,)
+        if self.weight_decay is not None:
+            base += (("weight_decay",) + self.weight_decay.config,)
+        return base
 
     @property
     def slots(self):
@@ -754,6 +821,13 @@ class LisecNet:
         # iteration count; _sync_lr rewrites it, stream-ordered, when a step needs other contents
         self._lr_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
         self._lr_host = None
+        # the coefficient of the decoupled weight decay (OptimizerSpec.weight_decay; csrc/weight_decay.hip): a second
+        # descriptor of the same type at a fixed address, written by _sync_wd as _sync_lr writes the rate's; and the
+        # chunk tables of the decayed variables, made when a selection is first used and kept for the net's life
+        # (recorded plans point at them): {DecaySpec.variables: (ascending offsets, device table)}
+        self._wd_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
+        self._wd_host = None
+        self._decay_tables = {}
         self.loss_out = torch.zeros(3, dtype=f32, device=dev)
         # the metrics of a LossSpec loss (lisec_head_loss), class output's first; fixed address, like loss_out
         self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
@@ -1386,6 +1460,38 @@ class LisecNet:
             ops.lr_schedule_set(self._lr_dev, opt.lr_descriptor)
             self._lr_host = opt.lr_descriptor                 # kept alive: the source of the copy
 
+    def _sync_wd(self, opt):
+        """_sync_lr for the coefficient of the decoupled weight decay: makes the device descriptor hold
+        opt.weight_decay.descriptor (nothing for a spec without decay)."""
+        if opt.weight_decay is None:
+            return
+        desc = opt.weight_decay.descriptor
+        if self._wd_host is None or bytes(self._wd_host) != bytes(desc):
+            ops.lr_schedule_set(self._wd_dev, desc)
+            self._wd_host = desc                              # kept alive: the source of the copy
+
+    def decay_table(self, variables=None):
+        """(ascending offsets, device chunk table) of the variables a DecaySpec selects (ops.decay_chunks: None, names
+        and / or kinds), made once per selection.  KeyError: a name the network does not have; ValueError: a variable
+        that is not trainable."""
+        entry = self._decay_tables.get(variables)
+        if entry is None:
+            rows = ops.decay_chunks(self.params, variables)
+            entry = self._decay_tables[variables] = ([r[0] for r in rows], ops.decay_table(rows, self.device))
+        return entry
+
+    def _decay(self, opt, lo, hi):
+        """The decoupled weight decay of the variables in theta[lo:hi] (lo: a variable boundary), on the current
+        stream: w <- w - wd_t*w at the device iteration count, which is read and left alone.  Nothing at all for a spec
+        without decay."""
+        if opt.weight_decay is None:
+            return
+        offsets, table = self.decay_table(opt.weight_decay.variables)
+        first = bisect.bisect_left(offsets, lo)
+        last = bisect.bisect_left(offsets, hi)
+        self._sync_wd(opt)
+        ops.weight_decay(self.params.theta, table, last - first, self._wd_dev, self._iter_dev, first=first)
+
     def _regularize(self, lo, hi, accumulate=False, fold=False, grad=True):
         """The weight penalties of the variables in theta[lo:hi] (lo: a variable boundary), on the current stream: grad +=
         2*l2*w + l1*sign(w) on the weights as they are now, reg_penalty = P of the range (accumulate: += P), and with fold
@@ -1411,8 +1517,12 @@ class LisecNet:
         entry of ops that the optimizer's record names: lr_t by value -- (lr, decay) are kernel arguments --, or with
         device_lr from the descriptor (a schedule, or a rate a callback may change).  With regularizers the penalty pass
         over the same range runs directly in front of it, on the same stream (second: the step's other part has stored
-        its share of the penalty already); the call that ends the step folds the penalty into loss_out[0]."""
+        its share of the penalty already); the call that ends the step folds the penalty into loss_out[0].  With a
+        decoupled weight decay the decay pass follows it and the optimizer entry updates the decayed variables: the
+        gradient term and the penalty are taken on the weights BEFORE the decay, as the regularization loss of Keras sits
+        in the tape and tfa's decay follows it."""
         self._regularize(lo, hi, accumulate=second, fold=advance)
+        self._decay(opt, lo, hi)
         rec = opt.record
         entry, names, args = opt.launch
         bufs = [None if name is None else self.slot(name)[lo:hi] for name in names]
@@ -1461,7 +1571,9 @@ class LisecNet:
         avg = self.average if opt.average is not None else None      # (made before the first launch of the update)
         if self._early is not None:
             lo, early_opt = self._early
-            if early_opt != opt or (opt.device_lr and bytes(early_opt.lr_descriptor) != bytes(opt.lr_descriptor)):
+            if (early_opt != opt or (opt.device_lr and bytes(early_opt.lr_descriptor) != bytes(opt.lr_descriptor))
+                    or (opt.weight_decay is not None
+                        and bytes(early_opt.weight_decay.descriptor) != bytes(opt.weight_decay.descriptor))):
                 raise RuntimeError(f"apply_gradients(opt={opt}) after an early update with {early_opt}: the variables "
                                    f"would be updated by two different optimizers")
             hi = lo                              # the tail of the buffer was updated during the backward pass

@@ -731,6 +731,64 @@ def weight_average_eval(desc, state, k, c_out=None, m_out=None):
                                                      _lib.ptr(m_out), _lib.current_stream()))
 
 
+def decay_chunks(params, names=None):
+    """The chunk table of lisec_weight_decay as a host list [(offset, count)], ascending in offset: every variable that
+    `names` selects, cut like reg_chunks into ceil(n / REG_CHUNK) chunks over its padded length (the padding floats of
+    theta are 0 and stay 0).  names: None -- every trainable variable --, or an iterable of ParamStore names and / or
+    the kinds 'kernel', 'bias', 'gamma', 'beta' (each: every variable of that kind).  params: a ParamStore, or anything
+    with its `specs` and `offsets`.  Pure host arithmetic: no device, no library.  KeyError: a name the network does not
+    have; ValueError: a variable that is not trainable (the BatchNormalization moving statistics)."""
+    from .params import TRAINABLE_KINDS
+    if names is None:
+        chosen = [n for n, _, kind in params.specs if kind in TRAINABLE_KINDS]
+    else:
+        if isinstance(names, str):
+            names = (names,)
+        chosen = []
+        for name in names:
+            if name in TRAINABLE_KINDS:
+                chosen.extend(n for n, _, kind in params.specs if kind == name)
+            else:
+                chosen.append(name)
+    rows = []
+    for name in dict.fromkeys(chosen):
+        which, off, shape = params.offsets[name]
+        if which != "theta":
+            raise ValueError(f"{name} is not a trainable variable: it cannot be decayed")
+        n = (math.prod(shape) + 3) // 4 * 4
+        for start in range(0, n, _lib.REG_CHUNK):
+            rows.append((off + start, min(_lib.REG_CHUNK, n - start)))
+    rows.sort()
+    return rows
+
+
+def decay_table(chunks, device):
+    """decay_chunks' list as the device table of lisec_weight_decay (uint8 tensor of len(chunks) lisec_decay_chunk
+    records)."""
+    arr = (_lib.DecayChunk * max(len(chunks), 1))()
+    for rec, (off, count) in zip(arr, chunks):
+        rec.offset, rec.count = off, count
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+
+def weight_decay(theta, table, n_chunks, coeff, state, first=0):
+    """lisec_weight_decay over chunks [first, first + n_chunks) of `table` (decay_table; offsets relative to theta as
+    given): w <- w - wd_t*w, a float32 multiply and a float32 subtraction, wd_t = float32(schedule(state[0])) of the
+    device descriptor `coeff` (lr_schedule_set; its decay 0).  state is read, never advanced."""
+    if first < 0 or (n_chunks > 0 and (first + n_chunks) * ctypes.sizeof(_lib.DecayChunk) > table.numel()):
+        raise ValueError(f"weight_decay: chunks [{first}, {first + n_chunks}) outside a table of "
+                         f"{table.numel() // ctypes.sizeof(_lib.DecayChunk)}")
+    chunks = ctypes.c_void_p(table.data_ptr() + first * ctypes.sizeof(_lib.DecayChunk))
+    _lib.check(_lib.load().lisec_weight_decay(_lib.ptr(theta), chunks, int(n_chunks), _lib.ptr(coeff), _lib.ptr(state),
+                                              _lib.current_stream()))
+
+
+def weight_decay_eval(coeff, state, k, out):
+    """out[j] = wd_t at iteration state[0] + j, j < k (lisec_weight_decay_eval; state is not advanced)."""
+    _lib.check(_lib.load().lisec_weight_decay_eval(_lib.ptr(coeff), _lib.ptr(state), int(k), _lib.ptr(out),
+                                                   _lib.current_stream()))
+
+
 def conv_field_forward_workspace_bytes(g, row_capacity):
     return _lib.load().lisec_conv_field_forward_workspace_bytes(ctypes.byref(g), row_capacity)
 

@@ -137,13 +137,25 @@ SLOT_KINDS = tuple(dict.fromkeys(s.kind for o in OPTIMIZERS for s in o.slots))
 LEGACY = BY_KIND["sgd"]
 
 
+def base_class(class_name):
+    """The class of the table whose record an optimizer class uses: itself for a class of the table, <Base> for <Base>W
+    -- the class optimizers.extend_with_decoupled_weight_decay makes of <Base>: same kernels, same slots, no row of its
+    own --, None for anything else."""
+    if class_name in BY_CLASS:
+        return class_name
+    if isinstance(class_name, str) and class_name.endswith("W") and class_name[:-1] in BY_CLASS:
+        return class_name[:-1]
+    return None
+
+
 def record_of(optimizer):
-    """The record of an optimizer dict (Optimizer.as_dict); a class that is not in the table is written as SGD, as it
-    always was."""
-    return BY_CLASS.get(optimizer.get("class_name"), LEGACY)
+    """The record of an optimizer dict (Optimizer.as_dict), <Base>W resolved to <Base>'s; a class that is not in the
+    table is written as SGD, as it always was."""
+    return BY_CLASS.get(base_class(optimizer.get("class_name")), LEGACY)
 
 
 def slot_name(class_name, kind):
     """The LisecNet slot name of the Keras slot `kind` in a file of optimizer `class_name` (one not in the table: kind)."""
+    class_name = base_class(class_name)
     slots = BY_CLASS[class_name].slots if class_name in BY_CLASS else ()
     return next((s.name for s in slots if s.kind == kind), kind)
