@@ -1114,6 +1114,71 @@ int lisec_weight_decay(float* theta, const lisec_decay_chunk* chunks /* device *
 int lisec_weight_decay_eval(const lisec_lr_schedule* coeff /* device */, const long long* state /* device */, long long k,
                             float* wd_out, lisec_stream_t stream);
 
+/* LAMB (optimizers.LAMB; You et al. 2019; csrc/lamb.hip): layer-wise adaptive Adam, this project's own restatement of
+ * tfa.optimizers.LAMB (parity unpinned).  The only update entry that is not element-wise: the step of a
+ * variable is scaled by its trust ratio r = ||w|| / ||u||, a reduction over the whole variable.
+ * The host cuts every trainable variable into chunks by the rules of lisec_reg_chunk: offset and count in floats and
+ * multiples of 4, offset relative to the theta / grad / m / v pointers given (all four are indexed alike), count <=
+ * LISEC_REG_CHUNK, a chunk never crosses a variable, ascending.  chunk.var is the index of the chunk's variable in
+ * `vars`, chunk.flags says whether the variable is decayed (LISEC_LAMB_DECAYED) and whether its ratio is used
+ * (LISEC_LAMB_ADAPTED; the chunks of one variable carry the same flags); vars[j] gives variable j's first chunk and
+ * chunk count, both counted from the start of the TABLE.  Both tables are device memory and are NOT checked: every
+ * [offset, offset + count) must lie inside all four buffers, every var inside `vars` and `ratios`.
+ * An entry works on chunks [first_chunk, first_chunk + n_chunks) and variables [first_var, first_var + n_vars) of the
+ * tables; the chunk range must be exactly the chunks of the variable range (a variable is never split between two
+ * calls).  The partials of chunk c live at workspace[2c], the ratio of variable j at ratios[j], whatever the range: the
+ * two parts of a split update use slots of their own, and after the step `ratios` holds every variable's r.
+ * With it = state[0], t = it + 1, lr_t as for lisec_adam_step_dev / lisec_adam_step_sched:
+ * THE ARITHMETIC IS A CONTRACT.  Each line is one IEEE fp32 round-to-nearest-even operation of its own, never
+ * contracted into an fma, never reassociated, the divisions never replaced by reciprocal multiplies, sqrtf correctly
+ * rounded, denormals kept:
+ *     per launch   omb1 = 1 - beta1;  omb2 = 1 - beta2;  c1 = (float)(1.0 - beta1^t), c2 likewise from beta2:
+ *                  the power in double by binary exponentiation over the integer t, the difference in double, rounded
+ *                  once -- it cancels (1 - 0.999^8 is 0.008), and in fp32 its error would be 1e-5 of u and of r
+ *     pass 1       gg = g*g;  ma = beta1*m;  mb = omb1*g;  m <- ma + mb;  va = beta2*v;  vb = omb2*gg;  v <- va + vb
+ *     u            mh = m/c1;  vh = v/c2;  q = sqrtf(vh);  d = q + epsilon;  u = mh/d;
+ *                  a DECAYED chunk: p = weight_decay_rate*w;  u = u + p
+ *     pass 2       step = r*lr_t;  e = step*u;  w <- w - e
+ * Pass 1 writes m and v and keeps u in registers; pass 2 forms u again from the stored m, v and the unchanged w by the
+ * same operations, hence with the same bits.  Between them, per variable, in fp64:
+ *     S_w = sum w*w,  S_u = sum u*u     per thread, then wave, then workgroup: one pair of partials per chunk; the
+ *                                       chunk partials of a variable are added by one wave (lane l: chunks l, l + 64,
+ *                                       ... in that order, then a butterfly) -- an order fixed by the table alone
+ *     r = (float)(sqrt(S_w) / sqrt(S_u))   if the variable is ADAPTED and S_w > 0 and S_u > 0, else exactly 1.0f
+ * No atomics other than the iteration ticket: theta, m, v and ratios have the same bits from run to run.  grad is only
+ * read.  Floats outside every chunk keep their bits in theta, m and v.  advance as for the other entries: 0 leaves the
+ * count alone (a part of the variables ahead of the rest of the step), 1 ends the step; with n_chunks == 0 and advance
+ * == 1 the count is still advanced.  Three launches (pass 1, ratios, pass 2), fixed addresses, no host reads, no
+ * allocation: they record into a step plan.  LISEC_EINVAL, nothing enqueued: a NULL pointer, theta / grad / m / v not
+ * 16-byte aligned, workspace / state / chunks not 8-byte aligned, a negative first or count, n_chunks == 0 with
+ * n_vars != 0 or the reverse, n_vars > n_chunks, workspace_bytes below lisec_lamb_workspace_bytes(first_chunk +
+ * n_chunks, first_var + n_vars), beta1 or beta2 outside [0, 1), a negative epsilon or weight_decay_rate, advance not
+ * 0/1.  HBM traffic: 10 floats per element (6 in pass 1, 4 in pass 2) against Adam's 7. */
+#define LISEC_LAMB_DECAYED 1
+#define LISEC_LAMB_ADAPTED 2
+typedef struct lisec_lamb_chunk {
+    long long offset;
+    int count;
+    int var;        /* index into vars / ratios */
+    int flags;      /* LISEC_LAMB_DECAYED | LISEC_LAMB_ADAPTED */
+    int reserved;   /* 0 */
+} lisec_lamb_chunk;
+typedef struct lisec_lamb_var {
+    int first_chunk;
+    int n_chunks;
+} lisec_lamb_var;
+size_t lisec_lamb_workspace_bytes(int n_chunks, int n_vars);
+int lisec_lamb_step_dev(float* theta, const float* grad, float* m, float* v, const lisec_lamb_chunk* chunks /* device */,
+                        int first_chunk, int n_chunks, const lisec_lamb_var* vars /* device */, int first_var, int n_vars,
+                        float* ratios /* device [>= first_var + n_vars] */, void* workspace, size_t workspace_bytes,
+                        double lr, double decay, float weight_decay_rate, float beta1, float beta2, float epsilon,
+                        long long* state, int advance, lisec_stream_t stream);
+int lisec_lamb_step_sched(float* theta, const float* grad, float* m, float* v, const lisec_lamb_chunk* chunks /* device */,
+                          int first_chunk, int n_chunks, const lisec_lamb_var* vars /* device */, int first_var, int n_vars,
+                          float* ratios /* device [>= first_var + n_vars] */, void* workspace, size_t workspace_bytes,
+                          const lisec_lr_schedule* sched /* device */, float weight_decay_rate, float beta1, float beta2,
+                          float epsilon, long long* state, int advance, lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4b. Data-parallel gradient exchange.  The reference trains in ONE process
  *     (model.fit, model_training.py:299); here whole samples are sharded over one process per GPU and the

@@ -126,6 +126,18 @@ class DecayChunk(Structure):                   # lisec_decay_chunk
     _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("reserved", c_int)]
 
 
+LAMB_DECAYED, LAMB_ADAPTED = 1, 2              # LISEC_LAMB_*: the flags of a lisec_lamb_chunk
+LAMB_BLOCKS = 2048                             # kLambBlocks of csrc/lamb.hip: the widest grid of a pass
+
+
+class LambChunk(Structure):                    # lisec_lamb_chunk
+    _fields_ = [("offset", ctypes.c_longlong), ("count", c_int), ("var", c_int), ("flags", c_int), ("reserved", c_int)]
+
+
+class LambVar(Structure):                      # lisec_lamb_var
+    _fields_ = [("first_chunk", c_int), ("n_chunks", c_int)]
+
+
 LOSS_MAX_METRICS = 4                           # LISEC_LOSS_MAX_METRICS
 
 
@@ -436,6 +448,14 @@ def _declare(lib):
     lib.lisec_weight_decay.argtypes = [P, P, c_int, P, P, P]
     lib.lisec_weight_decay_eval.restype = c_int
     lib.lisec_weight_decay_eval.argtypes = [P, P, LL, P, P]
+    lib.lisec_lamb_workspace_bytes.restype = c_size_t
+    lib.lisec_lamb_workspace_bytes.argtypes = [c_int, c_int]
+    lib.lisec_lamb_step_dev.restype = c_int
+    lib.lisec_lamb_step_dev.argtypes = [P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, c_double, c_double,
+                                        c_float, c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_lamb_step_sched.restype = c_int
+    lib.lisec_lamb_step_sched.argtypes = [P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P, c_float,
+                                          c_float, c_float, c_float, P, c_int, P]
     lib.lisec_comm_unique_id.restype = c_int
     lib.lisec_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.lisec_comm_init.restype = c_int

@@ -259,7 +259,9 @@ def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrap
     cls = written_class(o)
     oc = {"class_name": cls, "config": {
         "name": cls, "learning_rate": _rate(o.get("lr", rec.lr)), "decay": float(o.get("decay", rec.decay)),
-        **rec.values(o)}}
+        **rec.values(o),
+        # a layer-wise optimizer's exclusion lists (LAMB; names and kinds of this project, not tfa's regular expressions)
+        **{k: (None if o.get(k) is None else list(o[k])) for k in rec.lists}}}
     if cls != rec.class_name:                     # <Base>W: the coefficient (a number or a serialized schedule) and,
         oc["config"]["weight_decay"] = _rate(o.get("weight_decay", 0.0))          # only when given, the decayed variables
         if o.get("decay_var_list") is not None:
@@ -476,6 +478,8 @@ def load_model(path, grid=None):
             if rec is not None:               # another optimizer class: no optimizer, the model comes back uncompiled
                 out["optimizer"] = rec.as_dict(c.get("learning_rate", c.get("lr", rec.lr)), c.get("decay", rec.decay),
                                                {h.name: c.get(h.name, h.default) for h in rec.hyper})
+                for k in rec.lists:
+                    out["optimizer"][k] = None if c.get(k) is None else list(c[k])
                 if base != oc["class_name"]:  # <Base>W: the record is <Base>'s, the dict carries the class and the decay
                     out["optimizer"].update(class_name=oc["class_name"], weight_decay=c.get("weight_decay", 0.0))
                     if c.get("decay_var_list") is not None:

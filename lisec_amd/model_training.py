@@ -297,7 +297,13 @@ class _Optimizer:
         """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
         callbacks, which may change it between epochs)."""
         return OptimizerSpec(self.record.kind, self.lr, self.decay, device_lr=device_lr, weight_decay=self.decay_spec(),
-                             **self.hyper)
+                             **self.hyper, **self.lists)
+
+    @property
+    def lists(self):
+        """{name: value} of the variable lists of the class's record (a layer-wise optimizer's exclusion lists; none
+        for every other class)."""
+        return {name: getattr(self, name) for name in self.record.lists}
 
     def get_config(self):
         return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper}
@@ -364,7 +370,7 @@ class _AveragingOptimizer(_Optimizer):
     def spec(self, device_lr=False):
         inner = self._optimizer
         return OptimizerSpec(inner.record.kind, inner.lr, inner.decay, device_lr=device_lr, average=self.average_spec(),
-                             weight_decay=inner.decay_spec(), **inner.hyper)
+                             weight_decay=inner.decay_spec(), **inner.hyper, **inner.lists)
 
     def decay_spec(self):
         return self._optimizer.decay_spec()
@@ -491,6 +497,39 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
             optimizers.SGD.__init__(self, lr=lr if lr is not None else learning_rate, momentum=momentum,
                                     nesterov=nesterov, name=name, **kwargs)
 
+    class LAMB(_Optimizer):
+        """tfa.optimizers.LAMB (You et al. 2019) as this project restates it (parity unpinned: TensorFlow
+        Addons is not installed): layer-wise adaptive Adam for large batches.  Per trainable variable, t = iterations + 1:
+            m <- beta_1*m + (1 - beta_1)*g;  v <- beta_2*v + (1 - beta_2)*g*g
+            u  = (m / (1 - beta_1^t)) / (sqrt(v / (1 - beta_2^t)) + epsilon), + weight_decay_rate*w on a decayed variable
+            r  = ||w|| / ||u|| when both norms are > 0, else 1;  1 for a variable excluded from layer adaptation
+            w <- w - (r*lr_t)*u
+        (csrc/lamb.hip: two passes and a per-variable reduction in between; include/lisec_hip.h has the arithmetic).
+        exclude_from_weight_decay / exclude_from_layer_adaptation: the variables that are not decayed / whose ratio is
+        not used -- ParamStore names and / or the kinds 'kernel', 'bias', 'gamma', 'beta', as AdamW's decay_var_list
+        takes them; tfa takes regular expressions on TF variable names, which do not exist here.  As in tfa,
+        exclude_from_layer_adaptation=None means the list of exclude_from_weight_decay.  lr=, decay= and the clipping
+        keywords behave as in Adam (clipping is refused).  The slots are m and v; LisecNet.trust_ratios() returns r of
+        the last update.  ValueError: beta_1 or beta_2 outside [0, 1), a negative epsilon or weight_decay_rate, a list
+        that is not made of strings."""
+
+        def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-6, weight_decay_rate=0.0,
+                     exclude_from_weight_decay=None, exclude_from_layer_adaptation=None, name="LAMB", lr=None,
+                     decay=0.0, **kwargs):
+            for key, value in (("exclude_from_weight_decay", exclude_from_weight_decay),
+                               ("exclude_from_layer_adaptation", exclude_from_layer_adaptation)):
+                if value is not None:
+                    value = [value] if isinstance(value, str) else list(value)
+                setattr(self, key, value)
+            self._set(name, lr if lr is not None else learning_rate, decay, kwargs, weight_decay_rate=weight_decay_rate,
+                      beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
+
+        def get_config(self):
+            """tfa's keys in tfa's order: weight_decay_rate sits between learning_rate and decay."""
+            return {"name": self.name, "learning_rate": _serialize_rate(self.lr),
+                    "weight_decay_rate": self.weight_decay_rate, "decay": self.decay, "beta_1": self.beta_1,
+                    "beta_2": self.beta_2, "epsilon": self.epsilon, **self.lists}
+
     _DECOUPLED = {SGD: SGDW, Adam: AdamW}       # base class -> its class with decoupled weight decay, made once
 
     @staticmethod
@@ -506,6 +545,9 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
         if name not in optimizer_table.BY_CLASS or getattr(optimizers, name, None) is not base_class:
             raise ValueError(f"extend_with_decoupled_weight_decay takes one of the optimizer classes "
                              f"{', '.join(optimizer_table.BY_CLASS)}, not {base_class!r}")
+        if optimizer_table.BY_CLASS[name].layerwise:
+            raise ValueError(f"extend_with_decoupled_weight_decay({name}): {name} carries its own weight decay "
+                             f"(weight_decay_rate)")
 
         def __init__(self, weight_decay, *args, decay_var_list=None, **kwargs):
             self._set_decay(weight_decay, decay_var_list)
@@ -599,7 +641,7 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
         given = dict(learning_rate=lr, decay=c.get("decay", rec.decay), name=c.get("name", cls),
-                     **{h.name: c.get(h.name, h.default) for h in rec.hyper})
+                     **{h.name: c.get(h.name, h.default) for h in rec.hyper}, **{k: c.get(k) for k in rec.lists})
         if base == cls:
             return getattr(optimizers, cls)(**given)
         wd = c.get("weight_decay", 0.0)
@@ -798,6 +840,10 @@ class Model:
             # a decay_var_list this network cannot serve: KeyError for an unknown name, ValueError for a variable
             # that is not trainable (ops.decay_chunks)
             self.net.decay_table(wd.variables)
+        if optimizer.record.layerwise:
+            # exclusion lists this network cannot serve are refused here in the same way (ops.lamb_chunks); the tables,
+            # the workspace and the ratio buffer get their fixed addresses before any step is recorded
+            self.net.lamb_table(*optimizer.spec().lists)
         step_loss, names = losses.compile_loss(loss, loss_weights, metrics, weighted_metrics)
         self.optimizer, self.loss = optimizer, step_loss
         self._metric_names = names
@@ -1266,6 +1312,7 @@ class Model:
         if self.optimizer is not None:
             o, scalar = self.optimizer, self.optimizer.record.scalar
             opt = o.record.as_dict(_serialize_rate(o.lr), o.decay, o.hyper)
+            opt.update(o.lists)                                    # (LAMB's exclusion lists; no key for any other class)
             inner = o._optimizer if isinstance(o, _AveragingOptimizer) else o
             if isinstance(inner, _DecoupledWeightDecay):
                 # (only then: the file of an optimizer without decoupled decay keeps its bytes)
@@ -1384,7 +1431,8 @@ def load_model(path, custom_objects=None):
         if isinstance(lr, dict):
             lr = lr_schedules.deserialize(lr)
         rec = optimizer_table.record_of(o)
-        given = dict(learning_rate=lr, decay=o["decay"], **{h.name: o[h.name] for h in rec.hyper})
+        given = dict(learning_rate=lr, decay=o["decay"], **{h.name: o[h.name] for h in rec.hyper},
+                     **{k: o.get(k) for k in rec.lists})
         if o.get("weight_decay") is None:
             opt = getattr(optimizers, rec.class_name)(**given)
         else:                                                        # <Base>W: decoupled weight decay

@@ -185,13 +185,18 @@ class OptimizerSpec:
     average: an AverageSpec, or None (no averaging: the step issues exactly the launches it always did, and `config`
     is the tuple it always was).
     weight_decay: a DecaySpec, or None; the constant number 0 is the same as None (no decay: no launch, and the base
-    optimizer's `config`)."""
+    optimizer's `config`).
+    kind "lamb" (layer-wise: csrc/lamb.hip) keeps "m" and "v", has weight_decay_rate -- its own decay, inside the
+    step -- and the two lists exclude_from_weight_decay / exclude_from_layer_adaptation (None, or ParamStore names and /
+    or kinds; the second None: the first), which enter `config` for this kind alone, behind the hyper-parameters; the
+    network that runs the step resolves them (ops.lamb_chunks).  A DecaySpec is refused."""
 
     KINDS = tuple(optimizer_table.BY_KIND)
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
-                 epsilon=1e-7, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1,
-                 average=None, weight_decay=None):
+                 epsilon=None, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1,
+                 average=None, weight_decay=None, weight_decay_rate=0.0, exclude_from_weight_decay=None,
+                 exclude_from_layer_adaptation=None):
         rec = self.record = optimizer_table.BY_KIND.get(kind)
         if rec is None:
             raise ValueError(f"unknown optimizer kind {kind!r}")
@@ -211,14 +216,27 @@ class OptimizerSpec:
         self.lr_descriptor = (lr_schedules.descriptor(self.lr, 0.0 if rec.schedule_decay else self.decay)
                               if self.device_lr else None)
         given = dict(momentum=momentum, nesterov=nesterov, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon, amsgrad=amsgrad,
-                     rho=rho, centered=centered, initial_accumulator_value=initial_accumulator_value)
+                     rho=rho, centered=centered, initial_accumulator_value=initial_accumulator_value,
+                     weight_decay_rate=weight_decay_rate)
         for h in rec.hyper:                     # a spec carries the hyper-parameters of its own kind, and no others
-            value = h.coerce(given[h.name])
+            # (epsilon None: the default of the kind's record -- 1e-7 for the Keras optimizers, 1e-6 for LAMB)
+            value = h.coerce(h.default if given[h.name] is None else given[h.name])
             if not h.valid(value):
                 raise ValueError(h.error)
             setattr(self, h.name, value)
         if rec.schedule_decay and self.decay < 0:
             raise ValueError("schedule_decay must be >= 0")
+        if rec.layerwise and weight_decay is not None:
+            raise ValueError(f"{rec.class_name} carries its own weight decay (weight_decay_rate): it takes no DecaySpec")
+        lists = dict(exclude_from_weight_decay=exclude_from_weight_decay,
+                     exclude_from_layer_adaptation=exclude_from_layer_adaptation)
+        for name in rec.lists:                  # (of a layer-wise kind alone: no other spec has the attributes)
+            value = lists[name]
+            if value is not None:
+                value = (value,) if isinstance(value, str) else tuple(value)
+                if not all(isinstance(x, str) for x in value):
+                    raise ValueError(f"{name} takes variable names and kinds, not {lists[name]!r}")
+            setattr(self, name, value)
         # (ops entry, slot names, argument names) of LisecNet._update, worked out once: it runs twice in every eager step
         self.launch = rec.launch(self.hyper, self.device_lr)
 
@@ -239,12 +257,18 @@ class OptimizerSpec:
             rate = ("device",)
         else:
             rate = self.lr
-        base = (self.kind, rate, self.decay, *self.hyper.values())
+        base = (self.kind, rate, self.decay, *self.hyper.values(), *self.lists)
         if self.average is not None:
             base += (("average",) + self.average.config,)
         if self.weight_decay is not None:
             base += (("weight_decay",) + self.weight_decay.config,)
         return base
+
+    @property
+    def lists(self):
+        """The variable lists of a layer-wise kind (exclude_from_weight_decay, exclude_from_layer_adaptation), each a
+        tuple or None; () for every other kind."""
+        return tuple(getattr(self, name) for name in self.record.lists)
 
     @property
     def slots(self):
@@ -828,6 +852,11 @@ class LisecNet:
         self._wd_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
         self._wd_host = None
         self._decay_tables = {}
+        # a layer-wise optimizer (LAMB; csrc/lamb.hip): the chunk / variable tables per pair of exclusion lists, kept
+        # for the net's life like the decay tables, and -- made with the first table, every table has the same rows --
+        # the per-chunk workspace and the trust ratios of the last update, one per trainable variable
+        self._lamb_tables = {}
+        self._lamb_ws = self._lamb_ratios = None
         self.loss_out = torch.zeros(3, dtype=f32, device=dev)
         # the metrics of a LossSpec loss (lisec_head_loss), class output's first; fixed address, like loss_out
         self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
@@ -1525,6 +1554,9 @@ class LisecNet:
         self._decay(opt, lo, hi)
         rec = opt.record
         entry, names, args = opt.launch
+        if rec.layerwise:
+            self._update_layerwise(opt, lo, hi, advance)
+            return
         bufs = [None if name is None else self.slot(name)[lo:hi] for name in names]
         if rec.scalar is not None:
             bufs.append(getattr(self, rec.scalar))
@@ -1535,6 +1567,55 @@ class LisecNet:
             rate = (opt.lr,) if rec.schedule_decay else (opt.lr, opt.decay)
         getattr(ops, entry)(self.params.theta[lo:hi], self.grad[lo:hi], *bufs, *rate, *(getattr(opt, a) for a in args),
                             self._iter_dev, advance=advance)
+
+    def lamb_table(self, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None):
+        """(ascending chunk offsets, ascending variable offsets, variable names, ops.LambTable) of a layer-wise
+        optimizer with these exclusion lists (ops.lamb_chunks), made once per pair; the workspace and the ratio buffer
+        are made with the first.  KeyError: a name the network does not have; ValueError: a variable that is not
+        trainable."""
+        key = (exclude_from_weight_decay, exclude_from_layer_adaptation)
+        entry = self._lamb_tables.get(key)
+        if entry is None:
+            chunks, variables = ops.lamb_chunks(self.params, *key)
+            table = ops.lamb_table(chunks, variables, self.device)
+            if self._lamb_ws is None:
+                self._lamb_ws = ops.lamb_workspace(table.n_chunks, table.n_vars, self.device)
+                self._lamb_ratios = torch.ones(max(table.n_vars, 1), dtype=torch.float32, device=self.device)
+            entry = self._lamb_tables[key] = ([c[0] for c in chunks], [v[2] for v in variables],
+                                              [v[3] for v in variables], table)
+            torch.cuda.synchronize(self.device)   # whole before any stream of the step (the second one included) uses them
+        return entry
+
+    def _update_layerwise(self, opt, lo, hi, advance):
+        """_update's launch for a layer-wise optimizer: the variables whose first float lies in theta[lo:hi] -- lo and hi
+        are variable boundaries, and as the tables hold whole variables a variable is never split between the two parts
+        of a step --, by the chunk and variable rows that bisect finds at lo / hi, as _decay cuts its table.  The entry
+        gets the WHOLE buffers; every chunk and variable has its own slot of the workspace and of the ratio buffer, so
+        the early part and the closing part of a step together leave what one launch over everything leaves."""
+        entry, names, args = opt.launch
+        chunk_offsets, var_offsets, _, table = self.lamb_table(*opt.lists)
+        first, last = bisect.bisect_left(chunk_offsets, lo), bisect.bisect_left(chunk_offsets, hi)
+        first_var, last_var = bisect.bisect_left(var_offsets, lo), bisect.bisect_left(var_offsets, hi)
+        if opt.device_lr:
+            self._sync_lr(opt)
+            rate = (self._lr_dev,)
+        else:
+            rate = (opt.lr, opt.decay)
+        getattr(ops, entry)(self.params.theta, self.grad, *(self.slot(name) for name in names), *rate,
+                            *(getattr(opt, a) for a in args), self._iter_dev, advance=advance, table=table,
+                            ratios=self._lamb_ratios, workspace=self._lamb_ws, first=first, n_chunks=last - first,
+                            first_var=first_var, n_vars=last_var - first_var)
+
+    def trust_ratios(self):
+        """{variable name: r} of the last update of a layer-wise optimizer (LAMB): the trust ratio ||w|| / ||u|| each
+        trainable variable's step was scaled by, 1.0 for a variable excluded from layer adaptation or with a zero norm.
+        One device-to-host copy behind everything enqueued so far; never made during a step.  RuntimeError before the
+        first such update."""
+        if not self._lamb_tables:
+            raise RuntimeError("trust_ratios(): no update by a layer-wise optimizer (optimizers.LAMB) has run")
+        torch.cuda.current_stream().wait_stream(self.side)
+        names = next(iter(self._lamb_tables.values()))[2]
+        return dict(zip(names, self._lamb_ratios.cpu().tolist()))
 
     def early_update(self, lo, hi, opt=None):
         """`opt` (an OptimizerSpec; None: the reference's SGD-Nesterov) of theta[lo:hi] AHEAD of the rest of the step

@@ -789,6 +789,122 @@ def weight_decay_eval(coeff, state, k, out):
                                                    _lib.current_stream()))
 
 
+def _select_variables(params, names):
+    """The set of ParamStore names that `names` selects: None or empty -- none --, else ParamStore names and / or the
+    kinds 'kernel', 'bias', 'gamma', 'beta' (each: every variable of that kind), as decay_chunks reads them."""
+    from .params import TRAINABLE_KINDS
+    if names is None:
+        return set()
+    if isinstance(names, str):
+        names = (names,)
+    chosen = set()
+    for name in names:
+        if name in TRAINABLE_KINDS:
+            chosen.update(n for n, _, kind in params.specs if kind == name)
+        else:
+            which = params.offsets[name][0]                 # KeyError: a name the network does not have
+            if which != "theta":
+                raise ValueError(f"{name} is not a trainable variable: it cannot be excluded from an update")
+            chosen.add(name)
+    return chosen
+
+
+LAMB_BLOCKS = _lib.LAMB_BLOCKS                 # the widest grid of a LAMB pass: past it the workgroups stride over the table
+
+
+def lamb_chunks(params, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None):
+    """The tables of lisec_lamb_step_* as host lists, both ascending in offset: (chunk rows [(offset, count, var,
+    flags)], variable rows [(first_chunk, n_chunks, offset, name)]).  EVERY trainable variable is in them, cut like
+    reg_chunks into ceil(n / REG_CHUNK) chunks over its padded length (the padding floats of theta are 0, have a zero
+    gradient and add nothing to either norm); var is the index of the chunk's row in the variable rows; flags has
+    LAMB_DECAYED unless exclude_from_weight_decay selects the variable and LAMB_ADAPTED unless
+    exclude_from_layer_adaptation does -- None there: the list of exclude_from_weight_decay, as in tfa.  Both lists take
+    what decay_chunks' `names` takes: ParamStore names and / or the kinds 'kernel', 'bias', 'gamma', 'beta'.  Pure host
+    arithmetic: no device, no library.  KeyError: a name the network does not have; ValueError: a variable that is not
+    trainable (the BatchNormalization moving statistics)."""
+    from .params import TRAINABLE_KINDS
+    if exclude_from_layer_adaptation is None:
+        exclude_from_layer_adaptation = exclude_from_weight_decay
+    undecayed = _select_variables(params, exclude_from_weight_decay)
+    unadapted = _select_variables(params, exclude_from_layer_adaptation)
+    placed = sorted((params.offsets[n][1], n, shape) for n, shape, kind in params.specs if kind in TRAINABLE_KINDS)
+    chunks, variables = [], []
+    for off, name, shape in placed:
+        n = (math.prod(shape) + 3) // 4 * 4
+        flags = (0 if name in undecayed else _lib.LAMB_DECAYED) | (0 if name in unadapted else _lib.LAMB_ADAPTED)
+        first = len(chunks)
+        for start in range(0, n, _lib.REG_CHUNK):
+            chunks.append((off + start, min(_lib.REG_CHUNK, n - start), len(variables), flags))
+        variables.append((first, len(chunks) - first, off, name))
+    return chunks, variables
+
+
+class LambTable:
+    """lamb_chunks' lists on the device: `chunks` (uint8 tensor of lisec_lamb_chunk records), `variables` (uint8 tensor
+    of lisec_lamb_var records) and their lengths n_chunks / n_vars."""
+
+    def __init__(self, chunks, variables, device):
+        self.n_chunks, self.n_vars = len(chunks), len(variables)
+        carr = (_lib.LambChunk * max(len(chunks), 1))()
+        for rec, (off, count, var, flags) in zip(carr, chunks):
+            rec.offset, rec.count, rec.var, rec.flags = off, count, var, flags
+        varr = (_lib.LambVar * max(len(variables), 1))()
+        for rec, (first, n, *_) in zip(varr, variables):
+            rec.first_chunk, rec.n_chunks = first, n
+        self.chunks = torch.frombuffer(bytearray(bytes(carr)), dtype=torch.uint8).to(device)
+        self.variables = torch.frombuffer(bytearray(bytes(varr)), dtype=torch.uint8).to(device)
+
+
+def lamb_table(chunks, variables, device):
+    """lamb_chunks' two lists as the device tables of lisec_lamb_step_* (a LambTable); a variable row may be just
+    (first_chunk, n_chunks)."""
+    return LambTable(chunks, variables, device)
+
+
+def lamb_workspace(n_chunks, n_vars, device):
+    """The workspace of lisec_lamb_step_* for a table of n_chunks chunks and n_vars variables (uint8 tensor)."""
+    return torch.empty(_lib.load().lisec_lamb_workspace_bytes(int(n_chunks), int(n_vars)), dtype=torch.uint8,
+                       device=device)
+
+
+def _lamb_range(table, ratios, first, n_chunks, first_var, n_vars):
+    n_chunks = table.n_chunks - first if n_chunks is None else int(n_chunks)
+    n_vars = table.n_vars - first_var if n_vars is None else int(n_vars)
+    if first < 0 or n_chunks < 0 or first + n_chunks > table.n_chunks:
+        raise ValueError(f"lamb: chunks [{first}, {first + n_chunks}) outside a table of {table.n_chunks}")
+    if first_var < 0 or n_vars < 0 or first_var + n_vars > min(table.n_vars, ratios.numel()):
+        raise ValueError(f"lamb: variables [{first_var}, {first_var + n_vars}) outside a table of {table.n_vars} "
+                         f"with {ratios.numel()} ratios")
+    return int(first), n_chunks, int(first_var), n_vars
+
+
+def lamb_step_dev(theta, grad, m, v, lr, decay, weight_decay_rate, beta_1, beta_2, epsilon, state, advance=True, *,
+                  table, ratios, workspace, first=0, n_chunks=None, first_var=0, n_vars=None):
+    """LAMB on the device iteration count (lisec_lamb_step_dev) over chunks [first, first + n_chunks) and variables
+    [first_var, first_var + n_vars) of `table` (lamb_table; None: to the end; the chunks must be those of the
+    variables).  theta, grad, m, v are the WHOLE buffers the table's offsets count from; ratios (float32 device tensor,
+    one per variable of the table) receives r of the variables of the range; workspace: lamb_workspace."""
+    first, n_chunks, first_var, n_vars = _lamb_range(table, ratios, first, n_chunks, first_var, n_vars)
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_lamb_step_dev(P(theta), P(grad), P(m), P(v), P(table.chunks), first, n_chunks,
+                                               P(table.variables), first_var, n_vars, P(ratios), P(workspace),
+                                               workspace.numel(), float(lr), float(decay), float(weight_decay_rate),
+                                               float(beta_1), float(beta_2), float(epsilon), P(state),
+                                               1 if advance else 0, _lib.current_stream()))
+
+
+def lamb_step_sched(theta, grad, m, v, dev_desc, weight_decay_rate, beta_1, beta_2, epsilon, state, advance=True, *,
+                    table, ratios, workspace, first=0, n_chunks=None, first_var=0, n_vars=None):
+    """lamb_step_dev with lr_t from the device descriptor dev_desc (lisec_lamb_step_sched)."""
+    first, n_chunks, first_var, n_vars = _lamb_range(table, ratios, first, n_chunks, first_var, n_vars)
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_lamb_step_sched(P(theta), P(grad), P(m), P(v), P(table.chunks), first, n_chunks,
+                                                 P(table.variables), first_var, n_vars, P(ratios), P(workspace),
+                                                 workspace.numel(), P(dev_desc), float(weight_decay_rate),
+                                                 float(beta_1), float(beta_2), float(epsilon), P(state),
+                                                 1 if advance else 0, _lib.current_stream()))
+
+
 def conv_field_forward_workspace_bytes(g, row_capacity):
     return _lib.load().lisec_conv_field_forward_workspace_bytes(ctypes.byref(g), row_capacity)
 

@@ -45,8 +45,8 @@ def _slot(kind, when=None, name=None):
 
 
 class Optimizer(collections.namedtuple("Optimizer", "kind class_name lr decay hyper slots step args schedule_decay "
-                                                    "takes_schedule slot_start scalar",
-                                        defaults=(False, True, None, None))):
+                                                    "takes_schedule slot_start scalar layerwise",
+                                        defaults=(False, True, None, None, False))):
     """kind: OptimizerSpec's; class_name: Keras'.
     lr, decay: Keras' defaults.  schedule_decay: `decay` is the optimizer's momentum-schedule decay (Nadam's
         schedule_decay), not a decay of the rate: the learning-rate descriptor is built with decay 0 and the by-value
@@ -61,8 +61,18 @@ class Optimizer(collections.namedtuple("Optimizer", "kind class_name lr decay hy
     step: the names of the (by-value, descriptor) entries of lisec_amd.ops:
             by value    entry(theta, grad, *slots, [scalar], lr, [decay unless schedule_decay], *args, state, advance=)
             descriptor  entry(theta, grad, *slots, [scalar], device descriptor, *args, state, advance=)
-    args: the OptimizerSpec attributes both entries take after the rate."""
+    args: the OptimizerSpec attributes both entries take after the rate.
+    layerwise: the update is not element-wise -- a step of a variable depends on a reduction over the whole variable
+        (LAMB's trust ratio) --, so a range of theta can only be cut at variable boundaries: both entries take the WHOLE
+        buffers and, as keywords, the chunk / variable tables with the rows of the range, a workspace and the ratio
+        buffer (LisecNet._update; ops.lamb_step_dev).  Such an optimizer also has the two exclusion lists `lists`."""
     __slots__ = ()
+
+    @property
+    def lists(self):
+        """The names of the variable lists (tuples of ParamStore names and / or kinds, or None) the optimizer's config
+        carries behind its hyper-parameters: LAYERWISE_LISTS for a layer-wise optimizer, none otherwise."""
+        return LAYERWISE_LISTS if self.layerwise else ()
 
     def values(self, given):
         """{name: value} of every hyper-parameter, from a mapping that may lack some (Keras' default), coerced."""
@@ -86,6 +96,8 @@ class Optimizer(collections.namedtuple("Optimizer", "kind class_name lr decay hy
             return "sgd_nesterov_step_dev", names, ("momentum",)
         return self.step[1 if device_lr else 0], names, self.args
 
+
+LAYERWISE_LISTS = ("exclude_from_weight_decay", "exclude_from_layer_adaptation")
 
 _BETAS = "beta_1 and beta_2 must lie in [0, 1)"
 _ADAM = _BETAS + ", epsilon must be >= 0"
@@ -124,6 +136,13 @@ OPTIMIZERS = (
     Optimizer("nadam", "Nadam", lr=0.001, decay=0.004, schedule_decay=True, takes_schedule=False,
               hyper=_ADAMAX, slots=(_slot("m"), _slot("v")), scalar="momentum_cache",
               step=("nadam_step_dev", "nadam_step_sched"), args=("beta_1", "beta_2", "epsilon", "decay")),
+    # tfa.optimizers.LAMB as this project restates it: Adam's step, per variable of length ||w|| / ||u||
+    # (csrc/lamb.hip); weight_decay_rate is LAMB's own decay, inside the step -- not the decoupled pass of <Base>W
+    Optimizer("lamb", "LAMB", lr=0.001, decay=0.0, layerwise=True,
+              hyper=(_nonneg("weight_decay_rate", 0.0), _unit("beta_1", 0.9, _BETAS), _unit("beta_2", 0.999, _BETAS),
+                     _nonneg("epsilon", 1e-6)),
+              slots=(_slot("m"), _slot("v")),
+              step=("lamb_step_dev", "lamb_step_sched"), args=("weight_decay_rate", "beta_1", "beta_2", "epsilon")),
 )
 
 BY_KIND = {o.kind: o for o in OPTIMIZERS}
