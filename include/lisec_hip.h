@@ -1179,6 +1179,56 @@ int lisec_lamb_step_sched(float* theta, const float* grad, float* m, float* v, c
                           const lisec_lr_schedule* sched /* device */, float weight_decay_rate, float beta1, float beta2,
                           float epsilon, long long* state, int advance, lisec_stream_t stream);
 
+/* BatchNormalization recalibration (LisecNet.recalibrate_batchnorm; csrc/bn_recalibrate.hip): the moving statistics of
+ * every BatchNormalization layer are replaced by statistics of the CURRENT variables over K sweeps, as
+ * torch.optim.swa_utils.update_bn does with momentum=None.  This project's own restatement (parity
+ * unpinned); no finaliser changes.  Every finaliser updates a moving statistic as m <- (float)((double)m*a + batch*(1 - a)),
+ * so a training-mode forward over a ZEROED buffer of moving statistics leaves state[i] = fl32(batch_i * coef_i), coef_i =
+ * 1 - a of the finaliser that wrote it (lisec_bn_recalibrate_coef), the batch statistic to 2^-24 relative, the Bessel
+ * correction of the conv-sink layers applied as training applies it.
+ * `state` is the flat fp32 buffer of the moving statistics (device).  `table` is a HOST array of n_entries records, one
+ * per BatchNormalization layer, validated and copied into the launch: the layer's moving mean is state[mean_off, mean_off
+ * + C), its moving variance state[var_off, var_off + C), offsets in floats.  The ranges of different records must not
+ * overlap (not checked) and must lie inside state (not checked).  With j = (sum of C over the records in front) + c the
+ * running channel index and N = the sum of C over all records,
+ *     acc: double[3 * N], device, three planes:  S1 = acc[j]   S2 = acc[N + j]   Sq = acc[2N + j]
+ * lisec_bn_recalibrate_take -- one launch per sweep, behind its training-mode forward.  For every channel, in fp64, each
+ * line an IEEE operation of its own (the division correctly rounded, m*m never contracted into the addition):
+ *     m = (double)state[mean_off + c] / coef;   v = (double)state[var_off + c] / coef
+ *     S1 <- S1 + m;   S2 <- S2 + v;   Sq <- Sq + m*m
+ *     state[mean_off + c] <- +0.0f;   state[var_off + c] <- +0.0f         (ready for the next sweep)
+ * lisec_bn_recalibrate_finish -- once, behind the last take (acc is only read):
+ *     k = (double)sweeps;   mean = S1/k
+ *     LISEC_BN_STATS_MEAN    var = S2/k                                   (update_bn's rule: the mean of the batch variances)
+ *     LISEC_BN_STATS_POOLED  var = (S2/k + Sq/k) - mean*mean;  var < 0: var = 0     (plus the variance of the sweeps' means:
+ *                            "precise BN"; every sweep weighs the same, whatever its row count)
+ *     state[mean_off + c] <- (float)mean;   state[var_off + c] <- (float)var          each rounded once
+ * Denormals are kept (fp32 inputs and fp64 arithmetic).  No atomics, every channel owned by one thread, grid-stride
+ * loops: the same bits from run to run.  The floats of state outside every record -- the alignment pads -- are never read
+ * or written.  Fixed addresses, no host reads of device memory, no allocation.
+ * LISEC_EINVAL, nothing enqueued: NULL state, table or acc; n_entries < 1 or > LISEC_BN_RECAL_MAX_ENTRIES; a record with C
+ * < 1, coef outside the open interval (0, 1) (or NaN), a negative offset or one that is not a multiple of 4 floats;
+ * state not 4-byte or acc not 8-byte aligned; finish: sweeps < 1, an unknown `statistics`.
+ * lisec_bn_recalibrate_coef: coef of a finaliser family (host; 0.0 for an unknown family):
+ *     LISEC_BN_FINALIZER_CONV  1.0 - 0.99            lisec_bn_finalize (bn.hip) and the in-kernel finaliser of a lisec_bn_sink
+ *     LISEC_BN_FINALIZER_VFE   1.0 - (double)0.99f   the VFE finaliser (vfe.hip); 9.5e-7 relative away from the other */
+#define LISEC_BN_RECAL_MAX_ENTRIES 64
+enum { LISEC_BN_STATS_MEAN = 0, LISEC_BN_STATS_POOLED = 1 };
+enum { LISEC_BN_FINALIZER_CONV = 0, LISEC_BN_FINALIZER_VFE = 1 };
+typedef struct lisec_bn_recal_entry {
+    long long mean_off;  /* floats into state; a multiple of 4 */
+    long long var_off;   /* likewise */
+    int C;               /* channels */
+    int reserved;        /* 0 */
+    double coef;         /* 1 - momentum of the layer's finaliser: lisec_bn_recalibrate_coef */
+} lisec_bn_recal_entry;
+double lisec_bn_recalibrate_coef(int family);
+int lisec_bn_recalibrate_take(float* state, const lisec_bn_recal_entry* table /* host, copied */, int n_entries,
+                              double* acc /* device [3 * sum C] */, lisec_stream_t stream);
+int lisec_bn_recalibrate_finish(float* state, const lisec_bn_recal_entry* table /* host, copied */, int n_entries,
+                                const double* acc /* device [3 * sum C] */, long long sweeps, int statistics,
+                                lisec_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * 4b. Data-parallel gradient exchange.  The reference trains in ONE process
  *     (model.fit, model_training.py:299); here whole samples are sharded over one process per GPU and the

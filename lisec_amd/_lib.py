@@ -138,6 +138,16 @@ class LambVar(Structure):                      # lisec_lamb_var
     _fields_ = [("first_chunk", c_int), ("n_chunks", c_int)]
 
 
+BN_STATS_MEAN, BN_STATS_POOLED = 0, 1          # LISEC_BN_STATS_*: the rules of lisec_bn_recalibrate_finish
+BN_FINALIZER_CONV, BN_FINALIZER_VFE = 0, 1     # LISEC_BN_FINALIZER_*: the families of lisec_bn_recalibrate_coef
+BN_RECAL_MAX_ENTRIES = 64                      # LISEC_BN_RECAL_MAX_ENTRIES
+
+
+class BnRecalEntry(Structure):                 # lisec_bn_recal_entry
+    _fields_ = [("mean_off", ctypes.c_longlong), ("var_off", ctypes.c_longlong), ("C", c_int), ("reserved", c_int),
+                ("coef", c_double)]
+
+
 LOSS_MAX_METRICS = 4                           # LISEC_LOSS_MAX_METRICS
 
 
@@ -456,6 +466,12 @@ def _declare(lib):
     lib.lisec_lamb_step_sched.restype = c_int
     lib.lisec_lamb_step_sched.argtypes = [P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P, c_float,
                                           c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_bn_recalibrate_coef.restype = c_double
+    lib.lisec_bn_recalibrate_coef.argtypes = [c_int]
+    lib.lisec_bn_recalibrate_take.restype = c_int
+    lib.lisec_bn_recalibrate_take.argtypes = [P, POINTER(BnRecalEntry), c_int, P, P]
+    lib.lisec_bn_recalibrate_finish.restype = c_int
+    lib.lisec_bn_recalibrate_finish.argtypes = [P, POINTER(BnRecalEntry), c_int, P, LL, c_int, P]
     lib.lisec_comm_unique_id.restype = c_int
     lib.lisec_comm_unique_id.argtypes = [ctypes.c_char_p]
     lib.lisec_comm_init.restype = c_int

@@ -1,7 +1,8 @@
 """tf.keras 2.4 callbacks for Model.fit(callbacks=...) and Model.evaluate(callbacks=...), exposed as
 lisec_amd.model_training.callbacks: the Callback base class (set_model, set_params, on_train_begin / on_train_end,
 on_epoch_begin / on_epoch_end, on_test_begin / on_test_end), LearningRateScheduler, EarlyStopping, ModelCheckpoint and
-ReduceLROnPlateau; and DetectionEvaluation (ours), which logs the detection metric for them to monitor.  A learning rate set between epochs reaches the update kernels through the device descriptor of
+ReduceLROnPlateau; DetectionEvaluation (ours), which logs the detection metric for them to monitor; and PreciseBatchNorm
+(ours), which re-estimates the BatchNormalization moving statistics between epochs.  A learning rate set between epochs reaches the update kernels through the device descriptor of
 LisecNet, written on the stream of the step: the recorded step plan is not recorded again.  There are no per-batch hooks:
 the fit loop reads nothing back from the device inside an epoch."""
 import warnings
@@ -64,6 +65,14 @@ def _lr_number(optimizer, name):
         raise ValueError(f"{name} sets optimizer.lr, which is a {type(optimizer.lr).__name__} schedule here: give the "
                          f"optimizer a number, or keep the schedule without this callback")
     return float(optimizer.lr)
+
+
+def _statistics(statistics):
+    """'mean' or 'pooled', the rules of a BatchNormalization recalibration (ops.bn_statistics, restated: this module
+    imports nothing that needs the device library); anything else is a ValueError."""
+    if statistics not in ("mean", "pooled"):
+        raise ValueError(f"statistics must be 'mean' or 'pooled', not {statistics!r}")
+    return statistics
 
 
 class EarlyStopping(Callback):
@@ -186,13 +195,18 @@ class AverageModelCheckpoint(ModelCheckpoint):
     update_weights=False: the file is written inside Model.average_weights() -- its model weights are the averages, its
     `average` slot the live weights of that moment -- and training goes on with the live weights, bit for bit as without
     the callback.  update_weights=True: optimizer.assign_average_vars(model) first -- training goes on FROM the averages --
-    then the file is written, model weights and average both the averages."""
+    then the file is written, model weights and average both the averages.
+    update_bn=x (ours; what Model.recalibrate_batch_norm takes, `statistics` its rule): the BatchNormalization moving
+    statistics in the file are recalibrated for the averages over x (Model.average_weights(update_bn=x)) and the live
+    model's are left as they were, bit for bit.  With update_weights=True -- where the averages BECOME the live model --
+    the live statistics are recalibrated for them and kept.  An unknown `statistics` is a ValueError here."""
 
     def __init__(self, update_weights, filepath, monitor="val_loss", verbose=0, save_best_only=False,
-                 save_weights_only=False, mode="auto", save_freq="epoch", **kwargs):
+                 save_weights_only=False, mode="auto", save_freq="epoch", update_bn=None, statistics="mean", **kwargs):
         super().__init__(filepath, monitor=monitor, verbose=verbose, save_best_only=save_best_only,
                          save_weights_only=save_weights_only, mode=mode, save_freq=save_freq, **kwargs)
         self.update_weights = bool(update_weights)
+        self.update_bn, self.statistics = update_bn, _statistics(statistics)
 
     def on_train_begin(self, logs=None):
         if not hasattr(self.model.optimizer, "assign_average_vars"):
@@ -202,7 +216,12 @@ class AverageModelCheckpoint(ModelCheckpoint):
     def _save(self, filepath):
         if self.update_weights:
             self.model.optimizer.assign_average_vars(self.model)
+            if self.update_bn is not None:
+                self.model.recalibrate_batch_norm(self.update_bn, statistics=self.statistics)
             self.model.save(filepath)
+        elif self.update_bn is not None:
+            with self.model.average_weights(update_bn=self.update_bn, statistics=self.statistics):
+                self.model.save(filepath)
         else:
             with self.model.average_weights():
                 self.model.save(filepath)
@@ -331,7 +350,10 @@ class DetectionEvaluation(Callback):
 
     average_weights=True (a model compiled with optimizers.MovingAverage / SWA; otherwise ValueError at the first
     evaluation): the averages are evaluated, so val_mAP is their score and EarlyStopping / ModelCheckpoint select on it;
-    the variables and their average are swapped back afterwards, bit for bit.
+    the variables and their average are swapped back afterwards, bit for bit.  With update_bn=x (what
+    Model.recalibrate_batch_norm takes; only with average_weights, otherwise ValueError here) the averages are scored
+    with moving statistics recalibrated for them over x by the rule `statistics` (Model.average_weights(update_bn=x)),
+    and the live model's statistics are put back, bit for bit.
     Changes no variable, BatchNormalization statistic, optimizer slot or iteration count, and records nothing into a step
     plan: eager inference forwards between epochs, as fit's own validation runs them.  Data parallel: every rank evaluates
     every sweep with the rank-mean moving statistics (what save() writes), so the logs are identical on all ranks."""
@@ -339,8 +361,12 @@ class DetectionEvaluation(Callback):
     KEYS = ("mAP", "mAOS", "ATE", "ASE", "AOE", "best_f1")
 
     def __init__(self, sweeps, boxes, detector=None, iou_thresholds=None, mode="3d", min_points=0, every=1, prefix="val_",
-                 average_weights=False):
+                 average_weights=False, update_bn=None, statistics="mean"):
         super().__init__()
+        if update_bn is not None and not average_weights:
+            raise ValueError("DetectionEvaluation(update_bn=...) recalibrates the statistics for the averaged weights: "
+                             "it needs average_weights=True (callbacks.PreciseBatchNorm recalibrates the live model)")
+        self.update_bn, self.statistics = update_bn, _statistics(statistics)
         from .Predict import _check_detector
         sweeps, boxes = list(sweeps), [np.asarray(b, dtype=np.float64).reshape(-1, 7) for b in boxes]
         if len(sweeps) != len(boxes):
@@ -368,7 +394,11 @@ class DetectionEvaluation(Callback):
 
     def evaluate(self):
         """The evaluation of the model's current weights -- with average_weights, of their averages (inside
-        Model.average_weights(); the BatchNormalization moving statistics as they stand) --: a boxes.DetectionEval."""
+        Model.average_weights(); the BatchNormalization moving statistics as they stand, or with update_bn recalibrated
+        for the averages) --: a boxes.DetectionEval."""
+        if self.average_weights and self.update_bn is not None:
+            with self.model.average_weights(update_bn=self.update_bn, statistics=self.statistics):
+                return self._evaluate()
         if self.average_weights:
             with self.model.average_weights():
                 return self._evaluate()
@@ -409,3 +439,45 @@ class DetectionEvaluation(Callback):
         values = (r.mAP, r.mAOS, r.ate[lowest], r.ase[lowest], r.aoe[lowest], r.best_f1[lowest])
         for key, v in zip(self.KEYS, values):
             logs[self.prefix + key] = float(v)
+
+
+class PreciseBatchNorm(Callback):
+    """Re-estimates the BatchNormalization moving statistics of the LIVE model over the sweeps of x ("precise BN"; ours:
+    Keras has no counterpart) at the end of every `period`-th epoch (1-based) and when training ends, by
+    Model.recalibrate_batch_norm(x, steps=steps, statistics=statistics): instead of a 0.99 moving average fed by
+    single-sweep batches that trails the weights, the statistics of the weights as they are over N sweeps.  x: what
+    recalibrate_batch_norm takes; steps: at most that many sweeps; statistics: 'pooled' (the default here: plus the
+    variance of the sweeps' means) or 'mean'.  Training goes on from the recalibrated statistics, which the next steps'
+    finalisers move on from as from any others; no variable, slot or iteration count changes.
+    Place it in the callbacks list BEFORE ModelCheckpoint, EarlyStopping(restore_best_weights=True) and
+    DetectionEvaluation: fit calls the callbacks in list order, and a checkpoint written ahead of it would hold the
+    statistics from before the recalibration.  Fit's own validation runs before any callback and sees the statistics
+    of the previous recalibration.  ValueError here: a period or steps below 1, an unknown `statistics`."""
+
+    def __init__(self, x, period=1, steps=None, statistics="pooled"):
+        super().__init__()
+        for name, v in (("period", period), ("steps", steps)):
+            if v is None and name == "steps":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+                raise ValueError(f"{name} must be an integer >= 1, not {v!r}")
+        self.x, self.period, self.steps = x, int(period), None if steps is None else int(steps)
+        self.statistics = _statistics(statistics)
+        self.calls = 0                       # recalibrations so far
+        self._fresh = False                  # the statistics are those of the last recalibration (no step since)
+
+    def _recalibrate(self):
+        self.model.recalibrate_batch_norm(self.x, steps=self.steps, statistics=self.statistics)
+        self.calls += 1
+
+    def on_epoch_begin(self, epoch, logs=None):
+        self._fresh = False
+
+    def on_epoch_end(self, epoch, logs=None):
+        if (epoch + 1) % self.period == 0:
+            self._recalibrate()
+            self._fresh = True
+
+    def on_train_end(self, logs=None):
+        if not self._fresh:                  # (the last epoch's recalibration stands: the same sweeps, the same weights)
+            self._recalibrate()

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import Constants, _lib
-from . import callbacks, losses, lr_schedules, metrics, mixed_precision, optimizer_table, regularizers
+from . import callbacks, losses, lr_schedules, metrics, mixed_precision, ops, optimizer_table, regularizers
 from .network import (AverageSpec, DecaySpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len,
                       loss_acc_logs, loss_acc_split)
 from .params import ParamStore, fold_depth, param_specs
@@ -864,19 +864,58 @@ class Model:
         self.net.restart_average()               # a fresh averaging wrapper starts from the variables as they then are
 
     @contextlib.contextmanager
-    def average_weights(self):
+    def average_weights(self, update_bn=None, statistics="mean"):
         """with model.average_weights(): ... -- inside the block the variables ARE their averages (theta <-> average by
         content, LisecNet.swap_average): predict, evaluate and save see the averaged model, with the BatchNormalization
         moving statistics as they stand.  On leaving, also by an exception, they are swapped back: theta, the average
         and every later step are bit for bit those of a run that never entered.  Do not train inside the block.
-        ValueError on a model whose optimizer is not optimizers.MovingAverage / SWA."""
+        update_bn=x (what recalibrate_batch_norm takes; `statistics` its rule): the moving statistics are recalibrated
+        for the averages over x before the block runs (torch.optim.swa_utils.update_bn) and put back, bit for bit, on
+        leaving -- also when the recalibration itself or the block raises.  None: the method does what it always did.
+        ValueError on a model whose optimizer is not optimizers.MovingAverage / SWA, or for an unknown `statistics`."""
         if not isinstance(self.optimizer, _AveragingOptimizer):
             raise ValueError("average_weights() needs a model compiled with optimizers.MovingAverage or optimizers.SWA")
-        self.net.swap_average()
-        try:
-            yield self
-        finally:
+        if update_bn is None:
             self.net.swap_average()
+            try:
+                yield self
+            finally:
+                self.net.swap_average()
+            return
+        ops.bn_statistics(statistics)
+        net = self.net
+        net.swap_average()
+        try:
+            own = net.params.state.clone()
+            try:
+                self.recalibrate_batch_norm(update_bn, statistics=statistics)
+                yield self
+            finally:
+                net.params.state.copy_(own)
+                net.state_version += 1
+        finally:
+            net.swap_average()
+
+    def recalibrate_batch_norm(self, x, steps=None, statistics="mean"):
+        """Replaces the BatchNormalization moving statistics by statistics of the current variables over the sweeps of
+        x (LisecNet.recalibrate_batchnorm): 'mean' -- torch.optim.swa_utils.update_bn with momentum=None --, or 'pooled'
+        ("precise BN": plus the variance of the sweeps' means).  x: anything predict takes, or a Sequence as fit(x=...)
+        takes one (its labels are ignored; an augmenting Sequence is read at its current epoch); steps: at most that
+        many sweeps, from the front.  Data parallel: the sweeps are shared out over the ranks and every rank ends with
+        the same statistics.  Changes no variable, optimizer slot, iteration count or weight average; a recorded
+        training step stays valid for sweeps no larger than the training sweeps.  ValueError: no sweep, an unknown
+        `statistics`."""
+        ops.bn_statistics(statistics)
+        if _is_sequence(x):
+            n = len(x) if steps is None else min(len(x), int(steps))
+            rank, world = (0, 1) if self.dp is None else (self.dp.rank, self.dp.world)
+            # only this rank's share is voxelised; the others' places are never read (samples[rank::world])
+            samples = [self._sequence_item(x, i, False)[0] if i % world == rank else None for i in range(n)]
+        else:
+            samples = self._as_samples(x)
+            if steps is not None:
+                samples = samples[:int(steps)]
+        self.net.recalibrate_batchnorm(samples, statistics=statistics, dp=self.dp)
 
     @property
     def metrics_names(self):

@@ -857,7 +857,10 @@ class LisecNet:
         # the per-chunk workspace and the trust ratios of the last update, one per trainable variable
         self._lamb_tables = {}
         self._lamb_ws = self._lamb_ratios = None
-        self.loss_out = torch.zeros(3, dtype=f32, device=dev)
+        # BatchNormalization recalibration (recalibrate_batchnorm; csrc/bn_recalibrate.hip): the table of the layers'
+        # moving statistics and the fp64 accumulator, made when first used (bn_recal_table)
+        self._bn_recal = None
+        self.loss_out =torch.zeros(3, dtype=f32, device=dev)
         # the metrics of a LossSpec loss (lisec_head_loss), class output's first; fixed address, like loss_out
         self.metric_out = torch.zeros(2 * _lib.LOSS_MAX_METRICS, dtype=f32, device=dev)
         # [N_pos, N_neg] of a DetectionLossSpec loss (lisec_detection_loss); fixed address, like loss_out
@@ -1734,6 +1737,59 @@ class LisecNet:
     def assign_average(self):
         """theta <- average (the average is kept); otherwise as swap_average()."""
         self._exchange_average(False)
+
+    def bn_recal_table(self):
+        """(ops.BnRecalTable, accumulator) of recalibrate_batchnorm: one record per BatchNormalization layer -- the
+        offsets of its moving statistics in params.state (ParamStore.offsets), its channels, and the coefficient of
+        the finaliser that updates them (the VFE kernel for vfe1 / vfe2 / fcn, a conv sink for the rest) -- and the
+        float64 accumulator of three planes.  Made once."""
+        if self._bn_recal is None:
+            table = ops.bn_recal_table(ops.bn_recal_rows(self.params))
+            self._bn_recal = (table, ops.bn_recal_acc(table, self.device))
+        return self._bn_recal
+
+    def recalibrate_batchnorm(self, samples, statistics="mean", dp=None):
+        """Replaces every BatchNormalization layer's moving_mean / moving_variance by statistics of the CURRENT variables
+        over the given sweeps (VoxelSamples), as torch.optim.swa_utils.update_bn does with momentum=None: the buffer of
+        the moving statistics is zeroed, each sweep runs the ordinary forward(training=True) -- whose finalisers then
+        leave batch * (1 - momentum) there -- and one launch per sweep adds it to fp64 sums (csrc/bn_recalibrate.hip).
+        statistics 'mean': mean of the sweeps' means, mean of the sweeps' variances (update_bn's rule; the conv layers'
+        variances Bessel-corrected as training corrects them); 'pooled': the variance of the sweeps' means is added
+        ("precise BN").  Every sweep weighs the same.  dp (a DataParallel): rank r takes samples[r::world], the sums are
+        all-reduced, and every rank ends with the same statistics.
+        ValueError before any launch: no sweep, an unknown `statistics`.  RuntimeError while an early update is pending;
+        NotImplementedError for a bfloat16-compute network.  Any exception inside (a sweep of another grid, ...) puts
+        the moving statistics back as they were.  Eager, on the current stream.  Nothing of training moves: theta, the
+        optimizer slots, the iteration counts, params_version and the weight average keep their bits; only bnstate and
+        the activations are overwritten, which every forward rewrites before it reads them.  Sweeps no larger than the
+        training sweeps grow no workspace, so a recorded training step stays valid (_lib.alloc_generation())."""
+        samples = list(samples)
+        ops.bn_statistics(statistics)
+        if not samples:
+            raise ValueError("recalibrate_batchnorm needs at least one sweep")
+        if self._early is not None:
+            raise RuntimeError("the BatchNormalization statistics cannot be recalibrated while an early update is "
+                               "pending: apply_gradients() ends the step first")
+        self._refuse_bf16_training()
+        table, acc = self.bn_recal_table()
+        state = self.params.state
+        own = samples if dp is None else samples[dp.rank::dp.world]
+        keep = state.clone()
+        done = False
+        try:
+            state.zero_()
+            acc.zero_()
+            for sample in own:
+                self.forward(sample, training=True)
+                ops.bn_recalibrate_take(state, table, acc)
+            if dp is not None:
+                dp.sum_(acc)
+            ops.bn_recalibrate_finish(state, table, acc, len(samples), statistics)
+            done = True
+        finally:
+            if not done:
+                state.copy_(keep)
+            self.state_version += 1               # the inference folds are stale either way (bnstate was overwritten)
 
     def _arm_repack(self):
         """Repacks the variables now, on the current stream, and arms the two events the forward of a recorded step waits

@@ -905,6 +905,87 @@ def lamb_step_sched(theta, grad, m, v, dev_desc, weight_decay_rate, beta_1, beta
                                                  1 if advance else 0, _lib.current_stream()))
 
 
+BN_STATISTICS = {"mean": _lib.BN_STATS_MEAN, "pooled": _lib.BN_STATS_POOLED}     # the rules of bn_recalibrate_finish
+VFE_BN_LAYERS = ("vfe1.bn", "vfe2.bn", "fcn.bn")      # finalised by the VFE kernel; every other layer by a conv sink
+
+
+def bn_statistics(statistics):
+    """LISEC_BN_STATS_* of 'mean' / 'pooled'; ValueError for anything else.  No device, no library."""
+    try:
+        return BN_STATISTICS[statistics]
+    except (KeyError, TypeError):
+        raise ValueError(f"statistics must be 'mean' or 'pooled', not {statistics!r}") from None
+
+
+def bn_recal_rows(params):
+    """The table of lisec_bn_recalibrate_* as a host list [(mean_off, var_off, C, family)], one row per
+    BatchNormalization layer in forward order: the offsets of its moving statistics in ParamStore.state and the family
+    of the finaliser that updates them in a training forward (_lib.BN_FINALIZER_VFE for the three VFE layers,
+    BN_FINALIZER_CONV for the rest).  params: a ParamStore, or anything with its `specs` and `offsets`.  Pure host
+    arithmetic."""
+    rows = []
+    for name, shape, kind in params.specs:
+        if kind != "moving_mean":
+            continue
+        prefix = name[:-len(".moving_mean")]
+        family = _lib.BN_FINALIZER_VFE if prefix in VFE_BN_LAYERS else _lib.BN_FINALIZER_CONV
+        rows.append((params.offsets[name][1], params.offsets[prefix + ".moving_variance"][1], int(shape[0]), family))
+    return rows
+
+
+class BnRecalTable:
+    """rows [(mean_off, var_off, C, coef)] as the HOST table of lisec_bn_recalibrate_* (the library validates it and
+    copies it into each launch); `channels` = the sum of C: acc holds 3 * channels doubles."""
+
+    def __init__(self, rows):
+        self.n_entries = len(rows)
+        self.channels = sum(int(r[2]) for r in rows)
+        self.records = (_lib.BnRecalEntry * max(len(rows), 1))()
+        for rec, (mean_off, var_off, C, coef) in zip(self.records, rows):
+            rec.mean_off, rec.var_off, rec.C, rec.coef = int(mean_off), int(var_off), int(C), float(coef)
+
+
+def bn_recal_table(rows):
+    """bn_recal_rows' list as a BnRecalTable, each family replaced by its coefficient 1 - momentum as that finaliser
+    computes it (lisec_bn_recalibrate_coef: the constants live next to the kernels)."""
+    lib = _lib.load()
+    return BnRecalTable([(m, v, C, lib.lisec_bn_recalibrate_coef(int(family))) for m, v, C, family in rows])
+
+
+def bn_recal_acc(table, device):
+    """The zeroed accumulator of a recalibration: float64[3 * channels], the planes S1, S2, Sq (include/lisec_hip.h)."""
+    return torch.zeros(3 * table.channels, dtype=torch.float64, device=device)
+
+
+def _bn_recal_check(state, table, acc):
+    if state.dtype != torch.float32 or acc.dtype != torch.float64:
+        raise ValueError("bn_recalibrate: state must be float32 and acc float64")
+    if acc.numel() < 3 * table.channels:
+        raise ValueError(f"bn_recalibrate: acc holds {acc.numel()} doubles, the table needs {3 * table.channels}")
+    for rec in table.records[:table.n_entries]:
+        if max(rec.mean_off, rec.var_off) + rec.C > state.numel():
+            raise ValueError(f"bn_recalibrate: a record of {rec.C} channels at ({rec.mean_off}, {rec.var_off}) lies "
+                             f"outside a state of {state.numel()} floats")
+
+
+def bn_recalibrate_take(state, table, acc):
+    """One sweep of a recalibration (lisec_bn_recalibrate_take), behind its forward(training=True) over a zeroed
+    `state`: per channel S1 += m, S2 += v, Sq += m*m in fp64 with m, v = state / coef, and the two floats of state are
+    zeroed for the next sweep.  table: a BnRecalTable; acc: bn_recal_acc."""
+    _bn_recal_check(state, table, acc)
+    _lib.check(_lib.load().lisec_bn_recalibrate_take(_lib.ptr(state), table.records, table.n_entries, _lib.ptr(acc),
+                                                     _lib.current_stream()))
+
+
+def bn_recalibrate_finish(state, table, acc, sweeps, statistics="mean"):
+    """The moving statistics of `sweeps` takes (lisec_bn_recalibrate_finish): mean = S1/k; 'mean': var = S2/k,
+    'pooled': var = max(0, S2/k + Sq/k - mean*mean); each rounded once to float32 into state.  acc is only read."""
+    rule = bn_statistics(statistics)
+    _bn_recal_check(state, table, acc)
+    _lib.check(_lib.load().lisec_bn_recalibrate_finish(_lib.ptr(state), table.records, table.n_entries, _lib.ptr(acc),
+                                                       int(sweeps), rule, _lib.current_stream()))
+
+
 def conv_field_forward_workspace_bytes(g, row_capacity):
     return _lib.load().lisec_conv_field_forward_workspace_bytes(ctypes.byref(g), row_capacity)
 
