@@ -216,6 +216,9 @@ __global__ void k_label_fixup(lisec_rpn_cfg cfg, const double* __restrict__ fixe
     if (n_dev) B = min(B, max(*n_dev, 0));
     for (int b = 0; b < B; ++b) {
         if (count[b] != 0 || best_iou_bits[b] == 0ull) continue;
+        // no anchor of the second pass reproduced the best bits (the 0x7f fill is still there): the box goes without its
+        // positive, which a comparison of the maps shows, instead of the fill becoming a store index
+        if (best_order[b] < 0 || best_order[b] >= 2 * cfg.outX * cfg.outY) continue;
         const Anchor A = make_anchor(cfg, best_order[b]);
         double t[7];
         regression(A.box, fixed + (size_t)b * 7, t);
@@ -279,8 +282,8 @@ extern "C" int lisec_rpn_to_region(const lisec_rpn_cfg* cfg, const float* cls, i
         LISEC_LAUNCH(k_nms_suppress, dim3(cdiv(n, 256)), dim3(256), 0, st, ws.boxes, ws.alive, n, ws.picks,
                            max_picks, overlap_thresh, cfg->anchors[0][0], cfg->anchors[0][1]);
     }
-    LISEC_LAUNCH(k_nms_gather, dim3(1), dim3(256), 0, st, ws.boxes, ws.probs, ws.picks, ws.npicks, out_boxes,
-                       out_probs);
+    LISEC_LAUNCH(k_nms_gather, dim3(cdiv(max_picks, 256)), dim3(256), 0, st, ws.boxes, ws.probs, ws.picks, ws.npicks,
+                       out_boxes, out_probs);
     LISEC_HIP_TRY(hipMemcpyAsync(out_count, ws.npicks, sizeof(int), hipMemcpyDeviceToDevice, st));
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;

@@ -1,4 +1,5 @@
-"""Label generation and RPN decode + NMS (C ABI, float64) vs the CPU oracle (oracle/boxes_ref.py)."""
+"""Label generation and RPN decode + NMS (C ABI, float64) vs the CPU oracle (oracle/boxes_ref.py).
+The edges of both (ties, fixups, infinite and negative IoUs, small grids, > 256 picks): tests/test_gpu_box_edges.py."""
 import numpy as np
 import pytest
 
