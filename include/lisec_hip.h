@@ -976,11 +976,19 @@ int lisec_nadam_step_sched(float* theta, const float* grad, float* m, float* v, 
                            const lisec_lr_schedule* sched, float beta1, float beta2, float epsilon, float schedule_decay,
                            long long* state, int advance, lisec_stream_t stream);
 
+/* THE CHUNK RULES, of every chunk table below (lisec_reg_chunk, lisec_decay_chunk, lisec_lamb_chunk): the host cuts a
+ * variable of n floats into ceil(n / LISEC_REG_CHUNK) chunks.
+ *   - offset and count are in floats and multiples of 4; offset is relative to the buffer pointers of the call;
+ *   - count <= LISEC_REG_CHUNK;
+ *   - a chunk never crosses a variable;
+ *   - the chunks of a table are ascending in offset;
+ *   - the table is device memory and is NOT checked: every [offset, offset + count) must lie inside every buffer the
+ *     entry indexes by it. */
+
 /* Weight regularizers (tf.keras 2.4 regularizers.L1L2; csrc/regularize.hip), run in front of an optimizer entry on the
- * same range and stream.  The host cuts each regularised variable into ceil(n / LISEC_REG_CHUNK) chunks; a chunk never
- * crosses a variable, so it carries that variable's (l1, l2).  offset and count are in floats, multiples of 4, offset
- * relative to the theta / grad pointers given, count <= LISEC_REG_CHUNK.  The table is device memory and is NOT checked:
- * every [offset, offset + count) must lie inside both buffers.
+ * same range and stream.  The host cuts each regularised variable into chunks by the chunk rules above, offsets
+ * relative to the theta / grad pointers given; as a chunk never crosses a variable, it carries that variable's
+ * (l1, l2).
  *   grad[i] <- grad[i] + 2*l2*w + l1*sign(w) in fp32 (c2 = 2.0f*l2, sign(0) = 0) for every element of every chunk
  *   (grad == NULL: the penalty alone); the elements of a (0, 0) chunk and those outside every chunk keep their bits.
  *   P = sum over chunks of l1*sum|w| + l2*sum w^2: fp64 per thread, wave, workgroup and chunk; the per-chunk partials
@@ -1082,10 +1090,9 @@ int lisec_weight_average_eval(const lisec_weight_average_desc* desc /* host, cop
 /* Decoupled weight decay (optimizers.AdamW / SGDW / extend_with_decoupled_weight_decay; csrc/weight_decay.hip): one
  * streaming pass over the flat parameter buffer `theta`, run IN FRONT of an optimizer entry on the same range and the
  * same stream -- the order of tfa.optimizers.DecoupledWeightDecayExtension, which decays the variable first and then
- * updates the decayed variable.  The host cuts every DECAYED variable into chunks by the rules of lisec_reg_chunk:
- * offset and count in floats and multiples of 4, offset relative to the theta pointer given, count <= LISEC_REG_CHUNK, a
- * chunk never crosses a variable, ascending.  Only the decayed variables are in the table: an excluded variable costs
- * no traffic.  The table is device memory and is NOT checked: every [offset, offset + count) must lie inside theta.
+ * updates the decayed variable.  The host cuts every DECAYED variable into chunks by the chunk rules (above
+ * lisec_reg_chunk), offsets relative to the theta pointer given.  Only the decayed variables are in the table: an
+ * excluded variable costs no traffic.
  * coeff: a lisec_lr_schedule in DEVICE memory (written by lisec_lr_schedule_set; its `decay` must be 0).  With s =
  * state[0], the iteration count before the update -- read from the device, NEVER advanced, no ticket taken --
  *     wd_t = (float)schedule(s)     in double, once per workgroup, rounded once (the formulas of the table above)
@@ -1117,13 +1124,12 @@ int lisec_weight_decay_eval(const lisec_lr_schedule* coeff /* device */, const l
 /* LAMB (optimizers.LAMB; You et al. 2019; csrc/lamb.hip): layer-wise adaptive Adam, this project's own restatement of
  * tfa.optimizers.LAMB (parity unpinned).  The only update entry that is not element-wise: the step of a
  * variable is scaled by its trust ratio r = ||w|| / ||u||, a reduction over the whole variable.
- * The host cuts every trainable variable into chunks by the rules of lisec_reg_chunk: offset and count in floats and
- * multiples of 4, offset relative to the theta / grad / m / v pointers given (all four are indexed alike), count <=
- * LISEC_REG_CHUNK, a chunk never crosses a variable, ascending.  chunk.var is the index of the chunk's variable in
- * `vars`, chunk.flags says whether the variable is decayed (LISEC_LAMB_DECAYED) and whether its ratio is used
+ * The host cuts every trainable variable into chunks by the chunk rules (above lisec_reg_chunk), offsets relative to
+ * the theta / grad / m / v pointers given (all four are indexed alike).  chunk.var is the index of the chunk's variable
+ * in `vars`, chunk.flags says whether the variable is decayed (LISEC_LAMB_DECAYED) and whether its ratio is used
  * (LISEC_LAMB_ADAPTED; the chunks of one variable carry the same flags); vars[j] gives variable j's first chunk and
- * chunk count, both counted from the start of the TABLE.  Both tables are device memory and are NOT checked: every
- * [offset, offset + count) must lie inside all four buffers, every var inside `vars` and `ratios`.
+ * chunk count, both counted from the start of the TABLE.  `vars` is device memory and NOT checked either: every var
+ * must lie inside `vars` and `ratios`.
  * An entry works on chunks [first_chunk, first_chunk + n_chunks) and variables [first_var, first_var + n_vars) of the
  * tables; the chunk range must be exactly the chunks of the variable range (a variable is never split between two
  * calls).  The partials of chunk c live at workspace[2c], the ratio of variable j at ratios[j], whatever the range: the

@@ -1032,8 +1032,7 @@ class Model:
             # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
             # the descriptor on this stream, behind the previous epoch's last update
             captured = self._captured_step(samples, opt, seq_req, batch=B)
-            self.net._sync_lr(opt)
-            self.net._sync_wd(opt)               # likewise the coefficient of a decoupled weight decay
+            self.net._sync_lr(opt)               # (and the coefficient of a decoupled weight decay)
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
@@ -1051,7 +1050,7 @@ class Model:
                     return self._sequence_item(seq, i, points)
                 return (samples[i]._keepalive if points else samples[i], *target(i))
 
-            penalty = self.net.reg_penalty if self.net._reg_rows else None
+            penalty = self.net.reg_penalty if self.net.regularized else None
             t = 0                                           # sweeps trained on so far in this epoch
             for st, batch in enumerate(batches):
                 b = len(batch)

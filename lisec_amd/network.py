@@ -13,7 +13,6 @@ model_training.py:299):
     up_b  : concat[..., 256b:256(b+1)] = deconv(relu(bn(y_{b,q})))
     head  : (M,16) = concat @ [W_cls | W_reg] + bias     (cls = [:, :2], reg = [:, 2:])
 """
-import bisect
 import ctypes
 import json
 import math
@@ -282,6 +281,21 @@ class OptimizerSpec:
 
     def __repr__(self):
         return f"OptimizerSpec{self.config}"
+
+
+class _DeviceDescriptor:
+    """A lisec_lr_schedule at a fixed device address (`dev`) and the host descriptor last written into it (`host`)."""
+
+    def __init__(self, device):
+        self.dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=device)
+        self.host = None
+
+    def sync(self, desc):
+        """Makes `dev` hold desc: a copy on the current stream, behind every update already enqueued, when the contents
+        differ from the last ones written."""
+        if self.host is None or bytes(self.host) != bytes(desc):
+            ops.lr_schedule_set(self.dev, desc)
+            self.host = desc                                  # kept alive: the source of the copy
 
 
 class ConvLayer:
@@ -843,18 +857,16 @@ class LisecNet:
         self.momentum_cache = torch.ones(1, dtype=torch.float32, device=dev)
         # learning-rate descriptor (lisec_lr_schedule) of the OptimizerSpecs with device_lr, at a fixed address like the
         # iteration count; _sync_lr rewrites it, stream-ordered, when a step needs other contents
-        self._lr_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
-        self._lr_host = None
+        self._lr = _DeviceDescriptor(dev)
         # the coefficient of the decoupled weight decay (OptimizerSpec.weight_decay; csrc/weight_decay.hip): a second
-        # descriptor of the same type at a fixed address, written by _sync_wd as _sync_lr writes the rate's; and the
-        # chunk tables of the decayed variables, made when a selection is first used and kept for the net's life
-        # (recorded plans point at them): {DecaySpec.variables: (ascending offsets, device table)}
-        self._wd_dev = torch.zeros(ctypes.sizeof(_lib.LrSchedule), dtype=torch.uint8, device=dev)
-        self._wd_host = None
+        # descriptor of the same type, written likewise; and the chunk tables of the decayed variables, made when a
+        # selection is first used and kept for the net's life (recorded plans point at them):
+        # {DecaySpec.variables: ops.ChunkTable}
+        self._wd = _DeviceDescriptor(dev)
         self._decay_tables = {}
-        # a layer-wise optimizer (LAMB; csrc/lamb.hip): the chunk / variable tables per pair of exclusion lists, kept
-        # for the net's life like the decay tables, and -- made with the first table, every table has the same rows --
-        # the per-chunk workspace and the trust ratios of the last update, one per trainable variable
+        # a layer-wise optimizer (LAMB; csrc/lamb.hip): the ops.LambTable per pair of exclusion lists, kept for the
+        # net's life like the decay tables, and -- made with the first table, every table has the same rows -- the
+        # per-chunk workspace and the trust ratios of the last update, one per trainable variable
         self._lamb_tables = {}
         self._lamb_ws = self._lamb_ratios = None
         # BatchNormalization recalibration (recalibrate_batchnorm; csrc/bn_recalibrate.hip): the table of the layers'
@@ -867,21 +879,26 @@ class LisecNet:
         self.loss_counts = torch.zeros(2, dtype=torch.int64, device=dev)
         # [num0, den0, num1, den1, ...] of a DetectionLossSpec's metrics (lisec_detection_metrics); fixed address
         self.metric_pairs = torch.zeros(2 * _lib.DET_MAX_METRICS, dtype=torch.float64, device=dev)
-        # weight regularizers (csrc/regularize.hip): the chunk table (ascending offsets into theta), the penalty of the
-        # step and the per-chunk partials, at fixed addresses like loss_out; fixed for the net's life (id(net) keys the
-        # recorded plans)
+        # weight regularizers (csrc/regularize.hip): the chunk table (an ops.ChunkTable; None without regularizers), the
+        # per-chunk partials and the penalty of the step, at fixed addresses like loss_out; fixed for the net's life
+        # (id(net) keys the recorded plans)
         self.regularizers = {n: (float(a), float(b)) for n, (a, b) in (regularizers or {}).items() if a != 0 or b != 0}
         # the bias of a convolution that feeds a training-mode BatchNormalization has an identically zero gradient, and
         # the backward pass never writes its slot of grad (_BackwardPass.conv): the penalty pass must store its term
         # there, or the slot would carry the terms of every step so far
         self.unwritten_grads = tuple(L["conv"].bias for L in self.layers
                                      if L["kind"] in ("mid", "conv") and L["conv"].bias and L["conv"].bn)
-        self._reg_rows = ops.reg_chunks(self.params, self.regularizers, unwritten=self.unwritten_grads)
-        self._reg_offsets = [r[0] for r in self._reg_rows]
-        if self._reg_rows:
-            self._reg_table = ops.reg_table(self._reg_rows, dev)
-            self._reg_ws = ops.reg_workspace(len(self._reg_rows), dev)
+        rows = ops.reg_chunks(self.params, self.regularizers, unwritten=self.unwritten_grads)
+        self._reg = None
+        if rows:
+            self._reg = ops.reg_table(rows, dev)
+            self._reg_ws = ops.reg_workspace(len(rows), dev)
             self.reg_penalty = torch.zeros(1, dtype=torch.float64, device=dev)
+
+    @property
+    def regularized(self):
+        """Does a step of this net add weight penalties (reg_penalty exists and the update passes over a chunk table)?"""
+        return self._reg is not None
 
     @property
     def iterations(self):
@@ -1482,35 +1499,23 @@ class LisecNet:
         return dict(self._slots)
 
     def _sync_lr(self, opt):
-        """Makes the device learning-rate descriptor hold opt.lr_descriptor (nothing for a spec without device_lr): a
-        copy on the current stream, behind every update already enqueued, when the contents differ from the last ones
-        written.  A recorded step plan does not re-issue the copy; Model.fit calls this before the steps of an epoch."""
-        if not opt.device_lr:
-            return
-        raw = bytes(opt.lr_descriptor)
-        if self._lr_host is None or bytes(self._lr_host) != raw:
-            ops.lr_schedule_set(self._lr_dev, opt.lr_descriptor)
-            self._lr_host = opt.lr_descriptor                 # kept alive: the source of the copy
-
-    def _sync_wd(self, opt):
-        """_sync_lr for the coefficient of the decoupled weight decay: makes the device descriptor hold
-        opt.weight_decay.descriptor (nothing for a spec without decay)."""
-        if opt.weight_decay is None:
-            return
-        desc = opt.weight_decay.descriptor
-        if self._wd_host is None or bytes(self._wd_host) != bytes(desc):
-            ops.lr_schedule_set(self._wd_dev, desc)
-            self._wd_host = desc                              # kept alive: the source of the copy
+        """Makes the device descriptors (_DeviceDescriptor.sync) hold opt.lr_descriptor (nothing for a spec without
+        device_lr) and the coefficient of opt's decoupled weight decay (nothing for a spec without decay).  A recorded
+        step plan does not re-issue the copies; Model.fit calls this before the steps of an epoch."""
+        if opt.device_lr:
+            self._lr.sync(opt.lr_descriptor)
+        if opt.weight_decay is not None:
+            self._wd.sync(opt.weight_decay.descriptor)
 
     def decay_table(self, variables=None):
-        """(ascending offsets, device chunk table) of the variables a DecaySpec selects (ops.decay_chunks: None, names
-        and / or kinds), made once per selection.  KeyError: a name the network does not have; ValueError: a variable
-        that is not trainable."""
-        entry = self._decay_tables.get(variables)
-        if entry is None:
+        """The chunk table (ops.ChunkTable) of the variables a DecaySpec selects (ops.decay_chunks: None, names and /
+        or kinds), made once per selection.  KeyError: a name the network does not have; ValueError: a variable that is
+        not trainable."""
+        table = self._decay_tables.get(variables)
+        if table is None:
             rows = ops.decay_chunks(self.params, variables)
-            entry = self._decay_tables[variables] = ([r[0] for r in rows], ops.decay_table(rows, self.device))
-        return entry
+            table = self._decay_tables[variables] = ops.decay_table(rows, self.device)
+        return table
 
     def _decay(self, opt, lo, hi):
         """The decoupled weight decay of the variables in theta[lo:hi] (lo: a variable boundary), on the current
@@ -1518,28 +1523,26 @@ class LisecNet:
         without decay."""
         if opt.weight_decay is None:
             return
-        offsets, table = self.decay_table(opt.weight_decay.variables)
-        first = bisect.bisect_left(offsets, lo)
-        last = bisect.bisect_left(offsets, hi)
-        self._sync_wd(opt)
-        ops.weight_decay(self.params.theta, table, last - first, self._wd_dev, self._iter_dev, first=first)
+        table = self.decay_table(opt.weight_decay.variables)
+        first, count = table.span(lo, hi)
+        self._wd.sync(opt.weight_decay.descriptor)
+        ops.weight_decay(self.params.theta, table, count, self._wd.dev, self._iter_dev, first=first)
 
     def _regularize(self, lo, hi, accumulate=False, fold=False, grad=True):
         """The weight penalties of the variables in theta[lo:hi] (lo: a variable boundary), on the current stream: grad +=
         2*l2*w + l1*sign(w) on the weights as they are now, reg_penalty = P of the range (accumulate: += P), and with fold
         loss_out[0] = float32(loss_out[0] + reg_penalty) -- Keras adds the penalty to `loss` alone.  grad=False: P only.
         Nothing at all for a net without regularizers."""
-        if not self._reg_rows:
+        if not self.regularized:
             return
-        first = bisect.bisect_left(self._reg_offsets, lo)
-        last = bisect.bisect_left(self._reg_offsets, hi)
-        ops.regularize(self.params.theta, self.grad if grad else None, self._reg_table, last - first, self.reg_penalty,
+        first, count = self._reg.span(lo, hi)
+        ops.regularize(self.params.theta, self.grad if grad else None, self._reg, count, self.reg_penalty,
                        self._reg_ws, first=first, accumulate=accumulate, loss_total=self.loss_out if fold else None)
 
     def penalty(self):
         """Enqueues P = sum over the regularised variables of l1*sum|w| + l2*sum w^2 of the weights as they are now into
         reg_penalty (device float64[1]) and returns it; None for a net without regularizers.  No gradient is touched."""
-        if not self._reg_rows:
+        if not self.regularized:
             return None
         self._regularize(0, self.params.n_theta, grad=False)
         return self.reg_penalty
@@ -1557,57 +1560,40 @@ class LisecNet:
         self._decay(opt, lo, hi)
         rec = opt.record
         entry, names, args = opt.launch
-        if rec.layerwise:
-            self._update_layerwise(opt, lo, hi, advance)
-            return
-        bufs = [None if name is None else self.slot(name)[lo:hi] for name in names]
-        if rec.scalar is not None:
-            bufs.append(getattr(self, rec.scalar))
         if opt.device_lr:
-            self._sync_lr(opt)
-            rate = (self._lr_dev,)
+            self._lr.sync(opt.lr_descriptor)
+            rate = (self._lr.dev,)
         else:
             rate = (opt.lr,) if rec.schedule_decay else (opt.lr, opt.decay)
-        getattr(ops, entry)(self.params.theta[lo:hi], self.grad[lo:hi], *bufs, *rate, *(getattr(opt, a) for a in args),
-                            self._iter_dev, advance=advance)
+        cut, rows = slice(lo, hi), {}
+        if rec.layerwise:
+            # the entry gets the WHOLE buffers and the rows of the variables whose first float lies in theta[lo:hi]: the
+            # tables hold whole variables, so none is split between the two parts of a step, and every chunk and variable
+            # has its own slot of the workspace and of the ratio buffer -- the early part and the closing part together
+            # leave what one launch over everything leaves
+            table = self.lamb_table(*opt.lists)
+            (first, n_chunks), (first_var, n_vars) = table.chunks.span(lo, hi), table.variables.span(lo, hi)
+            cut, rows = slice(None), dict(table=table, ratios=self._lamb_ratios, workspace=self._lamb_ws, first=first,
+                                          n_chunks=n_chunks, first_var=first_var, n_vars=n_vars)
+        bufs = [None if name is None else self.slot(name)[cut] for name in names]
+        if rec.scalar is not None:
+            bufs.append(getattr(self, rec.scalar))
+        getattr(ops, entry)(self.params.theta[cut], self.grad[cut], *bufs, *rate, *(getattr(opt, a) for a in args),
+                            self._iter_dev, advance=advance, **rows)
 
     def lamb_table(self, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None):
-        """(ascending chunk offsets, ascending variable offsets, variable names, ops.LambTable) of a layer-wise
-        optimizer with these exclusion lists (ops.lamb_chunks), made once per pair; the workspace and the ratio buffer
-        are made with the first.  KeyError: a name the network does not have; ValueError: a variable that is not
-        trainable."""
+        """The ops.LambTable of a layer-wise optimizer with these exclusion lists (ops.lamb_chunks), made once per pair;
+        the workspace and the ratio buffer are made with the first.  KeyError: a name the network does not have;
+        ValueError: a variable that is not trainable."""
         key = (exclude_from_weight_decay, exclude_from_layer_adaptation)
-        entry = self._lamb_tables.get(key)
-        if entry is None:
-            chunks, variables = ops.lamb_chunks(self.params, *key)
-            table = ops.lamb_table(chunks, variables, self.device)
+        table = self._lamb_tables.get(key)
+        if table is None:
+            table = self._lamb_tables[key] = ops.lamb_table(*ops.lamb_chunks(self.params, *key), self.device)
             if self._lamb_ws is None:
                 self._lamb_ws = ops.lamb_workspace(table.n_chunks, table.n_vars, self.device)
                 self._lamb_ratios = torch.ones(max(table.n_vars, 1), dtype=torch.float32, device=self.device)
-            entry = self._lamb_tables[key] = ([c[0] for c in chunks], [v[2] for v in variables],
-                                              [v[3] for v in variables], table)
             torch.cuda.synchronize(self.device)   # whole before any stream of the step (the second one included) uses them
-        return entry
-
-    def _update_layerwise(self, opt, lo, hi, advance):
-        """_update's launch for a layer-wise optimizer: the variables whose first float lies in theta[lo:hi] -- lo and hi
-        are variable boundaries, and as the tables hold whole variables a variable is never split between the two parts
-        of a step --, by the chunk and variable rows that bisect finds at lo / hi, as _decay cuts its table.  The entry
-        gets the WHOLE buffers; every chunk and variable has its own slot of the workspace and of the ratio buffer, so
-        the early part and the closing part of a step together leave what one launch over everything leaves."""
-        entry, names, args = opt.launch
-        chunk_offsets, var_offsets, _, table = self.lamb_table(*opt.lists)
-        first, last = bisect.bisect_left(chunk_offsets, lo), bisect.bisect_left(chunk_offsets, hi)
-        first_var, last_var = bisect.bisect_left(var_offsets, lo), bisect.bisect_left(var_offsets, hi)
-        if opt.device_lr:
-            self._sync_lr(opt)
-            rate = (self._lr_dev,)
-        else:
-            rate = (opt.lr, opt.decay)
-        getattr(ops, entry)(self.params.theta, self.grad, *(self.slot(name) for name in names), *rate,
-                            *(getattr(opt, a) for a in args), self._iter_dev, advance=advance, table=table,
-                            ratios=self._lamb_ratios, workspace=self._lamb_ws, first=first, n_chunks=last - first,
-                            first_var=first_var, n_vars=last_var - first_var)
+        return table
 
     def trust_ratios(self):
         """{variable name: r} of the last update of a layer-wise optimizer (LAMB): the trust ratio ||w|| / ||u|| each
@@ -1617,7 +1603,7 @@ class LisecNet:
         if not self._lamb_tables:
             raise RuntimeError("trust_ratios(): no update by a layer-wise optimizer (optimizers.LAMB) has run")
         torch.cuda.current_stream().wait_stream(self.side)
-        names = next(iter(self._lamb_tables.values()))[2]
+        names = next(iter(self._lamb_tables.values())).names
         return dict(zip(names, self._lamb_ratios.cpu().tolist()))
 
     def early_update(self, lo, hi, opt=None):
@@ -1912,7 +1898,7 @@ class LisecNet:
         tot = torch.zeros(3, dtype=torch.float64, device=self.device)
         for s_, yc, yr, pos in zip(samples, y_cls, y_reg, self.batch_positions(b)):
             tot += self.train_micro_step(s_, yc, yr, pos, loss=loss, allreduce=allreduce, opt=opt)
-        if self._reg_rows and b > 1:
+        if self.regularized and b > 1:
             tot[0] += (b - 1) * self.reg_penalty[0]     # the last sweep's total holds P once; the mean keeps it whole
         return tot / b
 
@@ -2179,7 +2165,7 @@ class RecordedStep(_TrainingPlans):
       targets  (Ho,Wo,2) / (Ho,Wo,14) static buffers
       lr_t     derived by the optimizer kernels from the device iteration counter (lisec_sgd_nesterov_step_dev,
                lisec_sgd_step_dev, lisec_adam_step_dev) -- and with a learning-rate schedule or a rate that changes
-               between epochs, from the descriptor LisecNet._lr_dev (lisec_*_step_sched), which LisecNet._sync_lr
+               between epochs, from the descriptor LisecNet._lr.dev (lisec_*_step_sched), which LisecNet._sync_lr
                rewrites between replays
 
     Record and replay on ONE torch stream (the current stream at construction).  Data parallel (allreduce=): the gradient

@@ -1,5 +1,6 @@
 """Thin Python wrappers over the dense-contraction entry points of the C ABI (include/lisec_hip.h
 section 3).  Tensors are torch CUDA tensors used purely as device memory."""
+import bisect
 import ctypes
 import math
 
@@ -7,6 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import ConvGeom
+from .params import TRAINABLE_KINDS
 
 IN_RELU, OUT_RELU, ACCUMULATE, DY_RELU, SMALL_TILE, TAG_ROOFLINE = 1, 2, 4, 8, 16, 32
 # SMALL_TILE (conv_forward / conv_plan): a small K-sliced layer may run as 64-row tiles, two workgroups per CU
@@ -504,36 +506,96 @@ def detection_metrics(cfg, head, y_cls, y_reg, M, out, accumulate=False):
                                                    _lib.current_stream()))
 
 
+def select_variables(params, names, what):
+    """The ParamStore names that `names` selects, in the order given, each once.  names: a string or an iterable of
+    ParamStore names and / or the kinds 'kernel', 'bias', 'gamma', 'beta' (each: every variable of that kind, in the
+    order of params.specs).  params: a ParamStore, or anything with its `offsets` ({name: ("theta", offset, shape)})
+    and, for a kind, its `specs`.  What None means is the caller's business.  KeyError: a name the network does not
+    have (a kind of variable that is not trained among them); ValueError: a variable that is not trainable (the
+    BatchNormalization moving statistics), "... it cannot be {what}"."""
+    chosen = []
+    for name in (names,) if isinstance(names, str) else names:
+        if name in TRAINABLE_KINDS:
+            chosen.extend(n for n, _, kind in params.specs if kind == name)
+        elif params.offsets[name][0] != "theta":
+            raise ValueError(f"{name} is not a trainable variable: it cannot be {what}")
+        else:
+            chosen.append(name)
+    return list(dict.fromkeys(chosen))
+
+
+def variable_chunks(params, name):
+    """Yields the (offset, count) chunks of one trainable variable: its padded length -- up to the next multiple of 4
+    floats; the padding floats of theta are 0, stay 0 and add nothing to a sum -- cut into ceil(n / REG_CHUNK) pieces
+    of at most REG_CHUNK floats, ascending.  The chunk rules of include/lisec_hip.h, for every table of this module."""
+    _, off, shape = params.offsets[name]
+    n = (math.prod(shape) + 3) // 4 * 4
+    for start in range(0, n, _lib.REG_CHUNK):
+        yield off + start, min(_lib.REG_CHUNK, n - start)
+
+
+class ChunkTable:
+    """Host rows as a device table of `record`s (a ctypes Structure of _lib): `rows`, whose leading fields fill the
+    record's in order (the rest of a row is the host's own; the rest of a record stays 0); `offsets`, ascending, the
+    place in theta of each row (a row's first field unless given); len(); and `records`, the uint8 device tensor,
+    whose data_ptr / numel / numpy the table forwards: it stands where that tensor stood (_lib.ptr, a raw launch)."""
+
+    def __init__(self, record, rows, device, offsets=None):
+        self.record, self.rows = record, list(rows)
+        self.offsets = [r[0] for r in self.rows] if offsets is None else list(offsets)
+        arr = (record * max(len(self.rows), 1))()
+        for rec, row in zip(arr, self.rows):
+            for (field, _), value in zip(record._fields_, row):
+                setattr(rec, field, value)
+        self.records = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def data_ptr(self):
+        return self.records.data_ptr()
+
+    def numel(self):
+        return self.records.numel()
+
+    def numpy(self):
+        return self.records.numpy()
+
+    def span(self, lo, hi):
+        """(first, count) of the rows that lie in theta[lo:hi], lo and hi variable boundaries.  The spans of [lo, mid)
+        and [mid, hi) are adjacent and together that of [lo, hi): the early update of a step plus the closing one
+        visit exactly the rows of one update over everything."""
+        first = bisect.bisect_left(self.offsets, lo)
+        return first, bisect.bisect_left(self.offsets, hi) - first
+
+    def at(self, first, count, who):
+        """The address of record `first`, for a launch over rows [first, first + count); ValueError outside the table."""
+        if first < 0 or count < 0 or first + count > len(self):
+            raise ValueError(f"{who}: rows [{first}, {first + count}) outside a table of {len(self)}")
+        return ctypes.c_void_p(self.records.data_ptr() + first * ctypes.sizeof(self.record))
+
+
 def reg_chunks(params, coeffs, unwritten=()):
-    """The chunk table of lisec_regularize as a host list [(offset, count, l1, l2, flags)], ascending in offset: every
-    variable of coeffs ({ParamStore name: (l1, l2)}) with a pair other than (0, 0), cut into ceil(n / REG_CHUNK) chunks
-    over its padded length (the padding floats of theta are 0 and add nothing).  params: a ParamStore, or anything with
-    its `offsets` ({name: ("theta", offset, shape)}).  unwritten: the names of the variables whose gradient slot no
-    backward pass writes (the gradient is identically 0); their chunks carry REG_GRAD_IS_ZERO, so that the term is
-    stored into the slot, not added to what the step before left there.  Pure host arithmetic: no device, no library.
-    KeyError: a name the network does not have; ValueError: a variable that is not trainable."""
+    """The chunk table of lisec_regularize as a host list [(offset, count, l1, l2, flags)], ascending in offset: the
+    chunks (variable_chunks) of every variable of coeffs ({ParamStore name: (l1, l2)}) with a pair other than (0, 0).
+    unwritten: the names of the variables whose gradient slot no backward pass writes (the gradient is identically 0);
+    their chunks carry REG_GRAD_IS_ZERO, so that the term is stored into the slot, not added to what the step before
+    left there.  Pure host arithmetic: no device, no library.  KeyError, ValueError: select_variables'."""
     rows, unwritten = [], set(unwritten)
-    for name, (l1, l2) in coeffs.items():
-        which, off, shape = params.offsets[name]
-        if which != "theta":
-            raise ValueError(f"{name} is not a trainable variable: it cannot be regularised")
+    for name in select_variables(params, coeffs, "regularised"):
+        l1, l2 = coeffs[name]
         if l1 == 0 and l2 == 0:
             continue
-        n = (math.prod(shape) + 3) // 4 * 4
         flags = _lib.REG_GRAD_IS_ZERO if name in unwritten else 0
-        for start in range(0, n, _lib.REG_CHUNK):
-            rows.append((off + start, min(_lib.REG_CHUNK, n - start), float(l1), float(l2), flags))
+        rows.extend((off, count, float(l1), float(l2), flags) for off, count in variable_chunks(params, name))
     rows.sort()
     return rows
 
 
 def reg_table(chunks, device):
-    """reg_chunks' list as the device table of lisec_regularize (uint8 tensor of len(chunks) lisec_reg_chunk records);
-    a row may leave the flags out (0)."""
-    arr = (_lib.RegChunk * max(len(chunks), 1))()
-    for rec, (off, count, l1, l2, *flags) in zip(arr, chunks):
-        rec.offset, rec.count, rec.l1, rec.l2, rec.flags = off, count, l1, l2, (flags[0] if flags else 0)
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    """reg_chunks' list as the device table of lisec_regularize (a ChunkTable of lisec_reg_chunk records); a row may
+    leave the flags out (0)."""
+    return ChunkTable(_lib.RegChunk, chunks, device)
 
 
 def reg_workspace(n_chunks, device):
@@ -544,10 +606,7 @@ def regularize(theta, grad, table, n_chunks, penalty, workspace, first=0, accumu
     """lisec_regularize over chunks [first, first + n_chunks) of `table` (reg_table; offsets relative to theta / grad as
     given): grad += 2*l2*w + l1*sign(w) (grad None: the penalty alone), penalty (float64[1] device tensor) = P, or += P
     with accumulate, and loss_total[0] (float32 device tensor, or None) = float32(loss_total[0] + penalty)."""
-    if first < 0 or (n_chunks > 0 and (first + n_chunks) * ctypes.sizeof(_lib.RegChunk) > table.numel()):
-        raise ValueError(f"regularize: chunks [{first}, {first + n_chunks}) outside a table of "
-                         f"{table.numel() // ctypes.sizeof(_lib.RegChunk)}")
-    chunks = ctypes.c_void_p(table.data_ptr() + first * ctypes.sizeof(_lib.RegChunk))
+    chunks = table.at(first, int(n_chunks), "regularize")
     _lib.check(_lib.load().lisec_regularize(_lib.ptr(theta), _lib.ptr(grad), chunks, int(n_chunks), _lib.ptr(penalty),
                                             1 if accumulate else 0, _lib.ptr(loss_total), _lib.ptr(workspace),
                                             workspace.numel(), _lib.current_stream()))
@@ -732,53 +791,23 @@ def weight_average_eval(desc, state, k, c_out=None, m_out=None):
 
 
 def decay_chunks(params, names=None):
-    """The chunk table of lisec_weight_decay as a host list [(offset, count)], ascending in offset: every variable that
-    `names` selects, cut like reg_chunks into ceil(n / REG_CHUNK) chunks over its padded length (the padding floats of
-    theta are 0 and stay 0).  names: None -- every trainable variable --, or an iterable of ParamStore names and / or
-    the kinds 'kernel', 'bias', 'gamma', 'beta' (each: every variable of that kind).  params: a ParamStore, or anything
-    with its `specs` and `offsets`.  Pure host arithmetic: no device, no library.  KeyError: a name the network does not
-    have; ValueError: a variable that is not trainable (the BatchNormalization moving statistics)."""
-    from .params import TRAINABLE_KINDS
-    if names is None:
-        chosen = [n for n, _, kind in params.specs if kind in TRAINABLE_KINDS]
-    else:
-        if isinstance(names, str):
-            names = (names,)
-        chosen = []
-        for name in names:
-            if name in TRAINABLE_KINDS:
-                chosen.extend(n for n, _, kind in params.specs if kind == name)
-            else:
-                chosen.append(name)
-    rows = []
-    for name in dict.fromkeys(chosen):
-        which, off, shape = params.offsets[name]
-        if which != "theta":
-            raise ValueError(f"{name} is not a trainable variable: it cannot be decayed")
-        n = (math.prod(shape) + 3) // 4 * 4
-        for start in range(0, n, _lib.REG_CHUNK):
-            rows.append((off + start, min(_lib.REG_CHUNK, n - start)))
-    rows.sort()
-    return rows
+    """The chunk table of lisec_weight_decay as a host list [(offset, count)], ascending in offset: the chunks
+    (variable_chunks) of every variable that `names` selects (select_variables); None -- every trainable variable.
+    params: a ParamStore, or anything with its `specs` and `offsets`.  Pure host arithmetic: no device, no library."""
+    chosen = select_variables(params, TRAINABLE_KINDS if names is None else names, "decayed")
+    return sorted(chunk for name in chosen for chunk in variable_chunks(params, name))
 
 
 def decay_table(chunks, device):
-    """decay_chunks' list as the device table of lisec_weight_decay (uint8 tensor of len(chunks) lisec_decay_chunk
-    records)."""
-    arr = (_lib.DecayChunk * max(len(chunks), 1))()
-    for rec, (off, count) in zip(arr, chunks):
-        rec.offset, rec.count = off, count
-    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    """decay_chunks' list as the device table of lisec_weight_decay (a ChunkTable of lisec_decay_chunk records)."""
+    return ChunkTable(_lib.DecayChunk, chunks, device)
 
 
 def weight_decay(theta, table, n_chunks, coeff, state, first=0):
     """lisec_weight_decay over chunks [first, first + n_chunks) of `table` (decay_table; offsets relative to theta as
     given): w <- w - wd_t*w, a float32 multiply and a float32 subtraction, wd_t = float32(schedule(state[0])) of the
     device descriptor `coeff` (lr_schedule_set; its decay 0).  state is read, never advanced."""
-    if first < 0 or (n_chunks > 0 and (first + n_chunks) * ctypes.sizeof(_lib.DecayChunk) > table.numel()):
-        raise ValueError(f"weight_decay: chunks [{first}, {first + n_chunks}) outside a table of "
-                         f"{table.numel() // ctypes.sizeof(_lib.DecayChunk)}")
-    chunks = ctypes.c_void_p(table.data_ptr() + first * ctypes.sizeof(_lib.DecayChunk))
+    chunks = table.at(first, int(n_chunks), "weight_decay")
     _lib.check(_lib.load().lisec_weight_decay(_lib.ptr(theta), chunks, int(n_chunks), _lib.ptr(coeff), _lib.ptr(state),
                                               _lib.current_stream()))
 
@@ -789,70 +818,39 @@ def weight_decay_eval(coeff, state, k, out):
                                                    _lib.current_stream()))
 
 
-def _select_variables(params, names):
-    """The set of ParamStore names that `names` selects: None or empty -- none --, else ParamStore names and / or the
-    kinds 'kernel', 'bias', 'gamma', 'beta' (each: every variable of that kind), as decay_chunks reads them."""
-    from .params import TRAINABLE_KINDS
-    if names is None:
-        return set()
-    if isinstance(names, str):
-        names = (names,)
-    chosen = set()
-    for name in names:
-        if name in TRAINABLE_KINDS:
-            chosen.update(n for n, _, kind in params.specs if kind == name)
-        else:
-            which = params.offsets[name][0]                 # KeyError: a name the network does not have
-            if which != "theta":
-                raise ValueError(f"{name} is not a trainable variable: it cannot be excluded from an update")
-            chosen.add(name)
-    return chosen
-
-
 LAMB_BLOCKS = _lib.LAMB_BLOCKS                 # the widest grid of a LAMB pass: past it the workgroups stride over the table
 
 
 def lamb_chunks(params, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None):
     """The tables of lisec_lamb_step_* as host lists, both ascending in offset: (chunk rows [(offset, count, var,
-    flags)], variable rows [(first_chunk, n_chunks, offset, name)]).  EVERY trainable variable is in them, cut like
-    reg_chunks into ceil(n / REG_CHUNK) chunks over its padded length (the padding floats of theta are 0, have a zero
-    gradient and add nothing to either norm); var is the index of the chunk's row in the variable rows; flags has
-    LAMB_DECAYED unless exclude_from_weight_decay selects the variable and LAMB_ADAPTED unless
-    exclude_from_layer_adaptation does -- None there: the list of exclude_from_weight_decay, as in tfa.  Both lists take
-    what decay_chunks' `names` takes: ParamStore names and / or the kinds 'kernel', 'bias', 'gamma', 'beta'.  Pure host
-    arithmetic: no device, no library.  KeyError: a name the network does not have; ValueError: a variable that is not
-    trainable (the BatchNormalization moving statistics)."""
-    from .params import TRAINABLE_KINDS
+    flags)], variable rows [(first_chunk, n_chunks, offset, name)]).  EVERY trainable variable is in them, cut by
+    variable_chunks (the padding floats have a zero gradient and add nothing to either norm); var is the index of the
+    chunk's row in the variable rows; flags has LAMB_DECAYED unless exclude_from_weight_decay selects the variable and
+    LAMB_ADAPTED unless exclude_from_layer_adaptation does -- None there: the list of exclude_from_weight_decay, as in
+    tfa; None for both: no variable.  Both lists take what select_variables takes.  Pure host arithmetic."""
     if exclude_from_layer_adaptation is None:
         exclude_from_layer_adaptation = exclude_from_weight_decay
-    undecayed = _select_variables(params, exclude_from_weight_decay)
-    unadapted = _select_variables(params, exclude_from_layer_adaptation)
-    placed = sorted((params.offsets[n][1], n, shape) for n, shape, kind in params.specs if kind in TRAINABLE_KINDS)
+    undecayed, unadapted = (set(select_variables(params, () if names is None else names, "excluded from an update"))
+                            for names in (exclude_from_weight_decay, exclude_from_layer_adaptation))
     chunks, variables = [], []
-    for off, name, shape in placed:
-        n = (math.prod(shape) + 3) // 4 * 4
+    for name in sorted(select_variables(params, TRAINABLE_KINDS, "updated"), key=lambda n: params.offsets[n][1]):
         flags = (0 if name in undecayed else _lib.LAMB_DECAYED) | (0 if name in unadapted else _lib.LAMB_ADAPTED)
         first = len(chunks)
-        for start in range(0, n, _lib.REG_CHUNK):
-            chunks.append((off + start, min(_lib.REG_CHUNK, n - start), len(variables), flags))
-        variables.append((first, len(chunks) - first, off, name))
+        chunks.extend((off, count, len(variables), flags) for off, count in variable_chunks(params, name))
+        variables.append((first, len(chunks) - first, params.offsets[name][1], name))
     return chunks, variables
 
 
 class LambTable:
-    """lamb_chunks' lists on the device: `chunks` (uint8 tensor of lisec_lamb_chunk records), `variables` (uint8 tensor
-    of lisec_lamb_var records) and their lengths n_chunks / n_vars."""
+    """lamb_chunks' lists on the device: `chunks` (a ChunkTable of lisec_lamb_chunk records), `variables` (one of
+    lisec_lamb_var records, keyed by the offset of each variable's first chunk), their lengths n_chunks / n_vars and
+    `names`, the variables' (empty when the rows carry none)."""
 
     def __init__(self, chunks, variables, device):
+        self.chunks = ChunkTable(_lib.LambChunk, chunks, device)
+        self.variables = ChunkTable(_lib.LambVar, variables, device, offsets=[chunks[v[0]][0] for v in variables])
         self.n_chunks, self.n_vars = len(chunks), len(variables)
-        carr = (_lib.LambChunk * max(len(chunks), 1))()
-        for rec, (off, count, var, flags) in zip(carr, chunks):
-            rec.offset, rec.count, rec.var, rec.flags = off, count, var, flags
-        varr = (_lib.LambVar * max(len(variables), 1))()
-        for rec, (first, n, *_) in zip(varr, variables):
-            rec.first_chunk, rec.n_chunks = first, n
-        self.chunks = torch.frombuffer(bytearray(bytes(carr)), dtype=torch.uint8).to(device)
-        self.variables = torch.frombuffer(bytearray(bytes(varr)), dtype=torch.uint8).to(device)
+        self.names = [v[3] for v in variables if len(v) > 3]
 
 
 def lamb_table(chunks, variables, device):
@@ -868,13 +866,13 @@ def lamb_workspace(n_chunks, n_vars, device):
 
 
 def _lamb_range(table, ratios, first, n_chunks, first_var, n_vars):
+    """The rows of a launch as ints, None: to the end; ValueError outside either table or past the ratios."""
     n_chunks = table.n_chunks - first if n_chunks is None else int(n_chunks)
     n_vars = table.n_vars - first_var if n_vars is None else int(n_vars)
-    if first < 0 or n_chunks < 0 or first + n_chunks > table.n_chunks:
-        raise ValueError(f"lamb: chunks [{first}, {first + n_chunks}) outside a table of {table.n_chunks}")
-    if first_var < 0 or n_vars < 0 or first_var + n_vars > min(table.n_vars, ratios.numel()):
-        raise ValueError(f"lamb: variables [{first_var}, {first_var + n_vars}) outside a table of {table.n_vars} "
-                         f"with {ratios.numel()} ratios")
+    table.chunks.at(first, n_chunks, "lamb chunks")
+    table.variables.at(first_var, n_vars, "lamb variables")
+    if first_var + n_vars > ratios.numel():
+        raise ValueError(f"lamb: variables [{first_var}, {first_var + n_vars}) with {ratios.numel()} ratios")
     return int(first), n_chunks, int(first_var), n_vars
 
 

@@ -64,8 +64,9 @@ class Optimizer(collections.namedtuple("Optimizer", "kind class_name lr decay hy
     args: the OptimizerSpec attributes both entries take after the rate.
     layerwise: the update is not element-wise -- a step of a variable depends on a reduction over the whole variable
         (LAMB's trust ratio) --, so a range of theta can only be cut at variable boundaries: both entries take the WHOLE
-        buffers and, as keywords, the chunk / variable tables with the rows of the range, a workspace and the ratio
-        buffer (LisecNet._update; ops.lamb_step_dev).  Such an optimizer also has the two exclusion lists `lists`."""
+        buffers and, as keywords, an ops.LambTable with the rows of the range (first / n_chunks, first_var / n_vars: the
+        spans of its two ChunkTables), a workspace and the ratio buffer (LisecNet._update; ops.lamb_step_dev).  Such an
+        optimizer also has the two exclusion lists `lists`."""
     __slots__ = ()
 
     @property

@@ -54,7 +54,7 @@ if __name__ == "__main__":
         m = models[mode]
         size = _lib.load().lisec_step_plan_size(m._captured[1].plans[0]) if m._captured is not None else 0
         print(f"Model.fit ({args.cloud}), {mode}: median {np.median(a):.3f} ms/step (windows {min(a):.3f} .. {max(a):.3f}, "
-              f"{args.windows} x {args.steps} steps), step plan of {size} operations, {len(m.net._reg_rows)} chunks, "
+              f"{args.windows} x {args.steps} steps), step plan of {size} operations, {len(m.net._reg or ())} chunks, "
               f"loss {loss[mode]:.4f}")
     a, b = (np.median(v) for v in ms.values())
     print(f"regularised / plain = {b / a:.4f}  ({1e3 * (b - a):+.1f} us per step)")

@@ -32,14 +32,14 @@ def pass_alone(net, reps):
     dev = net.device
     theta = torch.randn(net.params.n_theta, dtype=torch.float32, device=dev)
     state = torch.tensor([1000, 0], dtype=torch.int64, device=dev)
-    coeff = torch.zeros_like(net._wd_dev)
+    coeff = torch.zeros_like(net._wd.dev)
     ops.lr_schedule_set(coeff, mt.lr_schedules.descriptor(1e-4, 0.0))
     for what, variables in (("every variable", None), ("the kernels", ("kernel",))):
-        offsets, table = net.decay_table(variables)
-        n = sum(c for _, c in ops.decay_chunks(net.params, variables))
+        table = net.decay_table(variables)
+        n = sum(c for _, c in table.rows)
 
         def call():
-            ops.weight_decay(theta, table, len(offsets), coeff, state)
+            ops.weight_decay(theta, table, len(table), coeff, state)
         for _ in range(20):
             call()
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -51,7 +51,7 @@ def pass_alone(net, reps):
         torch.cuda.synchronize()
         us = 1e3 * t0.elapsed_time(t1) / reps
         rate = 8 * n / (us * 1e-6)
-        print(f"(a) lisec_weight_decay, {what}: {us:.2f} us per pass over {n} floats in {len(offsets)} chunks "
+        print(f"(a) lisec_weight_decay, {what}: {us:.2f} us per pass over {n} floats in {len(table)} chunks "
               f"({8 * n / 1e6:.1f} MB), {rate / 1e12:.2f} TB/s = {rate / HBM_PEAK:.2f} of the HBM peak "
               f"({reps} back-to-back passes, launch gaps included)")
 
