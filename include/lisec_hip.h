@@ -1185,6 +1185,61 @@ int lisec_lamb_step_sched(float* theta, const float* grad, float* m, float* v, c
                           const lisec_lr_schedule* sched /* device */, float weight_decay_rate, float beta1, float beta2,
                           float epsilon, long long* state, int advance, lisec_stream_t stream);
 
+/* Gradient clipping (optimizers.clip_gradients; csrc/grad_clip.hip): clipvalue, clipnorm and global_clipnorm of tf.keras
+ * 2.4 in this project's own restatement (parity unpinned).  Passes over the flat gradient buffer `grad`, run
+ * IN FRONT of an optimizer entry on the same stream: behind the penalty pass (Keras' regularization loss sits in the
+ * tape, so its gradient is clipped with the rest) and in front of the decoupled weight decay (which acts on the
+ * variable).  The table is LAMB's -- lisec_lamb_chunk / lisec_lamb_var above, every trainable variable cut by the chunk
+ * rules, offsets relative to `grad`, chunk.var and var.first_chunk counted from the start of the TABLE, flags ignored:
+ * a per-variable norm needs exactly a chunk's variable and a variable's chunks, so no new record type is added.
+ * `clip` is the threshold c > 0.  An entry works on chunks [first_chunk, first_chunk + n_chunks) and, for the
+ * per-variable norm, variables [first_var, first_var + n_vars), which must be exactly the variables of those chunks.
+ * The partial of chunk k lives at workspace[k] (a double), the scale of variable j at scales[j], its norm at norms[j],
+ * whatever the range: the two parts of a split update use slots of their own.
+ * THE ARITHMETIC IS A CONTRACT (tests pin it bit for bit; the file is compiled with contraction off):
+ *   lisec_grad_clip_value    for every element of every chunk: g <- c where g > c, g <- -c where g < -c; every other g
+ *                            keeps its BITS -- a NaN (both comparisons are false; this is not fminf(fmaxf())), a -0, a
+ *                            denormal.  +-inf become +-c.  One launch, 8 bytes of traffic per element.
+ *   lisec_grad_clip_norm     three launches ordered by the stream alone:
+ *     1. S_k = sum over chunk k of (double)g*(double)g: the product exact, each addition an fp64 operation of its own,
+ *        per thread (one workgroup of 256 per chunk, float4 loads, thread t takes float4 t, t + 256, ...), then the
+ *        butterfly over the wave, then the four waves through LDS in wave order.  4 bytes per element.
+ *     2. one wave per variable: lane l adds S_k of the variable's chunks l, l + 64, ... in that order, then the
+ *        butterfly: S.   S not finite (an inf or a NaN in the variable): scale = NaN.   Otherwise n = sqrt(S) and
+ *            scale = (float)((double)c / n)  if n > c,  else exactly 1.0f
+ *        formed in fp64, rounded once.  scales[j] = scale;  norms[j] = (float)n  (inf or NaN where S is).
+ *     3. a workgroup reads its chunk's scale first.  Exactly 1.0f: the chunk is skipped -- no load, no store, the
+ *        gradient keeps its bits.  Otherwise g <- g*scale, one fp32 multiply per element (a NaN scale makes the whole
+ *        variable NaN, as tf.clip_by_norm does).
+ *   lisec_grad_clip_global_norm_partials   launch 1 over a chunk range: the sum of squares may be taken in parts (on
+ *        another stream, under the backward pass), each part into its own slots.
+ *   lisec_grad_clip_global_norm_finish     one workgroup of 256 adds ALL partials [0, table_chunks): thread t adds chunks
+ *        t, t + 256, ... in that order, then the butterfly over the wave, then the four waves through LDS in wave order
+ *        -- an order fixed by table_chunks alone.  scales[0] and norms[0] by the rule of 2.; then launch 3 over
+ *        [first_chunk, first_chunk + n_chunks) with scales[0] for every chunk.
+ * The pad floats of a variable, up to a multiple of 4, are inside its chunk as in every other table; they hold 0 in
+ * grad and add nothing.  No atomics anywhere: grad, scales and norms have the same bits from run to run.  Floats outside
+ * every chunk keep their bits.  Fixed addresses, no host reads, no allocation: every launch records into a step plan;
+ * the threshold is a kernel argument (a changed threshold is a new recording).  n_chunks == 0 is valid: nothing is
+ * enqueued (finish still stores scales[0] and norms[0]).  LISEC_EINVAL, nothing enqueued: a NULL pointer, grad not
+ * 16-byte aligned, workspace or chunks not 8-byte aligned, vars / scales / norms not 4-byte aligned, a negative first or
+ * count, norm: n_chunks == 0 with n_vars != 0 or the reverse, or n_vars > n_chunks; finish: first_chunk + n_chunks >
+ * table_chunks; workspace_bytes below lisec_grad_clip_workspace_bytes(first_chunk + n_chunks) (finish: of table_chunks);
+ * a threshold that is not a finite number > 0. */
+size_t lisec_grad_clip_workspace_bytes(int n_chunks);
+int lisec_grad_clip_value(float* grad, const lisec_lamb_chunk* chunks /* device */, int first_chunk, int n_chunks, float clip,
+                          lisec_stream_t stream);
+int lisec_grad_clip_norm(float* grad, const lisec_lamb_chunk* chunks /* device */, int first_chunk, int n_chunks,
+                         const lisec_lamb_var* vars /* device */, int first_var, int n_vars, float clip,
+                         float* scales /* device [>= first_var + n_vars] */, float* norms /* device, likewise */,
+                         void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+int lisec_grad_clip_global_norm_partials(const float* grad, const lisec_lamb_chunk* chunks /* device */, int first_chunk,
+                                         int n_chunks, void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+int lisec_grad_clip_global_norm_finish(float* grad, const lisec_lamb_chunk* chunks /* device */, int table_chunks,
+                                       int first_chunk, int n_chunks, float clip, float* scales /* device [>= 1] */,
+                                       float* norms /* device [>= 1] */, void* workspace, size_t workspace_bytes,
+                                       lisec_stream_t stream);
+
 /* BatchNormalization recalibration (LisecNet.recalibrate_batchnorm; csrc/bn_recalibrate.hip): the moving statistics of
  * every BatchNormalization layer are replaced by statistics of the CURRENT variables over K sweeps, as
  * torch.optim.swa_utils.update_bn does with momentum=None.  This project's own restatement (parity

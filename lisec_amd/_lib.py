@@ -466,6 +466,16 @@ def _declare(lib):
     lib.lisec_lamb_step_sched.restype = c_int
     lib.lisec_lamb_step_sched.argtypes = [P, P, P, P, P, c_int, c_int, P, c_int, c_int, P, P, c_size_t, P, c_float,
                                           c_float, c_float, c_float, P, c_int, P]
+    lib.lisec_grad_clip_workspace_bytes.restype = c_size_t
+    lib.lisec_grad_clip_workspace_bytes.argtypes = [c_int]
+    lib.lisec_grad_clip_value.restype = c_int
+    lib.lisec_grad_clip_value.argtypes = [P, P, c_int, c_int, c_float, P]
+    lib.lisec_grad_clip_norm.restype = c_int
+    lib.lisec_grad_clip_norm.argtypes = [P, P, c_int, c_int, P, c_int, c_int, c_float, P, P, P, c_size_t, P]
+    lib.lisec_grad_clip_global_norm_partials.restype = c_int
+    lib.lisec_grad_clip_global_norm_partials.argtypes = [P, P, c_int, c_int, P, c_size_t, P]
+    lib.lisec_grad_clip_global_norm_finish.restype = c_int
+    lib.lisec_grad_clip_global_norm_finish.argtypes = [P, P, c_int, c_int, c_int, c_float, P, P, P, c_size_t, P]
     lib.lisec_bn_recalibrate_coef.restype = c_double
     lib.lisec_bn_recalibrate_coef.argtypes = [c_int]
     lib.lisec_bn_recalibrate_take.restype = c_int

@@ -239,6 +239,9 @@ def _serialize_nested(x):
 # optimizer_config nests the wrapped optimizer's under "optimizer", their one slot kind follows the wrapped optimizer's
 WRAPPER_CLASSES = ("MovingAverage", "SWA")
 AVERAGE_KIND = "average"
+# the gradient-clipping keys of an optimizer dict and of its config (model_training.optimizers.clip_gradients): there
+# only when set, so a file without clipping has the bytes it always had; under a wrapper they sit in the nested config
+CLIP_KEYS = ("clipnorm", "clipvalue", "global_clipnorm")
 
 
 def written_class(optimizer):
@@ -266,6 +269,9 @@ def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrap
         oc["config"]["weight_decay"] = _rate(o.get("weight_decay", 0.0))          # only when given, the decayed variables
         if o.get("decay_var_list") is not None:
             oc["config"]["decay_var_list"] = list(o["decay_var_list"])
+    for k in CLIP_KEYS:                           # as in Keras, a clipping key is written only when it is set
+        if o.get(k) is not None:
+            oc["config"][k] = float(o[k])
     if wrapper is not None:
         c = dict(wrapper["config"])
         oc = {"class_name": wrapper["class_name"], "config": {"name": c.pop("name", wrapper["class_name"]),
@@ -484,6 +490,9 @@ def load_model(path, grid=None):
                     out["optimizer"].update(class_name=oc["class_name"], weight_decay=c.get("weight_decay", 0.0))
                     if c.get("decay_var_list") is not None:
                         out["optimizer"]["decay_var_list"] = list(c["decay_var_list"])
+                for k in CLIP_KEYS:
+                    if c.get(k) is not None:
+                        out["optimizer"][k] = float(c[k])
         if "optimizer_weights" in f:
             og = f["optimizer_weights"]
             slot_dataset = re.compile(r"([^/]+)/(.+)/(%s):0" % "|".join(optimizer_table.SLOT_KINDS + (AVERAGE_KIND,)))

@@ -26,8 +26,8 @@ import torch
 
 from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, ops, optimizer_table, regularizers
-from .network import (AverageSpec, DecaySpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep, loss_acc_len,
-                      loss_acc_logs, loss_acc_split)
+from .network import (AverageSpec, ClipSpec, DecaySpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep,
+                      loss_acc_len, loss_acc_logs, loss_acc_split)
 from .params import ParamStore, fold_depth, param_specs
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
@@ -247,14 +247,31 @@ class MaxPoolingVFELayer:
 
 
 # ---------------------------------------------------------------------------------------------------
+_CLIP_KINDS = {"clipnorm": "norm", "clipvalue": "value", "global_clipnorm": "global_norm"}      # attribute -> ClipSpec kind
+
+
 def _no_clipping(cls, kwargs):
-    """tf.keras optimizers take clipnorm / clipvalue / global_clipnorm: gradient clipping is not implemented here."""
-    clip = sorted(k for k in ("clipnorm", "clipvalue", "global_clipnorm") if kwargs.get(k) is not None)
+    """tf.keras optimizers take clipnorm / clipvalue / global_clipnorm as constructor keywords: those stay refused here.
+    Clipping is set on the constructed optimizer: the attributes of the same names, or optimizers.clip_gradients."""
+    clip = sorted(k for k in _CLIP_KINDS if kwargs.get(k) is not None)
     if clip:
-        raise NotImplementedError(f"{cls}: gradient clipping ({', '.join(clip)}) is not implemented")
-    rest = sorted(k for k in kwargs if k not in ("clipnorm", "clipvalue", "global_clipnorm"))
+        raise NotImplementedError(f"{cls}: gradient clipping ({', '.join(clip)}) is not implemented as a constructor "
+                                  f"keyword: use optimizers.clip_gradients(optimizer, ...) or assign the attribute")
+    rest = sorted(k for k in kwargs if k not in _CLIP_KINDS)
     if rest:
         raise TypeError(f"{cls}: unexpected keyword argument(s) {', '.join(rest)}")
+
+
+def _clip_spec(clipnorm, clipvalue, global_clipnorm):
+    """The ClipSpec of the three thresholds; None when all are None.  ValueError: more than one at once (tf.keras 2.4
+    takes clipvalue beside a norm; that combination is refused here), or a threshold that is not a finite number > 0."""
+    given = {k: v for k, v in (("clipnorm", clipnorm), ("clipvalue", clipvalue), ("global_clipnorm", global_clipnorm))
+             if v is not None}
+    if len(given) > 1:
+        raise ValueError(f"exactly one of clipnorm, clipvalue and global_clipnorm may be set, not {', '.join(given)}")
+    for key, value in given.items():
+        return ClipSpec(_CLIP_KINDS[key], value)
+    return None
 
 
 def _rate(lr):
@@ -270,11 +287,23 @@ def _serialize_rate(lr):
 class _Optimizer:
     """What the optimizers share: the attributes (lr, decay, name and the hyper-parameters of the class's record in
     lisec_amd/optimizer_table.py), spec() and get_config().  lr stays a plain attribute -- callbacks assign it between
-    epochs -- that spec() reads when it is called."""
+    epochs -- that spec() reads when it is called.  clipnorm, clipvalue and global_clipnorm are plain attributes too:
+    None after construction (the constructor keywords are refused), assignable afterwards or set by
+    optimizers.clip_gradients; spec() validates them, as they may have been assigned directly."""
+
+    clipnorm = clipvalue = global_clipnorm = None
 
     @property
     def record(self):
         return optimizer_table.BY_CLASS[optimizer_table.base_class(type(self).__name__)]
+
+    def clip_spec(self):
+        """The ClipSpec of the clipping attributes; None when none is set.  ValueError: _clip_spec's."""
+        return _clip_spec(self.clipnorm, self.clipvalue, self.global_clipnorm)
+
+    def _clip_config(self):
+        """The clipping keys of get_config(): as in Keras, a key is there only when its value is not None."""
+        return {k: getattr(self, k) for k in _CLIP_KINDS if getattr(self, k) is not None}
 
     def decay_spec(self):
         """The DecaySpec of the optimizer's decoupled weight decay; None for an optimizer without one."""
@@ -297,7 +326,7 @@ class _Optimizer:
         """device_lr: the kernels read the rate from the device descriptor even when it is a number (Model.fit with
         callbacks, which may change it between epochs)."""
         return OptimizerSpec(self.record.kind, self.lr, self.decay, device_lr=device_lr, weight_decay=self.decay_spec(),
-                             **self.hyper, **self.lists)
+                             clip=self.clip_spec(), **self.hyper, **self.lists)
 
     @property
     def lists(self):
@@ -306,7 +335,8 @@ class _Optimizer:
         return {name: getattr(self, name) for name in self.record.lists}
 
     def get_config(self):
-        return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper}
+        return {"name": self.name, "learning_rate": _serialize_rate(self.lr), "decay": self.decay, **self.hyper,
+                **self._clip_config()}
 
 
 class _DecoupledWeightDecay:
@@ -330,9 +360,11 @@ class _DecoupledWeightDecay:
 
     def get_config(self):
         config = super().get_config()
+        clip = {k: config.pop(k) for k in _CLIP_KINDS if k in config}        # (stay last, as a checkpoint writes them)
         config["weight_decay"] = _serialize_rate(self.weight_decay)
         if self.decay_var_list is not None:
             config["decay_var_list"] = list(self.decay_var_list)
+        config.update(clip)
         return config
 
 
@@ -356,6 +388,12 @@ class _AveragingOptimizer(_Optimizer):
     def record(self):
         return self._optimizer.record
 
+    # the clipping attributes are class attributes of _Optimizer, which __getattr__ below would never be asked for: they
+    # read through to the wrapped optimizer by name (assignments go there through __setattr__, like lr)
+    clipnorm = property(lambda self: self._optimizer.clipnorm)
+    clipvalue = property(lambda self: self._optimizer.clipvalue)
+    global_clipnorm = property(lambda self: self._optimizer.global_clipnorm)
+
     def __getattr__(self, attr):             # only reached for what the wrapper does not have itself
         if attr.startswith("_"):
             raise AttributeError(attr)
@@ -370,7 +408,7 @@ class _AveragingOptimizer(_Optimizer):
     def spec(self, device_lr=False):
         inner = self._optimizer
         return OptimizerSpec(inner.record.kind, inner.lr, inner.decay, device_lr=device_lr, average=self.average_spec(),
-                             weight_decay=inner.decay_spec(), **inner.hyper, **inner.lists)
+                             weight_decay=inner.decay_spec(), clip=inner.clip_spec(), **inner.hyper, **inner.lists)
 
     def decay_spec(self):
         return self._optimizer.decay_spec()
@@ -528,7 +566,7 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
             """tfa's keys in tfa's order: weight_decay_rate sits between learning_rate and decay."""
             return {"name": self.name, "learning_rate": _serialize_rate(self.lr),
                     "weight_decay_rate": self.weight_decay_rate, "decay": self.decay, "beta_1": self.beta_1,
-                    "beta_2": self.beta_2, "epsilon": self.epsilon, **self.lists}
+                    "beta_2": self.beta_2, "epsilon": self.epsilon, **self.lists, **self._clip_config()}
 
     _DECOUPLED = {SGD: SGDW, Adam: AdamW}       # base class -> its class with decoupled weight decay, made once
 
@@ -631,8 +669,14 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
         ValueError, naming the class, for one that is not implemented."""
         cls, c = config.get("class_name"), dict(config.get("config", {}))
         if cls in optimizers.WRAPPERS:
-            inner = optimizers.deserialize(c.pop("optimizer"))
+            inner = optimizers.deserialize(c.pop("optimizer"))       # (the clipping keys travel in the nested config)
             return getattr(optimizers, cls)(inner, **c)
+        clip = {k: c.get(k) for k in _CLIP_KINDS}
+        return optimizers.clip_gradients(optimizers._deserialize_plain(cls, c), **clip)
+
+    @staticmethod
+    def _deserialize_plain(cls, c):
+        """deserialize's optimizer of class `cls` from the config dict c, before its clipping keys are applied."""
         base = optimizer_table.base_class(cls)   # <Base>W: <Base> with decoupled weight decay
         rec = optimizer_table.BY_CLASS.get(base)
         if rec is None:
@@ -649,6 +693,26 @@ class optimizers:   # noqa: N801  (mirrors `from tensorflow.keras import optimiz
             wd = lr_schedules.deserialize(wd)
         return optimizers.extend_with_decoupled_weight_decay(getattr(optimizers, base))(
             wd, decay_var_list=c.get("decay_var_list"), **given)
+
+    @staticmethod
+    def clip_gradients(optimizer, clipnorm=None, clipvalue=None, global_clipnorm=None):
+        """Gradient clipping as tf.keras 2.4 defines it, in this project's restatement (parity unpinned), on
+        an optimizer object or one of the strings optimizers.get takes; returns the optimizer object, with the
+        attributes of the same names set (on a MovingAverage / SWA wrapper: the wrapped optimizer's).
+            clipvalue=c         every gradient element is clamped to [-c, c]
+            clipnorm=c          every variable's gradient is scaled so that its L2 norm is at most c
+            global_clipnorm=c   the whole gradient is scaled so that its L2 norm over all trainable variables is at most c
+        The clipped gradient is the regularised one (Keras' penalty sits in the tape) of the whole mini-batch, behind
+        the data-parallel average; a decoupled weight decay and LAMB's own act on the variable and are not clipped
+        (csrc/grad_clip.hip; include/lisec_hip.h has the arithmetic).  All three None clears the clipping.
+        ValueError: more than one threshold at once -- tf.keras 2.4 takes clipvalue beside a norm, this does not --, or
+        a threshold that is not a finite number > 0, finite in float32 (a bool is refused).  The constructor keywords
+        of the same names stay refused (NotImplementedError)."""
+        optimizer = optimizers.get(optimizer)
+        _clip_spec(clipnorm, clipvalue, global_clipnorm)                # every refusal, before anything is assigned
+        for key, value in (("clipnorm", clipnorm), ("clipvalue", clipvalue), ("global_clipnorm", global_clipnorm)):
+            setattr(optimizer, key, None if value is None else float(value))
+        return optimizer
 
     @staticmethod
     def get(identifier):
@@ -1357,7 +1421,8 @@ class Model:
                 opt.update(class_name=type(inner).__name__, weight_decay=_serialize_rate(inner.weight_decay))
                 if inner.decay_var_list is not None:
                     opt["decay_var_list"] = list(inner.decay_var_list)
-            if scalar is not None:                                 # Nadam's momentum_cache
+            opt.update(inner._clip_config())                       # (the clipping keys that are set; usually none)
+            if scalar is not None:                                # Nadam's momentum_cache
                 slots[scalar] = float(getattr(self.net, scalar).item())
             p = self.net.params
             for name in o.spec().slots:
@@ -1479,6 +1544,7 @@ def load_model(path, custom_objects=None):
                 wd = lr_schedules.deserialize(wd)
             opt = optimizers.extend_with_decoupled_weight_decay(getattr(optimizers, rec.class_name))(
                 wd, decay_var_list=o.get("decay_var_list"), **given)
+        optimizers.clip_gradients(opt, **{k: o.get(k) for k in _CLIP_KINDS})       # the clipping it was saved with
         w = ck.get("wrapper")
         if w is not None:
             if w["class_name"] not in optimizers.WRAPPERS:

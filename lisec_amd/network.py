@@ -162,6 +162,42 @@ class DecaySpec:
         return f"DecaySpec({self.weight_decay!r}, variables={self.variables!r})"
 
 
+class ClipSpec:
+    """The gradient clipping of a step (optimizers.clip_gradients; csrc/grad_clip.hip): behind the penalty pass and in
+    front of the decoupled weight decay and the optimizer entry, the gradient is bounded in place.
+    kind 'value': every element clamped to [-value, value]; 'norm': every variable scaled so that its L2 norm is at most
+    value; 'global_norm': the whole gradient scaled so that its L2 norm over all trainable variables is at most value.
+    value: a finite number > 0, finite in float32 (else ValueError; a bool is refused).  It is a kernel argument and
+    part of the config: a changed threshold is another recorded plan."""
+
+    KINDS = ("value", "norm", "global_norm")
+
+    def __init__(self, kind, value):
+        if kind not in self.KINDS:
+            raise ValueError(f"unknown clipping kind {kind!r}: one of {', '.join(self.KINDS)}")
+        try:
+            number = None if isinstance(value, bool) else float(value)
+        except (TypeError, ValueError):
+            number = None
+        if number is None or not 0 < number <= float(np.finfo(np.float32).max):       # (NaN fails both comparisons)
+            raise ValueError(f"a clipping threshold must be a finite number > 0 (finite in float32), not {value!r}")
+        self.kind, self.value = kind, number
+
+    @property
+    def config(self):
+        """Hashable; part of OptimizerSpec.config, the key of the recorded plans (the threshold is a launch argument)."""
+        return (self.kind, self.value)
+
+    def __eq__(self, other):
+        return isinstance(other, ClipSpec) and self.config == other.config
+
+    def __hash__(self):
+        return hash(self.config)
+
+    def __repr__(self):
+        return f"ClipSpec{self.config}"
+
+
 class OptimizerSpec:
     """One optimizer of the step: its kind, the tf.keras 2.4 hyper-parameters and the names of the slots it keeps --
     per-variable state buffers of LisecNet shaped like theta (LisecNet.slot).  The default is the reference's
@@ -188,20 +224,25 @@ class OptimizerSpec:
     kind "lamb" (layer-wise: csrc/lamb.hip) keeps "m" and "v", has weight_decay_rate -- its own decay, inside the
     step -- and the two lists exclude_from_weight_decay / exclude_from_layer_adaptation (None, or ParamStore names and /
     or kinds; the second None: the first), which enter `config` for this kind alone, behind the hyper-parameters; the
-    network that runs the step resolves them (ops.lamb_chunks).  A DecaySpec is refused."""
+    network that runs the step resolves them (ops.lamb_chunks).  A DecaySpec is refused.
+    clip: a ClipSpec, or None (no clipping: the step issues exactly the launches it always did, and `config` is the
+    tuple it always was)."""
 
     KINDS = tuple(optimizer_table.BY_KIND)
 
     def __init__(self, kind="sgd", lr=0.01, decay=1e-6, momentum=0.9, nesterov=True, beta_1=0.9, beta_2=0.999,
                  epsilon=None, amsgrad=False, device_lr=False, rho=0.9, centered=False, initial_accumulator_value=0.1,
                  average=None, weight_decay=None, weight_decay_rate=0.0, exclude_from_weight_decay=None,
-                 exclude_from_layer_adaptation=None):
+                 exclude_from_layer_adaptation=None, clip=None):
         rec = self.record = optimizer_table.BY_KIND.get(kind)
         if rec is None:
             raise ValueError(f"unknown optimizer kind {kind!r}")
         if average is not None and not isinstance(average, AverageSpec):
             raise ValueError(f"average must be an AverageSpec or None, not {average!r}")
         self.average = average
+        if clip is not None and not isinstance(clip, ClipSpec):
+            raise ValueError(f"clip must be a ClipSpec or None, not {clip!r}")
+        self.clip = clip
         if weight_decay is not None and not isinstance(weight_decay, DecaySpec):
             raise ValueError(f"weight_decay must be a DecaySpec or None, not {weight_decay!r}")
         self.weight_decay = None if weight_decay is None or weight_decay.is_zero else weight_decay
@@ -249,7 +290,7 @@ class OptimizerSpec:
         """Every hyper-parameter, hashable: two specs with equal configs issue the same launches.  A schedule enters with
         its whole Keras config; a number read from the device descriptor (device_lr) does not enter at all -- like the
         iteration count, it is data of the step, not of its launches.  The averaging joins only when there is one, and
-        so does the decoupled weight decay."""
+        so do the decoupled weight decay and the clipping."""
         if self.schedule is not None:
             rate = ("schedule", json.dumps(lr_schedules.serialize(self.schedule), sort_keys=True))
         elif self.device_lr:
@@ -261,6 +302,8 @@ class OptimizerSpec:
             base += (("average",) + self.average.config,)
         if self.weight_decay is not None:
             base += (("weight_decay",) + self.weight_decay.config,)
+        if self.clip is not None:
+            base += (("clip",) + self.clip.config,)
         return base
 
     @property
@@ -869,6 +912,11 @@ class LisecNet:
         # per-chunk workspace and the trust ratios of the last update, one per trainable variable
         self._lamb_tables = {}
         self._lamb_ws = self._lamb_ratios = None
+        # gradient clipping (OptimizerSpec.clip; csrc/grad_clip.hip): the table of every trainable variable (LAMB's
+        # records, no exclusions), the per-chunk workspace, and the scales and norms of the last update, one per
+        # variable (the global norm: slot 0), all made with the first clipped update and kept for the net's life;
+        # _clip_kind is the kind of the last update that left norms ('norm' / 'global_norm'), for gradient_norms()
+        self._clip_table = self._clip_ws = self._clip_scales = self._clip_norms = self._clip_kind = None
         # BatchNormalization recalibration (recalibrate_batchnorm; csrc/bn_recalibrate.hip): the table of the layers'
         # moving statistics and the fp64 accumulator, made when first used (bn_recal_table)
         self._bn_recal = None
@@ -1555,8 +1603,11 @@ class LisecNet:
         its share of the penalty already); the call that ends the step folds the penalty into loss_out[0].  With a
         decoupled weight decay the decay pass follows it and the optimizer entry updates the decayed variables: the
         gradient term and the penalty are taken on the weights BEFORE the decay, as the regularization loss of Keras sits
-        in the tape and tfa's decay follows it."""
+        in the tape and tfa's decay follows it.  With clipping (opt.clip) the clip passes sit between the two: the
+        regularised gradient is what is bounded, as Keras' penalty gradient is clipped with the rest, and the decay acts
+        on the variable, not on the gradient."""
         self._regularize(lo, hi, accumulate=second, fold=advance)
+        self._clip(opt, lo, hi)
         self._decay(opt, lo, hi)
         rec = opt.record
         entry, names, args = opt.launch
@@ -1580,6 +1631,56 @@ class LisecNet:
             bufs.append(getattr(self, rec.scalar))
         getattr(ops, entry)(self.params.theta[cut], self.grad[cut], *bufs, *rate, *(getattr(opt, a) for a in args),
                             self._iter_dev, advance=advance, **rows)
+
+    def clip_table(self):
+        """The ops.LambTable of the clipping passes (ops.clip_chunks: every trainable variable), made once together
+        with the workspace and the scale and norm buffers."""
+        if self._clip_table is None:
+            table = ops.lamb_table(*ops.clip_chunks(self.params), self.device)
+            self._clip_ws = ops.clip_workspace(table.n_chunks, self.device)
+            self._clip_scales = torch.ones(max(table.n_vars, 1), dtype=torch.float32, device=self.device)
+            self._clip_norms = torch.zeros(max(table.n_vars, 1), dtype=torch.float32, device=self.device)
+            self._clip_table = table
+            torch.cuda.synchronize(self.device)   # whole before any stream of the step (the second one included) uses them
+        return self._clip_table
+
+    def _clip(self, opt, lo, hi):
+        """The gradient clipping of the variables in theta[lo:hi] (lo, hi: variable boundaries), on the current stream,
+        in place in net.grad.  'value' and 'norm' are per element or per variable: each part of a split update clips the
+        variables of its own range, with slots of their own.  'global_norm' needs every gradient, so it only ever runs
+        over everything (early_update makes no update with such a spec).  Nothing at all for a spec without clipping."""
+        clip = opt.clip
+        if clip is None:
+            return
+        table = self.clip_table()
+        first, n_chunks = table.chunks.span(lo, hi)
+        self._clip_kind = clip.kind
+        if clip.kind == "value":
+            ops.grad_clip_value(self.grad, clip.value, table=table, first=first, n_chunks=n_chunks)
+            return
+        bufs = dict(table=table, scales=self._clip_scales, norms=self._clip_norms, workspace=self._clip_ws)
+        if clip.kind == "norm":
+            first_var, n_vars = table.variables.span(lo, hi)
+            ops.grad_clip_norm(self.grad, clip.value, first=first, n_chunks=n_chunks, first_var=first_var, n_vars=n_vars,
+                               **bufs)
+        else:
+            if (first, n_chunks) != (0, table.n_chunks):
+                raise RuntimeError("global_clipnorm needs the gradient of every variable: the update cannot be split")
+            ops.grad_clip_global_norm(self.grad, clip.value, **bufs)
+
+    def gradient_norms(self):
+        """The L2 norms the last clipped update measured, before clipping: {variable name: norm} of every trainable
+        variable for clipnorm, {'global': norm} for global_clipnorm (the regularised gradient where the net has
+        regularizers).  One device-to-host copy behind everything enqueued so far; never made during a step.
+        RuntimeError before the first clipped update, and when the last one clipped by value: it measures no norm.
+        The counterpart of trust_ratios()."""
+        if self._clip_kind not in ("norm", "global_norm"):
+            raise RuntimeError("gradient_norms(): the last update did not clip by clipnorm or global_clipnorm")
+        torch.cuda.current_stream().wait_stream(self.side)
+        norms = self._clip_norms.cpu().tolist()
+        if self._clip_kind == "global_norm":
+            return {"global": norms[0]}
+        return dict(zip(self._clip_table.names, norms))
 
     def lamb_table(self, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None):
         """The ops.LambTable of a layer-wise optimizer with these exclusion lists (ops.lamb_chunks), made once per pair;
@@ -1615,12 +1716,16 @@ class LisecNet:
         updates an element -- for every optimizer of OptimizerSpec, as both calls read the same iteration count: this one
         on the second stream, which the main stream joins before apply_gradients() updates theta[:lo] and advances the
         count.  The update stays pending until that apply_gradients(), which must be given the same spec; a second early
-        update before it raises RuntimeError."""
+        update before it raises RuntimeError.  A spec that clips by the GLOBAL norm needs every gradient before any
+        variable moves: with it this call makes no update and leaves nothing pending, and apply_gradients() updates
+        everything in one part behind the backward pass."""
         if self._early is not None:
             raise RuntimeError("early_update() while an early update is pending: apply_gradients() ends the step first")
         if lo % 4 or hi != self.params.n_theta:
             return
         opt = OptimizerSpec() if opt is None else opt
+        if opt.clip is not None and opt.clip.kind == "global_norm":
+            return
         if opt.average is not None:
             self.average                         # started from theta BEFORE any part of it is updated
         self._update(opt, lo, lo + (hi - lo) // 4 * 4, advance=False)
@@ -1634,7 +1739,10 @@ class LisecNet:
         update, so after a step net.grad holds the REGULARISED gradient and loss_out[0] includes the penalty, which
         reg_penalty holds on its own.  backward() alone leaves the plain gradient, except in the slots it never writes
         (unwritten_grads: the conv biases in front of a training-mode BatchNormalization, whose gradient is identically
-        0): those keep the term the last update stored, which the next update replaces, never adds to."""
+        0): those keep the term the last update stored, which the next update replaces, never adds to.
+        A spec with clipping (opt.clip): the clip passes run behind the penalty pass and in front of the decay and the
+        update, in place, so after a step net.grad holds the CLIPPED gradient (regularised where the net has
+        regularizers), and gradient_norms() the norms measured before clipping."""
         opt = OptimizerSpec() if opt is None else opt
         hi = self.params.theta.numel()
         second = self._early is not None

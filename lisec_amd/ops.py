@@ -903,6 +903,73 @@ def lamb_step_sched(theta, grad, m, v, dev_desc, weight_decay_rate, beta_1, beta
                                                  1 if advance else 0, _lib.current_stream()))
 
 
+def clip_chunks(params):
+    """The tables of lisec_grad_clip_* as host lists: lamb_chunks without exclusions -- every trainable variable, cut by
+    variable_chunks, each chunk with its variable's index (the flags are ignored by the clipping passes).  They become
+    device tables through lamb_table.  Pure host arithmetic."""
+    return lamb_chunks(params)
+
+
+def clip_workspace(n_chunks, device):
+    """The workspace of lisec_grad_clip_norm / _global_norm_* for a table of n_chunks chunks (uint8 tensor)."""
+    return torch.empty(_lib.load().lisec_grad_clip_workspace_bytes(int(n_chunks)), dtype=torch.uint8, device=device)
+
+
+def _clip_chunk_range(table, first, n_chunks):
+    n_chunks = table.n_chunks - first if n_chunks is None else int(n_chunks)
+    table.chunks.at(first, n_chunks, "grad_clip chunks")
+    return int(first), n_chunks
+
+
+def grad_clip_value(grad, clip, *, table, first=0, n_chunks=None):
+    """g <- min(max(g, -clip), clip) where g is ordered, a NaN keeps its bits (lisec_grad_clip_value) over chunks [first,
+    first + n_chunks) of `table` (lamb_table of clip_chunks; None: to the end).  grad is the WHOLE buffer the table's
+    offsets count from."""
+    first, n_chunks = _clip_chunk_range(table, first, n_chunks)
+    _lib.check(_lib.load().lisec_grad_clip_value(_lib.ptr(grad), _lib.ptr(table.chunks), first, n_chunks, float(clip),
+                                                 _lib.current_stream()))
+
+
+def grad_clip_norm(grad, clip, *, table, scales, norms, workspace, first=0, n_chunks=None, first_var=0, n_vars=None):
+    """Every variable of the range scaled so that its L2 norm is at most clip (lisec_grad_clip_norm) over chunks [first,
+    first + n_chunks) and variables [first_var, first_var + n_vars) of `table` (None: to the end; the chunks must be
+    those of the variables).  scales / norms (float32 device tensors, one per variable of the table) receive each
+    variable's scale and norm; workspace: clip_workspace."""
+    first, n_chunks, first_var, n_vars = _lamb_range(table, scales, first, n_chunks, first_var, n_vars)
+    if first_var + n_vars > norms.numel():
+        raise ValueError(f"grad_clip_norm: variables [{first_var}, {first_var + n_vars}) with {norms.numel()} norms")
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_grad_clip_norm(P(grad), P(table.chunks), first, n_chunks, P(table.variables), first_var,
+                                                n_vars, float(clip), P(scales), P(norms), P(workspace), workspace.numel(),
+                                                _lib.current_stream()))
+
+
+def grad_clip_global_norm_partials(grad, *, table, workspace, first=0, n_chunks=None):
+    """The per-chunk sums of squares of chunks [first, first + n_chunks) into their slots of the workspace
+    (lisec_grad_clip_global_norm_partials): a part of the global norm, ahead of grad_clip_global_norm_finish."""
+    first, n_chunks = _clip_chunk_range(table, first, n_chunks)
+    _lib.check(_lib.load().lisec_grad_clip_global_norm_partials(_lib.ptr(grad), _lib.ptr(table.chunks), first, n_chunks,
+                                                                _lib.ptr(workspace), workspace.numel(),
+                                                                _lib.current_stream()))
+
+
+def grad_clip_global_norm_finish(grad, clip, *, table, scales, norms, workspace, first=0, n_chunks=None):
+    """Adds the partials of ALL chunks of `table`, stores scales[0] / norms[0] and scales chunks [first, first + n_chunks)
+    (None: to the end) by scales[0] (lisec_grad_clip_global_norm_finish)."""
+    first, n_chunks = _clip_chunk_range(table, first, n_chunks)
+    P = _lib.ptr
+    _lib.check(_lib.load().lisec_grad_clip_global_norm_finish(P(grad), P(table.chunks), table.n_chunks, first, n_chunks,
+                                                              float(clip), P(scales), P(norms), P(workspace),
+                                                              workspace.numel(), _lib.current_stream()))
+
+
+def grad_clip_global_norm(grad, clip, *, table, scales, norms, workspace):
+    """The whole gradient scaled so that its L2 norm over every variable of `table` is at most clip: the partials of
+    every chunk, then grad_clip_global_norm_finish over every chunk."""
+    grad_clip_global_norm_partials(grad, table=table, workspace=workspace)
+    grad_clip_global_norm_finish(grad, clip, table=table, scales=scales, norms=norms, workspace=workspace)
+
+
 BN_STATISTICS = {"mean": _lib.BN_STATS_MEAN, "pooled": _lib.BN_STATS_POOLED}     # the rules of bn_recalibrate_finish
 VFE_BN_LAYERS = ("vfe1.bn", "vfe2.bn", "fcn.bn")      # finalised by the VFE kernel; every other layer by a conv sink
 
