@@ -1147,9 +1147,9 @@ int lisec_weight_decay_eval(const lisec_lr_schedule* coeff /* device */, const l
  *     pass 2       step = r*lr_t;  e = step*u;  w <- w - e
  * Pass 1 writes m and v and keeps u in registers; pass 2 forms u again from the stored m, v and the unchanged w by the
  * same operations, hence with the same bits.  Between them, per variable, in fp64:
- *     S_w = sum w*w,  S_u = sum u*u     per thread, then wave, then workgroup: one pair of partials per chunk; the
- *                                       chunk partials of a variable are added by one wave (lane l: chunks l, l + 64,
- *                                       ... in that order, then a butterfly) -- an order fixed by the table alone
+ *     S_w = sum w*w,  S_u = sum u*u     per thread, then over the workgroup: one pair of partials per chunk; the
+ *                                       chunk partials of a variable are added by one wave -- orders W and V of
+ *                                       csrc/reduce.h, fixed by the table alone
  *     r = (float)(sqrt(S_w) / sqrt(S_u))   if the variable is ADAPTED and S_w > 0 and S_u > 0, else exactly 1.0f
  * No atomics other than the iteration ticket: theta, m, v and ratios have the same bits from run to run.  grad is only
  * read.  Floats outside every chunk keep their bits in theta, m and v.  advance as for the other entries: 0 leaves the
@@ -1202,10 +1202,10 @@ int lisec_lamb_step_sched(float* theta, const float* grad, float* m, float* v, c
  *                            denormal.  +-inf become +-c.  One launch, 8 bytes of traffic per element.
  *   lisec_grad_clip_norm     three launches ordered by the stream alone:
  *     1. S_k = sum over chunk k of (double)g*(double)g: the product exact, each addition an fp64 operation of its own,
- *        per thread (one workgroup of 256 per chunk, float4 loads, thread t takes float4 t, t + 256, ...), then the
- *        butterfly over the wave, then the four waves through LDS in wave order.  4 bytes per element.
- *     2. one wave per variable: lane l adds S_k of the variable's chunks l, l + 64, ... in that order, then the
- *        butterfly: S.   S not finite (an inf or a NaN in the variable): scale = NaN.   Otherwise n = sqrt(S) and
+ *        per thread (one workgroup of 256 per chunk, float4 loads, thread t takes float4 t, t + 256, ...), then over
+ *        the workgroup in order W of csrc/reduce.h.  4 bytes per element.
+ *     2. one wave per variable: S_k of the variable's chunks in order V of csrc/reduce.h: S.   S not finite (an inf or
+ *        a NaN in the variable): scale = NaN.   Otherwise n = sqrt(S) and
  *            scale = (float)((double)c / n)  if n > c,  else exactly 1.0f
  *        formed in fp64, rounded once.  scales[j] = scale;  norms[j] = (float)n  (inf or NaN where S is).
  *     3. a workgroup reads its chunk's scale first.  Exactly 1.0f: the chunk is skipped -- no load, no store, the
@@ -1213,9 +1213,9 @@ int lisec_lamb_step_sched(float* theta, const float* grad, float* m, float* v, c
  *        variable NaN, as tf.clip_by_norm does).
  *   lisec_grad_clip_global_norm_partials   launch 1 over a chunk range: the sum of squares may be taken in parts (on
  *        another stream, under the backward pass), each part into its own slots.
- *   lisec_grad_clip_global_norm_finish     one workgroup of 256 adds ALL partials [0, table_chunks): thread t adds chunks
- *        t, t + 256, ... in that order, then the butterfly over the wave, then the four waves through LDS in wave order
- *        -- an order fixed by table_chunks alone.  scales[0] and norms[0] by the rule of 2.; then launch 3 over
+ *   lisec_grad_clip_global_norm_finish     one workgroup of 256 adds ALL partials [0, table_chunks): the strided sums
+ *        of order T, then order W over the 256 (csrc/reduce.h) -- an order fixed by table_chunks alone.  scales[0] and
+ *        norms[0] by the rule of 2.; then launch 3 over
  *        [first_chunk, first_chunk + n_chunks) with scales[0] for every chunk.
  * The pad floats of a variable, up to a multiple of 4, are inside its chunk as in every other table; they hold 0 in
  * grad and add nothing.  No atomics anywhere: grad, scales and norms have the same bits from run to run.  Floats outside

@@ -76,6 +76,14 @@ int rpn_labels_counted(const lisec_rpn_cfg* cfg, const double* fixed_boxes, int 
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
+// The grid of a grid-stride launch: ceil(n / threads) workgroups, at least 1 and at most `cap` (beyond, each strides on).
+// A launch of one workgroup per table row passes threads = 1.  The caps stay with their kernels, and their reasons.
+inline int grid_blocks(long long n, int threads, int cap) {
+    const long long b = (n + threads - 1) / threads;
+    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 
 // Bump allocator over a caller-provided workspace (all carve-outs 256 B aligned).
 struct Carver {

@@ -251,8 +251,6 @@ k_eval_integrate(const int64_t* __restrict__ rank, const uint8_t* __restrict__ s
     }
 }
 
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace lisec
 

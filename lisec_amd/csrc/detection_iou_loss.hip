@@ -14,7 +14,8 @@
 // The gradient needs no differentiation through the clipping: d area(P n G)/d theta is the integral of the normal velocity
 // of P's boundary over the parts of it inside G.  Each edge of P meets the convex G in one interval (the edge clipped against
 // G's four half-planes, in G's frame) and the velocity is linear along an edge, so midpoint times length is exact.
-// No atomics, a fixed partition, every address fixed, nothing read back: the house rules of detection_loss.hip.
+// No atomics, a fixed partition (order W of reduce.h), every address fixed, nothing read back: the house rules of
+// detection_loss.hip.
 // 256 threads per workgroup; for k_det_iou the compiler reports 164 VGPRs (3 waves per SIMD), 464 bytes of scratch per lane
 // (the clipping buffers of quad_intersection_area) and 16 KiB of LDS (a per-thread array it moves there, and 32 bytes of
 // partials): at 40 000 anchors that is 157 workgroups, under one per compute unit, and the launch is bound by its latency.
@@ -130,7 +131,7 @@ __global__ void __launch_bounds__(kIouThreads)
 k_det_iou(lisec_detection_iou_loss_cfg cfg, const float* __restrict__ head, const float* __restrict__ ycls,
           const float* __restrict__ yreg, long long M, float gscale, const long long* __restrict__ counts,
           float* __restrict__ dhead, double* __restrict__ parts) {
-    __shared__ double red[kIouThreads / 64];
+    __shared__ double red[1][kIouThreads / 64];
     const long long cp = counts[0];
     const double npos = cp > 0 ? (double)cp : 1.0;
     const double wreg = (double)gscale * cfg.det.weight[1] / npos;     // k_det_loss's
@@ -160,19 +161,11 @@ k_det_iou(lisec_detection_iou_loss_cfg cfg, const float* __restrict__ head, cons
             }
         }
     }
-    sum = wave_sum(sum);
-    if (lane_id() == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < kIouThreads / 64; ++w) s += red[w];
-        parts[(size_t)blockIdx.x * kDetVals + 2] += iw * s;   // this workgroup alone writes the word, after k_det_loss
-    }
-}
-
-int iou_blocks(long long M) {
-    const long long b = (M * 2 + kIouThreads - 1) / kIouThreads;
-    return (int)(b < 1 ? 1 : (b > kIouBlocks ? kIouBlocks : b));
+    const double v[1] = {sum};
+    double s[1];
+    block_sums_all<kIouThreads>(v, red, s);
+    // this workgroup alone writes the word, after k_det_loss
+    if (threadIdx.x == 0) parts[(size_t)blockIdx.x * kDetVals + 2] += iw * s[0];
 }
 
 int check_iou(const lisec_detection_iou_loss_cfg* cfg, long long M, const void* workspace, size_t workspace_bytes) {
@@ -202,12 +195,12 @@ int run_iou(const lisec_detection_iou_loss_cfg& cfg, const float* head, const fl
     Carver ws(workspace);
     long long* counts = ws.take<long long>(2);
     double* parts = ws.take<double>((size_t)kDetBlocks * kDetVals);
-    const int nb = det_blocks(M);
+    const int nb = grid_blocks(M * 16, kDetThreads, kDetBlocks);
     LISEC_LAUNCH(k_det_count, dim3(1), dim3(kCountThreads), 0, st, y_cls, M * 2, counts, counts_out);
     LISEC_LAUNCH(k_det_loss, dim3(nb), dim3(kDetThreads), 0, st, cfg.det, head, y_cls, y_reg, M, grad_scale, counts, dhead,
                  parts);
-    LISEC_LAUNCH(k_det_iou, dim3(iou_blocks(M)), dim3(kIouThreads), 0, st, cfg, head, y_cls, y_reg, M, grad_scale, counts,
-                 dhead, parts);
+    LISEC_LAUNCH(k_det_iou, dim3(grid_blocks(M * 2, kIouThreads, kIouBlocks)), dim3(kIouThreads), 0, st, cfg, head, y_cls,
+                 y_reg, M, grad_scale, counts, dhead, parts);
     LISEC_LAUNCH(k_det_finalize, dim3(1), dim3(256), 0, st, cfg.det, parts, nb, counts, loss_out, acc);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;

@@ -13,7 +13,7 @@ int run_det(const lisec_detection_loss_cfg& cfg, const float* head, const float*
     Carver ws(workspace);
     long long* counts = ws.take<long long>(2);
     double* parts = ws.take<double>((size_t)kDetBlocks * kDetVals);
-    const int nb = det_blocks(M);
+    const int nb = grid_blocks(M * 16, kDetThreads, kDetBlocks);
     LISEC_LAUNCH(k_det_count, dim3(1), dim3(kCountThreads), 0, st, y_cls, M * 2, counts, counts_out);
     LISEC_LAUNCH(k_det_loss, dim3(nb), dim3(kDetThreads), 0, st, cfg, head, y_cls, y_reg, M, grad_scale, counts, dhead, parts);
     LISEC_LAUNCH(k_det_finalize, dim3(1), dim3(256), 0, st, cfg, parts, nb, counts, loss_out, acc);

@@ -4,11 +4,11 @@
 //   k_det_loss      the element layout of k_head_loss (csrc/losses.hip): thread i holds element i of the flat head; every
 //                   element in double from the fp32 inputs, the gradient rounded once; per-workgroup fp64 partials of
 //                   {sum_pos class, sum_neg class, sum_pos regression}, not yet normalised
-//   k_det_finalize  one workgroup: the partials summed in index order, normalised by the counts
-// No atomics and a fixed partition: the same bits on every run.  Every address is fixed and nothing is read back: the
-// launches record into a step plan as they are.
+//   k_det_finalize  one workgroup: the partials summed, normalised by the counts
+// The count and the partials are order W of reduce.h, the finalize is order T: no atomics and a fixed partition.  Every
+// address is fixed and nothing is read back: the launches record into a step plan as they are.
 #pragma once
-#include "common.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -42,16 +42,9 @@ k_det_count(const float* __restrict__ ycls, long long n, long long* __restrict__
             nn += is_neg(c[u]) ? 1 : 0;
         }
     }
-    np = wave_sum(np);
-    nn = wave_sum(nn);
-    if (lane_id() == 0) {
-        red[0][threadIdx.x >> 6] = np;
-        red[1][threadIdx.x >> 6] = nn;
-    }
-    __syncthreads();
+    const long long v[2] = {np, nn};
+    const long long a = block_sum_own<kCountThreads>(v, red);
     if (threadIdx.x < 2) {
-        long long a = 0;
-        for (int w = 0; w < kCountThreads / 64; ++w) a += red[threadIdx.x][w];
         counts[threadIdx.x] = a;
         if (counts_out) counts_out[threadIdx.x] = a;
     }
@@ -120,18 +113,9 @@ k_det_loss(lisec_detection_loss_cfg cfg, const float* __restrict__ head, const f
         }
         if (grad) dhead[i] = gout;
     }
-    double v[kDetVals] = {spos, sneg, sreg};
-#pragma unroll
-    for (int k = 0; k < kDetVals; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kDetVals) {
-        double a = 0.0;
-        for (int w = 0; w < kDetThreads / 64; ++w) a += red[threadIdx.x][w];
-        parts[(size_t)blockIdx.x * kDetVals + threadIdx.x] = a;
-    }
+    const double v[kDetVals] = {spos, sneg, sreg};
+    const double a = block_sum_own<kDetThreads>(v, red);
+    if (threadIdx.x < kDetVals) parts[(size_t)blockIdx.x * kDetVals + threadIdx.x] = a;
 }
 
 // Training (acc == nullptr): loss_out[3]; evaluation: the same fp32 values added, as doubles, to acc, the sweep counted.
@@ -139,21 +123,9 @@ __global__ void __launch_bounds__(256)
 k_det_finalize(lisec_detection_loss_cfg cfg, const double* __restrict__ parts, int nparts,
                const long long* __restrict__ counts, float* __restrict__ loss_out, double* __restrict__ acc) {
     __shared__ double red[kDetVals][256];
-    double a[kDetVals] = {0.0, 0.0, 0.0};
-    for (int p = threadIdx.x; p < nparts; p += 256) {
-#pragma unroll
-        for (int k = 0; k < kDetVals; ++k) a[k] += parts[(size_t)p * kDetVals + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kDetVals; ++k) red[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int k = 0; k < kDetVals; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    double a[kDetVals];
+    strided_sums<256>(parts, nparts, a);
+    tree_sums<256>(a, red);
     if (threadIdx.x != 0) return;
     const long long cp = counts[0], cn = counts[1];
     const double npos = cp > 0 ? (double)cp : 1.0, nneg = cn > 0 ? (double)cn : 1.0;
@@ -164,11 +136,6 @@ k_det_finalize(lisec_detection_loss_cfg cfg, const double* __restrict__ parts, i
     } else {
         loss_out[0] = tot; loss_out[1] = fc; loss_out[2] = fr;
     }
-}
-
-int det_blocks(long long M) {
-    const long long b = (M * 16 + kDetThreads - 1) / kDetThreads;
-    return (int)(b < 1 ? 1 : (b > kDetBlocks ? kDetBlocks : b));
 }
 
 int check_det(const lisec_detection_loss_cfg* cfg, long long M, const void* workspace, size_t workspace_bytes) {

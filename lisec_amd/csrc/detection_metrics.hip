@@ -6,8 +6,8 @@
 //                    both boxes share, and pair_iou (box_geom.h); everything in double from the fp32 inputs; per-workgroup
 //                    fp64 partials of the 2 * n_metrics sums
 //   k_detm_finalize  one workgroup: the partials summed in index order, stored to out or added to it
-// No atomics and a fixed partition, the house rules of detection_loss.hip: the same bits on every run, every address fixed,
-// nothing read back, so the launches record into a step plan as they are.
+// No atomics and a fixed partition (k_detm_anchors: order W of reduce.h; the finalize has a strand order of its own), the
+// house rules of detection_loss.hip: every address fixed, nothing read back, so the launches record into a step plan.
 // Positives are ~1 % of the anchors, so the clipping branch is rare and divergent: a wave that holds one positive pays for
 // it alone.  At 40 000 anchors (the Lyft grid) that is 157 workgroups of 4 waves, under one per compute unit, and the launch
 // is bound by its latency, not by the lanes idle in the branch; no compaction pass is worth a third launch.  256 threads,
@@ -15,6 +15,7 @@
 // buffers of quad_intersection_area and 16.5 KiB of LDS (a per-thread array it moves there, and 512 bytes of partials) -- one
 // workgroup per compute unit fits with room to spare, and that is all this launch asks for.
 #include "box_geom.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -99,20 +100,14 @@ k_detm_anchors(lisec_detection_metrics_cfg cfg, const float* __restrict__ head, 
             }
         }
     }
+    double v[kDetmVals];
 #pragma unroll
     for (int i = 0; i < LISEC_DET_MAX_METRICS; ++i) {
-        const double sn = wave_sum(num[i]), sd = wave_sum(den[i]);
-        if (lane_id() == 0) {
-            red[2 * i][threadIdx.x >> 6] = sn;
-            red[2 * i + 1][threadIdx.x >> 6] = sd;
-        }
+        v[2 * i] = num[i];
+        v[2 * i + 1] = den[i];
     }
-    __syncthreads();
-    if (threadIdx.x < kDetmVals) {
-        double s = 0.0;
-        for (int w = 0; w < kDetmThreads / 64; ++w) s += red[threadIdx.x][w];
-        parts[(size_t)blockIdx.x * kDetmVals + threadIdx.x] = s;
-    }
+    const double s = block_sum_own<kDetmThreads>(v, red);
+    if (threadIdx.x < kDetmVals) parts[(size_t)blockIdx.x * kDetmVals + threadIdx.x] = s;
 }
 
 // thread t sums value t & 15 over the workgroups (t >> 4) + 16 i in index order; 16 threads then add the 16 strands in order
@@ -128,11 +123,6 @@ k_detm_finalize(const double* __restrict__ parts, int nparts, int nvals, double*
     double total = 0.0;
     for (int k = 0; k < 16; ++k) total += red[threadIdx.x][k];
     out[threadIdx.x] = accumulate ? out[threadIdx.x] + total : total;
-}
-
-int detm_blocks(long long M) {
-    const long long b = (M * 2 + kDetmThreads - 1) / kDetmThreads;
-    return (int)(b < 1 ? 1 : (b > kDetmBlocks ? kDetmBlocks : b));
 }
 
 }  // namespace
@@ -174,7 +164,7 @@ extern "C" int lisec_detection_metrics(const lisec_detection_metrics_cfg* cfg, c
                     lisec_detection_metrics_workspace_bytes());
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* parts = static_cast<double*>(workspace);
-    const int nb = detm_blocks(M);
+    const int nb = grid_blocks(M * 2, kDetmThreads, kDetmBlocks);
     LISEC_LAUNCH(k_detm_anchors, dim3(nb), dim3(kDetmThreads), 0, st, *cfg, head, y_cls, y_reg, M, parts);
     LISEC_LAUNCH(k_detm_finalize, dim3(1), dim3(256), 0, st, parts, nb, 2 * cfg->n_metrics, out, accumulate);
     LISEC_LAUNCH_CHECK();

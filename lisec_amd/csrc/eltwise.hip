@@ -3,6 +3,7 @@
 // All are streaming kernels: 16-byte accesses, coalesced along the channel axis, reductions as
 // per-block partials summed in index order (deterministic; no float atomics).
 #include "bn.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -127,6 +128,10 @@ k_colsum(const float* __restrict__ x, int stride, long long M, int C, double* __
 // kind 0: 'mse' + 'mse' (model_training.py:296): loss = mean((cls-yc)^2) + mean((reg-yr)^2)
 // kind 1: sigmoid cross-entropy on the class map (targets clipped to [0,1]) + SmoothL1 (delta 1) on the
 //         regression map, both as means (BASELINE config 4)
+// GRAD: the training entry, which also stores dhead.  Without it (Model.evaluate, fit's validation; dhead and gscale are
+// not read) the per-element losses, the block partition and the partials are the same, so the fp32 values of a sweep are
+// the bits lisec_rpn_loss writes to loss_out.  A compile-time flag: the training step's kernel has no branch on it.
+template <bool GRAD>
 __global__ void __launch_bounds__(kEwThreads)
 k_loss(const float* __restrict__ head, const float* __restrict__ ycls, const float* __restrict__ yreg,
        long long M, int kind, float gscale, float* __restrict__ dhead, double* __restrict__ parts) {
@@ -162,93 +167,29 @@ k_loss(const float* __restrict__ head, const float* __restrict__ ycls, const flo
                 g = (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wr;
             }
         }
-        dhead[i] = g;
+        if (GRAD) dhead[i] = g;
     }
-    lc = wave_sum(lc); lr = wave_sum(lr);
-    if (lane_id() == 0) { red[0][threadIdx.x >> 6] = lc; red[1][threadIdx.x >> 6] = lr; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double a = 0.0;
-        for (int k = 0; k < kEwThreads / 64; ++k) a += red[threadIdx.x][k];
-        parts[(size_t)blockIdx.x * 2 + threadIdx.x] = a;
-    }
+    const double v[2] = {lc, lr};
+    const double a = block_sum_own<kEwThreads>(v, red);                    // order W of reduce.h
+    if (threadIdx.x < 2) parts[(size_t)blockIdx.x * 2 + threadIdx.x] = a;
 }
 
+// Order T of reduce.h over the partials.  Training (acc == nullptr): loss_out[3]; evaluation: the same fp32
+// [total, class, regression] added, as doubles, to acc[0..2] and the sweep counted in acc[3] by the single finalizing
+// thread: stream-ordered, no atomics, the same bits on every run.
 __global__ void __launch_bounds__(256)
-k_loss_finalize(const double* __restrict__ parts, int nparts, double M, float* __restrict__ out) {
+k_loss_finalize(const double* __restrict__ parts, int nparts, double M, float* __restrict__ out, double* __restrict__ acc) {
     __shared__ double red[2][256];
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += 256) { a += parts[2 * k]; b += parts[2 * k + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a = red[0][0] / (M * 2.0); b = red[1][0] / (M * 14.0);
-        out[0] = (float)(a + b); out[1] = (float)a; out[2] = (float)b;
-    }
-}
-
-// Evaluation loss (Model.evaluate, fit's validation): k_loss's per-element losses, block partition and partials without
-// the gradient store, then k_loss_finalize's reduction order, so the fp32 [total, class, regression] of a sweep are the
-// bits lisec_rpn_loss writes to loss_out.  They are added, as doubles, to acc[0..2] and the sweep is counted in acc[3]
-// by the single finalizing thread: stream-ordered, no atomics, the same bits on every run.
-__global__ void __launch_bounds__(kEwThreads)
-k_loss_eval(const float* __restrict__ head, const float* __restrict__ ycls, const float* __restrict__ yreg,
-            long long M, int kind, double* __restrict__ parts) {
-    __shared__ double red[2][kEwThreads / 64];
-    double lc = 0.0, lr = 0.0;
-    for (long long i = blockIdx.x * (long long)kEwThreads + threadIdx.x; i < M * 16; i += (long long)gridDim.x * kEwThreads) {
-        const long long m = i >> 4;
-        const int c = (int)(i & 15);
-        const float p = head[i];
-        if (c < 2) {
-            const float t = ycls[m * 2 + c];
-            if (kind == 0) {
-                const float d = p - t;
-                lc += (double)d * d;
-            } else {
-                const float tt = fminf(fmaxf(t, 0.f), 1.f);
-                lc += (double)(fmaxf(p, 0.f) - p * tt + log1pf(expf(-fabsf(p))));
-            }
-        } else {
-            const float t = yreg[m * 14 + (c - 2)];
-            const float d = p - t;
-            if (kind == 0) {
-                lr += (double)d * d;
-            } else {
-                const float ad = fabsf(d);
-                lr += (double)(ad < 1.f ? 0.5f * d * d : ad - 0.5f);
-            }
-        }
-    }
-    lc = wave_sum(lc); lr = wave_sum(lr);
-    if (lane_id() == 0) { red[0][threadIdx.x >> 6] = lc; red[1][threadIdx.x >> 6] = lr; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double a = 0.0;
-        for (int k = 0; k < kEwThreads / 64; ++k) a += red[threadIdx.x][k];
-        parts[(size_t)blockIdx.x * 2 + threadIdx.x] = a;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-k_loss_eval_finalize(const double* __restrict__ parts, int nparts, double M, double* __restrict__ acc) {
-    __shared__ double red[2][256];
-    double a = 0.0, b = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += 256) { a += parts[2 * k]; b += parts[2 * k + 1]; }
-    red[0][threadIdx.x] = a; red[1][threadIdx.x] = b;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        a = red[0][0] / (M * 2.0); b = red[1][0] / (M * 14.0);
-        const float tot = (float)(a + b), cls = (float)a, reg = (float)b;
+    double s[2];
+    strided_sums<256>(parts, nparts, s);
+    tree_sums<256>(s, red);
+    if (threadIdx.x != 0) return;
+    const double a = red[0][0] / (M * 2.0), b = red[1][0] / (M * 14.0);
+    const float tot = (float)(a + b), cls = (float)a, reg = (float)b;
+    if (acc) {
         acc[0] += (double)tot; acc[1] += (double)cls; acc[2] += (double)reg; acc[3] += 1.0;
+    } else {
+        out[0] = tot; out[1] = cls; out[2] = reg;
     }
 }
 
@@ -318,12 +259,6 @@ __global__ void k_scale(float* __restrict__ x, long long n4, float s) {
         a.x *= s; a.y *= s; a.z *= s; a.w *= s;
         reinterpret_cast<float4*>(x)[i] = a;
     }
-}
-
-int ew_blocks(long long work_items) {
-    long long b = (work_items + kEwThreads - 1) / kEwThreads;
-    if (b < 1) b = 1;
-    return (int)(b > kEwBlocks ? kEwBlocks : b);
 }
 
 }  // namespace
@@ -436,8 +371,8 @@ extern "C" int lisec_copy2d_batched(const lisec_copy_desc* device_table, int n, 
 extern "C" int lisec_relu_mask(float* grad, const float* act, long long n, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(grad && act && n >= 0 && n % 4 == 0, "relu_mask: n must be a multiple of 4");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_relu_mask, dim3(ew_blocks(n / 4)), dim3(kEwThreads), 0, static_cast<hipStream_t>(stream_),
-                       grad, act, n / 4);
+    LISEC_LAUNCH(k_relu_mask, dim3(grid_blocks(n / 4, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
+                       static_cast<hipStream_t>(stream_), grad, act, n / 4);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -475,9 +410,9 @@ extern "C" int lisec_rpn_loss(const float* head, const float* y_cls, const float
     }
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* parts = static_cast<double*>(workspace);
-    int nb = ew_blocks(M * 16);
-    LISEC_LAUNCH(k_loss, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, grad_scale, dhead, parts);
-    LISEC_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, loss_out);
+    int nb = grid_blocks(M * 16, kEwThreads, kEwBlocks);
+    LISEC_LAUNCH(k_loss<true>, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, grad_scale, dhead, parts);
+    LISEC_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, loss_out, (double*)nullptr);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -492,9 +427,10 @@ extern "C" int lisec_rpn_loss_eval(const float* head, const float* y_cls, const 
     }
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* parts = static_cast<double*>(workspace);
-    int nb = ew_blocks(M * 16);                       // lisec_rpn_loss's partition: the same partials
-    LISEC_LAUNCH(k_loss_eval, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, parts);
-    LISEC_LAUNCH(k_loss_eval_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, acc);
+    int nb = grid_blocks(M * 16, kEwThreads, kEwBlocks);       // lisec_rpn_loss's partition: the same partials
+    LISEC_LAUNCH(k_loss<false>, dim3(nb), dim3(kEwThreads), 0, st, head, y_cls, y_reg, M, kind, 1.0f, (float*)nullptr,
+                 parts);
+    LISEC_LAUNCH(k_loss_finalize, dim3(1), dim3(256), 0, st, parts, nb, (double)M, (float*)nullptr, acc);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -503,8 +439,8 @@ extern "C" int lisec_sgd_nesterov_step(float* theta, const float* grad, float* v
                                        float lr_t, float momentum, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(theta && grad && velocity && n >= 0 && n % 4 == 0, "sgd: n must be a multiple of 4");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_sgd_nesterov, dim3(ew_blocks(n / 4)), dim3(kEwThreads), 0, static_cast<hipStream_t>(stream_),
-                       theta, grad, velocity, n / 4, lr_t, momentum);
+    LISEC_LAUNCH(k_sgd_nesterov, dim3(grid_blocks(n / 4, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
+                       static_cast<hipStream_t>(stream_), theta, grad, velocity, n / 4, lr_t, momentum);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -513,8 +449,8 @@ extern "C" int lisec_sgd_nesterov_step_dev(float* theta, const float* grad, floa
                                            double decay, float momentum, long long* state, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(theta && grad && velocity && state && n >= 0 && n % 4 == 0, "sgd: n must be a multiple of 4");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_sgd_nesterov_dev, dim3(ew_blocks(n / 4)), dim3(kEwThreads), 0, static_cast<hipStream_t>(stream_),
-                       theta, grad, velocity, n / 4, lr, decay, momentum, state, 1);
+    LISEC_LAUNCH(k_sgd_nesterov_dev, dim3(grid_blocks(n / 4, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
+                       static_cast<hipStream_t>(stream_), theta, grad, velocity, n / 4, lr, decay, momentum, state, 1);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -523,8 +459,9 @@ extern "C" int lisec_sgd_nesterov_step_dev_part(float* theta, const float* grad,
                                                 double decay, float momentum, const long long* state, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(theta && grad && velocity && state && n >= 0 && n % 4 == 0, "sgd: n must be a multiple of 4");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_sgd_nesterov_dev, dim3(ew_blocks(n / 4)), dim3(kEwThreads), 0, static_cast<hipStream_t>(stream_),
-                       theta, grad, velocity, n / 4, lr, decay, momentum, const_cast<long long*>(state), 0);
+    LISEC_LAUNCH(k_sgd_nesterov_dev, dim3(grid_blocks(n / 4, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
+                       static_cast<hipStream_t>(stream_), theta, grad, velocity, n / 4, lr, decay, momentum,
+                       const_cast<long long*>(state), 0);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -532,7 +469,7 @@ extern "C" int lisec_sgd_nesterov_step_dev_part(float* theta, const float* grad,
 extern "C" int lisec_fold_depth(const float* in, float* out, int D, long long HW, int C, int inverse, const float* mask,
                                 lisec_stream_t stream_) {
     LISEC_CHECK_ARG(in && out && D >= 1 && HW >= 1 && C >= 1, "bad fold arguments");
-    LISEC_LAUNCH(k_fold_depth, dim3(ew_blocks((long long)D * HW * C)), dim3(kEwThreads), 0,
+    LISEC_LAUNCH(k_fold_depth, dim3(grid_blocks((long long)D * HW * C, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
                        static_cast<hipStream_t>(stream_), in, out, D, HW, C, inverse, mask);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
@@ -541,7 +478,8 @@ extern "C" int lisec_fold_depth(const float* in, float* out, int D, long long HW
 extern "C" int lisec_scale(float* x, long long n, float s, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(x && n >= 0 && n % 4 == 0, "scale: n must be a multiple of 4");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_scale, dim3(ew_blocks(n / 4)), dim3(kEwThreads), 0, static_cast<hipStream_t>(stream_), x, n / 4, s);
+    LISEC_LAUNCH(k_scale, dim3(grid_blocks(n / 4, kEwThreads, kEwBlocks)), dim3(kEwThreads), 0,
+                       static_cast<hipStream_t>(stream_), x, n / 4, s);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }

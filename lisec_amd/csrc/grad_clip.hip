@@ -2,17 +2,16 @@
 // restates them): passes over the flat gradient buffer IN FRONT of an optimizer entry, on the same stream, behind the
 // penalty pass and in front of the decoupled weight decay.  The table is LAMB's (lisec_lamb_chunk / lisec_lamb_var: every
 // trainable variable cut by the chunk rules, each chunk with its variable's index; the flags are ignored here).
-//   k_clip_value    in the shape of k_weight_decay: one workgroup of 256 per chunk, float4 loads and stores; g <- c where
+//   k_clip_value    k_weight_decay's launch: one workgroup of 256 per chunk, float4 loads and stores; g <- c where
 //                   g > c, g <- -c where g < -c, any other g (a NaN, a -0, a denormal) keeps its BITS: the two
 //                   comparisons are ordered and the result is chosen among bit patterns, so nothing is canonicalised.
 //                   8 bytes of HBM traffic per element.
 //   k_clip_sumsq    one workgroup of 256 per chunk (past kClipBlocks chunks the workgroups stride over the table): float4
-//                   loads, (double)g*(double)g per thread, wave reduction, LDS reduction over the four waves in wave
-//                   order, one fp64 partial per chunk into the workspace.  4 bytes per element.
-//   k_clip_scales   one WAVE per variable: lane l adds the partials of chunks l, l + 64, ... in that order, then the
-//                   butterfly of wave_sum; S -> (scale, norm) by clip_scale below.
-//   k_clip_total    ONE workgroup of 256 for the global norm: thread t adds the partials of chunks t, t + 256, ... in
-//                   that order, then wave, then LDS in wave order -- an order fixed by n_chunks alone.
+//                   loads, (double)g*(double)g per thread, summed over the workgroup in order W of reduce.h, one fp64
+//                   partial per chunk into the workspace.  4 bytes per element.
+//   k_clip_scales   one WAVE per variable: the partials of its chunks in order V; S -> (scale, norm) by clip_scale below.
+//   k_clip_total    ONE workgroup of 256 for the global norm: the strided sums of order T over the partials of the whole
+//                   table, then order W over the 256 -- an order fixed by n_chunks alone.
 //   k_clip_apply    reads its chunk's scale first; exactly 1.0f: the chunk is skipped (no load, no store); otherwise
 //                   g <- g*scale, one fp32 multiply per element.  8 bytes per element of a clipped chunk, 0 of the others.
 // Launches are ordered by the stream alone, as k_lamb_moments / k_lamb_ratios / k_lamb_apply are: no fence, no counter,
@@ -22,12 +21,12 @@
 // The sum of squares must be (double)g*(double)g added to the running sum in two roundings (the contract of
 // include/lisec_hip.h), not an fma of one: everything below is compiled with contraction off, like its neighbours.
 #pragma clang fp contract(off)
+#include "reduce.h"
 
 namespace lisec {
 namespace {
 
 constexpr int kClipThreads = 256;
-constexpr int kClipWaves = kClipThreads / kWave;
 constexpr int kClipBlocks = 2048;       // 8 workgroups of 256 per CU on 256 CUs; the model's theta is ~1650 chunks
 
 __device__ __forceinline__ float clip_one(float g, float c, float nc) {
@@ -56,7 +55,7 @@ k_clip_value(float* __restrict__ grad, const lisec_lamb_chunk* __restrict__ chun
 __global__ void __launch_bounds__(kClipThreads)
 k_clip_sumsq(const float* __restrict__ grad, const lisec_lamb_chunk* __restrict__ chunks, int n_chunks,
              double* __restrict__ partials) {
-    __shared__ double sums[kClipWaves];
+    __shared__ double red[1][kClipThreads / kWave];
     for (int k = blockIdx.x; k < n_chunks; k += kClipBlocks) {
         const lisec_lamb_chunk ch = chunks[k];
         const float4* __restrict__ g4 = reinterpret_cast<const float4*>(grad + ch.offset);
@@ -69,16 +68,11 @@ k_clip_sumsq(const float* __restrict__ grad, const lisec_lamb_chunk* __restrict_
             s += (double)G.z * (double)G.z;
             s += (double)G.w * (double)G.w;
         }
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) sums[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0.0;
-#pragma unroll
-            for (int w = 0; w < kClipWaves; ++w) t += sums[w];
-            partials[k] = t;
-        }
-        __syncthreads();                                                  // sums is free for the next chunk
+        const double v[1] = {s};
+        double t[1];
+        block_sums_all<kClipThreads>(v, red, t);
+        if (threadIdx.x == 0) partials[k] = t[0];
+        __syncthreads();                                                  // red is free for the next chunk
     }
 }
 
@@ -101,10 +95,9 @@ k_clip_scales(const lisec_lamb_var* __restrict__ vars, int n_vars, const double*
               float* __restrict__ scales, float* __restrict__ norms) {
     for (int j = blockIdx.x; j < n_vars; j += kClipBlocks) {
         const lisec_lamb_var var = vars[j];
-        double s = 0.0;
-        for (int i = threadIdx.x; i < var.n_chunks; i += kWave) s += partials[(long long)var.first_chunk + i];
-        s = wave_sum(s);
-        if (threadIdx.x == 0) clip_scale(s, clip, scales + j, norms + j);
+        double s[1];
+        wave_strided_sums(partials, var.first_chunk, var.n_chunks, s);
+        if (threadIdx.x == 0) clip_scale(s[0], clip, scales + j, norms + j);
     }
 }
 
@@ -112,18 +105,11 @@ k_clip_scales(const lisec_lamb_var* __restrict__ vars, int n_vars, const double*
 __global__ void __launch_bounds__(kClipThreads)
 k_clip_total(const double* __restrict__ partials, int n_chunks, float clip, float* __restrict__ scales,
              float* __restrict__ norms) {
-    __shared__ double sums[kClipWaves];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < n_chunks; k += kClipThreads) s += partials[k];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sums[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-#pragma unroll
-        for (int w = 0; w < kClipWaves; ++w) t += sums[w];
-        clip_scale(t, clip, scales, norms);
-    }
+    __shared__ double red[1][kClipThreads / kWave];
+    double s[1], t[1];
+    strided_sums<kClipThreads>(partials, n_chunks, s);
+    block_sums_all<kClipThreads>(s, red, t);
+    if (threadIdx.x == 0) clip_scale(t[0], clip, scales, norms);
 }
 
 // shared_scale: every chunk reads scales[0] (the global norm); otherwise scales[chunk.var].
@@ -147,9 +133,9 @@ k_clip_apply(float* __restrict__ grad, const lisec_lamb_chunk* __restrict__ chun
     }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 inline bool threshold_ok(float c) { return c > 0.f && c <= 3.402823466e+38f; }       // (a NaN fails both comparisons)
-inline int wide(int n) { return n > kClipBlocks ? kClipBlocks : n; }
+// (1 for n == 0, but no entry launches over an empty range: each returns early, and n_vars is 0 only with n_chunks)
+inline int wide(int n) { return grid_blocks(n, 1, kClipBlocks); }
 
 // What every entry asks of its gradient, its chunk range and (unless there is none) its workspace.
 int check_range(const char* who, const float* grad, const lisec_lamb_chunk* chunks, int first_chunk, int n_chunks,

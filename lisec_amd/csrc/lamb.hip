@@ -11,11 +11,10 @@
 // lisec_lamb_var gives each variable's first chunk and chunk count.  Three launches, ordered by the stream alone:
 //   k_lamb_moments  one workgroup of 256 per chunk (past kLambBlocks chunks the workgroups stride over the table): float4
 //                   loads of g, m, v, w, float4 stores of m, v; u stays in registers; sum w^2 and sum u^2 per thread in
-//                   fp64, wave reduction, LDS reduction over the four waves, one pair of fp64 partials per chunk into
+//                   fp64, summed over the workgroup in order W of reduce.h, one pair of fp64 partials per chunk into
 //                   the workspace.  6 floats of HBM traffic per element.
-//   k_lamb_ratios   one WAVE per variable: lane l adds the partials of chunks l, l + 64, ... of the variable in that order,
-//                   then the butterfly of wave_sum -- an order fixed by the table alone; r is formed in fp64, rounded
-//                   once and stored into the caller's float[n_vars] buffer.
+//   k_lamb_ratios   one WAVE per variable: the pairs of the variable's chunks in order V of reduce.h; r is formed in
+//                   fp64, rounded once and stored into the caller's float[n_vars] buffer.
 //   k_lamb_apply    4 floats per element: reads m, v, w again, forms the SAME u (the same separately rounded operations, see
 //                   below), writes w, and ends the step through the ticket protocol of optim_common.h.
 // The reduction is a launch of its own rather than a prologue of k_lamb_apply: stream order is the only ordering it
@@ -29,12 +28,12 @@
 // below is compiled with contraction off: every operation named in include/lisec_hip.h is rounded on its own.
 #pragma clang fp contract(off)
 #include "optim_common.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
 
 constexpr int kLambThreads = 256;
-constexpr int kLambWaves = kLambThreads / kWave;
 constexpr int kLambBlocks = 2048;       // 8 workgroups of 256 per CU on 256 CUs; the model's theta is ~1650 chunks
 constexpr int kLambRatioThreads = kWave;
 
@@ -103,7 +102,7 @@ k_lamb_moments(const float* __restrict__ theta, const float* __restrict__ grad, 
                float* __restrict__ v, const lisec_lamb_chunk* __restrict__ chunks, int n_chunks,
                double* __restrict__ partials, float b1, float b2, float eps, float wd,
                const long long* __restrict__ state) {
-    __shared__ double s1[kLambWaves], s2[kLambWaves];
+    __shared__ double red[2][kLambThreads / kWave];
     const LambScalars s = lamb_scalars(b1, b2, eps, wd, read_iterations(state));
     for (int c = blockIdx.x; c < n_chunks; c += kLambBlocks) {           // (the grid is at most kLambBlocks wide)
         const lisec_lamb_chunk ch = chunks[c];
@@ -121,19 +120,14 @@ k_lamb_moments(const float* __restrict__ theta, const float* __restrict__ grad, 
             m4[i] = M;
             v4[i] = V;
         }
-        sw = wave_sum(sw);
-        su = wave_sum(su);
-        const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) { s1[wave] = sw; s2[wave] = su; }
-        __syncthreads();
+        const double a[2] = {sw, su};
+        double t[2];
+        block_sums_all<kLambThreads>(a, red, t);
         if (threadIdx.x == 0) {
-            double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-            for (int k = 0; k < kLambWaves; ++k) { t1 += s1[k]; t2 += s2[k]; }
-            partials[2 * (long long)c] = t1;
-            partials[2 * (long long)c + 1] = t2;
+            partials[2 * (long long)c] = t[0];
+            partials[2 * (long long)c + 1] = t[1];
         }
-        __syncthreads();                                                  // s1, s2 are free for the next chunk
+        __syncthreads();                                                  // red is free for the next chunk
     }
 }
 #undef LISEC_LAMB_MOMENTS
@@ -144,17 +138,11 @@ k_lamb_ratios(const lisec_lamb_chunk* __restrict__ chunks, const lisec_lamb_var*
               const double* __restrict__ partials, float* __restrict__ ratios) {
     for (int j = blockIdx.x; j < n_vars; j += kLambBlocks) {
         const lisec_lamb_var var = vars[j];
-        double sw = 0.0, su = 0.0;
-        for (int i = threadIdx.x; i < var.n_chunks; i += kLambRatioThreads) {
-            const long long c = (long long)var.first_chunk + i;
-            sw += partials[2 * c];
-            su += partials[2 * c + 1];
-        }
-        sw = wave_sum(sw);
-        su = wave_sum(su);
+        double s[2];                                                      // sum w^2, sum u^2
+        wave_strided_sums(partials, var.first_chunk, var.n_chunks, s);
         if (threadIdx.x == 0) {
             const bool adapted = var.n_chunks > 0 && (chunks[var.first_chunk].flags & LISEC_LAMB_ADAPTED) != 0;
-            ratios[j] = adapted && sw > 0.0 && su > 0.0 ? (float)(sqrt(sw) / sqrt(su)) : 1.0f;
+            ratios[j] = adapted && s[0] > 0.0 && s[1] > 0.0 ? (float)(sqrt(s[0]) / sqrt(s[1])) : 1.0f;
         }
     }
 }
@@ -212,12 +200,10 @@ int lamb_step(const char* who, float* theta, const float* grad, float* m, float*
     LISEC_CHECK_ARG(workspace_bytes >= lisec_lamb_workspace_bytes(first_chunk + n_chunks, first_var + n_vars),
                     "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
                     lisec_lamb_workspace_bytes(first_chunk + n_chunks, first_var + n_vars));
-    LISEC_CHECK_ARG((reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(m) |
-                     reinterpret_cast<uintptr_t>(v)) % 16 == 0,
+    LISEC_CHECK_ARG(aligned(theta, 16) && aligned(grad, 16) && aligned(m, 16) && aligned(v, 16),
                     "%s: theta, grad, m and v must be 16-byte aligned", who);
-    LISEC_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(state) |
-                     reinterpret_cast<uintptr_t>(chunks)) % 8 == 0 &&
-                        (reinterpret_cast<uintptr_t>(ratios) | reinterpret_cast<uintptr_t>(vars)) % 4 == 0,
+    LISEC_CHECK_ARG(aligned(workspace, 8) && aligned(state, 8) && aligned(chunks, 8) && aligned(ratios, 4) &&
+                        aligned(vars, 4),
                     "%s: workspace, state and chunks must be 8-byte aligned, ratios and vars 4-byte aligned", who);
     if (n_chunks == 0 && !advance) return LISEC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream_);
@@ -226,15 +212,15 @@ int lamb_step(const char* who, float* theta, const float* grad, float* m, float*
     // vars + first_var), but lisec_lamb_chunk.var and lisec_lamb_var.first_chunk count from the first row of the TABLE:
     // what is indexed by them (ratios in k_lamb_apply; chunks and partials in k_lamb_ratios) is passed whole.
     double* partials = static_cast<double*>(workspace);
-    const int wide = n_chunks > kLambBlocks ? kLambBlocks : n_chunks;
+    const int wide = grid_blocks(n_chunks, 1, kLambBlocks);            // (1 for an empty range: k_lamb_apply's ticket)
     if (n_chunks > 0) {
         LISEC_LAUNCH(k_lamb_moments, dim3(wide), dim3(kLambThreads), 0, st, (const float*)theta, grad, m, v,
                      chunks + first_chunk, n_chunks, partials + 2 * (long long)first_chunk, b1, b2, eps, wd,
                      (const long long*)state);
-        LISEC_LAUNCH(k_lamb_ratios, dim3(n_vars > kLambBlocks ? kLambBlocks : n_vars), dim3(kLambRatioThreads), 0, st,
+        LISEC_LAUNCH(k_lamb_ratios, dim3(grid_blocks(n_vars, 1, kLambBlocks)), dim3(kLambRatioThreads), 0, st,
                      chunks, vars + first_var, n_vars, (const double*)partials, ratios + first_var);
     }
-    LISEC_LAUNCH(k_lamb_apply, dim3(wide > 0 ? wide : 1), dim3(kLambThreads), 0, st, theta, (const float*)m,
+    LISEC_LAUNCH(k_lamb_apply, dim3(wide), dim3(kLambThreads), 0, st, theta, (const float*)m,
                  (const float*)v, chunks + first_chunk, n_chunks, (const float*)ratios, lr, decay, sched, b1, b2, eps, wd,
                  state, advance);
     LISEC_LAUNCH_CHECK();

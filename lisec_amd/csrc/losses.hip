@@ -2,14 +2,14 @@
 // (include/lisec_hip.h, lisec_head_loss*).  One pass over head / y_cls / y_reg in the element layout of k_loss
 // (csrc/eltwise.hip): thread i of the grid-stride loop holds element i of the flat (M,16) head, so the 16 lanes of a
 // cell are 16 consecutive lanes of one wave and a per-cell metric (categorical accuracy) is a butterfly over them.
-// It writes dhead and per-workgroup fp64 partials of both losses and of every metric; one single-workgroup finalize
-// sums them in index order.  No atomics: the same bits on every run, and the evaluation entry -- the same kernels with
-// a NULL gradient -- reproduces the training entry's values bit for bit.
+// It writes dhead and per-workgroup fp64 partials of both losses and of every metric (order W of reduce.h); one
+// single-workgroup finalize sums them (order T).  The evaluation entry is the same kernels with a NULL gradient, so it
+// reproduces the training entry's values bit for bit.
 //
 // Values: MSE and the two halves of lisec_rpn_loss kind 1 use k_loss's fp32 element arithmetic (so dhead of
 // ['mse','mse'] at unit weights is k_loss's, bit for bit); every other kind evaluates its element loss and gradient in
 // double from the fp32 inputs, then rounds the gradient once.  Sums are fp64 in both cases.
-#include "common.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -174,45 +174,21 @@ k_head_loss(lisec_loss_cfg cfg, const float* __restrict__ head, const float* __r
         v[2 + j] = o == 0 ? macc[j] : 0.0;
         v[2 + LISEC_LOSS_MAX_METRICS + j] = o == 1 ? macc[j] : 0.0;
     }
-#pragma unroll
-    for (int k = 0; k < kLossVals; ++k) {
-        if (!slot_used(cfg, k)) continue;             // uniform: the unused slots are never read
-        const double s = wave_sum(v[k]);
-        if (lane_id() == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < kLossVals && slot_used(cfg, threadIdx.x)) {
-        double a = 0.0;
-        for (int w = 0; w < kLossThreads / 64; ++w) a += red[threadIdx.x][w];
-        parts[(size_t)blockIdx.x * kLossVals + threadIdx.x] = a;
-    }
+    const auto used = [&](int k) { return slot_used(cfg, k); };          // uniform: the unused slots are never read
+    const double a = block_sum_own<kLossThreads>(v, red, used);
+    if (threadIdx.x < kLossVals && used(threadIdx.x)) parts[(size_t)blockIdx.x * kLossVals + threadIdx.x] = a;
 }
 
-// One workgroup: the partials of every value summed in index order.  Training (acc == nullptr): loss_out[3] and
+// One workgroup: the partials of every value in use, in order T.  Training (acc == nullptr): loss_out[3] and
 // metric_out; evaluation: the same fp32 values added, as doubles, to acc, and the sweep counted.
 __global__ void __launch_bounds__(256)
 k_head_loss_finalize(lisec_loss_cfg cfg, const double* __restrict__ parts, int nparts, double M, float* __restrict__ loss_out,
                      float* __restrict__ metric_out, double* __restrict__ acc) {
     __shared__ double red[kLossVals][256];
+    const auto used = [&](int k) { return slot_used(cfg, k); };
     double a[kLossVals];
-#pragma unroll
-    for (int k = 0; k < kLossVals; ++k) a[k] = 0.0;
-    for (int b = threadIdx.x; b < nparts; b += 256) {     // the loads of every value in use issued together
-#pragma unroll
-        for (int k = 0; k < kLossVals; ++k)
-            if (slot_used(cfg, k)) a[k] += parts[(size_t)b * kLossVals + k];
-    }
-#pragma unroll
-    for (int k = 0; k < kLossVals; ++k) red[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-#pragma unroll
-            for (int k = 0; k < kLossVals; ++k)
-                if (slot_used(cfg, k)) red[k][threadIdx.x] += red[k][threadIdx.x + s];
-        }
-        __syncthreads();
-    }
+    strided_sums<256>(parts, nparts, a, used);
+    tree_sums<256>(a, red, used);
     if (threadIdx.x != 0) return;
     const double lc = red[0][0] / (M * 2.0), lr = red[1][0] / (M * 14.0);
     const float tot = (float)((double)cfg.weight[0] * lc + (double)cfg.weight[1] * lr), fc = (float)lc, fr = (float)lr;
@@ -231,11 +207,6 @@ k_head_loss_finalize(lisec_loss_cfg cfg, const double* __restrict__ parts, int n
         }
     }
     if (acc) acc[3 + k] += 1.0;
-}
-
-int loss_blocks(long long M) {
-    const long long b = (M * 16 + kLossThreads - 1) / kLossThreads;
-    return (int)(b < 1 ? 1 : (b > kLossBlocks ? kLossBlocks : b));
 }
 
 bool valid_term(const lisec_loss_term& T, bool metric) {
@@ -279,7 +250,7 @@ extern "C" int lisec_head_loss(const lisec_loss_cfg* cfg, const float* head, con
     }
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* parts = static_cast<double*>(workspace);
-    const int nb = loss_blocks(M);
+    const int nb = grid_blocks(M * 16, kLossThreads, kLossBlocks);
     LISEC_LAUNCH(k_head_loss, dim3(nb), dim3(kLossThreads), 0, st, *cfg, head, y_cls, y_reg, M, grad_scale, dhead, parts);
     LISEC_LAUNCH(k_head_loss_finalize, dim3(1), dim3(256), 0, st, *cfg, parts, nb, (double)M, loss_out, metric_out,
                  (double*)nullptr);
@@ -298,7 +269,7 @@ extern "C" int lisec_head_loss_eval(const lisec_loss_cfg* cfg, const float* head
     }
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* parts = static_cast<double*>(workspace);
-    const int nb = loss_blocks(M);                    // lisec_head_loss's partition: the same partials
+    const int nb = grid_blocks(M * 16, kLossThreads, kLossBlocks);      // lisec_head_loss's partition: the same partials
     LISEC_LAUNCH(k_head_loss, dim3(nb), dim3(kLossThreads), 0, st, *cfg, head, y_cls, y_reg, M, 1.0f, (float*)nullptr,
                  parts);
     LISEC_LAUNCH(k_head_loss_finalize, dim3(1), dim3(256), 0, st, *cfg, parts, nb, (double)M, (float*)nullptr,

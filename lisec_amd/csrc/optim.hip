@@ -131,7 +131,7 @@ extern "C" int lisec_sgd_step_dev(float* theta, const float* grad, float* veloci
     LISEC_CHECK_ARG((velocity == nullptr) == (momentum == 0.f), "sgd: velocity must be NULL exactly when momentum == 0");
     if (n == 0) return LISEC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    const dim3 grid(grid_blocks(n / 4, kOptThreads, kOptBlocks)), block(kOptThreads);
     if (momentum == 0.f)
         LISEC_LAUNCH(k_sgd_dev<kSgdPlain>, grid, block, 0, st, theta, grad, velocity, n / 4, lr, decay, momentum, state, advance);
     else if (nesterov)
@@ -151,7 +151,7 @@ extern "C" int lisec_adam_step_dev(float* theta, const float* grad, float* m, fl
     LISEC_CHECK_ARG(advance == 0 || advance == 1, "adam: advance must be 0 or 1");
     if (n == 0) return LISEC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    const dim3 grid(grid_blocks(n / 4, kOptThreads, kOptBlocks)), block(kOptThreads);
     if (vhat)                                                          // AMSGrad
         LISEC_LAUNCH(k_adam_dev<true>, grid, block, 0, st, theta, grad, m, v, vhat, n / 4, lr, decay, beta1, beta2, epsilon,
                      state, advance);
@@ -185,8 +185,8 @@ extern "C" int lisec_lr_schedule_eval(const lisec_lr_schedule* sched, const long
                                       lisec_stream_t stream_) {
     LISEC_CHECK_ARG(sched && state && lr_out && n >= 0, "lr_schedule_eval: NULL pointer or n < 0");
     if (n == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_lr_schedule_eval, dim3(opt_blocks(n)), dim3(kOptThreads), 0, static_cast<hipStream_t>(stream_), sched,
-                 state, n, lr_out);
+    LISEC_LAUNCH(k_lr_schedule_eval, dim3(grid_blocks(n, kOptThreads, kOptBlocks)), dim3(kOptThreads), 0,
+                 static_cast<hipStream_t>(stream_), sched, state, n, lr_out);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
 }
@@ -200,7 +200,7 @@ extern "C" int lisec_sgd_step_sched(float* theta, const float* grad, float* velo
     LISEC_CHECK_ARG((velocity == nullptr) == (momentum == 0.f), "sgd_sched: velocity must be NULL exactly when momentum == 0");
     if (n == 0) return LISEC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    const dim3 grid(grid_blocks(n / 4, kOptThreads, kOptBlocks)), block(kOptThreads);
     if (momentum == 0.f)
         LISEC_LAUNCH(k_sgd_sched<kSgdPlain>, grid, block, 0, st, theta, grad, velocity, n / 4, sched, momentum, state, advance);
     else if (nesterov)
@@ -223,7 +223,7 @@ extern "C" int lisec_adam_step_sched(float* theta, const float* grad, float* m, 
     LISEC_CHECK_ARG(advance == 0 || advance == 1, "adam_sched: advance must be 0 or 1");
     if (n == 0) return LISEC_OK;
     hipStream_t st = static_cast<hipStream_t>(stream_);
-    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads);
+    const dim3 grid(grid_blocks(n / 4, kOptThreads, kOptBlocks)), block(kOptThreads);
     if (vhat)                                                          // AMSGrad
         LISEC_LAUNCH(k_adam_sched<true>, grid, block, 0, st, theta, grad, m, v, vhat, n / 4, sched, beta1, beta2, epsilon,
                      state, advance);

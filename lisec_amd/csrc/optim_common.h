@@ -10,12 +10,6 @@ namespace {
 constexpr int kOptBlocks = 1024;
 constexpr int kOptThreads = 256;
 
-int opt_blocks(long long work_items) {
-    long long b = (work_items + kOptThreads - 1) / kOptThreads;
-    if (b < 1) b = 1;
-    return (int)(b > kOptBlocks ? kOptBlocks : b);
-}
-
 // The iteration count of the step, read by every workgroup before any of them may advance it.
 __device__ __forceinline__ long long read_iterations(const long long* state) {
     return __hip_atomic_load(&state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

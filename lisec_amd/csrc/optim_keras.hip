@@ -220,7 +220,7 @@ using namespace lisec;
     LISEC_CHECK_ARG(advance == 0 || advance == 1, who ": advance must be 0 or 1");                                      \
     if (n == 0) return LISEC_OK;                                                                                        \
     hipStream_t st = static_cast<hipStream_t>(stream_);                                                                 \
-    const dim3 grid(opt_blocks(n / 4)), block(kOptThreads)
+    const dim3 grid(grid_blocks(n / 4, kOptThreads, kOptBlocks)), block(kOptThreads)
 
 #define LISEC_RMSPROP_CHECKS(who, sched_or_true)                                                                        \
     LISEC_OPT_CHECKS(who, rms && (mom == nullptr) == (momentum == 0.f) && (mg == nullptr) == !centered,                \

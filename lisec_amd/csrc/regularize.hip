@@ -4,20 +4,19 @@
 // crosses a variable, so it has one (l1, l2)); the table lives on the device.  A chunk flagged LISEC_REG_GRAD_IS_ZERO
 // belongs to a variable whose slot of grad no backward pass writes: its term is stored, not added.  Two launches:
 //   k_regularize         one workgroup of 256 per chunk: float4 loads of theta and grad, float4 store of grad, sum|w| and
-//                        sum w^2 per thread in fp64, wave reduction, LDS reduction over the four waves, one fp64 partial
+//                        sum w^2 per thread in fp64, summed over the workgroup in order W of reduce.h, one fp64 partial
 //                        l1*a1 + l2*a2 per chunk into the workspace;
-//   k_regularize_finish  one workgroup: thread t adds partials t, t+256, ... in that order, a fixed tree over the 256
-//                        sums, then *penalty = P (or += P) and, given loss_total, *loss_total = (float)(*loss_total + P).
+//   k_regularize_finish  one workgroup: the partials in order T of reduce.h, then *penalty = P (or += P) and, given
+//                        loss_total, *loss_total = (float)(*loss_total + P).
 // The finish is a launch of its own rather than the last workgroup to arrive: stream order is the only ordering it
 // needs, so no ticket, no fence and no counter to keep zero between launches, at ~2 us on a pass that runs under the
 // backward.  No atomics of any kind: P and the gradient have the same bits from run to run.
-#include "common.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
 
 constexpr int kRegThreads = 256;
-constexpr int kRegWaves = kRegThreads / 64;
 
 #define LISEC_REG_ELEM(f)                                                                  \
     {                                                                                      \
@@ -30,7 +29,7 @@ constexpr int kRegWaves = kRegThreads / 64;
 __global__ void __launch_bounds__(kRegThreads)
 k_regularize(const float* __restrict__ theta, float* __restrict__ grad, const lisec_reg_chunk* __restrict__ chunks,
              double* __restrict__ partials) {
-    __shared__ double s1[kRegWaves], s2[kRegWaves];
+    __shared__ double red[2][kRegThreads / kWave];
     const lisec_reg_chunk c = chunks[blockIdx.x];
     const int n4 = c.count / 4;
     const float4* __restrict__ w4 = reinterpret_cast<const float4*>(theta + c.offset);
@@ -47,34 +46,22 @@ k_regularize(const float* __restrict__ theta, float* __restrict__ grad, const li
         LISEC_REG_ELEM(x) LISEC_REG_ELEM(y) LISEC_REG_ELEM(z) LISEC_REG_ELEM(w)
         if (write) g4[i] = G;
     }
-    a1 = wave_sum(a1);
-    a2 = wave_sum(a2);
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s1[wave] = a1; s2[wave] = a2; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < kRegWaves; ++k) { t1 += s1[k]; t2 += s2[k]; }
-        partials[blockIdx.x] = (double)c.l1 * t1 + (double)c.l2 * t2;
-    }
+    const double a[2] = {a1, a2};
+    double t[2];
+    block_sums_all<kRegThreads>(a, red, t);
+    if (threadIdx.x == 0) partials[blockIdx.x] = (double)c.l1 * t[0] + (double)c.l2 * t[1];
 }
 #undef LISEC_REG_ELEM
 
 __global__ void __launch_bounds__(kRegThreads)
 k_regularize_finish(const double* __restrict__ partials, int n, double* __restrict__ penalty, int accumulate,
                     float* __restrict__ loss_total) {
-    __shared__ double s[kRegThreads];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += kRegThreads) a += partials[i];
-    s[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = kRegThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) s[threadIdx.x] += s[threadIdx.x + o];
-        __syncthreads();
-    }
+    __shared__ double red[1][kRegThreads];
+    double a[1];
+    strided_sums<kRegThreads>(partials, n, a);
+    tree_sums<kRegThreads>(a, red);
     if (threadIdx.x == 0) {
-        const double p = accumulate ? *penalty + s[0] : s[0];
+        const double p = accumulate ? *penalty + red[0][0] : red[0][0];
         *penalty = p;
         if (loss_total) *loss_total = (float)((double)*loss_total + p);
     }
@@ -98,8 +85,7 @@ extern "C" int lisec_regularize(const float* theta, float* grad, const lisec_reg
     LISEC_CHECK_ARG(workspace_bytes >= lisec_regularize_workspace_bytes(n_chunks),
                     "regularize: workspace of %zu bytes, %zu needed", workspace_bytes,
                     lisec_regularize_workspace_bytes(n_chunks));
-    LISEC_CHECK_ARG((reinterpret_cast<uintptr_t>(theta) | reinterpret_cast<uintptr_t>(grad)) % 16 == 0 &&
-                        reinterpret_cast<uintptr_t>(workspace) % 8 == 0,
+    LISEC_CHECK_ARG(aligned(theta, 16) && aligned(grad, 16) && aligned(workspace, 8),
                     "regularize: theta and grad must be 16-byte aligned, the workspace 8-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream_);
     double* partials = static_cast<double*>(workspace);

@@ -11,6 +11,7 @@
 // V-row contractions (row lists in igemm.hip / wgrad.hip) plus the two small kernels below -- the same
 // numbers up to fp32 summation order (what Keras' autograd computes densely, model_training.py:299).
 #include "conv.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -142,24 +143,19 @@ k_tap_sums(ConvGeom g, const float* __restrict__ line_s, float* __restrict__ S) 
     }
 }
 
-// g_all[c] = sum_tap sum_n W[tap][c][n] * S[tap][n]      (one block per c)
+// g_all[c] = sum_tap sum_n W[tap][c][n] * S[tap][n]      (one block per c; the 256 sums in the tree of reduce.h)
 __global__ void __launch_bounds__(256)
 k_const_field_gall(const float* __restrict__ W, const float* __restrict__ S, int ntaps, int Cin, int Cout,
                    float* __restrict__ g_all) {
-    __shared__ double red[256];
+    __shared__ double red[1][256];
     const int c = blockIdx.x;
-    double a = 0.0;
+    double a[1] = {0.0};
     for (int i = threadIdx.x; i < ntaps * Cout; i += 256) {
         const int tap = i / Cout, n = i - tap * Cout;
-        a += (double)W[((size_t)tap * Cin + c) * Cout + n] * (double)S[i];
+        a[0] += (double)W[((size_t)tap * Cin + c) * Cout + n] * (double)S[i];
     }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) g_all[c] = (float)red[0];
+    tree_sums<256>(a, red);
+    if (threadIdx.x == 0) g_all[c] = (float)red[0][0];
 }
 
 // dW[tap][c][n] += cvec[c] * S[tap][n]

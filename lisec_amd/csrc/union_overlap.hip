@@ -22,6 +22,7 @@
 // the edge of the lower box index first, and each of the two threads evaluates the same expression on the same operands.
 // float64 throughout; latency-bound scalar code: no MFMA, LDS for the rectangle cache and the final fixed-order reduction.
 #include "box_geom.h"
+#include "reduce.h"
 
 namespace lisec {
 namespace {
@@ -104,23 +105,19 @@ __device__ Span rect_span(Pt A, Pt B, double oi, bool e_is_lo, const Rect& K) {
     return S;
 }
 
-// sum over the workgroup in a fixed order (tree over LDS), result in every thread
-__device__ double block_sum(double v, double* red) {
-    __syncthreads();
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = kThreads / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    return red[0];
+// sum over the workgroup in a fixed order (the tree of reduce.h), result in every thread
+__device__ double block_sum(double v, double (&red)[1][kThreads]) {
+    const double a[1] = {v};
+    __syncthreads();                                           // red is free of the call before
+    tree_sums<kThreads>(a, red);
+    return red[0][0];
 }
 
 __global__ void __launch_bounds__(kThreads)
 k_union_overlap(const double* __restrict__ pred, const int32_t* __restrict__ pred_start, const double* __restrict__ label,
                 const int32_t* __restrict__ label_start, double* __restrict__ out) {
     __shared__ Rect cache[kCached];
-    __shared__ double red[kThreads];
+    __shared__ double red[1][kThreads];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int p0 = pred_start[s], l0 = label_start[s];
     const int nP = max(pred_start[s + 1] - p0, 0), nL = max(label_start[s + 1] - l0, 0), n = nP + nL;

@@ -79,10 +79,10 @@ extern "C" int lisec_weight_decay(float* theta, const lisec_decay_chunk* chunks,
                                   const long long* state, lisec_stream_t stream_) {
     LISEC_CHECK_ARG(theta && chunks && coeff && state, "weight_decay: NULL theta, chunks, coeff or state");
     LISEC_CHECK_ARG(n_chunks >= 0, "weight_decay: n_chunks = %d", n_chunks);
-    LISEC_CHECK_ARG(reinterpret_cast<uintptr_t>(theta) % 16 == 0, "weight_decay: theta must be 16-byte aligned");
-    LISEC_CHECK_ARG(reinterpret_cast<uintptr_t>(state) % 8 == 0, "weight_decay: state must be 8-byte aligned");
+    LISEC_CHECK_ARG(aligned(theta, 16), "weight_decay: theta must be 16-byte aligned");
+    LISEC_CHECK_ARG(aligned(state, 8), "weight_decay: state must be 8-byte aligned");
     if (n_chunks == 0) return LISEC_OK;
-    LISEC_LAUNCH(k_weight_decay, dim3(n_chunks > kDecayBlocks ? kDecayBlocks : n_chunks), dim3(kDecayThreads), 0,
+    LISEC_LAUNCH(k_weight_decay, dim3(grid_blocks(n_chunks, 1, kDecayBlocks)), dim3(kDecayThreads), 0,
                  static_cast<hipStream_t>(stream_), theta, chunks, n_chunks, coeff, state);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
@@ -91,10 +91,9 @@ extern "C" int lisec_weight_decay(float* theta, const lisec_decay_chunk* chunks,
 extern "C" int lisec_weight_decay_eval(const lisec_lr_schedule* coeff, const long long* state, long long k, float* wd_out,
                                        lisec_stream_t stream_) {
     LISEC_CHECK_ARG(coeff && state && wd_out && k >= 0, "weight_decay_eval: NULL pointer or k < 0");
-    LISEC_CHECK_ARG(reinterpret_cast<uintptr_t>(state) % 8 == 0, "weight_decay_eval: state must be 8-byte aligned");
+    LISEC_CHECK_ARG(aligned(state, 8), "weight_decay_eval: state must be 8-byte aligned");
     if (k == 0) return LISEC_OK;
-    const long long b = (k + kDecayThreads - 1) / kDecayThreads;
-    LISEC_LAUNCH(k_weight_decay_eval, dim3((unsigned)(b > kDecayBlocks ? kDecayBlocks : b)), dim3(kDecayThreads), 0,
+    LISEC_LAUNCH(k_weight_decay_eval, dim3(grid_blocks(k, kDecayThreads, kDecayBlocks)), dim3(kDecayThreads), 0,
                  static_cast<hipStream_t>(stream_), coeff, state, k, wd_out);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
