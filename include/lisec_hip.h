@@ -775,6 +775,58 @@ int lisec_detection_iou_loss_eval(const lisec_detection_iou_loss_cfg* cfg, const
                                   lisec_stream_t stream);
 size_t lisec_detection_iou_loss_workspace_bytes(void);     /* = lisec_detection_loss_workspace_bytes() */
 
+/* Sample weights of fit(sample_weight=) / evaluate(sample_weight=) for the three loss families above (ours where tf.keras
+ * 2.4 cannot be checked).  w_o[m] weighs cell m of output o (0 class, 1 regression): one device float for the sweep, or a
+ * map of M floats.  The weights are read when the launch runs, so a recorded plan sees what was staged at the address.
+ *   head loss:       L_o = 1/(M*C) sum_m w_o[m] sum_c v(m,c) -- the divisor stays the element count.  The fp32 kinds use
+ *                    the gradient scale wf * w (one fp32 multiply), the fp64 kinds wd * (double)w; the sum adds (double)w * v.
+ *   detection loss:  L_cls = alpha/N_pos sum_pos w_cls[m] (...) + beta/N_neg sum_neg w_cls[m] (...),
+ *                    L_reg = 1/N_pos sum_pos w_reg[m] [sum_k S(...) + iou_weight (1 - IoU)]; N_pos and N_neg stay the
+ *                    unweighted counts; the gradient scale is (wpos * (double)w), (wneg * (double)w), (wreg * (double)w).
+ * A weight of exactly 1.0f gives the bits of the unweighted entry, a power of two scales dhead exactly.  A weight is a
+ * factor, not a mask: 0 * NaN stays NaN, and a zero weight gives a zero gradient of either sign.
+ * A weighted metric of the head loss (bit j of weighted_metrics[o]) is sum w*v / sum w over the elements of output o (over
+ * its cells for CATEGORICAL_ACCURACY).  Every metric of a weighted head entry leaves as the fp64 pair {num, den}; den of an
+ * unweighted metric is the element (cell) count.  The caller pools pairs and divides once (0 when den == 0). */
+typedef struct lisec_sample_weights {
+    int struct_bytes;               /* sizeof(lisec_sample_weights), checked */
+    int per_cell[2];                /* 0: w[o] points at ONE float, the sweep's weight; 1: at M floats, one per cell */
+    const float* w[2];              /* device; [0] class, [1] regression; NULL: that output has weight 1 */
+    unsigned weighted_metrics[2];   /* head loss only: bit j = metric j of output o is weighted */
+} lisec_sample_weights;
+
+/* The argument lists of the unweighted entries with the descriptor behind cfg.  LISEC_EINVAL, with nothing enqueued and
+ * every output untouched: the refusals of the unweighted entry, a NULL descriptor, a struct_bytes of another size, a
+ * per_cell outside {0, 1}, a metric bit at or above n_metrics[o] (any metric bit, for the detection entries).
+ * lisec_head_loss_weighted writes metric_pairs[2 * (n_metrics[0] + n_metrics[1])] = {num0, den0, ...} (device doubles, the
+ * class output's metrics first); lisec_head_loss_weighted_eval ADDS to acc = {total, class, regression, sweeps, num0,
+ * den0, ...} (4 + 2 * metrics doubles, zeroed by the caller): the fp32 losses as doubles, the pairs as they are.  The
+ * detection entries keep the outputs of their twins. */
+int lisec_head_loss_weighted(const lisec_loss_cfg* cfg, const lisec_sample_weights* sw, const float* head,
+                             const float* y_cls, const float* y_reg, long long M, float grad_scale, float* dhead,
+                             float* loss_out, double* metric_pairs, void* workspace, size_t workspace_bytes,
+                             lisec_stream_t stream);
+int lisec_head_loss_weighted_eval(const lisec_loss_cfg* cfg, const lisec_sample_weights* sw, const float* head,
+                                  const float* y_cls, const float* y_reg, long long M, double* acc, void* workspace,
+                                  size_t workspace_bytes, lisec_stream_t stream);
+size_t lisec_head_loss_weighted_workspace_bytes(void);
+int lisec_detection_loss_weighted(const lisec_detection_loss_cfg* cfg, const lisec_sample_weights* sw, const float* head,
+                                  const float* y_cls, const float* y_reg, long long M, float grad_scale, float* dhead,
+                                  float* loss_out, long long* counts_out, void* workspace, size_t workspace_bytes,
+                                  lisec_stream_t stream);
+int lisec_detection_loss_weighted_eval(const lisec_detection_loss_cfg* cfg, const lisec_sample_weights* sw,
+                                       const float* head, const float* y_cls, const float* y_reg, long long M, double* acc,
+                                       void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+size_t lisec_detection_loss_weighted_workspace_bytes(void);        /* = lisec_detection_loss_workspace_bytes() */
+int lisec_detection_iou_loss_weighted(const lisec_detection_iou_loss_cfg* cfg, const lisec_sample_weights* sw,
+                                      const float* head, const float* y_cls, const float* y_reg, long long M,
+                                      float grad_scale, float* dhead, float* loss_out, long long* counts_out,
+                                      void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+int lisec_detection_iou_loss_weighted_eval(const lisec_detection_iou_loss_cfg* cfg, const lisec_sample_weights* sw,
+                                           const float* head, const float* y_cls, const float* y_reg, long long M,
+                                           double* acc, void* workspace, size_t workspace_bytes, lisec_stream_t stream);
+size_t lisec_detection_iou_loss_weighted_workspace_bytes(void);    /* = lisec_detection_loss_workspace_bytes() */
+
 /* Metrics that read the label code of the detection loss (csrc/detection_metrics.hip; ours, not Keras').  Inputs and the
  * meaning of pos / neg / ignored as for lisec_detection_loss.  Every metric is a pair {num, den} of sums over the 2M
  * anchors of a sweep; its value is num/den over whatever sweeps the caller pools (0 when den == 0).  With p = sigmoid(z) in

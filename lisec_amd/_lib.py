@@ -170,6 +170,11 @@ class DetectionIoULossCfg(Structure):          # lisec_detection_iou_loss_cfg
                 ("iou_mode", c_int), ("reserved2", c_int), ("anchors", (c_double * 4) * 2)]
 
 
+class SampleWeights(Structure):                # lisec_sample_weights
+    _fields_ = [("struct_bytes", c_int), ("per_cell", c_int * 2), ("w", ctypes.c_void_p * 2),
+                ("weighted_metrics", ctypes.c_uint * 2)]
+
+
 DET_MAX_METRICS = 8                            # LISEC_DET_MAX_METRICS
 
 
@@ -395,6 +400,18 @@ def _declare(lib):
     lib.lisec_detection_iou_loss_eval.argtypes = [POINTER(DetectionIoULossCfg), P, P, P, LL, P, P, c_size_t, P]
     lib.lisec_detection_iou_loss_workspace_bytes.restype = c_size_t
     lib.lisec_detection_iou_loss_workspace_bytes.argtypes = []
+    for name, cfg in (("head_loss", LossCfg), ("detection_loss", DetectionLossCfg),
+                      ("detection_iou_loss", DetectionIoULossCfg)):
+        head = [POINTER(cfg), POINTER(SampleWeights), P, P, P, LL]
+        fn = getattr(lib, f"lisec_{name}_weighted")
+        fn.restype = c_int
+        fn.argtypes = head + [c_float, P, P, P, P, c_size_t, P]
+        fn = getattr(lib, f"lisec_{name}_weighted_eval")
+        fn.restype = c_int
+        fn.argtypes = head + [P, P, c_size_t, P]
+        fn = getattr(lib, f"lisec_{name}_weighted_workspace_bytes")
+        fn.restype = c_size_t
+        fn.argtypes = []
     lib.lisec_detection_metrics.restype = c_int
     lib.lisec_detection_metrics.argtypes = [POINTER(DetectionMetricsCfg), P, P, P, LL, P, c_int, P, c_size_t, P]
     lib.lisec_detection_metrics_workspace_bytes.restype = c_size_t

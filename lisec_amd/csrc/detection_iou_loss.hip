@@ -127,16 +127,22 @@ __device__ double iou_term(const double* r, const double* t, const double* an, i
 }
 
 // dhead == nullptr: values only (the evaluation entry)
+// WEIGHTED (one CellWeights behind parts): the anchor's term and its gradient carry w_reg of the anchor's cell, as in the weighted k_det_loss:
+// (wreg * (double)w) times the derivative, the sum adds (double)w * (1 - IoU).
+template <bool WEIGHTED, typename... W>
 __global__ void __launch_bounds__(kIouThreads)
 k_det_iou(lisec_detection_iou_loss_cfg cfg, const float* __restrict__ head, const float* __restrict__ ycls,
           const float* __restrict__ yreg, long long M, float gscale, const long long* __restrict__ counts,
-          float* __restrict__ dhead, double* __restrict__ parts) {
+          float* __restrict__ dhead, double* __restrict__ parts, W... cw_) {
+    [[maybe_unused]] const CellWeights cw = the_weights(cw_...);
     __shared__ double red[1][kIouThreads / 64];
     const long long cp = counts[0];
     const double npos = cp > 0 ? (double)cp : 1.0;
     const double wreg = (double)gscale * cfg.det.weight[1] / npos;     // k_det_loss's
     const double b = cfg.det.smooth_l1_beta, iw = cfg.iou_weight;
     double sum = 0.0;
+    [[maybe_unused]] SweepWeights sws = {};
+    if constexpr (WEIGHTED) sws = sweep_weights(cw);
     const long long n = M * 2;
     for (long long base = blockIdx.x * (long long)kIouThreads; base < n; base += (long long)gridDim.x * kIouThreads) {
         const long long j = base + threadIdx.x;
@@ -152,12 +158,20 @@ k_det_iou(lisec_detection_iou_loss_cfg cfg, const float* __restrict__ head, cons
             r[k] = head[m * 16 + 2 + 7 * a + k];
             t[k] = (double)yreg[m * 14 + 7 * a + k] - cfg.det.target_offset;
         }
-        sum += iou_term(r, t, an, cfg.iou_mode, dterm);
+        [[maybe_unused]] double w = 1.0;
+        if constexpr (WEIGHTED) {
+            w = (double)cell_weight(cw, sws, 1, m);
+            sum += w * iou_term(r, t, an, cfg.iou_mode, dterm);
+        } else {
+            sum += iou_term(r, t, an, cfg.iou_mode, dterm);
+        }
         if (dhead) {
 #pragma unroll
             for (int k = 0; k < 7; ++k) {
                 const double s = smooth_l1_grad(r[k] - t[k], b), e = iw * dterm[k];
-                dhead[m * 16 + 2 + 7 * a + k] = (float)(wreg * (e != 0.0 ? s + e : s));   // e == 0: k_det_loss's bits
+                // e == 0: k_det_loss's bits
+                if constexpr (WEIGHTED) dhead[m * 16 + 2 + 7 * a + k] = (float)((wreg * w) * (e != 0.0 ? s + e : s));
+                else dhead[m * 16 + 2 + 7 * a + k] = (float)(wreg * (e != 0.0 ? s + e : s));
             }
         }
     }
@@ -189,7 +203,7 @@ int check_iou(const lisec_detection_iou_loss_cfg* cfg, long long M, const void* 
 
 int run_iou(const lisec_detection_iou_loss_cfg& cfg, const float* head, const float* y_cls, const float* y_reg,
             long long M, float grad_scale, float* dhead, float* loss_out, long long* counts_out, double* acc,
-            void* workspace, hipStream_t st) {
+            void* workspace, hipStream_t st, const lisec_sample_weights* sw = nullptr) {
     static_assert(kIouBlocks <= kDetBlocks && kIouThreads * 8 >= kDetThreads,
                   "k_det_iou's workgroup b adds to the partial of k_det_loss's workgroup b");
     Carver ws(workspace);
@@ -197,10 +211,19 @@ int run_iou(const lisec_detection_iou_loss_cfg& cfg, const float* head, const fl
     double* parts = ws.take<double>((size_t)kDetBlocks * kDetVals);
     const int nb = grid_blocks(M * 16, kDetThreads, kDetBlocks);
     LISEC_LAUNCH(k_det_count, dim3(1), dim3(kCountThreads), 0, st, y_cls, M * 2, counts, counts_out);
-    LISEC_LAUNCH(k_det_loss, dim3(nb), dim3(kDetThreads), 0, st, cfg.det, head, y_cls, y_reg, M, grad_scale, counts, dhead,
-                 parts);
-    LISEC_LAUNCH(k_det_iou, dim3(grid_blocks(M * 2, kIouThreads, kIouBlocks)), dim3(kIouThreads), 0, st, cfg, head, y_cls,
-                 y_reg, M, grad_scale, counts, dhead, parts);
+    const int nbi = grid_blocks(M * 2, kIouThreads, kIouBlocks);
+    if (sw) {
+        const CellWeights cw = cell_weights(*sw);
+        LISEC_LAUNCH(k_det_loss<true, CellWeights>, dim3(nb), dim3(kDetThreads), 0, st, cfg.det, head, y_cls, y_reg, M,
+                     grad_scale, counts, dhead, parts, cw);
+        LISEC_LAUNCH(k_det_iou<true, CellWeights>, dim3(nbi), dim3(kIouThreads), 0, st, cfg, head, y_cls, y_reg, M, grad_scale,
+                     counts, dhead, parts, cw);
+    } else {
+        LISEC_LAUNCH(k_det_loss<false>, dim3(nb), dim3(kDetThreads), 0, st, cfg.det, head, y_cls, y_reg, M, grad_scale, counts,
+                     dhead, parts);
+        LISEC_LAUNCH(k_det_iou<false>, dim3(nbi), dim3(kIouThreads), 0, st, cfg, head, y_cls, y_reg, M, grad_scale, counts, dhead,
+                     parts);
+    }
     LISEC_LAUNCH(k_det_finalize, dim3(1), dim3(256), 0, st, cfg.det, parts, nb, counts, loss_out, acc);
     LISEC_LAUNCH_CHECK();
     return LISEC_OK;
@@ -230,4 +253,29 @@ extern "C" int lisec_detection_iou_loss_eval(const lisec_detection_iou_loss_cfg*
     LISEC_CHECK_ARG(head && y_cls && y_reg && acc, "detection IoU loss: NULL pointer");
     return run_iou(*cfg, head, y_cls, y_reg, M, 1.0f, nullptr, nullptr, nullptr, acc, workspace,
                    static_cast<hipStream_t>(stream_));
+}
+
+// The weighted entries: the same four launches with the weighted k_det_loss and k_det_iou, the same workspace.
+extern "C" size_t lisec_detection_iou_loss_weighted_workspace_bytes(void) { return lisec_detection_loss_workspace_bytes(); }
+
+extern "C" int lisec_detection_iou_loss_weighted(const lisec_detection_iou_loss_cfg* cfg, const lisec_sample_weights* sw,
+                                                 const float* head, const float* y_cls, const float* y_reg, long long M,
+                                                 float grad_scale, float* dhead, float* loss_out, long long* counts_out,
+                                                 void* workspace, size_t workspace_bytes, lisec_stream_t stream_) {
+    if (int rc = check_iou(cfg, M, workspace, workspace_bytes)) return rc;
+    if (int rc = check_sample_weights(sw, nullptr)) return rc;
+    LISEC_CHECK_ARG(head && y_cls && y_reg && dhead && loss_out && counts_out, "detection IoU loss: NULL pointer");
+    return run_iou(*cfg, head, y_cls, y_reg, M, grad_scale, dhead, loss_out, counts_out, nullptr, workspace,
+                   static_cast<hipStream_t>(stream_), sw);
+}
+
+extern "C" int lisec_detection_iou_loss_weighted_eval(const lisec_detection_iou_loss_cfg* cfg,
+                                                      const lisec_sample_weights* sw, const float* head,
+                                                      const float* y_cls, const float* y_reg, long long M, double* acc,
+                                                      void* workspace, size_t workspace_bytes, lisec_stream_t stream_) {
+    if (int rc = check_iou(cfg, M, workspace, workspace_bytes)) return rc;
+    if (int rc = check_sample_weights(sw, nullptr)) return rc;
+    LISEC_CHECK_ARG(head && y_cls && y_reg && acc, "detection IoU loss: NULL pointer");
+    return run_iou(*cfg, head, y_cls, y_reg, M, 1.0f, nullptr, nullptr, nullptr, acc, workspace,
+                   static_cast<hipStream_t>(stream_), sw);
 }

@@ -9,6 +9,7 @@
 // address is fixed and nothing is read back: the launches record into a step plan as they are.
 #pragma once
 #include "reduce.h"
+#include "sample_weights.h"
 
 namespace lisec {
 namespace {
@@ -63,10 +64,16 @@ __device__ __forceinline__ double smooth_l1_grad(double d, double b) {
 }
 
 // dhead == nullptr: values only (the evaluation entry)
+// WEIGHTED (one CellWeights behind parts; sample_weights.h): cell m carries the factor w_cls[m] on its two class channels and w_reg[m] on its fourteen
+// regression channels: the gradient scale is (wpos * (double)w), (wneg * (double)w) or (wreg * (double)w) times the
+// derivative, in that order, and the sums add (double)w * v.  The counts stay unweighted.  w == 1.0f gives the bits of the
+// unweighted instantiation, which this template leaves as it was.
+template <bool WEIGHTED, typename... W>
 __global__ void __launch_bounds__(kDetThreads)
 k_det_loss(lisec_detection_loss_cfg cfg, const float* __restrict__ head, const float* __restrict__ ycls,
            const float* __restrict__ yreg, long long M, float gscale, const long long* __restrict__ counts,
-           float* __restrict__ dhead, double* __restrict__ parts) {
+           float* __restrict__ dhead, double* __restrict__ parts, W... cw_) {
+    [[maybe_unused]] const CellWeights cw = the_weights(cw_...);
     __shared__ double red[kDetVals][kDetThreads / 64];
     const int c = threadIdx.x & 15;
     const bool grad = dhead != nullptr;
@@ -77,6 +84,8 @@ k_det_loss(lisec_detection_loss_cfg cfg, const float* __restrict__ head, const f
     const double wreg = gs * cfg.weight[1] / npos;
     const double g = cfg.gamma, b = cfg.smooth_l1_beta;
     double spos = 0.0, sneg = 0.0, sreg = 0.0;
+    [[maybe_unused]] SweepWeights sws = {};
+    if constexpr (WEIGHTED) sws = sweep_weights(cw);
     const long long n = M * 16;
     for (long long base = blockIdx.x * (long long)kDetThreads; base < n; base += (long long)gridDim.x * kDetThreads) {
         const long long i = base + threadIdx.x;
@@ -100,15 +109,27 @@ k_det_loss(lisec_detection_loss_cfg cfg, const float* __restrict__ head, const f
                     v = f * s;
                     dv = f * (g * qx * s + px);
                 }
-                if (pos) spos += v; else sneg += v;
-                if (grad) gout = (float)(pos ? -(wpos * dv) : wneg * dv);        // dx/dz = -1 on a positive
+                if constexpr (WEIGHTED) {
+                    const double w = (double)cell_weight(cw, sws, 0, m);
+                    if (pos) spos += w * v; else sneg += w * v;
+                    if (grad) gout = (float)(pos ? -((wpos * w) * dv) : (wneg * w) * dv);
+                } else {
+                    if (pos) spos += v; else sneg += v;
+                    if (grad) gout = (float)(pos ? -(wpos * dv) : wneg * dv);    // dx/dz = -1 on a positive
+                }
             }
         } else {
             const int a = c < 9 ? 0 : 1;
             if (is_pos(ycls[m * 2 + a])) {
                 const double d = (double)head[i] - ((double)yreg[m * 14 + (c - 2)] - cfg.target_offset);
-                sreg += smooth_l1(d, b);
-                if (grad) gout = (float)(wreg * smooth_l1_grad(d, b));
+                if constexpr (WEIGHTED) {
+                    const double w = (double)cell_weight(cw, sws, 1, m);
+                    sreg += w * smooth_l1(d, b);
+                    if (grad) gout = (float)((wreg * w) * smooth_l1_grad(d, b));
+                } else {
+                    sreg += smooth_l1(d, b);
+                    if (grad) gout = (float)(wreg * smooth_l1_grad(d, b));
+                }
             }
         }
         if (grad) dhead[i] = gout;

@@ -253,7 +253,7 @@ def written_class(optimizer):
     return cls if cls != rec.class_name and optimizer_table.base_class(cls) == rec.class_name else rec.class_name
 
 
-def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrapper=None):
+def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrapper=None, weighted_metrics=None):
     """The training_config attribute.  loss / loss_weights / metrics: compile()'s arguments as given (None: the reference's
     loss=['mse','mse'], no weights, no metrics -- the bytes every earlier version wrote).  optimizer_config holds Keras'
     keys in Keras' order, a key the dict lacks at Keras' default (optimizer_table)."""
@@ -277,7 +277,7 @@ def _training_config(optimizer, loss=None, loss_weights=None, metrics=None, wrap
         oc = {"class_name": wrapper["class_name"], "config": {"name": c.pop("name", wrapper["class_name"]),
                                                               "optimizer": oc, **c}}
     return {"loss": ["mse", "mse"] if loss is None else _serialize_nested(loss), "metrics": _serialize_nested(metrics),
-            "weighted_metrics": None, "loss_weights": _serialize_nested(loss_weights), "optimizer_config": oc}
+            "weighted_metrics": _serialize_nested(weighted_metrics), "loss_weights": _serialize_nested(loss_weights), "optimizer_config": oc}
 
 
 # the slot arguments of save_model and slot keys of load_model: LisecNet's slot names, so Keras' "momentum" is "velocity"
@@ -287,7 +287,8 @@ SLOT_KEYS = optimizer_table.SLOT_NAMES
 
 # ---------------------------------------------------------------------------------------------------
 def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0, loss=None, loss_weights=None,
-               metrics=None, momentum_cache=1.0, regularizers=None, wrapper=None, average=None, **given):
+               metrics=None, momentum_cache=1.0, regularizers=None, wrapper=None, average=None, weighted_metrics=None,
+               **given):
     """params: dict ParamStore name -> array.  optimizer: dict(lr, decay, momentum, nesterov) for SGD,
     dict(class_name="Adam", lr, decay, beta_1, beta_2, epsilon, amsgrad) for Adam (lr: a number, or a learning-rate
     schedule serialized as Keras does, {"class_name", "config"}), or None (a model that was never
@@ -296,7 +297,7 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
     momentum (momentum > 0) and mg (centered) of RMSprop; accumulator of Adagrad; accum_grad and accum_var of Adadelta;
     m and v of Adamax and Nadam.  Other optimizers: dict(class_name=<Keras class>, lr, decay, <their config keys>)
     (Nadam's decay: schedule_decay); momentum_cache: Nadam's scalar.  optimizer_weights is written when every slot the optimizer keeps is given (SGD without momentum keeps none).
-    loss, loss_weights, metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
+    loss, loss_weights, metrics, weighted_metrics: Model.compile's arguments as given, written into training_config as Keras 2.4 does (names
     as they are, loss / metric objects as {"class_name", "config"}); None: loss ['mse','mse'], no weights, no metrics.
     regularizers: {ParamStore name: (l1, l2)} or None, written into the layer configs (model_config).
     wrapper: {"class_name": "MovingAverage" | "SWA", "config": its own keys, without "optimizer"} or None: the
@@ -318,7 +319,7 @@ def save_model(path, params, nx, ny, nz, maxPoints, optimizer=None, iterations=0
         f.attrs["model_config"] = json.dumps(model_config(nx, ny, nz, maxPoints, regularizers)).encode("utf8")
         if optimizer is not None:
             f.attrs["training_config"] = json.dumps(_training_config(optimizer, loss, loss_weights, metrics,
-                                                                     wrapper)).encode("utf8")
+                                                                     wrapper, weighted_metrics)).encode("utf8")
         g = f.create_group("model_weights")
         g.attrs["layer_names"] = [L["name"].encode("utf8") for L in layers]
         g.attrs["backend"] = b"tensorflow"
@@ -465,12 +466,13 @@ def load_model(path, grid=None):
                     params[pname] = vals[w]
                     keras_to_param[f"{lname}/{w}"] = pname
         out = dict(params=params, nx=int(nx), ny=int(ny), nz=int(nz), maxPoints=int(T), iterations=0, optimizer=None,
-                   loss=None, loss_weights=None, metrics=None, momentum_cache=None, regularizers=regs, wrapper=None,
-                   average=None,
+                   loss=None, loss_weights=None, metrics=None, weighted_metrics=None, momentum_cache=None,
+                   regularizers=regs, wrapper=None, average=None,
                    **{k: None for k in SLOT_KEYS})
         if "training_config" in f.attrs:
             tc = json.loads(_text(f.attrs["training_config"]))
-            out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"))
+            out.update(loss=tc.get("loss"), loss_weights=tc.get("loss_weights"), metrics=tc.get("metrics"),
+                       weighted_metrics=tc.get("weighted_metrics"))
             oc = tc.get("optimizer_config", {})
             c = oc.get("config", {})
             if isinstance(c.get("optimizer"), dict):              # a wrapper: the optimizer is the one it nests

@@ -309,20 +309,27 @@ def loss_term(identifier):
 class LossSpec:
     """The loss of a training step as the kernels see it: per output (class, regression) the loss term, its weight and
     up to MAX_METRICS metric terms; hashable, so that it keys recorded step plans.  A term is (kind, from_logits, param,
-    label_smoothing).  metric_names (Keras' "<output>_<name>", class output first) are not part of the key."""
+    label_smoothing).  metric_names (Keras' "<output>_<name>", class output first) are not part of the key.
+    weighted: per output, bit j = metric j is one of compile(weighted_metrics=): under sample weights it is sum w*v / sum w
+    (lisec_sample_weights.weighted_metrics); without them it is the unweighted metric.  Part of the key where any is set."""
 
-    def __init__(self, losses, weights=(1.0, 1.0), metrics=((), ()), metric_names=()):
+    def __init__(self, losses, weights=(1.0, 1.0), metrics=((), ()), metric_names=(), weighted=(0, 0)):
         self.losses = tuple(tuple(t) for t in losses)
         self.weights = tuple(float(w) for w in weights)
         self.metrics = tuple(tuple(tuple(t) for t in m) for m in metrics)
         self.metric_names = tuple(metric_names)
-        if len(self.losses) != 2 or len(self.weights) != 2 or len(self.metrics) != 2:
+        self.weighted = tuple(int(b) for b in weighted)
+        if len(self.losses) != 2 or len(self.weights) != 2 or len(self.metrics) != 2 or len(self.weighted) != 2:
             raise ValueError("a LossSpec has two outputs")
         if any(len(m) > MAX_METRICS for m in self.metrics):
             raise ValueError(f"at most {MAX_METRICS} metrics per output are implemented")
+        if any(b < 0 or b >> len(m) for b, m in zip(self.weighted, self.metrics)):
+            raise ValueError("a weighted-metric bit beyond the metrics of its output")
 
     @property
     def config(self):
+        if any(self.weighted):
+            return (self.losses, self.weights, self.metrics, self.weighted)
         return (self.losses, self.weights, self.metrics)
 
     @property
@@ -519,6 +526,17 @@ def _joint_loss(loss):
 
 
 def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
+    """The step loss of a compile() without weighted metrics: compile_weighted_loss(loss, loss_weights, metrics), whose
+    description is this function's.  weighted_metrics other than None is refused here (NotImplementedError), as it
+    always was: a step compiled through this function knows no sample weights.  Model.compile goes through
+    compile_weighted_loss."""
+    if weighted_metrics is not None:
+        raise NotImplementedError("weighted_metrics is not implemented by compile_loss (a step without sample weights): "
+                                  "compile_weighted_loss, which Model.compile calls, takes them")
+    return compile_weighted_loss(loss, loss_weights, metrics)
+
+
+def compile_weighted_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     """Model.compile's loss arguments -> (step loss, metric names).  The step loss is the plain string 'mse' or
     'smoothl1_ce' -- lisec_rpn_loss, the reference's step unchanged -- when the loss is MSE on both outputs, or the legacy
     'smoothl1_ce' spelling, with neither loss_weights nor metrics; a DetectionLossSpec (lisec_detection_loss) for a
@@ -528,13 +546,16 @@ def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     metric to its own output); with every other loss, the Keras metrics and only those.  Every refusal is raised here:
     ValueError (unknown name, unknown output key, a list of the wrong length, a VoxelNetLoss given per output, a
     detection metric on the wrong output, too many of them), NotImplementedError (a Keras loss or metric the kernels do
-    not implement, one's own callable, loss=None for an output, weighted_metrics, a Keras metric with a VoxelNetLoss, a
-    detection metric without one)."""
+    not implement, one's own callable, loss=None for an output, weighted_metrics with a VoxelNetLoss, a Keras metric with
+    a VoxelNetLoss, a detection metric without one).
+    weighted_metrics takes the Keras metrics in the forms metrics= takes; an output's weighted metrics follow its
+    metrics (Keras' order) under the names "<output>_weighted_<name>", and share the cap of MAX_METRICS per output."""
     from . import metrics as metrics_mod
-    if weighted_metrics is not None:
-        raise NotImplementedError("weighted_metrics is not implemented (there are no sample weights)")
     joint = _joint_loss(loss)
     if joint is not None:
+        if weighted_metrics is not None:
+            raise NotImplementedError("weighted_metrics with the VoxelNet detection loss is not implemented: the detection "
+                                      "metrics stay unweighted")
         mterms, names = metrics_mod.compile_detection_metrics(metrics)
         if isinstance(joint, VoxelNetIoULoss):
             return DetectionIoULossSpec(joint.params(), _weights(loss_weights), mterms, names,
@@ -546,10 +567,10 @@ def compile_loss(loss, loss_weights=None, metrics=None, weighted_metrics=None):
     else:
         terms = tuple(loss_term(get(x)) for x in _per_output(loss, "loss"))
     weights = _weights(loss_weights)
-    mterms, names = metrics_mod.compile_metrics(metrics)
+    mterms, names, weighted = metrics_mod.compile_metrics(metrics, weighted_metrics)
     if loss_weights is None and not any(mterms):
         if legacy is not None:
             return legacy, []
         if terms == LEGACY["mse"]:
             return "mse", []
-    return LossSpec(terms, weights, mterms, names), list(names)
+    return LossSpec(terms, weights, mterms, names, weighted), list(names)

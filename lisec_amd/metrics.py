@@ -262,39 +262,49 @@ def _as_list(x, what):
     return [x]
 
 
-def compile_metrics(metrics):
-    """compile(metrics=...) -> (terms per output, names): a list (every metric on each output), a list of two lists (one
-    per output) or a dict keyed by output name (a metric or a list of them each).  Names are Keras' multi-output
-    "<output>_<name>", in the order: the class output's metrics, then the regression output's."""
+def _metrics_per_output(metrics, what):
+    """[class output's list, regression output's list] of one of compile()'s metric arguments."""
     if metrics is None:
-        per = [[], []]
-    elif isinstance(metrics, dict):
-        per = [_as_list(m, "metrics") for m in _losses._per_output(metrics, "metrics")]
-    elif isinstance(metrics, (list, tuple)):
+        return [[], []]
+    if isinstance(metrics, dict):
+        return [_as_list(m, what) for m in _losses._per_output(metrics, what)]
+    if isinstance(metrics, (list, tuple)):
         nested = [isinstance(m, (list, tuple)) for m in metrics]
         if any(nested):
             if not all(nested) or len(metrics) != 2:
-                raise ValueError("metrics as nested lists need one list per model output (2 outputs), got "
+                raise ValueError(f"{what} as nested lists need one list per model output (2 outputs), got "
                                  f"{list(metrics)!r}")
-            per = [list(m) for m in metrics]
-        else:
-            per = [list(metrics), list(metrics)]
-    else:
-        raise TypeError(f"Type of `metrics` argument not understood. Expected a list or dictionary, found: {metrics!r}")
-    terms, names = [[], []], []
-    for o, ms in enumerate(per):
-        seen = set()
-        for m in ms:
-            t, name = metric_term(get(m))
-            if name in seen:
-                raise ValueError(f"metric name {name!r} appears twice for output {_losses.OUTPUTS[o]}")
-            seen.add(name)
-            terms[o].append(t)
-            names.append(f"{_losses.OUTPUTS[o]}_{name}")
+            return [list(m) for m in metrics]
+        return [list(metrics), list(metrics)]
+    raise TypeError(f"Type of `{what}` argument not understood. Expected a list or dictionary, found: {metrics!r}")
+
+
+def compile_metrics(metrics, weighted_metrics=None):
+    """compile(metrics=..., weighted_metrics=...) -> (terms per output, names, weighted bits per output): each argument a
+    list (every metric on each output), a list of two lists (one per output) or a dict keyed by output name (a metric or
+    a list of them each).  Names are Keras' multi-output "<output>_<name>", in the order: the class output's metrics and
+    behind them its weighted metrics, then the regression output's.  A weighted metric is named
+    "<output>_weighted_<name>" (our choice: a metric in both lists has two keys); bit j of an output's word says that its
+    metric j is a weighted one.  The two lists share the cap of MAX_METRICS per output."""
+    per = _metrics_per_output(metrics, "metrics")
+    wper = _metrics_per_output(weighted_metrics, "weighted_metrics")
+    terms, names, bits = [[], []], [], [0, 0]
+    for o in range(2):
+        for ms, prefix in ((per[o], ""), (wper[o], "weighted_")):
+            seen = set()
+            for m in ms:
+                t, name = metric_term(get(m))
+                if name in seen:
+                    raise ValueError(f"metric name {prefix + name!r} appears twice for output {_losses.OUTPUTS[o]}")
+                seen.add(name)
+                if prefix:
+                    bits[o] |= 1 << len(terms[o])
+                terms[o].append(t)
+                names.append(f"{_losses.OUTPUTS[o]}_{prefix}{name}")
         if len(terms[o]) > _losses.MAX_METRICS:
-            raise ValueError(f"at most {_losses.MAX_METRICS} metrics per output are implemented, "
-                             f"{_losses.OUTPUTS[o]} has {len(terms[o])}")
-    return (tuple(terms[0]), tuple(terms[1])), names
+            raise ValueError(f"at most {_losses.MAX_METRICS} metrics per output are implemented (metrics and "
+                             f"weighted_metrics together), {_losses.OUTPUTS[o]} has {len(terms[o])}")
+    return (tuple(terms[0]), tuple(terms[1])), names, tuple(bits)
 
 
 def _detection_metric(identifier):

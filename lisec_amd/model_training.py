@@ -27,7 +27,7 @@ import torch
 from . import Constants, _lib
 from . import callbacks, losses, lr_schedules, metrics, mixed_precision, ops, optimizer_table, regularizers
 from .network import (AverageSpec, ClipSpec, DecaySpec, EvalStep, LisecNet, OptimizerSpec, PipelinedStep, RecordedStep,
-                      loss_acc_len, loss_acc_logs, loss_acc_split)
+                      loss_acc_len, loss_acc_logs, loss_acc_split, weight_form)
 from .params import ParamStore, fold_depth, param_specs
 from .voxelizer import VoxelSample, Voxelizer, check_subsample, host_row_stats
 
@@ -831,6 +831,97 @@ def _targets(ycls, yreg, rows, dev):
     return lambda i: (upload(ycls[i]), upload(yreg[i]))
 
 
+def _sample_weight_arrays(sample_weight, n, grid, what="sample_weight"):
+    """fit / evaluate's sample_weight -> None, or [w_cls, w_reg], each None (that output has weight 1) or a float32 array
+    of at least n rows: (rows,) -- one weight per sweep -- or (rows, Ho, Wo) -- one per cell of the output grid.  One
+    array serves both outputs, a list or tuple holds one entry per output, a dict is keyed by output name; None entries
+    are allowed.  ValueError: another shape, fewer rows than samples, a value that is not finite, a list of another
+    length, an unknown output name."""
+    if sample_weight is None:
+        return None
+    if isinstance(sample_weight, (dict, list, tuple)):
+        per = losses._per_output(sample_weight, what)
+    else:
+        per = [sample_weight, sample_weight]
+    out = []
+    for name, w in zip(losses.OUTPUTS, per):
+        if w is None:
+            out.append(None)
+            continue
+        try:
+            a = np.asarray(w, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} for {name} is not an array of numbers") from None
+        if a.ndim not in (1, 3) or (a.ndim == 3 and tuple(a.shape[1:]) != tuple(grid)):
+            raise ValueError(f"{what} for {name} must have the shape (n,) or (n, {grid[0]}, {grid[1]}), got {a.shape}")
+        if a.shape[0] < n:
+            raise ValueError(f"{what} for {name} has {a.shape[0]} rows for {n} samples")
+        if not np.isfinite(a[:n]).all():
+            raise ValueError(f"{what} for {name} holds a value that is not finite")
+        out.append(a)
+    return None if all(a is None for a in out) else out
+
+
+def _refuse_empty_sample_weight(sample_weight):
+    """A sample_weight array without a single row weighs no sweep: the weighted losses would be means over nothing and
+    every weighted metric 0/0.  NotImplementedError, raised by evaluate() and fit() in front of everything else they do
+    with their data; None, and None entries, pass."""
+    if sample_weight is None:
+        return
+    if isinstance(sample_weight, dict):
+        entries = list(sample_weight.values())
+    elif isinstance(sample_weight, (list, tuple)):
+        entries = list(sample_weight)
+    else:
+        entries = [sample_weight]
+    for w in entries:
+        if w is not None and np.size(w) == 0:
+            raise NotImplementedError("a sample_weight array without any row is not implemented: pass sample_weight=None "
+                                      "to evaluate or fit without weights")
+
+
+def _weight_form(sw):
+    """network.weight_form of _sample_weight_arrays' result: None, or per output None / 'sweep' / 'cell'."""
+    if sw is None:
+        return None
+    return tuple(None if a is None else ("sweep" if a.ndim == 1 else "cell") for a in sw)
+
+
+def _weights_at(sw, rows, dev):
+    """weight(i) -> the device sample weights of sample i, for the i of `rows` (a range): a pair of float32 tensors,
+    (1,) or (Ho, Wo), or None per output; the arrays live on the device for the whole call (80 KB per Lyft-grid map)."""
+    if sw is None:
+        return None
+    maps = slice(rows.start, rows.stop, rows.step)
+    up = [None if a is None else torch.from_numpy(np.ascontiguousarray(a[maps])).to(dev) for a in sw]
+
+    def weight(i, at=rows.index):
+        k = at(i)
+        return tuple(None if u is None else (u[k:k + 1] if u.dim() == 1 else u[k]) for u in up)
+    return weight
+
+
+def _item_weights(w, grid, dev=None):
+    """The sample weights of ONE sweep, as a Sequence item brings them (its third element): _sample_weight_arrays' forms
+    without the leading axis -- a number or an (Ho, Wo) map per output.  -> None, or a pair of float32 arrays / None of
+    the shapes (1,) and (Ho, Wo) (device tensors with `dev`)."""
+    if w is None:
+        return None
+    if isinstance(w, (dict, list, tuple)):
+        per = losses._per_output(w, "sample_weight")
+    else:
+        per = [w, w]
+    rows = [None if a is None else np.asarray(a, dtype=np.float32)[None] for a in per]
+    rows = [a.reshape(1) if a is not None and a.size == 1 else a for a in rows]
+    sw = _sample_weight_arrays(rows, 1, grid, "a Sequence item's sample_weight")
+    if sw is None:
+        return None
+    out = tuple(None if a is None else np.ascontiguousarray(a[0] if a.ndim == 3 else a[:1]) for a in sw)
+    if dev is None:
+        return out
+    return tuple(None if a is None else torch.from_numpy(a).to(dev) for a in out)
+
+
 def _is_sequence(x):
     """keras.utils.Sequence by its interface; lists, arrays and voxelised sweeps are not."""
     return (not isinstance(x, (list, tuple, np.ndarray)) and all(callable(getattr(x, m, None))
@@ -896,7 +987,11 @@ class Model:
         routing each to the output it belongs to, unlike Keras).  loss_weights: a list
         or dict of floats (default 1): the step minimises w_c*L_c + w_r*L_r, History's `loss`; the per-output losses are
         logged unweighted.  metrics: a list (for each output), a list of two lists or a dict per output name; logged as
-        "<output>_<name>" (see metrics_names).  weighted_metrics: not implemented (there are no sample weights).
+        "<output>_<name>" (see metrics_names).  weighted_metrics: the Keras metrics in the forms metrics= takes, logged
+        behind their output's metrics as "<output>_weighted_<name>": under fit / evaluate(sample_weight=) each is
+        sum w*v / sum w pooled over the epoch's or evaluation's sweeps (0.0 when the weights sum to 0), without sample
+        weights the unweighted metric; the two lists share the cap of 4 per output; with a VoxelNet loss
+        NotImplementedError.
         Every refusal (ValueError, NotImplementedError) is raised here, before any launch."""
         optimizer = optimizers.get(optimizer)
         wd = optimizer.decay_spec()
@@ -908,12 +1003,14 @@ class Model:
             # exclusion lists this network cannot serve are refused here in the same way (ops.lamb_chunks); the tables,
             # the workspace and the ratio buffer get their fixed addresses before any step is recorded
             self.net.lamb_table(*optimizer.spec().lists)
-        step_loss, names = losses.compile_loss(loss, loss_weights, metrics, weighted_metrics)
+        step_loss, names = losses.compile_weighted_loss(loss, loss_weights, metrics, weighted_metrics)
         self.optimizer, self.loss = optimizer, step_loss
         self._metric_names = names
         # the arguments as given, for the training_config of save() (a legacy step records today's ['mse','mse'])
         self._compile_args = None if isinstance(step_loss, str) else dict(loss=loss, loss_weights=loss_weights,
                                                                          metrics=metrics)
+        if self._compile_args is not None and weighted_metrics is not None:
+            self._compile_args["weighted_metrics"] = weighted_metrics
         self.net._prepare_training()
         spec, start = optimizer.spec(), optimizer.record.slot_start
         for name in spec.slots:
@@ -1005,7 +1102,8 @@ class Model:
         return [dense_to_sample(a, self.net.device) for a in arr]
 
     def fit(self, x, y=None, batch_size=1, verbose=1, epochs=1, steps_per_epoch=None, shuffle=True, callbacks=None,
-            validation_split=0.0, validation_data=None, validation_steps=None, validation_freq=1):
+            validation_split=0.0, validation_data=None, validation_steps=None, validation_freq=1, sample_weight=None,
+            class_weight=None):
         """fit(x=trainPoints, y=[outClass, outRegress], batch_size=1, epochs=1, steps_per_epoch=180)
         (model_training.py:299).  batch_size=B (an integer >= 1; anything else is a ValueError before any launch): every
         update is made with the mean gradient of B sweeps, each run at batch 1 -- BatchNormalization statistics and
@@ -1032,15 +1130,34 @@ class Model:
         x may be a keras.utils.Sequence-like object (__len__, __getitem__(i) -> (points (n, >= 3), [y_cls, y_reg]),
         on_epoch_end()), e.g. augment.AugmentedSweeps, with y=None: step st trains on item order[st], made when the step
         stages its sweep, and on_epoch_end() is called after every epoch.  y given with it is a ValueError, as in Keras;
-        validation_split is refused (pass validation_data).  Everything else works as for lists."""
+        validation_split is refused (pass validation_data).  Everything else works as for lists.
+        sample_weight: one array for both outputs, a list of two or a dict by output name (None entries allowed), each
+        (n,) -- a weight per sweep -- or (n, Ho, Wo) -- a weight per cell of the output grid: every sweep's loss is
+        1/(M*C) sum_m w[m] sum_c v(m,c) per output (the divisor stays the element count: Keras' SUM_OVER_BATCH_SIZE at
+        batch 1), for a VoxelNet loss the weighted sums over its positives and negatives with the unweighted counts; the
+        weights are applied inside the loss pass on the device (lisec_*_loss_weighted).  An epoch's `loss` stays the
+        mean of the sweeps' weighted losses and batch_size=B divides by B; metrics= stay unweighted, weighted_metrics= are
+        sum w*v / sum w pooled over the epoch.  An array without any row is NotImplementedError.  validation_split splits the weights with the labels, validation_data
+        may be (x, y, sample_weight), a Sequence item may be (points, [y_cls, y_reg], sample_weight) with a number or an
+        (Ho, Wo) map per output -- every item in the form of item 0 --, and sample_weight= together with a Sequence is a
+        ValueError, as in Keras.  Another shape, fewer rows than samples or a value that is not finite: ValueError before
+        any launch.  class_weight: ValueError unless None (Keras supports it for single-output models only)."""
         B = _check_batch_size(batch_size)        # first of all: nothing of the model or the GPU is touched before it
         _refuse_mixed_training(self.dtype_policy)
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
+        if class_weight is not None:
+            raise ValueError("`class_weight` is only supported for Models with a single output.")
+        _refuse_empty_sample_weight(sample_weight)
+        if validation_data is not None and len(validation_data) > 2:
+            _refuse_empty_sample_weight(validation_data[2])
+        grid = (self.net.Ho, self.net.Wo)
         seq = x if _is_sequence(x) else None
         if seq is not None:
             if y is not None:
                 raise ValueError("`y` argument is not supported when using `keras.utils.Sequence` as input.")
+            if sample_weight is not None:
+                raise ValueError("`sample_weight` argument is not supported when using `keras.utils.Sequence` as input.")
             if validation_split:
                 raise ValueError("`validation_split` is only supported for lists and arrays: pass validation_data")
             samples, ycls, yreg, n = None, None, None, len(seq)
@@ -1053,20 +1170,29 @@ class Model:
             n = len(samples)
             if len(ycls) < n or len(yreg) < n:
                 raise ValueError("fewer label maps than samples")
+        sw = None if seq is not None else _sample_weight_arrays(sample_weight, n, grid)
         val = None
         if validation_data is not None:
-            if len(validation_data) > 2 and validation_data[2] is not None:
-                raise NotImplementedError("validation sample weights are not implemented")
             val_samples = self._as_samples(validation_data[0])
             val_y = validation_data[1]
+            val_w = validation_data[2] if len(validation_data) > 2 else None
         elif validation_split:
             at = _validation_split_at(n, validation_split)
             val_samples, val_y = samples[at:], (ycls[at:n], yreg[at:n])
+            val_w = None if sw is None else [None if a is None else a[at:n] for a in sw]
             samples, n = samples[:at], at
         if validation_data is not None or validation_split:
             vn = len(val_samples) if validation_steps is None else min(len(val_samples), int(validation_steps) * B)
-            val = (val_samples[:vn],) + self._labels(val_y, vn)
+            val = (val_samples[:vn],) + self._labels(val_y, vn) + (_sample_weight_arrays(val_w, vn, grid,
+                                                                                        "validation sample_weight"),)
             _should_validate(0, validation_freq)           # a malformed validation_freq is refused before any step
+        if seq is not None and not hasattr(seq, "staged") and len(seq):
+            # a Sequence of (points, labels, sample_weight) items: item 0 says in which form every item brings its weights
+            first = seq[0]
+            wform = weight_form(_item_weights(first[2], grid, dev=self.net.device) if len(first) > 2 else None)
+        else:
+            wform = _weight_form(sw)
+        weighted = wform is not None
         self.stop_training = False
         idx = list(range(n))
         if self.dp is not None:
@@ -1083,8 +1209,9 @@ class Model:
             cb.set_model(self)
             cb.set_params(dict(verbose=verbose, epochs=epochs, steps=steps))
         target = _targets(ycls, yreg, range(n), dev) if seq is None else None
+        weight = _weights_at(sw, range(n), dev)
         seq_req = self._sequence_request(seq) if seq is not None else None
-        nm = loss_acc_len(self.loss) - 4                    # metric words of the compiled loss (loss_acc_len's layout)
+        nm = loss_acc_len(self.loss, weighted) - 4          # metric words of the compiled loss (loss_acc_len's layout)
         for cb in callbacks:
             cb.on_train_begin()
         for epoch in range(epochs):
@@ -1095,24 +1222,26 @@ class Model:
                 self.net.average                 # started from the variables as they are now, if compile() asked for it
             # the same plan every epoch (a rate from the descriptor is not part of its key); a new rate is copied into
             # the descriptor on this stream, behind the previous epoch's last update
-            captured = self._captured_step(samples, opt, seq_req, batch=B)
+            captured = self._captured_step(samples, opt, seq_req, batch=B, wform=wform)
             self.net._sync_lr(opt)               # (and the coefficient of a decoupled weight decay)
             order = list(np.random.permutation(idx)) if shuffle else list(idx)
             # the running loss stays on the device: reading it back every step would stall the host behind the GPU and
             # expose the time it needs to enqueue the next step; the progress line is refreshed ~20 times per epoch
             tot_dev = torch.zeros(3, dtype=torch.float64, device=dev)
             met_dev = torch.zeros(nm, dtype=torch.float64, device=dev) if nm else None
-            met_step = self.net.step_metrics(self.loss)     # where a step leaves its metric words; None without metrics
+            met_step = self.net.step_metrics(self.loss, weighted)     # where a step leaves its metric words, if any
             every = max(1, steps // 20)
             t0 = time.time()
 
             def sweep(t, points=captured is not None):
                 """What sweep t of the epoch trains on: (points of the sweep for a recorded step, else its voxel sample,
-                y_cls, y_reg).  The batches are consecutive runs of the order, so sweep t is order[t % n]."""
+                y_cls, y_reg, and under sample weights the sweep's).  The batches are consecutive runs of the order, so
+                sweep t is order[t % n]."""
                 i = int(order[t % len(order)])
                 if seq is not None:
-                    return self._sequence_item(seq, i, points)
-                return (samples[i]._keepalive if points else samples[i], *target(i))
+                    return self._sequence_item(seq, i, points, weighted)
+                item = (samples[i]._keepalive if points else samples[i], *target(i))
+                return item + (weight(i),) if weighted else item
 
             penalty = self.net.reg_penalty if self.net.regularized else None
             t = 0                                           # sweeps trained on so far in this epoch
@@ -1126,8 +1255,10 @@ class Model:
                         # call (PipelinedStep: it also voxelises the next sweep, on the second stream)
                         captured.fit_step(sweep, t, sweeps, position=position)
                     else:
-                        self.net.train_micro_step(*sweep(t), position, loss=self.loss, opt=opt,
-                                                  allreduce=self.dp.bucketed() if self.dp is not None else None)
+                        item = sweep(t)
+                        self.net.train_micro_step(*item[:3], position, loss=self.loss, opt=opt,
+                                                  allreduce=self.dp.bucketed() if self.dp is not None else None,
+                                                  weights=item[3] if weighted else None)
                     _add_sweep_logs(tot_dev, self.net.loss_out, b, position in ("single", "last"), penalty)
                     if nm:
                         met_dev += met_step
@@ -1139,7 +1270,7 @@ class Model:
                 print(f" - {time.time() - t0:.1f}s")
             if nm:
                 tot = np.concatenate([tot, met_dev.cpu().numpy()])
-            logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, tot, max(sweeps, 1))))
+            logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, tot, max(sweeps, 1), weighted)))
             if val is not None and _should_validate(epoch, validation_freq):
                 vlogs = self._evaluate(*val, callbacks=callbacks, verbose=0)
                 logs.update({"val_" + key: v for key, v in vlogs.items()})
@@ -1176,21 +1307,33 @@ class Model:
         key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype, mode)
         return key, grid, dtype, int(need), max(1024, -(-int(need) // 4096) * 4096), mode
 
-    def _sequence_item(self, seq, i, recorded):
+    def _sequence_item(self, seq, i, recorded, weighted=None):
         """What a step trains on when x is a Sequence: for a recorded step the item as something that stages itself into
         the step's buffers (AugmentedSweeps.staged) or its (points, y_cls, y_reg); for the Python schedule the voxelised
-        sweep and its targets."""
+        sweep and its targets.  weighted=True: the item is (points, [y_cls, y_reg], sample_weight) and its weights come fourth
+        (_item_weights; a step recorded for another form refuses them); False: an item that brings weights is refused;
+        None: whatever weights it brings are ignored (recalibrate_batch_norm)."""
         if recorded and hasattr(seq, "staged"):
             return seq.staged(i), None, None
-        pts, (y_cls, y_reg) = seq[i]
+        item = seq[i]
+        pts, (y_cls, y_reg) = item[0], item[1]
+        w = ()
+        if weighted:
+            got = _item_weights(item[2] if len(item) > 2 else None, (self.net.Ho, self.net.Wo),
+                                dev=None if recorded else self.net.device)
+            if got is None:
+                raise ValueError(f"item {i} of the Sequence brings no sample_weight, item 0 did")
+            w = (got,)
+        elif weighted is not None and len(item) > 2 and item[2] is not None:
+            raise ValueError(f"item {i} of the Sequence brings a sample_weight, item 0 did not")
         if recorded:
-            return pts, y_cls, y_reg
+            return (pts, y_cls, y_reg) + w
         dev = self.net.device
         draw = {}
         if _sequence_subsample(seq) == "random":       # the draw the recorded step's buffer set is given
             draw = dict(seed=seq.seed, item=i, epoch=seq.epoch)
         vox = VFE_preprocessing(pts, *self._sequence_grid(), **draw).sample
-        return (vox, torch.as_tensor(y_cls, dtype=torch.float32).to(dev), torch.as_tensor(y_reg, dtype=torch.float32).to(dev))
+        return (vox, torch.as_tensor(y_cls, dtype=torch.float32).to(dev), torch.as_tensor(y_reg, dtype=torch.float32).to(dev)) + w
 
     def _plan_request(self, samples):
         """What a recorded plan for these samples takes: (cache key without the optimizer, the one voxel grid, point
@@ -1204,7 +1347,7 @@ class Model:
         key = (grid, dtype, self.loss, id(self.net), torch.cuda.current_stream().cuda_stream, self.net.compute_dtype)
         return key, grid, dtype, need, max(1024, -(-need // 4096) * 4096), "first"     # a little head-room for later calls
 
-    def _captured_step(self, samples, opt, seq_req=None, batch=1):
+    def _captured_step(self, samples, opt, seq_req=None, batch=1, wform=None):
         """The recorded form of the step (lisec_amd.network.RecordedStep: the eager schedule re-issued by
         lisec_step_plan_run, one C call per step), when it applies: one GPU, every sample a voxelised sweep that still
         holds its device points, one grid (data parallel included: the gradient exchange is recorded with the step).
@@ -1217,16 +1360,18 @@ class Model:
         key, grid, dtype, need, capacity, mode = req
         # the full optimizer config: a re-compile with another optimizer records a new plan; the batch size: a fit with
         # another one records its own plans (those of a batch's micro-steps exist for batch_size > 1 only)
-        key += (opt.config, int(batch))
+        # the form of the sample weights per output (none, one per sweep, one per cell): a weighted step records the
+        # weighted loss launches and owns weight buffers; an unweighted one is keyed as it always was
+        key += (opt.config, int(batch)) + (() if wform is None else (wform,))
         step = _reusable(self._captured, key, need)
         if step is None:
             cls = PipelinedStep if _lib.knob("pipeline_voxels", True) else RecordedStep
             step = cls(self.net, Voxelizer(*grid, device=self.net.device, subsample=mode), capacity, dtype=dtype, loss=self.loss,
-                       opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None, batch=batch)
+                       opt=opt, allreduce=self.dp.bucketed() if self.dp is not None else None, batch=batch, wform=wform)
             self._captured = (key, step)
         return step
 
-    def _eval_step(self, samples):
+    def _eval_step(self, samples, wform=None):
         """The recorded evaluation sweep (lisec_amd.network.EvalStep: voxelise + forward(training=False) + eval loss, one
         C call per sweep) when it applies -- as for _captured_step: every sample a voxelised sweep that still holds its
         device points, one grid -- and LISEC_TUNING=eval_plan=1 asks for it.  Otherwise (None) the eager forward evaluates
@@ -1236,6 +1381,7 @@ class Model:
         if req is None:
             return None
         key, grid, dtype, need, capacity, _ = req
+        key += () if wform is None else (wform,)
         step = _reusable(self._eval_captured, key, need)
         if step is None:
             # the training step's voxeliser, whose workspace already holds a training sweep: a validation sweep no
@@ -1245,7 +1391,7 @@ class Model:
                 vox = train[1].vox
             else:
                 vox = Voxelizer(*grid, device=self.net.device)
-            step = EvalStep(self.net, vox, capacity, dtype=dtype, loss=self.loss)
+            step = EvalStep(self.net, vox, capacity, dtype=dtype, loss=self.loss, wform=wform)
             self._eval_captured = (key, step)
         return step
 
@@ -1272,29 +1418,33 @@ class Model:
         equal within rounding on others (kernels that plan per capacity may sum in another order).  Data parallel: every
         rank evaluates its share samples[rank::world] with the rank-mean moving statistics (what save() writes) and all
         ranks return the same values.  Changes no variable, slot or iteration count.  With weight regularizers `loss`
-        includes their penalty P (the per-output losses do not), computed once per evaluation on the device."""
+        includes their penalty P (the per-output losses do not), computed once per evaluation on the device.
+        sample_weight: as for fit() -- the losses are the means over the sweeps of the weighted losses, weighted_metrics=
+        are sum w*v / sum w pooled over the sweeps, metrics= stay unweighted.  A sample_weight array without any row is
+        refused (NotImplementedError) in front of everything else: it weighs no sweep."""
         if self.optimizer is None:
             raise RuntimeError("compile() the model first")
-        if sample_weight is not None:
-            raise NotImplementedError("evaluate(sample_weight=...) is not implemented")
+        _refuse_empty_sample_weight(sample_weight)
         samples = self._as_samples(x)
         n = len(samples)
         if steps is not None:
             n = min(n, int(steps) * (32 if batch_size is None else int(batch_size)))
         ycls, yreg = self._labels(y, n)
+        sw = _sample_weight_arrays(sample_weight, n, (self.net.Ho, self.net.Wo))
         callbacks = list(callbacks or [])
         for cb in callbacks:
             cb.set_model(self)
             cb.set_params(dict(verbose=verbose, epochs=1, steps=steps))
-        logs = self._evaluate(samples[:n], ycls, yreg, callbacks=callbacks, verbose=verbose)
+        logs = self._evaluate(samples[:n], ycls, yreg, sw, callbacks=callbacks, verbose=verbose)
         return dict(logs) if return_dict else [logs[k] for k in self.metrics_names]
 
-    def _evaluate(self, samples, ycls, yreg, callbacks=(), verbose=0):
+    def _evaluate(self, samples, ycls, yreg, sw=None, callbacks=(), verbose=0):
         for cb in callbacks:
             cb.on_test_begin()
         t0 = time.time()
-        sums, count = loss_acc_split(self.loss, self._eval_sums(samples, ycls, yreg))
-        logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, sums, count)))
+        weighted = sw is not None
+        sums, count = loss_acc_split(self.loss, self._eval_sums(samples, ycls, yreg, sw), weighted)
+        logs = dict(zip(self.metrics_names, loss_acc_logs(self.loss, sums, count, weighted)))
         if verbose:
             print(f"{int(count)}/{int(count)} - {time.time() - t0:.1f}s - " +
                   " - ".join(f"{k}: {v:.4f}" for k, v in logs.items()))
@@ -1302,7 +1452,7 @@ class Model:
             cb.on_test_end(logs)
         return logs
 
-    def _eval_sums(self, samples, ycls, yreg):
+    def _eval_sums(self, samples, ycls, yreg, sw=None):
         """The float64 accumulator of loss_acc_len's layout summed over the sweeps, read back once.  Data parallel: rank r takes
         samples[r::world] (every sweep is evaluated once; DataParallel.shard would drop the tail), evaluates with the
         rank-mean BatchNormalization moving statistics (copy, average, evaluate, restore) and the sums are all-reduced."""
@@ -1315,20 +1465,23 @@ class Model:
             self.dp.average_(net.params.state)
             net.state_version += 1                  # the folds of the replica's own statistics are stale
         try:
-            step = self._eval_step([samples[i] for i in idx]) if idx else None
+            weighted = sw is not None
+            step = self._eval_step([samples[i] for i in idx], _weight_form(sw)) if idx else None
             if step is not None:
                 step.reset()
                 acc = step.acc
             else:
-                acc = torch.zeros(loss_acc_len(self.loss), dtype=torch.float64, device=dev)
+                acc = torch.zeros(loss_acc_len(self.loss, weighted), dtype=torch.float64, device=dev)
             if idx:
                 target = _targets(ycls, yreg, idx, dev)
+                weight = _weights_at(sw, idx, dev)
                 for i in idx:
+                    w = weight(i) if weighted else None
                     if step is not None:
-                        step(samples[i]._keepalive, *target(i))
+                        step(samples[i]._keepalive, *target(i), w)
                     else:
                         net.forward(samples[i], training=False)
-                        net.loss_eval(self.loss, *target(i), acc)
+                        net.loss_eval(self.loss, *target(i), acc, w)
             if self.dp is not None:
                 self.dp.sum_(acc)
             # the weight penalty, once per evaluation and enqueued behind the sweeps: every sweep's `loss` includes it
@@ -1336,7 +1489,7 @@ class Model:
             pen = net.penalty()
             out = acc.cpu().numpy().copy()
             if pen is not None:
-                out[0] += loss_acc_split(self.loss, out)[1] * float(pen.item())
+                out[0] += loss_acc_split(self.loss, out, weighted)[1] * float(pen.item())
             return out
         finally:
             if own is not None:
@@ -1479,14 +1632,16 @@ def _deserialize_nested(x, deserialize):
 
 def _compile_saved(m, opt, ck):
     """Compiles a loaded model with the optimizer and the loss, loss_weights and metrics of its training_config."""
-    saved = {k: ck.get(k) for k in ("loss", "loss_weights", "metrics")}
+    saved = {k: ck.get(k) for k in ("loss", "loss_weights", "metrics", "weighted_metrics")}
     try:
         loss = _deserialize_nested(saved["loss"], losses.deserialize) if saved["loss"] is not None else ['mse', 'mse']
         m.compile(optimizer=opt, loss=loss, loss_weights=saved["loss_weights"],
-                  metrics=_deserialize_nested(saved["metrics"], metrics.deserialize))
+                  metrics=_deserialize_nested(saved["metrics"], metrics.deserialize),
+                  weighted_metrics=_deserialize_nested(saved["weighted_metrics"], metrics.deserialize))
     except (ValueError, NotImplementedError, TypeError) as e:
         warnings.warn(f"load_model: could not restore the compiled loss={saved['loss']!r}, "
-                      f"loss_weights={saved['loss_weights']!r}, metrics={saved['metrics']!r} ({e}); "
+                      f"loss_weights={saved['loss_weights']!r}, metrics={saved['metrics']!r}, "
+                      f"weighted_metrics={saved['weighted_metrics']!r} ({e}); "
                       "compiled with loss=['mse', 'mse']", stacklevel=3)
         m.compile(optimizer=opt, loss=['mse', 'mse'])
 

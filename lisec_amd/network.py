@@ -30,36 +30,57 @@ from .vfe import VFEStack
 LEGACY_LOSS_KINDS = {"mse": 0, "smoothl1_ce": 1}        # the `kind` of lisec_rpn_loss / lisec_rpn_loss_eval
 
 
-def loss_acc_len(loss):
+def weight_form(weights):
+    """The form of a step's sample weights, per output: None (no weights at all), or a pair of None (that output has
+    weight 1), 'sweep' (one float) or 'cell' (one per cell of the output grid).  weights: None, or a pair of float32
+    device tensors / None.  The form is part of the key of a recorded plan; the values are device data."""
+    if weights is None:
+        return None
+    return tuple(None if w is None else ("sweep" if w.numel() == 1 else "cell") for w in weights)
+
+
+def _paired(loss, weighted):
+    """Do the metric words of this step loss's accumulator hold {num, den} pairs behind a sweep count in acc[3]?  The
+    detection losses always; a LossSpec where the step is weighted (lisec_head_loss_weighted*)."""
+    return isinstance(loss, DetectionLossSpec) or (weighted and isinstance(loss, LossSpec))
+
+
+def loss_acc_len(loss, weighted=False):
     """Length of the evaluation accumulator of a step loss; KeyError for a string that names no legacy loss.  The layout:
         legacy string      [total, class, regression, sweeps]
         LossSpec           [total, class, regression, metrics..., sweeps]     (per-sweep values, summed)
         DetectionLossSpec  [total, class, regression, sweeps, num0, den0, num1, den1, ...]
+        weighted LossSpec  the layout of the DetectionLossSpec (lisec_head_loss_weighted_eval)
     A DetectionLossSpec keeps the sweep count in acc[3], where lisec_detection_loss_eval writes it, and appends the
-    {num, den} pairs of its metrics (lisec_detection_metrics with accumulate): sums pooled over the sweeps."""
+    {num, den} pairs of its metrics (lisec_detection_metrics with accumulate): sums pooled over the sweeps.  weighted: the
+    step runs under sample weights; a legacy string then runs as its LossSpec without metrics, whose layout is its own."""
+    if _paired(loss, weighted):
+        return 4 + 2 * loss.n_metrics
     if isinstance(loss, LossSpec):
         return 4 + loss.n_metrics
-    if isinstance(loss, DetectionLossSpec):
-        return 4 + 2 * loss.n_metrics
     LEGACY_LOSS_KINDS[loss]                 # refuses an unknown name
     return 4
 
 
-def loss_acc_logs(loss, sums, count):
+def pair_values(pairs):
+    """[num0, den0, num1, den1, ...] -> [num/den, ...]; 0.0 where den == 0 (Keras' div_no_nan)."""
+    return [float(n / d) if d != 0 else 0.0 for n, d in zip(pairs[0::2], pairs[1::2])]
+
+
+def loss_acc_logs(loss, sums, count, weighted=False):
     """[total, class, regression, metrics...] in the order of Model.metrics_names from sums, laid out as [total, class,
-    regression, the metric words of loss_acc_len's layout...] (numpy float64), over `count` sweeps: the losses and a
-    LossSpec's metrics are means over the sweeps (NaN without any); a DetectionLossSpec's metrics are num/den of the
-    pooled pairs, 0.0 when den == 0 (Keras' div_no_nan)."""
+    regression, the metric words of loss_acc_len's layout...] (numpy float64), over `count` sweeps: the losses and an
+    unweighted LossSpec's metrics are means over the sweeps (NaN without any); metrics kept as pairs (a
+    DetectionLossSpec's, a weighted LossSpec's) are num/den of the pooled pairs, 0.0 when den == 0 (Keras' div_no_nan)."""
     mean = [float(v / count) if count else float("nan") for v in sums[:3]]
-    if isinstance(loss, DetectionLossSpec):
-        pairs = sums[3:3 + 2 * loss.n_metrics]
-        return mean + [float(n / d) if d != 0 else 0.0 for n, d in zip(pairs[0::2], pairs[1::2])]
+    if _paired(loss, weighted):
+        return mean + pair_values(sums[3:3 + 2 * loss.n_metrics])
     return mean + [float(v / count) if count else float("nan") for v in sums[3:]]
 
 
-def loss_acc_split(loss, acc):
+def loss_acc_split(loss, acc, weighted=False):
     """An evaluation accumulator (numpy, loss_acc_len's layout) -> (sums as loss_acc_logs takes them, sweeps)."""
-    if isinstance(loss, DetectionLossSpec):
+    if _paired(loss, weighted):
         return np.concatenate([acc[:3], acc[4:]]), acc[3]
     return acc[:-1], acc[-1]
 
@@ -1396,13 +1417,14 @@ class LisecNet:
                                           out=self.packed_wu_t[c.name])
         self._packed_t_version = (self.params_version, self.params.version)
 
-    def backward(self, y_cls, y_reg, loss="mse", grad_scale=1.0, rpn_grads_ready=None, side_filler=None):
+    def backward(self, y_cls, y_reg, loss="mse", grad_scale=1.0, rpn_grads_ready=None, side_filler=None, weights=None):
         """y_cls (Ho,Wo,2), y_reg (Ho,Wo,14): float32 device tensors.  Fills self.grad (layout of theta)
         and self.loss_out = [total, class, regression].  Must follow forward(training=True).
         loss: 'mse' (loss=['mse','mse'], the reference's) or 'smoothl1_ce' -- lisec_rpn_loss -- or a LossSpec (Keras losses,
         loss_weights and metrics: lisec_head_loss, which also fills self.metric_out[:loss.n_metrics]) or a
         DetectionLossSpec (the VoxelNet detection loss: lisec_detection_loss, which also fills self.loss_counts; its
         metrics: lisec_detection_metrics, into self.metric_pairs[:2 * loss.n_metrics]).
+        weights: the sample weights of the sweep (see _loss_backward); None: the unweighted launches.
         side_filler: optional callable issued on the second stream behind the head-phase leaves, where that stream has
         nothing to do for ~200 us (the weight gradients of the last RPN block wait for its chain): independent work such as
         the NEXT sweep's voxelisation (PipelinedStep).
@@ -1411,7 +1433,7 @@ class LisecNet:
         middle layers and the VFE are still being differentiated: data parallelism starts its all-reduce there."""
         prev_pin = _lib.pin_stream(torch.cuda.current_stream().cuda_stream)
         try:
-            return self._backward(y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler)
+            return self._backward(y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler, weights)
         finally:
             _lib.pin_stream(prev_pin)
 
@@ -1428,25 +1450,47 @@ class LisecNet:
             self._loss_descs[key] = spec.metrics_descriptor()
         return self._loss_descs[key]
 
-    def step_metrics(self, loss):
+    def step_metrics(self, loss, weighted=False):
         """What the last training step left of the metrics of its loss, as the words fit() sums over an epoch (the metric
-        words of loss_acc_len's layout): a LossSpec's fp32 values in metric_out, a DetectionLossSpec's fp64 pairs in
-        metric_pairs; None without metrics."""
+        words of loss_acc_len's layout): a LossSpec's fp32 values in metric_out, a DetectionLossSpec's fp64 pairs -- and
+        those of a LossSpec whose step ran under sample weights -- in metric_pairs; None without metrics."""
+        if _paired(loss, weighted) and loss.n_metrics:
+            return self.metric_pairs[:2 * loss.n_metrics]
         if isinstance(loss, LossSpec) and loss.n_metrics:
             return self.metric_out[:loss.n_metrics]
-        if isinstance(loss, DetectionLossSpec) and loss.n_metrics:
-            return self.metric_pairs[:2 * loss.n_metrics]
         return None
 
-    def _loss_backward(self, loss, y_cls, y_reg, grad_scale):
+    def _sample_weights(self, loss, weights):
+        """The lisec_sample_weights of a weighted step: the weight tensors of both outputs (float32, device, one element
+        or Ho*Wo; None: weight 1) and the weighted-metric bits of a LossSpec.  It holds their addresses."""
+        bits = loss.weighted if isinstance(loss, LossSpec) else (0, 0)
+        return ops.sample_weights(weights[0], weights[1], self.Ho * self.Wo, weighted_metrics=bits)
+
+    def _loss_backward(self, loss, y_cls, y_reg, grad_scale, weights=None):
         """The loss of the head map against the targets into loss_out (a LossSpec: and its metrics into metric_out), its
         gradient into dact["head"].  A step loss is a legacy string (lisec_rpn_loss*), a LossSpec (lisec_head_loss*) or a
         DetectionLossSpec (lisec_detection_loss*, or lisec_detection_iou_loss* for the DetectionIoULossSpec among them; its
         counts into loss_counts, and lisec_detection_metrics, its metric pairs into metric_pairs): this, loss_eval(),
         step_metrics() and loss_acc_len() with its two readers (loss_acc_logs,
-        loss_acc_split) are the only code that tells them apart."""
+        loss_acc_split) are the only code that tells them apart.
+        weights: None -- the launches above, as they always were -- or the sample weights of the sweep as a pair of float32
+        device tensors / None (weight_form): the weighted entry of the same family, a legacy string as the LossSpec of its
+        two terms (at unit weights its gradient is lisec_rpn_loss's, bit for bit); the metrics of a LossSpec then leave as
+        pairs in metric_pairs, and the detection metrics stay unweighted."""
         head, dhead, M = self.act["head"], self.dact["head"], self.Ho * self.Wo
-        if isinstance(loss, LossSpec):
+        if weights is not None:
+            if not isinstance(loss, (LossSpec, DetectionLossSpec)):
+                loss = self._legacy_spec(loss)
+            sw = self._sample_weights(loss, weights)
+            if isinstance(loss, LossSpec):
+                ops.head_loss_weighted(self._loss_descriptor(loss), sw, head, y_cls, y_reg, M, dhead, self.loss_out,
+                                       self.metric_pairs, grad_scale=grad_scale)
+            else:
+                ops.detection_loss_weighted(self._loss_descriptor(loss), sw, head, y_cls, y_reg, M, dhead, self.loss_out,
+                                            self.loss_counts, grad_scale=grad_scale)
+                if loss.n_metrics:
+                    ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, self.metric_pairs)
+        elif isinstance(loss, LossSpec):
             ops.head_loss(self._loss_descriptor(loss), head, y_cls, y_reg, M, dhead, self.loss_out, self.metric_out,
                           grad_scale=grad_scale)
         elif isinstance(loss, DetectionLossSpec):
@@ -1458,11 +1502,28 @@ class LisecNet:
         else:
             ops.rpn_loss(head, y_cls, y_reg, M, LEGACY_LOSS_KINDS[loss], dhead, self.loss_out, grad_scale=grad_scale)
 
-    def loss_eval(self, loss, y_cls, y_reg, acc):
+    def _legacy_spec(self, name):
+        """The LossSpec a legacy string loss runs as under sample weights: its two terms, unit loss weights, no metrics."""
+        from .losses import LEGACY
+        LEGACY_LOSS_KINDS[name]
+        return LossSpec(LEGACY[name])
+
+    def loss_eval(self, loss, y_cls, y_reg, acc, weights=None):
         """Adds the loss (and the metrics of a LossSpec or DetectionLossSpec) of the head map against the targets to acc
-        (float64, device, loss_acc_len(loss) long, in the layout stated there) and counts the sweep in it."""
+        (float64, device, loss_acc_len(loss, weights is not None) long, in the layout stated there) and counts the sweep
+        in it.  weights: as for _loss_backward."""
         head, M = self.act["head"], self.Ho * self.Wo
-        if isinstance(loss, LossSpec):
+        if weights is not None:
+            if not isinstance(loss, (LossSpec, DetectionLossSpec)):
+                loss = self._legacy_spec(loss)
+            sw = self._sample_weights(loss, weights)
+            if isinstance(loss, LossSpec):
+                ops.head_loss_weighted_eval(self._loss_descriptor(loss), sw, head, y_cls, y_reg, M, acc)
+            else:
+                ops.detection_loss_weighted_eval(self._loss_descriptor(loss), sw, head, y_cls, y_reg, M, acc)
+                if loss.n_metrics:
+                    ops.detection_metrics(self._metrics_descriptor(loss), head, y_cls, y_reg, M, acc[4:], accumulate=True)
+        elif isinstance(loss, LossSpec):
             ops.head_loss_eval(self._loss_descriptor(loss), head, y_cls, y_reg, M, acc)
         elif isinstance(loss, DetectionLossSpec):
             run = ops.detection_iou_loss_eval if isinstance(loss, DetectionIoULossSpec) else ops.detection_loss_eval
@@ -1506,7 +1567,7 @@ class LisecNet:
             self.dout_rows = torch.empty((sample.cap + 1, 64), dtype=torch.float32, device=self.device)
             _lib.bump_alloc_generation()           # recorded step plans hold the old addresses
 
-    def _backward(self, y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler=None):
+    def _backward(self, y_cls, y_reg, loss, grad_scale, rpn_grads_ready, side_filler=None, weights=None):
         """The driver of the backward schedule: the loss, then the layers last to first (_BackwardPass), the leaves of
         the graph beside the chain on the second stream (_SideQueue)."""
         self._prepare_training()
@@ -1517,7 +1578,7 @@ class LisecNet:
         q.begin(torch.cuda.current_stream())
         bp = _BackwardPass(self, q, sample, rpn_grads_ready, side_filler)
         self._mark("bwd:start")
-        self._loss_backward(loss, y_cls, y_reg, grad_scale)
+        self._loss_backward(loss, y_cls, y_reg, grad_scale, weights)
         bp.heads()
         bp.early_branches()
         step = {"deconv": bp.deconv, "conv": bp.conv, "mid": bp.mid}
@@ -1942,7 +2003,8 @@ class LisecNet:
     def _accumulate(self, lo, hi, mode):
         ops.grad_accumulate(self.grad[lo:hi], self._acc[lo:hi], mode, self._acc_scale)
 
-    def train_micro_step(self, sample, y_cls, y_reg, position, loss="mse", allreduce=None, opt=None, side_filler=None):
+    def train_micro_step(self, sample, y_cls, y_reg, position, loss="mse", allreduce=None, opt=None, side_filler=None,
+                         weights=None):
         """Sweep `position` ('first', 'middle' or 'last'; 'single': train_step, a batch of one) of a mini-batch whose
         divisor set_batch_divisor() wrote: the forward (batch statistics of THIS sweep; the moving statistics move once
         per sweep, in order) and the backward of train_step, unchanged, then
@@ -1958,7 +2020,8 @@ class LisecNet:
         or the term the last regularised update stored, which the penalty pass of this batch's update REPLACES (it
         stores into LISEC_REG_GRAD_IS_ZERO chunks), so a regularised bias gets its term once per update."""
         if position == "single":
-            return self.train_step(sample, y_cls, y_reg, loss=loss, allreduce=allreduce, opt=opt, side_filler=side_filler)
+            return self.train_step(sample, y_cls, y_reg, loss=loss, allreduce=allreduce, opt=opt, side_filler=side_filler,
+                                   weights=weights)
         if position not in self._ACC_MODE:
             raise ValueError(f"position must be one of {self.BATCH_POSITIONS}, not {position!r}")
         self._batch_buffers()
@@ -1979,7 +2042,7 @@ class LisecNet:
                 self.early_update(lo, hi, opt=opt)
 
         self.forward(sample, training=True)
-        self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, rpn_grads_ready=tail)
+        self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, rpn_grads_ready=tail, weights=weights)
         self._accumulate(0, head[0], mode)
         if last:
             if bucketed:
@@ -1994,7 +2057,7 @@ class LisecNet:
         """The positions of the b sweeps of one batch, in order."""
         return ["single"] if b == 1 else ["first"] + ["middle"] * (b - 2) + ["last"]
 
-    def train_batch(self, samples, y_cls, y_reg, loss="mse", allreduce=None, opt=None):
+    def train_batch(self, samples, y_cls, y_reg, loss="mse", allreduce=None, opt=None, weights=None):
         """One update on the mean gradient of len(samples) sweeps (eager): y_cls[i], y_reg[i] are the targets of
         samples[i].  Returns [total, class, regression] of the batch as a float64 device tensor: the mean of the sweeps'
         losses, the total plus the weight penalty P once.  net.loss_out holds the last sweep's."""
@@ -2004,33 +2067,36 @@ class LisecNet:
         if b > 1:
             self.set_batch_divisor(b)
         tot = torch.zeros(3, dtype=torch.float64, device=self.device)
-        for s_, yc, yr, pos in zip(samples, y_cls, y_reg, self.batch_positions(b)):
-            tot += self.train_micro_step(s_, yc, yr, pos, loss=loss, allreduce=allreduce, opt=opt)
+        for k, (s_, yc, yr, pos) in enumerate(zip(samples, y_cls, y_reg, self.batch_positions(b))):
+            tot += self.train_micro_step(s_, yc, yr, pos, loss=loss, allreduce=allreduce, opt=opt,
+                                         weights=None if weights is None else weights[k])
         if self.regularized and b > 1:
             tot[0] += (b - 1) * self.reg_penalty[0]     # the last sweep's total holds P once; the mean keeps it whole
         return tot / b
 
-    def train_step(self, sample, y_cls, y_reg, loss="mse", allreduce=None, opt=None, side_filler=None):
+    def train_step(self, sample, y_cls, y_reg, loss="mse", allreduce=None, opt=None, side_filler=None, weights=None):
         """One fit() step at batch_size=1: forward (batch statistics) + backward + the update by `opt` (an OptimizerSpec;
         None: the reference's SGD-Nesterov).  side_filler: see backward().
         allreduce: optional data-parallel gradient average -- with start_tail (parallel._BucketedAverage) in two buckets,
         otherwise a callable(grad) run after the backward pass.
         opt.average (an AverageSpec): one averaging pass over theta follows the update, on the second stream behind the
-        repacks (apply_gradients); the update itself is untouched."""
+        repacks (apply_gradients); the update itself is untouched.
+        weights: the sample weights of the sweep, a pair of float32 device tensors / None (one element: the sweep's
+        weight; Ho*Wo: one per cell); None: the unweighted step."""
         if opt is not None and opt.average is not None:
             self.average                           # made before the first launch of a step that averages
         self.forward(sample, training=True)
         if allreduce is not None and hasattr(allreduce, "start_tail"):
             # two buckets: the RPN + head gradients (the tail of theta) are reduced under the rest of the backward
-            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler,
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, weights=weights,
                           rpn_grads_ready=lambda lo, hi: allreduce.start_tail(self.grad, lo, hi))
             allreduce.finish(self.grad)
         elif allreduce is not None:
-            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler)
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, weights=weights)
             allreduce(self.grad)
         else:
             # one rank: the RPN + head variables are updated under the rest of the backward
-            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler,
+            self.backward(y_cls, y_reg, loss=loss, side_filler=side_filler, weights=weights,
                           rpn_grads_ready=lambda lo, hi: self.early_update(lo, hi, opt=opt))
         self.apply_gradients(opt=opt)
         return self.loss_out
@@ -2047,7 +2113,7 @@ class _StepPlans:
 
     PAD = 1.0e6          # metres: floor(1e6 / 0.5) is far beyond maxVoxelX, the point is dropped like any other outlier
 
-    def __init__(self, net, voxelizer, capacity, nbuf, dtype, loss):
+    def __init__(self, net, voxelizer, capacity, nbuf, dtype, loss, wform=None):
         self.net, self.vox, self.capacity, self.loss = net, voxelizer, int(capacity), loss
         self.lib = _lib.load()
         self.plans, self.launches, self.alloc_gen = [], 0, None
@@ -2055,6 +2121,14 @@ class _StepPlans:
         self.points = [torch.full((self.capacity, 3), self.PAD, dtype=dtype, device=dev) for _ in range(nbuf)]
         self.ycls = [torch.zeros((net.Ho, net.Wo, 2), dtype=torch.float32, device=dev) for _ in range(nbuf)]
         self.yreg = [torch.zeros((net.Ho, net.Wo, 14), dtype=torch.float32, device=dev) for _ in range(nbuf)]
+        # a weighted plan (wform: weight_form's pair): per buffer set one weight buffer per weighted output, (1,) for
+        # the sweep's weight or (Ho, Wo) for the map, which the recorded weighted loss launches read when they run
+        self.wform = wform
+        self.weights = None
+        if wform is not None:
+            shape = {"sweep": (1,), "cell": (net.Ho, net.Wo)}
+            self.weights = [tuple(None if f is None else torch.ones(shape[f], dtype=torch.float32, device=dev)
+                                  for f in wform) for _ in range(nbuf)]
         self.stream_handle = torch.cuda.current_stream().cuda_stream
 
     def _record(self, enqueue):
@@ -2085,10 +2159,12 @@ class _StepPlans:
                 "reallocated (an eager call on a larger sweep or grid): replaying it would write through freed "
                 "addresses.  Record a new one (Model.fit and Model.evaluate do so by themselves).")
 
-    def _load(self, j, points, ycls, yreg):
+    def _load(self, j, points, ycls, yreg, weights=None):
         """Stages one sweep into buffer set j: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets
-        (Ho,Wo,2|14) -- or `points` an object with stage_into(points, y_cls, y_reg) -> n that fills the buffers itself."""
+        (Ho,Wo,2|14) -- or `points` an object with stage_into(points, y_cls, y_reg) -> n that fills the buffers itself.
+        weights: the sweep's sample weights in the form the plan was recorded for (weight_form); ValueError otherwise."""
         self._check_stream()
+        self._load_weights(j, weights)
         stage = getattr(points, "stage_into", None)
         if stage is not None:
             # an item of a Sequence that makes its sweep on the device (augment.AugmentedSweeps): its kernels write the
@@ -2112,6 +2188,17 @@ class _StepPlans:
             self.points[j][n:].fill_(self.PAD)
         self.ycls[j].copy_(torch.as_tensor(ycls).reshape(self.ycls[j].shape), non_blocking=True)
         self.yreg[j].copy_(torch.as_tensor(yreg).reshape(self.yreg[j].shape), non_blocking=True)
+
+    def _load_weights(self, j, weights):
+        got = None if weights is None else tuple(None if w is None else ("sweep" if torch.as_tensor(w).numel() == 1
+                                                                         else "cell") for w in weights)
+        if got != self.wform:
+            raise ValueError(f"this {type(self).__name__} was recorded for sample weights of the form {self.wform}, the "
+                             f"sweep brings {got}")
+        if weights is not None:
+            for buf, w in zip(self.weights[j], weights):
+                if buf is not None:
+                    buf.copy_(torch.as_tensor(w, dtype=torch.float32).reshape(buf.shape), non_blocking=True)
 
     def close(self):
         if self.plans:
@@ -2141,9 +2228,9 @@ class _TrainingPlans(_StepPlans):
     one is the batch-1 plan)."""
 
     def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", warmup=2, allreduce=None, opt=None,
-                 batch=1):
+                 batch=1, wform=None):
         nbuf = self.NBUF                         # the number of buffer sets, and of batch-1 plans
-        super().__init__(net, voxelizer, capacity, nbuf, dtype, loss)
+        super().__init__(net, voxelizer, capacity, nbuf, dtype, loss, wform)
         # data parallel: the two-bucket gradient exchange (parallel._BucketedAverage) is part of the recorded schedule --
         # lisec_allreduce_grads and its event edges record themselves, a torch.distributed exchange rides as host calls.
         # Every rank records and replays the same sequence (the warm-up and recording steps exchange gradients for real).
@@ -2227,7 +2314,8 @@ class _TrainingPlans(_StepPlans):
     def _enqueue(self, j, position="single"):
         """One eager step on buffer set j (warm-up, or recorded while it runs)."""
         self.net.train_micro_step(self.samples[j], self.ycls[j], self.yreg[j], position, loss=self.loss,
-                                  allreduce=self.allreduce, opt=self.opt, side_filler=self._voxelise(j))
+                                  allreduce=self.allreduce, opt=self.opt, side_filler=self._voxelise(j),
+                                  weights=None if self.weights is None else self.weights[j])
 
     def _run(self, position="single"):
         """Replays the plan of the current buffer set (position: of the micro-step of a batch, see LisecNet.
@@ -2285,16 +2373,17 @@ class RecordedStep(_TrainingPlans):
         self.vox(self.points[0], out=self.samples[0])       # at the head of the step
         return None
 
-    def load(self, points, ycls, yreg):
-        """Stage one sweep: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets (Ho,Wo,2|14)."""
-        self._load(0, points, ycls, yreg)
+    def load(self, points, ycls, yreg, weights=None):
+        """Stage one sweep: points (n <= capacity, >= 3 columns; device or host tensor / numpy), targets (Ho,Wo,2|14),
+        and the sample weights of a weighted plan."""
+        self._load(0, points, ycls, yreg, weights)
 
     def replay(self, position="single"):
         """Runs the recorded step on what load() staged; returns net.loss_out (device, [total, class, regression])."""
         return self._run(position)
 
-    def __call__(self, points, ycls, yreg, position="single"):
-        self.load(points, ycls, yreg)
+    def __call__(self, points, ycls, yreg, weights=None, position="single"):
+        self.load(points, ycls, yreg, weights)
         return self.replay(position)
 
     def fit_step(self, sweep, st, steps, position="single"):
@@ -2321,19 +2410,19 @@ class PipelinedStep(_TrainingPlans):
         # the sweep of this step was voxelised by the step before; this one voxelises the next under its backward pass
         return lambda: self.vox(self.points[1 - j], out=self.samples[1 - j])
 
-    def prime(self, points, ycls, yreg):
+    def prime(self, points, ycls, yreg, weights=None):
         """Stages the FIRST sweep and voxelises it (outside the plans); the next step() trains on it."""
-        self._load(self.cur, points, ycls, yreg)
+        self._load(self.cur, points, ycls, yreg, weights)
         self.vox(self.points[self.cur], out=self.samples[self.cur])
 
-    def stage_next(self, points, ycls, yreg):
+    def stage_next(self, points, ycls, yreg, weights=None):
         """Stages the sweep the next step() voxelises (and the step() after it trains on)."""
-        self._load(1 - self.cur, points, ycls, yreg)
+        self._load(1 - self.cur, points, ycls, yreg, weights)
 
-    def step(self, next_points=None, next_ycls=None, next_yreg=None, position="single"):
+    def step(self, next_points=None, next_ycls=None, next_yreg=None, next_weights=None, position="single"):
         """Trains on the current sweep and voxelises the staged next one; returns net.loss_out (device)."""
         if next_points is not None:
-            self._load(1 - self.cur, next_points, next_ycls, next_yreg)
+            self._load(1 - self.cur, next_points, next_ycls, next_yreg, next_weights)
         return self._run(position)
 
     def fit_step(self, sweep, st, steps, position="single"):
@@ -2369,9 +2458,9 @@ class EvalStep(_StepPlans):
 
     Record and replay on ONE torch stream (the current stream at construction)."""
 
-    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse"):
-        self.nacc = loss_acc_len(loss)            # refuses an unknown loss before anything is allocated
-        super().__init__(net, voxelizer, capacity, 1, dtype, loss)
+    def __init__(self, net, voxelizer, capacity, dtype=torch.float32, loss="mse", wform=None):
+        self.nacc = loss_acc_len(loss, wform is not None)    # refuses an unknown loss before anything is allocated
+        super().__init__(net, voxelizer, capacity, 1, dtype, loss, wform)
         dev = net.device
         self.acc = torch.zeros(self.nacc, dtype=torch.float64, device=dev)
         self._ready = None                        # the (params_version, state_version, params.version) prepare() served
@@ -2393,7 +2482,7 @@ class EvalStep(_StepPlans):
             net.forward(self.sample, training=False)
         finally:
             net._pack_pending, net._late_pending = pending
-        net.loss_eval(self.loss, self.ycls[0], self.yreg[0], acc)
+        net.loss_eval(self.loss, self.ycls[0], self.yreg[0], acc, None if self.weights is None else self.weights[0])
 
     def prepare(self):
         """Packed kernels and BatchNormalization folds current for the weights and statistics of now (see the class)."""
@@ -2418,11 +2507,11 @@ class EvalStep(_StepPlans):
         """Zeroes the accumulator (stream-ordered)."""
         self.acc.zero_()
 
-    def __call__(self, points, ycls, yreg):
-        """Stages one sweep (points: n <= capacity rows, >= 3 columns; targets (Ho,Wo,2|14)) and replays the plan: its
-        loss is added to self.acc."""
+    def __call__(self, points, ycls, yreg, weights=None):
+        """Stages one sweep (points: n <= capacity rows, >= 3 columns; targets (Ho,Wo,2|14); the sample weights of a
+        weighted plan) and replays the plan: its loss is added to self.acc."""
         self._check_fresh()
-        self._load(0, points, ycls, yreg)
+        self._load(0, points, ycls, yreg, weights)
         self.prepare()
         _lib.check(self.lib.lisec_step_plan_run(self.plans[0]))
         self.sample._host_info = None

@@ -496,6 +496,66 @@ def detection_iou_loss_eval(cfg, head, y_cls, y_reg, M, acc):
                                                          _lib.current_stream()))
 
 
+def sample_weights(w_cls, w_reg, M, weighted_metrics=(0, 0), per_cell=None):
+    """The lisec_sample_weights (an _lib.SampleWeights) of one weight tensor per output (float32, device; None: that
+    output has weight 1): one element is the sweep's weight, more are the map over the M cells.  per_cell overrides the
+    form read from the sizes (a value outside {0, 1} is the library's to refuse).  The descriptor holds addresses: the caller keeps the tensors alive, and a recorded plan
+    reads whatever they hold when it is replayed.  weighted_metrics: per output, bit j = metric j is weighted."""
+    sw = _lib.SampleWeights()
+    sw.struct_bytes = ctypes.sizeof(_lib.SampleWeights)
+    for o, w in enumerate((w_cls, w_reg)):
+        if w is not None:
+            assert w.dtype == torch.float32 and w.is_contiguous()
+        sw.per_cell[o] = int(per_cell[o]) if per_cell is not None else int(w is not None and w.numel() > 1)
+        if w is not None and sw.per_cell[o] == 1 and w.numel() < M:
+            raise ValueError(f"a weight map of {w.numel()} cells for a grid of {M}")
+        sw.w[o] = _lib.ptr(w)
+        sw.weighted_metrics[o] = int(weighted_metrics[o])
+    return sw
+
+
+def head_loss_weighted(cfg, sw, head, y_cls, y_reg, M, dhead, loss_out, metric_pairs=None, grad_scale=1.0):
+    """head_loss under the sample weights sw (sample_weights()): dhead, loss_out, and metric_pairs (float64 device tensor)
+    = [num0, den0, num1, den1, ...], one pair per metric of cfg."""
+    ws = _ew_workspace(head.device)
+    assert ws.numel() >= _lib.load().lisec_head_loss_weighted_workspace_bytes()
+    _lib.check(_lib.load().lisec_head_loss_weighted(ctypes.byref(cfg), ctypes.byref(sw), _lib.ptr(head), _lib.ptr(y_cls),
+                                                    _lib.ptr(y_reg), M, grad_scale, _lib.ptr(dhead), _lib.ptr(loss_out),
+                                                    _lib.ptr(metric_pairs), _lib.ptr(ws), ws.numel(),
+                                                    _lib.current_stream()))
+
+
+def head_loss_weighted_eval(cfg, sw, head, y_cls, y_reg, M, acc):
+    """Adds the weighted losses (the fp32 bits head_loss_weighted writes, as doubles) and its metric pairs to acc =
+    [total, class, regression, sweeps, num0, den0, ...] (float64 device tensor) and counts the sweep; no gradient."""
+    ws = _ew_workspace(head.device)
+    assert ws.numel() >= _lib.load().lisec_head_loss_weighted_workspace_bytes()
+    _lib.check(_lib.load().lisec_head_loss_weighted_eval(ctypes.byref(cfg), ctypes.byref(sw), _lib.ptr(head),
+                                                         _lib.ptr(y_cls), _lib.ptr(y_reg), M, _lib.ptr(acc), _lib.ptr(ws),
+                                                         ws.numel(), _lib.current_stream()))
+
+
+def detection_loss_weighted(cfg, sw, head, y_cls, y_reg, M, dhead, loss_out, counts_out, grad_scale=1.0):
+    """detection_loss (an _lib.DetectionLossCfg) or detection_iou_loss (an _lib.DetectionIoULossCfg) under the sample
+    weights sw; the counts stay unweighted."""
+    iou = isinstance(cfg, _lib.DetectionIoULossCfg)
+    run = _lib.load().lisec_detection_iou_loss_weighted if iou else _lib.load().lisec_detection_loss_weighted
+    ws = _detection_workspace(head.device)
+    _lib.check(run(ctypes.byref(cfg), ctypes.byref(sw), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M, grad_scale,
+                   _lib.ptr(dhead), _lib.ptr(loss_out), _lib.ptr(counts_out), _lib.ptr(ws), ws.numel(),
+                   _lib.current_stream()))
+
+
+def detection_loss_weighted_eval(cfg, sw, head, y_cls, y_reg, M, acc):
+    """Adds the [total, class, regression] detection_loss_weighted would write to acc[0:3] and counts the sweep in
+    acc[3]; either descriptor, as there."""
+    iou = isinstance(cfg, _lib.DetectionIoULossCfg)
+    run = _lib.load().lisec_detection_iou_loss_weighted_eval if iou else _lib.load().lisec_detection_loss_weighted_eval
+    ws = _detection_workspace(head.device)
+    _lib.check(run(ctypes.byref(cfg), ctypes.byref(sw), _lib.ptr(head), _lib.ptr(y_cls), _lib.ptr(y_reg), M,
+                   _lib.ptr(acc), _lib.ptr(ws), ws.numel(), _lib.current_stream()))
+
+
 def detection_metrics(cfg, head, y_cls, y_reg, M, out, accumulate=False):
     """The detection metrics of cfg (an _lib.DetectionMetricsCfg, lisec_detection_metrics_cfg) as pairs of sums over the
     sweep's anchors: out (float64 device tensor) = [num0, den0, num1, den1, ...], stored, or added with accumulate."""
